@@ -13,6 +13,12 @@ instances per GPU -> weak scaling), inputs resident in HBM.  K timed steps are b
 synchronise on both sides, the max over ranks is taken, rank 0 prints ONE JSON line.  `value` = transitions of all
 ranks / that time.
 
+A plain run does only what the headline needs: set-up, settling and warm-up launches, the K timed steps, the line
+(`roofline` included: at the default configuration it takes its counters from the committed summary and its kernel times
+from the last timed step, no run of its own).  `--full` adds the legs below -- dense, vi, cpu_baseline (with the
+oracle check of the timed work), sustained, strong -- and the rocprofv3 child passes that measure the counters in the run.
+`--dump-outputs DIR` writes what the timed path left after its last step as DIR/<name>.npy (float64, see dump_outputs).
+
 Objects on the line (prompt section 4; DESIGN.md section 4 explains every figure):
   roofline      the dominant kernel (K1T `k_rollout_tmpl` at the default configuration: one successor table per
                 workgroup, per-instance swap bits and count deltas).  The tables are in LDS, so it is bound by the
@@ -81,6 +87,31 @@ class HipEvents:
         assert self.hip.hipEventElapsedTime(C.byref(ms), a, b) == 0
         return float(ms.value)
 
+    def destroy(self, ev):
+        assert self.hip.hipEventDestroy(ev) == 0
+
+
+CPU_SAMPLE_TRANSITIONS = 512 * 3_200_000   # --full: bound of the oracle's work on one core (about 25 s; a quarter per thread of all cores)
+DUMP_BYTES = 64 << 20     # --dump-outputs: all files together stay below this
+DUMP_INSTANCES = 2048     # ... and the per-state visit counters are those of a fixed, seeded sample of this many instances
+
+
+def dump_outputs(env, directory, B, S, start):
+    """What a caller of the timed path reads after its last step, as float64 .npy files: every instance's current state,
+    its step within the episode and its episode count (visits of the start state); the state and state-action visit
+    counters of a fixed sample of instances (`sample_instances`, drawn with seed 0).  The counters accumulate from reset()
+    over the settling, warm-up and timed launches, so the same arguments give the same files."""
+    os.makedirs(directory, exist_ok=True)
+    vs, vsa = env.visits()
+    cur, h, _ = env.state()
+    vs, vsa = vs.reshape(B, S), vsa.reshape(B, -1)
+    n = int(min(B, DUMP_INSTANCES, max(0, DUMP_BYTES - 8 * 3 * B) // (8 * (1 + vs.shape[1] + vsa.shape[1]))))
+    pick = np.sort(np.random.default_rng(0).choice(B, n, replace=False))
+    out = {"state": cur, "step_in_episode": h, "episodes": vs[:, start], "sample_instances": pick,
+           "visits_s": vs[pick], "visits_sa": vsa[pick]}
+    for name, a in out.items():
+        np.save(os.path.join(directory, name + ".npy"), np.asarray(a, np.float64))
+
 
 def frozenlake_dp_tables(seeds, size, workers):
     from colosseum_amd.mdp.fast_batch import frozenlake_dp_tables as build
@@ -142,6 +173,7 @@ def sustained_leg(env, ev, launch_steps, seconds, B):
     stream = env.stream
     a, b = ev.create(), ev.create()
     env.synchronize()
+    env.reset_visits()   # (the timed steps may have used most of the int32 counters' room: start this leg with all of it)
     th.start()
     t0 = time.perf_counter()
     ev.record(a, stream)
@@ -336,9 +368,16 @@ def main():
     ap.add_argument("--pmc-child-out", default="", help=argparse.SUPPRESS)           # ... which leaves its sweep count here
     ap.add_argument("--layout", default="csr", choices=["csr", "dense"],
                     help="layout of the HEADLINE leg: csr (default, fastest) or dense (then --launch-steps applies to K1D)")
+    ap.add_argument("--full", action="store_true", help="also run the dense, vi, cpu_baseline (oracle check), sustained and strong "
+                    "legs and the rocprofv3 child passes (off: the headline steps only)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write what they computed as "
+                    "DIR/<name>.npy (float64, < 64 MB; rank 0's shard)")
     args = ap.parse_args()
+    if args.save_pmc and not args.full:
+        ap.error("--save-pmc writes the counters of the rocprofv3 child passes, which run with --full only")
 
     if args.pmc_child:   # a few launches of the headline and dense kernels, nothing else, nothing printed
+        args.full = True
         args.steps, args.warmup, args.dense_steps = 3, 1, 2
         args.no_cpu, args.no_live_pmc, args.sustained_seconds, args.strong_share = True, True, 0.0, 0
         # the VI leg of the SQ pass: a few instances built WITHOUT a process pool (the profiler's preload has initialised the GPU
@@ -355,7 +394,7 @@ def main():
     # Host-side model construction of the VI leg first: it uses a fork()ed process pool, which must not happen
     # after the HIP runtime / RCCL have been initialised in this process.
     fl, fl_build_s = None, 0.0
-    if args.vi_instances > 0:
+    if args.full and args.vi_instances > 0:
         workers = 1 if args.pmc_child else max(1, min(16, (os.cpu_count() or 1) // max(1, world)))
         tb = time.time()
         fl = frozenlake_dp_tables(np.arange(rank * args.vi_instances, (rank + 1) * args.vi_instances), 20, workers)
@@ -427,7 +466,10 @@ def main():
         env.synchronize()
         barrier()
         wall = time.perf_counter() - t0
-        return wall, [ev.elapsed_ms(marks[k], marks[k + 1]) for k in range(n_launch)]
+        ms = [ev.elapsed_ms(marks[k], marks[k + 1]) for k in range(n_launch)]
+        for m in marks:
+            ev.destroy(m)
+        return wall, ms
 
     # ---- C2 workload: this rank's shard of DeepSeaEpisodic(seed=i, size=30), i in [rank*B, (rank+1)*B) ----
     if args.scaling == "strong":
@@ -471,15 +513,18 @@ def main():
             L.check(lib.cmdp_stat(env.handle, which, C.byref(v)))
             timed_kernel_ms[name] = v.value
     elapsed = max_over_ranks(elapsed)
+    start = int(tables["start_state"][0])
+    if args.dump_outputs and rank == 0:
+        dump_outputs(env, args.dump_outputs, B, S, start)
 
     # ---- final gather over RCCL (the only collective): per-instance episode counts = visits of the start state ----
-    vs, _ = env.visits(sa=False)
-    start = int(tables["start_state"][0])
-    episodes = vs.reshape(B, S)[:, start].copy()
+    # (the visit counters are read before `sustained` adds launches: the oracle check of --full covers exactly the steps above)
+    vs = env.visits(sa=False)[0] if dist is not None or args.full else None
     gather_ms = None
     if dist is not None:
         import torch
 
+        episodes = vs.reshape(B, S)[:, start].copy()
         local = torch.from_numpy(episodes).to(coll_device)
         allv = torch.empty(world * B, dtype=torch.int64, device=coll_device)
         if coll_device == "cuda":
@@ -493,7 +538,7 @@ def main():
 
     # ---- sustained leg: back-to-back launches for >= --sustained-seconds, SMI sampled meanwhile (N = 1 only) -------------
     sustained = None
-    if args.sustained_seconds > 0 and world == 1 and not dense_headline:
+    if args.full and args.sustained_seconds > 0 and world == 1 and not dense_headline:
         sustained = sustained_leg(env, ev, args.launch_steps, args.sustained_seconds, B)
 
     # ---- HBM traffic of the headline and dense kernels, measured now (child runs under rocprofv3 --pmc; N = 1 only) ------
@@ -501,7 +546,7 @@ def main():
     # (not when this run is itself profiled: the profiler's preload has initialised the GPU before main(), and the GPU boxes
     # refuse a fork + exec from such a process -- the committed summary is used then)
     under_profiler = "rocprof" in os.environ.get("LD_PRELOAD", "") or any(k.startswith(("ROCPROFILER_", "ROCPROF_")) for k in os.environ)
-    if world == 1 and not args.no_live_pmc and not dense_headline and not under_profiler:
+    if args.full and world == 1 and not args.no_live_pmc and not dense_headline and not under_profiler:
         t_pmc = time.time()
         LIVE_PMC = live_pmc(["--instances", str(B), "--size", str(args.size), "--launch-steps", str(args.launch_steps),
                              "--dense-instances", str(args.dense_instances), "--dense-launch-steps", str(args.dense_launch_steps),
@@ -709,7 +754,7 @@ def main():
             "settle_launches": settle,
             "settle_note": "untimed launches of the same step before the W warm-up steps: the first ~40 launches on a freshly built handle "
                            "run 2-9 % slower than the level `sustained` shows (first-touch of the code-word buffers, clock / power "
-                           "management after the idle build phase); the in-run oracle check covers them too",
+                           "management after the idle build phase); the oracle check of --full covers them too",
         },
         "build_id": build_id[:16],
         "roofline": roofline,
@@ -726,7 +771,7 @@ def main():
         line["sustained"] = sustained
 
     # ---- strong-scaling rehearsal: one rank's share of 65 536 instances TOTAL over `--strong-share` GPUs ---------------
-    if args.strong_share > 1 and world == 1 and args.scaling == "weak" and not dense_headline and B % args.strong_share == 0:
+    if args.full and args.strong_share > 1 and world == 1 and args.scaling == "weak" and not dense_headline and B % args.strong_share == 0:
         Bs = B // args.strong_share
         senv = BatchedMDP(tables=deepsea_episodic_tables(seeds[:Bs], args.size, with_dp=False), rng_mode=L.RNG_PHILOX,
                           philox_keys=keys[:Bs])
@@ -752,7 +797,7 @@ def main():
 
     # ---- dense-row leg (north-star layout, K1D): same instances, rows streamed from HBM -------------------------
     dense_env = None
-    if args.dense_instances > 0 and not dense_headline:
+    if args.full and args.dense_instances > 0 and not dense_headline:
         Bd = args.dense_instances
         td = time.time()
         dseeds = seeds[:Bd]
@@ -777,7 +822,7 @@ def main():
         }
 
     # ---- VI leg (config C3): FrozenLake 20x20, gamma .99, eps 1e-6, the reference's own scheme rule --------
-    if args.vi_instances > 0:
+    if fl is not None:   # (built above with --full)
         tb = time.time()
         dp = BatchedMDP(tables=fl, with_env=False)
         tb = time.time() - tb + fl_build_s
@@ -863,11 +908,13 @@ def main():
         dp.close()
 
     # ---- CPU baseline: the oracle, one core, bounded sample of the same workload (rank 0, N = 1 only) -----
-    if rank == 0 and world == 1 and not args.no_cpu and args.cpu_instances > 0:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu and args.cpu_instances > 0:
         from oracle import oracle as O
 
-        n = min(args.cpu_instances, B)
         n_steps = args.launch_steps * (args.steps + args.warmup + settle)  # everything the GPU did since reset()
+        # the sample shrinks as the steps grow: at most CPU_SAMPLE_TRANSITIONS on this core (512 instances at the defaults),
+        # and at least one instance checked over every transition
+        n = max(1, min(args.cpu_instances, B, CPU_SAMPLE_TRANSITIONS // n_steps))
         c0 = time.perf_counter()
         last, rsum, cvs, _ = O.batch_rollout(tables, 0, n, n_steps, rng_mode=1, philox_keys=keys, want_visits=True)
         cpu_s = time.perf_counter() - c0
@@ -903,7 +950,7 @@ def main():
         if cores > 1:
             from concurrent.futures import ThreadPoolExecutor
 
-            n_mt = min(B, 128 * cores)
+            n_mt = min(B, cores * max(1, min(128, CPU_SAMPLE_TRANSITIONS // 4 // n_steps)))   # 128 per thread at the defaults
             per = -(-n_mt // cores)
             ranges = [(lo, min(n_mt, lo + per)) for lo in range(0, n_mt, per)]
             c0 = time.perf_counter()

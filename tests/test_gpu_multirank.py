@@ -29,7 +29,7 @@ def _torchrun(n, port):
             "--master-port", str(port)]
 
 
-SMALL = ["--instances", "2048", "--launch-steps", "600", "--steps", "3", "--warmup", "1", "--dense-instances", "0",
+SMALL = ["--full", "--instances", "2048", "--launch-steps", "600", "--steps", "3", "--warmup", "1", "--dense-instances", "0",
          "--vi-instances", "32", "--no-cpu", "--share-gpu", "--dist-backend", "gloo"]
 
 
