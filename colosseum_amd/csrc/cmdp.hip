@@ -195,15 +195,12 @@ struct cmdp {
   bool k1u_ok = false, k1u_auto = false;
   K1uPlan k1u{};
   size_t k1u_lds = 0;
-  DevBuf<uint4> d_k1u_trace[2];
-  DevBuf<int32_t> d_k1u_resets[2];
-  // the histogram of segment k runs on a second stream under the chain kernel of segment k + 1 (two trace buffers)
-  bool k1u_overlap = false, k1u_overlap_fits = false, k1u_pending = false;
-  hipStream_t aux_stream = nullptr;
-  hipEvent_t ev_trace[2] = {nullptr, nullptr}, ev_hist[2] = {nullptr, nullptr};
-  bool ev_hist_used[2] = {false, false}, k1u_last_overlap = false;
-  int64_t k1u_seq = 0;
-  hipEvent_t ev_k1u[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // CMDP_STAT_ROLLOUT_KERNEL_MS / _HIST_KERNEL_MS of the last segment
+  DevBuf<uint4> d_k1u_trace;
+  DevBuf<int32_t> d_k1u_resets;
+  // CMDP_STAT_ROLLOUT_KERNEL_MS / _HIST_KERNEL_MS: around the two kernels of the last segment of the last K1U or K1E launch
+  // (events 0-1: the rollout kernel; 1-2: the second kernel on the handle's stream, or 3-4 on the second stream: ev_time_aux)
+  hipEvent_t ev_time[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  bool ev_time_aux = false;
   // K1E: the episode-parallel rollout (cmdp_k1e.h): lane = (instance, episode), private {successor | count} tables in LDS
   bool k1e_ok = false;
   K1ePlan k1e{};
@@ -212,9 +209,13 @@ struct cmdp {
   DevBuf<uint2> d_k1e_codes[2];    // two sets: the reward scan of one segment runs (second stream) under the walk of the next
   DevBuf<uint32_t> d_k1e_cnts[2];
   DevBuf<int32_t> d_k1e_h0b;       // second seg_h0 buffer
-  hipEvent_t ev_k1e_walk[2] = {nullptr, nullptr}, ev_k1e_scan[2] = {nullptr, nullptr};
-  bool ev_k1e_scan_used[2] = {false, false}, k1e_scan_pending = false;
-  int64_t k1e_seq = 0;
+  struct {                         // the second stream: K1E's reward scans (scan of code set i after the walk that wrote it)
+    hipStream_t stream = nullptr;
+    hipEvent_t walk[2] = {nullptr, nullptr}, scan[2] = {nullptr, nullptr};
+    bool used[2] = {false, false};
+    int64_t seq = 0;               // scans enqueued: the next segment takes set seq & 1
+    bool pending = false;          // the handle's stream has not waited for the last scan yet
+  } aux;                           // (cmdp_qlearning_run_logged evaluates on the stream too, after bind() has settled it)
   DevBuf<int2> d_k1e_dep;          // departure counts of the K1E launches since the last fold (k_epi_fold)
   DevBuf<int32_t> d_k1e_dep_res, d_vis_ovf;
   int64_t vis_bound = 0;           // upper bound of every device visit counter (int32): CMDP_ERR_OVERFLOW guard
@@ -281,48 +282,21 @@ struct cmdp {
 
 namespace {
 
-// the main stream waits for the histogram the second stream still owes (K1U): before anything reads or writes the counters
-int k1u_join(cmdp_t* h) {
-  if (h->k1u_pending) {
-    HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_hist[(h->k1u_seq + 1) & 1], 0));
-    h->k1u_pending = false;
-  }
-  return CMDP_OK;
-}
-
-// ... the main stream waits for the reward scan K1E still owes on the second stream: before anything reads the reward sums
-int k1e_scan_join(cmdp_t* h) {
-  if (h->k1e_scan_pending) {
-    HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_k1e_scan[(h->k1e_seq + 1) & 1], 0));
-    h->k1e_scan_pending = false;
-  }
-  return CMDP_OK;
-}
-
-// ... and the departure counts the episode-parallel rollout K1E has accumulated are turned into the visit counters
-int k1e_fold(cmdp_t* h);
-int visits_join(cmdp_t* h) {
-  if (int rc = k1u_join(h)) return rc;
-  if (int rc = k1e_scan_join(h)) return rc;
-  return k1e_fold(h);
-}
-
 // The device visit counters are int32.  No counter can grow by more than two per transition (the arrival and, when the
 // episode ends there, the reset), so `vis_bound` bounds all of them; a call that could carry one past 2^31 - 1 is refused.
-int visits_room(cmdp_t* h, int64_t n_transitions) {
+int visits_check(const cmdp_t* h, int64_t n_transitions) {
   if (h->vis_bound + 2 * n_transitions > 0x7fffffffLL)
     return fail(CMDP_ERR_OVERFLOW, "a visit counter (int32 on the device) could wrap: up to %lld counted since the last "
                 "cmdp_reset_visits / cmdp_set_visits, %lld more transitions asked for -- read the counters (cmdp_visits) and reset them",
                 (long long)h->vis_bound, (long long)n_transitions);
-  h->vis_bound += 2 * n_transitions;
   return CMDP_OK;
 }
 
-int bind(cmdp_t* h, bool join = true) {
-  if (!h) return fail(CMDP_ERR_INVALID, "null handle");
-  HIP_TRY(hipSetDevice(h->device));
-  if (join) return visits_join(h);
-  return CMDP_OK;
+// ... and the call's transitions are added to the bound once its kernels may have run: after success, or after a HIP error
+// (one of several launches can fail); a call refused with any other code has stepped nothing
+int visits_commit(cmdp_t* h, int64_t n_transitions, int rc = CMDP_OK) {
+  if (rc == CMDP_OK || rc == CMDP_ERR_HIP) h->vis_bound += 2 * n_transitions;
+  return rc;
 }
 
 inline int grid_for(int64_t n, int block) { return (int)((n + block - 1) / block); }
@@ -354,6 +328,27 @@ int k1e_fold(cmdp_t* h) {
   return CMDP_OK;
 }
 
+// the handle's stream waits for the reward scan K1E still owes on the second stream: before anything reads the reward sums
+int k1e_scan_join(cmdp_t* h) {
+  if (h->aux.pending) {
+    HIP_TRY(hipStreamWaitEvent(h->stream, h->aux.scan[(h->aux.seq + 1) & 1], 0));
+    h->aux.pending = false;
+  }
+  return CMDP_OK;
+}
+
+// ... and also folds the departure counts K1E has accumulated into the visit counters: what every other kernel and every
+// read of the counters needs first
+int k1e_settle(cmdp_t* h) {
+  if (int rc = k1e_scan_join(h)) return rc;
+  return k1e_fold(h);
+}
+
+int bind(cmdp_t* h, bool settle = true) {
+  if (!h) return fail(CMDP_ERR_INVALID, "null handle");
+  HIP_TRY(hipSetDevice(h->device));
+  return settle ? k1e_settle(h) : CMDP_OK;
+}
 
 }  // namespace
 
@@ -572,19 +567,15 @@ int cmdp_destroy(cmdp_t* h) {
     (void)hipStreamDestroy(h->stream);
   }
   for (int i = 0; i < 2; ++i) {
-    if (h->ev_k1e_walk[i]) (void)hipEventDestroy(h->ev_k1e_walk[i]);
-    if (h->ev_k1e_scan[i]) (void)hipEventDestroy(h->ev_k1e_scan[i]);
+    if (h->aux.walk[i]) (void)hipEventDestroy(h->aux.walk[i]);
+    if (h->aux.scan[i]) (void)hipEventDestroy(h->aux.scan[i]);
   }
-  if (h->aux_stream) {
-    (void)hipStreamSynchronize(h->aux_stream);
-    (void)hipStreamDestroy(h->aux_stream);
-  }
-  for (int i = 0; i < 2; ++i) {
-    if (h->ev_trace[i]) (void)hipEventDestroy(h->ev_trace[i]);
-    if (h->ev_hist[i]) (void)hipEventDestroy(h->ev_hist[i]);
+  if (h->aux.stream) {
+    (void)hipStreamSynchronize(h->aux.stream);
+    (void)hipStreamDestroy(h->aux.stream);
   }
   for (int i = 0; i < 5; ++i)
-    if (h->ev_k1u[i]) (void)hipEventDestroy(h->ev_k1u[i]);
+    if (h->ev_time[i]) (void)hipEventDestroy(h->ev_time[i]);
   for (int i = 0; i < 2; ++i)
     if (h->ev_row[i]) (void)hipEventDestroy(h->ev_row[i]);
   for (double* c : h->rc_chunks) (void)hipFree(c);
@@ -1005,12 +996,10 @@ int cmdp_create(cmdp_t** out, const cmdp_desc* d) {
                   h->k1u_lds = k1u_lds_bytes(u, u.G);
                   h->k1u_ok = true;
                   h->k1u_auto = h->tmpl_auto && rounds_u < rounds_t;
-                  // the histogram of one launch under the chain of the next (second stream) was measured at C2 and LOST:
-                  // co-resident, the chain kernel slows from 2.2 to 3.0 ms (the histogram's LDS atomics sit in the same
-                  // in-order LDS pipeline as the chain's dependent reads) -- 3.25 ms per step against 3.00 one after the
-                  // other.  Kept behind CMDP_K1U_OVERLAP=1 for batches where both workgroups fit one CU.
-                  h->k1u_overlap = false;
-                  h->k1u_overlap_fits = h->k1u_lds + k1h_lds_bytes(S, 32) + 1024 <= (size_t)kLdsBudget;
+                  // (the histogram of one launch under the chain of the next, on a second stream, was measured at C2 and
+                  // LOST: co-resident, the chain kernel slows from 2.2 to 3.0 ms -- the histogram's LDS atomics sit in the
+                  // same in-order LDS pipeline as the chain's dependent reads -- 3.25 ms per step against 3.00 one after
+                  // the other; the two kernels run on the handle's stream)
                   if (const char* ue = std::getenv("CMDP_K1U")) h->k1u_auto = std::atoi(ue) != 0;
                 }
               }
@@ -1179,7 +1168,7 @@ int cmdp_create(cmdp_t** out, const cmdp_desc* d) {
 int cmdp_reset(cmdp_t* h, const uint8_t* mask, int32_t* obs_out) {
   if (int rc = bind(h)) return rc;
   if (!h->has_env) return fail(CMDP_ERR_INVALID, "handle was created without the sampler half");
-  if (int rc = visits_room(h, 1)) return rc;
+  if (int rc = visits_check(h, 1)) return rc;
   hipStream_t st = h->stream;
   uint8_t* dmask = nullptr;
   if (mask) {
@@ -1190,6 +1179,7 @@ int cmdp_reset(cmdp_t* h, const uint8_t* mask, int32_t* obs_out) {
   if (obs_out && mask) HIP_TRY(hipMemcpyAsync(h->d_last_obs.p, obs_out, sizeof(int32_t) * h->B, hipMemcpyHostToDevice, st));
   hipLaunchKernelGGL(k_reset, dim3(grid_for(h->B, 256)), dim3(256), 0, st, h->env(), dmask,
                      obs_out ? h->d_last_obs.p : nullptr);
+  visits_commit(h, 1);
   HIP_TRY(hipGetLastError());
   if (obs_out) HIP_TRY(hipMemcpyAsync(obs_out, h->d_last_obs.p, sizeof(int32_t) * h->B, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
@@ -1336,7 +1326,7 @@ int cmdp_step(cmdp_t* h, const int32_t* actions, int auto_reset, int32_t* obs, d
   if (!h->has_env) return fail(CMDP_ERR_INVALID, "handle was created without the sampler half");
   if (!actions || !obs || !reward || !step_type) return fail(CMDP_ERR_INVALID, "null argument");
   if (h->layout == CMDP_LAYOUT_DENSE) return fail(CMDP_ERR_UNSUPPORTED, "dense layout: use cmdp_rollout");
-  if (int rc = visits_room(h, 1)) return rc;
+  if (int rc = visits_check(h, 1)) return rc;
   hipStream_t st = h->stream;
   const int B = h->B;
   if (h->d_i32_scratch.n < (size_t)2 * B) HIP_TRY(h->d_i32_scratch.alloc((size_t)2 * B));
@@ -1357,16 +1347,17 @@ int cmdp_step(cmdp_t* h, const int32_t* actions, int auto_reset, int32_t* obs, d
   if (f & 1) return fail(CMDP_ERR_NEEDS_RESET, "step() on an instance that needs reset()");
   h->known_reset = false;  // a step may end an episode (LAST): the async rollout re-checks before its next launch
   if (h->reward_cache) {
-    if (int rc = rc_drive(h, [&](int resume) -> int {
+    if (int rc = visits_commit(h, 1, rc_drive(h, [&](int resume) -> int {
           hipLaunchKernelGGL(k_step<true>, dim3(grid_for(B, 256)), dim3(256), 0, st, h->env(), d_act, auto_reset, d_obs,
                              h->d_f64_scratch.p, h->d_u8_scratch.p, h->rcache(), resume);
           HIP_TRY(hipGetLastError());
           return CMDP_OK;
-        }))
+        })))
       return rc;
   } else {
     hipLaunchKernelGGL(k_step<false>, dim3(grid_for(B, 256)), dim3(256), 0, st, h->env(), d_act, auto_reset, d_obs,
                        h->d_f64_scratch.p, h->d_u8_scratch.p, RewardCache{}, 0);
+    visits_commit(h, 1);
     HIP_TRY(hipGetLastError());
   }
   HIP_TRY(hipMemcpyAsync(obs, d_obs, sizeof(int32_t) * B, hipMemcpyDeviceToHost, st));
@@ -1376,270 +1367,46 @@ int cmdp_step(cmdp_t* h, const int32_t* actions, int auto_reset, int32_t* obs, d
   return CMDP_OK;
 }
 
-static int launch_rollout(cmdp_t* h, int policy, const int8_t* d_actions, int64_t n_steps, double* d_rsum,
-                          int32_t* d_last, int32_t* d_tobs, double* d_trew, uint8_t* d_ttype, const float* d_q = nullptr,
-                          int resume = 0) {
-  hipStream_t st = h->stream;
-  const dim3 grid(grid_for(h->B, 256)), block(256);
-  const bool trace = d_tobs || d_trew || d_ttype;
-  EnvTables t = h->env();
-  // K1E accumulates DEPARTURE counts over its launches (cmdp_k1e.h); every other kernel updates the visit counters itself,
-  // so the image is folded into them first
-  const bool take_k1e = !h->reward_cache && policy == CMDP_POLICY_RANDOM && h->layout != CMDP_LAYOUT_DENSE && h->lds_ok && !trace &&
-                        h->k1e_ok && n_steps > 0 && (h->rollout_kernel == 6 || (h->rollout_kernel == 0 && n_steps >= 64));
-  if (!take_k1e) { if (int rc = k1e_fold(h)) return rc; }
-  if (h->reward_cache) {  // reference-exact reward caches: the lane-per-instance kernel with the park protocol
-    const RewardCache rc = h->rcache();
-#define ROLL_RC(P, TR) \
-  hipLaunchKernelGGL((k_rollout<P, TR, false, true>), grid, block, 0, st, t, d_actions, n_steps, d_rsum, d_last, d_tobs, d_trew, d_ttype, d_q, rc, resume)
-    if (policy == CMDP_POLICY_RANDOM) { if (trace) ROLL_RC(0, true); else ROLL_RC(0, false); }
-    else if (policy == CMDP_POLICY_HOST_ACTIONS) { if (trace) ROLL_RC(1, true); else ROLL_RC(1, false); }
-    else { if (trace) ROLL_RC(2, true); else ROLL_RC(2, false); }
-#undef ROLL_RC
-    HIP_TRY(hipGetLastError());
-    return CMDP_OK;
-  }
-  if (policy == CMDP_POLICY_GREEDY_Q) {
-    if (h->layout == CMDP_LAYOUT_DENSE) return fail(CMDP_ERR_UNSUPPORTED, "CMDP_POLICY_GREEDY_Q runs on the CSR layout");
-    if (trace) hipLaunchKernelGGL((k_rollout<2, true, true>), grid, block, 0, st, t, d_actions, n_steps, d_rsum, d_last, d_tobs, d_trew, d_ttype, d_q);
-    else hipLaunchKernelGGL((k_rollout<2, false, true>), grid, block, 0, st, t, d_actions, n_steps, d_rsum, d_last, d_tobs, d_trew, d_ttype, d_q);
-    HIP_TRY(hipGetLastError());
-    return CMDP_OK;
-  }
-  if (h->layout == CMDP_LAYOUT_DENSE) {
-    if (trace) return fail(CMDP_ERR_UNSUPPORTED, "the dense-layout rollout does not record traces");
-    DenseArgs dn{h->d_dense.p, h->dense_spad};
-    // two instances per wavefront (software-pipelined: one row in flight while the other is scanned) when the row fits
-    // the registers twice; CMDP_K1D_NI = 1 / 2 overrides (tuning aid)
-    static const int ni_env = std::getenv("CMDP_K1D_NI") ? std::atoi(std::getenv("CMDP_K1D_NI")) : 0;
-    const int nv = h->dense_spad / 256;
-    const int ni = ni_env ? ni_env : (nv <= 4 ? 2 : 1);
-    const dim3 dgrid(grid_for(h->B, 4 * ni));
-#define DENSE_LAUNCH(P, NV, BT, NI) \
-  hipLaunchKernelGGL((k_rollout_dense<P, NV, BT, NI>), dgrid, block, 0, st, t, dn, d_actions, n_steps, d_rsum, d_last)
-#define DENSE_CASE(NV, NI)                                                                        \
-  if (nv == NV && ni == NI) {                                                                     \
-    if (policy == CMDP_POLICY_RANDOM) { if (h->sample_beta) DENSE_LAUNCH(0, NV, true, NI); else DENSE_LAUNCH(0, NV, false, NI); } \
-    else { if (h->sample_beta) DENSE_LAUNCH(1, NV, true, NI); else DENSE_LAUNCH(1, NV, false, NI); }      \
-  } else
-    DENSE_CASE(1, 1) DENSE_CASE(2, 1) DENSE_CASE(3, 1) DENSE_CASE(4, 1) DENSE_CASE(6, 1) DENSE_CASE(8, 1) DENSE_CASE(12, 1)
-    DENSE_CASE(16, 1) DENSE_CASE(1, 2) DENSE_CASE(2, 2) DENSE_CASE(3, 2) DENSE_CASE(4, 2)
-    { return fail(CMDP_ERR_UNSUPPORTED, "dense layout: no kernel for a row stride of %d floats, %d instances per wavefront", h->dense_spad, ni); }
-#undef DENSE_CASE
-#undef DENSE_LAUNCH
-    HIP_TRY(hipGetLastError());
-    return CMDP_OK;
-  }
-  const bool lds_eligible = h->lds_ok && policy == CMDP_POLICY_RANDOM && !trace;
-  if (h->rollout_kernel == 2 && !lds_eligible)
+// ---- rollout: the kernel a launch takes, then one launcher per kernel -----------------------------------
+enum class RolloutKernel { K1, K1_REWARD_CACHE, K1_GREEDY, K1D, K1L, K1P, K1T, K1U, K1E, K1S };
+
+struct RolloutCall {
+  int policy;
+  const int8_t* actions;   // CMDP_POLICY_HOST_ACTIONS: [n][B]
+  const float* q;          // CMDP_POLICY_GREEDY_Q: the Q table
+  int64_t n;
+  double* rsum;
+  int32_t* last;
+  int32_t* tobs; double* trew; uint8_t* ttype;   // the trace (only K1 records one)
+  int resume;              // reward caches: 1 when only the lanes that parked continue
+  bool trace() const { return tobs || trew || ttype; }
+};
+
+// No HIP calls.  CMDP_OPT_ROLLOUT_KERNEL forces a kernel (refused when the batch is not eligible); the reward-cache,
+// greedy-Q and dense-layout paths ignore it.  Automatically the LDS-resident kernels are taken from 64 transitions on
+// (they pay a fixed staging + flush cost per launch), the most specialised eligible one first.
+static int pick_rollout(const cmdp_t* h, int policy, bool trace, int64_t n_steps, RolloutKernel* out) {
+  using K = RolloutKernel;
+  const int rk = h->rollout_kernel;
+  const bool dense = h->layout == CMDP_LAYOUT_DENSE, wide = rk == 0 && n_steps >= 64;
+  *out = h->reward_cache ? K::K1_REWARD_CACHE : policy == CMDP_POLICY_GREEDY_Q ? K::K1_GREEDY : dense ? K::K1D : K::K1;
+  if (*out == K::K1_GREEDY && dense) return fail(CMDP_ERR_UNSUPPORTED, "CMDP_POLICY_GREEDY_Q runs on the CSR layout");
+  if (*out == K::K1D && trace) return fail(CMDP_ERR_UNSUPPORTED, "the dense-layout rollout does not record traces");
+  if (*out != K::K1) return CMDP_OK;
+  const bool lds = h->lds_ok && policy == CMDP_POLICY_RANDOM && !trace, k1s = h->k1s_ok && policy == CMDP_POLICY_RANDOM && !trace;
+  if (rk == 2 && !lds)
     return fail(CMDP_ERR_UNSUPPORTED, "LDS-resident rollout needs deterministic dynamics, one start state, <= 65535 "
                                       "states, <= 256 distinct rewards, the random policy and no trace");
-  // the LDS kernel pays a fixed staging + flush cost per launch: worth it from a few dozen transitions on
-  if (h->rollout_kernel == 4 && !(lds_eligible && h->tmpl_ok))
+  if (rk == 4 && !(lds && h->tmpl_ok))
     return fail(CMDP_ERR_UNSUPPORTED, "the shared-table rollout K1T needs a batch eligible for K1P with two actions whose instances "
                                       "are per-state action permutations of the first one, the random policy and no trace");
-  if (h->rollout_kernel == 5 && !(lds_eligible && h->k1u_ok))
+  if (rk == 5 && !(lds && h->k1u_ok))
     return fail(CMDP_ERR_UNSUPPORTED, "the streamed-trace rollout K1U needs a batch eligible for the shared-table rollout K1T (CMDP_OPT_ROLLOUT_KERNEL 4) "
                                       "and room for 64 instances per workgroup");
-  if (h->rollout_kernel == 6 && !(lds_eligible && h->k1e_ok))
+  if (rk == 6 && !(lds && h->k1e_ok))
     return fail(CMDP_ERR_UNSUPPORTED, "the episode-parallel rollout K1E needs a batch eligible for the LDS-resident kernels (CMDP_OPT_ROLLOUT_KERNEL 2) "
                                       "that is episodic, has two actions, at most four distinct reward values, at most 512 states per instance and a horizon whose action bits for 128 episodes fit LDS");
-  if (take_k1e) {
-    // K1E: per segment of <= K1E_SEG transitions (16-bit counts in the table dwords; the code buffer) the walk kernel, then
-    // the reward scan over the code words it left in HBM
-    if (int rc = k1u_join(h)) return rc;
-    if (!h->ev_k1u[0])
-      for (int i = 0; i < 5; ++i) HIP_TRY(hipEventCreateWithFlags(&h->ev_k1u[i], hipEventDisableSystemFence));   // (timestamps only: no host-visibility cache flush per launch)
-    K1ePlan e = h->k1e;
-    if (!h->d_k1e_dep.p) {
-      const size_t nd = (size_t)grid_for(h->B, K1E_NI) * (size_t)e.gdw;
-      HIP_TRY(h->d_k1e_dep.alloc(nd));
-      HIP_TRY(h->d_k1e_dep.zero(st));
-      HIP_TRY(h->d_k1e_dep_res.alloc(h->B));
-      HIP_TRY(h->d_k1e_dep_res.zero(st));
-      HIP_TRY(h->d_vis_ovf.alloc(1));
-      HIP_TRY(h->d_vis_ovf.zero(st));
-    }
-    if (h->k1e_pending_steps + n_steps > 0x7fff0000LL) { if (int rc = k1e_fold(h)) return rc; }   // the departure image is int32
-    e.dep = h->d_k1e_dep.p;
-    e.dep_res = h->d_k1e_dep_res.p;
-    // The reward scan of a segment runs on a second stream under the walk of the next segment / launch (two sets of code
-    // buffers): it is one wavefront per SIMD of sequential sums, the walk fills the rest of the chip (CMDP_K1E_OVERLAP=0: one
-    // stream).  cmdp_rollout / cmdp_synchronize / every call that reads the sums waits for it.
-    static const int ov_env = std::getenv("CMDP_K1E_OVERLAP") ? std::atoi(std::getenv("CMDP_K1E_OVERLAP")) : 1;
-    const bool ov = ov_env != 0;
-    if (ov && !h->aux_stream) HIP_TRY(hipStreamCreateWithFlags(&h->aux_stream, hipStreamNonBlocking));
-    if (ov && !h->ev_k1e_walk[0])
-      for (int i = 0; i < 2; ++i) {
-        HIP_TRY(hipEventCreateWithFlags(&h->ev_k1e_walk[i], hipEventDisableTiming | hipEventDisableSystemFence));
-        HIP_TRY(hipEventCreateWithFlags(&h->ev_k1e_scan[i], hipEventDisableTiming | hipEventDisableSystemFence));
-      }
-    if (!ov) { if (int rc = k1e_scan_join(h)) return rc; }
-    // segment length: the code words of a segment (12 bytes per episode chunk and instance, two sets) stay within ~1.5 GB
-    const int64_t budget_words = std::max<int64_t>(4, (int64_t)((768ll << 20) / (12 * (int64_t)h->B * e.nch)));
-    const int64_t seg = std::max<int64_t>(e.H, std::min<int64_t>(K1E_SEG, (budget_words - 2) * e.H));
-    const int64_t epi_cap = k1e_max_episodes(std::min<int64_t>(n_steps, seg), e.H);
-    const size_t need = (size_t)epi_cap * (size_t)e.nch * (size_t)h->B;
-    if (h->d_k1e_h0.n < (size_t)h->B) HIP_TRY(h->d_k1e_h0.alloc(h->B));
-    if (h->d_k1e_h0b.n < (size_t)h->B) HIP_TRY(h->d_k1e_h0b.alloc(h->B));
-    if (int rc = set_lds(k_rollout_epi<true>, h->k1e_lds)) return rc;
-    if (int rc = set_lds(k_rollout_epi<false>, h->k1e_lds)) return rc;
-    for (int64_t s0 = 0; s0 < n_steps; s0 += seg) {
-      const int64_t n = std::min<int64_t>(seg, n_steps - s0);
-      const int i = ov ? (int)(h->k1e_seq & 1) : 0;
-      if (h->d_k1e_codes[i].n < need || h->d_k1e_cnts[i].n < need) {
-        if (h->aux_stream) HIP_TRY(hipStreamSynchronize(h->aux_stream));   // a scan may still read the buffers
-        if (h->d_k1e_codes[i].alloc(need) != hipSuccess || h->d_k1e_cnts[i].alloc(need) != hipSuccess) {
-          // no room for the code words (12 bytes per episode and instance): the chain kernels need no workspace -- this
-          // handle takes them from now on (possible before the first segment only: the buffers never shrink)
-          (void)hipGetLastError();
-          if (s0 > 0) return fail(CMDP_ERR_HIP, "K1E: out of device memory for the code words of a later segment");
-          h->d_k1e_codes[i].release();
-          h->d_k1e_cnts[i].release();
-          h->k1e_ok = false;
-          if (h->rollout_kernel == 6) return fail(CMDP_ERR_HIP, "K1E: out of device memory for %zu code words", need);
-          return launch_rollout(h, policy, d_actions, n_steps, d_rsum, d_last, d_tobs, d_trew, d_ttype, d_q, resume);
-        }
-      }
-      e.codes = h->d_k1e_codes[i].p;
-      e.cnts = h->d_k1e_cnts[i].p;
-      e.seg_h0 = i ? h->d_k1e_h0b.p : h->d_k1e_h0.p;
-      e.n_pass = (int)((k1e_max_episodes(n, e.H) + K1E_EPP - 1) / K1E_EPP);
-      if (ov && h->ev_k1e_scan_used[i]) HIP_TRY(hipStreamWaitEvent(st, h->ev_k1e_scan[i], 0));   // its last scan has read this set
-      const bool last = s0 + seg >= n_steps;
-      if (last) HIP_TRY(hipEventRecord(h->ev_k1u[0], st));
-      // one workgroup per CU (the tables take the CU's LDS), each walking its groups one after the other with the next
-      // group's table image in flight under the walk; CMDP_K1E_GRID = workgroups (timing experiments; any value is correct)
-      int k1e_grid = std::min(grid_for(h->B, K1E_NI), h->cus);
-      if (const char* gs = std::getenv("CMDP_K1E_GRID")) k1e_grid = std::max(1, std::min(grid_for(h->B, K1E_NI), std::atoi(gs)));
-      if (e.n_codes <= 3) hipLaunchKernelGGL(k_rollout_epi<true>, dim3(k1e_grid), dim3(K1E_THREADS), h->k1e_lds, st, t, e, (int)n, d_last);
-      else hipLaunchKernelGGL(k_rollout_epi<false>, dim3(k1e_grid), dim3(K1E_THREADS), h->k1e_lds, st, t, e, (int)n, d_last);
-      if (last) HIP_TRY(hipEventRecord(h->ev_k1u[1], st));
-      if (ov) {
-        HIP_TRY(hipEventRecord(h->ev_k1e_walk[i], st));
-        HIP_TRY(hipStreamWaitEvent(h->aux_stream, h->ev_k1e_walk[i], 0));
-        if (last) HIP_TRY(hipEventRecord(h->ev_k1u[3], h->aux_stream));
-        hipLaunchKernelGGL(k_reward_scan, dim3(grid_for(h->B, K1R_THREADS)), dim3(K1R_THREADS), 0, h->aux_stream, t, e, n, d_rsum, s0 > 0 ? 1 : 0);
-        if (last) HIP_TRY(hipEventRecord(h->ev_k1u[4], h->aux_stream));
-        HIP_TRY(hipEventRecord(h->ev_k1e_scan[i], h->aux_stream));
-        h->ev_k1e_scan_used[i] = true;
-        h->k1e_scan_pending = true;
-        h->k1e_seq++;
-      } else {
-        hipLaunchKernelGGL(k_reward_scan, dim3(grid_for(h->B, K1R_THREADS)), dim3(K1R_THREADS), 0, st, t, e, n, d_rsum, s0 > 0 ? 1 : 0);
-        if (last) HIP_TRY(hipEventRecord(h->ev_k1u[2], st));
-      }
-    }
-    h->k1u_last_overlap = ov;
-    h->k1e_pending = true;
-    h->k1e_pending_steps += n_steps;
-    HIP_TRY(hipGetLastError());
-    return CMDP_OK;
-  }
-  const bool take_k1u = lds_eligible && h->k1u_ok && (h->rollout_kernel == 5 || (h->rollout_kernel == 0 && h->k1u_auto && n_steps >= 64));
-  if (!take_k1u) {
-    if (int rc = k1u_join(h)) return rc;   // every other kernel updates the visit counters itself
-  } else {
-    // K1U: per segment of <= K1U_SEG transitions the chain kernel (trace -> HBM), then the histogram of that trace -- on a
-    // second stream, under the chain kernel of the next segment / launch (two trace buffers), unless switched off
-    static const int ov_env = std::getenv("CMDP_K1U_OVERLAP") ? std::atoi(std::getenv("CMDP_K1U_OVERLAP")) : -1;
-    const bool ov = (ov_env < 0 ? h->k1u_overlap : ov_env != 0) && h->k1u_overlap_fits;
-    if (!h->ev_k1u[0])
-      for (int i = 0; i < 5; ++i) HIP_TRY(hipEventCreateWithFlags(&h->ev_k1u[i], hipEventDisableSystemFence));   // (timestamps only: no host-visibility cache flush per launch)
-    if (ov && !h->aux_stream) {
-      HIP_TRY(hipStreamCreateWithFlags(&h->aux_stream, hipStreamNonBlocking));
-      for (int i = 0; i < 2; ++i) {
-        HIP_TRY(hipEventCreateWithFlags(&h->ev_trace[i], hipEventDisableTiming | hipEventDisableSystemFence));
-        HIP_TRY(hipEventCreateWithFlags(&h->ev_hist[i], hipEventDisableTiming | hipEventDisableSystemFence));
-      }
-    }
-    if (!ov) { if (int rc = k1u_join(h)) return rc; }
-    const int64_t seg_max = std::min<int64_t>(n_steps, K1U_SEG);
-    K1uPlan u = h->k1u;
-    const int epp = K1U_EPP(u.pack10);
-    const size_t need = (size_t)((seg_max + epp - 1) / epp) * (size_t)h->B;
-    const size_t hist_lds = k1h_lds_bytes(h->max_S, ov ? 32 : 64);
-#define K1U_SET_LDS(P10)                                                                             \
-    {                                                                                                \
-      if (int rc = set_lds(k_rollout_tmpl_stream<P10>, h->k1u_lds)) return rc;                       \
-      if (ov) { if (int rc = set_lds(k_trace_hist<32, 512, P10>, hist_lds)) return rc; }             \
-      else { if (int rc = set_lds(k_trace_hist<64, 1024, P10>, hist_lds)) return rc; }               \
-    }
-    if (u.pack10) K1U_SET_LDS(true) else K1U_SET_LDS(false)
-#undef K1U_SET_LDS
-    for (int64_t s0 = 0; s0 < n_steps; s0 += K1U_SEG) {
-      const int64_t n = std::min<int64_t>(K1U_SEG, n_steps - s0);
-      const int i = ov ? (int)(h->k1u_seq & 1) : 0;
-      if (h->d_k1u_trace[i].n < need) {
-        if (ov && h->aux_stream) HIP_TRY(hipStreamSynchronize(h->aux_stream));   // the buffer may still be read
-        if (h->d_k1u_trace[i].alloc(need) != hipSuccess) {
-          // no room for the trace (16 bytes per 8-12 transitions and instance): K1T counts in LDS and needs none -- this
-          // handle takes it from now on (possible before the first segment only: the buffer never shrinks)
-          (void)hipGetLastError();
-          if (s0 > 0) return fail(CMDP_ERR_HIP, "K1U: out of device memory for the trace of a later segment");
-          h->d_k1u_trace[i].release();
-          h->k1u_ok = false;
-          if (h->rollout_kernel == 5) return fail(CMDP_ERR_HIP, "K1U: out of device memory for a trace of %zu pieces", need);
-          return launch_rollout(h, policy, d_actions, n_steps, d_rsum, d_last, d_tobs, d_trew, d_ttype, d_q, resume);
-        }
-      }
-      if (h->d_k1u_resets[i].n < (size_t)h->B) HIP_TRY(h->d_k1u_resets[i].alloc(h->B));
-      u.trace = h->d_k1u_trace[i].p;
-      u.seg_resets = h->d_k1u_resets[i].p;
-      if (ov && h->ev_hist_used[i]) HIP_TRY(hipStreamWaitEvent(st, h->ev_hist[i], 0));   // its last histogram has read the buffer
-      const bool last = s0 + K1U_SEG >= n_steps;
-      if (last) HIP_TRY(hipEventRecord(h->ev_k1u[0], st));
-      const dim3 rgrid(grid_for(h->B, u.G)), rblock(K1U_THREADS);
-      if (u.pack10) hipLaunchKernelGGL(k_rollout_tmpl_stream<true>, rgrid, rblock, h->k1u_lds, st, t, u, n, d_rsum, d_last, s0 > 0 ? 1 : 0);
-      else hipLaunchKernelGGL(k_rollout_tmpl_stream<false>, rgrid, rblock, h->k1u_lds, st, t, u, n, d_rsum, d_last, s0 > 0 ? 1 : 0);
-      if (last) HIP_TRY(hipEventRecord(h->ev_k1u[1], st));
-      if (ov) {
-        HIP_TRY(hipEventRecord(h->ev_trace[i], st));
-        HIP_TRY(hipStreamWaitEvent(h->aux_stream, h->ev_trace[i], 0));
-        if (last) HIP_TRY(hipEventRecord(h->ev_k1u[3], h->aux_stream));
-        const dim3 hgrid(grid_for(h->B, 32)), hblock(512);
-        if (u.pack10) hipLaunchKernelGGL((k_trace_hist<32, 512, true>), hgrid, hblock, hist_lds, h->aux_stream, t, u.trace, u.seg_resets, n, u.code_shift);
-        else hipLaunchKernelGGL((k_trace_hist<32, 512, false>), hgrid, hblock, hist_lds, h->aux_stream, t, u.trace, u.seg_resets, n, u.code_shift);
-        if (last) HIP_TRY(hipEventRecord(h->ev_k1u[4], h->aux_stream));
-        HIP_TRY(hipEventRecord(h->ev_hist[i], h->aux_stream));
-        h->ev_hist_used[i] = true;
-        h->k1u_pending = true;
-        h->k1u_seq++;
-      } else {
-        const dim3 hgrid(grid_for(h->B, 64)), hblock(1024);
-        if (u.pack10) hipLaunchKernelGGL((k_trace_hist<64, 1024, true>), hgrid, hblock, hist_lds, st, t, u.trace, u.seg_resets, n, u.code_shift);
-        else hipLaunchKernelGGL((k_trace_hist<64, 1024, false>), hgrid, hblock, hist_lds, st, t, u.trace, u.seg_resets, n, u.code_shift);
-        if (last) HIP_TRY(hipEventRecord(h->ev_k1u[2], st));
-      }
-    }
-    h->k1u_last_overlap = ov;
-    HIP_TRY(hipGetLastError());
-    return CMDP_OK;
-  }
-  if (lds_eligible && h->tmpl_ok && (h->rollout_kernel == 4 || (h->rollout_kernel == 0 && h->tmpl_auto && n_steps >= 64))) {
-    if (int rc = set_lds(k_rollout_tmpl, h->tmpl_lds)) return rc;
-    hipLaunchKernelGGL(k_rollout_tmpl, dim3(grid_for(h->B, h->tmpl_plan.G)), dim3(K1T_THREADS), h->tmpl_lds, st, t, h->tmpl_plan,
-                       n_steps, d_rsum, d_last);
-    HIP_TRY(hipGetLastError());
-    return CMDP_OK;
-  }
-  if (lds_eligible && (h->rollout_kernel == 2 || (h->rollout_kernel == 0 && n_steps >= 64))) {
-    const dim3 lgrid(grid_for(h->B, h->lds_plan.G)), lblock(K1L_THREADS);
-    if (h->lds_plan.pipe) {
-      if (int rc = set_lds(k_rollout_pipe, h->lds_bytes)) return rc;
-      hipLaunchKernelGGL(k_rollout_pipe, lgrid, dim3(K1P_THREADS), h->lds_bytes, st, t, h->lds_plan, n_steps, d_rsum, d_last);
-    } else if (h->lds_plan.code_shift) {
-      if (int rc = set_lds(k_rollout_lds<true>, h->lds_bytes)) return rc;
-      hipLaunchKernelGGL(k_rollout_lds<true>, lgrid, lblock, h->lds_bytes, st, t, h->lds_plan, n_steps, d_rsum, d_last);
-    } else {
-      if (int rc = set_lds(k_rollout_lds<false>, h->lds_bytes)) return rc;
-      hipLaunchKernelGGL(k_rollout_lds<false>, lgrid, lblock, h->lds_bytes, st, t, h->lds_plan, n_steps, d_rsum, d_last);
-    }
-    HIP_TRY(hipGetLastError());
-    return CMDP_OK;
-  }
-  const bool k1s_eligible = h->k1s_ok && policy == CMDP_POLICY_RANDOM && !trace;
-  if (h->rollout_kernel == 3 && !k1s_eligible)
+  if (rk == 3 && !k1s)
     return fail(CMDP_ERR_UNSUPPORTED, "the LDS-resident stochastic rollout K1S needs Philox mode, the random policy, no trace, equal "
                                       "state counts, <= 16 entries per row and <= 16 distinct successors per state, <= 64 "
                                       "cumulative-probability patterns, deterministic rewards that depend on the successor or on "
@@ -1652,38 +1419,269 @@ static int launch_rollout(cmdp_t* h, int policy, const int8_t* d_actions, int64_
   // (profiles/r03_k1s_walkers.txt); the model is kept for batches where few instances fit a CU.
   const double k1_rate = (double)h->B * 2.5e5 / (1.0 + (double)h->B / 4.0e4);
   const double k1s_rate = (double)h->cus * (double)h->k1s.G / 450e-9;
-  const bool k1s_pays = k1_rate < 1.1 * k1s_rate;
-  if (k1s_eligible && (h->rollout_kernel == 3 || (h->rollout_kernel == 0 && n_steps >= 64 && k1s_pays))) {
-    if (int rc = set_lds(k_rollout_stoch, h->k1s_bytes)) return rc;
-    hipLaunchKernelGGL(k_rollout_stoch, dim3(grid_for(h->B, h->k1s.G)), dim3(K1S_THREADS), h->k1s_bytes, st, t, h->k1s, n_steps,
-                       d_rsum, d_last);
-    HIP_TRY(hipGetLastError());
-    return CMDP_OK;
+  if (lds && h->k1e_ok && n_steps > 0 && (rk == 6 || wide)) *out = K::K1E;
+  else if (lds && h->k1u_ok && (rk == 5 || (wide && h->k1u_auto))) *out = K::K1U;
+  else if (lds && h->tmpl_ok && (rk == 4 || (wide && h->tmpl_auto))) *out = K::K1T;
+  else if (lds && (rk == 2 || wide)) *out = h->lds_plan.pipe ? K::K1P : K::K1L;
+  else if (k1s && (rk == 3 || (wide && k1_rate < 1.1 * k1s_rate))) *out = K::K1S;
+  return CMDP_OK;
+}
+
+// K1E / K1U: no device memory for the workspace of a launch's first segment (nothing enqueued yet)
+constexpr int kNoWorkspace = 1;
+
+// K1E: per segment of <= K1E_SEG transitions (16-bit counts in the table dwords; the code buffer) the walk kernel, then the
+// reward scan over the code words it left in HBM.  The walk accumulates DEPARTURE counts over launches (cmdp_k1e.h), which
+// k1e_settle folds into the visit counters before any other kernel or read.
+static int launch_k1e(cmdp_t* h, const RolloutCall& c) {
+  hipStream_t st = h->stream; EnvTables t = h->env();
+  if (!h->ev_time[0])   // (timestamps only: no host-visibility cache flush per launch)
+    for (int i = 0; i < 5; ++i) HIP_TRY(hipEventCreateWithFlags(&h->ev_time[i], hipEventDisableSystemFence));
+  K1ePlan e = h->k1e;
+  if (!h->d_k1e_dep.p) {
+    const size_t nd = (size_t)grid_for(h->B, K1E_NI) * (size_t)e.gdw;
+    HIP_TRY(h->d_k1e_dep.alloc(nd));
+    HIP_TRY(h->d_k1e_dep.zero(st));
+    HIP_TRY(h->d_k1e_dep_res.alloc(h->B));
+    HIP_TRY(h->d_k1e_dep_res.zero(st));
+    HIP_TRY(h->d_vis_ovf.alloc(1));
+    HIP_TRY(h->d_vis_ovf.zero(st));
   }
-#define ROLL(P, TR, BT) \
-  hipLaunchKernelGGL((k_rollout<P, TR, BT>), grid, block, 0, st, t, d_actions, n_steps, d_rsum, d_last, d_tobs, d_trew, d_ttype)
-  const bool bt = h->sample_beta;
-  if (policy == CMDP_POLICY_RANDOM) {
-    if (trace) { if (bt) ROLL(0, true, true); else ROLL(0, true, false); }
-    else { if (bt) ROLL(0, false, true); else ROLL(0, false, false); }
-  } else {
-    if (trace) { if (bt) ROLL(1, true, true); else ROLL(1, true, false); }
-    else { if (bt) ROLL(1, false, true); else ROLL(1, false, false); }
+  if (h->k1e_pending_steps + c.n > 0x7fff0000LL) { if (int rc = k1e_fold(h)) return rc; }   // the departure image is int32
+  e.dep = h->d_k1e_dep.p;
+  e.dep_res = h->d_k1e_dep_res.p;
+  // The reward scan of a segment runs on the second stream under the walk of the next segment / launch (two sets of code
+  // buffers): it is one wavefront per SIMD of sequential sums, the walk fills the rest of the chip (CMDP_K1E_OVERLAP=0: one
+  // stream).  cmdp_rollout / cmdp_synchronize / every call that reads the sums waits for it.
+  static const int ov_env = std::getenv("CMDP_K1E_OVERLAP") ? std::atoi(std::getenv("CMDP_K1E_OVERLAP")) : 1;
+  const bool ov = ov_env != 0;
+  if (ov && !h->aux.stream) HIP_TRY(hipStreamCreateWithFlags(&h->aux.stream, hipStreamNonBlocking));
+  if (ov && !h->aux.walk[0])
+    for (int i = 0; i < 2; ++i) {
+      HIP_TRY(hipEventCreateWithFlags(&h->aux.walk[i], hipEventDisableTiming | hipEventDisableSystemFence));
+      HIP_TRY(hipEventCreateWithFlags(&h->aux.scan[i], hipEventDisableTiming | hipEventDisableSystemFence));
+    }
+  if (!ov) { if (int rc = k1e_scan_join(h)) return rc; }
+  // segment length: the code words of a segment (12 bytes per episode chunk and instance, two sets) stay within ~1.5 GB
+  const int64_t budget_words = std::max<int64_t>(4, (int64_t)((768ll << 20) / (12 * (int64_t)h->B * e.nch)));
+  const int64_t seg = std::max<int64_t>(e.H, std::min<int64_t>(K1E_SEG, (budget_words - 2) * e.H));
+  const int64_t epi_cap = k1e_max_episodes(std::min<int64_t>(c.n, seg), e.H);
+  const size_t need = (size_t)epi_cap * (size_t)e.nch * (size_t)h->B;
+  if (h->d_k1e_h0.n < (size_t)h->B) HIP_TRY(h->d_k1e_h0.alloc(h->B));
+  if (h->d_k1e_h0b.n < (size_t)h->B) HIP_TRY(h->d_k1e_h0b.alloc(h->B));
+  if (int rc = set_lds(k_rollout_epi<true>, h->k1e_lds)) return rc;
+  if (int rc = set_lds(k_rollout_epi<false>, h->k1e_lds)) return rc;
+  for (int64_t s0 = 0; s0 < c.n; s0 += seg) {
+    const int64_t n = std::min<int64_t>(seg, c.n - s0);
+    const int i = ov ? (int)(h->aux.seq & 1) : 0;
+    if (h->d_k1e_codes[i].n < need || h->d_k1e_cnts[i].n < need) {
+      if (h->aux.stream) HIP_TRY(hipStreamSynchronize(h->aux.stream));   // a scan may still read the buffers
+      if (h->d_k1e_codes[i].alloc(need) != hipSuccess || h->d_k1e_cnts[i].alloc(need) != hipSuccess) {
+        // no room for the code words (12 bytes per episode and instance): possible before the first segment only (the
+        // buffers never shrink)
+        (void)hipGetLastError();
+        if (s0 > 0) return fail(CMDP_ERR_HIP, "K1E: out of device memory for the code words of a later segment");
+        h->d_k1e_codes[i].release();
+        h->d_k1e_cnts[i].release();
+        return fail(kNoWorkspace, "K1E: out of device memory for %zu code words", need);
+      }
+    }
+    e.codes = h->d_k1e_codes[i].p;
+    e.cnts = h->d_k1e_cnts[i].p;
+    e.seg_h0 = i ? h->d_k1e_h0b.p : h->d_k1e_h0.p;
+    e.n_pass = (int)((k1e_max_episodes(n, e.H) + K1E_EPP - 1) / K1E_EPP);
+    if (ov && h->aux.used[i]) HIP_TRY(hipStreamWaitEvent(st, h->aux.scan[i], 0));   // its last scan has read this set
+    const bool last = s0 + seg >= c.n;
+    if (last) HIP_TRY(hipEventRecord(h->ev_time[0], st));
+    // one workgroup per CU (the tables take the CU's LDS), each walking its groups one after the other with the next
+    // group's table image in flight under the walk; CMDP_K1E_GRID = workgroups (timing experiments; any value is correct)
+    int k1e_grid = std::min(grid_for(h->B, K1E_NI), h->cus);
+    if (const char* gs = std::getenv("CMDP_K1E_GRID")) k1e_grid = std::max(1, std::min(grid_for(h->B, K1E_NI), std::atoi(gs)));
+    if (e.n_codes <= 3) hipLaunchKernelGGL(k_rollout_epi<true>, dim3(k1e_grid), dim3(K1E_THREADS), h->k1e_lds, st, t, e, (int)n, c.last);
+    else hipLaunchKernelGGL(k_rollout_epi<false>, dim3(k1e_grid), dim3(K1E_THREADS), h->k1e_lds, st, t, e, (int)n, c.last);
+    if (last) HIP_TRY(hipEventRecord(h->ev_time[1], st));
+    if (ov) {
+      HIP_TRY(hipEventRecord(h->aux.walk[i], st));
+      HIP_TRY(hipStreamWaitEvent(h->aux.stream, h->aux.walk[i], 0));
+      if (last) HIP_TRY(hipEventRecord(h->ev_time[3], h->aux.stream));
+      hipLaunchKernelGGL(k_reward_scan, dim3(grid_for(h->B, K1R_THREADS)), dim3(K1R_THREADS), 0, h->aux.stream, t, e, n, c.rsum, s0 > 0 ? 1 : 0);
+      if (last) HIP_TRY(hipEventRecord(h->ev_time[4], h->aux.stream));
+      HIP_TRY(hipEventRecord(h->aux.scan[i], h->aux.stream));
+      h->aux.used[i] = true;
+      h->aux.pending = true;
+      h->aux.seq++;
+    } else {
+      hipLaunchKernelGGL(k_reward_scan, dim3(grid_for(h->B, K1R_THREADS)), dim3(K1R_THREADS), 0, st, t, e, n, c.rsum, s0 > 0 ? 1 : 0);
+      if (last) HIP_TRY(hipEventRecord(h->ev_time[2], st));
+    }
   }
-#undef ROLL
+  h->ev_time_aux = ov;
+  h->k1e_pending = true;
+  h->k1e_pending_steps += c.n;
   HIP_TRY(hipGetLastError());
   return CMDP_OK;
 }
 
+// K1U: per segment of <= K1U_SEG transitions the chain kernel (trace -> HBM), then the histogram of that trace
+static int launch_k1u(cmdp_t* h, const RolloutCall& c) {
+  hipStream_t st = h->stream; EnvTables t = h->env();
+  if (!h->ev_time[0])   // (timestamps only: no host-visibility cache flush per launch)
+    for (int i = 0; i < 5; ++i) HIP_TRY(hipEventCreateWithFlags(&h->ev_time[i], hipEventDisableSystemFence));
+  K1uPlan u = h->k1u;
+  const int epp = K1U_EPP(u.pack10);
+  const size_t need = (size_t)((std::min<int64_t>(c.n, K1U_SEG) + epp - 1) / epp) * (size_t)h->B;
+  const size_t hist_lds = k1h_lds_bytes(h->max_S, 64);
+  if (int rc = u.pack10 ? set_lds(k_rollout_tmpl_stream<true>, h->k1u_lds) : set_lds(k_rollout_tmpl_stream<false>, h->k1u_lds)) return rc;
+  if (int rc = u.pack10 ? set_lds(k_trace_hist<64, 1024, true>, hist_lds) : set_lds(k_trace_hist<64, 1024, false>, hist_lds)) return rc;
+  if (h->d_k1u_trace.n < need && h->d_k1u_trace.alloc(need) != hipSuccess) {
+    // no room for the trace (16 bytes per 8-12 transitions and instance; every segment of a launch uses the one buffer)
+    (void)hipGetLastError();
+    h->d_k1u_trace.release();
+    return fail(kNoWorkspace, "K1U: out of device memory for a trace of %zu pieces", need);
+  }
+  if (h->d_k1u_resets.n < (size_t)h->B) HIP_TRY(h->d_k1u_resets.alloc(h->B));
+  u.trace = h->d_k1u_trace.p; u.seg_resets = h->d_k1u_resets.p;
+  const dim3 rgrid(grid_for(h->B, u.G)), rblock(K1U_THREADS), hgrid(grid_for(h->B, 64)), hblock(1024);
+  for (int64_t s0 = 0; s0 < c.n; s0 += K1U_SEG) {
+    const int64_t n = std::min<int64_t>(K1U_SEG, c.n - s0);
+    const bool last = s0 + K1U_SEG >= c.n;
+    if (last) HIP_TRY(hipEventRecord(h->ev_time[0], st));
+    if (u.pack10) hipLaunchKernelGGL(k_rollout_tmpl_stream<true>, rgrid, rblock, h->k1u_lds, st, t, u, n, c.rsum, c.last, s0 > 0 ? 1 : 0);
+    else hipLaunchKernelGGL(k_rollout_tmpl_stream<false>, rgrid, rblock, h->k1u_lds, st, t, u, n, c.rsum, c.last, s0 > 0 ? 1 : 0);
+    if (last) HIP_TRY(hipEventRecord(h->ev_time[1], st));
+    if (u.pack10) hipLaunchKernelGGL((k_trace_hist<64, 1024, true>), hgrid, hblock, hist_lds, st, t, u.trace, u.seg_resets, n, u.code_shift);
+    else hipLaunchKernelGGL((k_trace_hist<64, 1024, false>), hgrid, hblock, hist_lds, st, t, u.trace, u.seg_resets, n, u.code_shift);
+    if (last) HIP_TRY(hipEventRecord(h->ev_time[2], st));
+  }
+  h->ev_time_aux = false;
+  HIP_TRY(hipGetLastError());
+  return CMDP_OK;
+}
+
+static int launch_k1t(cmdp_t* h, const RolloutCall& c) {
+  if (int rc = set_lds(k_rollout_tmpl, h->tmpl_lds)) return rc;
+  hipLaunchKernelGGL(k_rollout_tmpl, dim3(grid_for(h->B, h->tmpl_plan.G)), dim3(K1T_THREADS), h->tmpl_lds, h->stream, h->env(),
+                     h->tmpl_plan, c.n, c.rsum, c.last);
+  HIP_TRY(hipGetLastError());
+  return CMDP_OK;
+}
+
+static int launch_k1lp(cmdp_t* h, const RolloutCall& c) {
+  hipStream_t st = h->stream; EnvTables t = h->env();
+  const dim3 lgrid(grid_for(h->B, h->lds_plan.G)), lblock(K1L_THREADS);
+  if (h->lds_plan.pipe) {
+    if (int rc = set_lds(k_rollout_pipe, h->lds_bytes)) return rc;
+    hipLaunchKernelGGL(k_rollout_pipe, lgrid, dim3(K1P_THREADS), h->lds_bytes, st, t, h->lds_plan, c.n, c.rsum, c.last);
+  } else if (h->lds_plan.code_shift) {
+    if (int rc = set_lds(k_rollout_lds<true>, h->lds_bytes)) return rc;
+    hipLaunchKernelGGL(k_rollout_lds<true>, lgrid, lblock, h->lds_bytes, st, t, h->lds_plan, c.n, c.rsum, c.last);
+  } else {
+    if (int rc = set_lds(k_rollout_lds<false>, h->lds_bytes)) return rc;
+    hipLaunchKernelGGL(k_rollout_lds<false>, lgrid, lblock, h->lds_bytes, st, t, h->lds_plan, c.n, c.rsum, c.last);
+  }
+  HIP_TRY(hipGetLastError());
+  return CMDP_OK;
+}
+
+static int launch_k1s(cmdp_t* h, const RolloutCall& c) {
+  if (int rc = set_lds(k_rollout_stoch, h->k1s_bytes)) return rc;
+  hipLaunchKernelGGL(k_rollout_stoch, dim3(grid_for(h->B, h->k1s.G)), dim3(K1S_THREADS), h->k1s_bytes, h->stream, h->env(), h->k1s,
+                     c.n, c.rsum, c.last);
+  HIP_TRY(hipGetLastError());
+  return CMDP_OK;
+}
+
+static int launch_k1d(cmdp_t* h, const RolloutCall& c) {
+  hipStream_t st = h->stream; EnvTables t = h->env();
+  DenseArgs dn{h->d_dense.p, h->dense_spad};
+  // two instances per wavefront (software-pipelined: one row in flight while the other is scanned) when the row fits
+  // the registers twice; CMDP_K1D_NI = 1 / 2 overrides (tuning aid)
+  static const int ni_env = std::getenv("CMDP_K1D_NI") ? std::atoi(std::getenv("CMDP_K1D_NI")) : 0;
+  const int nv = h->dense_spad / 256;
+  const int ni = ni_env ? ni_env : (nv <= 4 ? 2 : 1);
+  const dim3 dgrid(grid_for(h->B, 4 * ni));
+#define DENSE_LAUNCH(P, NV, BT, NI) \
+  hipLaunchKernelGGL((k_rollout_dense<P, NV, BT, NI>), dgrid, dim3(256), 0, st, t, dn, c.actions, c.n, c.rsum, c.last)
+#define DENSE_CASE(NV, NI)                                                                        \
+  if (nv == NV && ni == NI) {                                                                     \
+    if (c.policy == CMDP_POLICY_RANDOM) { if (h->sample_beta) DENSE_LAUNCH(0, NV, true, NI); else DENSE_LAUNCH(0, NV, false, NI); } \
+    else { if (h->sample_beta) DENSE_LAUNCH(1, NV, true, NI); else DENSE_LAUNCH(1, NV, false, NI); }      \
+  } else
+  DENSE_CASE(1, 1) DENSE_CASE(2, 1) DENSE_CASE(3, 1) DENSE_CASE(4, 1) DENSE_CASE(6, 1) DENSE_CASE(8, 1) DENSE_CASE(12, 1)
+  DENSE_CASE(16, 1) DENSE_CASE(1, 2) DENSE_CASE(2, 2) DENSE_CASE(3, 2) DENSE_CASE(4, 2)
+  { return fail(CMDP_ERR_UNSUPPORTED, "dense layout: no kernel for a row stride of %d floats, %d instances per wavefront", h->dense_spad, ni); }
+#undef DENSE_CASE
+#undef DENSE_LAUNCH
+  HIP_TRY(hipGetLastError());
+  return CMDP_OK;
+}
+
+// K1, lane = instance, tables in HBM: the reward-cache form (park protocol, every policy), the greedy-Q form, the plain one
+static int launch_k1(cmdp_t* h, RolloutKernel k, const RolloutCall& c) {
+  hipStream_t st = h->stream; EnvTables t = h->env();
+  const dim3 grid(grid_for(h->B, 256)), block(256);
+  const bool trace = c.trace(), bt = h->sample_beta;
+  if (k == RolloutKernel::K1_REWARD_CACHE) {
+    const RewardCache rc = h->rcache();
+#define ROLL_RC(P, TR) \
+  hipLaunchKernelGGL((k_rollout<P, TR, false, true>), grid, block, 0, st, t, c.actions, c.n, c.rsum, c.last, c.tobs, c.trew, c.ttype, c.q, rc, c.resume)
+    if (c.policy == CMDP_POLICY_RANDOM) { if (trace) ROLL_RC(0, true); else ROLL_RC(0, false); }
+    else if (c.policy == CMDP_POLICY_HOST_ACTIONS) { if (trace) ROLL_RC(1, true); else ROLL_RC(1, false); }
+    else { if (trace) ROLL_RC(2, true); else ROLL_RC(2, false); }
+#undef ROLL_RC
+  } else if (k == RolloutKernel::K1_GREEDY) {
+    if (trace) hipLaunchKernelGGL((k_rollout<2, true, true>), grid, block, 0, st, t, c.actions, c.n, c.rsum, c.last, c.tobs, c.trew, c.ttype, c.q);
+    else hipLaunchKernelGGL((k_rollout<2, false, true>), grid, block, 0, st, t, c.actions, c.n, c.rsum, c.last, c.tobs, c.trew, c.ttype, c.q);
+  } else {
+#define ROLL(P, TR, BT) \
+  hipLaunchKernelGGL((k_rollout<P, TR, BT>), grid, block, 0, st, t, c.actions, c.n, c.rsum, c.last, c.tobs, c.trew, c.ttype)
+    if (c.policy == CMDP_POLICY_RANDOM) {
+      if (trace) { if (bt) ROLL(0, true, true); else ROLL(0, true, false); }
+      else { if (bt) ROLL(0, false, true); else ROLL(0, false, false); }
+    } else {
+      if (trace) { if (bt) ROLL(1, true, true); else ROLL(1, true, false); }
+      else { if (bt) ROLL(1, false, true); else ROLL(1, false, false); }
+    }
+#undef ROLL
+  }
+  HIP_TRY(hipGetLastError());
+  return CMDP_OK;
+}
+
+// Pick, check the visit bound, settle what K1E left on the second stream and in its departure image (every other kernel
+// reads and writes the sums and counters itself), launch.  The caller commits the visit bound.
+static int launch_rollout(cmdp_t* h, const RolloutCall& c) {
+  using K = RolloutKernel;
+  for (;;) {
+    K k = K::K1;
+    if (int rc = pick_rollout(h, c.policy, c.trace(), c.n, &k)) return rc;
+    if (int rc = visits_check(h, c.n)) return rc;
+    if (k != K::K1E) { if (int rc = k1e_settle(h)) return rc; }
+    int rc = CMDP_OK;
+    switch (k) {
+      case K::K1E: rc = launch_k1e(h, c); break;
+      case K::K1U: rc = launch_k1u(h, c); break;
+      case K::K1T: rc = launch_k1t(h, c); break;
+      case K::K1L: case K::K1P: rc = launch_k1lp(h, c); break;
+      case K::K1S: rc = launch_k1s(h, c); break;
+      case K::K1D: rc = launch_k1d(h, c); break;
+      default: rc = launch_k1(h, k, c); break;
+    }
+    if (rc != kNoWorkspace) return rc;
+    // the chain kernels need no workspace: this handle takes them from now on, unless K1E / K1U was forced
+    (k == K::K1E ? h->k1e_ok : h->k1u_ok) = false;
+    if (h->rollout_kernel) return CMDP_ERR_HIP;   // (the launcher has said why)
+  }
+}
+
 int cmdp_rollout(cmdp_t* h, int policy, const void* policy_arg, int64_t n_steps, int32_t* last_obs, double* reward_sum,
                  int32_t* trace_obs, double* trace_reward, uint8_t* trace_type) {
-  if (int rc = bind(h, false)) return rc;   // (launch_rollout joins what the kernel it takes needs joined)
+  if (int rc = bind(h, false)) return rc;   // (launch_rollout settles K1E unless it takes K1E again)
   if (!h->has_env) return fail(CMDP_ERR_INVALID, "handle was created without the sampler half");
   if (n_steps < 0) return fail(CMDP_ERR_INVALID, "n_steps < 0");
   if (policy != CMDP_POLICY_RANDOM && policy != CMDP_POLICY_HOST_ACTIONS && policy != CMDP_POLICY_GREEDY_Q)
     return fail(CMDP_ERR_INVALID, "policy");
   if (policy != CMDP_POLICY_RANDOM && !policy_arg && n_steps > 0) return fail(CMDP_ERR_INVALID, "policy_arg missing");
-  if (int rc = visits_room(h, n_steps)) return rc;
   bool any = false;
   if (int rc = any_needs_reset(h, &any)) return rc;
   if (any) return fail(CMDP_ERR_NEEDS_RESET, "rollout() on an instance that needs reset()");
@@ -1710,11 +1708,10 @@ int cmdp_rollout(cmdp_t* h, int policy, const void* policy_arg, int64_t n_steps,
   if (trace_reward && h->d_tr_rew.n < NB) HIP_TRY(h->d_tr_rew.alloc(NB));
   if (trace_type && h->d_tr_type.n < NB) HIP_TRY(h->d_tr_type.alloc(NB));
   auto launch = [&](int resume) -> int {
-    return launch_rollout(h, policy, d_act, n_steps, h->d_rsum.p, h->d_last_obs.p, trace_obs ? h->d_tr_obs.p : nullptr,
-                          trace_reward ? h->d_tr_rew.p : nullptr, trace_type ? h->d_tr_type.p : nullptr, d_q, resume);
+    return launch_rollout(h, {policy, d_act, d_q, n_steps, h->d_rsum.p, h->d_last_obs.p, trace_obs ? h->d_tr_obs.p : nullptr,
+                              trace_reward ? h->d_tr_rew.p : nullptr, trace_type ? h->d_tr_type.p : nullptr, resume});
   };
-  if (h->reward_cache) { if (int rc = rc_drive(h, launch)) return rc; }
-  else if (int rc = launch(0)) return rc;
+  if (int rc = visits_commit(h, n_steps, h->reward_cache ? rc_drive(h, launch) : launch(0))) return rc;
   if (int rc = k1e_scan_join(h)) return rc;   // (K1E: the sums of the last segment come from the second stream)
   if (last_obs) HIP_TRY(hipMemcpyAsync(last_obs, h->d_last_obs.p, sizeof(int32_t) * B, hipMemcpyDeviceToHost, st));
   if (reward_sum) HIP_TRY(hipMemcpyAsync(reward_sum, h->d_rsum.p, sizeof(double) * B, hipMemcpyDeviceToHost, st));
@@ -1726,11 +1723,10 @@ int cmdp_rollout(cmdp_t* h, int policy, const void* policy_arg, int64_t n_steps,
 }
 
 int cmdp_rollout_async(cmdp_t* h, int policy, int64_t n_steps) {
-  if (int rc = bind(h, false)) return rc;   // K1U's histogram of the previous launch may still run (launch_rollout joins otherwise)
+  if (int rc = bind(h, false)) return rc;   // (launch_rollout settles K1E unless it takes K1E again)
   if (!h->has_env) return fail(CMDP_ERR_INVALID, "handle was created without the sampler half");
   if (policy != CMDP_POLICY_RANDOM) return fail(CMDP_ERR_INVALID, "rollout_async supports CMDP_POLICY_RANDOM only");
   if (n_steps < 0) return fail(CMDP_ERR_INVALID, "n_steps < 0");
-  if (int rc = visits_room(h, n_steps)) return rc;
   if (!h->known_reset) {  // one 4-byte read-back on the first call after create / cmdp_step, none afterwards
     bool any = false;
     if (int rc = any_needs_reset(h, &any)) return rc;
@@ -1739,11 +1735,11 @@ int cmdp_rollout_async(cmdp_t* h, int policy, int64_t n_steps) {
   }
   if (h->d_rsum.n < (size_t)h->B) HIP_TRY(h->d_rsum.alloc(h->B));
   if (h->d_last_obs.n < (size_t)h->B) HIP_TRY(h->d_last_obs.alloc(h->B));
-  if (h->reward_cache)  // the park / fill / relaunch loop needs the host: synchronous in this mode
-    return rc_drive(h, [&](int resume) -> int {
-      return launch_rollout(h, policy, nullptr, n_steps, h->d_rsum.p, h->d_last_obs.p, nullptr, nullptr, nullptr, nullptr, resume);
-    });
-  return launch_rollout(h, policy, nullptr, n_steps, h->d_rsum.p, h->d_last_obs.p, nullptr, nullptr, nullptr);
+  auto launch = [&](int resume) -> int {
+    return launch_rollout(h, {policy, nullptr, nullptr, n_steps, h->d_rsum.p, h->d_last_obs.p, nullptr, nullptr, nullptr, resume});
+  };
+  // (reward caches: the park / fill / relaunch loop needs the host -- synchronous in this mode)
+  return visits_commit(h, n_steps, h->reward_cache ? rc_drive(h, launch) : launch(0));
 }
 
 int cmdp_set_option(cmdp_t* h, int option, int64_t value) {
@@ -1792,19 +1788,23 @@ int cmdp_set_option(cmdp_t* h, int option, int64_t value) {
 
 int cmdp_lds_plan(cmdp_t* h, int32_t plan[4]) {
   if (!h || !plan) return fail(CMDP_ERR_INVALID, "bad argument");
+  // what a launch of the random policy without trace and of >= 64 transitions takes; when that is no LDS-resident kernel,
+  // the one the batch is eligible for
+  RolloutKernel k = RolloutKernel::K1;
+  const std::string err = g_err;   // (a forced kernel the batch cannot take is no error of this call)
+  if (pick_rollout(h, CMDP_POLICY_RANDOM, false, 64, &k) != CMDP_OK) k = RolloutKernel::K1;
+  g_err = err;
+  const int32_t k1e[3] = {5, K1E_NI, K1E_EPP}, k1u[3] = {4, h->k1u.G, h->k1u.ch}, k1t[3] = {3, h->tmpl_plan.G, h->tmpl_plan.ch},
+                k1lp[3] = {h->lds_plan.pipe, h->lds_plan.G, h->lds_plan.ch}, k1s[3] = {2, h->k1s.G, h->k1s.ch}, none[3] = {0, 0, 0};
+  const int32_t* p = k == RolloutKernel::K1E ? k1e : k == RolloutKernel::K1U ? k1u : k == RolloutKernel::K1T ? k1t
+                     : h->lds_ok ? k1lp : h->k1s_ok ? k1s : none;   // (K1L / K1P / K1S: the batch's only LDS-resident kernel)
   plan[0] = (h->lds_ok || h->k1s_ok) ? 1 : 0;
-  const bool k1e = h->lds_ok && h->k1e_ok && (h->rollout_kernel == 6 || h->rollout_kernel == 0);
-  const bool k1u = !k1e && h->lds_ok && h->k1u_ok && (h->rollout_kernel == 5 || (h->rollout_kernel == 0 && h->k1u_auto));
-  const bool k1t = !k1e && !k1u && h->lds_ok && h->tmpl_ok && (h->rollout_kernel == 4 || (h->rollout_kernel == 0 && h->tmpl_auto));   // what a launch takes
-  plan[1] = k1e ? 5 : k1u ? 4 : k1t ? 3 : (h->lds_ok ? h->lds_plan.pipe : (h->k1s_ok ? 2 : 0));
-  plan[2] = k1e ? K1E_NI : k1u ? h->k1u.G : k1t ? h->tmpl_plan.G : (h->lds_ok ? h->lds_plan.G : (h->k1s_ok ? h->k1s.G : 0));
-  plan[3] = k1e ? K1E_EPP : k1u ? h->k1u.ch : k1t ? h->tmpl_plan.ch : (h->lds_ok ? h->lds_plan.ch : (h->k1s_ok ? h->k1s.ch : 0));
+  std::copy(p, p + 3, plan + 1);
   return CMDP_OK;
 }
 
 int cmdp_synchronize(cmdp_t* h) {
   if (int rc = bind(h, false)) return rc;   // (the departure image of K1E stays as it is: nothing here reads the counters)
-  if (int rc = k1u_join(h)) return rc;
   if (int rc = k1e_scan_join(h)) return rc;
   HIP_TRY(hipStreamSynchronize(h->stream));
   return CMDP_OK;
@@ -1826,10 +1826,10 @@ int cmdp_stat(cmdp_t* h, int which, double* out) {
     return CMDP_OK;
   }
   if (which == CMDP_STAT_ROLLOUT_KERNEL_MS || which == CMDP_STAT_HIST_KERNEL_MS) {
-    if (!h->ev_k1u[0]) return fail(CMDP_ERR_INVALID, "no streamed-trace rollout (K1U) has run on this handle");
+    if (!h->ev_time[0]) return fail(CMDP_ERR_INVALID, "no streamed-trace (K1U) or episode-parallel (K1E) rollout has run on this handle");
     const bool hist = which == CMDP_STAT_HIST_KERNEL_MS;
-    hipEvent_t e0 = hist ? (h->k1u_last_overlap ? h->ev_k1u[3] : h->ev_k1u[1]) : h->ev_k1u[0];
-    hipEvent_t e1 = hist ? (h->k1u_last_overlap ? h->ev_k1u[4] : h->ev_k1u[2]) : h->ev_k1u[1];
+    hipEvent_t e0 = hist ? (h->ev_time_aux ? h->ev_time[3] : h->ev_time[1]) : h->ev_time[0];
+    hipEvent_t e1 = hist ? (h->ev_time_aux ? h->ev_time[4] : h->ev_time[2]) : h->ev_time[1];
     HIP_TRY(hipEventSynchronize(e1));
     float ms = 0;
     HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
@@ -3724,10 +3724,9 @@ static int ql_launch(cmdp_agent_t* a, int64_t n_steps, const uint8_t* dmask, int
 // the kernel is relaunched); otherwise nothing is synchronised.
 // `cum_host` (nullable): page-locked host array that receives the running reward sums at the end of the launch.
 static int ql_enqueue_run(cmdp_agent_t* a, int64_t n_steps, const uint8_t* dmask, int8_t* d_actions, double* cum_host = nullptr) {
-  if (int rc = visits_room(a->env, n_steps)) return rc;
-  if (a->env->reward_cache)
-    return rc_drive(a->env, [&](int resume) -> int { return ql_launch(a, n_steps, dmask, d_actions, resume, cum_host); });
-  return ql_launch(a, n_steps, dmask, d_actions, 0, cum_host);
+  if (int rc = visits_check(a->env, n_steps)) return rc;
+  auto launch = [&](int resume) -> int { return ql_launch(a, n_steps, dmask, d_actions, resume, cum_host); };
+  return visits_commit(a->env, n_steps, a->env->reward_cache ? rc_drive(a->env, launch) : launch(0));
 }
 
 int cmdp_qlearning_run(cmdp_agent_t* a, int64_t n_steps, const uint8_t* train_mask, int8_t* actions_trace,
@@ -3897,8 +3896,8 @@ int cmdp_qlearning_run_logged(cmdp_agent_t* a, const cmdp_loop_desc* d, int64_t 
     if (!h->ev_row[i]) HIP_TRY(hipEventCreateWithFlags(&h->ev_row[i], hipEventDisableTiming | (block_env ? hipEventBlockingSync : 0)));
   hipStream_t sx = st;
   if (!episodic && pipeline_env) {
-    if (!h->aux_stream) HIP_TRY(hipStreamCreateWithFlags(&h->aux_stream, hipStreamNonBlocking));
-    sx = h->aux_stream;
+    if (!h->aux.stream) HIP_TRY(hipStreamCreateWithFlags(&h->aux.stream, hipStreamNonBlocking));
+    sx = h->aux.stream;
     if (h->d_cur_snap.n < (size_t)B) HIP_TRY(h->d_cur_snap.alloc(B));
   }
   const double atol = episodic ? 1e-4 : 1e-5;

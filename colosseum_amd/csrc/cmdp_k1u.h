@@ -44,7 +44,7 @@ struct K1uPlan {
   const uint16_t* tmpl;
   const uint8_t* swap_bits;
   const double* rvals;
-  uint4* trace;          // [pieces of the segment][B] 8 trace entries each (one of two buffers when the histogram overlaps)
+  uint4* trace;          // [pieces of the segment][B] 8 trace entries each
   int32_t* seg_resets;   // [B] episode resets of the segment (visits of the start state the histogram adds)
 };
 
@@ -269,10 +269,9 @@ __global__ void __launch_bounds__(K1U_THREADS) k_rollout_tmpl_stream(EnvTables t
   if (role == 1 && owner && reward_sum) reward_sum[b] = sum;
 }
 
-// Histogram of a segment's trace: arrival row r = (entry & smask) >> 1 of every transition of the group's G instances.
-// G = 64: lane = instance (119 KB of counters at C2: the kernel has the CU to itself).  G = 32: two lanes per instance on
-// alternating pieces and 60 KB of counters, so that a workgroup fits NEXT TO a resident k_rollout_tmpl_stream workgroup
-// (74 KB at chunk 32) and the histogram of one step runs under the chain of the next (second stream).
+// Histogram of a segment's trace: arrival row r = (entry & smask) >> 1 of every transition of the group's G instances,
+// on the handle's stream after the chain kernel.  Launched with G = 64: lane = instance (119 KB of counters at C2: the
+// kernel has the CU to itself); G < 64 puts 64 / G lanes on alternating pieces of an instance.
 template <int G, int THREADS, bool PACK10>
 __global__ void __launch_bounds__(THREADS) k_trace_hist(EnvTables t, const uint4* __restrict__ trace,
                                                        const int32_t* __restrict__ seg_resets, int64_t n_steps,

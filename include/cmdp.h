@@ -218,8 +218,10 @@ int cmdp_synchronize(cmdp_t* h);
 enum { CMDP_STAT_DP_KERNEL_MS = 1, CMDP_STAT_DP_KERNEL = 2,
        CMDP_STAT_REWARD_FILLS = 3,   /* CMDP_FLAG_REWARD_CACHE: blocks of 5000 samples drawn so far                */
        CMDP_STAT_REWARD_ROUNDS = 4,  /* ... and park / fill / relaunch rounds                                        */
-       CMDP_STAT_ROLLOUT_KERNEL_MS = 5, /* K1U: HIP-event time of k_rollout_tmpl_stream in the last launch (last segment) */
-       CMDP_STAT_HIST_KERNEL_MS = 6,    /* K1U: ... and of its k_trace_hist (on the second stream when overlapped)          */
+       CMDP_STAT_ROLLOUT_KERNEL_MS = 5, /* K1U / K1E: HIP-event time of the rollout kernel (k_rollout_tmpl_stream /
+                                           k_rollout_epi) in the last launch of either (last segment)                       */
+       CMDP_STAT_HIST_KERNEL_MS = 6,    /* ... and of its second kernel (k_trace_hist / k_reward_scan, the latter on the
+                                           second stream unless CMDP_K1E_OVERLAP=0)                                         */
        CMDP_STAT_CHAIN_FAST_INSTANCES = 7 /* instances (evaluated or masked out) the last average-reward call did NOT hand to K9:
                                              those K9F solved (irreducible chain, fill-reducing elimination order)          */,
        CMDP_STAT_REWARD_FILL_MS = 8,   /* CMDP_FLAG_REWARD_CACHE: host wall time spent drawing blocks (all host threads together

@@ -404,6 +404,23 @@ def test_episode_parallel_rollout_interleaved_with_everything_else(need_gpu):
     env.rollout_async(64)
     oracle_rollout(64)
     check("K1E / K1 / K1E", a["reward_sum"] + b_["reward_sum"], oa + ob)
+    # a long asynchronous K1E launch, at once a synchronous one of fewer than 64 transitions (K1): K1 writes the reward
+    # sums the K1E scan on the second stream writes too
+    env.rollout_async(5000)
+    short = env.rollout(10)
+    oracle_rollout(5000)
+    check("K1 right behind an async K1E", short["reward_sum"], oracle_rollout(10))
+    # K1E, the streamed-trace kernel K1U forced on the same handle, K1E again
+    env.rollout_async(2000)
+    oracle_rollout(2000)
+    env.set_rollout_kernel(L.ROLLOUT_LDS_TEMPLATE_STREAM)
+    assert env.lds_plan()["kernel"] == "k_rollout_tmpl_stream"
+    u = env.rollout(3000)
+    ou = oracle_rollout(3000)
+    env.set_rollout_kernel(L.ROLLOUT_AUTO)
+    e2 = env.rollout(1500)
+    oe2 = oracle_rollout(1500)
+    check("K1E / K1U / K1E", u["reward_sum"] + e2["reward_sum"], ou + oe2)
     # counters reset while K1E's image holds counts: they must not come back
     env.rollout_async(3000)
     oracle_rollout(3000)
@@ -440,6 +457,12 @@ def test_visit_counter_overflow_is_refused_not_wrapped(need_gpu):
         for a, b in zip(before, env.state()):
             np.testing.assert_array_equal(a, b)
         np.testing.assert_array_equal(env.visits()[0], vs2)        # nothing was counted
+        env.set_rollout_kernel(L.ROLLOUT_LDS_STOCHASTIC)           # refused calls take no room
+        for _ in range(3):
+            with pytest.raises(L.CmdpError) as ei:
+                env.rollout(100)
+            assert ei.value.code == L.ERR_UNSUPPORTED
+        env.set_rollout_kernel(which)
         env.rollout(100)                                           # this much fits
         vs3, _ = env.visits()
         assert vs3[start] > vs2[start] and vs3.min() >= 0 and vs3[start] <= 2**31 - 1
@@ -450,6 +473,21 @@ def test_visit_counter_overflow_is_refused_not_wrapped(need_gpu):
         env.rollout(5000)                                          # counters cleared: room again
         assert env.visits()[0].reshape(40, -1).sum(1).min() >= 5000
         env.close()
+    # a call refused because an instance needs reset takes no room either: every instance at the end of an episode first
+    # (cmdp_set_visits resets the bound), then exactly room for the reset (2) and 100 transitions (200)
+    env = BatchedMDP(tables=tables, rng_mode=L.RNG_PHILOX, philox_keys=np.arange(40, dtype=np.uint64) + 5)
+    env.reset()
+    while not env.state()[2].all():
+        env.step(np.zeros(40, np.int32), auto_reset=False)
+    vs, vsa = env.visits()
+    vs2 = vs.copy()
+    vs2[int(tables["start_state"][0])] = 2**31 - 1 - 202
+    env.set_visits(vs2, vsa)
+    with pytest.raises(AssertionError, match="needs reset"):     # (CMDP_ERR_NEEDS_RESET: the reference's AssertionError)
+        env.rollout(100)
+    env.reset()
+    env.rollout(100)
+    env.close()
     with pytest.raises(L.CmdpError):                               # values beyond int32 cannot be restored
         env = BatchedMDP(tables=tables, rng_mode=L.RNG_PHILOX)
         bad = np.zeros(int(tables["state_off"][-1]), np.int64)
