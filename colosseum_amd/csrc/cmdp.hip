@@ -26,6 +26,7 @@ extern char** environ;
 #include "cmdp_k1t.h"
 #include "cmdp_k1u.h"
 #include "cmdp_k1e.h"
+#include "cmdp_rollout_plan.h"
 #include "cmdp_agent.h"
 #include "cmdp_chain.h"
 
@@ -49,7 +50,6 @@ int fail(int code, const char* fmt, ...) {
     if (e_ != hipSuccess) return fail(CMDP_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
   } while (0)
 
-constexpr int kLdsBudget = 160 * 1024;  // bytes of LDS one workgroup may claim on gfx950
 constexpr int kDpBlock = 256;
 
 // Device buffer that only grows: hipFree (and often hipMalloc) synchronises the WHOLE device, which would serialise
@@ -301,12 +301,6 @@ int visits_commit(cmdp_t* h, int64_t n_transitions, int rc = CMDP_OK) {
 
 inline int grid_for(int64_t n, int block) { return (int)((n + block - 1) / block); }
 
-// dynamic LDS of a K1L / K1P workgroup of g instances
-size_t k1l_lds_bytes(const LdsPlan& p, int g) {
-  const int rings = p.pipe ? 2 * K1P_ACT_STRIDE(p.ch) + 2 * K1P_TR_STRIDE(p.ch) : 2 * p.ch;
-  return (size_t)K1L_FIXED + (size_t)g * (size_t)(p.slot_bytes + rings);
-}
-
 template <typename K>
 int set_lds(K kernel, size_t bytes) {
   if (bytes > 64 * 1024)
@@ -352,174 +346,367 @@ int bind(cmdp_t* h, bool settle = true) {
 
 }  // namespace
 
-// Host side of K1S (cmdp_k1s.h): compresses the sampler tables of a batch with stochastic dynamics into shared
-// cumulative-probability patterns, per-state successor sets and 4-bit entry codes, and sizes the LDS plan.  Leaves
-// h->k1s_ok false (the batch then takes K1) whenever a limit of the format is exceeded.
-static int build_k1s(cmdp_t* h, const cmdp_desc* d) {
-  const int B = h->B, A = h->A;
-  if (h->rng_mode != CMDP_RNG_PHILOX || h->sample_beta || h->reward_cache || h->layout != CMDP_LAYOUT_CSR) return CMDP_OK;
-  const int64_t S0 = h->max_S;   // slots are sized for the largest instance
-  if (S0 * A >= 65536 || S0 < 1) return CMDP_OK;
-  if (d->sp_rkind)
-    for (int64_t e = 0; e < h->n_entries; ++e)
-      if (d->sp_rkind[e] != 0) return CMDP_OK;   // reward means of Beta entries: K1 reports them
-  const int64_t R = h->n_rows, NS = h->n_states;
-  std::vector<uint16_t> shape((size_t)R, 0);
-  std::vector<uint4> dict;
-  std::map<std::tuple<int, unsigned long long, int>, int> shape_of;
-  std::vector<unsigned long long> words((size_t)R, 0);
-  std::vector<uint8_t> pat_ids((size_t)R, 0);
-  std::vector<double> patterns;
-  std::map<std::vector<uint64_t>, int> pat_of;
-  std::map<uint64_t, int> code_of;
-  std::vector<double> rvals;
-  std::vector<std::vector<int32_t>> sets((size_t)NS);
-  // reward value of every entry -> code
-  std::vector<int> ecode((size_t)h->n_entries);
-  for (int64_t e = 0; e < h->n_entries; ++e) {
-    uint64_t bits;
-    std::memcpy(&bits, &d->sp_reward[e], sizeof bits);
-    auto it = code_of.find(bits);
-    if (it == code_of.end()) {
-      if (rvals.size() == 256) return CMDP_OK;
-      it = code_of.emplace(bits, (int)rvals.size()).first;
-      rvals.push_back(d->sp_reward[e]);
-    }
-    ecode[(size_t)e] = it->second;
+// ---- cmdp_create, step by step ----------------------------------------------------------------------------------------
+// The description's shape; *max_S: the largest instance.
+static int check_desc(const cmdp_desc* d, int* max_S) {
+  if (d->n_instances < 1 || d->n_actions < 1 || d->n_actions > 64 || d->horizon < 0)
+    return fail(CMDP_ERR_INVALID, "n_instances/n_actions/horizon out of range (1 <= A <= 64)");
+  if (d->rng_mode != CMDP_RNG_MT_COMPAT && d->rng_mode != CMDP_RNG_PHILOX) return fail(CMDP_ERR_INVALID, "rng_mode");
+  if (d->layout != CMDP_LAYOUT_CSR && d->layout != CMDP_LAYOUT_DENSE) return fail(CMDP_ERR_INVALID, "layout");
+  if (d->layout == CMDP_LAYOUT_DENSE && (d->rng_mode != CMDP_RNG_PHILOX || !d->sp_ptr || !d->csr_ptr))
+    return fail(CMDP_ERR_INVALID, "CMDP_LAYOUT_DENSE needs CMDP_RNG_PHILOX and both halves of the description "
+                                  "(the float32 rows come from the DP half, rewards and starts from the sampler half)");
+  if (!d->state_off) return fail(CMDP_ERR_INVALID, "state_off is required");
+  const bool has_env = d->sp_ptr != nullptr, has_dp = d->csr_ptr != nullptr;
+  if (!has_env && !has_dp) return fail(CMDP_ERR_INVALID, "neither the sampler half nor the DP half is present");
+  if (has_env && (!d->sp_next || !d->sp_cum || !d->sp_reward || !d->start_off || !d->start_state || !d->start_cum))
+    return fail(CMDP_ERR_INVALID, "sampler half is incomplete");
+  if (has_env && d->rng_mode == CMDP_RNG_MT_COMPAT && (!d->sp_seed || !d->start_seed))
+    return fail(CMDP_ERR_INVALID, "MT_COMPAT needs sp_seed and start_seed");
+  if (has_dp && (!d->csr_col || !d->csr_val || !d->R)) return fail(CMDP_ERR_INVALID, "DP half is incomplete");
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(CMDP_ERR_NO_DEVICE, "no HIP device visible");
+  if (d->state_off[0] != 0) return fail(CMDP_ERR_INVALID, "state_off[0] != 0");
+  *max_S = 0;
+  for (int b = 0; b < d->n_instances; ++b) {
+    const int64_t S = d->state_off[b + 1] - d->state_off[b];
+    if (S < 1 || S > (1 << 28)) return fail(CMDP_ERR_INVALID, "instance %d has %lld states", b, (long long)S);
+    *max_S = std::max<int>(*max_S, (int)S);
   }
-  int U = 1;
-  bool by_state = true, by_row = true;      // is the reward a function of the successor state alone / of the row alone?
-  std::vector<int> rc_state((size_t)NS, -1), rc_row((size_t)R, -1);
-  for (int b = 0; b < B; ++b) {
-    const int64_t so = h->state_off[b], Sb = h->state_off[b + 1] - so;
-    for (int64_t s = 0; s < Sb; ++s) {
-      auto& set = sets[(size_t)(so + s)];
-      for (int a = 0; a < A; ++a) {
-        const int64_t r = (so + s) * A + a;
-        const int64_t lo = d->sp_ptr[r], hi = d->sp_ptr[r + 1];
-        const int n = (int)(hi - lo);
-        if (n < 1 || n > K1S_MAXE) return CMDP_OK;
-        std::vector<uint64_t> key((size_t)n);
-        std::memcpy(key.data(), d->sp_cum + lo, sizeof(double) * (size_t)n);
-        auto it = pat_of.find(key);
-        if (it == pat_of.end()) {
-          if (pat_of.size() == 64) return CMDP_OK;
-          it = pat_of.emplace(key, (int)pat_of.size()).first;
-          for (int k = 0; k < K1S_MAXE; ++k)
-            patterns.push_back(k < n - 1 ? d->sp_cum[lo + k] : std::numeric_limits<double>::infinity());
-          patterns.push_back(d->sp_cum[hi - 1]);
-        }
-        const int pat_id = it->second;
-        unsigned long long word = 0;
-        for (int k = 0; k < n; ++k) {
-          const int32_t nx = d->sp_next[lo + k];
-          int idx = -1;
-          for (size_t j = 0; j < set.size(); ++j)
-            if (set[j] == nx) { idx = (int)j; break; }
-          if (idx < 0) {
-            if (set.size() == 16) return CMDP_OK;
-            idx = (int)set.size();
-            set.push_back(nx);
-          }
-          word |= (unsigned long long)idx << (4 * k);
-          const int c = ecode[(size_t)(lo + k)];
-          if (rc_state[(size_t)(so + nx)] < 0) rc_state[(size_t)(so + nx)] = c;
-          else if (rc_state[(size_t)(so + nx)] != c) by_state = false;
-          if (rc_row[(size_t)r] < 0) rc_row[(size_t)r] = c;
-          else if (rc_row[(size_t)r] != c) by_row = false;
-        }
-        words[(size_t)r] = word;
-        pat_ids[(size_t)r] = (uint8_t)pat_id;
-      }
-      U = std::max(U, (int)set.size());
-    }
-    if (d->start_off[b + 1] - d->start_off[b] > K1S_MAXSTART) return CMDP_OK;
-  }
-  if (!by_state && !by_row) return CMDP_OK;
-  // row shapes: (pattern, word) -- and, when the reward is a function of the row rather than of the successor state, the
-  // row's reward code, so that the shape's dictionary entry carries it
-  for (int64_t r = 0; r < R; ++r) {
-    const int rcd = by_state ? 0 : std::max(0, rc_row[(size_t)r]);
-    const auto key = std::make_tuple((int)pat_ids[(size_t)r], words[(size_t)r], rcd);
-    auto sh = shape_of.find(key);
-    if (sh == shape_of.end()) {
-      if (dict.size() == 65535) return CMDP_OK;
-      sh = shape_of.emplace(key, (int)dict.size()).first;
-      dict.push_back(make_uint4((uint32_t)words[(size_t)r], (uint32_t)(words[(size_t)r] >> 32), (uint32_t)pat_ids[(size_t)r], (uint32_t)rcd));
-    }
-    shape[(size_t)r] = (uint16_t)sh->second;
-  }
-  K1sPlan p{};
-  p.S = (int)S0; p.rows = (int)S0 * A; p.U = U; p.n_pat = (int)pat_of.size(); p.n_codes = (int)rvals.size();
-  p.reward_mode = by_state ? 0 : 1;
-  p.ch = 32;
-  p.n_shapes = (int)dict.size();
-  p.shape_bytes = p.n_shapes <= 256 ? 1 : 2;
-  auto up8 = [](int x) { return (x + 7) & ~7; };
-  p.off_cnt = up8(p.rows * p.shape_bytes);
-  p.off_ovf = up8(p.off_cnt + p.rows);
-  p.off_sets = up8(p.off_ovf + 2 * (K1S_OVF + 2));
-  // reward code of the arrival state in the top four bits of its successor-set entries (no separate look-up on the walk)
-  // when both fit sixteen bits; per-row codes travel in the shape's dictionary entry: no per-instance code table then
-  p.rc_packed = (by_state && S0 <= 4096 && rvals.size() <= 16) ? 1 : 0;
-  p.off_rc = up8(p.off_sets + 2 * p.S * U);
-  p.off_start = up8(p.off_rc + ((by_state && !p.rc_packed) ? p.S : 0));
-  p.slot_bytes = up8(p.off_start + 48 + 8 * K1S_MAXSTART + 4 * K1S_MAXSTART);
-  const size_t fixed = k1s_fixed_bytes(p.n_pat, p.n_shapes) + 64;
-  const size_t per = (size_t)p.slot_bytes + k1s_ring_bytes(p.ch);
-  if (fixed + 4 * per > (size_t)kLdsBudget) return CMDP_OK;   // fewer than four instances per CU: not worth it
-  const int cap = (int)std::min<size_t>(64, ((size_t)kLdsBudget - fixed) / per);
-  // the fewest instances per workgroup that keep the number of rounds (as for K1L)
-  const int64_t wgs = (B + cap - 1) / cap, rounds = (wgs + h->cus - 1) / h->cus;
-  p.G = (int)std::min<int64_t>(cap, std::max<int64_t>(1, (B + rounds * h->cus - 1) / (rounds * h->cus)));
-  // walker wavefronts and lanes per instance in them.  Round 2 (ONE walker wavefront; FrozenLake-20 / MiniGrid-8 /
-  // DeepSea-20 with p_rand, G = 8 / 11 / 22): teams of 8 (two entries per lane, two ballots) +19 %; teams of 4 (four
-  // ballots) -3 %; of 2 -31 % against a lane per instance counting its 16 entries itself -- so teams only where a lane
-  // gets at most two entries.  With up to four walker wavefronts a wavefront has a quarter of the instances and its teams
-  // are larger.  CMDP_K1S_NW / CMDP_K1S_TEAM override (tuning aids, read per handle).
-  p.nw = p.G >= 4 ? 4 : (p.G >= 2 ? 2 : 1);
-  if (const char* e = std::getenv("CMDP_K1S_NW")) p.nw = std::max(1, std::min(4, std::atoi(e)));
-  p.nw = std::min(p.nw, p.G);
-  p.gw = (p.G + p.nw - 1) / p.nw;
-  p.team = p.gw <= 4 ? 16 : (p.gw <= 8 ? 8 : 1);
-  if (const char* e = std::getenv("CMDP_K1S_TEAM")) {
-    const int tm = std::atoi(e);
-    if ((tm == 1 || tm == 2 || tm == 4 || tm == 8 || tm == 16) && tm * p.gw <= 64) p.team = tm;
-  }
+  return CMDP_OK;
+}
+
+// Reward kinds: deterministic values, Beta rewards drawn on the device, or the reference-exact reward caches.
+static int upload_rewards(cmdp_t* h, const cmdp_desc* d) {
   hipStream_t st = h->stream;
-  std::vector<uint16_t> sets_flat((size_t)NS * U, 0);
-  for (int b = 0; b < B; ++b) {
-    const int64_t so = h->state_off[b];
-    for (int64_t s = so; s < h->state_off[b + 1]; ++s)
-      for (size_t j = 0; j < sets[(size_t)s].size(); ++j) {
-        const int32_t nx = sets[(size_t)s][j];
-        const int code = p.rc_packed ? std::max(0, rc_state[(size_t)(so + nx)]) : 0;
-        sets_flat[(size_t)s * U + j] = (uint16_t)(nx | (code << 12));
-      }
+  const int B = h->B;
+  const int64_t R = h->n_rows, E = h->n_entries;
+  bool any_beta = false;
+  if (d->sp_rkind)
+    for (int64_t e = 0; e < E; ++e) {
+      if (d->sp_rkind[e] > 1) return fail(CMDP_ERR_UNSUPPORTED, "unknown reward distribution kind at entry %lld", (long long)e);
+      any_beta |= d->sp_rkind[e] == 1;
+    }
+  if ((d->flags & CMDP_FLAG_REWARD_MEANS) && (d->flags & CMDP_FLAG_REWARD_CACHE))
+    return fail(CMDP_ERR_INVALID, "CMDP_FLAG_REWARD_MEANS and CMDP_FLAG_REWARD_CACHE exclude each other");
+  h->reward_cache = any_beta && (d->flags & CMDP_FLAG_REWARD_CACHE);
+  h->sample_beta = any_beta && !(d->flags & (CMDP_FLAG_REWARD_MEANS | CMDP_FLAG_REWARD_CACHE));
+  h->beta_gammas = (d->flags & CMDP_FLAG_BETA_GAMMAS) != 0;
+  if (h->reward_cache && (!d->sp_rp0 || !d->sp_rp1 || d->layout != CMDP_LAYOUT_CSR))
+    return fail(CMDP_ERR_INVALID, "CMDP_FLAG_REWARD_CACHE needs sp_rp0 / sp_rp1 and the CSR layout");
+  if (h->reward_cache && E > 0x7fffffffLL) return fail(CMDP_ERR_UNSUPPORTED, "CMDP_FLAG_REWARD_CACHE: more than 2^31 entries");
+  if (h->sample_beta && (d->rng_mode != CMDP_RNG_PHILOX || !d->sp_rp0 || !d->sp_rp1))
+    return fail(CMDP_ERR_UNSUPPORTED, "Beta rewards are sampled on the device only in CMDP_RNG_PHILOX mode with sp_rp0/"
+                                      "sp_rp1; the reference-exact stream is host side (CMDP_FLAG_REWARD_MEANS)");
+  if (!h->reward_cache && !h->sample_beta) return CMDP_OK;
+  for (int64_t e = 0; e < E; ++e)
+    if (d->sp_rkind[e] == 1 && !(d->sp_rp0[e] > 0.0 && d->sp_rp1[e] > 0.0))
+      return fail(CMDP_ERR_INVALID, "Beta parameters must be positive (entry %lld)", (long long)e);
+  HIP_TRY(h->d_sp_rkind.upload(d->sp_rkind, E, st));
+  if (h->sample_beta) {
+    HIP_TRY(h->d_sp_rp0.upload(d->sp_rp0, E, st));
+    HIP_TRY(h->d_sp_rp1.upload(d->sp_rp1, E, st));
+    return CMDP_OK;
   }
-  std::vector<uint8_t> rc(by_state ? (size_t)NS : (size_t)R, 0);
-  for (size_t i = 0; i < rc.size(); ++i) rc[i] = (uint8_t)std::max(0, by_state ? rc_state[i] : rc_row[i]);
+  h->h_rkind.assign(d->sp_rkind, d->sp_rkind + E);
+  h->h_rp0.assign(d->sp_rp0, d->sp_rp0 + E);
+  h->h_rp1.assign(d->sp_rp1, d->sp_rp1 + E);
+  // the reference keys its caches by (node, action, next_node): entries of a row that name the same successor
+  // (p_rand adds repeated successors) share one cache -- represented by the first of them
+  h->h_canon.resize((size_t)E);
+  for (int64_t r = 0; r < R; ++r) {
+    const int64_t lo = d->sp_ptr[r], hi = d->sp_ptr[r + 1];
+    for (int64_t e = lo; e < hi; ++e) {
+      int64_t c = e;
+      for (int64_t f = lo; f < e; ++f)
+        if (d->sp_next[f] == d->sp_next[e]) { c = f; break; }
+      h->h_canon[(size_t)e] = (int32_t)c;
+    }
+  }
+  HIP_TRY(h->d_rc_canon.upload(h->h_canon.data(), E, st));
+  HIP_TRY(h->d_rc_blk.alloc(E)); HIP_TRY(h->d_rc_blk.zero(st));
+  HIP_TRY(h->d_rc_pos.alloc(E)); HIP_TRY(h->d_rc_pos.zero(st));
+  HIP_TRY(h->d_rc_pend_e.alloc(B)); HIP_TRY(hipMemsetAsync(h->d_rc_pend_e.p, 0xff, sizeof(int32_t) * B, st));
+  HIP_TRY(h->d_rc_pend_prev.alloc(B)); HIP_TRY(h->d_rc_pend_prev.zero(st));
+  HIP_TRY(h->d_rc_pend_act.alloc(B)); HIP_TRY(h->d_rc_pend_act.zero(st));
+  HIP_TRY(h->d_rc_park_count.alloc(1)); HIP_TRY(h->d_rc_park_count.zero(st));
+  HIP_TRY(h->d_rc_park_list.alloc(B));
+  HIP_TRY(h->d_rc_left.alloc(B)); HIP_TRY(h->d_rc_left.zero(st));
+  h->rc_blk_h.assign((size_t)E, nullptr);
+  h->rc_cap = std::min(B, 1024);
+  h->rc_chunk_blocks = (size_t)std::max(256, std::min(B * 8, 4096));  // 10 .. 164 MB per chunk
+  HIP_TRY(h->d_rc_stage.alloc((size_t)h->rc_cap * CMDP_RC_BLOCK));
+  HIP_TRY(h->d_rc_dst.alloc(h->rc_cap));
+  HIP_TRY(h->d_rc_ent.alloc(h->rc_cap));
+  HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h->rc_stage_h), sizeof(double) * (size_t)h->rc_cap * CMDP_RC_BLOCK, 0));
+  HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h->rc_dst_h), sizeof(double*) * (size_t)h->rc_cap, 0));
+  HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h->rc_ent_h), sizeof(int32_t) * (size_t)h->rc_cap, 0));
+  HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h->rc_list_h), sizeof(int32_t) * (size_t)B, 0));
+  HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h->rc_pend_h), sizeof(int32_t) * (size_t)B, 0));
+  return CMDP_OK;
+}
+
+// The sampler half: row descriptors, entry bases and MT slots -- validated on the host so that no kernel can index out
+// of range -- and the per-instance state.  *rows and *seeds stay with the caller for the rollout plans and the MT streams.
+static int upload_sampler(cmdp_t* h, const cmdp_desc* d, std::vector<RowDesc>* rows, std::vector<int32_t>* seeds) {
+  hipStream_t st = h->stream;
+  const int B = h->B, A = h->A;
+  const int64_t NS = h->n_states, R = h->n_rows, E = d->sp_ptr[R];
+  h->n_entries = E;
+  if (d->sp_ptr[0] != 0) return fail(CMDP_ERR_INVALID, "sp_ptr[0] != 0");
+  if (int rc = upload_rewards(h, d)) return rc;
+  rows->resize((size_t)R);
+  std::vector<int64_t> ebase((size_t)B);
+  for (int b = 0; b < B; ++b) {
+    const int64_t s0 = d->state_off[b], S = d->state_off[b + 1] - s0;
+    const int64_t r0 = s0 * A, r1 = (s0 + S) * A;
+    ebase[b] = d->sp_ptr[r0];
+    for (int64_t r = r0; r < r1; ++r) {
+      const int64_t lo = d->sp_ptr[r], n = d->sp_ptr[r + 1] - lo;
+      if (n < 1 || n > 4096 || lo - ebase[b] > 0x7fffffffLL)
+        return fail(CMDP_ERR_INVALID, "row %lld has %lld successors", (long long)r, (long long)n);
+      for (int64_t e = lo; e < lo + n; ++e) {
+        if (d->sp_next[e] < 0 || d->sp_next[e] >= S)
+          return fail(CMDP_ERR_INVALID, "successor index out of range at entry %lld", (long long)e);
+        if (e > lo && d->sp_cum[e] < d->sp_cum[e - 1])
+          return fail(CMDP_ERR_INVALID, "sp_cum not non-decreasing at entry %lld", (long long)e);
+      }
+      RowDesc rd;
+      rd.first = (int32_t)(lo - ebase[b]);
+      rd.n = (int32_t)n;
+      rd.next_if_det = d->sp_next[lo];
+      rd.reward_if_det = d->sp_reward[lo];
+      rd.pad = 0.0;
+      rd.mt_slot = -1;
+      if (n > 1 && d->rng_mode == CMDP_RNG_MT_COMPAT) {
+        rd.mt_slot = (int32_t)seeds->size();
+        seeds->push_back(d->sp_seed[r]);
+      }
+      (*rows)[(size_t)r] = rd;
+    }
+  }
+  std::vector<int32_t> start_slot((size_t)B, -1);
+  if (d->start_off[0] != 0) return fail(CMDP_ERR_INVALID, "start_off[0] != 0");
+  for (int b = 0; b < B; ++b) {
+    const int64_t lo = d->start_off[b], n = d->start_off[b + 1] - lo;
+    const int64_t S = d->state_off[b + 1] - d->state_off[b];
+    if (n < 1) return fail(CMDP_ERR_INVALID, "instance %d has no starting state", b);
+    for (int64_t i = lo; i < lo + n; ++i)
+      if (d->start_state[i] < 0 || d->start_state[i] >= S)
+        return fail(CMDP_ERR_INVALID, "starting state out of range (instance %d)", b);
+    if (n > 1 && d->rng_mode == CMDP_RNG_MT_COMPAT) {
+      start_slot[b] = (int32_t)seeds->size();
+      seeds->push_back(d->start_seed[b]);
+    }
+  }
+  if (seeds->size() > 0x7fffffffULL / 2) return fail(CMDP_ERR_INVALID, "too many MT19937 sampler streams");
+  h->n_slots = (int64_t)seeds->size();
+  const int64_t NSt = d->start_off[B];
+  HIP_TRY(h->d_row.upload(rows->data(), rows->size(), st));
+  HIP_TRY(h->d_entry_base.upload(ebase.data(), ebase.size(), st));
+  HIP_TRY(h->d_sp_next.upload(d->sp_next, E, st));
+  HIP_TRY(h->d_sp_cum.upload(d->sp_cum, E, st));
+  HIP_TRY(h->d_sp_reward.upload(d->sp_reward, E, st));
+  HIP_TRY(h->d_start_off.upload(d->start_off, B + 1, st));
+  HIP_TRY(h->d_start_state.upload(d->start_state, NSt, st));
+  HIP_TRY(h->d_start_cum.upload(d->start_cum, NSt, st));
+  HIP_TRY(h->d_start_slot.upload(start_slot.data(), B, st));
+  std::vector<uint2> keys((size_t)B);
+  for (int b = 0; b < B; ++b) {
+    const uint64_t k = d->philox_key ? d->philox_key[b] : 0;
+    keys[b] = make_uint2((uint32_t)k, (uint32_t)(k >> 32));
+  }
+  HIP_TRY(h->d_key.upload(keys.data(), B, st));
+  HIP_TRY(h->d_cur.alloc(B));
+  HIP_TRY(h->d_cur.zero(st));
+  HIP_TRY(h->d_last_start.alloc(B));
+  HIP_TRY(h->d_last_start.zero(st));
+  HIP_TRY(h->d_prev_start.alloc(B));
+  HIP_TRY(h->d_prev_start.zero(st));
+  HIP_TRY(h->d_h.alloc(B));
+  HIP_TRY(h->d_h.zero(st));
+  HIP_TRY(h->d_need_reset.alloc(B));
+  HIP_TRY(hipMemsetAsync(h->d_need_reset.p, 1, B, st));  // BaseMDP starts with a reset pending
+  HIP_TRY(h->d_ntrans.alloc(B));
+  HIP_TRY(h->d_ntrans.zero(st));
+  HIP_TRY(h->d_nreset.alloc(B));
+  HIP_TRY(h->d_nreset.zero(st));
+  HIP_TRY(h->d_visits_s.alloc(NS));
+  HIP_TRY(h->d_visits_s.zero(st));
+  HIP_TRY(h->d_visits_sa.alloc(R));
+  HIP_TRY(h->d_visits_sa.zero(st));
+  HIP_TRY(hipStreamSynchronize(st));  // keys and start_slot go out of scope
+  return CMDP_OK;
+}
+
+// K1S: the plan's tables to the device
+static int install_k1s(cmdp_t* h, K1sChoice* ks) {
+  hipStream_t st = h->stream;
+  K1sPlan& p = ks->p;
   if (p.shape_bytes == 1) {
-    std::vector<uint8_t> s8((size_t)R);
-    for (int64_t r = 0; r < R; ++r) s8[(size_t)r] = (uint8_t)shape[(size_t)r];
-    HIP_TRY(h->d_k1s_pat.upload(s8.data(), s8.size(), st));
-    HIP_TRY(hipStreamSynchronize(st));
+    HIP_TRY(h->d_k1s_pat.upload(ks->shape8.data(), ks->shape8.size(), st));
     p.shape = h->d_k1s_pat.p;
   } else {
-    HIP_TRY(h->d_k1s_shape16.upload(shape.data(), shape.size(), st));
+    HIP_TRY(h->d_k1s_shape16.upload(ks->shape16.data(), ks->shape16.size(), st));
     p.shape = h->d_k1s_shape16.p;
   }
-  HIP_TRY(h->d_k1s_dict.upload(dict.data(), dict.size(), st));
-  HIP_TRY(h->d_k1s_sets.upload(sets_flat.data(), sets_flat.size(), st));
-  HIP_TRY(h->d_k1s_rc.upload(rc.data(), rc.size(), st));
-  HIP_TRY(h->d_k1s_patterns.upload(patterns.data(), patterns.size(), st));
-  HIP_TRY(h->d_k1s_rvals.upload(rvals.data(), rvals.size(), st));
-  HIP_TRY(hipStreamSynchronize(st));
+  HIP_TRY(h->d_k1s_dict.upload(ks->dict.data(), ks->dict.size(), st));
+  HIP_TRY(h->d_k1s_sets.upload(ks->sets.data(), ks->sets.size(), st));
+  HIP_TRY(h->d_k1s_rc.upload(ks->rc.data(), ks->rc.size(), st));
+  HIP_TRY(h->d_k1s_patterns.upload(ks->patterns.data(), ks->patterns.size(), st));
+  HIP_TRY(h->d_k1s_rvals.upload(ks->rvals.data(), ks->rvals.size(), st));
+  HIP_TRY(hipStreamSynchronize(st));  // the host images die with the caller's scope
   p.dict = h->d_k1s_dict.p; p.sets = h->d_k1s_sets.p; p.rcode = h->d_k1s_rc.p;
   p.patterns = h->d_k1s_patterns.p; p.rvals = h->d_k1s_rvals.p;
   h->k1s = p;
-  h->k1s_bytes = fixed + (size_t)p.G * per + 16;
+  h->k1s_bytes = ks->bytes;
   h->k1s_ok = true;
+  return CMDP_OK;
+}
+
+// The LDS-resident rollout kernels the batch is eligible for (cmdp_rollout_plan.h), and the tables they read.
+static int install_rollout_plans(cmdp_t* h, const cmdp_desc* d, const std::vector<RowDesc>& rows) {
+  hipStream_t st = h->stream;
+  const PlanInput in{d, rows.data(), h->B, h->A, h->H, h->max_S, h->cus};
+  const PlanKnobs knobs = plan_knobs();
+  const bool table_rewards = !h->sample_beta && !h->reward_cache;   // the rewards are the table's values
+  DetTables t;
+  K1lpChoice lp;
+  if (table_rewards && h->n_slots == 0 && det_tables(in, &t)) lp = plan_k1lp(in, t, knobs);
+  if (!lp.ok) {
+    if (!table_rewards || h->rng_mode != CMDP_RNG_PHILOX || h->layout != CMDP_LAYOUT_CSR) return CMDP_OK;
+    K1sChoice ks = plan_k1s(in);
+    return ks.ok ? install_k1s(h, &ks) : CMDP_OK;
+  }
+  K1tChoice kt = plan_k1t(in, t, lp, knobs);
+  const K1uChoice ku = plan_k1u(in, kt, knobs);
+  K1eChoice ke = plan_k1e(in, t, knobs);
+  k1lp_images(lp.p, h->A, &t);
+  HIP_TRY(h->d_next16.upload(t.next16.data(), t.next16.size(), st));
+  HIP_TRY(h->d_rcode.upload(t.codes.data(), t.codes.size(), st));
+  HIP_TRY(h->d_rvals.upload(t.vals.data(), t.vals.size(), st));
+  lp.p.next16 = h->d_next16.p + 8; lp.p.rcode = h->d_rcode.p + 16; lp.p.rvals = h->d_rvals.p;
+  h->lds_plan = lp.p;
+  h->lds_bytes = k1l_lds_bytes(lp.p, lp.p.G);
+  h->lds_G1 = lp.G1;
+  h->lds_G2 = lp.G2;
+  h->lds_ok = true;
+  if (kt.ok) {   // eligible: CMDP_OPT_ROLLOUT_KERNEL 4 may force it, and the automatic choice when it needs fewer rounds x time
+    HIP_TRY(h->d_tmpl_words.upload(kt.words.data(), kt.words.size(), st));
+    HIP_TRY(h->d_swap_bits.upload(kt.swap_bits.data(), kt.swap_bits.size(), st));
+    kt.q.tmpl = h->d_tmpl_words.p; kt.q.swap_bits = h->d_swap_bits.p; kt.q.rvals = h->d_rvals.p;
+    h->tmpl_plan = kt.q;
+    h->tmpl_lds = k1t_lds_bytes(kt.q, kt.q.G);
+    h->tmpl_ok = true;
+    h->tmpl_auto = kt.autos;
+  }
+  if (ku.ok) {
+    h->k1u = ku.u;
+    h->k1u.tmpl = h->d_tmpl_words.p; h->k1u.swap_bits = h->d_swap_bits.p; h->k1u.rvals = h->d_rvals.p;
+    h->k1u_lds = k1u_lds_bytes(ku.u, ku.u.G);
+    h->k1u_ok = true;
+    h->k1u_auto = ku.autos;
+  }
+  if (ke.ok) {
+    HIP_TRY(h->d_etab.upload(ke.etab.data(), ke.etab.size(), st));
+    ke.e.etab = h->d_etab.p; ke.e.rvals = h->d_rvals.p;
+    h->k1e = ke.e;
+    h->k1e_lds = k1e_lds_bytes(ke.e);
+    h->k1e_ok = true;
+  }
+  HIP_TRY(hipStreamSynchronize(st));  // the host images die with this scope
+  return CMDP_OK;
+}
+
+// One MT19937 state per sampler stream of CMDP_RNG_MT_COMPAT (rows with several successors, instances with several starts)
+static int seed_mt(cmdp_t* h, const std::vector<int32_t>& seeds) {
+  if (!h->n_slots) return CMDP_OK;
+  hipStream_t st = h->stream;
+  DevBuf<int32_t> d_seeds;
+  HIP_TRY(d_seeds.upload(seeds.data(), seeds.size(), st));
+  HIP_TRY(h->d_mt.alloc((size_t)h->n_slots * 624));
+  HIP_TRY(h->d_mt_pos.alloc(h->n_slots));
+  hipLaunchKernelGGL(k_mt_seed, dim3(grid_for(h->n_slots, 64)), dim3(64), 0, st, h->d_mt.p, h->d_mt_pos.p,
+                     d_seeds.p, h->n_slots);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(st));  // d_seeds is released at scope exit
+  return CMDP_OK;
+}
+
+// The DP half: CSR rows, validated, and the shape statistics the DP kernels are chosen by.
+static int upload_dp(cmdp_t* h, const cmdp_desc* d) {
+  hipStream_t st = h->stream;
+  const int B = h->B, A = h->A;
+  const int64_t R = h->n_rows;
+  if (d->csr_ptr[0] != 0) return fail(CMDP_ERR_INVALID, "csr_ptr[0] != 0");
+  const int64_t N = d->csr_ptr[R];
+  h->n_csr = N;
+  h->csr_nnz.resize(B);
+  for (int b = 0; b < B; ++b) {
+    const int64_t s0 = d->state_off[b], S = d->state_off[b + 1] - s0;
+    const int64_t r0 = s0 * A, r1 = (s0 + S) * A;
+    h->csr_nnz[b] = d->csr_ptr[r1] - d->csr_ptr[r0];
+    if (h->csr_nnz[b] > 0x7fffffffLL) return fail(CMDP_ERR_INVALID, "instance %d has too many non-zeros", b);
+    h->max_inst_nnz = std::max(h->max_inst_nnz, h->csr_nnz[b]);
+    for (int64_t r = r0; r < r1; ++r) {
+      if (d->csr_ptr[r + 1] < d->csr_ptr[r]) return fail(CMDP_ERR_INVALID, "csr_ptr decreasing at row %lld", (long long)r);
+      h->max_row_nnz = std::max<int>(h->max_row_nnz, (int)std::min<int64_t>(d->csr_ptr[r + 1] - d->csr_ptr[r], 1 << 30));
+      for (int64_t k = d->csr_ptr[r]; k < d->csr_ptr[r + 1]; ++k)
+        if (d->csr_col[k] < 0 || d->csr_col[k] >= S)
+          return fail(CMDP_ERR_INVALID, "csr_col out of range at %lld", (long long)k);
+    }
+  }
+  // K2U (k_dp_regu): distinct successor columns per STATE over its A rows, and whether every row lists its columns
+  // in strictly ascending order (the dense-over-the-distinct-set sum is the ascending-column sum)
+  h->max_state_unique = 0;
+  if (A <= 4 && h->max_row_nnz <= 8 && h->max_S <= 1024) {
+    bool sorted = true;
+    int32_t cols[32];
+    for (int64_t s = 0; s < d->state_off[B] && sorted; ++s) {
+      int n = 0;
+      for (int a = 0; a < A; ++a) {
+        const int64_t r = s * A + a;
+        for (int64_t k = d->csr_ptr[r]; k < d->csr_ptr[r + 1]; ++k) {
+          if (k > d->csr_ptr[r] && d->csr_col[k] <= d->csr_col[k - 1]) sorted = false;
+          cols[n++] = d->csr_col[k];
+        }
+      }
+      std::sort(cols, cols + n);
+      const int u = (int)(std::unique(cols, cols + n) - cols);
+      h->max_state_unique = std::max(h->max_state_unique, u);
+    }
+    if (!sorted) h->max_state_unique = 0;
+  }
+  HIP_TRY(h->d_csr_ptr.upload(d->csr_ptr, R + 1, st));
+  HIP_TRY(h->d_csr_col.upload(d->csr_col, N, st));
+  HIP_TRY(h->d_csr_val.upload(d->csr_val, N, st));
+  HIP_TRY(h->d_R.upload(d->R, R, st));
+  return CMDP_OK;
+}
+
+// CMDP_LAYOUT_DENSE: the float32 rows of the DP half as dense [R][dense_spad] rows.
+static int build_dense(cmdp_t* h, const cmdp_desc* d) {
+  const int64_t R = h->n_rows;
+  // exact float64 prefix sums need every probability to be a multiple of 2^-52 after scaling: p >= 2^-28
+  for (int64_t k = 0; k < h->n_csr; ++k)
+    if (!(d->csr_val[k] >= 3.7252902984619141e-09f) || d->csr_val[k] > 1.0f)
+      return fail(CMDP_ERR_INVALID, "dense layout needs probabilities in [2^-28, 1] (entry %lld)", (long long)k);
+  const int nv = (h->max_S + 255) / 256;
+  const int allowed[] = {1, 2, 3, 4, 6, 8, 12, 16};
+  int pick = 0;
+  for (int v : allowed) if (v >= nv) { pick = v; break; }
+  if (!pick) return fail(CMDP_ERR_UNSUPPORTED, "dense layout supports at most 4096 states per instance");
+  h->dense_spad = pick * 256;
+  const size_t n = (size_t)R * h->dense_spad;
+  size_t free_b = 0, total_b = 0;
+  HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+  if (n * sizeof(float) > free_b)
+    return fail(CMDP_ERR_INVALID, "dense layout needs %zu MiB, %zu MiB free", n * sizeof(float) >> 20, free_b >> 20);
+  HIP_TRY(h->d_dense.alloc(n));
+  HIP_TRY(h->d_dense.zero(h->stream));
+  hipLaunchKernelGGL(k_dense_fill, dim3(grid_for(R, 256)), dim3(256), 0, h->stream, h->d_dense.p, h->dense_spad,
+                     h->d_csr_ptr.p, h->d_csr_col.p, h->d_csr_val.p, R);
+  HIP_TRY(hipGetLastError());
   return CMDP_OK;
 }
 
@@ -591,34 +778,9 @@ int cmdp_destroy(cmdp_t* h) {
 int cmdp_create(cmdp_t** out, const cmdp_desc* d) {
   if (!out || !d) return fail(CMDP_ERR_INVALID, "null argument");
   *out = nullptr;
-  if (d->n_instances < 1 || d->n_actions < 1 || d->n_actions > 64 || d->horizon < 0)
-    return fail(CMDP_ERR_INVALID, "n_instances/n_actions/horizon out of range (1 <= A <= 64)");
-  if (d->rng_mode != CMDP_RNG_MT_COMPAT && d->rng_mode != CMDP_RNG_PHILOX) return fail(CMDP_ERR_INVALID, "rng_mode");
-  if (d->layout != CMDP_LAYOUT_CSR && d->layout != CMDP_LAYOUT_DENSE) return fail(CMDP_ERR_INVALID, "layout");
-  if (d->layout == CMDP_LAYOUT_DENSE && (d->rng_mode != CMDP_RNG_PHILOX || !d->sp_ptr || !d->csr_ptr))
-    return fail(CMDP_ERR_INVALID, "CMDP_LAYOUT_DENSE needs CMDP_RNG_PHILOX and both halves of the description "
-                                  "(the float32 rows come from the DP half, rewards and starts from the sampler half)");
-  if (!d->state_off) return fail(CMDP_ERR_INVALID, "state_off is required");
-  const bool has_env = d->sp_ptr != nullptr;
-  const bool has_dp = d->csr_ptr != nullptr;
-  if (!has_env && !has_dp) return fail(CMDP_ERR_INVALID, "neither the sampler half nor the DP half is present");
-  if (has_env && (!d->sp_next || !d->sp_cum || !d->sp_reward || !d->start_off || !d->start_state || !d->start_cum))
-    return fail(CMDP_ERR_INVALID, "sampler half is incomplete");
-  if (has_env && d->rng_mode == CMDP_RNG_MT_COMPAT && (!d->sp_seed || !d->start_seed))
-    return fail(CMDP_ERR_INVALID, "MT_COMPAT needs sp_seed and start_seed");
-  if (has_dp && (!d->csr_col || !d->csr_val || !d->R)) return fail(CMDP_ERR_INVALID, "DP half is incomplete");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(CMDP_ERR_NO_DEVICE, "no HIP device visible");
-
-  const int B = d->n_instances, A = d->n_actions;
-  if (d->state_off[0] != 0) return fail(CMDP_ERR_INVALID, "state_off[0] != 0");
   int max_S = 0;
-  for (int b = 0; b < B; ++b) {
-    const int64_t S = d->state_off[b + 1] - d->state_off[b];
-    if (S < 1 || S > (1 << 28)) return fail(CMDP_ERR_INVALID, "instance %d has %lld states", b, (long long)S);
-    max_S = std::max<int>(max_S, (int)S);
-  }
-  const int64_t NS = d->state_off[B], R = NS * A;
+  if (int rc = check_desc(d, &max_S)) return rc;
+  const int B = d->n_instances, A = d->n_actions;
 
   cmdp_t* h = new cmdp;
   struct Guard {
@@ -628,537 +790,27 @@ int cmdp_create(cmdp_t** out, const cmdp_desc* d) {
   HIP_TRY(hipGetDevice(&h->device));
   if (hipDeviceGetAttribute(&h->cus, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess || h->cus < 1) h->cus = 256;
   HIP_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-  hipStream_t st = h->stream;
   h->B = B; h->A = A; h->H = d->horizon; h->rng_mode = d->rng_mode; h->layout = d->layout;
   h->rmin = d->reward_min; h->rmax = d->reward_max;
-  h->n_states = NS; h->n_rows = R; h->max_S = max_S;
-  h->has_env = has_env; h->has_dp = has_dp;
+  h->n_states = d->state_off[B]; h->n_rows = h->n_states * A; h->max_S = max_S;
+  h->has_env = d->sp_ptr != nullptr; h->has_dp = d->csr_ptr != nullptr;
   h->state_off.assign(d->state_off, d->state_off + B + 1);
-  HIP_TRY(h->d_state_off.upload(d->state_off, B + 1, st));
+  HIP_TRY(h->d_state_off.upload(d->state_off, B + 1, h->stream));
   HIP_TRY(h->d_flag.alloc(1));
-
-  if (has_env) {
-    const int64_t E = d->sp_ptr[R];
-    h->n_entries = E;
-    if (d->sp_ptr[0] != 0) return fail(CMDP_ERR_INVALID, "sp_ptr[0] != 0");
-    bool any_beta = false;
-    if (d->sp_rkind)
-      for (int64_t e = 0; e < E; ++e) {
-        if (d->sp_rkind[e] > 1) return fail(CMDP_ERR_UNSUPPORTED, "unknown reward distribution kind at entry %lld", (long long)e);
-        any_beta |= d->sp_rkind[e] == 1;
-      }
-    if ((d->flags & CMDP_FLAG_REWARD_MEANS) && (d->flags & CMDP_FLAG_REWARD_CACHE))
-      return fail(CMDP_ERR_INVALID, "CMDP_FLAG_REWARD_MEANS and CMDP_FLAG_REWARD_CACHE exclude each other");
-    const bool reward_cache = any_beta && (d->flags & CMDP_FLAG_REWARD_CACHE);
-    const bool sample_beta = any_beta && !(d->flags & (CMDP_FLAG_REWARD_MEANS | CMDP_FLAG_REWARD_CACHE));
-    h->sample_beta = sample_beta;
-    h->beta_gammas = (d->flags & CMDP_FLAG_BETA_GAMMAS) != 0;
-    h->reward_cache = reward_cache;
-    if (reward_cache) {
-      if (!d->sp_rp0 || !d->sp_rp1 || d->layout != CMDP_LAYOUT_CSR)
-        return fail(CMDP_ERR_INVALID, "CMDP_FLAG_REWARD_CACHE needs sp_rp0 / sp_rp1 and the CSR layout");
-      if (E > 0x7fffffffLL) return fail(CMDP_ERR_UNSUPPORTED, "CMDP_FLAG_REWARD_CACHE: more than 2^31 entries");
-      for (int64_t e = 0; e < E; ++e)
-        if (d->sp_rkind[e] == 1 && !(d->sp_rp0[e] > 0.0 && d->sp_rp1[e] > 0.0))
-          return fail(CMDP_ERR_INVALID, "Beta parameters must be positive (entry %lld)", (long long)e);
-      h->h_rkind.assign(d->sp_rkind, d->sp_rkind + E);
-      h->h_rp0.assign(d->sp_rp0, d->sp_rp0 + E);
-      h->h_rp1.assign(d->sp_rp1, d->sp_rp1 + E);
-      // the reference keys its caches by (node, action, next_node): entries of a row that name the same successor
-      // (p_rand adds repeated successors) share one cache -- represented by the first of them
-      h->h_canon.resize((size_t)E);
-      for (int64_t r = 0; r < R; ++r) {
-        const int64_t lo = d->sp_ptr[r], hi = d->sp_ptr[r + 1];
-        for (int64_t e = lo; e < hi; ++e) {
-          int64_t c = e;
-          for (int64_t f = lo; f < e; ++f)
-            if (d->sp_next[f] == d->sp_next[e]) { c = f; break; }
-          h->h_canon[(size_t)e] = (int32_t)c;
-        }
-      }
-      HIP_TRY(h->d_sp_rkind.upload(d->sp_rkind, E, st));
-      HIP_TRY(h->d_rc_canon.upload(h->h_canon.data(), E, st));
-      HIP_TRY(h->d_rc_blk.alloc(E)); HIP_TRY(h->d_rc_blk.zero(st));
-      HIP_TRY(h->d_rc_pos.alloc(E)); HIP_TRY(h->d_rc_pos.zero(st));
-      HIP_TRY(h->d_rc_pend_e.alloc(B)); HIP_TRY(hipMemsetAsync(h->d_rc_pend_e.p, 0xff, sizeof(int32_t) * B, st));
-      HIP_TRY(h->d_rc_pend_prev.alloc(B)); HIP_TRY(h->d_rc_pend_prev.zero(st));
-      HIP_TRY(h->d_rc_pend_act.alloc(B)); HIP_TRY(h->d_rc_pend_act.zero(st));
-      HIP_TRY(h->d_rc_park_count.alloc(1)); HIP_TRY(h->d_rc_park_count.zero(st));
-      HIP_TRY(h->d_rc_park_list.alloc(B));
-      HIP_TRY(h->d_rc_left.alloc(B)); HIP_TRY(h->d_rc_left.zero(st));
-      h->rc_blk_h.assign((size_t)E, nullptr);
-      h->rc_cap = std::min(B, 1024);
-      h->rc_chunk_blocks = (size_t)std::max(256, std::min(B * 8, 4096));  // 10 .. 164 MB per chunk
-      HIP_TRY(h->d_rc_stage.alloc((size_t)h->rc_cap * CMDP_RC_BLOCK));
-      HIP_TRY(h->d_rc_dst.alloc(h->rc_cap));
-      HIP_TRY(h->d_rc_ent.alloc(h->rc_cap));
-      HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h->rc_stage_h), sizeof(double) * (size_t)h->rc_cap * CMDP_RC_BLOCK, 0));
-      HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h->rc_dst_h), sizeof(double*) * (size_t)h->rc_cap, 0));
-      HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h->rc_ent_h), sizeof(int32_t) * (size_t)h->rc_cap, 0));
-      HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h->rc_list_h), sizeof(int32_t) * (size_t)B, 0));
-      HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h->rc_pend_h), sizeof(int32_t) * (size_t)B, 0));
-    }
-    if (sample_beta) {
-      if (d->rng_mode != CMDP_RNG_PHILOX || !d->sp_rp0 || !d->sp_rp1)
-        return fail(CMDP_ERR_UNSUPPORTED, "Beta rewards are sampled on the device only in CMDP_RNG_PHILOX mode with sp_rp0/"
-                                          "sp_rp1; the reference-exact stream is host side (CMDP_FLAG_REWARD_MEANS)");
-      for (int64_t e = 0; e < E; ++e)
-        if (d->sp_rkind[e] == 1 && !(d->sp_rp0[e] > 0.0 && d->sp_rp1[e] > 0.0))
-          return fail(CMDP_ERR_INVALID, "Beta parameters must be positive (entry %lld)", (long long)e);
-      HIP_TRY(h->d_sp_rkind.upload(d->sp_rkind, E, st));
-      HIP_TRY(h->d_sp_rp0.upload(d->sp_rp0, E, st));
-      HIP_TRY(h->d_sp_rp1.upload(d->sp_rp1, E, st));
-    }
-    // row descriptors, entry bases, MT slots -- validated on the host so that no kernel can index out of range
-    std::vector<RowDesc> rows((size_t)R);
-    std::vector<int64_t> ebase((size_t)B);
+  if (h->has_env) {
+    std::vector<RowDesc> rows;
     std::vector<int32_t> seeds;
-    for (int b = 0; b < B; ++b) {
-      const int64_t s0 = d->state_off[b], S = d->state_off[b + 1] - s0;
-      const int64_t r0 = s0 * A, r1 = (s0 + S) * A;
-      ebase[b] = d->sp_ptr[r0];
-      for (int64_t r = r0; r < r1; ++r) {
-        const int64_t lo = d->sp_ptr[r], n = d->sp_ptr[r + 1] - lo;
-        if (n < 1 || n > 4096 || lo - ebase[b] > 0x7fffffffLL)
-          return fail(CMDP_ERR_INVALID, "row %lld has %lld successors", (long long)r, (long long)n);
-        for (int64_t e = lo; e < lo + n; ++e) {
-          if (d->sp_next[e] < 0 || d->sp_next[e] >= S)
-            return fail(CMDP_ERR_INVALID, "successor index out of range at entry %lld", (long long)e);
-          if (e > lo && d->sp_cum[e] < d->sp_cum[e - 1])
-            return fail(CMDP_ERR_INVALID, "sp_cum not non-decreasing at entry %lld", (long long)e);
-        }
-        RowDesc rd;
-        rd.first = (int32_t)(lo - ebase[b]);
-        rd.n = (int32_t)n;
-        rd.next_if_det = d->sp_next[lo];
-        rd.reward_if_det = d->sp_reward[lo];
-        rd.pad = 0.0;
-        rd.mt_slot = -1;
-        if (n > 1 && d->rng_mode == CMDP_RNG_MT_COMPAT) {
-          rd.mt_slot = (int32_t)seeds.size();
-          seeds.push_back(d->sp_seed[r]);
-        }
-        rows[(size_t)r] = rd;
-      }
-    }
-    std::vector<int32_t> start_slot((size_t)B, -1);
-    if (d->start_off[0] != 0) return fail(CMDP_ERR_INVALID, "start_off[0] != 0");
-    for (int b = 0; b < B; ++b) {
-      const int64_t lo = d->start_off[b], n = d->start_off[b + 1] - lo;
-      const int64_t S = d->state_off[b + 1] - d->state_off[b];
-      if (n < 1) return fail(CMDP_ERR_INVALID, "instance %d has no starting state", b);
-      for (int64_t i = lo; i < lo + n; ++i)
-        if (d->start_state[i] < 0 || d->start_state[i] >= S)
-          return fail(CMDP_ERR_INVALID, "starting state out of range (instance %d)", b);
-      if (n > 1 && d->rng_mode == CMDP_RNG_MT_COMPAT) {
-        start_slot[b] = (int32_t)seeds.size();
-        seeds.push_back(d->start_seed[b]);
-      }
-    }
-    if (seeds.size() > 0x7fffffffULL / 2) return fail(CMDP_ERR_INVALID, "too many MT19937 sampler streams");
-    h->n_slots = (int64_t)seeds.size();
-    const int64_t NSt = d->start_off[B];
-    HIP_TRY(h->d_row.upload(rows.data(), rows.size(), st));
-    HIP_TRY(h->d_entry_base.upload(ebase.data(), ebase.size(), st));
-    HIP_TRY(h->d_sp_next.upload(d->sp_next, E, st));
-    HIP_TRY(h->d_sp_cum.upload(d->sp_cum, E, st));
-    HIP_TRY(h->d_sp_reward.upload(d->sp_reward, E, st));
-    HIP_TRY(h->d_start_off.upload(d->start_off, B + 1, st));
-    HIP_TRY(h->d_start_state.upload(d->start_state, NSt, st));
-    HIP_TRY(h->d_start_cum.upload(d->start_cum, NSt, st));
-    HIP_TRY(h->d_start_slot.upload(start_slot.data(), B, st));
-    std::vector<uint2> keys((size_t)B);
-    for (int b = 0; b < B; ++b) {
-      const uint64_t k = d->philox_key ? d->philox_key[b] : 0;
-      keys[b] = make_uint2((uint32_t)k, (uint32_t)(k >> 32));
-    }
-    HIP_TRY(h->d_key.upload(keys.data(), B, st));
-    HIP_TRY(h->d_cur.alloc(B));
-    HIP_TRY(h->d_cur.zero(st));
-    HIP_TRY(h->d_last_start.alloc(B));
-    HIP_TRY(h->d_last_start.zero(st));
-    HIP_TRY(h->d_prev_start.alloc(B));
-    HIP_TRY(h->d_prev_start.zero(st));
-    HIP_TRY(h->d_h.alloc(B));
-    HIP_TRY(h->d_h.zero(st));
-    HIP_TRY(h->d_need_reset.alloc(B));
-    HIP_TRY(hipMemsetAsync(h->d_need_reset.p, 1, B, st));  // BaseMDP starts with a reset pending
-    HIP_TRY(h->d_ntrans.alloc(B));
-    HIP_TRY(h->d_ntrans.zero(st));
-    HIP_TRY(h->d_nreset.alloc(B));
-    HIP_TRY(h->d_nreset.zero(st));
-    HIP_TRY(h->d_visits_s.alloc(NS));
-    HIP_TRY(h->d_visits_s.zero(st));
-    HIP_TRY(h->d_visits_sa.alloc(R));
-    HIP_TRY(h->d_visits_sa.zero(st));
-    // ---- eligibility of the LDS-resident rollout kernel --------------------------------------------------
-    {
-      bool ok = max_S <= 65535 && h->n_slots == 0 && !sample_beta && !reward_cache;
-      for (int b = 0; ok && b < B; ++b) ok = (d->state_off[b + 1] - d->state_off[b]) == max_S;  // uniform S
-      for (int64_t r = 0; ok && r < R; ++r) ok = rows[(size_t)r].n == 1;
-      for (int b = 0; ok && b < B; ++b) ok = (d->start_off[b + 1] - d->start_off[b]) == 1;
-      std::vector<double> vals;
-      std::unordered_map<uint64_t, int> code_of;
-      std::vector<uint8_t> codes;
-      std::vector<uint16_t> next16;
-      if (ok) {
-        codes.resize((size_t)R);
-        next16.resize((size_t)R);
-        for (int64_t r = 0; ok && r < R; ++r) {
-          const double v = rows[(size_t)r].reward_if_det;
-          uint64_t bits;
-          std::memcpy(&bits, &v, sizeof bits);
-          auto it = code_of.find(bits);
-          if (it == code_of.end()) {
-            if (vals.size() == 256) { ok = false; break; }
-            it = code_of.emplace(bits, (int)vals.size()).first;
-            vals.push_back(v);
-          }
-          codes[(size_t)r] = (uint8_t)it->second;
-          next16[(size_t)r] = (uint16_t)rows[(size_t)r].next_if_det;
-        }
-      }
-      if (ok) {
-        const int rows_max = max_S * A;
-        LdsPlan p{};
-        p.rows_max = rows_max;
-        // reward code in the upper bits of the successor word when both fit 16 bits: one table and one LDS read less
-        // (the successor is stored as its row base, successor * A)
-        int bits_s = 1, bits_c = 0;
-        while ((1 << bits_s) < rows_max) ++bits_s;
-        while ((1 << bits_c) < (int)vals.size()) ++bits_c;
-        p.code_shift = (bits_s + bits_c <= 16) ? bits_s : 0;
-        const bool pipe_ok = bits_s + 1 + bits_c <= 16;  // K1P stores the row base as a byte offset: one more bit
-        p.off_rcode = (rows_max * 2 + 3) & ~3;
-        if (p.code_shift) {  // packed: successor words, 8-bit count deltas (+ the walker's dummy counter), overflow list
-          p.off_cnt = p.off_rcode;
-          p.off_ovf = p.off_cnt + ((rows_max + 4 + 3) & ~3);
-          p.slot_bytes = p.off_ovf + ((2 * K1L_OVF + 3) & ~3);
-        } else {
-          p.off_cnt = p.off_rcode + ((rows_max + 3) & ~3);
-          p.off_ovf = 0;
-          p.slot_bytes = p.off_cnt + (((rows_max + 1) / 2) * 4) + 4;  // + the walker's dummy count dword
-        }
-        const int fixed = K1L_FIXED;
-        // The walk is bound by the latency of one transition times the number of "rounds" of workgroups the batch
-        // needs (instances resident per CU are limited by LDS capacity).  Choose the action-ring chunk length and the
-        // workgroups per CU (two overlap one group's staging / flush with the other's walk, one holds a few more
-        // instances) that need the fewest rounds; ties go to the longer chunk (fewer barriers), then to two per CU.
-        int cus = 256;
-        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device);
-        if (cus < 1) cus = 256;
-        h->cus = cus;
-        double best_cost = -1.0;
-        int best_cap = 0;  // LDS capacity (instances per workgroup) of the chosen candidate
-        p.ch = 256;
-        p.G = 0;
-        const int force_ch = std::getenv("CMDP_K1L_CH") ? std::atoi(std::getenv("CMDP_K1L_CH")) : 0;      // tuning aids
-        const int force_pipe = std::getenv("CMDP_K1L_PIPE") ? std::atoi(std::getenv("CMDP_K1L_PIPE")) : -1;
-        struct Cand { int pipe, ch; };
-        // Packed tables can also run as the wavefront pipeline K1P: ~0.62x the time per transition plus one barrier
-        // per chunk (measured at C2: 53 / 56 / 62 ns per transition at ch = 64 / 32 / 16 against K1L's 82), for
-        // 6 ch + 16 bytes of rings per instance instead of 2 ch.
-        const Cand cands[] = {{0, 256}, {0, 128}, {0, 112}, {0, 64}, {1, 64}, {1, 32}, {1, 16}};
-        for (const Cand& c : cands) {
-          if (force_ch && c.ch != force_ch) continue;
-          if (c.pipe && !pipe_ok) continue;
-          if (force_pipe >= 0 && c.pipe != force_pipe) continue;
-          const int pi = p.slot_bytes + (c.pipe ? 2 * K1P_ACT_STRIDE(c.ch) + 2 * K1P_TR_STRIDE(c.ch) : 2 * c.ch);
-          const int fx = fixed;
-          const int g1 = std::min<int>(64, (kLdsBudget - fx) / pi);
-          // K1P: one workgroup per CU.  Two (26 + 26 instances at C2) need <= 128 VGPRs to be co-resident at all (it has
-          // 145: the "1.8x slower" of the first trial was simply one resident group at a time); forced to 128 it spills,
-          // and two resident groups gain nothing -- they run in lockstep, so their flushes coincide, and a CU holds
-          // the same 52 instances either way.
-          const int g2 = c.pipe ? 0 : std::min<int>(64, (kLdsBudget / 2 - fx) / pi);
-          for (int per_cu : {2, 1}) {
-            const int g = per_cu == 2 ? g2 : g1;
-            if (g < (per_cu == 2 ? 12 : 8)) continue;
-            const int64_t wgs = (B + g - 1) / g, slots_n = (int64_t)cus * per_cu;
-            const int64_t rounds = (wgs + slots_n - 1) / slots_n;
-            const double per_step = c.pipe ? 0.62 * (1.0 + 3.5 / c.ch) : 1.0 + 2.0 / c.ch;
-            const double cost = (double)rounds * per_step;
-            if (best_cost < 0 || cost < best_cost) {
-              best_cost = cost;
-              best_cap = g;
-              p.ch = c.ch;
-              p.pipe = c.pipe;
-              // the fewest instances per workgroup that still need `rounds` rounds: evens out the last round and keeps
-              // LDS bank conflicts down (53 instead of 52 lanes per walker measured +1.2 % at C2)
-              p.G = (int)std::min<int64_t>(g, std::max<int64_t>(1, (B + rounds * slots_n - 1) / (rounds * slots_n)));
-              h->lds_G1 = g1;
-              h->lds_G2 = g2;
-            }
-          }
-        }
-        if (p.pipe) p.code_shift = bits_s + 1;
-        if (p.code_shift)
-          for (int64_t r = 0; r < R; ++r)
-            next16[(size_t)r] = (uint16_t)((next16[(size_t)r] * A * (p.pipe ? 2 : 1)) | (codes[(size_t)r] << p.code_shift));
-        p.n_codes = (int)vals.size();
-        // K1T (cmdp_k1t.h): when every instance's packed words are, state by state, instance 0's words or their swap
-        // (A = 2; seeds of a family whose structure does not depend on the seed only permute the actions), the workgroup
-        // keeps ONE table and a swap bit per state and instance: 2-3 x the instances per CU.
-        static const int k1t_env = std::getenv("CMDP_K1T") ? std::atoi(std::getenv("CMDP_K1T")) : -1;   // tuning aid: 0 off, 1 on
-        // (K1T packs its own words -- successor row base as a byte offset | reward code above it, K1P's format -- whichever
-        // of K1L / K1P the plan above chose: small instances plan onto two K1L workgroups per CU, and K1T still beats that)
-        if (best_cap >= 8 && pipe_ok && A == 2 && k1t_env != 0) {
-          const int S = max_S, rws = S * 2;
-          const int cs_t = bits_s + 1;
-          std::vector<uint16_t> w16((size_t)R);
-          for (int64_t r = 0; r < R; ++r)
-            w16[(size_t)r] = (uint16_t)((rows[(size_t)r].next_if_det * A * 2) | (codes[(size_t)r] << cs_t));
-          TmplPlan q{};
-          q.rows = rws;
-          q.tmpl_bytes = (rws * 2 + 15) & ~15;
-          q.mask_bytes = ((S + 7) / 8 + 3) & ~3;
-          q.off_cnt = q.mask_bytes;
-          q.off_ovf = q.off_cnt + ((rws + 4 + 3) & ~3);
-          // two spare entries: the counts wavefront stores ovf[n_ovf] unconditionally before it knows whether a counter
-          // wrapped (branch-free), so with the list full the store must still land inside the instance's own slot
-          q.slot_bytes = q.off_ovf + ((2 * (K1T_OVF + 2) + 3) & ~3);
-          if (((q.slot_bytes / 4) & 1) == 0) q.slot_bytes += 4;   // odd dword stride: the lanes' slots start on different banks
-          q.n_codes = p.n_codes;
-          q.code_shift = cs_t;
-          if (const char* de = std::getenv("CMDP_K1T_DEBUG")) {   // timing experiments: stages switched off
-            q.debug = std::atoi(de);
-            if (q.debug) std::fprintf(stderr, "libcmdp: CMDP_K1T_DEBUG=%d switches stages of k_rollout_tmpl off -- results are INVALID (timing experiments only)\n", q.debug);
-          }
-          std::vector<uint8_t> bits((size_t)B * q.mask_bytes, 0);
-          bool same = true;
-          const uint16_t* T = w16.data();
-          for (int b = 0; same && b < B; ++b) {
-            const uint16_t* W = w16.data() + (size_t)b * rws;
-            uint8_t* mb = bits.data() + (size_t)b * q.mask_bytes;
-            for (int s2 = 0; s2 < S; ++s2) {
-              const uint16_t w0 = W[2 * s2], w1 = W[2 * s2 + 1], t0 = T[2 * s2], t1 = T[2 * s2 + 1];
-              if (w0 == t0 && w1 == t1) continue;
-              if (w0 == t1 && w1 == t0) { mb[s2 >> 3] |= (uint8_t)(1u << (s2 & 7)); continue; }
-              same = false;
-              break;
-            }
-          }
-          if (same) {
-            // chunk length and instances per workgroup: fewest rounds x time per transition (K1T's chain carries ~4 more
-            // dependent instructions than K1P's: ~1.3 x its time per transition), as for K1L / K1P above
-            double best_t = -1.0;
-            for (int ch : {64, 32, 16}) {
-              if (force_ch && ch != force_ch) continue;
-              q.ch = ch;
-              const int per = q.slot_bytes + 2 * K1P_ACT_STRIDE(ch) + 2 * K1P_TR_STRIDE(ch);
-              const int cap = std::min<int>(128, (kLdsBudget - K1T_FIXED - q.tmpl_bytes) / per);
-              if (cap < 16) continue;
-              const int64_t wgs = (B + cap - 1) / cap, rounds = (wgs + cus - 1) / cus;
-              const double cost = (double)rounds * 1.3 * 0.62 * (1.0 + 3.5 / ch);
-              if (best_t < 0 || cost < best_t) {
-                best_t = cost;
-                h->tmpl_plan = q;
-                h->tmpl_plan.G = (int)std::min<int64_t>(cap, std::max<int64_t>(1, (B + rounds * cus - 1) / (rounds * cus)));
-                if (const char* ge = std::getenv("CMDP_K1T_G"))   // tests: instances per workgroup (read per handle)
-                  h->tmpl_plan.G = std::max(1, std::min(cap, std::atoi(ge)));
-              }
-            }
-            if (best_t > 0) {
-              std::vector<uint16_t> tw(T, T + rws);
-              tw.resize((size_t)h->tmpl_plan.tmpl_bytes / 2, 0);
-              HIP_TRY(h->d_tmpl_words.upload(tw.data(), tw.size(), st));
-              HIP_TRY(h->d_swap_bits.upload(bits.data(), bits.size(), st));
-              HIP_TRY(hipStreamSynchronize(st));
-              h->tmpl_plan.tmpl = h->d_tmpl_words.p;
-              h->tmpl_plan.swap_bits = h->d_swap_bits.p;
-              h->tmpl_lds = k1t_lds_bytes(h->tmpl_plan, h->tmpl_plan.G);
-              h->tmpl_ok = true;                                   // eligible: CMDP_OPT_ROLLOUT_KERNEL 4 may force it
-              h->tmpl_auto = best_t < best_cost || k1t_env == 1;   // and the automatic choice when it needs fewer rounds x time
-              // K1U: the same chain with the visit counts histogrammed from an HBM trace -- an instance keeps only its swap
-              // bits and the rings in LDS, up to 256 instances per workgroup.  Taken automatically when that saves a round
-              // of workgroups over K1T (config C2: one round of 256 instead of two of 128); otherwise the histogram pass
-              // is pure overhead and K1T stays.
-              {
-                K1uPlan u{};
-                u.rows = q.rows; u.tmpl_bytes = q.tmpl_bytes; u.mask_bytes = q.mask_bytes;
-                u.slot_bytes = q.mask_bytes + ((((q.mask_bytes / 4) & 1) == 0) ? 4 : 0);
-                u.n_codes = q.n_codes; u.code_shift = q.code_shift;
-                u.pack10 = u.rows <= 1024 ? 1 : 0;
-                if (const char* pe = std::getenv("CMDP_K1U_PACK10")) u.pack10 = (std::atoi(pe) != 0 && u.rows <= 1024) ? 1 : 0;
-                // chunk length: one barrier per chunk (measured at C2: 2.20 ms per launch at 32 transitions, 2.06 ms at 64)
-                u.ch = u.pack10 ? 72 : 64;
-                if (const char* ce = std::getenv("CMDP_K1U_CH")) u.ch = std::max(8, std::min(240, std::atoi(ce)));
-                u.ch = u.pack10 ? std::max(24, u.ch / 24 * 24) : std::max(8, u.ch & ~7);
-                const int per = u.slot_bytes + 2 * K1P_ACT_STRIDE(u.ch) + 2 * K1P_TR_STRIDE(u.ch);
-                const int cap = std::min<int>(256, (kLdsBudget - K1U_FIXED - u.tmpl_bytes) / per);
-                if (cap >= 64 && k1h_lds_bytes(S, 64) <= (size_t)kLdsBudget) {
-                  const int64_t wgs = (B + cap - 1) / cap, rounds_u = (wgs + cus - 1) / cus;
-                  u.G = (int)std::min<int64_t>(cap, std::max<int64_t>(1, (B + rounds_u * cus - 1) / (rounds_u * cus)));
-                  if (const char* ge = std::getenv("CMDP_K1U_G")) u.G = std::max(1, std::min(cap, std::atoi(ge)));
-                  const int64_t wgs_t = (B + h->tmpl_plan.G - 1) / h->tmpl_plan.G, rounds_t = (wgs_t + cus - 1) / cus;
-                  u.tmpl = h->d_tmpl_words.p; u.swap_bits = h->d_swap_bits.p;
-                  h->k1u = u;
-                  h->k1u_lds = k1u_lds_bytes(u, u.G);
-                  h->k1u_ok = true;
-                  h->k1u_auto = h->tmpl_auto && rounds_u < rounds_t;
-                  // (the histogram of one launch under the chain of the next, on a second stream, was measured at C2 and
-                  // LOST: co-resident, the chain kernel slows from 2.2 to 3.0 ms -- the histogram's LDS atomics sit in the
-                  // same in-order LDS pipeline as the chain's dependent reads -- 3.25 ms per step against 3.00 one after
-                  // the other; the two kernels run on the handle's stream)
-                  if (const char* ue = std::getenv("CMDP_K1U")) h->k1u_auto = std::atoi(ue) != 0;
-                }
-              }
-            }
-          }
-        }
-        // K1E (cmdp_k1e.h): episodic batches with two actions and at most four distinct rewards walk their EPISODES in
-        // parallel (private {successor word | count} tables of 32 instances per workgroup): throughput- instead of
-        // latency-bound, and the tables need not be action-permuted copies of one MDP.
-        static const int k1e_env = std::getenv("CMDP_K1E") ? std::atoi(std::getenv("CMDP_K1E")) : -1;   // tuning aid: 0 off
-        if (A == 2 && h->H > 0 && h->H < (1 << 14) && vals.size() <= 4 && k1e_env != 0) {
-          K1ePlan e{};
-          e.S = max_S;
-          e.H = h->H;
-          e.n_codes = (int)vals.size();
-          e.nch = (h->H + 31) / 32;
-          // a wavefront's ring: the blocks the eight episodes of a round can touch (cmdp_k1e.h)
-          const int64_t round_bits = (int64_t)2 * K1E_EPL * h->H;
-          int rb = 2;
-          while (rb < (round_bits + 126) / 128 + 1) rb <<= 1;
-          e.ring_blocks = rb;
-          e.ash = 12;   // (at least 32 padded states: an action's image then holds whole rounds of the workgroup's 1024 lanes)
-          while ((1 << (e.ash - 7)) < max_S) ++e.ash;   // action stride: states padded to a power of two, 128 B per state
-          if (const char* de = std::getenv("CMDP_K1E_DEBUG")) {   // timing experiments: phases switched off
-            e.debug = std::atoi(de);
-            if (e.debug) std::fprintf(stderr, "libcmdp: CMDP_K1E_DEBUG=%d switches phases of k_rollout_epi off -- results are INVALID (timing experiments only)\n", e.debug);
-          }
-          e.gdw = (int32_t)((((int64_t)max_S * K1E_NI + K1E_THREADS - 1) / K1E_THREADS) * K1E_THREADS);   // a group's image: whole rounds of the workgroup's loads
-          const size_t k1e_behind = k1e_lds_bytes(e);
-          const bool k1e_fits = k1e_behind <= (size_t)kLdsBudget;
-          if (std::getenv("CMDP_K1E_VERBOSE"))
-            std::fprintf(stderr, "libcmdp: K1E plan S %d H %d codes %d ash %d ring_blocks %d gdw %d tables+rings %zu B fits %d\n", e.S, e.H, e.n_codes,
-                         e.ash, e.ring_blocks, e.gdw, k1e_behind, (int)k1e_fits);
-          if (max_S <= 512 && k1e_fits) {
-            // interleaved by instance like the LDS image: [group of 32][state][instance in group]
-            const int64_t groups = ((int64_t)B + K1E_NI - 1) / K1E_NI;
-            std::vector<uint32_t> et((size_t)groups * (size_t)e.gdw, 0u);
-            for (int64_t b2 = 0; b2 < B; ++b2)
-              for (int s2 = 0; s2 < max_S; ++s2) {
-                const int64_t sidx = b2 * max_S + s2;
-                const uint32_t w0 = ((uint32_t)rows[(size_t)(2 * sidx)].next_if_det << 7) | codes[(size_t)(2 * sidx)];
-                const uint32_t w1 = ((uint32_t)rows[(size_t)(2 * sidx + 1)].next_if_det << 7) | codes[(size_t)(2 * sidx + 1)];
-                et[(size_t)(b2 / K1E_NI) * (size_t)e.gdw + (size_t)s2 * K1E_NI + (size_t)(b2 % K1E_NI)] = w0 | (w1 << 16);
-              }
-            HIP_TRY(h->d_etab.upload(et.data(), et.size(), st));
-            HIP_TRY(hipStreamSynchronize(st));
-            e.etab = h->d_etab.p;
-            h->k1e = e;
-            h->k1e_lds = k1e_lds_bytes(e);
-            h->k1e_ok = true;
-          }
-        }
-        if (best_cap >= 8) {
-          // 16 bytes of slack in front of and behind both element arrays: the staging loads are 16-byte wide
-          // from the aligned-down address of a group's first element
-          next16.insert(next16.begin(), 8, 0);
-          next16.insert(next16.end(), 8, 0);
-          codes.insert(codes.begin(), 16, 0);
-          codes.insert(codes.end(), 16, 0);
-          HIP_TRY(h->d_next16.upload(next16.data(), next16.size(), st));
-          HIP_TRY(h->d_rcode.upload(codes.data(), codes.size(), st));
-          HIP_TRY(h->d_rvals.upload(vals.data(), vals.size(), st));
-          p.next16 = h->d_next16.p + 8; p.rcode = h->d_rcode.p + 16; p.rvals = h->d_rvals.p;
-          h->lds_plan = p;
-          h->lds_bytes = k1l_lds_bytes(p, p.G);
-          h->lds_ok = true;
-          h->tmpl_plan.rvals = p.rvals;
-          h->k1u.rvals = p.rvals;
-          h->k1e.rvals = p.rvals;
-          HIP_TRY(hipStreamSynchronize(st));  // staging vectors die with this scope
-        }
-      }
-    }
-    if (!h->lds_ok) h->k1e_ok = false;   // (its reward values are uploaded with the K1L tables)
-    if (!h->lds_ok)
-      if (int rc = build_k1s(h, d)) return rc;
-    if (h->n_slots) {
-      DevBuf<int32_t> d_seeds;
-      HIP_TRY(d_seeds.upload(seeds.data(), seeds.size(), st));
-      HIP_TRY(h->d_mt.alloc((size_t)h->n_slots * 624));
-      HIP_TRY(h->d_mt_pos.alloc(h->n_slots));
-      hipLaunchKernelGGL(k_mt_seed, dim3(grid_for(h->n_slots, 64)), dim3(64), 0, st, h->d_mt.p, h->d_mt_pos.p,
-                         d_seeds.p, h->n_slots);
-      HIP_TRY(hipGetLastError());
-      HIP_TRY(hipStreamSynchronize(st));  // d_seeds is released at scope exit
-    }
+    if (int rc = upload_sampler(h, d, &rows, &seeds)) return rc;
+    if (int rc = install_rollout_plans(h, d, rows)) return rc;
+    if (int rc = seed_mt(h, seeds)) return rc;
   }
-
-  if (has_dp) {
-    if (d->csr_ptr[0] != 0) return fail(CMDP_ERR_INVALID, "csr_ptr[0] != 0");
-    const int64_t N = d->csr_ptr[R];
-    h->n_csr = N;
-    h->csr_nnz.resize(B);
-    for (int b = 0; b < B; ++b) {
-      const int64_t s0 = d->state_off[b], S = d->state_off[b + 1] - s0;
-      const int64_t r0 = s0 * A, r1 = (s0 + S) * A;
-      h->csr_nnz[b] = d->csr_ptr[r1] - d->csr_ptr[r0];
-      if (h->csr_nnz[b] > 0x7fffffffLL) return fail(CMDP_ERR_INVALID, "instance %d has too many non-zeros", b);
-      h->max_inst_nnz = std::max(h->max_inst_nnz, h->csr_nnz[b]);
-      for (int64_t r = r0; r < r1; ++r) {
-        if (d->csr_ptr[r + 1] < d->csr_ptr[r]) return fail(CMDP_ERR_INVALID, "csr_ptr decreasing at row %lld", (long long)r);
-        h->max_row_nnz = std::max<int>(h->max_row_nnz, (int)std::min<int64_t>(d->csr_ptr[r + 1] - d->csr_ptr[r], 1 << 30));
-        for (int64_t k = d->csr_ptr[r]; k < d->csr_ptr[r + 1]; ++k)
-          if (d->csr_col[k] < 0 || d->csr_col[k] >= S)
-            return fail(CMDP_ERR_INVALID, "csr_col out of range at %lld", (long long)k);
-      }
-    }
-    // K2U (k_dp_regu): distinct successor columns per STATE over its A rows, and whether every row lists its columns
-    // in strictly ascending order (the dense-over-the-distinct-set sum is the ascending-column sum)
-    h->max_state_unique = 0;
-    if (A <= 4 && h->max_row_nnz <= 8 && max_S <= 1024) {
-      bool sorted = true;
-      int32_t cols[32];
-      for (int64_t s = 0; s < d->state_off[B] && sorted; ++s) {
-        int n = 0;
-        for (int a = 0; a < A; ++a) {
-          const int64_t r = s * A + a;
-          for (int64_t k = d->csr_ptr[r]; k < d->csr_ptr[r + 1]; ++k) {
-            if (k > d->csr_ptr[r] && d->csr_col[k] <= d->csr_col[k - 1]) sorted = false;
-            cols[n++] = d->csr_col[k];
-          }
-        }
-        std::sort(cols, cols + n);
-        const int u = (int)(std::unique(cols, cols + n) - cols);
-        h->max_state_unique = std::max(h->max_state_unique, u);
-      }
-      if (!sorted) h->max_state_unique = 0;
-    }
-    HIP_TRY(h->d_csr_ptr.upload(d->csr_ptr, R + 1, st));
-    HIP_TRY(h->d_csr_col.upload(d->csr_col, N, st));
-    HIP_TRY(h->d_csr_val.upload(d->csr_val, N, st));
-    HIP_TRY(h->d_R.upload(d->R, R, st));
+  if (h->has_dp) {
+    if (int rc = upload_dp(h, d)) return rc;
   }
   if (d->layout == CMDP_LAYOUT_DENSE) {
-    // exact float64 prefix sums need every probability to be a multiple of 2^-52 after scaling: p >= 2^-28
-    for (int64_t k = 0; k < h->n_csr; ++k)
-      if (!(d->csr_val[k] >= 3.7252902984619141e-09f) || d->csr_val[k] > 1.0f)
-        return fail(CMDP_ERR_INVALID, "dense layout needs probabilities in [2^-28, 1] (entry %lld)", (long long)k);
-    h->dense_spad = ((max_S + 255) / 256) * 256;
-    {
-      const int nv = h->dense_spad / 256;
-      const int allowed[] = {1, 2, 3, 4, 6, 8, 12, 16};
-      int pick = 0;
-      for (int v : allowed) if (v >= nv) { pick = v; break; }
-      if (!pick) return fail(CMDP_ERR_UNSUPPORTED, "dense layout supports at most 4096 states per instance");
-      h->dense_spad = pick * 256;
-    }
-    const size_t n = (size_t)R * h->dense_spad;
-    size_t free_b = 0, total_b = 0;
-    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-    if (n * sizeof(float) > free_b)
-      return fail(CMDP_ERR_INVALID, "dense layout needs %zu MiB, %zu MiB free", n * sizeof(float) >> 20, free_b >> 20);
-    HIP_TRY(h->d_dense.alloc(n));
-    HIP_TRY(h->d_dense.zero(st));
-    hipLaunchKernelGGL(k_dense_fill, dim3(grid_for(R, 256)), dim3(256), 0, st, h->d_dense.p, h->dense_spad,
-                       h->d_csr_ptr.p, h->d_csr_col.p, h->d_csr_val.p, R);
-    HIP_TRY(hipGetLastError());
+    if (int rc = build_dense(h, d)) return rc;
   }
-  HIP_TRY(hipStreamSynchronize(st));  // host staging vectors go out of scope
+  HIP_TRY(hipStreamSynchronize(h->stream));  // host staging vectors go out of scope
   guard.h = nullptr;
   *out = h;
   return CMDP_OK;
@@ -1755,11 +1407,8 @@ int cmdp_set_option(cmdp_t* h, int option, int64_t value) {
                   "(its successor table is encoded for K1P at cmdp_create: set CMDP_K1L_PIPE=0 before creating the handle to use K1L)");
     const int cap = value == 1 ? h->lds_G1 : h->lds_G2;
     if (cap < 1) return fail(CMDP_ERR_INVALID, "no room for %lld workgroups per CU", (long long)value);
-    // the fewest instances per workgroup that keep the round count at this many groups per CU (as cmdp_create does)
-    const int64_t slots = (int64_t)h->cus * value, wgs = (h->B + cap - 1) / cap, rounds = (wgs + slots - 1) / slots;
-    const int g = (int)std::min<int64_t>(cap, std::max<int64_t>(1, (h->B + rounds * slots - 1) / (rounds * slots)));
-    h->lds_plan.G = g;
-    h->lds_bytes = k1l_lds_bytes(h->lds_plan, g);
+    h->lds_plan.G = even_groups(h->B, cap, (int64_t)h->cus * value).G;   // (as cmdp_create plans it)
+    h->lds_bytes = k1l_lds_bytes(h->lds_plan, h->lds_plan.G);
     return CMDP_OK;
   }
   if (option == CMDP_OPT_DP_KERNEL && value >= 0 && value <= 7) {
