@@ -45,7 +45,7 @@ EXPORTS = [
     "cmdp_vi_episodic", "cmdp_pe_episodic", "cmdp_diameter", "cmdp_diameter_episodic", "cmdp_value_norm", "cmdp_gth", "cmdp_qlearning_create", "cmdp_qlearning_destroy", "cmdp_qlearning_run",
     "cmdp_qlearning_tables", "cmdp_qlearning_evaluate", "cmdp_greedy_policy_episodic", "cmdp_qlearning_continuous_create",
     "cmdp_qlearning_policy", "cmdp_qlearning_average_reward", "cmdp_qlearning_run_logged", "cmdp_tracker_replay", "cmdp_average_reward", "cmdp_diameter_range", "cmdp_diameter_sparse_f64", "cmdp_mixing_time", "cmdp_set_observation_table", "cmdp_observe", "cmdp_observe_noise",
-    "cmdp_set_reward_streams", "cmdp_legacy_beta",
+    "cmdp_set_reward_streams", "cmdp_legacy_beta", "cmdp_extended_vi",
 ]
 
 
@@ -171,6 +171,7 @@ def load():
         L.cmdp_diameter_episodic.argtypes = [vp, i32, vp, vp, vp, f64, i64, vp, vp]
         L.cmdp_value_norm.argtypes = [vp, vp, vp]
         L.cmdp_gth.argtypes = [i32, vp, vp, vp]
+        L.cmdp_extended_vi.argtypes = [i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, f64, i64, vp, vp, vp, vp, vp]
         L.cmdp_qlearning_create.argtypes = [C.POINTER(vp), vp, vp, i64, f64, f64, f64, f64, i32]
         L.cmdp_qlearning_destroy.argtypes = [vp]
         L.cmdp_qlearning_run.argtypes = [vp, i64, vp, vp, vp]

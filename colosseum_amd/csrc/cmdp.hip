@@ -29,6 +29,7 @@ extern char** environ;
 #include "cmdp_rollout_plan.h"
 #include "cmdp_agent.h"
 #include "cmdp_chain.h"
+#include "cmdp_evi.h"
 
 namespace {
 
@@ -3782,6 +3783,121 @@ int cmdp_gth(int count, const int32_t* dims, const double* mats, double* out) {
   hipLaunchKernelGGL(k_gth, dim3(count), dim3(256), 0, st, d_moff.p, d_dims.p, d_xoff.p, d_mats.p, d_x.p);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(out, d_x.p, sizeof(double) * (size_t)xt, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return CMDP_OK;
+}
+
+int cmdp_extended_vi(int count, const int32_t* n_states, const int32_t* n_actions, const int64_t* csr_ptr,
+                     const int32_t* csr_col, const float* csr_val, const float* uniform, const float* rewards,
+                     const double* beta_r, const double* beta_p0, const double* r_max, double epsilon,
+                     int64_t max_sweeps, float* Q, float* V, double* span, int64_t* sweeps, int32_t* status) {
+  if (count < 0) return fail(CMDP_ERR_INVALID, "count %d is negative", count);
+  if (count == 0) return CMDP_OK;
+  if (!n_states || !n_actions || !csr_ptr || !rewards || !beta_r || !beta_p0 || !r_max || !Q || !V || !span ||
+      !sweeps || !status)
+    return fail(CMDP_ERR_INVALID, "null argument");
+  if (!(epsilon >= 0.0) || !std::isfinite(epsilon)) return fail(CMDP_ERR_INVALID, "epsilon %g is not a finite value >= 0", epsilon);
+  if (max_sweeps < 1) return fail(CMDP_ERR_INVALID, "max_sweeps %lld < 1", (long long)max_sweeps);
+  std::vector<int64_t> soff((size_t)count), roff((size_t)count);
+  int64_t ns = 0, nr = 0;
+  size_t lds = 0;
+  for (int b = 0; b < count; ++b) {
+    const int S = n_states[b], A = n_actions[b];
+    if (S < 1) return fail(CMDP_ERR_INVALID, "n_states[%d] = %d < 1", b, S);
+    if (A < 1) return fail(CMDP_ERR_INVALID, "n_actions[%d] = %d < 1", b, A);
+    if (!std::isfinite(r_max[b])) return fail(CMDP_ERR_INVALID, "r_max[%d] is not finite", b);
+    soff[b] = ns; roff[b] = nr;
+    ns += S;
+    nr += (int64_t)S * A;
+  }
+  for (int b = 0; b < count; ++b)
+    if (n_states[b] > EVI_MAX_STATES)
+      return fail(CMDP_ERR_UNSUPPORTED, "instance %d has %d states: extended value iteration keeps u1, u2 and the order in "
+                  "LDS for at most %d states", b, n_states[b], EVI_MAX_STATES);
+  if (csr_ptr[0] != 0) return fail(CMDP_ERR_INVALID, "csr_ptr[0] = %lld, not 0", (long long)csr_ptr[0]);
+  for (int64_t r = 0; r < nr; ++r)
+    if (csr_ptr[r + 1] < csr_ptr[r]) return fail(CMDP_ERR_INVALID, "csr_ptr decreases at row %lld", (long long)r);
+  const int64_t nnz = csr_ptr[nr];
+  if (nnz > 0 && (!csr_col || !csr_val)) return fail(CMDP_ERR_INVALID, "null csr_col / csr_val");
+  std::vector<float> uni((size_t)nr, 0.0f);
+  for (int b = 0; b < count; ++b) {
+    const int S = n_states[b], A = n_actions[b];
+    int P = 1;
+    while (P < S) P <<= 1;
+    lds = std::max(lds, (size_t)P * 8 + (size_t)S * 10);
+    for (int64_t r = roff[b]; r < roff[b] + (int64_t)S * A; ++r) {
+      const int64_t rb = csr_ptr[r], re = csr_ptr[r + 1];
+      for (int64_t k = rb; k < re; ++k) {
+        if (csr_col[k] < 0 || csr_col[k] >= S || (k > rb && csr_col[k] <= csr_col[k - 1]))
+          return fail(CMDP_ERR_INVALID, "csr_col of row %lld is not ascending within [0, %d)", (long long)r, S);
+        if (!(csr_val[k] >= 0.0f) || !std::isfinite(csr_val[k]))
+          return fail(CMDP_ERR_INVALID, "csr_val[%lld] = %g is not a finite probability >= 0", (long long)k, (double)csr_val[k]);
+      }
+      if (!std::isfinite(rewards[r])) return fail(CMDP_ERR_INVALID, "rewards[%lld] is not finite", (long long)r);
+      if (!std::isfinite(beta_r[r])) return fail(CMDP_ERR_INVALID, "beta_r[%lld] is not finite", (long long)r);
+      if (!std::isfinite(beta_p0[r])) return fail(CMDP_ERR_INVALID, "beta_p0[%lld] is not finite", (long long)r);
+      if (uniform && uniform[r] != 0.0f) {
+        if (!(uniform[r] > 0.0f) || !std::isfinite(uniform[r]) || re != rb)
+          return fail(CMDP_ERR_INVALID, "uniform[%lld] = %g: must be finite > 0 on a row without CSR entries",
+                      (long long)r, (double)uniform[r]);
+        uni[(size_t)r] = uniform[r];
+      } else if (re - rb == S && csr_val[rb] > 0.0f) {  // a full row of one value is taken as uniform too
+        bool same = true;
+        for (int64_t k = rb + 1; k < re && same; ++k) same = csr_val[k] == csr_val[rb];
+        if (same) uni[(size_t)r] = csr_val[rb];
+      }
+    }
+  }
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(CMDP_ERR_NO_DEVICE, "no HIP device visible");
+  // Workspace reused across calls (UCRL2 solves once per episode; hipMalloc / hipFree synchronise the device) and
+  // deliberately leaked at exit; calls are serialised by a mutex.  One workspace per device.
+  struct Ws {
+    DevBuf<int32_t> S, A, col, status;
+    DevBuf<int64_t> soff, roff, ptr, sweeps;
+    DevBuf<float> val, uni, R, Q, V;
+    DevBuf<double> beta_r, beta_p0, r_max, span;
+    hipStream_t st = nullptr;
+  };
+  static std::mutex mu;
+  static std::map<int, Ws*>* all = new std::map<int, Ws*>;
+  std::lock_guard<std::mutex> lock(mu);
+  int dev = 0;
+  HIP_TRY(hipGetDevice(&dev));
+  Ws*& ws = (*all)[dev];
+  if (!ws) {
+    ws = new Ws;
+    HIP_TRY(hipStreamCreateWithFlags(&ws->st, hipStreamNonBlocking));
+  }
+  hipStream_t st = ws->st;
+  HIP_TRY(ws->S.upload(n_states, count, st));
+  HIP_TRY(ws->A.upload(n_actions, count, st));
+  HIP_TRY(ws->soff.upload(soff.data(), count, st));
+  HIP_TRY(ws->roff.upload(roff.data(), count, st));
+  HIP_TRY(ws->ptr.upload(csr_ptr, (size_t)nr + 1, st));
+  HIP_TRY(ws->col.upload(csr_col, (size_t)nnz, st));
+  HIP_TRY(ws->val.upload(csr_val, (size_t)nnz, st));
+  HIP_TRY(ws->uni.upload(uni.data(), (size_t)nr, st));
+  HIP_TRY(ws->R.upload(rewards, (size_t)nr, st));
+  HIP_TRY(ws->beta_r.upload(beta_r, (size_t)nr, st));
+  HIP_TRY(ws->beta_p0.upload(beta_p0, (size_t)nr, st));
+  HIP_TRY(ws->r_max.upload(r_max, count, st));
+  HIP_TRY(ws->Q.alloc((size_t)nr));
+  HIP_TRY(ws->V.alloc((size_t)ns));
+  HIP_TRY(ws->span.alloc(count));
+  HIP_TRY(ws->sweeps.alloc(count));
+  HIP_TRY(ws->status.alloc(count));
+  if (int rc = set_lds(k_evi, lds)) return rc;
+  EviArgs a{ws->S.p, ws->A.p, ws->soff.p, ws->roff.p, ws->ptr.p, ws->col.p, ws->val.p, ws->uni.p, ws->R.p,
+            ws->beta_r.p, ws->beta_p0.p, ws->r_max.p, epsilon, max_sweeps, ws->Q.p, ws->V.p, ws->span.p,
+            ws->sweeps.p, ws->status.p};
+  hipLaunchKernelGGL(k_evi, dim3(count), dim3(EVI_THREADS), lds, st, a);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(Q, ws->Q.p, sizeof(float) * (size_t)nr, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(V, ws->V.p, sizeof(float) * (size_t)ns, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(span, ws->span.p, sizeof(double) * count, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(sweeps, ws->sweeps.p, sizeof(int64_t) * count, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(status, ws->status.p, sizeof(int32_t) * count, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   return CMDP_OK;
 }

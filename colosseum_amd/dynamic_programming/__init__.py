@@ -108,6 +108,93 @@ def discounted_policy_iteration(T, R, gamma=0.99, epsilon=1e-7):
     raise DynamicProgrammingMaxIterationExceeded()
 
 
+# ---- extended value iteration (reference infinite_horizon.py:67-118, _max_proba :222-251), kernel K10 --------------
+def _evi_problem(T, estimated_rewards, beta_r, beta_p, r_max):
+    """One (T, estimated_rewards, beta_r, beta_p, r_max) 5-tuple -> (S, A, ptr, col, val, uniform, R, beta_r, beta_p0,
+    r_max) in the C ABI's types.  beta_p is [S, A, 1] (Chernoff) or [S, A, S] (Bernstein); only element 0 of each row
+    is read, as in the reference."""
+    T = np.asarray(T)
+    if T.ndim != 3 or T.shape[0] != T.shape[2] or T.shape[0] < 1 or T.shape[1] < 1:
+        raise ValueError(f"T must be [S, A, S] with S, A >= 1, got shape {T.shape}")
+    S, A, _ = T.shape
+    T = np.ascontiguousarray(T, np.float32)
+    if not np.isfinite(T).all() or (T < 0).any():
+        raise ValueError("T must hold finite probabilities >= 0")
+    R = np.ascontiguousarray(estimated_rewards, np.float32)
+    br = np.ascontiguousarray(beta_r, np.float64)  # float32 bounds are widened: the one precision difference
+    bp = np.asarray(beta_p, np.float64)
+    if R.shape != (S, A):
+        raise ValueError(f"estimated_rewards must be [S, A] = {(S, A)}, got {R.shape}")
+    if br.shape != (S, A):
+        raise ValueError(f"beta_r must be [S, A] = {(S, A)}, got {br.shape}")
+    if bp.ndim != 3 or bp.shape[:2] != (S, A) or bp.shape[2] not in (1, S):
+        raise ValueError(f"beta_p must be [S, A, 1] or [S, A, S] with S, A = {(S, A)}, got {bp.shape}")
+    rm = float(r_max)
+    T2 = T.reshape(S * A, S)
+    uniform = np.where((T2[:, 0] > 0) & (T2 == T2[:, :1]).all(axis=1), T2[:, 0], np.float32(0)).astype(np.float32)
+    rows, cols = np.nonzero(T2 * (uniform == 0)[:, None])
+    ptr = np.concatenate([[0], np.cumsum(np.bincount(rows, minlength=S * A))]).astype(np.int64)
+    return (S, A, ptr, cols.astype(np.int32), T2[rows, cols], uniform, R.ravel(), br.ravel(),
+            np.ascontiguousarray(bp[:, :, 0], np.float64).ravel(), rm)
+
+
+def _evi_run(problems, epsilon, max_sweeps):
+    """Packs the problems into one cmdp_extended_vi call: [(span, Q, V) or None], sweeps [B] int64."""
+    eps = float(epsilon)
+    if not np.isfinite(eps) or eps < 0:
+        raise ValueError(f"epsilon must be finite and >= 0, got {epsilon}")
+    if int(max_sweeps) < 1:
+        raise ValueError(f"max_sweeps must be >= 1, got {max_sweeps}")
+    P = [_evi_problem(*p) for p in problems]
+    B = len(P)
+    if B == 0:
+        return [], np.zeros(0, np.int64)
+    S = np.array([p[0] for p in P], np.int32)
+    A = np.array([p[1] for p in P], np.int32)
+    nnz = np.array([len(p[3]) for p in P], np.int64)
+    nz_off = np.concatenate([[0], np.cumsum(nnz)])
+    ptr = np.concatenate([[0]] + [p[2][1:] + nz_off[b] for b, p in enumerate(P)]).astype(np.int64)
+    cat = lambda i, dt: np.ascontiguousarray(np.concatenate([p[i] for p in P]), dt)  # noqa: E731
+    col, val, uni, R, br, bp0 = (cat(3, np.int32), cat(4, np.float32), cat(5, np.float32), cat(6, np.float32),
+                                 cat(7, np.float64), cat(8, np.float64))
+    rmax = np.array([p[9] for p in P], np.float64)
+    rows = (S.astype(np.int64) * A).sum()
+    Q = np.empty(rows, np.float32)
+    V = np.empty(int(S.sum()), np.float32)
+    span = np.empty(B, np.float64)
+    sweeps = np.empty(B, np.int64)
+    status = np.empty(B, np.int32)
+    L.check(L.load().cmdp_extended_vi(B, L.ptr(S), L.ptr(A), L.ptr(ptr), L.ptr(col), L.ptr(val), L.ptr(uni), L.ptr(R),
+                                      L.ptr(br), L.ptr(bp0), L.ptr(rmax), eps, int(max_sweeps), L.ptr(Q), L.ptr(V),
+                                      L.ptr(span), L.ptr(sweeps), L.ptr(status)))
+    out, q0, v0 = [], 0, 0
+    for b in range(B):
+        s, a = int(S[b]), int(A[b])
+        if status[b] == L.OK:
+            out.append((np.float32(span[b]), Q[q0:q0 + s * a].reshape(s, a).copy(), V[v0:v0 + s].copy()))
+        else:
+            out.append(None)
+        q0 += s * a
+        v0 += s
+    return out, sweeps
+
+
+def extended_value_iteration(T, estimated_rewards, beta_r, beta_p, r_max, epsilon=1e-3):
+    """reference infinite_horizon.py:67-118 (UCRL2's optimistic solver).  Returns (span, Q [S,A] float32, V [S]
+    float32), span the float32 ptp of the value vector the last sweep read, or None after DP_MAX_ITERATION sweeps.
+    beta_p is [S,A,1] or [S,A,S]; only element 0 of each row is read, as in the reference.  The reference's agent
+    passes float64 bounds; float32 bounds are widened to float64 here (the one precision difference to a call with
+    float32 bounds there).  Ties in the value vector are ordered by ascending state index."""
+    return _evi_run([(T, estimated_rewards, beta_r, beta_p, r_max)], epsilon, DP_MAX_ITERATION)[0][0]
+
+
+def extended_value_iteration_batch(problems, epsilon=1e-3, max_sweeps=DP_MAX_ITERATION):
+    """`extended_value_iteration` for many (T, estimated_rewards, beta_r, beta_p, r_max) problems in one launch; the
+    problems may differ in S and A.  Returns ([(span, Q, V) or None per problem], sweeps [B] int64): None where a
+    problem did not converge within max_sweeps, which leaves the others unaffected."""
+    return _evi_run(list(problems), epsilon, max_sweeps)
+
+
 # ---- argmax with uniform random tie-break (reference dynamic_programming/utils.py:12-100) ----------------
 # The reference re-seeds *numba's* generator with 42 on every call; without numba the tie winner cannot be
 # reproduced (SURVEY 8c caveat 1).  Tie-free rows are exact; ties are broken by RandomState(42).choice,

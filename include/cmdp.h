@@ -510,6 +510,26 @@ int cmdp_average_reward(cmdp_t* h, const int32_t* actions, const int32_t* start_
    out + sum_{i<m} dims[i]. */
 int cmdp_gth(int count, const int32_t* dims, const double* mats, double* out);
 
+/* extended_value_iteration (colosseum/dynamic_programming/infinite_horizon.py:67-118, _max_proba at :222-251), the
+   optimistic solver of UCRL2, for `count` estimated models at once on the current device; one launch runs every
+   instance to convergence or to max_sweeps.  Instance b has n_states[b] <= 4096 states and n_actions[b] actions; its
+   S*A rows follow those of the instances before it, its states likewise.  Rows: csr_ptr [n_rows + 1] (csr_ptr[0] = 0)
+   into csr_col (instance-relative successors, ascending within a row) and csr_val (float32 T[s, a, col] >= 0);
+   uniform [n_rows] (may be NULL): uniform[r] = c > 0 makes row r equal to c at every state and then the row has no
+   CSR entries (the estimated model's unvisited pairs, 1/S, without S entries each; a full CSR row of one value is
+   detected as well);
+   rewards [n_rows] float32 estimated rewards; beta_r [n_rows] and beta_p0 [n_rows] (element 0 of beta_p[s, a], the
+   only one the reference reads) float64; r_max [count] float64; epsilon >= 0 as in the reference (1e-3 there);
+   max_sweeps >= 1 (10**6 there).  Outputs: Q [n_rows] and V [n_states] float32 of the last sweep, span [count] =
+   ptp(u1) of the last sweep's input (NaN when not converged), sweeps [count] sweeps run, status [count] 0 or
+   CMDP_ERR_MAX_ITER -- an instance that does not converge does not fail the call.  CMDP_ERR_INVALID names a bad
+   argument; CMDP_ERR_UNSUPPORTED when an instance exceeds the LDS budget.  A per-device workspace is reused across calls
+   (no allocation in steady state); calls are serialised. */
+int cmdp_extended_vi(int count, const int32_t* n_states, const int32_t* n_actions, const int64_t* csr_ptr,
+                     const int32_t* csr_col, const float* csr_val, const float* uniform, const float* rewards,
+                     const double* beta_r, const double* beta_p0, const double* r_max, double epsilon,
+                     int64_t max_sweeps, float* Q, float* V, double* span, int64_t* sweeps, int32_t* status);
+
 #ifdef __cplusplus
 }
 #endif
