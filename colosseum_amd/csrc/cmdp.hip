@@ -256,6 +256,7 @@ struct cmdp {
   DevBuf<uint8_t> d_ch_mask;
   // K9F: fill-reducing elimination plan of every instance (build_chain_plan), built at the first average-reward call
   bool chain_plan_built = false, chain_plan_any = false;
+  bool chain_fast_ran = false;  // K9F was launched by the last average-reward call (its `slow` flags are that call's)
   DevBuf<int32_t> d_cf_rank, d_cf_cptr, d_cf_nrounds, d_cf_rptr, d_cf_piv;
   DevBuf<int64_t> d_cf_cbase, d_cf_rbase;
   DevBuf<uint16_t> d_cf_cand;
@@ -1487,7 +1488,7 @@ int cmdp_stat(cmdp_t* h, int which, double* out) {
     return CMDP_OK;
   }
   if (which == CMDP_STAT_CHAIN_FAST_INSTANCES) {
-    if (!h->chain_plan_any) { *out = 0.0; return CMDP_OK; }
+    if (!h->chain_fast_ran) { *out = 0.0; return CMDP_OK; }   // K9 alone: no plan, K9F beyond the LDS budget, exact order
     std::vector<uint8_t> slow((size_t)h->B);
     HIP_TRY(hipMemcpyAsync(slow.data(), h->d_cf_slow.p, (size_t)h->B, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
@@ -2777,8 +2778,8 @@ int cmdp_qlearning_policy(cmdp_agent_t* a, float* pi) {
 
 // K9F's host side (cmdp_chain.h): per instance a minimum-degree elimination order of the MDP's transition graph (union over
 // the actions, symmetrised), every pivot's candidate list in the filled graph, and a schedule of rounds of up to 16 pivots
-// that are pairwise non-adjacent and share at most one candidate.  Instances without a plan (a pivot with more than 64
-// candidates, more than 65 535 states) keep K9.
+// that are pairwise non-adjacent and share at most one candidate.  Instances without a plan (a pivot with more than
+// K9F_MAXC = 128 candidates, fewer than 2 or more than 65 535 states) keep K9.
 static int build_chain_plan(cmdp_t* h) {
   h->chain_plan_built = true;
   const int B = h->B, A = h->A;
@@ -2973,6 +2974,7 @@ static int chain_launch(cmdp_t* h, const float* d_pi, const int32_t* d_act, cons
   // K9F first (irreducible chains, fill-reducing elimination order, rounds of independent pivots); it flags the instances
   // it leaves to K9.  The reference's summation order (CMDP_OPT_CHAIN_EXACT_ORDER) keeps K9 alone.
   static const int fast_env = std::getenv("CMDP_CHAIN_FAST") ? std::atoi(std::getenv("CMDP_CHAIN_FAST")) : 1;
+  h->chain_fast_ran = false;
   if (!h->chain_exact && fast_env) {
     if (!h->chain_plan_built)
       if (int rc = build_chain_plan(h)) return rc;
@@ -2985,6 +2987,7 @@ static int chain_launch(cmdp_t* h, const float* d_pi, const int32_t* d_act, cons
       if (int rc = set_lds(k_chain_fast<16>, flds)) return rc;
       hipLaunchKernelGGL((k_chain_fast<16>), dim3(B), dim3(1024), flds, st, c, f);
       c.mask = h->d_cf_slow.p;
+      h->chain_fast_ran = true;
     }
   }
   if (h->chain_exact) hipLaunchKernelGGL((k_chain_average_reward<16, true>), dim3(B), dim3(1024), lds, st, c);

@@ -223,7 +223,8 @@ enum { CMDP_STAT_DP_KERNEL_MS = 1, CMDP_STAT_DP_KERNEL = 2,
        CMDP_STAT_HIST_KERNEL_MS = 6,    /* ... and of its second kernel (k_trace_hist / k_reward_scan, the latter on the
                                            second stream unless CMDP_K1E_OVERLAP=0)                                         */
        CMDP_STAT_CHAIN_FAST_INSTANCES = 7 /* instances (evaluated or masked out) the last average-reward call did NOT hand to K9:
-                                             those K9F solved (irreducible chain, fill-reducing elimination order)          */,
+                                             those K9F solved (irreducible chain, fill-reducing elimination order); 0 when
+                                             that call did not launch K9F (exact order, no plan, K9F beyond the LDS budget) */,
        CMDP_STAT_REWARD_FILL_MS = 8,   /* CMDP_FLAG_REWARD_CACHE: host wall time spent drawing blocks (all host threads together
                                           count once: the time the calling thread waited for the draws)                       */
        CMDP_STAT_REWARD_ROUND_MS = 9   /* ... and wall time of the park rounds as a whole: copy of the park list, draws, install,
