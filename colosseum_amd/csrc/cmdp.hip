@@ -27,6 +27,7 @@ extern char** environ;
 #include "cmdp_k1u.h"
 #include "cmdp_k1e.h"
 #include "cmdp_rollout_plan.h"
+#include "cmdp_dp_plan.h"
 #include "cmdp_agent.h"
 #include "cmdp_chain.h"
 #include "cmdp_evi.h"
@@ -51,8 +52,6 @@ int fail(int code, const char* fmt, ...) {
     hipError_t e_ = (expr);                                                                    \
     if (e_ != hipSuccess) return fail(CMDP_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
   } while (0)
-
-constexpr int kDpBlock = 256;
 
 // Device buffer that only grows: hipFree (and often hipMalloc) synchronises the WHOLE device, which would serialise
 // handles that run concurrently on their own streams (benchmark runner: one host thread per device batch), so steady-state
@@ -89,12 +88,17 @@ struct DevBuf {
   ~DevBuf() { release(); }
 };
 
-// Page-locked host memory for the per-log read-backs of the logged loop.
+// Page-locked host memory for the per-log read-backs of the logged loop.  Only grows, like DevBuf.
 template <typename T>
 struct PinnedBuf {
   T* p = nullptr;
+  size_t cap = 0;
   int alloc(size_t n) {
+    if (p && n <= cap) return CMDP_OK;
+    if (p) (void)hipHostFree(p);
+    p = nullptr, cap = 0;
     HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&p), sizeof(T) * std::max<size_t>(n, 1), 0));
+    cap = std::max<size_t>(n, 1);
     return CMDP_OK;
   }
   ~PinnedBuf() { if (p) (void)hipHostFree(p); }
@@ -149,13 +153,9 @@ struct cmdp {
   hipEvent_t ev_dp0 = nullptr, ev_dp1 = nullptr;  // around the sweep kernel of the last discounted solve (cmdp_stat)
   hipEvent_t ev_row[2] = {nullptr, nullptr};      // logged loop: policy + state snapshot taken | evaluation of the row complete
   DevBuf<int32_t> d_cur_snap;                     // logged loop: current states at the row (the solve runs beside the next interval)
-  int last_dp_kernel = 0;     // CMDP_STAT_DP_KERNEL: 1 K2, 2 K2R, 5 K2U, 6 K3 (Gauss-Seidel)
-  float *zc_Q = nullptr, *zc_V = nullptr;   // discounted(): device aliases of page-locked result arrays (run_sweeps)
-  int64_t* zc_sweeps = nullptr;
-  bool zc_used = false;
-  PinnedBuf<int32_t> pin_status;   // ... and the per-instance status words of such a solve (read after the stream has drained)
-  size_t pin_status_n = 0;
-  int dp_kernel = 0;  // 0 auto, 1 LDS/global-CSR workgroup kernel, 2 register-resident kernel K2R, 5 its distinct-successor form K2U (3, 4: diameter only)
+  int last_dp_kernel = 0;     // CMDP_STAT_DP_KERNEL: 1 K2, 2 K2R, 5 K2U, 7 K2W, 6 K3 (Gauss-Seidel) -- SweepFamily
+  PinnedBuf<int32_t> pin_status;   // discounted(): the status words of a solve that stores into page-locked result arrays
+  int dp_kernel = 0;  // CMDP_OPT_DP_KERNEL: DP_KERNEL_AUTO .. DP_KERNEL_K2W (cmdp_dp_plan.h; 3, 4, 6: diameter only)
 
   DevBuf<int64_t> d_state_off, d_entry_base, d_start_off, d_csr_ptr;
   DevBuf<RowDesc> d_row;
@@ -1680,164 +1680,80 @@ int resolve_scheme(cmdp_t* h, int scheme, bool pe, bool diam, int* out) {
   return CMDP_OK;
 }
 
-// Launches the sweep kernels for `units` work items (instances, or (instance,target) pairs).
-int run_sweeps(cmdp_t* h, int mode, bool diam, int scheme, DpTables t, int64_t units) {
+DpShape dp_shape(const cmdp_t* h) { return {h->A, h->max_row_nnz, h->max_state_unique, h->max_S, h->max_inst_nnz}; }
+
+// The fields every DP kernel reads: the batch's CSR and its rewards.  The rest is zero; callers set what their kernel needs.
+DpTables dp_tables(const cmdp_t* h) {
+  DpTables t{};
+  t.B = h->B; t.A = h->A; t.state_off = h->d_state_off.p; t.csr_ptr = h->d_csr_ptr.p; t.csr_col = h->d_csr_col.p;
+  t.csr_val = h->d_csr_val.p; t.R = h->d_R.p;
+  return t;
+}
+
+// Device aliases of page-locked result arrays (discounted): the register-resident kernels touch Q, V and the sweep counts
+// exactly once, when an instance has converged, so they store into the caller's arrays directly (BatchedMDP.dp_buffers) --
+// the results of the instances that converge early cross PCIe under the sweeps of the rest, and no copy follows the kernel
+struct ZeroCopy {
+  float *Q = nullptr, *V = nullptr;  // both or neither
+  int64_t* sweeps = nullptr;         // null: the caller's counts are pageable (or not asked for)
+  int32_t* status = nullptr;
+  bool used = false;                 // run_sweeps: the kernel stored through these
+};
+
+// Launches the sweep kernel for `units` work items (instances, or (instance,target) pairs).
+int run_sweeps(cmdp_t* h, int mode, bool diam, int scheme, DpTables t, int64_t units, ZeroCopy* zc = nullptr) {
   hipStream_t st = h->stream;
   if (units > 0x7fffffffLL) return fail(CMDP_ERR_INVALID, "too many work items");
-  const size_t v_bytes = sizeof(float) * (size_t)h->max_S;
-  const DpTables t_dev = t;
-  h->zc_used = false;
-  if (scheme == CMDP_SCHEME_JACOBI && !diam && h->dp_kernel != 1) {
-    // The register-resident kernels touch Q, V and the sweep counts exactly once, when an instance has converged: if the
-    // caller's result arrays are page-locked (BatchedMDP.dp_buffers), the kernels store into them directly -- the results of
-    // the instances that converge early cross PCIe under the sweeps of the rest, and no copy follows the kernel
-    if (h->zc_V) {
-      t.Q = h->zc_Q; t.V = h->zc_V;
-      if (h->zc_sweeps) t.sweeps = h->zc_sweeps;
-      if (h->pin_status.p && h->pin_status_n >= (size_t)units) t.status = h->pin_status.p;
-    }
-    // register-resident CSR (K2R) when the shapes fit one of the compiled instantiations
-    const int A = h->A, K = h->max_row_nnz <= 4 ? 4 : (h->max_row_nnz <= 8 ? 8 : 0);
-    const int spt = h->max_S <= 256 ? 1 : (h->max_S <= 512 ? 2 : (h->max_S <= 1024 ? 4 : 0));
-    const size_t lds = 2 * sizeof(float) * 256 * (size_t)std::max(spt, 1) + sizeof(float) * 16;  // Va, Vb at fixed offsets
-    bool launched = true;
-    const dim3 grid((unsigned)units), block(256);
-    // K2U when the states' rows share their successors: U gathers instead of A x K (dp_kernel 5 forces it, 2 forbids it)
-    const int U = h->max_state_unique == 0 ? 0 : (h->max_state_unique <= 5 ? 5 : (h->max_state_unique <= 8 ? 8 : 0));
-    const bool want_u = U > 0 && K > 0 && spt > 0 && spt * U <= 20 && h->dp_kernel != 2 &&
-                        (h->dp_kernel == 5 || h->dp_kernel == 7 || 2 * U <= A * K);
-    if (h->dp_kernel == 5 && !want_u)
-      return fail(CMDP_ERR_UNSUPPORTED, "no distinct-successor instantiation (A=%d, %d distinct successors per state, %d states)",
-                  A, h->max_state_unique, h->max_S);
-    // K2W (one wavefront per instance, 5..7 states per lane): the batches the reference's scheme rule sends to Jacobi
-    // sweeps start at ~260 states, and up to 448 the whole instance fits a wavefront's registers.  Option 7 forces it,
-    // 5 keeps K2U.
-    const int sptw = (h->max_S + 63) / 64;
-    const bool want_w = want_u && U == 5 && K == 4 && sptw <= 7 && (h->dp_kernel == 7 || (h->dp_kernel == 0 && sptw >= 5));
-    if (h->dp_kernel == 7 && !want_w)
-      return fail(CMDP_ERR_UNSUPPORTED, "no one-wavefront instantiation (A=%d, %d distinct successors per state, %d non-zeros/row, %d states)",
-                  A, h->max_state_unique, h->max_row_nnz, h->max_S);
-    if (want_w) {
-      bool done = true;
-      const int st_w = sptw <= 5 ? 5 : sptw;
-      const size_t ldsw = 2 * sizeof(float) * 64 * (size_t)st_w;
-#define REGW_CASE(AT, ST)                                                                                        \
-  if (A == AT && st_w == ST) {                                                                                   \
-    if (mode == DP_VI) hipLaunchKernelGGL((k_dp_regw<DP_VI, AT, 5, 4, ST>), grid, dim3(64), ldsw, st, t);          \
-    else hipLaunchKernelGGL((k_dp_regw<DP_PE, AT, 5, 4, ST>), grid, dim3(64), ldsw, st, t);                        \
-  } else
-      // (only instantiations that keep their tables in registers: with four actions, seven states per lane -- and six under
-      // policy evaluation, which also holds the policy's rows -- spill to scratch; those batches take K2U below)
-      REGW_CASE(2, 5) REGW_CASE(2, 6) REGW_CASE(2, 7) REGW_CASE(3, 5) REGW_CASE(3, 6) REGW_CASE(3, 7)
-      REGW_CASE(4, 5)
-      if (A == 4 && st_w == 6 && mode == DP_VI) hipLaunchKernelGGL((k_dp_regw<DP_VI, 4, 5, 4, 6>), grid, dim3(64), ldsw, st, t);
-      else
-      { done = false; }
-#undef REGW_CASE
-      if (done) {
-        HIP_TRY(hipGetLastError());
-        h->last_dp_kernel = 7;
-        h->zc_used = h->zc_V != nullptr;
-        return CMDP_OK;
-      }
-      if (h->dp_kernel == 7) return fail(CMDP_ERR_UNSUPPORTED, "no one-wavefront instantiation for A=%d, %d states per lane%s", A, st_w,
-                                         mode == DP_PE ? " (policy evaluation)" : "");
-    }
-    if (want_u) {
-      bool done = true;
-#define REGU_CASE(AT, UT, KT, ST)                                                                             \
-  if (A == AT && U == UT && K == KT && spt == ST) {                                                           \
-    if (mode == DP_VI) hipLaunchKernelGGL((k_dp_regu<DP_VI, AT, UT, KT, ST>), grid, block, lds, st, t);        \
-    else hipLaunchKernelGGL((k_dp_regu<DP_PE, AT, UT, KT, ST>), grid, block, lds, st, t);                      \
-  } else
-      REGU_CASE(2, 5, 4, 1) REGU_CASE(2, 5, 4, 2) REGU_CASE(2, 5, 8, 1) REGU_CASE(2, 5, 8, 2)
-      REGU_CASE(3, 5, 4, 1) REGU_CASE(3, 5, 4, 2) REGU_CASE(3, 5, 8, 1) REGU_CASE(3, 5, 8, 2)
-      REGU_CASE(4, 5, 4, 1) REGU_CASE(4, 5, 4, 2) REGU_CASE(4, 5, 8, 1) REGU_CASE(4, 5, 8, 2)
-      REGU_CASE(2, 5, 4, 4) REGU_CASE(3, 5, 4, 4) REGU_CASE(4, 5, 4, 4) REGU_CASE(4, 5, 8, 4)
-      REGU_CASE(2, 5, 8, 4) REGU_CASE(3, 5, 8, 4)
-      REGU_CASE(3, 8, 8, 1) REGU_CASE(3, 8, 8, 2) REGU_CASE(4, 8, 4, 1) REGU_CASE(4, 8, 4, 2)
-      REGU_CASE(4, 8, 8, 1) REGU_CASE(4, 8, 8, 2)
-      { done = false; }
-#undef REGU_CASE
-      if (done) {
-        HIP_TRY(hipGetLastError());
-        h->last_dp_kernel = 5;
-        h->zc_used = h->zc_V != nullptr;
-        return CMDP_OK;
-      }
-      if (h->dp_kernel == 5)
-        return fail(CMDP_ERR_UNSUPPORTED, "no distinct-successor instantiation for A=%d, U=%d, %d non-zeros/row, %d states", A, U, h->max_row_nnz, h->max_S);
-    }
-#define REG_CASE(AT, KT, ST)                                                                                  \
-  if (A == AT && K == KT && spt == ST) {                                                                      \
-    if (mode == DP_VI) hipLaunchKernelGGL((k_dp_reg<DP_VI, AT, KT, ST>), grid, block, lds, st, t);             \
-    else hipLaunchKernelGGL((k_dp_reg<DP_PE, AT, KT, ST>), grid, block, lds, st, t);                           \
-  } else
-    REG_CASE(2, 4, 1) REG_CASE(2, 4, 2) REG_CASE(2, 4, 4)
-    REG_CASE(3, 4, 1) REG_CASE(3, 4, 2) REG_CASE(3, 4, 4)
-    REG_CASE(4, 4, 1) REG_CASE(4, 4, 2) REG_CASE(4, 4, 4)
-    REG_CASE(2, 8, 1) REG_CASE(2, 8, 2)
-    REG_CASE(3, 8, 1) REG_CASE(3, 8, 2)
-    REG_CASE(4, 8, 1) REG_CASE(4, 8, 2)
-    { launched = false; }
-#undef REG_CASE
-    if (launched) {
-      HIP_TRY(hipGetLastError());
-      h->last_dp_kernel = 2;
-      h->zc_used = h->zc_V != nullptr;
-      return CMDP_OK;
-    }
-    if (h->dp_kernel == 2) return fail(CMDP_ERR_UNSUPPORTED, "no register-resident instantiation for A=%d, %d non-zeros/row, %d states", A, h->max_row_nnz, h->max_S);
+  SweepChoice c{};
+  if (int rc = pick_sweep(dp_shape(h), mode, diam, scheme, h->dp_kernel, &c)) return rc;
+  if (zc && zc->V && c.reg()) {   // (the workgroup / wavefront kernels keep their working values in the device arrays)
+    t.Q = zc->Q; t.V = zc->V; t.status = zc->status;
+    if (zc->sweeps) t.sweeps = zc->sweeps;
+    zc->used = true;
   }
-  t = t_dev;   // the workgroup / wavefront kernels below keep their working values in the device arrays
-  if (scheme == CMDP_SCHEME_JACOBI) {
-    const size_t base = 2 * v_bytes + sizeof(float) * 4 * (kDpBlock / 64);
-    const size_t csr = sizeof(int32_t) * ((size_t)h->max_S * h->A + 1) + 8 * (size_t)h->max_inst_nnz +
-                       sizeof(float) * (size_t)h->max_S * h->A;
-    if (base > (size_t)kLdsBudget)
-      return fail(CMDP_ERR_UNSUPPORTED, "instance with %d states does not fit the LDS-resident sweep (2*4*S > 160 KiB)", h->max_S);
-    // CSR in LDS when two workgroups still fit on a CU; otherwise it is streamed from L2/HBM every sweep
-    const bool csr_lds = base + csr <= (size_t)kLdsBudget / 2;
-    const size_t lds = csr_lds ? base + csr : base;
-    const dim3 grid((unsigned)units), block(kDpBlock);
-#define LAUNCH_BLOCK(MODE, DIAM)                                                                         \
-  do {                                                                                                   \
-    if (csr_lds) {                                                                                       \
-      if (int rc = set_lds(k_dp_block<MODE, DIAM, true>, lds)) return rc;                                \
-      hipLaunchKernelGGL((k_dp_block<MODE, DIAM, true>), grid, block, lds, st, t);                        \
-    } else {                                                                                             \
-      if (int rc = set_lds(k_dp_block<MODE, DIAM, false>, lds)) return rc;                               \
-      hipLaunchKernelGGL((k_dp_block<MODE, DIAM, false>), grid, block, lds, st, t);                       \
-    }                                                                                                    \
-  } while (0)
-    if (diam) LAUNCH_BLOCK(DP_VI, true);
-    else if (mode == DP_VI) LAUNCH_BLOCK(DP_VI, false);
-    else LAUNCH_BLOCK(DP_PE, false);
-#undef LAUNCH_BLOCK
-    h->last_dp_kernel = 1;
-  } else {
-    if (v_bytes > (size_t)kLdsBudget)
-      return fail(CMDP_ERR_UNSUPPORTED, "instance with %d states does not fit the LDS-resident sweep", h->max_S);
-    const dim3 grid((unsigned)units), block(64);
-#define LAUNCH_WAVE(MODE, DIAM)                                                       \
-  do {                                                                                \
-    if (int rc = set_lds(k_dp_wave_gs<MODE, DIAM>, v_bytes)) return rc;               \
-    hipLaunchKernelGGL((k_dp_wave_gs<MODE, DIAM>), grid, block, v_bytes, st, t);       \
-  } while (0)
-    if (diam) LAUNCH_WAVE(DP_VI, true);
-    else if (mode == DP_VI) LAUNCH_WAVE(DP_VI, false);
-    else LAUNCH_WAVE(DP_PE, false);
-#undef LAUNCH_WAVE
-    h->last_dp_kernel = 6;
+  // every sweep kernel takes the tables alone; K2 and K3 may claim more than 64 KiB of LDS
+  auto launch = [&](void (*kernel)(DpTables)) -> int {
+    if (int rc = set_lds(kernel, c.lds)) return rc;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)units), dim3(c.block), c.lds, st, t);
+    return CMDP_OK;
+  };
+#define BOTH_MODES(NAME, ...) (mode == DP_VI ? launch(NAME<DP_VI, __VA_ARGS__>) : launch(NAME<DP_PE, __VA_ARGS__>))
+#define DIAM_MODES(NAME, ...)                                                                                   \
+  (diam ? launch(NAME<DP_VI, true, ##__VA_ARGS__>) : mode == DP_VI ? launch(NAME<DP_VI, false, ##__VA_ARGS__>) \
+                                                                   : launch(NAME<DP_PE, false, ##__VA_ARGS__>))
+#define K2W_VI_PE(AT, ST) BOTH_MODES(k_dp_regw, AT, 5, 4, ST)
+#define K2W_VI(AT, ST) launch(k_dp_regw<DP_VI, AT, 5, 4, ST>)
+#define K2W_CASE(AT, ST, MODES) c.A == AT && c.spt == ST ? K2W_##MODES(AT, ST) :
+#define K2U_CASE(AT, UT, KT, ST) c.A == AT && c.U == UT && c.K == KT && c.spt == ST ? BOTH_MODES(k_dp_regu, AT, UT, KT, ST) :
+#define K2R_CASE(AT, KT, ST) c.A == AT && c.K == KT && c.spt == ST ? BOTH_MODES(k_dp_reg, AT, KT, ST) :
+  int rc = CMDP_OK;   // (pick_sweep chose a compiled shape: the last alternative of a list is never taken)
+  switch (c.family) {
+    case SWEEP_K2W: rc = CMDP_K2W_SHAPES(K2W_CASE) CMDP_OK; break;
+    case SWEEP_K2U: rc = CMDP_K2U_SHAPES(K2U_CASE) CMDP_OK; break;
+    case SWEEP_K2R: rc = CMDP_K2R_SHAPES(K2R_CASE) CMDP_OK; break;
+    case SWEEP_K2: rc = c.csr_lds ? DIAM_MODES(k_dp_block, true) : DIAM_MODES(k_dp_block, false); break;
+    default: rc = DIAM_MODES(k_dp_wave_gs); break;
   }
+#undef K2R_CASE
+#undef K2U_CASE
+#undef K2W_CASE
+#undef K2W_VI
+#undef K2W_VI_PE
+#undef DIAM_MODES
+#undef BOTH_MODES
+  if (rc) return rc;
   HIP_TRY(hipGetLastError());
+  h->last_dp_kernel = c.family;
   return CMDP_OK;
 }
 
-int check_status(cmdp_t* h, int64_t units) {
-  std::vector<int32_t> status((size_t)units);
-  HIP_TRY(hipMemcpyAsync(status.data(), h->d_status.p, sizeof(int32_t) * units, hipMemcpyDeviceToHost, h->stream));
+// Waits for the stream and scans the status words of `units` work items: those in d_status, or `pinned` ones that the
+// kernel stored into page-locked host memory (nothing left to copy)
+int check_status(cmdp_t* h, int64_t units, const int32_t* pinned = nullptr) {
+  std::vector<int32_t> copy(pinned ? 0 : (size_t)units);
+  if (!pinned) HIP_TRY(hipMemcpyAsync(copy.data(), h->d_status.p, sizeof(int32_t) * units, hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(hipStreamSynchronize(h->stream));
+  const int32_t* status = pinned ? pinned : copy.data();
   for (int64_t u = 0; u < units; ++u) {
     if (status[u] == CMDP_ERR_MAX_ITER) return fail(CMDP_ERR_MAX_ITER, "work item %lld did not converge within max_sweeps", (long long)u);
     if (status[u] == CMDP_ERR_MAX_VALUE) return fail(CMDP_ERR_MAX_VALUE, "work item %lld exceeded max_abs_value", (long long)u);
@@ -1862,16 +1778,16 @@ int discounted(cmdp_t* h, int mode, const float* pi, float gamma, double eps, in
   if (h->d_V.n < (size_t)NS) HIP_TRY(h->d_V.alloc(NS));
   if (h->d_sweeps.n < (size_t)h->B) HIP_TRY(h->d_sweeps.alloc(h->B));
   if (h->d_status.n < (size_t)h->B) HIP_TRY(h->d_status.alloc(h->B));
-  DpTables t{};
-  t.B = h->B; t.A = h->A; t.state_off = h->d_state_off.p; t.csr_ptr = h->d_csr_ptr.p; t.csr_col = h->d_csr_col.p;
-  t.csr_val = h->d_csr_val.p; t.R = R_override ? h->d_Rov.p : h->d_R.p; t.pi = pi ? h->d_pi.p : nullptr;
-  t.unit_off = nullptr; t.gamma = gamma; t.eps = eps; t.max_abs = max_abs; t.max_sweeps = max_sweeps;
-  t.Q = h->d_Q.p; t.V = h->d_V.p; t.sweeps = h->d_sweeps.p; t.per_target = nullptr; t.status = h->d_status.p;
+  DpTables t = dp_tables(h);
+  if (R_override) t.R = h->d_Rov.p;
+  t.pi = pi ? h->d_pi.p : nullptr;
+  t.gamma = gamma; t.eps = eps; t.max_abs = max_abs; t.max_sweeps = max_sweeps;
+  t.Q = h->d_Q.p; t.V = h->d_V.p; t.sweeps = h->d_sweeps.p; t.status = h->d_status.p;
   if (!h->ev_dp0) {
     HIP_TRY(hipEventCreate(&h->ev_dp0));
     HIP_TRY(hipEventCreate(&h->ev_dp1));
   }
-  // device-visible aliases of page-locked result arrays (null for pageable memory): see run_sweeps
+  // device-visible aliases of page-locked result arrays (null for pageable memory)
   auto alias = [](void* p) -> void* {
     hipPointerAttribute_t a{};
     if (p && hipPointerGetAttributes(&a, p) == hipSuccess && a.type == hipMemoryTypeHost && a.devicePointer) return a.devicePointer;
@@ -1879,35 +1795,24 @@ int discounted(cmdp_t* h, int mode, const float* pi, float gamma, double eps, in
     return nullptr;
   };
   static const bool zc_env = !(std::getenv("CMDP_DP_ZERO_COPY") && std::atoi(std::getenv("CMDP_DP_ZERO_COPY")) == 0);
-  h->zc_Q = zc_env ? static_cast<float*>(alias(Q)) : nullptr;
-  h->zc_V = (zc_env && h->zc_Q) ? static_cast<float*>(alias(V)) : nullptr;
-  h->zc_sweeps = (h->zc_V && sweeps) ? static_cast<int64_t*>(alias(sweeps)) : nullptr;
-  if (!h->zc_V) h->zc_Q = nullptr;
-  if (h->zc_V && h->pin_status_n < (size_t)h->B) {
-    if (h->pin_status.p) { (void)hipHostFree(h->pin_status.p); h->pin_status.p = nullptr; }
+  ZeroCopy zc;
+  zc.Q = zc_env ? static_cast<float*>(alias(Q)) : nullptr;
+  zc.V = zc.Q ? static_cast<float*>(alias(V)) : nullptr;
+  if (!zc.V) zc.Q = nullptr;
+  if (zc.V) {
+    if (sweeps) zc.sweeps = static_cast<int64_t*>(alias(sweeps));
     if (int rc = h->pin_status.alloc((size_t)h->B)) return rc;
-    h->pin_status_n = (size_t)h->B;
+    zc.status = h->pin_status.p;
   }
   HIP_TRY(hipEventRecord(h->ev_dp0, st));
-  const int rc_run = run_sweeps(h, mode, false, sch, t, h->B);
-  const bool zc = h->zc_used, zc_sw = zc && h->zc_sweeps;
-  h->zc_Q = h->zc_V = nullptr; h->zc_sweeps = nullptr; h->zc_used = false;
-  if (rc_run) return rc_run;
+  if (int rc = run_sweeps(h, mode, false, sch, t, h->B, &zc)) return rc;
   HIP_TRY(hipEventRecord(h->ev_dp1, st));
-  if (!zc) {
+  if (!zc.used) {
     HIP_TRY(hipMemcpyAsync(Q, h->d_Q.p, sizeof(float) * R, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(V, h->d_V.p, sizeof(float) * NS, hipMemcpyDeviceToHost, st));
   }
-  if (sweeps && !zc_sw) HIP_TRY(hipMemcpyAsync(sweeps, h->d_sweeps.p, sizeof(int64_t) * h->B, hipMemcpyDeviceToHost, st));
-  if (zc) {   // the kernels wrote the status words into page-locked memory as well: nothing left to copy
-    HIP_TRY(hipStreamSynchronize(st));
-    for (int64_t u = 0; u < h->B; ++u) {
-      if (h->pin_status.p[u] == CMDP_ERR_MAX_ITER) return fail(CMDP_ERR_MAX_ITER, "work item %lld did not converge within max_sweeps", (long long)u);
-      if (h->pin_status.p[u] == CMDP_ERR_MAX_VALUE) return fail(CMDP_ERR_MAX_VALUE, "work item %lld exceeded max_abs_value", (long long)u);
-    }
-    return CMDP_OK;
-  }
-  return check_status(h, h->B);
+  if (sweeps && !(zc.used && zc.sweeps)) HIP_TRY(hipMemcpyAsync(sweeps, h->d_sweeps.p, sizeof(int64_t) * h->B, hipMemcpyDeviceToHost, st));
+  return check_status(h, h->B, zc.used ? zc.status : nullptr);
 }
 
 int episodic(cmdp_t* h, int mode, int H, const float* pi, const float* R_override, float* Q, float* V) {
@@ -1924,9 +1829,9 @@ int episodic(cmdp_t* h, int mode, int H, const float* pi, const float* R_overrid
   const size_t nq = (size_t)(H + 1) * R, nv = (size_t)(H + 1) * NS;
   if (h->d_Q.n < nq) HIP_TRY(h->d_Q.alloc(nq));
   if (h->d_V.n < nv) HIP_TRY(h->d_V.alloc(nv));
-  DpTables t{};
-  t.B = h->B; t.A = h->A; t.state_off = h->d_state_off.p; t.csr_ptr = h->d_csr_ptr.p; t.csr_col = h->d_csr_col.p;
-  t.csr_val = h->d_csr_val.p; t.R = R_override ? h->d_Rov.p : h->d_R.p; t.pi = pi ? h->d_pi.p : nullptr;
+  DpTables t = dp_tables(h);
+  if (R_override) t.R = h->d_Rov.p;
+  t.pi = pi ? h->d_pi.p : nullptr;
   const dim3 grid(h->B), block(kDpBlock);
   if (mode == DP_VI) {
     if (int rc = set_lds(k_episodic<DP_VI>, lds)) return rc;
@@ -2253,8 +2158,10 @@ static int diameter_lanes(cmdp_t* h, DpTables t, int64_t unit_lo, int64_t unit_h
   hipStream_t st = h->stream;
   std::vector<int32_t> inst, t0, cnt;
   std::vector<int64_t> vfl;  // floats per group
-  const int K_ell = h->max_row_nnz <= 2 ? 2 : (h->max_row_nnz <= 4 ? 4 : (h->max_row_nnz <= 8 ? 8 : 0));
-  const bool ell_ok = K_ell && h->dp_kernel != 4 && h->dp_kernel != 6 && h->A >= 2 && h->A <= 4 && h->A * K_ell <= 32;
+  // fixed-width-row kernels when a compiled (A, K) shape fits
+  const int A = h->A, K = fixed_width_K(h->max_row_nnz);
+  const bool fixed_ok = fixed_width_compiled(A, K);
+  const bool ell_ok = fixed_ok && h->dp_kernel != DP_KERNEL_K5S_CSR && h->dp_kernel != DP_KERNEL_K5T;
   // (two targets per lane -- value rows of 128 floats, the row walk paid once per 128 targets -- measured 2.47 s against
   // 1.79 s at C5: the wider rows halve every group's window in L2; not kept)
   // K5C: clusters of workgroups per group (k_diam_cluster) for instances large enough for the value rows to overflow the L2s;
@@ -2279,7 +2186,7 @@ static int diameter_lanes(cmdp_t* h, DpTables t, int64_t unit_lo, int64_t unit_h
   }
   const size_t G = inst.size();
   if (use_cluster && G > 0) {
-    if (int rc = ensure_ell(h, K_ell)) return rc;
+    if (int rc = ensure_ell(h, K)) return rc;
     const int n_clusters = h->cus / CLs;
     DiamClusterArgs ca{};
     ca.n_groups = (int)G; ca.n_clusters = n_clusters; ca.vstride = 2 * (int64_t)h->max_S * 64;
@@ -2299,7 +2206,6 @@ static int diameter_lanes(cmdp_t* h, DpTables t, int64_t unit_lo, int64_t unit_h
     ca.timeout_ticks = std::getenv("CMDP_K5C_TIMEOUT_TICKS") ? std::atoll(std::getenv("CMDP_K5C_TIMEOUT_TICKS")) : 200000000LL;
     DiamLanesArgs g{h->d_dl_inst.p, h->d_dl_t0.p, h->d_dl_cnt.p, nullptr, h->d_dl_v.p};
     const int32_t* new_of = h->ell_relabelled ? h->d_ell_newof.p : nullptr;
-    const int A = h->A, K = K_ell;
     const unsigned grid = (unsigned)(n_clusters * CLs);
     // first with the XCD-scope barriers (the members verify that they share an XCD); a cluster spread over XCDs makes the
     // launch end with err = 2 and it is repeated with agent-scope barriers; CMDP_K5C_SCOPE = agent skips the first form
@@ -2312,10 +2218,7 @@ static int diameter_lanes(cmdp_t* h, DpTables t, int64_t unit_lo, int64_t unit_h
     if (pass == 0) hipLaunchKernelGGL((k_diam_cluster<CLT, AT, KT, true>), dim3(grid), dim3(1024), 0, st, t, g, ca, h->d_ell_col.p, h->d_ell_val.p, new_of); \
     else hipLaunchKernelGGL((k_diam_cluster<CLT, AT, KT, false>), dim3(grid), dim3(1024), 0, st, t, g, ca, h->d_ell_col.p, h->d_ell_val.p, new_of); \
   } else
-#define K5C_SHAPES(CLT) K5C_CASE(CLT, 2, 2) K5C_CASE(CLT, 2, 4) K5C_CASE(CLT, 2, 8) K5C_CASE(CLT, 3, 2) K5C_CASE(CLT, 3, 4) \
-                        K5C_CASE(CLT, 3, 8) K5C_CASE(CLT, 4, 2) K5C_CASE(CLT, 4, 4) K5C_CASE(CLT, 4, 8)
-      K5C_SHAPES(8) K5C_SHAPES(16) K5C_SHAPES(32) { launched = false; }
-#undef K5C_SHAPES
+      CMDP_FIXED_WIDTH_SHAPES(K5C_CASE, 8) CMDP_FIXED_WIDTH_SHAPES(K5C_CASE, 16) CMDP_FIXED_WIDTH_SHAPES(K5C_CASE, 32) { launched = false; }
 #undef K5C_CASE
       if (!launched) break;
       HIP_TRY(hipGetLastError());
@@ -2357,37 +2260,34 @@ static int diameter_lanes(cmdp_t* h, DpTables t, int64_t unit_lo, int64_t unit_h
     HIP_TRY(h->d_dl_cnt.upload(cnt.data() + g0, n, st));
     HIP_TRY(h->d_dl_voff.upload(voff.data(), n, st));
     DiamLanesArgs g{h->d_dl_inst.p, h->d_dl_t0.p, h->d_dl_cnt.p, h->d_dl_voff.p, h->d_dl_v.p};
-    // fixed-width-row kernel when a compiled (A, K) shape fits; option value 4 keeps the generic CSR walker
-    const int A = h->A, K = h->max_row_nnz <= 2 ? 2 : (h->max_row_nnz <= 4 ? 4 : (h->max_row_nnz <= 8 ? 8 : 0));
     bool ell = false;
     // K5T (value rows gathered into LDS tiles per cluster of states): on request only (option 6).  At C5 it halves the
     // HBM traffic of K5S and is bit-equal, but runs 2.3 s against 2.05 s -- see DESIGN.md.
     bool tiles = false;
-    if (K && A >= 2 && A <= 4 && A * K <= 32 && h->dp_kernel == 6) {
+    if (fixed_ok && h->dp_kernel == DP_KERNEL_K5T) {
       if (h->tile_K != K) {
         const int rc = build_tiles(h, K);
-        if (rc != CMDP_OK && (rc != CMDP_ERR_UNSUPPORTED || h->dp_kernel == 6)) return rc;
+        if (rc != CMDP_OK && (rc != CMDP_ERR_UNSUPPORTED || h->dp_kernel == DP_KERNEL_K5T)) return rc;
       }
       // worth it only while the halo stays small (two rows gathered per state would equal K5S's traffic at best)
-      tiles = h->tile_K == K && (h->dp_kernel == 6 || h->tile_rows_per_state <= 2.0);
+      tiles = h->tile_K == K && (h->dp_kernel == DP_KERNEL_K5T || h->tile_rows_per_state <= 2.0);
     }
     if (tiles) {
       TileArgs ta{h->d_tl_c0.p, h->d_tl_ncl.p, h->d_tl_n.p, h->d_tl_R.p, h->d_tl_rows.p, h->d_tl_lcol.p, h->d_tl_val.p};
       const size_t lds = sizeof(float) * 64 * (size_t)kK5tRmax * kK5tNw;
       bool launched = true;
-#define TILE_CASE(AT, KT)                                                                                       \
+#define TILE_CASE(P, AT, KT)                                                                                     \
   if (A == AT && K == KT) {                                                                                     \
     if (int rc = set_lds(k_diam_tiles<kK5tNw, AT, KT, kK5tRmax>, lds)) return rc;                               \
     hipLaunchKernelGGL((k_diam_tiles<kK5tNw, AT, KT, kK5tRmax>), dim3((unsigned)n), dim3(kK5tNw * 64), lds, st, t, g, ta); \
   } else
-      TILE_CASE(2, 2) TILE_CASE(2, 4) TILE_CASE(2, 8) TILE_CASE(3, 2) TILE_CASE(3, 4) TILE_CASE(3, 8) TILE_CASE(4, 2)
-      TILE_CASE(4, 4) TILE_CASE(4, 8) { launched = false; }
+      CMDP_FIXED_WIDTH_SHAPES(TILE_CASE, _) { launched = false; }
 #undef TILE_CASE
       if (!launched) tiles = false;
     }
     if (tiles) {
       ell = true;  // handled
-    } else if (K && h->dp_kernel != 4 && A >= 2 && A <= 4 && A * K <= 32) {
+    } else if (fixed_ok && h->dp_kernel != DP_KERNEL_K5S_CSR) {   // option value 4 keeps the generic CSR walker
       if (int rc = ensure_ell(h, K)) return rc;
       const int32_t* new_of = h->ell_relabelled ? h->d_ell_newof.p : nullptr;
       ell = true;
@@ -2397,7 +2297,7 @@ static int diameter_lanes(cmdp_t* h, DpTables t, int64_t unit_lo, int64_t unit_h
       // (and 16 with the locality order: half as many groups share an L2, so a row is still there when the next chunk
       // wants it -- C5 1.83 -> 1.75 s)
       const int k5s_nw = k5s_env ? k5s_env : (((int64_t)n <= (int64_t)h->cus || h->ell_relabelled) ? 16 : 8);
-#define ELL_CASE(AT, KT)                                                                                          \
+#define ELL_CASE(P, AT, KT)                                                                                        \
   if (A == AT && K == KT) {                                                                                       \
     if (k5s_nw == 16)                                                                                             \
       hipLaunchKernelGGL((k_diam_lanes_ell<16, AT, KT>), dim3((unsigned)n), dim3(1024), 0, st, t, g, \
@@ -2409,8 +2309,7 @@ static int diameter_lanes(cmdp_t* h, DpTables t, int64_t unit_lo, int64_t unit_h
       hipLaunchKernelGGL((k_diam_lanes_ell<8, AT, KT>), dim3((unsigned)n), dim3(512), 0, st, t, g, \
                          h->d_ell_col.p, h->d_ell_val.p, new_of);                                                 \
   } else
-      ELL_CASE(2, 2) ELL_CASE(2, 4) ELL_CASE(2, 8) ELL_CASE(3, 2) ELL_CASE(3, 4) ELL_CASE(3, 8) ELL_CASE(4, 2)
-      ELL_CASE(4, 4) ELL_CASE(4, 8) { ell = false; }
+      CMDP_FIXED_WIDTH_SHAPES(ELL_CASE, _) { ell = false; }
 #undef ELL_CASE
     }
     if (!ell) hipLaunchKernelGGL(k_diam_lanes<8>, dim3((unsigned)n), dim3(512), 0, st, t, g);
@@ -2432,13 +2331,12 @@ int cmdp_diameter(cmdp_t* h, double epsilon, int scheme, int64_t max_sweeps, flo
   const int64_t NS = h->n_states;
   if (h->d_per_target.n < (size_t)NS) HIP_TRY(h->d_per_target.alloc(NS));
   if (h->d_status.n < (size_t)NS) HIP_TRY(h->d_status.alloc(NS));
-  DpTables t{};
-  t.B = h->B; t.A = h->A; t.state_off = h->d_state_off.p; t.csr_ptr = h->d_csr_ptr.p; t.csr_col = h->d_csr_col.p;
-  t.csr_val = h->d_csr_val.p; t.R = h->d_R.p; t.pi = nullptr; t.unit_off = h->d_state_off.p;
-  t.gamma = 1.0f; t.eps = epsilon; t.max_abs = 0.0; t.max_sweeps = max_sweeps;
-  t.Q = nullptr; t.V = nullptr; t.sweeps = nullptr; t.per_target = h->d_per_target.p; t.status = h->d_status.p;
-  const size_t v_need = 2 * sizeof(float) * (size_t)h->max_S + sizeof(float) * 4 * (kDpBlock / 64);
-  const bool lanes = sch == CMDP_SCHEME_JACOBI && (h->dp_kernel == 3 || h->dp_kernel == 4 || h->dp_kernel == 6 || v_need > (size_t)kLdsBudget);
+  DpTables t = dp_tables(h);
+  t.unit_off = h->d_state_off.p; t.gamma = 1.0f; t.eps = epsilon; t.max_sweeps = max_sweeps;
+  t.per_target = h->d_per_target.p; t.status = h->d_status.p;
+  // K5S on request, and when the value vectors of an instance do not fit the workgroup kernel's LDS
+  const bool lanes = sch == CMDP_SCHEME_JACOBI && (h->dp_kernel == DP_KERNEL_K5S || h->dp_kernel == DP_KERNEL_K5S_CSR ||
+                                                   h->dp_kernel == DP_KERNEL_K5T || k2_value_lds(h->max_S) > (size_t)kLdsBudget);
   if (lanes) {
     if (int rc = diameter_lanes(h, t, 0, NS)) return rc;
   } else if (int rc = run_sweeps(h, DP_VI, true, sch, t, NS)) return rc;
@@ -2463,9 +2361,8 @@ int cmdp_diameter_sparse_f64(cmdp_t* h, double epsilon, int64_t max_sweeps, doub
   hipStream_t st = h->stream;
   const int64_t NS = h->n_states;
   if (h->d_status.n < (size_t)NS) HIP_TRY(h->d_status.alloc(NS));
-  DpTables t{};
-  t.B = h->B; t.A = h->A; t.state_off = h->d_state_off.p; t.csr_ptr = h->d_csr_ptr.p; t.csr_col = h->d_csr_col.p;
-  t.csr_val = h->d_csr_val.p; t.eps = epsilon; t.max_sweeps = max_sweeps; t.status = h->d_status.p;
+  DpTables t = dp_tables(h);
+  t.eps = epsilon; t.max_sweeps = max_sweeps; t.status = h->d_status.p;
   constexpr int kLogCap = 2048;  // sweeps between diff < 0.05 and diff < eps that can be logged per target
   std::vector<int32_t> inst, t0, cnt;
   std::vector<int64_t> vdoubles;
@@ -2555,10 +2452,8 @@ int cmdp_diameter_range(cmdp_t* h, double epsilon, int64_t max_sweeps, int64_t t
   if (h->d_per_target.n < (size_t)NS) HIP_TRY(h->d_per_target.alloc(NS));
   if (h->d_status.n < (size_t)NS) HIP_TRY(h->d_status.alloc(NS));
   HIP_TRY(hipMemsetAsync(h->d_status.p, 0, sizeof(int32_t) * NS, st));
-  DpTables t{};
-  t.B = h->B; t.A = h->A; t.state_off = h->d_state_off.p; t.csr_ptr = h->d_csr_ptr.p; t.csr_col = h->d_csr_col.p;
-  t.csr_val = h->d_csr_val.p; t.R = h->d_R.p; t.pi = nullptr; t.unit_off = h->d_state_off.p;
-  t.gamma = 1.0f; t.eps = epsilon; t.max_abs = 0.0; t.max_sweeps = max_sweeps;
+  DpTables t = dp_tables(h);
+  t.unit_off = h->d_state_off.p; t.gamma = 1.0f; t.eps = epsilon; t.max_sweeps = max_sweeps;
   t.per_target = h->d_per_target.p; t.status = h->d_status.p;
   if (int rc = diameter_lanes(h, t, target_lo, target_hi)) return rc;
   HIP_TRY(hipMemcpyAsync(per_target, h->d_per_target.p + target_lo, sizeof(float) * (target_hi - target_lo),
@@ -2614,13 +2509,11 @@ int cmdp_diameter_episodic(cmdp_t* h, int H, const int64_t* start_off, const int
   HIP_TRY(d_sprob.upload(start_prob, start_off[B], st));
   if (h->d_per_target.n < (size_t)NS) HIP_TRY(h->d_per_target.alloc(NS));
   if (h->d_status.n < (size_t)NS) HIP_TRY(h->d_status.alloc(NS));
-  DpTables t{};
-  t.B = B; t.A = A; t.state_off = h->d_state_off.p; t.csr_ptr = h->d_csr_ptr.p; t.csr_col = h->d_csr_col.p;
-  t.csr_val = h->d_csr_val.p; t.R = h->d_R.p; t.unit_off = h->d_state_off.p; t.eps = epsilon; t.max_sweeps = max_sweeps;
+  DpTables t = dp_tables(h);
+  t.unit_off = h->d_state_off.p; t.eps = epsilon; t.max_sweeps = max_sweeps;
   t.per_target = h->d_per_target.p; t.status = h->d_status.p;
   EpiDiamArgs e{H, d_soff.p, d_sstate.p, d_sprob.p, d_reach.p};
-  if (lds > 64 * 1024)
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_diam_episodic), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  if (int rc = set_lds(k_diam_episodic, lds)) return rc;
   hipLaunchKernelGGL(k_diam_episodic, dim3((unsigned)NS), dim3(256), lds, st, t, e);
   HIP_TRY(hipGetLastError());
   std::vector<float> per((size_t)NS);
@@ -3448,11 +3341,9 @@ static int ql_enqueue_evaluate(cmdp_agent_t* a, float* v0_out = nullptr, int32_t
   const size_t nq = (size_t)(H + 1) * h->n_rows, nv = (size_t)(H + 1) * h->n_states;
   if (h->d_Q.n < nq) HIP_TRY(h->d_Q.alloc(nq));
   if (h->d_V.n < nv) HIP_TRY(h->d_V.alloc(nv));
-  DpTables t{};
-  t.B = h->B; t.A = h->A; t.state_off = h->d_state_off.p; t.csr_ptr = h->d_csr_ptr.p; t.csr_col = h->d_csr_col.p;
-  t.csr_val = h->d_csr_val.p; t.R = h->d_R.p; t.pi = a->d_pi.p;
-  if (lds > 64 * 1024)
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_episodic<DP_PE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  DpTables t = dp_tables(h);
+  t.pi = a->d_pi.p;
+  if (int rc = set_lds(k_episodic<DP_PE>, lds)) return rc;
   hipLaunchKernelGGL((k_episodic<DP_PE>), dim3(h->B), dim3(kDpBlock), lds, st, t, H, h->d_Q.p, h->d_V.p);
   HIP_TRY(hipGetLastError());
   // V[0, :] of instance b sits at (H+1)*state_off[b]: pack
@@ -3947,9 +3838,7 @@ int cmdp_value_norm(cmdp_t* h, const float* V, float* out) {
   HIP_TRY(h->d_V.upload(V, h->n_states, st));
   if (h->d_Ev.n < (size_t)h->n_rows) HIP_TRY(h->d_Ev.alloc(h->n_rows));
   if (h->d_out.n < (size_t)h->B) HIP_TRY(h->d_out.alloc(h->B));
-  DpTables t{};
-  t.B = h->B; t.A = h->A; t.state_off = h->d_state_off.p; t.csr_ptr = h->d_csr_ptr.p; t.csr_col = h->d_csr_col.p;
-  t.csr_val = h->d_csr_val.p; t.R = h->d_R.p;
+  const DpTables t = dp_tables(h);
   hipLaunchKernelGGL(k_value_norm, dim3(h->B), dim3(256), 0, st, t, h->d_V.p, h->d_Ev.p, h->d_out.p);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(out, h->d_out.p, sizeof(float) * h->B, hipMemcpyDeviceToHost, st));

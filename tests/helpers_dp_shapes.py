@@ -1,5 +1,5 @@
 """Synthetic CSR batches of exactly controlled shape for the discounted sweep kernels, a host mirror of the kernel choice
-of `run_sweeps` (colosseum_amd/csrc/cmdp.hip), the table of compiled register-resident instantiations, and float64
+of `pick_sweep` (colosseum_amd/csrc/cmdp_dp_plan.h), the table of compiled register-resident instantiations, and float64
 references (policy iteration and linear solves) of the discounted solutions.  Host only: no GPU is touched here."""
 import os
 import re
@@ -7,7 +7,7 @@ import re
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CMDP_HIP = os.path.join(ROOT, "colosseum_amd", "csrc", "cmdp.hip")
+DP_PLAN_H = os.path.join(ROOT, "colosseum_amd", "csrc", "cmdp_dp_plan.h")
 
 # CMDP_OPT_DP_KERNEL values and the STAT_DP_KERNEL codes of the sweep families
 AUTO, WORKGROUP, FORCE_K2R, FORCE_K2U, FORCE_K2W = 0, 1, 2, 5, 7
@@ -47,25 +47,21 @@ def shapes():
     return d
 
 
-def parse_compiled(path=CMDP_HIP):
-    """The same set as `compiled_cases`, read from the `REGW_CASE` / `REGU_CASE` / `REG_CASE` invocations of run_sweeps
-    and its hand-written (A == 4, st_w == 6, VI) one-wavefront launch."""
+def parse_compiled(path=DP_PLAN_H):
+    """The same set as `compiled_cases`, read from the shape lists `CMDP_K2R_SHAPES`, `CMDP_K2U_SHAPES` and
+    `CMDP_K2W_SHAPES` of cmdp_dp_plan.h: one X(...) per shape, the K2W rows marked VI_PE or VI."""
     src = open(path).read()
-    body = src[src.index("int run_sweeps("):]
-    body = body[:body.index("\n}\n")]
-    body = re.sub(r"#define[^\n]*(\\\n[^\n]*)*", "", body)  # the macro definitions themselves
     out = set()
-    for name, fam in (("REGW_CASE", "K2W"), ("REGU_CASE", "K2U"), ("REG_CASE", "K2R")):
-        for args in re.findall(r"\b%s\(([^)]*)\)" % name, body):
-            key = tuple(int(x) for x in args.split(","))
-            out |= {(fam, key, "VI"), (fam, key, "PE")}
-    for a, st in re.findall(r"if \(A == (\d+) && st_w == (\d+) && mode == DP_VI\) hipLaunchKernelGGL\(\(k_dp_regw<DP_VI, \1, 5, 4, \2>\)",
-                            body):
-        out.add(("K2W", (int(a), int(st)), "VI"))
+    for fam in ("K2R", "K2U", "K2W"):
+        body = re.search(r"#define CMDP_%s_SHAPES\(X\)((?:[^\n]*\\\n)*[^\n]*)" % fam, src).group(1)
+        for args in re.findall(r"\bX\(([^)]*)\)", body):
+            args = [a.strip() for a in args.split(",")]
+            modes = args.pop().split("_") if fam == "K2W" else ["VI", "PE"]
+            out |= {(fam, tuple(int(x) for x in args), m) for m in modes}
     return out
 
 
-# ---- host mirror of the shape statistics (cmdp_create) and of the kernel choice (run_sweeps) -----------------------------
+# ---- host mirror of the shape statistics (cmdp_create) and of the kernel choice (pick_sweep) -----------------------------
 def shape_stats(t):
     """(A, max row nnz, max distinct successors per state (0 when some row is not strictly ascending, or when the
     statistic is not gathered), max S, max nnz of one instance) as cmdp_create computes them."""
@@ -86,7 +82,7 @@ def shape_stats(t):
 
 
 def select(stats, mode, scheme=1, forced=AUTO):
-    """(family, key) that run_sweeps launches for a batch with `stats` (shape_stats), or (UNSUPPORTED, reason).
+    """(family, key) that pick_sweep chooses for a batch with `stats` (shape_stats), or (UNSUPPORTED, reason).
     family K2 has key "lds" / "hbm" (where the CSR lives), GS has key None."""
     A, nnz, mu, S, inst_nnz = stats
     if scheme == 1 and forced != WORKGROUP:

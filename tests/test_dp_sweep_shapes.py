@@ -1,7 +1,7 @@
 """Every compiled discounted sweep kernel against the oracle (bit for bit) and against float64 solutions.
 
 The Jacobi sweeps run on K2 (k_dp_block, CSR in LDS or HBM), K2R (k_dp_reg), K2U (k_dp_regu) or K2W (k_dp_regw), the
-Gauss-Seidel sweeps on k_dp_wave_gs; the register-resident families are template instantiations that run_sweeps picks by
+Gauss-Seidel sweeps on k_dp_wave_gs; the register-resident families are template instantiations that pick_sweep picks by
 the batch's shape (helpers_dp_shapes.select mirrors that choice).  All batches are synthetic, drawn with fixed seeds."""
 import ctypes
 
@@ -57,20 +57,20 @@ EDGE_IDS = [f"A{c[0]}-S{c[1][0]}-k{c[2]}-u{c[3]}" + ("" if c[4] else "-unsorted"
 
 
 def test_shape_table_is_the_compiled_list():
-    """The test's table of register-resident instantiations is exactly what run_sweeps compiles: 47 shapes, 93 kernels."""
+    """The test's table of register-resident instantiations is exactly what the shape lists of cmdp_dp_plan.h compile: 47 shapes, 93 kernels."""
     assert H.parse_compiled() == H.compiled_cases()
     assert len(H.compiled_cases()) == 93 and len(H.shapes()) == 47
 
 
 def test_shape_table_parser_sees_one_deleted_case(tmp_path):
-    src = open(H.CMDP_HIP).read()
-    cut = src.replace("REGU_CASE(4, 8, 4, 2)", "", 1)
-    assert cut != src
-    p = tmp_path / "cmdp.hip"
-    p.write_text(cut)
-    assert H.compiled_cases() - H.parse_compiled(str(p)) == {("K2U", (4, 8, 4, 2), "VI"), ("K2U", (4, 8, 4, 2), "PE")}
-    p.write_text(src.replace("  if (A == 4 && st_w == 6 && mode == DP_VI)", "  if (false)", 1))
-    assert H.compiled_cases() - H.parse_compiled(str(p)) == {("K2W", (4, 6), "VI")}
+    src = open(H.DP_PLAN_H).read()
+    p = tmp_path / "cmdp_dp_plan.h"
+    for row, lost in ((" X(4, 8, 4, 2)", {("K2U", (4, 8, 4, 2), "VI"), ("K2U", (4, 8, 4, 2), "PE")}),
+                      (" X(4, 6, VI)", {("K2W", (4, 6), "VI")})):
+        assert src.count(row) == 1
+        p.write_text(src.replace(row, ""))
+        assert H.compiled_cases() - H.parse_compiled(str(p)) == lost
+        assert H.parse_compiled(str(p)) <= H.compiled_cases()
 
 
 @pytest.mark.parametrize("fam,key", sorted(H.shapes()))
