@@ -30,6 +30,9 @@ STAT_REWARD_FILL_MS, STAT_REWARD_ROUND_MS = 8, 9
 STAT_DIAMETER_CLUSTER_LAUNCHES, STAT_DIAMETER_CLUSTER_FALLBACKS = 10, 11
 STAT_UCRL2_UNCONVERGED, STAT_UCRL2_ROUNDS, STAT_UCRL2_SOLVES, STAT_UCRL2_ROUND_MS = 12, 13, 14, 15
 STAT_UCRL2_WAIT_MS = 16
+STAT_PSRL_ROUNDS, STAT_PSRL_SOLVES, STAT_PSRL_SAMPLE_KERNEL_MS, STAT_PSRL_VI_KERNEL_MS, STAT_PSRL_REFERENCE_MS = 17, 18, 19, 20, 21
+PSRL_SAMPLER_REFERENCE, PSRL_SAMPLER_PHILOX = 0, 1
+PSRL_KEY_HI = 0x5053524C
 BOUND_CHERNOFF, BOUND_BERNSTEIN = 0, 1
 ACTOR_GREEDY, ACTOR_EPSILON_GREEDY, ACTOR_BOLTZMANN = 0, 1, 2
 UCRL2_OPT_MAX_SWEEPS = 1
@@ -53,6 +56,8 @@ EXPORTS = [
     "cmdp_set_reward_streams", "cmdp_legacy_beta", "cmdp_extended_vi",
     "cmdp_ucrl2_create", "cmdp_ucrl2_destroy", "cmdp_ucrl2_run", "cmdp_ucrl2_layout", "cmdp_ucrl2_model", "cmdp_ucrl2_last_solve",
     "cmdp_ucrl2_set_option",
+    "cmdp_psrl_create", "cmdp_psrl_destroy", "cmdp_psrl_run", "cmdp_psrl_layout", "cmdp_psrl_model", "cmdp_psrl_last_sample",
+    "cmdp_psrl_reference_sample", "cmdp_vi_episodic_dense", "cmdp_psrl_episode_end_update",
 ]
 
 
@@ -206,6 +211,15 @@ def load():
         L.cmdp_ucrl2_model.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         L.cmdp_ucrl2_last_solve.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         L.cmdp_ucrl2_set_option.argtypes = [vp, i32, i64]
+        L.cmdp_psrl_create.argtypes = [C.POINTER(vp), vp, vp, i64, vp, vp, i32, i32]
+        L.cmdp_psrl_destroy.argtypes = [vp]
+        L.cmdp_psrl_run.argtypes = [vp, i64, i32, vp, vp, vp, vp, vp, vp]
+        L.cmdp_psrl_episode_end_update.argtypes = [vp]
+        L.cmdp_psrl_layout.argtypes = [vp, vp, vp, vp]
+        L.cmdp_psrl_model.argtypes = [vp, vp, vp, vp, vp]
+        L.cmdp_psrl_last_sample.argtypes = [vp, vp, vp, vp]
+        L.cmdp_psrl_reference_sample.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, f32, vp, vp, vp]
+        L.cmdp_vi_episodic_dense.argtypes = [i32, vp, vp, i32, vp, vp, vp, vp]
         _lib = L
     return _lib
 

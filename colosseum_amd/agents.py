@@ -257,3 +257,159 @@ class BatchedUCRL2Continuous:
             self.close()
         except Exception:
             pass
+
+
+class BatchedPSRLEpisodic:
+    """One reference `PSRLEpisodic` (colosseum/agent/agents/episodic/posterior_sampling.py) per instance of an episodic
+    `BatchedMDP`, driven as `MDPLoop.run` drives it: interaction, the N_NIG / M_DIR posterior tables, the posterior sample,
+    the solve (k_vi_episodic_dense) and the actor's Q stay on the device (kernel K12, csrc/cmdp_psrl.h).  The keyword
+    names and defaults are the reference's.  `sampler="reference"` draws the reference's own numbers (numpy's legacy
+    samplers on the host, one RandomState(seed) per conjugate model); `sampler="philox"` draws on the device: the same
+    distributions from a counter-based stream, a pure function of (seed, episode, tables).  Per-pair prior lists, the
+    N_N reward model and the exploration actors are refused."""
+
+    _SAMPLERS = {"reference": L.PSRL_SAMPLER_REFERENCE, "philox": L.PSRL_SAMPLER_PHILOX}
+
+    def __init__(self, env: BatchedMDP, seeds: Sequence[int], optimization_horizon: int, reward_prior_model=None,
+                 transitions_prior_model=None, rewards_prior_prms=None, transitions_prior_prms=None, epsilon_greedy=None,
+                 boltzmann_temperature=None, sampler="reference"):
+        if sampler not in self._SAMPLERS:
+            raise ValueError(f"sampler {sampler!r}: 'reference' or 'philox'")
+        if epsilon_greedy is not None or boltzmann_temperature is not None:
+            raise NotImplementedError("only the greedy actor is built: epsilon_greedy and boltzmann_temperature must be None")
+        name = lambda m: getattr(m, "name", m)  # noqa: E731  (the reference passes enum members)
+        if reward_prior_model is not None and name(reward_prior_model) != "N_NIG":
+            raise NotImplementedError(f"reward_prior_model {name(reward_prior_model)!r}: only N_NIG is built")
+        if transitions_prior_model is not None and name(transitions_prior_model) != "M_DIR":
+            raise NotImplementedError(f"transitions_prior_model {name(transitions_prior_model)!r}: only M_DIR is built")
+        # bayesian_model.py:48-53: a prior model left None takes the reference's default parameters too
+        if reward_prior_model is None:
+            rewards_prior_prms = None
+        if transitions_prior_model is None:
+            transitions_prior_prms = None
+        for prms in (rewards_prior_prms, transitions_prior_prms):
+            if prms is not None and (isinstance(prms, dict) or type(prms[0]) in (list, tuple, np.ndarray)):
+                raise NotImplementedError("per-pair prior lists are not built: give one parameter list for all pairs")
+        self._lib = L.load()
+        self.env = env
+        seeds = np.ascontiguousarray(seeds, np.int32)
+        assert len(seeds) == env.B
+        if rewards_prior_prms is None:
+            rewards_prior_prms = [float(env.rewards_range[1]), 1, 1, 1]
+        assert len(rewards_prior_prms) == 4 and (transitions_prior_prms is None or len(transitions_prior_prms) == 1)
+        # base_conjugate.py:49 `np.tile(...).astype(np.float32)`, then N_NIG.__init__'s "interpretable parameters" transform
+        # (conjugate_rewards.py:54-63) with its float32 scalars: (mu, n_mu, n_tau * 0.5, (0.5 * n_tau) / tau)
+        mu, n_mu, tau, n_tau = np.tile(rewards_prior_prms, (1, 1, 1)).astype(np.float32)[0, 0]
+        hp = np.zeros(4, np.float32)
+        hp[:] = (mu, n_mu, n_tau * 0.5, (0.5 * n_tau) / tau)
+        rprior = np.ascontiguousarray(np.tile(hp, (env.B, 1)), np.float32)
+        if transitions_prior_prms is None:
+            tprior = np.array([np.tile([1.0 / int(S)], (1, 1, 1)).astype(np.float32)[0, 0, 0] for S in env.n_states], np.float32)
+        else:
+            tprior = np.full(env.B, np.tile(transitions_prior_prms, (1, 1, 1)).astype(np.float32)[0, 0, 0], np.float32)
+        self._h = C.c_void_p()
+        L.check(self._lib.cmdp_psrl_create(C.byref(self._h), env._h, L.ptr(seeds), int(optimization_horizon), L.ptr(rprior),
+                                           L.ptr(tprior), self._SAMPLERS[sampler], L.ACTOR_GREEDY))
+        env._register_agent(self)
+        nz = C.c_int64()
+        L.check(self._lib.cmdp_psrl_layout(self._h, C.byref(nz), None, None))
+        self._nz = int(nz.value)
+        self._ptr = np.zeros(int(env.row_off[-1]) + 1, np.int64)
+        self._col = np.zeros(self._nz, np.int32)
+        L.check(self._lib.cmdp_psrl_layout(self._h, None, L.ptr(self._ptr), L.ptr(self._col)))
+        self._rows = np.repeat(np.arange(len(self._ptr) - 1), np.diff(self._ptr))
+
+    def run(self, n_steps: int, train=True, trace: bool = False, stop_at_episode_end: bool = False):
+        """n_steps of select_action -> step -> step_update -> (episode_end_update, reset) per instance; with
+        `stop_at_episode_end` every instance stops after its next episode_end_update.  Returns `cumulative_reward` (since
+        creation), `steps_taken` [B] and, with `trace`, `actions`, `observations` (after the step; -1 at an episode's last
+        step) and float64 `rewards`, each [n_steps, B] with row t of instance b valid for t < steps_taken[b]."""
+        n_steps, B = int(n_steps), self.env.B
+        acts = np.zeros((n_steps, B), np.int8) if trace else None
+        obs = np.zeros((n_steps, B), np.int32) if trace else None
+        rew = np.zeros((n_steps, B), np.float64) if trace else None
+        rsum = np.zeros(B, np.float64)
+        taken = np.zeros(B, np.int64)
+        mask = None
+        if train is not True:
+            mask = np.ascontiguousarray(np.broadcast_to(np.asarray(train, bool), (B,)), np.uint8)
+        L.check(self._lib.cmdp_psrl_run(self._h, n_steps, int(bool(stop_at_episode_end)), L.ptr(mask), L.ptr(acts), L.ptr(obs),
+                                        L.ptr(rew), L.ptr(rsum), L.ptr(taken)))
+        return dict(cumulative_reward=rsum, steps_taken=taken, actions=acts, observations=obs, rewards=rew)
+
+    def episode_end_update(self):
+        """`PSRLEpisodic.episode_end_update()` for every instance: a new posterior sample on the tables as they are, its
+        solve and the new Q; no step is taken, the environment is not reset."""
+        L.check(self._lib.cmdp_psrl_episode_end_update(self._h))
+
+    def model(self):
+        """Per instance the reference model's tables: `transitions` dense [S, A, S] float32 (M_DIR.hyper_params) and
+        `rewards` [S, A, 4] float32 (N_NIG.hyper_params); `episode` [B]: posterior samples drawn so far."""
+        env = self.env
+        R = int(env.row_off[-1])
+        rp, tp = np.zeros(R * 4, np.float32), np.zeros(self._nz, np.float32)
+        prior, ep = np.zeros(env.B, np.float32), np.zeros(env.B, np.int64)
+        L.check(self._lib.cmdp_psrl_model(self._h, L.ptr(rp), L.ptr(tp), L.ptr(prior), L.ptr(ep)))
+        trans = []
+        for b in range(env.B):
+            S = int(env.n_states[b])
+            r0, r1 = int(env.row_off[b]), int(env.row_off[b + 1])
+            z0, z1 = int(self._ptr[r0]), int(self._ptr[r1])
+            M = np.full((r1 - r0, S), prior[b], np.float32)
+            M[self._rows[z0:z1] - r0, self._col[z0:z1]] = tp[z0:z1]
+            trans.append(M.reshape(S, env.A, S))
+        rew = [x.reshape(-1, env.A, 4) for x in env.split_rows(rp.reshape(R, 4))]
+        return dict(transitions=trans, rewards=rew, episode=ep)
+
+    def last_sample(self):
+        """The last posterior sample of every instance, `T` [S, A, S] and `R` [S, A] float32, and the `Q` [H + 1, S, A]
+        the actor holds (solved on them)."""
+        env, H = self.env, int(self.env.H)
+        R = int(env.row_off[-1])
+        nT = int(sum(int(S) * env.A * int(S) for S in env.n_states))
+        T, Rs, Q = np.zeros(nT, np.float32), np.zeros(R, np.float32), np.zeros((H + 1) * R, np.float32)
+        L.check(self._lib.cmdp_psrl_last_sample(self._h, L.ptr(T), L.ptr(Rs), L.ptr(Q)))
+        Ts, Qs, o = [], [], 0
+        for b in range(env.B):
+            S = int(env.n_states[b])
+            n = S * env.A * S
+            Ts.append(T[o:o + n].reshape(S, env.A, S))
+            o += n
+            q0 = (H + 1) * int(env.row_off[b])
+            Qs.append(Q[q0:q0 + (H + 1) * S * env.A].reshape(H + 1, S, env.A))
+        return dict(T=Ts, R=[x.reshape(-1, env.A) for x in env.split_rows(Rs)], Q=Qs)
+
+    def map_estimate(self):
+        """BayesianMDPModel.get_map_estimate per instance: (hyper_params / hyper_params.sum(-1, keepdims=True),
+        hyper_params[:, :, 0])."""
+        m = self.model()
+        return [(t / t.sum(-1, keepdims=True), r[:, :, 0]) for t, r in zip(m["transitions"], m["rewards"])]
+
+    def current_optimal_stochastic_policy(self):
+        """posterior_sampling.py:78-82 per instance: argmax_3d of episodic value iteration on the MAP estimate (host side:
+        it is called per log row only)."""
+        from .dynamic_programming import argmax_3d, episodic_value_iteration
+
+        return [argmax_3d(episodic_value_iteration(int(self.env.H), np.ascontiguousarray(T), np.ascontiguousarray(R))[0])
+                for T, R in self.map_estimate()]
+
+    def stats(self) -> dict:
+        """Rounds of parked instances, instances solved in them, HIP-event times of the last round's sample and solve
+        kernels, host time of the reference sampler's draws.  Kept per ENVIRONMENT handle."""
+        v, out = C.c_double(), {}
+        for k, w in (("rounds", L.STAT_PSRL_ROUNDS), ("solves", L.STAT_PSRL_SOLVES), ("sample_kernel_ms", L.STAT_PSRL_SAMPLE_KERNEL_MS),
+                     ("vi_kernel_ms", L.STAT_PSRL_VI_KERNEL_MS), ("reference_ms", L.STAT_PSRL_REFERENCE_MS)):
+            L.check(self._lib.cmdp_stat(self.env._h, w, C.byref(v)))
+            out[k] = float(v.value) if k.endswith("_ms") else int(v.value)
+        return out
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            self._lib.cmdp_psrl_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

@@ -74,6 +74,7 @@ class BatchedMDP:
         self.B, self.A, self.H = int(tables["B"]), int(tables["A"]), int(tables["H"])
         A = self.A
         rr = tables["rewards_range"]
+        self.rewards_range = (float(rr[0]), float(rr[1]))
         self.state_off = np.ascontiguousarray(tables["state_off"], np.int64)
         self.n_states = np.diff(self.state_off)
         self.row_off = self.state_off * A

@@ -20,6 +20,7 @@
 
 extern char** environ;
 
+#include <new>
 #include "cmdp_kernels.h"
 #include "cmdp_tracker.h"
 #include "cmdp_k1s.h"
@@ -32,6 +33,7 @@ extern char** environ;
 #include "cmdp_chain.h"
 #include "cmdp_evi.h"
 #include "cmdp_ucrl2.h"
+#include "cmdp_psrl.h"
 
 namespace {
 
@@ -270,6 +272,9 @@ struct cmdp {
   int64_t uc_rounds = 0, uc_solves = 0;
   double uc_round_ms = 0.0, uc_wait_ms = 0.0;
   DevBuf<int32_t> d_uc_unconverged;
+  // PSRL agents on this handle (cmdp_psrl_*): CMDP_STAT_PSRL_*
+  int64_t ps_rounds = 0, ps_solves = 0;
+  double ps_sample_ms = 0.0, ps_vi_ms = 0.0, ps_ref_ms = 0.0;
   DevBuf<float> d_dense;  // CMDP_LAYOUT_DENSE: [R][dense_spad]
   int dense_spad = 0;
   DevBuf<uint16_t> d_next16;
@@ -1525,6 +1530,11 @@ int cmdp_stat(cmdp_t* h, int which, double* out) {
   }
   if (which == CMDP_STAT_UCRL2_ROUNDS || which == CMDP_STAT_UCRL2_SOLVES || which == CMDP_STAT_UCRL2_ROUND_MS) {
     *out = which == CMDP_STAT_UCRL2_ROUNDS ? (double)h->uc_rounds : which == CMDP_STAT_UCRL2_SOLVES ? (double)h->uc_solves : h->uc_round_ms;
+    return CMDP_OK;
+  }
+  if (which >= CMDP_STAT_PSRL_ROUNDS && which <= CMDP_STAT_PSRL_REFERENCE_MS) {
+    *out = which == CMDP_STAT_PSRL_ROUNDS ? (double)h->ps_rounds : which == CMDP_STAT_PSRL_SOLVES ? (double)h->ps_solves
+           : which == CMDP_STAT_PSRL_SAMPLE_KERNEL_MS ? h->ps_sample_ms : which == CMDP_STAT_PSRL_VI_KERNEL_MS ? h->ps_vi_ms : h->ps_ref_ms;
     return CMDP_OK;
   }
   if (which == CMDP_STAT_UCRL2_UNCONVERGED) {
@@ -4204,5 +4214,492 @@ int cmdp_ucrl2_last_solve(cmdp_ucrl2_t* a, float* P_val, float* uniform, float* 
   return CMDP_OK;
 }
 #undef UC_FETCH
+
+}  // extern "C"
+
+// ---- PSRL on the device (K12, cmdp_psrl.h) --------------------------------------------------------------------------
+struct cmdp_psrl {
+  cmdp_t* env = nullptr;
+  int sampler = CMDP_PSRL_SAMPLER_REFERENCE;
+  int64_t nz = 0, t_total = 0;
+  size_t sample_lds = 0, vi_lds = 0;
+  std::vector<int64_t> steps_total;    // [B] transitions taken since creation: bounds the float32 counts' exactness check
+  std::vector<int64_t> h_toff, h_ptr;  // [B] padded offsets of the dense T; the layout (reference sampler)
+  std::vector<int32_t> h_col;
+  std::vector<float> h_prior, h_tp, h_rp, h_T, h_R;
+  std::vector<cmdp_rc::NumpyStream> ts, rs;   // [B] RandomState(seed) of M_DIR and of N_NIG (reference sampler)
+  PsArgs args{};
+  DevBuf<int64_t> d_row_ptr, d_episode, d_toff, d_roff, d_taken;
+  DevBuf<int32_t> d_col, d_slot, d_mtpos, d_park, d_S, d_A, d_obs;
+  DevBuf<float> d_tp, d_tprior, d_rp, d_T, d_Rs, d_Q, d_V;
+  DevBuf<double> d_rsum, d_rew;
+  DevBuf<long long> d_left;
+  DevBuf<uint32_t> d_mt;
+  DevBuf<uint2> d_key;
+  DevBuf<int8_t> d_act;
+  DevBuf<uint8_t> d_mask;
+  PinnedBuf<int32_t> pin_park;   // [2 + B]: park count, unused, park list
+  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};   // around k_psrl_sample and k_vi_episodic_dense of the last round
+  bool ev_sample = false, ev_vi = false;
+  ~cmdp_psrl() {
+    for (hipEvent_t e : ev)
+      if (e) (void)hipEventDestroy(e);
+  }
+};
+
+namespace {
+
+// K12's solver on device-resident arguments: what cmdp_vi_episodic_dense does after its uploads and what the PSRL agent
+// does for the instances of a round
+int dvi_launch(const DviArgs& g, int count, size_t lds, hipStream_t st) {
+  if (int rc = set_lds(k_vi_episodic_dense, lds)) return rc;
+  hipLaunchKernelGGL(k_vi_episodic_dense, dim3(count), dim3(PSRL_VI_THREADS), lds, st, g);
+  HIP_TRY(hipGetLastError());
+  return CMDP_OK;
+}
+
+void psrl_times(cmdp_psrl_t* a) {   // after a stream synchronisation: the last round's kernel times
+  float ms = 0.0f;
+  if (a->ev_sample && hipEventElapsedTime(&ms, a->ev[0], a->ev[1]) == hipSuccess) a->env->ps_sample_ms = ms;
+  if (a->ev_vi && hipEventElapsedTime(&ms, a->ev[2], a->ev[3]) == hipSuccess) a->env->ps_vi_ms = ms;
+  (void)hipGetLastError();
+}
+
+// sample -> solve (straight into the actor's Q) -> reset -> release for the `count` instances of pin_park's list (already on
+// the device at d_park + 2)
+int psrl_round(cmdp_psrl_t* a, int count, int do_reset, int stop, int64_t n_steps) {
+  cmdp_t* h = a->env;
+  hipStream_t st = h->stream;
+  const int A = h->A;
+  const int32_t* list = a->d_park.p + 2;
+  if (a->sampler == CMDP_PSRL_SAMPLER_PHILOX) {
+    const int bpi = grid_for((int64_t)h->max_S * A, PSRL_SAMPLE_THREADS / 64);
+    HIP_TRY(hipEventRecord(a->ev[0], st));
+    if (int rc = set_lds(k_psrl_sample, a->sample_lds)) return rc;
+    hipLaunchKernelGGL(k_psrl_sample, dim3((unsigned)((int64_t)bpi * count)), dim3(PSRL_SAMPLE_THREADS), a->sample_lds, st,
+                       a->args, list, h->d_state_off.p, A, h->max_S, bpi);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(a->ev[1], st));
+    a->ev_sample = true;
+  } else {
+    HIP_TRY(hipMemcpyAsync(a->h_tp.data(), a->d_tp.p, sizeof(float) * a->nz, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(a->h_rp.data(), a->d_rp.p, sizeof(float) * 4 * h->n_rows, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const auto t0 = std::chrono::steady_clock::now();
+    const int32_t* hl = a->pin_park.p + 2;
+    cmdp_rc::Pool::get().parallel_for(count, [&](int k) {   // one stream pair per instance: sequential inside, parallel across
+      const int b = hl[k];
+      const int64_t soff = h->state_off[b];
+      const int S = (int)(h->state_off[b + 1] - soff);
+      psrl_host::reference_draw(a->ts[b], a->rs[b], S, A, nullptr, a->h_ptr.data() + soff * A, a->h_col.data(), a->h_tp.data(),
+                                a->h_prior[b], a->h_rp.data() + soff * A * 4, a->h_T.data() + a->h_toff[b],
+                                a->h_R.data() + soff * A);
+    });
+    h->ps_ref_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    for (int k = 0; k < count; ++k) {
+      const int b = hl[k];
+      const int64_t soff = h->state_off[b], S = h->state_off[b + 1] - soff;
+      HIP_TRY(hipMemcpyAsync(a->d_T.p + a->h_toff[b], a->h_T.data() + a->h_toff[b], sizeof(float) * S * A * S, hipMemcpyHostToDevice, st));
+      HIP_TRY(hipMemcpyAsync(a->d_Rs.p + soff * A, a->h_R.data() + soff * A, sizeof(float) * S * A, hipMemcpyHostToDevice, st));
+    }
+  }
+  DviArgs g{list, a->d_S.p, a->d_A.p, a->d_toff.p, a->d_roff.p, h->d_state_off.p, a->d_T.p, a->d_Rs.p, a->d_Q.p, a->d_V.p, h->H};
+  HIP_TRY(hipEventRecord(a->ev[2], st));
+  if (int rc = dvi_launch(g, count, a->vi_lds, st)) return rc;
+  HIP_TRY(hipEventRecord(a->ev[3], st));
+  a->ev_vi = true;
+  hipLaunchKernelGGL(k_psrl_resume, dim3(grid_for(count, 256)), dim3(256), 0, st, h->env(), a->args, list, count, do_reset, stop,
+                     n_steps);
+  HIP_TRY(hipGetLastError());
+  h->ps_rounds += 1;
+  h->ps_solves += count;
+  return CMDP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int cmdp_psrl_create(cmdp_psrl_t** out, cmdp_t* env, const int32_t* seeds, int64_t optimization_horizon,
+                     const float* reward_prior, const float* transition_prior, int sampler, int actor) {
+  if (!out) return fail(CMDP_ERR_INVALID, "null output");
+  *out = nullptr;
+  if (sampler != CMDP_PSRL_SAMPLER_REFERENCE && sampler != CMDP_PSRL_SAMPLER_PHILOX)
+    return fail(CMDP_ERR_INVALID, "sampler %d: CMDP_PSRL_SAMPLER_REFERENCE or CMDP_PSRL_SAMPLER_PHILOX", sampler);
+  if (actor != CMDP_ACTOR_GREEDY)
+    return fail(CMDP_ERR_UNSUPPORTED, "only the greedy actor is built: epsilon-greedy and Boltzmann exploration are not");
+  if (!env || !seeds || !reward_prior || !transition_prior)
+    return fail(CMDP_ERR_INVALID, "null argument (environment handle, seeds or priors)");
+  if (optimization_horizon < 1) return fail(CMDP_ERR_INVALID, "optimization_horizon < 1");
+  if (int rc = bind(env)) return rc;
+  if (!env->has_env) return fail(CMDP_ERR_INVALID, "the environment handle was created without the sampler half");
+  if (env->H <= 0) return fail(CMDP_ERR_UNSUPPORTED, "PSRLEpisodic is the episodic setting's agent (PSRLContinuous is not built): "
+                               "the environment handle is continuous");
+  if (env->layout != CMDP_LAYOUT_CSR) return fail(CMDP_ERR_UNSUPPORTED, "agents run on the CSR layout");
+  if (env->reward_cache) return fail(CMDP_ERR_UNSUPPORTED, "CMDP_FLAG_REWARD_CACHE handles are not supported by the PSRL agent: "
+                                     "its walk kernel does not park for reward blocks");
+  if (env->max_S > PSRL_MAX_STATES)
+    return fail(CMDP_ERR_UNSUPPORTED, "an instance has %d states: the dense solver (K12) takes at most %d", env->max_S, PSRL_MAX_STATES);
+  const int B = env->B, A = env->A, H = env->H;
+  const int64_t R = env->n_rows, E = env->n_entries;
+  if ((int64_t)env->max_S * A * env->max_S > 0xffffffffLL)
+    return fail(CMDP_ERR_UNSUPPORTED, "S * A * S of an instance exceeds 2^32: the Philox counter holds row * S + column in 32 bits");
+  for (int b = 0; b < B; ++b) {
+    const float* rp = reward_prior + 4 * b;
+    if (!(transition_prior[b] > 0.0f) || !std::isfinite(transition_prior[b]))
+      return fail(CMDP_ERR_INVALID, "transition_prior[%d] = %g is not a finite value > 0", b, (double)transition_prior[b]);
+    if (!std::isfinite(rp[0]) || !(rp[1] > 0.0f) || !(rp[2] > 0.0f) || !(rp[3] > 0.0f) || !std::isfinite(rp[1]) || !std::isfinite(rp[2]) ||
+        !std::isfinite(rp[3]))
+      return fail(CMDP_ERR_INVALID, "reward_prior[%d]: mu finite, lambda, alpha and beta finite and > 0", b);
+  }
+  hipStream_t st = env->stream;
+  cmdp_psrl_t* a = new cmdp_psrl;
+  struct Guard { cmdp_psrl_t* a; ~Guard() { delete a; } } guard{a};
+  a->env = env;
+  a->sampler = sampler;
+  a->steps_total.assign((size_t)B, 0);
+  // K11's layout from the sampler's: per row the distinct successors in ascending order, every entry mapped to its position
+  std::vector<RowDesc> rows((size_t)R);
+  std::vector<int32_t> nxt((size_t)E);
+  std::vector<int64_t> ebase((size_t)B);
+  HIP_TRY(hipMemcpyAsync(rows.data(), env->d_row.p, sizeof(RowDesc) * R, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(nxt.data(), env->d_sp_next.p, sizeof(int32_t) * E, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(ebase.data(), env->d_entry_base.p, sizeof(int64_t) * B, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  std::vector<int64_t>& ptr = a->h_ptr;
+  std::vector<int32_t>& col = a->h_col;
+  ptr.assign((size_t)R + 1, 0);
+  std::vector<int32_t> slot((size_t)E, 0), tmp;
+  std::vector<float> tp;
+  for (int b = 0; b < B; ++b)
+    for (int64_t r = env->state_off[b] * A; r < env->state_off[b + 1] * A; ++r) {
+      const int64_t lo = ebase[b] + rows[(size_t)r].first, n = rows[(size_t)r].n;
+      tmp.assign(nxt.begin() + lo, nxt.begin() + lo + n);
+      std::sort(tmp.begin(), tmp.end());
+      tmp.erase(std::unique(tmp.begin(), tmp.end()), tmp.end());
+      const int64_t z0 = (int64_t)col.size();
+      for (int64_t e = lo; e < lo + n; ++e)
+        slot[(size_t)e] = (int32_t)(z0 + (std::lower_bound(tmp.begin(), tmp.end(), nxt[(size_t)e]) - tmp.begin()));
+      col.insert(col.end(), tmp.begin(), tmp.end());
+      tp.insert(tp.end(), tmp.size(), transition_prior[b]);
+      ptr[(size_t)r + 1] = (int64_t)col.size();
+    }
+  const int64_t NZ = (int64_t)col.size();
+  if (NZ > 0x7fffffffLL) return fail(CMDP_ERR_UNSUPPORTED, "more than 2^31 successor positions");
+  a->nz = NZ;
+  std::vector<int32_t> hS((size_t)B), hA((size_t)B, A);
+  std::vector<int64_t> roff((size_t)B);
+  std::vector<float> rp((size_t)R * 4);
+  std::vector<uint2> keys((size_t)B);
+  a->h_toff.assign((size_t)B, 0);
+  a->h_prior.assign(transition_prior, transition_prior + B);
+  int64_t tt = 0;
+  for (int b = 0; b < B; ++b) {
+    const int64_t soff = env->state_off[b], S = env->state_off[b + 1] - soff;
+    hS[b] = (int32_t)S;
+    roff[b] = soff * A;
+    a->h_toff[b] = tt;
+    tt += (S * A * S + 3) & ~(int64_t)3;   // every instance's T starts on a 16-byte boundary
+    for (int64_t r = soff * A; r < (soff + S) * A; ++r) std::memcpy(&rp[(size_t)r * 4], reward_prior + 4 * b, 4 * sizeof(float));
+    keys[b] = make_uint2((uint32_t)seeds[b], CMDP_PSRL_KEY_HI);
+  }
+  a->t_total = tt;
+  a->sample_lds = (size_t)(PSRL_SAMPLE_THREADS / 64) * env->max_S * sizeof(float);
+  a->vi_lds = (size_t)2 * ((env->max_S + 3) & ~3) * sizeof(float);
+  if (tt > (int64_t)1 << 40 || a->d_T.alloc((size_t)tt) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(CMDP_ERR_OVERFLOW, "the dense workspace of the sampled transition models cannot be allocated: %lld bytes for the "
+                "batch (sum of S * A * S float32) -- create smaller batches", (long long)(tt * 4));
+  }
+  HIP_TRY(a->d_T.zero(st));
+  HIP_TRY(a->d_row_ptr.upload(ptr.data(), ptr.size(), st));
+  HIP_TRY(a->d_col.upload(col.data(), col.size(), st));
+  HIP_TRY(a->d_slot.upload(slot.data(), slot.size(), st));
+  HIP_TRY(a->d_tp.upload(tp.data(), tp.size(), st));
+  HIP_TRY(a->d_tprior.upload(transition_prior, B, st));
+  HIP_TRY(a->d_rp.upload(rp.data(), rp.size(), st));
+  HIP_TRY(a->d_toff.upload(a->h_toff.data(), B, st));
+  HIP_TRY(a->d_roff.upload(roff.data(), B, st));
+  HIP_TRY(a->d_S.upload(hS.data(), B, st));
+  HIP_TRY(a->d_A.upload(hA.data(), B, st));
+  HIP_TRY(a->d_key.upload(keys.data(), B, st));
+#define PS_ZERO(buf, n) HIP_TRY(a->buf.alloc((size_t)(n))); HIP_TRY(a->buf.zero(st))
+  PS_ZERO(d_episode, B); PS_ZERO(d_Rs, R); PS_ZERO(d_Q, (size_t)(H + 1) * R); PS_ZERO(d_V, (size_t)(H + 1) * env->n_states);
+  PS_ZERO(d_left, B); PS_ZERO(d_taken, B); PS_ZERO(d_park, B + 2); PS_ZERO(d_rsum, B);
+#undef PS_ZERO
+  HIP_TRY(a->d_mt.alloc((size_t)B * 624));
+  HIP_TRY(a->d_mtpos.alloc(B));
+  if (int rc = a->pin_park.alloc((size_t)B + 2)) return rc;
+  for (hipEvent_t& e : a->ev) HIP_TRY(hipEventCreate(&e));
+  std::vector<uint32_t> useeds((size_t)B);
+  for (int b = 0; b < B; ++b) useeds[b] = (uint32_t)seeds[b];
+  DevBuf<uint32_t> d_seeds;
+  HIP_TRY(d_seeds.upload(useeds.data(), B, st));
+  hipLaunchKernelGGL(k_mt_seed_numpy, dim3(grid_for(B, 64)), dim3(64), 0, st, a->d_mt.p, a->d_mtpos.p, d_seeds.p, B);
+  HIP_TRY(hipGetLastError());
+  if (sampler == CMDP_PSRL_SAMPLER_REFERENCE) {
+    a->ts.resize((size_t)B);
+    a->rs.resize((size_t)B);
+    for (int b = 0; b < B; ++b) { psrl_host::seed_numpy(a->ts[b], useeds[b]); psrl_host::seed_numpy(a->rs[b], useeds[b]); }
+    try {
+      a->h_tp.resize((size_t)NZ); a->h_rp.resize((size_t)R * 4); a->h_T.resize((size_t)tt); a->h_R.resize((size_t)R);
+    } catch (const std::bad_alloc&) {
+      return fail(CMDP_ERR_OVERFLOW, "the host staging of the reference sampler's dense models cannot be allocated: %lld bytes "
+                  "for the batch -- create smaller batches", (long long)(tt * 4));
+    }
+  }
+  PsArgs& p = a->args;
+  p.row_ptr = a->d_row_ptr.p; p.col = a->d_col.p; p.slot = a->d_slot.p;
+  p.tp = a->d_tp.p; p.tprior = a->d_tprior.p; p.rp = a->d_rp.p; p.episode = a->d_episode.p; p.key = a->d_key.p;
+  p.t_off = a->d_toff.p; p.T = a->d_T.p; p.Rs = a->d_Rs.p; p.Q = a->d_Q.p; p.V = a->d_V.p;
+  p.mt = a->d_mt.p; p.mt_pos = a->d_mtpos.p;
+  p.left = a->d_left.p; p.taken = a->d_taken.p; p.park_count = a->d_park.p; p.park_list = a->d_park.p + 2;
+  // before_start_interacting (posterior_sampling.py:146-147): one episode_end_update on the prior -- every instance
+  a->pin_park.p[0] = B; a->pin_park.p[1] = 0;
+  for (int b = 0; b < B; ++b) a->pin_park.p[2 + b] = b;
+  HIP_TRY(hipMemcpyAsync(a->d_park.p, a->pin_park.p, sizeof(int32_t) * (B + 2), hipMemcpyHostToDevice, st));
+  if (int rc = psrl_round(a, B, 0, 0, 0)) return rc;
+  HIP_TRY(hipStreamSynchronize(st));
+  psrl_times(a);
+  env->uc_backrefs.push_back(&a->env);
+  guard.a = nullptr;
+  *out = a;
+  return CMDP_OK;
+}
+
+int cmdp_psrl_destroy(cmdp_psrl_t* a) {
+  if (!a) return CMDP_OK;
+  if (a->env) {   // null once the environment handle has been destroyed (its stream was drained then)
+    (void)hipSetDevice(a->env->device);
+    (void)hipStreamSynchronize(a->env->stream);
+    auto& v = a->env->uc_backrefs;
+    v.erase(std::remove(v.begin(), v.end(), &a->env), v.end());
+  }
+  delete a;
+  return CMDP_OK;
+}
+
+int cmdp_psrl_run(cmdp_psrl_t* a, int64_t n_steps, int stop_at_episode_end, const uint8_t* train_mask, int8_t* actions_trace,
+                  int32_t* obs_trace, double* reward_trace, double* cumulative_reward, int64_t* steps_taken) {
+  if (!a) return fail(CMDP_ERR_INVALID, "null agent");
+  cmdp_t* h = a->env;
+  if (int rc = bind(h)) return rc;
+  if (n_steps < 0) return fail(CMDP_ERR_INVALID, "n_steps < 0");
+  bool any = false;
+  if (int rc = any_needs_reset(h, &any)) return rc;
+  if (any) return fail(CMDP_ERR_NEEDS_RESET, "the environment needs reset() before the agent can run");
+  const int B = h->B;
+  hipStream_t st = h->stream;
+  if (int rc = visits_check(h, n_steps)) return rc;
+  for (int b = 0; b < B; ++b)
+    if (a->steps_total[b] + n_steps > (1LL << 24))
+      return fail(CMDP_ERR_OVERFLOW, "a transition count of the model (float32, as the reference's hyper-parameters) would stop "
+                  "counting at 2^24: instance %d has taken %lld steps, %lld more asked for", b, (long long)a->steps_total[b],
+                  (long long)n_steps);
+  const size_t NB = (size_t)n_steps * B;
+  if (actions_trace && a->d_act.n < NB) HIP_TRY(a->d_act.alloc(NB));
+  if (obs_trace && a->d_obs.n < NB) HIP_TRY(a->d_obs.alloc(NB));
+  if (reward_trace && a->d_rew.n < NB) HIP_TRY(a->d_rew.alloc(NB));
+  const uint8_t* dmask = nullptr;
+  if (train_mask) {
+    HIP_TRY(a->d_mask.upload(train_mask, B, st));
+    dmask = a->d_mask.p;
+  }
+  std::vector<long long> left((size_t)B, (long long)n_steps);
+  std::vector<int64_t> taken((size_t)B, n_steps);
+  HIP_TRY(hipMemcpyAsync(a->d_left.p, left.data(), sizeof(long long) * B, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(a->d_taken.p, taken.data(), sizeof(int64_t) * B, hipMemcpyHostToDevice, st));
+  int rc = CMDP_OK;
+  while (n_steps > 0) {
+    HIP_TRY(hipMemsetAsync(a->d_park.p, 0, sizeof(int32_t) * 2, st));
+    hipLaunchKernelGGL(k_psrl_walk, dim3(grid_for(B, 256)), dim3(256), 0, st, h->env(), a->args, n_steps, dmask,
+                       actions_trace ? a->d_act.p : nullptr, obs_trace ? a->d_obs.p : nullptr,
+                       reward_trace ? a->d_rew.p : nullptr, a->d_rsum.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(a->pin_park.p, a->d_park.p, sizeof(int32_t) * (B + 2), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));   // the previous round's kernels and this walk
+    psrl_times(a);
+    const int count = a->pin_park.p[0];
+    if (count == 0) break;
+    std::sort(a->pin_park.p + 2, a->pin_park.p + 2 + count);   // the order instances parked in is not deterministic
+    HIP_TRY(hipMemcpyAsync(a->d_park.p + 2, a->pin_park.p + 2, sizeof(int32_t) * count, hipMemcpyHostToDevice, st));
+    if ((rc = psrl_round(a, count, 1, stop_at_episode_end ? 1 : 0, n_steps))) break;
+    if (stop_at_episode_end) break;   // every instance either finished its steps or has just been stopped
+  }
+  if (rc == CMDP_OK && n_steps > 0) {
+    HIP_TRY(hipMemcpyAsync(taken.data(), a->d_taken.p, sizeof(int64_t) * B, hipMemcpyDeviceToHost, st));
+    if (actions_trace) HIP_TRY(hipMemcpyAsync(actions_trace, a->d_act.p, NB, hipMemcpyDeviceToHost, st));
+    if (obs_trace) HIP_TRY(hipMemcpyAsync(obs_trace, a->d_obs.p, sizeof(int32_t) * NB, hipMemcpyDeviceToHost, st));
+    if (reward_trace) HIP_TRY(hipMemcpyAsync(reward_trace, a->d_rew.p, sizeof(double) * NB, hipMemcpyDeviceToHost, st));
+  }
+  if (cumulative_reward) HIP_TRY(hipMemcpyAsync(cumulative_reward, a->d_rsum.p, sizeof(double) * B, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  psrl_times(a);
+  for (int b = 0; b < B; ++b) {
+    a->steps_total[b] += rc == CMDP_OK ? taken[b] : n_steps;
+    if (steps_taken) steps_taken[b] = taken[b];
+  }
+  return visits_commit(h, n_steps, rc);
+}
+
+int cmdp_psrl_episode_end_update(cmdp_psrl_t* a) {
+  if (!a) return fail(CMDP_ERR_INVALID, "null agent");
+  cmdp_t* h = a->env;
+  if (int rc = bind(h)) return rc;
+  const int B = h->B;
+  hipStream_t st = h->stream;
+  a->pin_park.p[0] = B; a->pin_park.p[1] = 0;
+  for (int b = 0; b < B; ++b) a->pin_park.p[2 + b] = b;
+  HIP_TRY(hipMemcpyAsync(a->d_park.p, a->pin_park.p, sizeof(int32_t) * (B + 2), hipMemcpyHostToDevice, st));
+  if (int rc = psrl_round(a, B, 0, 0, 0)) return rc;
+  HIP_TRY(hipStreamSynchronize(st));
+  psrl_times(a);
+  return CMDP_OK;
+}
+
+int cmdp_psrl_layout(cmdp_psrl_t* a, int64_t* n_positions, int64_t* row_ptr, int32_t* col) {
+  if (!a) return fail(CMDP_ERR_INVALID, "null agent");
+  cmdp_t* h = a->env;
+  if (int rc = bind(h)) return rc;
+  if (n_positions) *n_positions = a->nz;
+  if (row_ptr) std::memcpy(row_ptr, a->h_ptr.data(), sizeof(int64_t) * (h->n_rows + 1));
+  if (col) std::memcpy(col, a->h_col.data(), sizeof(int32_t) * a->nz);
+  return CMDP_OK;
+}
+
+int cmdp_psrl_model(cmdp_psrl_t* a, float* reward_hp, float* transition_hp, float* transition_prior, int64_t* episodes) {
+  if (!a) return fail(CMDP_ERR_INVALID, "null agent");
+  cmdp_t* h = a->env;
+  if (int rc = bind(h)) return rc;
+  hipStream_t st = h->stream;
+  if (reward_hp) HIP_TRY(hipMemcpyAsync(reward_hp, a->d_rp.p, sizeof(float) * 4 * h->n_rows, hipMemcpyDeviceToHost, st));
+  if (transition_hp) HIP_TRY(hipMemcpyAsync(transition_hp, a->d_tp.p, sizeof(float) * a->nz, hipMemcpyDeviceToHost, st));
+  if (transition_prior) std::memcpy(transition_prior, a->h_prior.data(), sizeof(float) * h->B);
+  if (episodes) HIP_TRY(hipMemcpyAsync(episodes, a->d_episode.p, sizeof(int64_t) * h->B, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return CMDP_OK;
+}
+
+int cmdp_psrl_last_sample(cmdp_psrl_t* a, float* T, float* R, float* Q) {
+  if (!a) return fail(CMDP_ERR_INVALID, "null agent");
+  cmdp_t* h = a->env;
+  if (int rc = bind(h)) return rc;
+  hipStream_t st = h->stream;
+  if (T) {
+    int64_t o = 0;
+    for (int b = 0; b < h->B; ++b) {   // the workspace pads every instance to 16 bytes; the caller's array is dense
+      const int64_t S = h->state_off[b + 1] - h->state_off[b], n = S * h->A * S;
+      HIP_TRY(hipMemcpyAsync(T + o, a->d_T.p + a->h_toff[b], sizeof(float) * n, hipMemcpyDeviceToHost, st));
+      o += n;
+    }
+  }
+  if (R) HIP_TRY(hipMemcpyAsync(R, a->d_Rs.p, sizeof(float) * h->n_rows, hipMemcpyDeviceToHost, st));
+  if (Q) HIP_TRY(hipMemcpyAsync(Q, a->d_Q.p, sizeof(float) * (h->H + 1) * h->n_rows, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return CMDP_OK;
+}
+
+int cmdp_psrl_reference_sample(uint32_t* t_key, int32_t* t_pos, int32_t* t_has_gauss, double* t_gauss, uint32_t* r_key,
+                               int32_t* r_pos, int32_t* r_has_gauss, double* r_gauss, int n_states, int n_actions,
+                               const float* transition_hp_dense, const int64_t* row_ptr, const int32_t* col, const float* val,
+                               float prior, const float* reward_hp, float* T, float* R) {
+  if (!t_key || !t_pos || !t_has_gauss || !t_gauss || !r_key || !r_pos || !r_has_gauss || !r_gauss || !reward_hp || !T || !R)
+    return fail(CMDP_ERR_INVALID, "null argument");
+  if (n_states < 1 || n_actions < 1) return fail(CMDP_ERR_INVALID, "n_states and n_actions must be >= 1");
+  if (!transition_hp_dense && (!row_ptr || !col || !val || !(prior > 0.0f)))
+    return fail(CMDP_ERR_INVALID, "transition hyper-parameters: a dense array, or a layout (row_ptr, col, val) and a prior > 0");
+  if (*t_pos < 0 || *t_pos > 624 || *r_pos < 0 || *r_pos > 624) return fail(CMDP_ERR_INVALID, "MT19937 position outside [0, 624]");
+  const int64_t SA = (int64_t)n_states * n_actions;
+  if (transition_hp_dense) {
+    for (int64_t i = 0; i < SA * n_states; ++i)
+      if (!(transition_hp_dense[i] >= 0.0f)) return fail(CMDP_ERR_INVALID, "transition hyper-parameter %lld is negative or NaN", (long long)i);
+  } else {
+    for (int64_t r = 0; r < SA; ++r) {
+      if (row_ptr[r + 1] < row_ptr[r]) return fail(CMDP_ERR_INVALID, "row_ptr decreases at row %lld", (long long)r);
+      for (int64_t z = row_ptr[r]; z < row_ptr[r + 1]; ++z)
+        if (col[z] < 0 || col[z] >= n_states || (z > row_ptr[r] && col[z] <= col[z - 1]) || !(val[z] >= 0.0f))
+          return fail(CMDP_ERR_INVALID, "row %lld of the layout: columns ascending within [0, %d), values >= 0", (long long)r, n_states);
+    }
+  }
+  for (int64_t r = 0; r < SA; ++r)
+    if (!(reward_hp[4 * r + 1] > 0.0f) || !(reward_hp[4 * r + 2] > 0.0f) || !(reward_hp[4 * r + 3] > 0.0f))
+      return fail(CMDP_ERR_INVALID, "reward hyper-parameters of row %lld: lambda, alpha and beta must be > 0", (long long)r);
+  cmdp_rc::NumpyStream ts, rs;
+  std::memcpy(ts.key, t_key, sizeof ts.key);
+  ts.pos = *t_pos; ts.has_gauss = *t_has_gauss; ts.gauss = *t_gauss;
+  std::memcpy(rs.key, r_key, sizeof rs.key);
+  rs.pos = *r_pos; rs.has_gauss = *r_has_gauss; rs.gauss = *r_gauss;
+  psrl_host::reference_draw(ts, rs, n_states, n_actions, transition_hp_dense, row_ptr, col, val, prior, reward_hp, T, R);
+  std::memcpy(t_key, ts.key, sizeof ts.key);
+  *t_pos = ts.pos; *t_has_gauss = ts.has_gauss; *t_gauss = ts.gauss;
+  std::memcpy(r_key, rs.key, sizeof rs.key);
+  *r_pos = rs.pos; *r_has_gauss = rs.has_gauss; *r_gauss = rs.gauss;
+  return CMDP_OK;
+}
+
+int cmdp_vi_episodic_dense(int count, const int32_t* n_states, const int32_t* n_actions, int H, const float* T, const float* R,
+                           float* Q, float* V) {
+  if (count < 0) return fail(CMDP_ERR_INVALID, "count %d is negative", count);
+  if (count == 0) return CMDP_OK;
+  if (!n_states || !n_actions || !T || !R || !Q || !V) return fail(CMDP_ERR_INVALID, "null argument");
+  if (H < 1) return fail(CMDP_ERR_INVALID, "H %d < 1", H);
+  std::vector<int64_t> soff((size_t)count + 1), roff((size_t)count), toff((size_t)count), tsrc((size_t)count);
+  int64_t ns = 0, nr = 0, nt = 0, nsrc = 0;
+  int max_S = 1;
+  for (int b = 0; b < count; ++b) {
+    const int64_t S = n_states[b], A = n_actions[b];
+    if (S < 1) return fail(CMDP_ERR_INVALID, "n_states[%d] = %d < 1", b, (int)S);
+    if (A < 1) return fail(CMDP_ERR_INVALID, "n_actions[%d] = %d < 1", b, (int)A);
+    if (S > PSRL_MAX_STATES)
+      return fail(CMDP_ERR_UNSUPPORTED, "instance %d has %d states: the dense episodic solver keeps two value layers in LDS for at "
+                  "most %d states", b, (int)S, PSRL_MAX_STATES);
+    soff[b] = ns; roff[b] = nr; toff[b] = nt; tsrc[b] = nsrc;
+    ns += S; nr += S * A; nsrc += S * A * S;
+    nt += (S * A * S + 3) & ~(int64_t)3;
+    max_S = std::max(max_S, (int)S);
+  }
+  soff[count] = ns;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(CMDP_ERR_NO_DEVICE, "no HIP device visible");
+  // Workspace reused across calls, one per device, deliberately leaked at exit; calls are serialised by a mutex
+  struct Ws {
+    DevBuf<int32_t> S, A;
+    DevBuf<int64_t> soff, roff, toff;
+    DevBuf<float> T, R, Q, V;
+    hipStream_t st = nullptr;
+  };
+  static std::mutex mu;
+  static std::map<int, Ws*>* all = new std::map<int, Ws*>;
+  std::lock_guard<std::mutex> lock(mu);
+  int dev = 0;
+  HIP_TRY(hipGetDevice(&dev));
+  Ws*& ws = (*all)[dev];
+  if (!ws) {
+    ws = new Ws;
+    HIP_TRY(hipStreamCreateWithFlags(&ws->st, hipStreamNonBlocking));
+  }
+  hipStream_t st = ws->st;
+  HIP_TRY(ws->S.upload(n_states, count, st));
+  HIP_TRY(ws->A.upload(n_actions, count, st));
+  HIP_TRY(ws->soff.upload(soff.data(), count + 1, st));
+  HIP_TRY(ws->roff.upload(roff.data(), count, st));
+  HIP_TRY(ws->toff.upload(toff.data(), count, st));
+  if (ws->T.alloc((size_t)nt) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(CMDP_ERR_OVERFLOW, "the dense transition models cannot be held on the device: %lld bytes", (long long)(nt * 4));
+  }
+  for (int b = 0; b < count; ++b)
+    HIP_TRY(hipMemcpyAsync(ws->T.p + toff[b], T + tsrc[b], sizeof(float) * (size_t)n_states[b] * n_actions[b] * n_states[b],
+                           hipMemcpyHostToDevice, st));
+  HIP_TRY(ws->R.upload(R, (size_t)nr, st));
+  HIP_TRY(ws->Q.alloc((size_t)(H + 1) * nr));
+  HIP_TRY(ws->V.alloc((size_t)(H + 1) * ns));
+  DviArgs g{nullptr, ws->S.p, ws->A.p, ws->toff.p, ws->roff.p, ws->soff.p, ws->T.p, ws->R.p, ws->Q.p, ws->V.p, H};
+  if (int rc = dvi_launch(g, count, (size_t)2 * ((max_S + 3) & ~3) * sizeof(float), st)) return rc;
+  HIP_TRY(hipMemcpyAsync(Q, ws->Q.p, sizeof(float) * (size_t)(H + 1) * nr, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(V, ws->V.p, sizeof(float) * (size_t)(H + 1) * ns, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return CMDP_OK;
+}
 
 }  // extern "C"

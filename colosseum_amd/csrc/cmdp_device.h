@@ -15,6 +15,11 @@
 //           (A = 2: 128 one-bit actions per block, least significant bit of word 0 first);
 //           any other A: block n >> 2, word (n & 3), a = (word * A) >> 32 (four actions per block).
 // domain 3, n = transition index, c3 = draw counter : Beta reward of the transition (philox_beta below)
+// domain 6, PSRL transition sample (cmdp_psrl.h), key = (agent seed, CMDP_PSRL_KEY_HI): n = episode << 32 | (row * S + column)
+//           with row = s * A + a instance-relative (S * A * S < 2^32 is checked at creation), c3 = draw counter of
+//           philox_gamma: the gamma variate of element (row, column) of the Dirichlet sample of episode `episode`
+// domain 7, PSRL reward sample, same key: n = episode << 32 | row, c3 = draw counter: philox_gamma for tau, then ONE more
+//           block whose four words give the two uniforms of a Box-Muller normal (sqrt(-2 log(1 - u1)) cos(2 pi u2))
 // ---------------------------------------------------------------------------------------------------
 __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,
                                               uint32_t k1, uint32_t (&w)[4]) {

@@ -86,6 +86,31 @@ def episodic_value_iteration(H, T, R, max_value=None):
     return Q, V
 
 
+def episodic_value_iteration_dense_batch(problems, H):
+    """`episodic_value_iteration(H, T, R)` for many dense (T [S, A, S], R [S, A]) float32 problems in one launch of
+    k_vi_episodic_dense (the PSRL agent's solver; the problems may differ in S and A): the dot products are accumulated in
+    float64 in a fixed order and rounded once.  Returns [(Q [H + 1, S, A], V [H + 1, S]) per problem]."""
+    problems = [(np.ascontiguousarray(T, np.float32), np.ascontiguousarray(R, np.float32)) for T, R in problems]
+    if not problems:
+        return []
+    S = np.array([T.shape[0] for T, _ in problems], np.int32)
+    A = np.array([T.shape[1] for T, _ in problems], np.int32)
+    for (T, R), s, a in zip(problems, S, A):
+        assert T.shape == (s, a, s) and R.shape == (s, a), (T.shape, R.shape)
+    Tc = np.concatenate([T.ravel() for T, _ in problems])
+    Rc = np.concatenate([R.ravel() for _, R in problems])
+    H = int(H)
+    Q = np.zeros((H + 1) * int((S * A).sum()), np.float32)
+    V = np.zeros((H + 1) * int(S.sum()), np.float32)
+    L.check(L.load().cmdp_vi_episodic_dense(len(problems), L.ptr(S), L.ptr(A), H, L.ptr(Tc), L.ptr(Rc), L.ptr(Q), L.ptr(V)))
+    out, q0, v0 = [], 0, 0
+    for s, a in zip(S.tolist(), A.tolist()):
+        nq, nv = (H + 1) * s * a, (H + 1) * s
+        out.append((Q[q0:q0 + nq].reshape(H + 1, s, a), V[v0:v0 + nv].reshape(H + 1, s)))
+        q0, v0 = q0 + nq, v0 + nv
+    return out
+
+
 def episodic_policy_evaluation(H, T, R, policy):
     """reference finite_horizon.py:29-42; policy [H,S,A]."""
     S, A, _ = T.shape

@@ -239,8 +239,13 @@ enum { CMDP_STAT_DP_KERNEL_MS = 1, CMDP_STAT_DP_KERNEL = 2,
        CMDP_STAT_UCRL2_ROUND_MS = 15     /* ... host wall time from reading a park list to having enqueued its round (and,
                                             with stop_at_episode_end, to the round's completion)                              */,
        CMDP_STAT_UCRL2_WAIT_MS = 16      /* ... host wall time spent waiting for the stream inside cmdp_ucrl2_run's rounds: the
-                                            device's share (walk kernel + the previous round's bounds, K10 and update)       */ };
-/* The UCRL2 statistics belong to the environment handle: agents created on the same handle share them. */
+                                            device's share (walk kernel + the previous round's bounds, K10 and update)       */,
+       CMDP_STAT_PSRL_ROUNDS = 17,           /* PSRL agents of this handle: rounds of parked instances (sample -> solve -> reset)  */
+       CMDP_STAT_PSRL_SOLVES = 18,           /* ... instances solved in those rounds (= episodes, the solve on the prior included) */
+       CMDP_STAT_PSRL_SAMPLE_KERNEL_MS = 19, /* ... HIP-event time of the last round's k_psrl_sample (Philox sampler)              */
+       CMDP_STAT_PSRL_VI_KERNEL_MS = 20,     /* ... HIP-event time of the last round's k_vi_episodic_dense                         */
+       CMDP_STAT_PSRL_REFERENCE_MS = 21      /* ... host wall time spent in the reference sampler's draws, all rounds together     */ };
+/* The UCRL2 and PSRL statistics belong to the environment handle: agents created on the same handle share them. */
 int cmdp_stat(cmdp_t* h, int which, double* out);
 /* Latency floor of the LDS-resident rollout kernels, measured on the current device: one wavefront per CU follows
    per-lane uint16 tables in LDS for n_steps dependent reads.  CMDP_CALIB_LDS_READ: the bare dependent ds_read_u16
@@ -589,6 +594,60 @@ int cmdp_ucrl2_last_solve(cmdp_ucrl2_t* a, float* P_val, float* uniform, float* 
    not-converged path. */
 enum { CMDP_UCRL2_OPT_MAX_SWEEPS = 1 };
 int cmdp_ucrl2_set_option(cmdp_ucrl2_t* a, int option, int64_t value);
+
+/* One PSRLEpisodic (colosseum/agent/agents/episodic/posterior_sampling.py with BayesianMDPModel, N_NIG rewards and M_DIR
+   transitions) per instance of an EPISODIC environment handle, driven as MDPLoop.run drives it
+   (agent_mdp_interaction.py:224-298).  The interaction, the posterior tables, the posterior sample, the solve
+   (k_vi_episodic_dense) and the actor's Q stay on the device (K12, csrc/cmdp_psrl.h).  seeds [B] seed the greedy actor's
+   tie-break stream, the reference sampler's two RandomState streams and the Philox sampler's key (seed, CMDP_PSRL_KEY_HI).
+   reward_prior [B][4]: N_NIG's hyper-parameters (mu, lambda, alpha, beta) float32 AFTER the "interpretable parameters"
+   transform of N_NIG.__init__; transition_prior [B]: M_DIR's prior, the same for every element of the instance.
+   sampler: CMDP_PSRL_SAMPLER_REFERENCE draws the reference's own numbers on the host (numpy's legacy samplers, one
+   RandomState(seed) per conjugate model and instance); CMDP_PSRL_SAMPLER_PHILOX draws on the device (k_psrl_sample:
+   distribution-exact, counter-based, a pure function of (key, episode, tables)).  actor: CMDP_ACTOR_GREEDY; the others
+   are CMDP_ERR_UNSUPPORTED, as are continuous handles, CMDP_FLAG_REWARD_CACHE handles and instances with more than 4096
+   states.  CMDP_ERR_OVERFLOW when the dense workspace of the sampled models (sum of S * A * S float32) cannot be
+   allocated.  Creation performs before_start_interacting: the first sample and solve, on the prior. */
+enum { CMDP_PSRL_SAMPLER_REFERENCE = 0, CMDP_PSRL_SAMPLER_PHILOX = 1 };
+#define CMDP_PSRL_KEY_HI 0x5053524Cu
+typedef struct cmdp_psrl cmdp_psrl_t;
+int cmdp_psrl_create(cmdp_psrl_t** out, cmdp_t* env, const int32_t* seeds, int64_t optimization_horizon,
+                     const float* reward_prior, const float* transition_prior, int sampler, int actor);
+int cmdp_psrl_destroy(cmdp_psrl_t* a);
+/* n_steps of select_action -> step -> step_update per instance; an instance whose step was its episode's last gets its
+   episode_end_update (sample -> solve -> the new Q) and then the environment's reset().  Arguments and results as
+   cmdp_ucrl2_run: stop_at_episode_end stops every instance after its next episode_end_update, steps_taken [B] says where;
+   train_mask [B] (NULL: all train) 0 = the instance acts on the Q it holds, updates nothing and samples nothing (the
+   environment still resets); traces [n_steps][B] (observation -1 at an episode's last step).  A call that could carry a
+   visit counter of the environment past 2^31 - 1, or a float32 transition count past 2^24, is refused with
+   CMDP_ERR_OVERFLOW before anything is stepped. */
+int cmdp_psrl_run(cmdp_psrl_t* a, int64_t n_steps, int stop_at_episode_end, const uint8_t* train_mask, int8_t* actions_trace,
+                  int32_t* obs_trace, double* reward_trace, double* cumulative_reward, int64_t* steps_taken);
+/* PSRLEpisodic.episode_end_update() for EVERY instance, outside the loop: a new posterior sample on the tables as they are, its
+   solve, the new Q; no step is taken and the environment is not reset (what creation does once on the prior). */
+int cmdp_psrl_episode_end_update(cmdp_psrl_t* a);
+/* The transition model's sparse layout (as cmdp_ucrl2_layout). */
+int cmdp_psrl_layout(cmdp_psrl_t* a, int64_t* n_positions, int64_t* row_ptr, int32_t* col);
+/* reward_hp [R][4] float32; transition_hp per position of the layout (every other element of the dense array equals
+   transition_prior [B]); episodes [B]: posterior samples drawn so far, the one at creation included.  Each may be NULL. */
+int cmdp_psrl_model(cmdp_psrl_t* a, float* reward_hp, float* transition_hp, float* transition_prior, int64_t* episodes);
+/* The last posterior sample of every instance: T dense [sum S * A * S], R [R], and the Q [sum (H + 1) * S * A] the actor
+   holds (instance b: [H + 1][S][A], layer H zero).  Each may be NULL. */
+int cmdp_psrl_last_sample(cmdp_psrl_t* a, float* T, float* R, float* Q);
+/* Host only: M_DIR.sample and N_NIG.sample of one instance on two numpy RandomState streams given as `get_state()`
+   leaves them (key [624], position, has_gauss, cached_gaussian; updated in place).  Transition hyper-parameters: dense
+   [S * A * S], or -- when that is NULL -- a layout (row_ptr [S * A + 1], col ascending, val) over `prior`.  reward_hp
+   [S * A][4].  Outputs T [S * A * S] and R [S * A] float32: numpy's numbers, draw for draw. */
+int cmdp_psrl_reference_sample(uint32_t* t_key, int32_t* t_pos, int32_t* t_has_gauss, double* t_gauss, uint32_t* r_key,
+                               int32_t* r_pos, int32_t* r_has_gauss, double* r_gauss, int n_states, int n_actions,
+                               const float* transition_hp_dense, const int64_t* row_ptr, const int32_t* col, const float* val,
+                               float prior, const float* reward_hp, float* T, float* R);
+/* episodic_value_iteration(H, T, R) (colosseum/dynamic_programming/finite_horizon.py:11-26) on `count` dense float32
+   problems: T concatenated [S, A, S] per instance, R [S, A]; Q receives [H + 1][S][A] and V [H + 1][S] per instance, layer H
+   zero.  Q[h, s, a] = float(double(R[s, a]) + sum_j double(T[s, a, j]) * double(V[h + 1, j])), the sum in float64 in a fixed
+   order.  The kernel the PSRL agent solves with.  CMDP_ERR_UNSUPPORTED beyond 4096 states. */
+int cmdp_vi_episodic_dense(int count, const int32_t* n_states, const int32_t* n_actions, int H, const float* T, const float* R,
+                           float* Q, float* V);
 
 #ifdef __cplusplus
 }
