@@ -12,7 +12,26 @@ from . import _lib as L
 from .batched import BatchedMDP
 
 
-class BatchedQLearningEpisodic:
+class _DeviceAgent:
+    """A handle of the library's: `_DESTROY` names the C function that frees it."""
+
+    _DESTROY = None
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            getattr(self._lib, self._DESTROY)(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class BatchedQLearningEpisodic(_DeviceAgent):
+    _DESTROY = "cmdp_qlearning_destroy"
+
     def __init__(self, env: BatchedMDP, seeds: Sequence[int], optimization_horizon: int, p: float, c_1: float,
                  c_2: Optional[float] = None, min_at: float = 0.0, UCB_type: str = "hoeffding"):
         ucb = {"hoeffding": 0, "bernstein": 1}[UCB_type.lower()]
@@ -68,17 +87,6 @@ class BatchedQLearningEpisodic:
         ns = [x.reshape(env.H, -1, env.A) for x in env.split_rows(N, env.H)]
         return qs, ns
 
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            self._lib.cmdp_qlearning_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 class BatchedQLearningContinuous(BatchedQLearningEpisodic):
     """One reference `QLearningContinuous` (colosseum/agent/agents/infinite_horizon/q_learning.py) per instance."""
@@ -124,13 +132,72 @@ class BatchedQLearningContinuous(BatchedQLearningEpisodic):
         return [x.reshape(-1, env.A) for x in env.split_rows(pi)]
 
 
-class BatchedUCRL2Continuous:
+class _ParkAndSolveAgent(_DeviceAgent):
+    """What the agents that park their instances for a solve share (csrc: ParkAgent): the layout of the model's tables (per
+    row the distinct successors), run(), stats().  `_PREFIX` names the agent's C functions, `_STATS` its counters."""
+
+    _PREFIX = None
+    _STATS = ()
+
+    def _fetch_layout(self):
+        layout = getattr(self._lib, self._PREFIX + "_layout")
+        nz = C.c_int64()
+        L.check(layout(self._h, C.byref(nz), None, None))
+        self._nz = int(nz.value)
+        self._ptr = np.zeros(int(self.env.row_off[-1]) + 1, np.int64)
+        self._col = np.zeros(self._nz, np.int32)
+        L.check(layout(self._h, None, L.ptr(self._ptr), L.ptr(self._col)))
+        # dense position of every layout entry inside its instance's [S * A, S] array
+        self._rows = np.repeat(np.arange(len(self._ptr) - 1), np.diff(self._ptr))
+
+    def _run(self, n_steps, train, trace, stop_at_episode_end):
+        n_steps, B = int(n_steps), self.env.B
+        acts = np.zeros((n_steps, B), np.int8) if trace else None
+        obs = np.zeros((n_steps, B), np.int32) if trace else None
+        rew = np.zeros((n_steps, B), np.float64) if trace else None
+        rsum = np.zeros(B, np.float64)
+        taken = np.zeros(B, np.int64)
+        mask = None
+        if train is not True:
+            mask = np.ascontiguousarray(np.broadcast_to(np.asarray(train, bool), (B,)), np.uint8)
+        L.check(getattr(self._lib, self._PREFIX + "_run")(self._h, n_steps, int(bool(stop_at_episode_end)), L.ptr(mask),
+                                                          L.ptr(acts), L.ptr(obs), L.ptr(rew), L.ptr(rsum), L.ptr(taken)))
+        return dict(cumulative_reward=rsum, steps_taken=taken, actions=acts, observations=obs, rewards=rew)
+
+    def _dense(self, values, dtype, fill=None, uniform=None):
+        """Layout values as dense [S, A, S] arrays per instance; elsewhere `fill[b]` (default 0), and rows with
+        `uniform` > 0 hold that value at every state."""
+        env, out = self.env, []
+        for b in range(env.B):
+            S = int(env.n_states[b])
+            r0, r1 = int(env.row_off[b]), int(env.row_off[b + 1])
+            z0, z1 = int(self._ptr[r0]), int(self._ptr[r1])
+            M = np.full((r1 - r0, S), 0 if fill is None else fill[b], dtype)
+            M[self._rows[z0:z1] - r0, self._col[z0:z1]] = values[z0:z1]
+            if uniform is not None:
+                u = uniform[r0:r1]
+                M[u > 0] = u[u > 0, None]
+            out.append(M.reshape(S, env.A, S))
+        return out
+
+    def _stats(self) -> dict:
+        v, out = C.c_double(), {}
+        for k, w in self._STATS:
+            L.check(self._lib.cmdp_stat(self.env._h, w, C.byref(v)))
+            out[k] = float(v.value) if k.endswith("_ms") else int(v.value)
+        return out
+
+
+class BatchedUCRL2Continuous(_ParkAndSolveAgent):
     """One reference `UCRL2Continuous` (colosseum/agent/agents/infinite_horizon/ucrl2.py) per instance of a continuous
     `BatchedMDP`, driven as `MDPLoop.run` drives it: interaction, counts, confidence bounds, the estimated model and the
     optimistic solves (extended value iteration, kernel K10) stay on the device (kernel K11, csrc/cmdp_ucrl2.h).  The
     keyword names and defaults are the reference's.  `bound_type_rew="bernstein"` is refused: the reference raises
     AttributeError there at its first solve."""
 
+    _DESTROY, _PREFIX = "cmdp_ucrl2_destroy", "cmdp_ucrl2"
+    _STATS = (("rounds", L.STAT_UCRL2_ROUNDS), ("solves", L.STAT_UCRL2_SOLVES), ("unconverged", L.STAT_UCRL2_UNCONVERGED),
+              ("round_ms", L.STAT_UCRL2_ROUND_MS), ("wait_ms", L.STAT_UCRL2_WAIT_MS))
     _BOUNDS = {"_chernoff": L.BOUND_CHERNOFF, "bernstein": L.BOUND_BERNSTEIN}
 
     def __init__(self, env: BatchedMDP, seeds: Sequence[int], optimization_horizon: int, alpha_r=1.0, alpha_p=1.0,
@@ -149,46 +216,14 @@ class BatchedUCRL2Continuous:
         L.check(self._lib.cmdp_ucrl2_create(C.byref(self._h), env._h, L.ptr(seeds), int(optimization_horizon), float(alpha_r),
                                             float(alpha_p), self._BOUNDS[bound_type_p], self._BOUNDS[bound_type_rew], actor))
         env._register_agent(self)
-        nz = C.c_int64()
-        L.check(self._lib.cmdp_ucrl2_layout(self._h, C.byref(nz), None, None))
-        self._nz = int(nz.value)
-        self._ptr = np.zeros(int(env.row_off[-1]) + 1, np.int64)
-        self._col = np.zeros(self._nz, np.int32)
-        L.check(self._lib.cmdp_ucrl2_layout(self._h, None, L.ptr(self._ptr), L.ptr(self._col)))
-        # dense position of every layout entry inside its instance's [S * A, S] array
-        self._rows = np.repeat(np.arange(len(self._ptr) - 1), np.diff(self._ptr))
+        self._fetch_layout()
 
     def run(self, n_steps: int, train=True, trace: bool = False, stop_at_episode_end: bool = False):
         """n_steps of select_action -> step -> step_update -> (episode_end_update) per instance; with
         `stop_at_episode_end` every instance stops after its next episode_end_update.  Returns `cumulative_reward` (since
         creation), `steps_taken` [B] and, with `trace`, `actions`, `observations` (after the step) and float64 `rewards`,
         each [n_steps, B] with row t of instance b valid for t < steps_taken[b]."""
-        n_steps, B = int(n_steps), self.env.B
-        acts = np.zeros((n_steps, B), np.int8) if trace else None
-        obs = np.zeros((n_steps, B), np.int32) if trace else None
-        rew = np.zeros((n_steps, B), np.float64) if trace else None
-        rsum = np.zeros(B, np.float64)
-        taken = np.zeros(B, np.int64)
-        mask = None
-        if train is not True:
-            mask = np.ascontiguousarray(np.broadcast_to(np.asarray(train, bool), (B,)), np.uint8)
-        L.check(self._lib.cmdp_ucrl2_run(self._h, n_steps, int(bool(stop_at_episode_end)), L.ptr(mask), L.ptr(acts), L.ptr(obs),
-                                         L.ptr(rew), L.ptr(rsum), L.ptr(taken)))
-        return dict(cumulative_reward=rsum, steps_taken=taken, actions=acts, observations=obs, rewards=rew)
-
-    def _dense(self, values, uniform, dtype):
-        env, out = self.env, []
-        for b in range(env.B):
-            S = int(env.n_states[b])
-            r0, r1 = int(env.row_off[b]), int(env.row_off[b + 1])
-            z0, z1 = int(self._ptr[r0]), int(self._ptr[r1])
-            M = np.zeros((r1 - r0, S), dtype)
-            M[self._rows[z0:z1] - r0, self._col[z0:z1]] = values[z0:z1]
-            if uniform is not None:
-                u = uniform[r0:r1]
-                M[u > 0] = u[u > 0, None]
-            out.append(M.reshape(S, env.A, S))
-        return out
+        return self._run(n_steps, train, trace, stop_at_episode_end)
 
     def model(self):
         """Per instance the reference agent's tables: dense `N` [S, A, S] int32 and `P` float32, `estimated_rewards`,
@@ -201,7 +236,7 @@ class BatchedUCRL2Continuous:
         L.check(self._lib.cmdp_ucrl2_model(self._h, L.ptr(N), L.ptr(P), L.ptr(uni), L.ptr(er), L.ptr(vr), L.ptr(ht), L.ptr(it),
                                            L.ptr(ep), L.ptr(delta)))
         sa = lambda x: [y.reshape(-1, env.A) for y in env.split_rows(x)]  # noqa: E731
-        return dict(N=self._dense(N, None, np.int32), P=self._dense(P, uni, np.float32), estimated_rewards=sa(er),
+        return dict(N=self._dense(N, np.int32), P=self._dense(P, np.float32, uniform=uni), estimated_rewards=sa(er),
                     variance_proxy_reward=sa(vr), estimated_holding_times=sa(ht), iteration=it, episode=ep, delta=delta)
 
     def last_solve(self):
@@ -216,7 +251,7 @@ class BatchedUCRL2Continuous:
         L.check(self._lib.cmdp_ucrl2_last_solve(self._h, L.ptr(P), L.ptr(uni), L.ptr(er), L.ptr(br), L.ptr(bp), L.ptr(Q),
                                                 L.ptr(span), L.ptr(sweeps), L.ptr(status)))
         sa = lambda x: [y.reshape(-1, env.A) for y in env.split_rows(x)]  # noqa: E731
-        return dict(P=self._dense(P, uni, np.float32), estimated_rewards=sa(er), beta_r=sa(br), beta_p0=sa(bp), Q=sa(Q),
+        return dict(P=self._dense(P, np.float32, uniform=uni), estimated_rewards=sa(er), beta_r=sa(br), beta_p0=sa(bp), Q=sa(Q),
                     span=span, sweeps=sweeps, status=status)
 
     def current_optimal_stochastic_policy(self):
@@ -236,30 +271,14 @@ class BatchedUCRL2Continuous:
         """Rounds of parked instances, instances solved in them, solves that did not converge, host time of the rounds
         (park list, logarithms, enqueue) and time spent waiting for the device in them.  Kept per ENVIRONMENT handle:
         agents created on the same environment share these counters."""
-        v, out = C.c_double(), {}
-        for k, w in (("rounds", L.STAT_UCRL2_ROUNDS), ("solves", L.STAT_UCRL2_SOLVES), ("unconverged", L.STAT_UCRL2_UNCONVERGED),
-                     ("round_ms", L.STAT_UCRL2_ROUND_MS), ("wait_ms", L.STAT_UCRL2_WAIT_MS)):
-            L.check(self._lib.cmdp_stat(self.env._h, w, C.byref(v)))
-            out[k] = float(v.value) if k.endswith("_ms") else int(v.value)
-        return out
+        return self._stats()
 
     def _set_max_sweeps(self, n: int):
         """Test hook: the sweeps a solve may take (the not-converged path keeps the previous Q)."""
         L.check(self._lib.cmdp_ucrl2_set_option(self._h, L.UCRL2_OPT_MAX_SWEEPS, int(n)))
 
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            self._lib.cmdp_ucrl2_destroy(self._h)
-            self._h = C.c_void_p()
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class BatchedPSRLEpisodic:
+class BatchedPSRLEpisodic(_ParkAndSolveAgent):
     """One reference `PSRLEpisodic` (colosseum/agent/agents/episodic/posterior_sampling.py) per instance of an episodic
     `BatchedMDP`, driven as `MDPLoop.run` drives it: interaction, the N_NIG / M_DIR posterior tables, the posterior sample,
     the solve (k_vi_episodic_dense) and the actor's Q stay on the device (kernel K12, csrc/cmdp_psrl.h).  The keyword
@@ -268,6 +287,9 @@ class BatchedPSRLEpisodic:
     distributions from a counter-based stream, a pure function of (seed, episode, tables).  Per-pair prior lists, the
     N_N reward model and the exploration actors are refused."""
 
+    _DESTROY, _PREFIX = "cmdp_psrl_destroy", "cmdp_psrl"
+    _STATS = (("rounds", L.STAT_PSRL_ROUNDS), ("solves", L.STAT_PSRL_SOLVES), ("sample_kernel_ms", L.STAT_PSRL_SAMPLE_KERNEL_MS),
+              ("vi_kernel_ms", L.STAT_PSRL_VI_KERNEL_MS), ("reference_ms", L.STAT_PSRL_REFERENCE_MS))
     _SAMPLERS = {"reference": L.PSRL_SAMPLER_REFERENCE, "philox": L.PSRL_SAMPLER_PHILOX}
 
     def __init__(self, env: BatchedMDP, seeds: Sequence[int], optimization_horizon: int, reward_prior_model=None,
@@ -311,31 +333,14 @@ class BatchedPSRLEpisodic:
         L.check(self._lib.cmdp_psrl_create(C.byref(self._h), env._h, L.ptr(seeds), int(optimization_horizon), L.ptr(rprior),
                                            L.ptr(tprior), self._SAMPLERS[sampler], L.ACTOR_GREEDY))
         env._register_agent(self)
-        nz = C.c_int64()
-        L.check(self._lib.cmdp_psrl_layout(self._h, C.byref(nz), None, None))
-        self._nz = int(nz.value)
-        self._ptr = np.zeros(int(env.row_off[-1]) + 1, np.int64)
-        self._col = np.zeros(self._nz, np.int32)
-        L.check(self._lib.cmdp_psrl_layout(self._h, None, L.ptr(self._ptr), L.ptr(self._col)))
-        self._rows = np.repeat(np.arange(len(self._ptr) - 1), np.diff(self._ptr))
+        self._fetch_layout()
 
     def run(self, n_steps: int, train=True, trace: bool = False, stop_at_episode_end: bool = False):
         """n_steps of select_action -> step -> step_update -> (episode_end_update, reset) per instance; with
         `stop_at_episode_end` every instance stops after its next episode_end_update.  Returns `cumulative_reward` (since
         creation), `steps_taken` [B] and, with `trace`, `actions`, `observations` (after the step; -1 at an episode's last
         step) and float64 `rewards`, each [n_steps, B] with row t of instance b valid for t < steps_taken[b]."""
-        n_steps, B = int(n_steps), self.env.B
-        acts = np.zeros((n_steps, B), np.int8) if trace else None
-        obs = np.zeros((n_steps, B), np.int32) if trace else None
-        rew = np.zeros((n_steps, B), np.float64) if trace else None
-        rsum = np.zeros(B, np.float64)
-        taken = np.zeros(B, np.int64)
-        mask = None
-        if train is not True:
-            mask = np.ascontiguousarray(np.broadcast_to(np.asarray(train, bool), (B,)), np.uint8)
-        L.check(self._lib.cmdp_psrl_run(self._h, n_steps, int(bool(stop_at_episode_end)), L.ptr(mask), L.ptr(acts), L.ptr(obs),
-                                        L.ptr(rew), L.ptr(rsum), L.ptr(taken)))
-        return dict(cumulative_reward=rsum, steps_taken=taken, actions=acts, observations=obs, rewards=rew)
+        return self._run(n_steps, train, trace, stop_at_episode_end)
 
     def episode_end_update(self):
         """`PSRLEpisodic.episode_end_update()` for every instance: a new posterior sample on the tables as they are, its
@@ -350,14 +355,7 @@ class BatchedPSRLEpisodic:
         rp, tp = np.zeros(R * 4, np.float32), np.zeros(self._nz, np.float32)
         prior, ep = np.zeros(env.B, np.float32), np.zeros(env.B, np.int64)
         L.check(self._lib.cmdp_psrl_model(self._h, L.ptr(rp), L.ptr(tp), L.ptr(prior), L.ptr(ep)))
-        trans = []
-        for b in range(env.B):
-            S = int(env.n_states[b])
-            r0, r1 = int(env.row_off[b]), int(env.row_off[b + 1])
-            z0, z1 = int(self._ptr[r0]), int(self._ptr[r1])
-            M = np.full((r1 - r0, S), prior[b], np.float32)
-            M[self._rows[z0:z1] - r0, self._col[z0:z1]] = tp[z0:z1]
-            trans.append(M.reshape(S, env.A, S))
+        trans = self._dense(tp, np.float32, fill=prior)
         rew = [x.reshape(-1, env.A, 4) for x in env.split_rows(rp.reshape(R, 4))]
         return dict(transitions=trans, rewards=rew, episode=ep)
 
@@ -396,20 +394,4 @@ class BatchedPSRLEpisodic:
     def stats(self) -> dict:
         """Rounds of parked instances, instances solved in them, HIP-event times of the last round's sample and solve
         kernels, host time of the reference sampler's draws.  Kept per ENVIRONMENT handle."""
-        v, out = C.c_double(), {}
-        for k, w in (("rounds", L.STAT_PSRL_ROUNDS), ("solves", L.STAT_PSRL_SOLVES), ("sample_kernel_ms", L.STAT_PSRL_SAMPLE_KERNEL_MS),
-                     ("vi_kernel_ms", L.STAT_PSRL_VI_KERNEL_MS), ("reference_ms", L.STAT_PSRL_REFERENCE_MS)):
-            L.check(self._lib.cmdp_stat(self.env._h, w, C.byref(v)))
-            out[k] = float(v.value) if k.endswith("_ms") else int(v.value)
-        return out
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            self._lib.cmdp_psrl_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return self._stats()

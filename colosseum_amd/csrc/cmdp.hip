@@ -13,6 +13,7 @@
 #include <cmath>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <unordered_map>
@@ -2541,6 +2542,241 @@ int cmdp_diameter_episodic(cmdp_t* h, int H, const int64_t* start_off, const int
 // ---- device agents -----------------------------------------------------------------------------------------
 }  // extern "C"
 
+// What every device agent's create and getters do to a buffer `a->buf`, with `a`, `st` / `h` in scope
+#define AGENT_ZERO(buf, n) HIP_TRY(a->buf.alloc((size_t)(n))); HIP_TRY(a->buf.zero(st))
+#define AGENT_FETCH(dst, buf, n) \
+  if (dst) HIP_TRY(hipMemcpyAsync(dst, a->buf.p, sizeof(*a->buf.p) * (size_t)(n), hipMemcpyDeviceToHost, h->stream))
+
+namespace {
+
+// The actor's stream of every instance, numpy RandomState(seeds[b]), on the device; returns once the seeds have been read
+int seed_actor(cmdp_t* env, const int32_t* seeds, DevBuf<uint32_t>& d_mt, DevBuf<int32_t>& d_mtpos) {
+  const int B = env->B;
+  HIP_TRY(d_mt.alloc((size_t)B * 624));
+  HIP_TRY(d_mtpos.alloc(B));
+  std::vector<uint32_t> useeds((size_t)B);
+  for (int b = 0; b < B; ++b) useeds[b] = (uint32_t)seeds[b];
+  DevBuf<uint32_t> d_seeds;
+  HIP_TRY(d_seeds.upload(useeds.data(), B, env->stream));
+  hipLaunchKernelGGL(k_mt_seed_numpy, dim3(grid_for(B, 64)), dim3(64), 0, env->stream, d_mt.p, d_mtpos.p, d_seeds.p, B);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(env->stream));
+  return CMDP_OK;
+}
+
+int agent_check_actor(int actor) {
+  if (actor != CMDP_ACTOR_GREEDY)
+    return fail(CMDP_ERR_UNSUPPORTED, "only the greedy actor is built: epsilon-greedy and Boltzmann exploration are not");
+  return CMDP_OK;
+}
+
+// ---- agents that park their instances for a solve (UCRL2: K11, PSRL: K12) -------------------------------------------------
+// A walk kernel steps every instance until it has taken the call's steps or its (artificial) episode ends; the instances
+// that parked are solved in one round of kernels, released, and walked again.
+struct ParkAgent {
+  cmdp_t* env = nullptr;
+  int64_t nz = 0;                      // positions of the model's layout
+  std::vector<int64_t> steps_total;    // [B] transitions taken since creation: bounds the model's counts
+  DevBuf<int64_t> d_row_ptr, d_taken;  // layout: d_row_ptr, d_col, d_slot (build_model_layout)
+  DevBuf<int32_t> d_col, d_slot, d_mtpos, d_park, d_obs;
+  DevBuf<long long> d_left;
+  DevBuf<uint32_t> d_mt;
+  DevBuf<double> d_rsum, d_rew;
+  DevBuf<int8_t> d_act;
+  DevBuf<uint8_t> d_mask;
+  PinnedBuf<int32_t> pin_park;         // [2 + B]: park count, overflow flag (UCRL2 only), park list
+  // a read-back of the agent's own, enqueued after the park list's of every walk (UCRL2: `iteration`)
+  void* walk_dst = nullptr;
+  const void* walk_src = nullptr;
+  size_t walk_bytes = 0;
+
+  ParkCall call() const { return ParkCall{d_left.p, d_taken.p, d_park.p, d_park.p + 2}; }
+};
+
+// What both agents ask of the environment handle (after bind); `other_setting` is the refusal of a handle of the setting
+// the agent is not built for and may print the horizon
+int park_check_env(cmdp_t* env, bool episodic, const char* other_setting, const char* name, const char* solver, int max_states) {
+  if (!env->has_env) return fail(CMDP_ERR_INVALID, "the environment handle was created without the sampler half");
+  if (episodic ? env->H <= 0 : env->H != 0) return fail(CMDP_ERR_UNSUPPORTED, other_setting, env->H);
+  if (env->layout != CMDP_LAYOUT_CSR) return fail(CMDP_ERR_UNSUPPORTED, "agents run on the CSR layout");
+  if (env->reward_cache) return fail(CMDP_ERR_UNSUPPORTED, "CMDP_FLAG_REWARD_CACHE handles are not supported by the %s agent: "
+                                     "its walk kernel does not park for reward blocks", name);
+  if (env->max_S > max_states)
+    return fail(CMDP_ERR_UNSUPPORTED, "an instance has %d states: %s takes at most %d", env->max_S, solver, max_states);
+  return CMDP_OK;
+}
+
+// The model's layout from the sampler's tables: per row the distinct successors in ascending order (`ptr` / `col`, K10's
+// layout), every sampler entry mapped to its position (`slot`).  Uploaded into the agent; `ptr` and `col` stay with the caller.
+int build_model_layout(ParkAgent* a, std::vector<int64_t>& ptr, std::vector<int32_t>& col) {
+  cmdp_t* env = a->env;
+  const int B = env->B, A = env->A;
+  const int64_t R = env->n_rows, E = env->n_entries;
+  hipStream_t st = env->stream;
+  std::vector<RowDesc> rows((size_t)R);
+  std::vector<int32_t> nxt((size_t)E);
+  std::vector<int64_t> ebase((size_t)B);
+  HIP_TRY(hipMemcpyAsync(rows.data(), env->d_row.p, sizeof(RowDesc) * R, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(nxt.data(), env->d_sp_next.p, sizeof(int32_t) * E, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(ebase.data(), env->d_entry_base.p, sizeof(int64_t) * B, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  ptr.assign((size_t)R + 1, 0);
+  col.clear();
+  std::vector<int32_t> slot((size_t)E, 0), tmp;
+  for (int b = 0; b < B; ++b)
+    for (int64_t r = env->state_off[b] * A; r < env->state_off[b + 1] * A; ++r) {
+      const int64_t lo = ebase[b] + rows[(size_t)r].first, n = rows[(size_t)r].n;
+      tmp.assign(nxt.begin() + lo, nxt.begin() + lo + n);
+      std::sort(tmp.begin(), tmp.end());
+      tmp.erase(std::unique(tmp.begin(), tmp.end()), tmp.end());
+      const int64_t z0 = (int64_t)col.size();
+      for (int64_t e = lo; e < lo + n; ++e)
+        slot[(size_t)e] = (int32_t)(z0 + (std::lower_bound(tmp.begin(), tmp.end(), nxt[(size_t)e]) - tmp.begin()));
+      col.insert(col.end(), tmp.begin(), tmp.end());
+      ptr[(size_t)r + 1] = (int64_t)col.size();
+    }
+  if ((int64_t)col.size() > 0x7fffffffLL) return fail(CMDP_ERR_UNSUPPORTED, "more than 2^31 successor positions");
+  a->nz = (int64_t)col.size();
+  HIP_TRY(a->d_row_ptr.upload(ptr.data(), ptr.size(), st));
+  HIP_TRY(a->d_col.upload(col.data(), col.size(), st));
+  HIP_TRY(a->d_slot.upload(slot.data(), slot.size(), st));
+  HIP_TRY(hipStreamSynchronize(st));   // `slot` dies here
+  return CMDP_OK;
+}
+
+int park_layout(ParkAgent* a, int64_t* n_positions, int64_t* row_ptr, int32_t* col) {
+  if (!a) return fail(CMDP_ERR_INVALID, "null agent");
+  cmdp_t* h = a->env;
+  if (int rc = bind(h)) return rc;
+  if (n_positions) *n_positions = a->nz;
+  AGENT_FETCH(row_ptr, d_row_ptr, h->n_rows + 1);
+  AGENT_FETCH(col, d_col, a->nz);
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  return CMDP_OK;
+}
+
+// What every create allocates for the calls to come: their state, the cumulative reward, the actor's stream
+int park_alloc(ParkAgent* a, const int32_t* seeds) {
+  const int B = a->env->B;
+  hipStream_t st = a->env->stream;
+  a->steps_total.assign((size_t)B, 0);
+  AGENT_ZERO(d_left, B); AGENT_ZERO(d_taken, B); AGENT_ZERO(d_park, B + 2); AGENT_ZERO(d_rsum, B);
+  if (int rc = a->pin_park.alloc((size_t)B + 2)) return rc;
+  return seed_actor(a->env, seeds, a->d_mt, a->d_mtpos);
+}
+
+// Parks every instance: the list of a round that solves the whole batch (before_start_interacting, episode_end_update)
+int park_all(ParkAgent* a) {
+  const int B = a->env->B;
+  a->pin_park.p[0] = B; a->pin_park.p[1] = 0;
+  for (int b = 0; b < B; ++b) a->pin_park.p[2 + b] = b;
+  HIP_TRY(hipMemcpyAsync(a->d_park.p, a->pin_park.p, sizeof(int32_t) * (B + 2), hipMemcpyHostToDevice, a->env->stream));
+  return CMDP_OK;
+}
+
+// The environment handle clears `env` of the agents attached to it when it is destroyed first (garbage collection picks
+// the order): such an agent frees its own memory and touches nothing of the handle
+template <typename T>
+int park_attach(std::unique_ptr<T>& a, T** out) {
+  a->env->uc_backrefs.push_back(&a->env);
+  *out = a.release();
+  return CMDP_OK;
+}
+
+template <typename T>
+int park_destroy(T* a) {
+  if (!a) return CMDP_OK;
+  if (a->env) {   // null once the environment handle has been destroyed (its stream was drained then)
+    (void)hipSetDevice(a->env->device);
+    (void)hipStreamSynchronize(a->env->stream);
+    auto& v = a->env->uc_backrefs;
+    v.erase(std::remove(v.begin(), v.end(), &a->env), v.end());
+  }
+  delete a;
+  return CMDP_OK;
+}
+
+// What a run() call refuses before anything is stepped.  `limit_text` prints the instance, its steps so far and n_steps.
+int park_run_check(ParkAgent* a, int64_t n_steps, int64_t limit, const char* limit_text) {
+  if (!a) return fail(CMDP_ERR_INVALID, "null agent");
+  cmdp_t* h = a->env;
+  if (int rc = bind(h)) return rc;
+  if (n_steps < 0) return fail(CMDP_ERR_INVALID, "n_steps < 0");
+  bool any = false;
+  if (int rc = any_needs_reset(h, &any)) return rc;
+  if (any) return fail(CMDP_ERR_NEEDS_RESET, "the environment needs reset() before the agent can run");
+  if (int rc = visits_check(h, n_steps)) return rc;
+  for (int b = 0; b < h->B; ++b)
+    if (a->steps_total[b] + n_steps > limit)
+      return fail(CMDP_ERR_OVERFLOW, limit_text, b, (long long)a->steps_total[b], (long long)n_steps);
+  return CMDP_OK;
+}
+
+// One run() call after park_run_check.  `walk(mask, actions, observations, rewards)` enqueues the agent's walk kernel on the
+// device buffers of the traces the caller asked for; `after_walk()` runs right after the synchronisation that follows it,
+// on what the walk left in pinned memory (not CMDP_OK: the call ends with that code); `round(count)` enqueues the solve and
+// the release of the `count` instances of pin_park's list, sorted and on the device at d_park + 2.  With `round_ms` the
+// call waits for the round it stops after, so that the two intervals are the device's and the host's share.
+template <typename Walk, typename AfterWalk, typename Round>
+int park_run(ParkAgent* a, int64_t n_steps, int stop_at_episode_end, const uint8_t* train_mask, int8_t* actions_trace,
+             int32_t* obs_trace, double* reward_trace, double* cumulative_reward, int64_t* steps_taken, Walk&& walk,
+             AfterWalk&& after_walk, Round&& round, double* wait_ms = nullptr, double* round_ms = nullptr) {
+  using clk = std::chrono::steady_clock;
+  const auto ms_since = [](clk::time_point t0) { return std::chrono::duration<double, std::milli>(clk::now() - t0).count(); };
+  cmdp_t* h = a->env;
+  const int B = h->B;
+  hipStream_t st = h->stream;
+  const size_t NB = (size_t)n_steps * B;
+  if (actions_trace && a->d_act.n < NB) HIP_TRY(a->d_act.alloc(NB));
+  if (obs_trace && a->d_obs.n < NB) HIP_TRY(a->d_obs.alloc(NB));
+  if (reward_trace && a->d_rew.n < NB) HIP_TRY(a->d_rew.alloc(NB));
+  const uint8_t* dmask = nullptr;
+  if (train_mask) {
+    HIP_TRY(a->d_mask.upload(train_mask, B, st));
+    dmask = a->d_mask.p;
+  }
+  std::vector<long long> left((size_t)B, (long long)n_steps);
+  std::vector<int64_t> taken((size_t)B, n_steps);
+  HIP_TRY(hipMemcpyAsync(a->d_left.p, left.data(), sizeof(long long) * B, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(a->d_taken.p, taken.data(), sizeof(int64_t) * B, hipMemcpyHostToDevice, st));
+  int rc = CMDP_OK;
+  while (n_steps > 0) {
+    HIP_TRY(hipMemsetAsync(a->d_park.p, 0, sizeof(int32_t) * 2, st));
+    walk(dmask, actions_trace ? a->d_act.p : nullptr, obs_trace ? a->d_obs.p : nullptr, reward_trace ? a->d_rew.p : nullptr);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(a->pin_park.p, a->d_park.p, sizeof(int32_t) * (B + 2), hipMemcpyDeviceToHost, st));
+    if (a->walk_bytes) HIP_TRY(hipMemcpyAsync(a->walk_dst, a->walk_src, a->walk_bytes, hipMemcpyDeviceToHost, st));
+    const auto w0 = clk::now();
+    HIP_TRY(hipStreamSynchronize(st));   // the device's share: the previous round's kernels and this walk
+    if (wait_ms) *wait_ms += ms_since(w0);
+    if ((rc = after_walk())) break;
+    const int count = a->pin_park.p[0];
+    if (count == 0) break;
+    const auto t0 = clk::now();
+    std::sort(a->pin_park.p + 2, a->pin_park.p + 2 + count);   // the order instances parked in is not deterministic
+    HIP_TRY(hipMemcpyAsync(a->d_park.p + 2, a->pin_park.p + 2, sizeof(int32_t) * count, hipMemcpyHostToDevice, st));
+    if ((rc = round(count))) break;
+    if (stop_at_episode_end && round_ms) HIP_TRY(hipStreamSynchronize(st));
+    if (round_ms) *round_ms += ms_since(t0);
+    if (stop_at_episode_end) break;   // every instance either finished its steps or has just been stopped
+  }
+  if (rc == CMDP_OK && n_steps > 0) {
+    HIP_TRY(hipMemcpyAsync(taken.data(), a->d_taken.p, sizeof(int64_t) * B, hipMemcpyDeviceToHost, st));
+    if (actions_trace) HIP_TRY(hipMemcpyAsync(actions_trace, a->d_act.p, NB, hipMemcpyDeviceToHost, st));
+    if (obs_trace) HIP_TRY(hipMemcpyAsync(obs_trace, a->d_obs.p, sizeof(int32_t) * NB, hipMemcpyDeviceToHost, st));
+    if (reward_trace) HIP_TRY(hipMemcpyAsync(reward_trace, a->d_rew.p, sizeof(double) * NB, hipMemcpyDeviceToHost, st));
+  }
+  if (cumulative_reward) HIP_TRY(hipMemcpyAsync(cumulative_reward, a->d_rsum.p, sizeof(double) * B, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  for (int b = 0; b < B; ++b) {
+    a->steps_total[b] += rc == CMDP_OK ? taken[b] : n_steps;
+    if (steps_taken) steps_taken[b] = taken[b];
+  }
+  return visits_commit(h, n_steps, rc);
+}
+
+}  // namespace
+
 struct cmdp_agent {
   cmdp_t* env = nullptr;
   bool continuous = false;
@@ -2574,7 +2810,7 @@ int cmdp_qlearning_create(cmdp_agent_t** out, cmdp_t* env, const int32_t* seeds,
     return fail(CMDP_ERR_INVALID, "hyper-parameters out of range (0<p<1, c_1>0, 0<=min_at<0.99, bernstein needs c_2>0)");
   const int B = env->B, A = env->A, H = env->H;
   cmdp_agent_t* a = new cmdp_agent;
-  struct Guard { cmdp_agent_t* a; ~Guard() { delete a; } } guard{a};
+  std::unique_ptr<cmdp_agent> guard(a);
   a->env = env;
   hipStream_t st = env->stream;
   std::vector<double> ilog((size_t)B), s7((size_t)B);
@@ -2595,31 +2831,17 @@ int cmdp_qlearning_create(cmdp_agent_t** out, cmdp_t* env, const int32_t* seeds,
   HIP_TRY(a->d_voff.upload(voff.data(), B, st));
   HIP_TRY(a->d_N.alloc(a->n_q));
   HIP_TRY(a->d_Q.alloc(a->n_q));
-  HIP_TRY(a->d_V.alloc(a->n_v));
-  HIP_TRY(a->d_V.zero(st));
-  HIP_TRY(a->d_mu.alloc(a->n_q)); HIP_TRY(a->d_mu.zero(st));
-  HIP_TRY(a->d_sigma.alloc(a->n_q)); HIP_TRY(a->d_sigma.zero(st));
-  HIP_TRY(a->d_beta.alloc(a->n_q)); HIP_TRY(a->d_beta.zero(st));
+  AGENT_ZERO(d_V, a->n_v); AGENT_ZERO(d_mu, a->n_q); AGENT_ZERO(d_sigma, a->n_q); AGENT_ZERO(d_beta, a->n_q);
   hipLaunchKernelGGL(k_fill_i32, dim3(grid_for(a->n_q, 256)), dim3(256), 0, st, a->d_N.p, 1, a->n_q);
   hipLaunchKernelGGL(k_fill_f32, dim3(grid_for(a->n_q, 256)), dim3(256), 0, st, a->d_Q.p, (float)H, a->n_q);
-  HIP_TRY(a->d_mt.alloc((size_t)B * 624));
-  HIP_TRY(a->d_mtpos.alloc(B));
-  HIP_TRY(a->d_rsum.alloc(B));
-  HIP_TRY(a->d_rsum.zero(st));
-  std::vector<uint32_t> useeds((size_t)B);
-  for (int b = 0; b < B; ++b) useeds[b] = (uint32_t)seeds[b];
-  DevBuf<uint32_t> d_seeds;
-  HIP_TRY(d_seeds.upload(useeds.data(), B, st));
-  hipLaunchKernelGGL(k_mt_seed_numpy, dim3(grid_for(B, 64)), dim3(64), 0, st, a->d_mt.p, a->d_mtpos.p, d_seeds.p, B);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipStreamSynchronize(st));
+  AGENT_ZERO(d_rsum, B);
+  if (int rc = seed_actor(env, seeds, a->d_mt, a->d_mtpos)) return rc;   // synchronises: the staging vectors die below
   QlArgs& q = a->args;
   q.H = H; q.ucb = ucb_type; q.c1 = c_1; q.c2 = c_2; q.min_at = min_at; q.H3 = (double)H * H * H;
   q.i_log = a->d_ilog.p; q.sqrtH7SA = a->d_s7.p; q.q_off = a->d_qoff.p; q.v_off = a->d_voff.p;
   q.N = a->d_N.p; q.Q = a->d_Q.p; q.V = a->d_V.p; q.mu = a->d_mu.p; q.sigma = a->d_sigma.p; q.beta = a->d_beta.p;
   q.mt = a->d_mt.p; q.mt_pos = a->d_mtpos.p;
-  guard.a = nullptr;
-  *out = a;
+  *out = guard.release();
   return CMDP_OK;
 }
 
@@ -2635,7 +2857,7 @@ int cmdp_qlearning_continuous_create(cmdp_agent_t** out, cmdp_t* env, const int3
     return fail(CMDP_ERR_INVALID, "hyper-parameters out of range");
   const int B = env->B, A = env->A;
   cmdp_agent_t* a = new cmdp_agent;
-  struct Guard { cmdp_agent_t* a; ~Guard() { delete a; } } guard{a};
+  std::unique_ptr<cmdp_agent> guard(a);
   a->env = env;
   a->continuous = true;
   hipStream_t st = env->stream;
@@ -2656,7 +2878,7 @@ int cmdp_qlearning_continuous_create(cmdp_agent_t** out, cmdp_t* env, const int3
   HIP_TRY(a->d_Hh.upload(Hh.data(), B, st));
   HIP_TRY(a->d_gamma.upload(gm.data(), B, st));
   HIP_TRY(a->d_qoff.upload(qoff.data(), B, st));
-  HIP_TRY(a->d_N.alloc(a->n_q)); HIP_TRY(a->d_N.zero(st));
+  AGENT_ZERO(d_N, a->n_q);
   HIP_TRY(a->d_Qc.alloc(a->n_q));
   HIP_TRY(a->d_Qmainc.alloc(a->n_q));
   HIP_TRY(a->d_Vc.alloc(a->n_v));
@@ -2669,25 +2891,15 @@ int cmdp_qlearning_continuous_create(cmdp_agent_t** out, cmdp_t* env, const int3
   HIP_TRY(hipMemcpyAsync(a->d_Qc.p, q0.data(), sizeof(double) * a->n_q, hipMemcpyHostToDevice, st));
   HIP_TRY(hipMemcpyAsync(a->d_Qmainc.p, q0.data(), sizeof(double) * a->n_q, hipMemcpyHostToDevice, st));
   HIP_TRY(hipMemcpyAsync(a->d_Vc.p, v0.data(), sizeof(double) * a->n_v, hipMemcpyHostToDevice, st));
-  HIP_TRY(a->d_mt.alloc((size_t)B * 624));
-  HIP_TRY(a->d_mtpos.alloc(B));
-  HIP_TRY(a->d_rsum.alloc(B));
-  HIP_TRY(a->d_rsum.zero(st));
-  std::vector<uint32_t> useeds((size_t)B);
-  for (int b = 0; b < B; ++b) useeds[b] = (uint32_t)seeds[b];
-  DevBuf<uint32_t> d_seeds;
-  HIP_TRY(d_seeds.upload(useeds.data(), B, st));
-  hipLaunchKernelGGL(k_mt_seed_numpy, dim3(grid_for(B, 64)), dim3(64), 0, st, a->d_mt.p, a->d_mtpos.p, d_seeds.p, B);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipStreamSynchronize(st));
+  AGENT_ZERO(d_rsum, B);
+  if (int rc = seed_actor(env, seeds, a->d_mt, a->d_mtpos)) return rc;   // synchronises: the staging vectors die below
   QlcArgs& q = a->cargs;
   q.min_at = min_at > 0.009 ? min_at : 0.0;
   q.four_span = 4 * span_approx_weight;
   q.log_term = std::log(2 * T / confidence);
   q.Hh = a->d_Hh.p; q.gamma = a->d_gamma.p; q.q_off = a->d_qoff.p;
   q.N = a->d_N.p; q.Q = a->d_Qc.p; q.Qmain = a->d_Qmainc.p; q.V = a->d_Vc.p; q.mt = a->d_mt.p; q.mt_pos = a->d_mtpos.p;
-  guard.a = nullptr;
-  *out = a;
+  *out = guard.release();
   return CMDP_OK;
 }
 
@@ -3859,24 +4071,16 @@ int cmdp_value_norm(cmdp_t* h, const float* V, float* out) {
 }  // extern "C"
 
 // ---- UCRL2 on the device (K11, cmdp_ucrl2.h) ------------------------------------------------------------------------
-struct cmdp_ucrl2 {
-  cmdp_t* env = nullptr;
+struct cmdp_ucrl2 : ParkAgent {
   int bernstein_p = 0;
   double alpha_r = 1.0, alpha_p = 1.0;
   int64_t max_sweeps = 1000000;        // DP_MAX_ITERATION of the reference; CMDP_UCRL2_OPT_MAX_SWEEPS
   size_t evi_lds = 0;
-  int64_t nz = 0;
-  std::vector<int64_t> steps_total;    // [B] transitions taken since creation: bounds every count and every episode
   UcArgs args{};
-  DevBuf<int64_t> d_row_ptr, d_iteration, d_episode, d_tr_len, d_taken, d_sweeps, d_e_soff, d_e_roff, d_e_sweeps;
-  DevBuf<int32_t> d_col, d_slot, d_N, d_N_row, d_nu, d_kdone, d_mtpos, d_tr_row, d_park, d_status, d_eS, d_eA, d_e_status, d_obs;
+  DevBuf<int64_t> d_iteration, d_episode, d_tr_len, d_sweeps, d_e_soff, d_e_roff, d_e_sweeps;
+  DevBuf<int32_t> d_N, d_N_row, d_nu, d_kdone, d_tr_row, d_status, d_eS, d_eA, d_e_status;
   DevBuf<float> d_val, d_uni, d_ER, d_VR, d_HT, d_Q, d_sv_val, d_sv_uni, d_sv_R, d_Qs, d_V;
-  DevBuf<double> d_delta, d_tr_rew, d_beta_r, d_beta_p0, d_span, d_e_rmax, d_e_span, d_host, d_rsum, d_rew;
-  DevBuf<long long> d_left;
-  DevBuf<uint32_t> d_mt;
-  DevBuf<int8_t> d_act;
-  DevBuf<uint8_t> d_mask;
-  PinnedBuf<int32_t> pin_park;   // [2 + B]: park count, overflow flag, park list
+  DevBuf<double> d_delta, d_tr_rew, d_beta_r, d_beta_p0, d_span, d_e_rmax, d_e_span, d_host;
   PinnedBuf<int64_t> pin_iter;   // [B]
   PinnedBuf<double> pin_host;    // [3][B]: the round's scalars per parked instance
 };
@@ -3972,62 +4176,30 @@ int cmdp_ucrl2_create(cmdp_ucrl2_t** out, cmdp_t* env, const int32_t* seeds, int
   if (bound_type_rew == CMDP_BOUND_BERNSTEIN)
     return fail(CMDP_ERR_UNSUPPORTED, "bound_type_rew = bernstein: the reference raises AttributeError at its first solve "
                 "(ucrl2.py:268 reads self.r_max, which does not exist), so there is nothing to reproduce");
-  if (actor != CMDP_ACTOR_GREEDY)
-    return fail(CMDP_ERR_UNSUPPORTED, "only the greedy actor is built: epsilon-greedy and Boltzmann exploration are not");
+  if (int rc = agent_check_actor(actor)) return rc;
   if (!env || !seeds) return fail(CMDP_ERR_INVALID, "null argument (environment handle or seeds)");
   if (!(alpha_r > 0) || !(alpha_p > 0) || !std::isfinite(alpha_r) || !std::isfinite(alpha_p) || optimization_horizon < 1)
     return fail(CMDP_ERR_INVALID, "hyper-parameters out of range (alpha_r > 0, alpha_p > 0, optimization_horizon >= 1)");
   if (int rc = bind(env)) return rc;
-  if (!env->has_env) return fail(CMDP_ERR_INVALID, "the environment handle was created without the sampler half");
-  if (env->H != 0) return fail(CMDP_ERR_UNSUPPORTED, "UCRL2 is the continuous setting's agent (the reference has no episodic "
-                               "UCRL2): the environment handle is episodic, horizon %d", env->H);
-  if (env->layout != CMDP_LAYOUT_CSR) return fail(CMDP_ERR_UNSUPPORTED, "agents run on the CSR layout");
-  if (env->reward_cache) return fail(CMDP_ERR_UNSUPPORTED, "CMDP_FLAG_REWARD_CACHE handles are not supported by the UCRL2 agent: "
-                                     "its walk kernel does not park for reward blocks");
-  if (env->max_S > EVI_MAX_STATES)
-    return fail(CMDP_ERR_UNSUPPORTED, "an instance has %d states: extended value iteration (K10) takes at most %d", env->max_S,
-                EVI_MAX_STATES);
+  if (int rc = park_check_env(env, false, "UCRL2 is the continuous setting's agent (the reference has no episodic UCRL2): the "
+                              "environment handle is episodic, horizon %d", "UCRL2", "extended value iteration (K10)", EVI_MAX_STATES))
+    return rc;
   const int B = env->B, A = env->A;
-  const int64_t R = env->n_rows, E = env->n_entries;
+  const int64_t R = env->n_rows;
   hipStream_t st = env->stream;
   cmdp_ucrl2_t* a = new cmdp_ucrl2;
-  struct Guard { cmdp_ucrl2_t* a; ~Guard() { delete a; } } guard{a};
+  std::unique_ptr<cmdp_ucrl2> guard(a);
   a->env = env;
   a->bernstein_p = bound_type_p == CMDP_BOUND_BERNSTEIN;
   a->alpha_r = alpha_r;
   a->alpha_p = alpha_p;
-  a->steps_total.assign((size_t)B, 0);
-  // K10's layout from the sampler's: per row the distinct successors in ascending order, every entry mapped to its position
-  std::vector<RowDesc> rows((size_t)R);
-  std::vector<int32_t> nxt((size_t)E);
-  std::vector<int64_t> ebase((size_t)B);
-  HIP_TRY(hipMemcpyAsync(rows.data(), env->d_row.p, sizeof(RowDesc) * R, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(nxt.data(), env->d_sp_next.p, sizeof(int32_t) * E, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(ebase.data(), env->d_entry_base.p, sizeof(int64_t) * B, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  std::vector<int64_t> ptr((size_t)R + 1, 0);
-  std::vector<int32_t> col, slot((size_t)E, 0), tmp;
-  for (int b = 0; b < B; ++b)
-    for (int64_t r = env->state_off[b] * A; r < env->state_off[b + 1] * A; ++r) {
-      const int64_t lo = ebase[b] + rows[(size_t)r].first, n = rows[(size_t)r].n;
-      tmp.assign(nxt.begin() + lo, nxt.begin() + lo + n);
-      std::sort(tmp.begin(), tmp.end());
-      tmp.erase(std::unique(tmp.begin(), tmp.end()), tmp.end());
-      const int64_t z0 = (int64_t)col.size();
-      for (int64_t e = lo; e < lo + n; ++e)
-        slot[(size_t)e] = (int32_t)(z0 + (std::lower_bound(tmp.begin(), tmp.end(), nxt[(size_t)e]) - tmp.begin()));
-      col.insert(col.end(), tmp.begin(), tmp.end());
-      ptr[(size_t)r + 1] = (int64_t)col.size();
-    }
-  const int64_t NZ = (int64_t)col.size();
-  if (NZ > 0x7fffffffLL) return fail(CMDP_ERR_UNSUPPORTED, "more than 2^31 successor positions");
-  a->nz = NZ;
+  std::vector<int64_t> ptr;
+  std::vector<int32_t> col;
+  if (int rc = build_model_layout(a, ptr, col)) return rc;
+  const int64_t NZ = a->nz;
   int P = 1;
   while (P < env->max_S) P <<= 1;
   a->evi_lds = (size_t)P * 8 + (size_t)env->max_S * 10;
-  HIP_TRY(a->d_row_ptr.upload(ptr.data(), ptr.size(), st));
-  HIP_TRY(a->d_col.upload(col.data(), col.size(), st));
-  HIP_TRY(a->d_slot.upload(slot.data(), slot.size(), st));
   // tables as UCRL2Continuous.__init__ leaves them (ucrl2.py:140-159)
   std::vector<float> uni((size_t)R), er((size_t)R, (float)env->rmax), ht((size_t)R, 1.0f);
   for (int b = 0; b < B; ++b) {
@@ -4037,27 +4209,18 @@ int cmdp_ucrl2_create(cmdp_ucrl2_t** out, cmdp_t* env, const int32_t* seeds, int
   HIP_TRY(a->d_uni.upload(uni.data(), R, st));
   HIP_TRY(a->d_ER.upload(er.data(), R, st));
   HIP_TRY(a->d_HT.upload(ht.data(), R, st));
-#define UC_ZERO(buf, n) HIP_TRY(a->buf.alloc((size_t)(n))); HIP_TRY(a->buf.zero(st))
-  UC_ZERO(d_VR, R); UC_ZERO(d_N, NZ); UC_ZERO(d_val, NZ); UC_ZERO(d_N_row, R); UC_ZERO(d_nu, R); UC_ZERO(d_kdone, R);
-  UC_ZERO(d_iteration, B); UC_ZERO(d_episode, B); UC_ZERO(d_delta, B); UC_ZERO(d_Q, R); UC_ZERO(d_tr_len, B);
-  UC_ZERO(d_left, B); UC_ZERO(d_taken, B); UC_ZERO(d_park, B + 2); UC_ZERO(d_sv_val, NZ); UC_ZERO(d_sv_uni, R); UC_ZERO(d_sv_R, R);
-  UC_ZERO(d_beta_r, R); UC_ZERO(d_beta_p0, R); UC_ZERO(d_Qs, R); UC_ZERO(d_V, env->n_states); UC_ZERO(d_span, B);
-  UC_ZERO(d_sweeps, B); UC_ZERO(d_status, B); UC_ZERO(d_eS, B); UC_ZERO(d_eA, B); UC_ZERO(d_e_soff, B); UC_ZERO(d_e_roff, B);
-  UC_ZERO(d_e_rmax, B); UC_ZERO(d_e_span, B); UC_ZERO(d_e_sweeps, B); UC_ZERO(d_e_status, B); UC_ZERO(d_host, 3 * (size_t)B);
-  UC_ZERO(d_rsum, B);
-#undef UC_ZERO
+  AGENT_ZERO(d_VR, R); AGENT_ZERO(d_N, NZ); AGENT_ZERO(d_val, NZ); AGENT_ZERO(d_N_row, R); AGENT_ZERO(d_nu, R);
+  AGENT_ZERO(d_kdone, R); AGENT_ZERO(d_iteration, B); AGENT_ZERO(d_episode, B); AGENT_ZERO(d_delta, B); AGENT_ZERO(d_Q, R);
+  AGENT_ZERO(d_tr_len, B); AGENT_ZERO(d_sv_val, NZ); AGENT_ZERO(d_sv_uni, R); AGENT_ZERO(d_sv_R, R); AGENT_ZERO(d_beta_r, R);
+  AGENT_ZERO(d_beta_p0, R); AGENT_ZERO(d_Qs, R); AGENT_ZERO(d_V, env->n_states); AGENT_ZERO(d_span, B); AGENT_ZERO(d_sweeps, B);
+  AGENT_ZERO(d_status, B); AGENT_ZERO(d_eS, B); AGENT_ZERO(d_eA, B); AGENT_ZERO(d_e_soff, B); AGENT_ZERO(d_e_roff, B);
+  AGENT_ZERO(d_e_rmax, B); AGENT_ZERO(d_e_span, B); AGENT_ZERO(d_e_sweeps, B); AGENT_ZERO(d_e_status, B);
+  AGENT_ZERO(d_host, 3 * (size_t)B);
   if (!env->d_uc_unconverged.p) { HIP_TRY(env->d_uc_unconverged.alloc(1)); HIP_TRY(env->d_uc_unconverged.zero(st)); }
-  HIP_TRY(a->d_mt.alloc((size_t)B * 624));
-  HIP_TRY(a->d_mtpos.alloc(B));
-  if (int rc = a->pin_park.alloc((size_t)B + 2)) return rc;
+  if (int rc = park_alloc(a, seeds)) return rc;
   if (int rc = a->pin_iter.alloc(B)) return rc;
   if (int rc = a->pin_host.alloc(3 * (size_t)B)) return rc;
-  std::vector<uint32_t> useeds((size_t)B);
-  for (int b = 0; b < B; ++b) useeds[b] = (uint32_t)seeds[b];
-  DevBuf<uint32_t> d_seeds;
-  HIP_TRY(d_seeds.upload(useeds.data(), B, st));
-  hipLaunchKernelGGL(k_mt_seed_numpy, dim3(grid_for(B, 64)), dim3(64), 0, st, a->d_mt.p, a->d_mtpos.p, d_seeds.p, B);
-  HIP_TRY(hipGetLastError());
+  a->walk_dst = a->pin_iter.p; a->walk_src = a->d_iteration.p; a->walk_bytes = sizeof(int64_t) * B;
   UcArgs& u = a->args;
   u.row_ptr = a->d_row_ptr.p; u.col = a->d_col.p; u.slot = a->d_slot.p;
   u.N = a->d_N.p; u.N_row = a->d_N_row.p; u.nu = a->d_nu.p; u.kdone = a->d_kdone.p;
@@ -4065,32 +4228,18 @@ int cmdp_ucrl2_create(cmdp_ucrl2_t** out, cmdp_t* env, const int32_t* seeds, int
   u.iteration = a->d_iteration.p; u.episode = a->d_episode.p; u.delta = a->d_delta.p;
   u.Q = a->d_Q.p; u.mt = a->d_mt.p; u.mt_pos = a->d_mtpos.p;
   u.tr_row = nullptr; u.tr_rew = nullptr; u.tr_len = a->d_tr_len.p; u.tr_cap = 0;
-  u.left = a->d_left.p; u.taken = a->d_taken.p; u.park_count = a->d_park.p; u.overflow = a->d_park.p + 1; u.park_list = a->d_park.p + 2;
+  u.call = a->call(); u.overflow = a->d_park.p + 1;
   u.sv_val = a->d_sv_val.p; u.sv_uni = a->d_sv_uni.p; u.sv_R = a->d_sv_R.p; u.beta_r = a->d_beta_r.p; u.beta_p0 = a->d_beta_p0.p;
   u.Qs = a->d_Qs.p; u.span = a->d_span.p; u.sweeps = a->d_sweeps.p; u.status = a->d_status.p;
   // before_start_interacting (ucrl2.py:192-193): one episode_end_update without data -- every instance, one solve
-  a->pin_park.p[0] = B; a->pin_park.p[1] = 0;
-  for (int b = 0; b < B; ++b) { a->pin_park.p[2 + b] = b; a->pin_iter.p[b] = 0; }
-  HIP_TRY(hipMemcpyAsync(a->d_park.p, a->pin_park.p, sizeof(int32_t) * (B + 2), hipMemcpyHostToDevice, st));
+  for (int b = 0; b < B; ++b) a->pin_iter.p[b] = 0;
+  if (int rc = park_all(a)) return rc;
   if (int rc = ucrl2_round(a, B, 0, 0)) return rc;
   HIP_TRY(hipStreamSynchronize(st));
-  env->uc_backrefs.push_back(&a->env);
-  guard.a = nullptr;
-  *out = a;
-  return CMDP_OK;
+  return park_attach(guard, out);
 }
 
-int cmdp_ucrl2_destroy(cmdp_ucrl2_t* a) {
-  if (!a) return CMDP_OK;
-  if (a->env) {   // null once the environment handle has been destroyed (its stream was drained then)
-    (void)hipSetDevice(a->env->device);
-    (void)hipStreamSynchronize(a->env->stream);
-    auto& v = a->env->uc_backrefs;
-    v.erase(std::remove(v.begin(), v.end(), &a->env), v.end());
-  }
-  delete a;
-  return CMDP_OK;
-}
+int cmdp_ucrl2_destroy(cmdp_ucrl2_t* a) { return park_destroy(a); }
 
 int cmdp_ucrl2_set_option(cmdp_ucrl2_t* a, int option, int64_t value) {
   if (!a || !a->env) return fail(CMDP_ERR_INVALID, "null agent, or its environment handle has been destroyed");
@@ -4104,89 +4253,28 @@ int cmdp_ucrl2_set_option(cmdp_ucrl2_t* a, int option, int64_t value) {
 
 int cmdp_ucrl2_run(cmdp_ucrl2_t* a, int64_t n_steps, int stop_at_episode_end, const uint8_t* train_mask, int8_t* actions_trace,
                    int32_t* obs_trace, double* reward_trace, double* cumulative_reward, int64_t* steps_taken) {
-  if (!a) return fail(CMDP_ERR_INVALID, "null agent");
-  cmdp_t* h = a->env;
-  if (int rc = bind(h)) return rc;
-  if (n_steps < 0) return fail(CMDP_ERR_INVALID, "n_steps < 0");
-  bool any = false;
-  if (int rc = any_needs_reset(h, &any)) return rc;
-  if (any) return fail(CMDP_ERR_NEEDS_RESET, "the environment needs reset() before the agent can run");
-  const int B = h->B;
-  hipStream_t st = h->stream;
-  if (int rc = visits_check(h, n_steps)) return rc;
-  for (int b = 0; b < B; ++b)
-    if (a->steps_total[b] + n_steps > 0x7fffffffLL)
-      return fail(CMDP_ERR_OVERFLOW, "a transition count of the model (int32, as the reference's N) could wrap: instance %d has "
-                  "taken %lld steps, %lld more asked for", b, (long long)a->steps_total[b], (long long)n_steps);
+  if (int rc = park_run_check(a, n_steps, 0x7fffffffLL, "a transition count of the model (int32, as the reference's N) could wrap: "
+                              "instance %d has taken %lld steps, %lld more asked for")) return rc;
   if (int rc = ucrl2_ensure_trace(a, n_steps)) return rc;
-  const size_t NB = (size_t)n_steps * B;
-  if (actions_trace && a->d_act.n < NB) HIP_TRY(a->d_act.alloc(NB));
-  if (obs_trace && a->d_obs.n < NB) HIP_TRY(a->d_obs.alloc(NB));
-  if (reward_trace && a->d_rew.n < NB) HIP_TRY(a->d_rew.alloc(NB));
-  const uint8_t* dmask = nullptr;
-  if (train_mask) {
-    HIP_TRY(a->d_mask.upload(train_mask, B, st));
-    dmask = a->d_mask.p;
-  }
-  std::vector<long long> left((size_t)B, (long long)n_steps);
-  std::vector<int64_t> taken((size_t)B, n_steps);
-  HIP_TRY(hipMemcpyAsync(a->d_left.p, left.data(), sizeof(long long) * B, hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemcpyAsync(a->d_taken.p, taken.data(), sizeof(int64_t) * B, hipMemcpyHostToDevice, st));
-  int rc = CMDP_OK;
-  while (n_steps > 0) {
-    HIP_TRY(hipMemsetAsync(a->d_park.p, 0, sizeof(int32_t) * 2, st));
-    hipLaunchKernelGGL(k_ucrl2_walk, dim3(grid_for(B, 256)), dim3(256), 0, st, h->env(), a->args, n_steps, dmask,
-                       actions_trace ? a->d_act.p : nullptr, obs_trace ? a->d_obs.p : nullptr,
-                       reward_trace ? a->d_rew.p : nullptr, a->d_rsum.p);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(a->pin_park.p, a->d_park.p, sizeof(int32_t) * (B + 2), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(a->pin_iter.p, a->d_iteration.p, sizeof(int64_t) * B, hipMemcpyDeviceToHost, st));
-    const auto w0 = std::chrono::steady_clock::now();
-    HIP_TRY(hipStreamSynchronize(st));   // the device's share: the previous round's three kernels and this walk
-    h->uc_wait_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count();
-    if (a->pin_park.p[1]) { rc = fail(CMDP_ERR_OVERFLOW, "an artificial episode outgrew its trace buffer: the bound the buffer is sized from does "
-                "not hold (a defect of the library); the instance's last transition was taken and not counted, destroy the agent"); break; }
-    const int count = a->pin_park.p[0];
-    if (count == 0) break;
-    const auto t0 = std::chrono::steady_clock::now();
-    std::sort(a->pin_park.p + 2, a->pin_park.p + 2 + count);   // the order instances parked in is not deterministic
-    HIP_TRY(hipMemcpyAsync(a->d_park.p + 2, a->pin_park.p + 2, sizeof(int32_t) * count, hipMemcpyHostToDevice, st));
-    if ((rc = ucrl2_round(a, count, stop_at_episode_end ? 1 : 0, n_steps))) break;
-    if (stop_at_episode_end) {   // every instance either finished its steps or has just been stopped
-      HIP_TRY(hipStreamSynchronize(st));
-      h->uc_round_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-      break;
-    }
-    h->uc_round_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  }
-  if (rc == CMDP_OK && n_steps > 0) {
-    HIP_TRY(hipMemcpyAsync(taken.data(), a->d_taken.p, sizeof(int64_t) * B, hipMemcpyDeviceToHost, st));
-    if (actions_trace) HIP_TRY(hipMemcpyAsync(actions_trace, a->d_act.p, NB, hipMemcpyDeviceToHost, st));
-    if (obs_trace) HIP_TRY(hipMemcpyAsync(obs_trace, a->d_obs.p, sizeof(int32_t) * NB, hipMemcpyDeviceToHost, st));
-    if (reward_trace) HIP_TRY(hipMemcpyAsync(reward_trace, a->d_rew.p, sizeof(double) * NB, hipMemcpyDeviceToHost, st));
-  }
-  if (cumulative_reward) HIP_TRY(hipMemcpyAsync(cumulative_reward, a->d_rsum.p, sizeof(double) * B, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  for (int b = 0; b < B; ++b) {
-    a->steps_total[b] += rc == CMDP_OK ? taken[b] : n_steps;
-    if (steps_taken) steps_taken[b] = taken[b];
-  }
-  return visits_commit(h, n_steps, rc);
+  cmdp_t* h = a->env;
+  const int stop = stop_at_episode_end ? 1 : 0;
+  return park_run(
+      a, n_steps, stop, train_mask, actions_trace, obs_trace, reward_trace, cumulative_reward, steps_taken,
+      [&](const uint8_t* dmask, int8_t* act, int32_t* obs, double* rew) {
+        hipLaunchKernelGGL(k_ucrl2_walk, dim3(grid_for(h->B, 256)), dim3(256), 0, h->stream, h->env(), a->args, n_steps, dmask, act,
+                           obs, rew, a->d_rsum.p);
+      },
+      [&]() -> int {
+        if (!a->pin_park.p[1]) return CMDP_OK;
+        return fail(CMDP_ERR_OVERFLOW, "an artificial episode outgrew its trace buffer: the bound the buffer is sized from does "
+                    "not hold (a defect of the library); the instance's last transition was taken and not counted, destroy the agent");
+      },
+      [&](int count) { return ucrl2_round(a, count, stop, n_steps); }, &h->uc_wait_ms, &h->uc_round_ms);
 }
 
 int cmdp_ucrl2_layout(cmdp_ucrl2_t* a, int64_t* n_positions, int64_t* row_ptr, int32_t* col) {
-  if (!a) return fail(CMDP_ERR_INVALID, "null agent");
-  cmdp_t* h = a->env;
-  if (int rc = bind(h)) return rc;
-  if (n_positions) *n_positions = a->nz;
-  if (row_ptr) HIP_TRY(hipMemcpyAsync(row_ptr, a->d_row_ptr.p, sizeof(int64_t) * (h->n_rows + 1), hipMemcpyDeviceToHost, h->stream));
-  if (col) HIP_TRY(hipMemcpyAsync(col, a->d_col.p, sizeof(int32_t) * a->nz, hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  return CMDP_OK;
+  return park_layout(a, n_positions, row_ptr, col);
 }
-
-#define UC_FETCH(dst, buf, type, n) \
-  if (dst) HIP_TRY(hipMemcpyAsync(dst, a->buf.p, sizeof(type) * (size_t)(n), hipMemcpyDeviceToHost, h->stream))
 
 int cmdp_ucrl2_model(cmdp_ucrl2_t* a, int32_t* N, float* P_val, float* uniform, float* estimated_rewards, float* variance_proxy,
                      float* holding_times, int64_t* iteration, int64_t* episode, double* delta) {
@@ -4194,9 +4282,9 @@ int cmdp_ucrl2_model(cmdp_ucrl2_t* a, int32_t* N, float* P_val, float* uniform, 
   cmdp_t* h = a->env;
   if (int rc = bind(h)) return rc;
   const int64_t R = h->n_rows;
-  UC_FETCH(N, d_N, int32_t, a->nz); UC_FETCH(P_val, d_val, float, a->nz); UC_FETCH(uniform, d_uni, float, R);
-  UC_FETCH(estimated_rewards, d_ER, float, R); UC_FETCH(variance_proxy, d_VR, float, R); UC_FETCH(holding_times, d_HT, float, R);
-  UC_FETCH(iteration, d_iteration, int64_t, h->B); UC_FETCH(episode, d_episode, int64_t, h->B); UC_FETCH(delta, d_delta, double, h->B);
+  AGENT_FETCH(N, d_N, a->nz); AGENT_FETCH(P_val, d_val, a->nz); AGENT_FETCH(uniform, d_uni, R);
+  AGENT_FETCH(estimated_rewards, d_ER, R); AGENT_FETCH(variance_proxy, d_VR, R); AGENT_FETCH(holding_times, d_HT, R);
+  AGENT_FETCH(iteration, d_iteration, h->B); AGENT_FETCH(episode, d_episode, h->B); AGENT_FETCH(delta, d_delta, h->B);
   HIP_TRY(hipStreamSynchronize(h->stream));
   return CMDP_OK;
 }
@@ -4207,38 +4295,29 @@ int cmdp_ucrl2_last_solve(cmdp_ucrl2_t* a, float* P_val, float* uniform, float* 
   cmdp_t* h = a->env;
   if (int rc = bind(h)) return rc;
   const int64_t R = h->n_rows;
-  UC_FETCH(P_val, d_sv_val, float, a->nz); UC_FETCH(uniform, d_sv_uni, float, R); UC_FETCH(rewards, d_sv_R, float, R);
-  UC_FETCH(beta_r, d_beta_r, double, R); UC_FETCH(beta_p0, d_beta_p0, double, R); UC_FETCH(Q, d_Q, float, R);
-  UC_FETCH(span, d_span, double, h->B); UC_FETCH(sweeps, d_sweeps, int64_t, h->B); UC_FETCH(status, d_status, int32_t, h->B);
+  AGENT_FETCH(P_val, d_sv_val, a->nz); AGENT_FETCH(uniform, d_sv_uni, R); AGENT_FETCH(rewards, d_sv_R, R);
+  AGENT_FETCH(beta_r, d_beta_r, R); AGENT_FETCH(beta_p0, d_beta_p0, R); AGENT_FETCH(Q, d_Q, R);
+  AGENT_FETCH(span, d_span, h->B); AGENT_FETCH(sweeps, d_sweeps, h->B); AGENT_FETCH(status, d_status, h->B);
   HIP_TRY(hipStreamSynchronize(h->stream));
   return CMDP_OK;
 }
-#undef UC_FETCH
 
 }  // extern "C"
 
 // ---- PSRL on the device (K12, cmdp_psrl.h) --------------------------------------------------------------------------
-struct cmdp_psrl {
-  cmdp_t* env = nullptr;
+struct cmdp_psrl : ParkAgent {
   int sampler = CMDP_PSRL_SAMPLER_REFERENCE;
-  int64_t nz = 0, t_total = 0;
+  int64_t t_total = 0;
   size_t sample_lds = 0, vi_lds = 0;
-  std::vector<int64_t> steps_total;    // [B] transitions taken since creation: bounds the float32 counts' exactness check
   std::vector<int64_t> h_toff, h_ptr;  // [B] padded offsets of the dense T; the layout (reference sampler)
   std::vector<int32_t> h_col;
   std::vector<float> h_prior, h_tp, h_rp, h_T, h_R;
   std::vector<cmdp_rc::NumpyStream> ts, rs;   // [B] RandomState(seed) of M_DIR and of N_NIG (reference sampler)
   PsArgs args{};
-  DevBuf<int64_t> d_row_ptr, d_episode, d_toff, d_roff, d_taken;
-  DevBuf<int32_t> d_col, d_slot, d_mtpos, d_park, d_S, d_A, d_obs;
+  DevBuf<int64_t> d_episode, d_toff, d_roff;
+  DevBuf<int32_t> d_S, d_A;
   DevBuf<float> d_tp, d_tprior, d_rp, d_T, d_Rs, d_Q, d_V;
-  DevBuf<double> d_rsum, d_rew;
-  DevBuf<long long> d_left;
-  DevBuf<uint32_t> d_mt;
   DevBuf<uint2> d_key;
-  DevBuf<int8_t> d_act;
-  DevBuf<uint8_t> d_mask;
-  PinnedBuf<int32_t> pin_park;   // [2 + B]: park count, unused, park list
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};   // around k_psrl_sample and k_vi_episodic_dense of the last round
   bool ev_sample = false, ev_vi = false;
   ~cmdp_psrl() {
@@ -4326,22 +4405,15 @@ int cmdp_psrl_create(cmdp_psrl_t** out, cmdp_t* env, const int32_t* seeds, int64
   *out = nullptr;
   if (sampler != CMDP_PSRL_SAMPLER_REFERENCE && sampler != CMDP_PSRL_SAMPLER_PHILOX)
     return fail(CMDP_ERR_INVALID, "sampler %d: CMDP_PSRL_SAMPLER_REFERENCE or CMDP_PSRL_SAMPLER_PHILOX", sampler);
-  if (actor != CMDP_ACTOR_GREEDY)
-    return fail(CMDP_ERR_UNSUPPORTED, "only the greedy actor is built: epsilon-greedy and Boltzmann exploration are not");
+  if (int rc = agent_check_actor(actor)) return rc;
   if (!env || !seeds || !reward_prior || !transition_prior)
     return fail(CMDP_ERR_INVALID, "null argument (environment handle, seeds or priors)");
   if (optimization_horizon < 1) return fail(CMDP_ERR_INVALID, "optimization_horizon < 1");
   if (int rc = bind(env)) return rc;
-  if (!env->has_env) return fail(CMDP_ERR_INVALID, "the environment handle was created without the sampler half");
-  if (env->H <= 0) return fail(CMDP_ERR_UNSUPPORTED, "PSRLEpisodic is the episodic setting's agent (PSRLContinuous is not built): "
-                               "the environment handle is continuous");
-  if (env->layout != CMDP_LAYOUT_CSR) return fail(CMDP_ERR_UNSUPPORTED, "agents run on the CSR layout");
-  if (env->reward_cache) return fail(CMDP_ERR_UNSUPPORTED, "CMDP_FLAG_REWARD_CACHE handles are not supported by the PSRL agent: "
-                                     "its walk kernel does not park for reward blocks");
-  if (env->max_S > PSRL_MAX_STATES)
-    return fail(CMDP_ERR_UNSUPPORTED, "an instance has %d states: the dense solver (K12) takes at most %d", env->max_S, PSRL_MAX_STATES);
+  if (int rc = park_check_env(env, true, "PSRLEpisodic is the episodic setting's agent (PSRLContinuous is not built): the "
+                              "environment handle is continuous", "PSRL", "the dense solver (K12)", PSRL_MAX_STATES)) return rc;
   const int B = env->B, A = env->A, H = env->H;
-  const int64_t R = env->n_rows, E = env->n_entries;
+  const int64_t R = env->n_rows;
   if ((int64_t)env->max_S * A * env->max_S > 0xffffffffLL)
     return fail(CMDP_ERR_UNSUPPORTED, "S * A * S of an instance exceeds 2^32: the Philox counter holds row * S + column in 32 bits");
   for (int b = 0; b < B; ++b) {
@@ -4354,39 +4426,15 @@ int cmdp_psrl_create(cmdp_psrl_t** out, cmdp_t* env, const int32_t* seeds, int64
   }
   hipStream_t st = env->stream;
   cmdp_psrl_t* a = new cmdp_psrl;
-  struct Guard { cmdp_psrl_t* a; ~Guard() { delete a; } } guard{a};
+  std::unique_ptr<cmdp_psrl> guard(a);
   a->env = env;
   a->sampler = sampler;
-  a->steps_total.assign((size_t)B, 0);
-  // K11's layout from the sampler's: per row the distinct successors in ascending order, every entry mapped to its position
-  std::vector<RowDesc> rows((size_t)R);
-  std::vector<int32_t> nxt((size_t)E);
-  std::vector<int64_t> ebase((size_t)B);
-  HIP_TRY(hipMemcpyAsync(rows.data(), env->d_row.p, sizeof(RowDesc) * R, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(nxt.data(), env->d_sp_next.p, sizeof(int32_t) * E, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(ebase.data(), env->d_entry_base.p, sizeof(int64_t) * B, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  std::vector<int64_t>& ptr = a->h_ptr;
-  std::vector<int32_t>& col = a->h_col;
-  ptr.assign((size_t)R + 1, 0);
-  std::vector<int32_t> slot((size_t)E, 0), tmp;
-  std::vector<float> tp;
+  if (int rc = build_model_layout(a, a->h_ptr, a->h_col)) return rc;
+  const int64_t NZ = a->nz;
+  std::vector<float> tp((size_t)NZ);   // the prior at every position of the instance's rows
   for (int b = 0; b < B; ++b)
-    for (int64_t r = env->state_off[b] * A; r < env->state_off[b + 1] * A; ++r) {
-      const int64_t lo = ebase[b] + rows[(size_t)r].first, n = rows[(size_t)r].n;
-      tmp.assign(nxt.begin() + lo, nxt.begin() + lo + n);
-      std::sort(tmp.begin(), tmp.end());
-      tmp.erase(std::unique(tmp.begin(), tmp.end()), tmp.end());
-      const int64_t z0 = (int64_t)col.size();
-      for (int64_t e = lo; e < lo + n; ++e)
-        slot[(size_t)e] = (int32_t)(z0 + (std::lower_bound(tmp.begin(), tmp.end(), nxt[(size_t)e]) - tmp.begin()));
-      col.insert(col.end(), tmp.begin(), tmp.end());
-      tp.insert(tp.end(), tmp.size(), transition_prior[b]);
-      ptr[(size_t)r + 1] = (int64_t)col.size();
-    }
-  const int64_t NZ = (int64_t)col.size();
-  if (NZ > 0x7fffffffLL) return fail(CMDP_ERR_UNSUPPORTED, "more than 2^31 successor positions");
-  a->nz = NZ;
+    std::fill(tp.begin() + a->h_ptr[(size_t)(env->state_off[b] * A)], tp.begin() + a->h_ptr[(size_t)(env->state_off[b + 1] * A)],
+              transition_prior[b]);
   std::vector<int32_t> hS((size_t)B), hA((size_t)B, A);
   std::vector<int64_t> roff((size_t)B);
   std::vector<float> rp((size_t)R * 4);
@@ -4412,9 +4460,6 @@ int cmdp_psrl_create(cmdp_psrl_t** out, cmdp_t* env, const int32_t* seeds, int64
                 "batch (sum of S * A * S float32) -- create smaller batches", (long long)(tt * 4));
   }
   HIP_TRY(a->d_T.zero(st));
-  HIP_TRY(a->d_row_ptr.upload(ptr.data(), ptr.size(), st));
-  HIP_TRY(a->d_col.upload(col.data(), col.size(), st));
-  HIP_TRY(a->d_slot.upload(slot.data(), slot.size(), st));
   HIP_TRY(a->d_tp.upload(tp.data(), tp.size(), st));
   HIP_TRY(a->d_tprior.upload(transition_prior, B, st));
   HIP_TRY(a->d_rp.upload(rp.data(), rp.size(), st));
@@ -4423,24 +4468,13 @@ int cmdp_psrl_create(cmdp_psrl_t** out, cmdp_t* env, const int32_t* seeds, int64
   HIP_TRY(a->d_S.upload(hS.data(), B, st));
   HIP_TRY(a->d_A.upload(hA.data(), B, st));
   HIP_TRY(a->d_key.upload(keys.data(), B, st));
-#define PS_ZERO(buf, n) HIP_TRY(a->buf.alloc((size_t)(n))); HIP_TRY(a->buf.zero(st))
-  PS_ZERO(d_episode, B); PS_ZERO(d_Rs, R); PS_ZERO(d_Q, (size_t)(H + 1) * R); PS_ZERO(d_V, (size_t)(H + 1) * env->n_states);
-  PS_ZERO(d_left, B); PS_ZERO(d_taken, B); PS_ZERO(d_park, B + 2); PS_ZERO(d_rsum, B);
-#undef PS_ZERO
-  HIP_TRY(a->d_mt.alloc((size_t)B * 624));
-  HIP_TRY(a->d_mtpos.alloc(B));
-  if (int rc = a->pin_park.alloc((size_t)B + 2)) return rc;
+  AGENT_ZERO(d_episode, B); AGENT_ZERO(d_Rs, R); AGENT_ZERO(d_Q, (size_t)(H + 1) * R); AGENT_ZERO(d_V, (size_t)(H + 1) * env->n_states);
+  if (int rc = park_alloc(a, seeds)) return rc;
   for (hipEvent_t& e : a->ev) HIP_TRY(hipEventCreate(&e));
-  std::vector<uint32_t> useeds((size_t)B);
-  for (int b = 0; b < B; ++b) useeds[b] = (uint32_t)seeds[b];
-  DevBuf<uint32_t> d_seeds;
-  HIP_TRY(d_seeds.upload(useeds.data(), B, st));
-  hipLaunchKernelGGL(k_mt_seed_numpy, dim3(grid_for(B, 64)), dim3(64), 0, st, a->d_mt.p, a->d_mtpos.p, d_seeds.p, B);
-  HIP_TRY(hipGetLastError());
   if (sampler == CMDP_PSRL_SAMPLER_REFERENCE) {
     a->ts.resize((size_t)B);
     a->rs.resize((size_t)B);
-    for (int b = 0; b < B; ++b) { psrl_host::seed_numpy(a->ts[b], useeds[b]); psrl_host::seed_numpy(a->rs[b], useeds[b]); }
+    for (int b = 0; b < B; ++b) { psrl_host::seed_numpy(a->ts[b], (uint32_t)seeds[b]); psrl_host::seed_numpy(a->rs[b], (uint32_t)seeds[b]); }
     try {
       a->h_tp.resize((size_t)NZ); a->h_rp.resize((size_t)R * 4); a->h_T.resize((size_t)tt); a->h_R.resize((size_t)R);
     } catch (const std::bad_alloc&) {
@@ -4453,130 +4487,57 @@ int cmdp_psrl_create(cmdp_psrl_t** out, cmdp_t* env, const int32_t* seeds, int64
   p.tp = a->d_tp.p; p.tprior = a->d_tprior.p; p.rp = a->d_rp.p; p.episode = a->d_episode.p; p.key = a->d_key.p;
   p.t_off = a->d_toff.p; p.T = a->d_T.p; p.Rs = a->d_Rs.p; p.Q = a->d_Q.p; p.V = a->d_V.p;
   p.mt = a->d_mt.p; p.mt_pos = a->d_mtpos.p;
-  p.left = a->d_left.p; p.taken = a->d_taken.p; p.park_count = a->d_park.p; p.park_list = a->d_park.p + 2;
+  p.call = a->call();
   // before_start_interacting (posterior_sampling.py:146-147): one episode_end_update on the prior -- every instance
-  a->pin_park.p[0] = B; a->pin_park.p[1] = 0;
-  for (int b = 0; b < B; ++b) a->pin_park.p[2 + b] = b;
-  HIP_TRY(hipMemcpyAsync(a->d_park.p, a->pin_park.p, sizeof(int32_t) * (B + 2), hipMemcpyHostToDevice, st));
+  if (int rc = park_all(a)) return rc;
   if (int rc = psrl_round(a, B, 0, 0, 0)) return rc;
   HIP_TRY(hipStreamSynchronize(st));
   psrl_times(a);
-  env->uc_backrefs.push_back(&a->env);
-  guard.a = nullptr;
-  *out = a;
-  return CMDP_OK;
+  return park_attach(guard, out);
 }
 
-int cmdp_psrl_destroy(cmdp_psrl_t* a) {
-  if (!a) return CMDP_OK;
-  if (a->env) {   // null once the environment handle has been destroyed (its stream was drained then)
-    (void)hipSetDevice(a->env->device);
-    (void)hipStreamSynchronize(a->env->stream);
-    auto& v = a->env->uc_backrefs;
-    v.erase(std::remove(v.begin(), v.end(), &a->env), v.end());
-  }
-  delete a;
-  return CMDP_OK;
-}
+int cmdp_psrl_destroy(cmdp_psrl_t* a) { return park_destroy(a); }
 
 int cmdp_psrl_run(cmdp_psrl_t* a, int64_t n_steps, int stop_at_episode_end, const uint8_t* train_mask, int8_t* actions_trace,
                   int32_t* obs_trace, double* reward_trace, double* cumulative_reward, int64_t* steps_taken) {
-  if (!a) return fail(CMDP_ERR_INVALID, "null agent");
+  if (int rc = park_run_check(a, n_steps, 1LL << 24, "a transition count of the model (float32, as the reference's "
+                              "hyper-parameters) would stop counting at 2^24: instance %d has taken %lld steps, %lld more asked for"))
+    return rc;
   cmdp_t* h = a->env;
-  if (int rc = bind(h)) return rc;
-  if (n_steps < 0) return fail(CMDP_ERR_INVALID, "n_steps < 0");
-  bool any = false;
-  if (int rc = any_needs_reset(h, &any)) return rc;
-  if (any) return fail(CMDP_ERR_NEEDS_RESET, "the environment needs reset() before the agent can run");
-  const int B = h->B;
-  hipStream_t st = h->stream;
-  if (int rc = visits_check(h, n_steps)) return rc;
-  for (int b = 0; b < B; ++b)
-    if (a->steps_total[b] + n_steps > (1LL << 24))
-      return fail(CMDP_ERR_OVERFLOW, "a transition count of the model (float32, as the reference's hyper-parameters) would stop "
-                  "counting at 2^24: instance %d has taken %lld steps, %lld more asked for", b, (long long)a->steps_total[b],
-                  (long long)n_steps);
-  const size_t NB = (size_t)n_steps * B;
-  if (actions_trace && a->d_act.n < NB) HIP_TRY(a->d_act.alloc(NB));
-  if (obs_trace && a->d_obs.n < NB) HIP_TRY(a->d_obs.alloc(NB));
-  if (reward_trace && a->d_rew.n < NB) HIP_TRY(a->d_rew.alloc(NB));
-  const uint8_t* dmask = nullptr;
-  if (train_mask) {
-    HIP_TRY(a->d_mask.upload(train_mask, B, st));
-    dmask = a->d_mask.p;
-  }
-  std::vector<long long> left((size_t)B, (long long)n_steps);
-  std::vector<int64_t> taken((size_t)B, n_steps);
-  HIP_TRY(hipMemcpyAsync(a->d_left.p, left.data(), sizeof(long long) * B, hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemcpyAsync(a->d_taken.p, taken.data(), sizeof(int64_t) * B, hipMemcpyHostToDevice, st));
-  int rc = CMDP_OK;
-  while (n_steps > 0) {
-    HIP_TRY(hipMemsetAsync(a->d_park.p, 0, sizeof(int32_t) * 2, st));
-    hipLaunchKernelGGL(k_psrl_walk, dim3(grid_for(B, 256)), dim3(256), 0, st, h->env(), a->args, n_steps, dmask,
-                       actions_trace ? a->d_act.p : nullptr, obs_trace ? a->d_obs.p : nullptr,
-                       reward_trace ? a->d_rew.p : nullptr, a->d_rsum.p);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(a->pin_park.p, a->d_park.p, sizeof(int32_t) * (B + 2), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));   // the previous round's kernels and this walk
-    psrl_times(a);
-    const int count = a->pin_park.p[0];
-    if (count == 0) break;
-    std::sort(a->pin_park.p + 2, a->pin_park.p + 2 + count);   // the order instances parked in is not deterministic
-    HIP_TRY(hipMemcpyAsync(a->d_park.p + 2, a->pin_park.p + 2, sizeof(int32_t) * count, hipMemcpyHostToDevice, st));
-    if ((rc = psrl_round(a, count, 1, stop_at_episode_end ? 1 : 0, n_steps))) break;
-    if (stop_at_episode_end) break;   // every instance either finished its steps or has just been stopped
-  }
-  if (rc == CMDP_OK && n_steps > 0) {
-    HIP_TRY(hipMemcpyAsync(taken.data(), a->d_taken.p, sizeof(int64_t) * B, hipMemcpyDeviceToHost, st));
-    if (actions_trace) HIP_TRY(hipMemcpyAsync(actions_trace, a->d_act.p, NB, hipMemcpyDeviceToHost, st));
-    if (obs_trace) HIP_TRY(hipMemcpyAsync(obs_trace, a->d_obs.p, sizeof(int32_t) * NB, hipMemcpyDeviceToHost, st));
-    if (reward_trace) HIP_TRY(hipMemcpyAsync(reward_trace, a->d_rew.p, sizeof(double) * NB, hipMemcpyDeviceToHost, st));
-  }
-  if (cumulative_reward) HIP_TRY(hipMemcpyAsync(cumulative_reward, a->d_rsum.p, sizeof(double) * B, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  psrl_times(a);
-  for (int b = 0; b < B; ++b) {
-    a->steps_total[b] += rc == CMDP_OK ? taken[b] : n_steps;
-    if (steps_taken) steps_taken[b] = taken[b];
-  }
-  return visits_commit(h, n_steps, rc);
+  const int stop = stop_at_episode_end ? 1 : 0;
+  const int rc = park_run(
+      a, n_steps, stop, train_mask, actions_trace, obs_trace, reward_trace, cumulative_reward, steps_taken,
+      [&](const uint8_t* dmask, int8_t* act, int32_t* obs, double* rew) {
+        hipLaunchKernelGGL(k_psrl_walk, dim3(grid_for(h->B, 256)), dim3(256), 0, h->stream, h->env(), a->args, n_steps, dmask, act,
+                           obs, rew, a->d_rsum.p);
+      },
+      [&]() -> int { psrl_times(a); return CMDP_OK; }, [&](int count) { return psrl_round(a, count, 1, stop, n_steps); });
+  psrl_times(a);   // after the call's last synchronisation
+  return rc;
 }
 
 int cmdp_psrl_episode_end_update(cmdp_psrl_t* a) {
   if (!a) return fail(CMDP_ERR_INVALID, "null agent");
   cmdp_t* h = a->env;
   if (int rc = bind(h)) return rc;
-  const int B = h->B;
-  hipStream_t st = h->stream;
-  a->pin_park.p[0] = B; a->pin_park.p[1] = 0;
-  for (int b = 0; b < B; ++b) a->pin_park.p[2 + b] = b;
-  HIP_TRY(hipMemcpyAsync(a->d_park.p, a->pin_park.p, sizeof(int32_t) * (B + 2), hipMemcpyHostToDevice, st));
-  if (int rc = psrl_round(a, B, 0, 0, 0)) return rc;
-  HIP_TRY(hipStreamSynchronize(st));
+  if (int rc = park_all(a)) return rc;
+  if (int rc = psrl_round(a, h->B, 0, 0, 0)) return rc;
+  HIP_TRY(hipStreamSynchronize(h->stream));
   psrl_times(a);
   return CMDP_OK;
 }
 
 int cmdp_psrl_layout(cmdp_psrl_t* a, int64_t* n_positions, int64_t* row_ptr, int32_t* col) {
-  if (!a) return fail(CMDP_ERR_INVALID, "null agent");
-  cmdp_t* h = a->env;
-  if (int rc = bind(h)) return rc;
-  if (n_positions) *n_positions = a->nz;
-  if (row_ptr) std::memcpy(row_ptr, a->h_ptr.data(), sizeof(int64_t) * (h->n_rows + 1));
-  if (col) std::memcpy(col, a->h_col.data(), sizeof(int32_t) * a->nz);
-  return CMDP_OK;
+  return park_layout(a, n_positions, row_ptr, col);
 }
 
 int cmdp_psrl_model(cmdp_psrl_t* a, float* reward_hp, float* transition_hp, float* transition_prior, int64_t* episodes) {
   if (!a) return fail(CMDP_ERR_INVALID, "null agent");
   cmdp_t* h = a->env;
   if (int rc = bind(h)) return rc;
-  hipStream_t st = h->stream;
-  if (reward_hp) HIP_TRY(hipMemcpyAsync(reward_hp, a->d_rp.p, sizeof(float) * 4 * h->n_rows, hipMemcpyDeviceToHost, st));
-  if (transition_hp) HIP_TRY(hipMemcpyAsync(transition_hp, a->d_tp.p, sizeof(float) * a->nz, hipMemcpyDeviceToHost, st));
+  AGENT_FETCH(reward_hp, d_rp, 4 * h->n_rows); AGENT_FETCH(transition_hp, d_tp, a->nz); AGENT_FETCH(episodes, d_episode, h->B);
   if (transition_prior) std::memcpy(transition_prior, a->h_prior.data(), sizeof(float) * h->B);
-  if (episodes) HIP_TRY(hipMemcpyAsync(episodes, a->d_episode.p, sizeof(int64_t) * h->B, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
+  HIP_TRY(hipStreamSynchronize(h->stream));
   return CMDP_OK;
 }
 
@@ -4593,8 +4554,7 @@ int cmdp_psrl_last_sample(cmdp_psrl_t* a, float* T, float* R, float* Q) {
       o += n;
     }
   }
-  if (R) HIP_TRY(hipMemcpyAsync(R, a->d_Rs.p, sizeof(float) * h->n_rows, hipMemcpyDeviceToHost, st));
-  if (Q) HIP_TRY(hipMemcpyAsync(Q, a->d_Q.p, sizeof(float) * (h->H + 1) * h->n_rows, hipMemcpyDeviceToHost, st));
+  AGENT_FETCH(R, d_Rs, h->n_rows); AGENT_FETCH(Q, d_Q, (h->H + 1) * h->n_rows);
   HIP_TRY(hipStreamSynchronize(st));
   return CMDP_OK;
 }

@@ -44,6 +44,50 @@ __global__ void k_fill_i32(int32_t* __restrict__ p, int32_t v, int64_t n) {
   if (i < n) p[i] = v;
 }
 
+// ---- QValuesActor.select_action (Q_values_actor.py:67-88): greedy with uniform tie-break ----
+// The draw of every agent's walk kernel.  RandomState.choice(ties) == ties[randint(0, n)]: masked rejection on 32-bit draws
+__device__ __forceinline__ int tie_break_draw(int n_tie, uint32_t* mt, int32_t* mtp) {
+  const uint32_t mx = (uint32_t)(n_tie - 1);
+  uint32_t mask = mx;
+  mask |= mask >> 1; mask |= mask >> 2; mask |= mask >> 4; mask |= mask >> 8; mask |= mask >> 16;
+  int pos = *mtp;
+  uint32_t v;
+  do { v = mt_next_word(mt, pos) & mask; } while (v > mx);
+  *mtp = pos;
+  return (int)v;
+}
+
+// The whole selection on a row in memory (any A).  k_psrl_walk uses it; the kernels that keep the row in registers for
+// A <= 4 (k_qlearn_episodic, k_qlearn_continuous, k_ucrl2_walk) spell the selection out around tie_break_draw: behind a
+// helper their register allocation changes (they sit at 256 VGPRs), so their text stays as it was.
+__device__ __forceinline__ int greedy_action_row(const float* qrow, int A, uint32_t* mt, int32_t* mtp) {
+  float qmax = qrow[0];
+  int n_tie = 0;
+  for (int a = 1; a < A; ++a) qmax = fmaxf(qmax, qrow[a]);
+  for (int a = 0; a < A; ++a) n_tie += (qrow[a] == qmax) ? 1 : 0;
+  const int pick = n_tie > 1 ? tie_break_draw(n_tie, mt, mtp) : 0;
+  int action = 0;
+  for (int a = 0, k = 0; a < A; ++a)
+    if (qrow[a] == qmax) { if (k == pick) action = a; ++k; }
+  return action;
+}
+
+// State of one run() call of an agent that parks its instances for a solve (UCRL2, PSRL)
+struct ParkCall {
+  long long* left;         // [B] steps the instance still owes
+  int64_t* taken;          // [B] steps taken when the instance was stopped at an episode end
+  int32_t* park_count;
+  int32_t* park_list;      // [B]
+};
+
+// the end of a round: with `stop` the instance gives up the steps it still owes
+__device__ __forceinline__ void park_release(const ParkCall& c, int b, int stop, int64_t n_steps) {
+  if (stop) {
+    c.taken[b] = n_steps - c.left[b];
+    c.left[b] = 0;
+  }
+}
+
 // RC: reference-exact reward caches (cmdp_reward_cache.h) -- a lane parks after a transition whose reward block is
 // missing; the relaunch (`resume`) completes the saved step first and continues with the steps the lane still owes.
 template <int UCB, bool RC>
@@ -129,17 +173,7 @@ __global__ void __launch_bounds__(256) k_qlearn_episodic(EnvTables t, QlArgs q, 
         for (int a = 1; a < A; ++a) qmax = fmaxf(qmax, qrow[a]);
         for (int a = 0; a < A; ++a) n_tie += (qrow[a] == qmax) ? 1 : 0;
       }
-      int pick = 0;
-      if (n_tie > 1) {  // RandomState.choice(ties) == ties[randint(0, n)]: masked rejection on 32-bit draws
-        const uint32_t mx = (uint32_t)(n_tie - 1);
-        uint32_t mask = mx;
-        mask |= mask >> 1; mask |= mask >> 2; mask |= mask >> 4; mask |= mask >> 8; mask |= mask >> 16;
-        int pos = *mtp;
-        uint32_t v;
-        do { v = mt_next_word(mt, pos) & mask; } while (v > mx);
-        *mtp = pos;
-        pick = (int)v;
-      }
+      const int pick = n_tie > 1 ? tie_break_draw(n_tie, mt, mtp) : 0;
       if (fastA) {
         int k = 0;
 #pragma unroll
@@ -560,17 +594,7 @@ __global__ void __launch_bounds__(256) k_qlearn_continuous(EnvTables t, QlcArgs 
         for (int a = 1; a < A; ++a) qmax = fmax(qmax, qrow[a]);
         for (int a = 0; a < A; ++a) n_tie += (qrow[a] == qmax) ? 1 : 0;
       }
-      int pick = 0;
-      if (n_tie > 1) {
-        const uint32_t mx = (uint32_t)(n_tie - 1);
-        uint32_t mask = mx;
-        mask |= mask >> 1; mask |= mask >> 2; mask |= mask >> 4; mask |= mask >> 8; mask |= mask >> 16;
-        int pos = *mtp;
-        uint32_t v;
-        do { v = mt_next_word(mt, pos) & mask; } while (v > mx);
-        *mtp = pos;
-        pick = (int)v;
-      }
+      const int pick = n_tie > 1 ? tie_break_draw(n_tie, mt, mtp) : 0;
       if (fastA) {
         int k = 0;
 #pragma unroll

@@ -24,7 +24,7 @@
 // CMDP_PSRL_SAMPLER_REFERENCE draws on the host instead of k_psrl_sample (psrl_host::reference_draw below: numpy's legacy
 // samplers on each instance's two RandomState(seed) streams, glibc's libm, numpy's pairwise float32 sum).
 #pragma once
-#include "cmdp_kernels.h"
+#include "cmdp_agent.h"
 #include "cmdp_reward_cache.h"
 
 #define PSRL_SAMPLE_THREADS 256
@@ -50,11 +50,7 @@ struct PsArgs {
   float* V;                // [(H + 1) * n_states]
   uint32_t* mt;            // [B][624] numpy RandomState(seed) of the actor
   int32_t* mt_pos;
-  // state of the call
-  long long* left;         // [B] steps the instance still owes
-  int64_t* taken;          // [B] steps taken when the instance was stopped at an episode end
-  int32_t* park_count;
-  int32_t* park_list;      // [B]
+  ParkCall call;           // state of the call
 };
 
 __global__ void __launch_bounds__(256) k_psrl_walk(EnvTables t, PsArgs p, int64_t n_steps, const uint8_t* __restrict__ train_mask,
@@ -62,7 +58,7 @@ __global__ void __launch_bounds__(256) k_psrl_walk(EnvTables t, PsArgs p, int64_
                                                    double* __restrict__ rew_trace, double* __restrict__ cum_reward) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= t.B) return;
-  long long left = p.left[b];
+  long long left = p.call.left[b];
   if (left == 0) return;
   const int64_t soff = t.state_off[b], ebase = t.entry_base[b];
   const int S = (int)(t.state_off[b + 1] - soff);
@@ -82,23 +78,7 @@ __global__ void __launch_bounds__(256) k_psrl_walk(EnvTables t, PsArgs p, int64_
     int action = 0;
     {  // ---- QValuesActor.select_action: greedy with uniform tie-break ----
       const float* qrow = Q + ((int64_t)h * S + cur) * A;
-      float qmax = qrow[0];
-      int n_tie = 0;
-      for (int a = 1; a < A; ++a) qmax = fmaxf(qmax, qrow[a]);
-      for (int a = 0; a < A; ++a) n_tie += (qrow[a] == qmax) ? 1 : 0;
-      int pick = 0;
-      if (n_tie > 1) {  // RandomState.choice(ties) == ties[randint(0, n)]: masked rejection on 32-bit draws
-        const uint32_t mx = (uint32_t)(n_tie - 1);
-        uint32_t mask = mx;
-        mask |= mask >> 1; mask |= mask >> 2; mask |= mask >> 4; mask |= mask >> 8; mask |= mask >> 16;
-        int pos = *mtp;
-        uint32_t v;
-        do { v = mt_next_word(mt, pos) & mask; } while (v > mx);
-        *mtp = pos;
-        pick = (int)v;
-      }
-      for (int a = 0, k = 0; a < A; ++a)
-        if (qrow[a] == qmax) { if (k == pick) action = a; ++k; }
+      action = greedy_action_row(qrow, A, mt, mtp);
     }
     const int32_t idx = cur * A + action;
     // ---- BaseMDP.step ----
@@ -146,8 +126,8 @@ __global__ void __launch_bounds__(256) k_psrl_walk(EnvTables t, PsArgs p, int64_
   t.n_trans[b] = nt;
   t.n_reset[b] = nr;
   cum_reward[b] = sum;
-  p.left[b] = left;
-  if (parked) p.park_list[atomicAdd(p.park_count, 1)] = b;
+  p.call.left[b] = left;
+  if (parked) p.call.park_list[atomicAdd(p.call.park_count, 1)] = b;
 }
 
 __device__ __forceinline__ double psrl_wave_sum(double x) {
@@ -291,10 +271,7 @@ __global__ void __launch_bounds__(256) k_psrl_resume(EnvTables t, PsArgs p, cons
     t.need_reset[b] = 0;
   }
   p.episode[b] += 1;
-  if (stop) {
-    p.taken[b] = n_steps - p.left[b];
-    p.left[b] = 0;
-  }
+  park_release(p.call, b, stop, n_steps);
 }
 
 // ---- host side: the reference's own posterior sample ----------------------------------------------------------------

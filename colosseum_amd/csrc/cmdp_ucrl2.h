@@ -19,7 +19,7 @@
 // The only transcendental of the bounds, math.log(log_C * (iteration + 1) / delta), is one or two scalars per instance
 // and solve: the host takes them with std::log (what CPython calls) while it reads the park list.
 #pragma once
-#include "cmdp_kernels.h"
+#include "cmdp_agent.h"
 
 #define UCRL2_THREADS 256
 
@@ -50,11 +50,7 @@ struct UcArgs {
   double* tr_rew;
   int64_t* tr_len;         // [B]
   int64_t tr_cap;
-  // state of the call
-  long long* left;         // [B] steps the instance still owes
-  int64_t* taken;          // [B] steps taken when the instance was stopped at an episode end
-  int32_t* park_count;
-  int32_t* park_list;      // [B]
+  ParkCall call;           // state of the call
   int32_t* overflow;       // set when a trace would not fit (cannot happen: the host sizes it from the episode bound)
   // the last solve: its inputs (snapshot) and outputs
   float* sv_val; float* sv_uni; float* sv_R;
@@ -82,7 +78,7 @@ __global__ void __launch_bounds__(256) k_ucrl2_walk(EnvTables t, UcArgs u, int64
                                                     double* __restrict__ cum_reward) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= t.B) return;
-  long long left = u.left[b];
+  long long left = u.call.left[b];
   if (left == 0) return;
   const int64_t soff = t.state_off[b], ebase = t.entry_base[b];
   const int A = t.A;
@@ -132,17 +128,7 @@ __global__ void __launch_bounds__(256) k_ucrl2_walk(EnvTables t, UcArgs u, int64
         for (int a = 1; a < A; ++a) qmax = fmaxf(qmax, qrow[a]);
         for (int a = 0; a < A; ++a) n_tie += (qrow[a] == qmax) ? 1 : 0;
       }
-      int pick = 0;
-      if (n_tie > 1) {  // RandomState.choice(ties) == ties[randint(0, n)]: masked rejection on 32-bit draws
-        const uint32_t mx = (uint32_t)(n_tie - 1);
-        uint32_t mask = mx;
-        mask |= mask >> 1; mask |= mask >> 2; mask |= mask >> 4; mask |= mask >> 8; mask |= mask >> 16;
-        int pos = *mtp;
-        uint32_t v;
-        do { v = mt_next_word(mt, pos) & mask; } while (v > mx);
-        *mtp = pos;
-        pick = (int)v;
-      }
+      const int pick = n_tie > 1 ? tie_break_draw(n_tie, mt, mtp) : 0;
       if (fastA) {
         int k = 0;
 #pragma unroll
@@ -202,9 +188,9 @@ __global__ void __launch_bounds__(256) k_ucrl2_walk(EnvTables t, UcArgs u, int64
   t.hstep[b] = h;
   t.n_trans[b] = nt;
   cum_reward[b] = sum;
-  u.left[b] = left;
+  u.call.left[b] = left;
   u.tr_len[b] = len;
-  if (parked) u.park_list[atomicAdd(u.park_count, 1)] = b;
+  if (parked) u.call.park_list[atomicAdd(u.call.park_count, 1)] = b;
 }
 
 // beta_r (ucrl2.py:240-259, Chernoff) and element 0 of beta_p[s, a] (:275-308, the only one extended_value_iteration reads)
@@ -331,9 +317,6 @@ __global__ void __launch_bounds__(UCRL2_THREADS) k_ucrl2_update(UcArgs u, UcRoun
     u.episode[b] += 1;
     u.delta[b] = g.delta[k];
     u.tr_len[b] = 0;
-    if (stop) {
-      u.taken[b] = n_steps - u.left[b];
-      u.left[b] = 0;
-    }
+    park_release(u.call, b, stop, n_steps);
   }
 }

@@ -387,3 +387,17 @@ def test_refusals(need_gpu):
     with pytest.raises(L.CmdpError) as e:
         agent.run(1 << 25)
     assert e.value.code == L.ERR_OVERFLOW
+
+
+def test_agent_destroyed_after_its_environment(need_gpu):
+    """Garbage collection picks the order: cmdp_destroy orphans the handle's agents, which then refuse to run and free
+    only their own memory (the path tests/test_gpu_ucrl2.py holds the UCRL2 agent to)."""
+    env = make_env([make_model("DeepSeaEpisodic", seed=0, size=4)], "mt", False)
+    agent = BatchedPSRLEpisodic(env, [0], 100)
+    agent.run(50)
+    env._agents = []   # as when the weak references are already dead
+    env.close()
+    with pytest.raises(L.CmdpError) as ei:
+        agent.run(10)
+    assert ei.value.code == L.ERR_INVALID
+    agent.close()
