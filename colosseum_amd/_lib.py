@@ -31,6 +31,7 @@ STAT_DIAMETER_CLUSTER_LAUNCHES, STAT_DIAMETER_CLUSTER_FALLBACKS = 10, 11
 STAT_UCRL2_UNCONVERGED, STAT_UCRL2_ROUNDS, STAT_UCRL2_SOLVES, STAT_UCRL2_ROUND_MS = 12, 13, 14, 15
 STAT_UCRL2_WAIT_MS = 16
 STAT_PSRL_ROUNDS, STAT_PSRL_SOLVES, STAT_PSRL_SAMPLE_KERNEL_MS, STAT_PSRL_VI_KERNEL_MS, STAT_PSRL_REFERENCE_MS = 17, 18, 19, 20, 21
+STAT_DIAMETER_KERNEL = 22  # family * 1000 + n * 10 + flag, see include/cmdp.h
 PSRL_SAMPLER_REFERENCE, PSRL_SAMPLER_PHILOX = 0, 1
 PSRL_KEY_HI = 0x5053524C
 BOUND_CHERNOFF, BOUND_BERNSTEIN = 0, 1

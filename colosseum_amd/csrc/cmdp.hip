@@ -247,6 +247,7 @@ struct cmdp {
   int64_t k5c_launches = 0, k5c_timeouts = 0;
   int k5c_skip = 0, k5c_backoff = 0;   // after a give-up K5C is skipped for `k5c_backoff` calls (8, 16, ... 1024), then tried again
   bool k5c_agent_scope = false;     // K5C: a cluster was found spread over XCDs once -- agent-scope barriers from then on
+  int last_diam_kernel = 0;         // CMDP_STAT_DIAMETER_KERNEL: diam_code(...) of the last launch of the last diameter call
   size_t dl_ws_bytes = (size_t)24 << 30;  // value arrays of the target groups in flight per launch
   // observation tables (k_emit)
   DevBuf<float> d_obs_table, d_obs_out, d_obs_chol;
@@ -1517,6 +1518,10 @@ int cmdp_stat(cmdp_t* h, int which, double* out) {
     *out = (double)(which == CMDP_STAT_REWARD_FILLS ? h->rc_fills : h->rc_rounds);
     return CMDP_OK;
   }
+  if (which == CMDP_STAT_DIAMETER_KERNEL) {
+    *out = h->last_diam_kernel;
+    return CMDP_OK;
+  }
   if (which == CMDP_STAT_DIAMETER_CLUSTER_LAUNCHES || which == CMDP_STAT_DIAMETER_CLUSTER_FALLBACKS) {
     *out = (double)(which == CMDP_STAT_DIAMETER_CLUSTER_LAUNCHES ? h->k5c_launches : h->k5c_timeouts);
     return CMDP_OK;
@@ -1691,6 +1696,11 @@ int resolve_scheme(cmdp_t* h, int scheme, bool pe, bool diam, int* out) {
   return CMDP_OK;
 }
 
+// CMDP_STAT_DIAMETER_KERNEL (include/cmdp.h documents the encoding): family, wavefronts per group or workgroups per
+// cluster, and a flag -- K2: the CSR lives in LDS; K5C: the barriers are XCD-scope
+enum DiamFamily { DIAM_K2 = 1, DIAM_K3 = 2, DIAM_K5S_ELL = 3, DIAM_K5S_CSR = 4, DIAM_K5C = 5, DIAM_K5T = 6 };
+constexpr int diam_code(int family, int n, bool flag) { return family * 1000 + n * 10 + (flag ? 1 : 0); }
+
 DpShape dp_shape(const cmdp_t* h) { return {h->A, h->max_row_nnz, h->max_state_unique, h->max_S, h->max_inst_nnz}; }
 
 // The fields every DP kernel reads: the batch's CSR and its rewards.  The rest is zero; callers set what their kernel needs.
@@ -1755,6 +1765,7 @@ int run_sweeps(cmdp_t* h, int mode, bool diam, int scheme, DpTables t, int64_t u
   if (rc) return rc;
   HIP_TRY(hipGetLastError());
   h->last_dp_kernel = c.family;
+  if (diam) h->last_diam_kernel = c.family == SWEEP_K2 ? diam_code(DIAM_K2, 0, c.csr_lds) : diam_code(DIAM_K3, 0, 0);
   return CMDP_OK;
 }
 
@@ -2236,7 +2247,12 @@ static int diameter_lanes(cmdp_t* h, DpTables t, int64_t unit_lo, int64_t unit_h
       int err = 0;
       HIP_TRY(hipMemcpyAsync(&err, ca.err, sizeof(int), hipMemcpyDeviceToHost, st));
       HIP_TRY(hipStreamSynchronize(st));
-      if (!err) { h->k5c_launches++; h->k5c_backoff = 0; return CMDP_OK; }
+      if (!err) {
+        h->k5c_launches++;
+        h->k5c_backoff = 0;
+        h->last_diam_kernel = diam_code(DIAM_K5C, CLs, pass == 0);
+        return CMDP_OK;
+      }
       if (err == 2 && pass == 0) { h->k5c_agent_scope = true; continue; }   // this device does not deal workgroups as assumed
       h->k5c_timeouts++;   // a cluster's workgroups were not all resident: the groups are solved again, one workgroup each
       h->k5c_backoff = std::min(1024, std::max(8, 2 * h->k5c_backoff));
@@ -2272,6 +2288,7 @@ static int diameter_lanes(cmdp_t* h, DpTables t, int64_t unit_lo, int64_t unit_h
     HIP_TRY(h->d_dl_voff.upload(voff.data(), n, st));
     DiamLanesArgs g{h->d_dl_inst.p, h->d_dl_t0.p, h->d_dl_cnt.p, h->d_dl_voff.p, h->d_dl_v.p};
     bool ell = false;
+    int ell_nw = 0;  // wavefronts per group of the K5S-ELL launch
     // K5T (value rows gathered into LDS tiles per cluster of states): on request only (option 6).  At C5 it halves the
     // HBM traffic of K5S and is bit-equal, but runs 2.3 s against 2.05 s -- see DESIGN.md.
     bool tiles = false;
@@ -2308,6 +2325,7 @@ static int diameter_lanes(cmdp_t* h, DpTables t, int64_t unit_lo, int64_t unit_h
       // (and 16 with the locality order: half as many groups share an L2, so a row is still there when the next chunk
       // wants it -- C5 1.83 -> 1.75 s)
       const int k5s_nw = k5s_env ? k5s_env : (((int64_t)n <= (int64_t)h->cus || h->ell_relabelled) ? 16 : 8);
+      ell_nw = k5s_nw == 16 || k5s_nw == 4 ? k5s_nw : 8;
 #define ELL_CASE(P, AT, KT)                                                                                        \
   if (A == AT && K == KT) {                                                                                       \
     if (k5s_nw == 16)                                                                                             \
@@ -2325,6 +2343,8 @@ static int diameter_lanes(cmdp_t* h, DpTables t, int64_t unit_lo, int64_t unit_h
     }
     if (!ell) hipLaunchKernelGGL(k_diam_lanes<8>, dim3((unsigned)n), dim3(512), 0, st, t, g);
     HIP_TRY(hipGetLastError());
+    h->last_diam_kernel = tiles ? diam_code(DIAM_K5T, kK5tNw, false) : ell ? diam_code(DIAM_K5S_ELL, ell_nw, false)
+                                                                           : diam_code(DIAM_K5S_CSR, 8, false);
     HIP_TRY(hipStreamSynchronize(st));  // the upload staging vectors die at the end of this iteration
     g0 = g1;
   }

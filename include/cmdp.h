@@ -244,7 +244,22 @@ enum { CMDP_STAT_DP_KERNEL_MS = 1, CMDP_STAT_DP_KERNEL = 2,
        CMDP_STAT_PSRL_SOLVES = 18,           /* ... instances solved in those rounds (= episodes, the solve on the prior included) */
        CMDP_STAT_PSRL_SAMPLE_KERNEL_MS = 19, /* ... HIP-event time of the last round's k_psrl_sample (Philox sampler)              */
        CMDP_STAT_PSRL_VI_KERNEL_MS = 20,     /* ... HIP-event time of the last round's k_vi_episodic_dense                         */
-       CMDP_STAT_PSRL_REFERENCE_MS = 21      /* ... host wall time spent in the reference sampler's draws, all rounds together     */ };
+       CMDP_STAT_PSRL_REFERENCE_MS = 21      /* ... host wall time spent in the reference sampler's draws, all rounds together     */,
+       CMDP_STAT_DIAMETER_KERNEL = 22        /* the kernel of the last cmdp_diameter / cmdp_diameter_range that launched one (0: none
+                                                yet), the kernel that produced its results where it returned CMDP_OK.  A call
+                                                that fails after its launch (CMDP_ERR_MAX_ITER) sets it too; an empty range
+                                                launches nothing and leaves it.  Encoded as family * 1000 + n * 10 + flag:
+                                                  1 K2, k_dp_block, one workgroup per target (n = 0; flag 1: CSR in LDS, 0: in HBM)
+                                                  2 K3, k_dp_wave_gs, Gauss-Seidel (n = 0, flag = 0)
+                                                  3 K5S with fixed-width rows, k_diam_lanes_ell (n = wavefronts per group: 4, 8, 16)
+                                                  4 K5S with the generic CSR walker, k_diam_lanes (n = 8)
+                                                  5 K5C, k_diam_cluster (n = workgroups per cluster: 8, 16, 32; flag 1: the launch
+                                                    that succeeded used XCD-scope barriers, 0: agent-scope barriers)
+                                                  6 K5T, k_diam_tiles (n = 6 wavefronts per group)
+                                                -- e.g. 3160 = K5S-ELL with 16 wavefronts, 5081 = K5C with clusters of 8 at XCD
+                                                scope.  A K5C launch that gave up reports the K5S kernel that solved the targets
+                                                instead.  When the workspace limit splits a call into several launches of
+                                                different widths, the last launch is reported.  Set on the host; read-only.        */ };
 /* The UCRL2 and PSRL statistics belong to the environment handle: agents created on the same handle share them. */
 int cmdp_stat(cmdp_t* h, int which, double* out);
 /* Latency floor of the LDS-resident rollout kernels, measured on the current device: one wavefront per CU follows
