@@ -1696,11 +1696,6 @@ int resolve_scheme(cmdp_t* h, int scheme, bool pe, bool diam, int* out) {
   return CMDP_OK;
 }
 
-// CMDP_STAT_DIAMETER_KERNEL (include/cmdp.h documents the encoding): family, wavefronts per group or workgroups per
-// cluster, and a flag -- K2: the CSR lives in LDS; K5C: the barriers are XCD-scope
-enum DiamFamily { DIAM_K2 = 1, DIAM_K3 = 2, DIAM_K5S_ELL = 3, DIAM_K5S_CSR = 4, DIAM_K5C = 5, DIAM_K5T = 6 };
-constexpr int diam_code(int family, int n, bool flag) { return family * 1000 + n * 10 + (flag ? 1 : 0); }
-
 DpShape dp_shape(const cmdp_t* h) { return {h->A, h->max_row_nnz, h->max_state_unique, h->max_S, h->max_inst_nnz}; }
 
 // The fields every DP kernel reads: the batch's CSR and its rewards.  The rest is zero; callers set what their kernel needs.
@@ -1709,6 +1704,19 @@ DpTables dp_tables(const cmdp_t* h) {
   t.B = h->B; t.A = h->A; t.state_off = h->d_state_off.p; t.csr_ptr = h->d_csr_ptr.p; t.csr_col = h->d_csr_col.p;
   t.csr_val = h->d_csr_val.p; t.R = h->d_R.p;
   return t;
+}
+
+// Host copy of the batch's CSR for the planners that run on the host (`val` may be null); returns after the copies have landed
+int fetch_csr(cmdp_t* h, std::vector<int64_t>* ptr, std::vector<int32_t>* col, std::vector<float>* val) {
+  hipStream_t st = h->stream;
+  ptr->resize((size_t)h->n_rows + 1);
+  col->resize((size_t)h->n_csr);
+  if (val) val->resize((size_t)h->n_csr);
+  HIP_TRY(hipMemcpyAsync(ptr->data(), h->d_csr_ptr.p, sizeof(int64_t) * ptr->size(), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(col->data(), h->d_csr_col.p, sizeof(int32_t) * col->size(), hipMemcpyDeviceToHost, st));
+  if (val) HIP_TRY(hipMemcpyAsync(val->data(), h->d_csr_val.p, sizeof(float) * val->size(), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return CMDP_OK;
 }
 
 // Device aliases of page-locked result arrays (discounted): the register-resident kernels touch Q, V and the sweep counts
@@ -1780,6 +1788,42 @@ int check_status(cmdp_t* h, int64_t units, const int32_t* pinned = nullptr) {
     if (status[u] == CMDP_ERR_MAX_ITER) return fail(CMDP_ERR_MAX_ITER, "work item %lld did not converge within max_sweeps", (long long)u);
     if (status[u] == CMDP_ERR_MAX_VALUE) return fail(CMDP_ERR_MAX_VALUE, "work item %lld exceeded max_abs_value", (long long)u);
   }
+  return CMDP_OK;
+}
+
+// ---- what the per-target entry points (cmdp_diameter, _range, _sparse_f64, _episodic) share ---------------------------------
+// First of all; each entry point's own argument checks follow it, in the order its callers have always seen them fail
+int diam_check(cmdp_t* h) {
+  if (int rc = bind(h)) return rc;
+  if (!h->has_dp) return fail(CMDP_ERR_INVALID, "handle was created without the DP half");
+  return CMDP_OK;
+}
+
+// ... after the checks: one result and one status word per state of the batch, and the tables of a per-target solve
+// (gamma 1 in the continuous setting; the episodic kernel reads none and has always been handed 0)
+int diam_tables(cmdp_t* h, float gamma, double eps, int64_t max_sweeps, DpTables* out) {
+  const int64_t NS = h->n_states;
+  if (h->d_per_target.n < (size_t)NS) HIP_TRY(h->d_per_target.alloc(NS));
+  if (h->d_status.n < (size_t)NS) HIP_TRY(h->d_status.alloc(NS));
+  DpTables& t = *out = dp_tables(h);
+  t.unit_off = h->d_state_off.p; t.gamma = gamma; t.eps = eps; t.max_sweeps = max_sweeps;
+  t.per_target = h->d_per_target.p; t.status = h->d_status.p;
+  return CMDP_OK;
+}
+
+// ... after the kernels: the status of every target, and per instance the maximum over its targets starting from `start`
+// (the reference's `diameter = 0` of the continuous setting, diameter.py:99-105, and `-np.inf` of the episodic, :203)
+int diam_finish(cmdp_t* h, float start, float* per_target, float* diameter) {
+  const int64_t NS = h->n_states;
+  std::vector<float> per((size_t)NS);
+  HIP_TRY(hipMemcpyAsync(per.data(), h->d_per_target.p, sizeof(float) * NS, hipMemcpyDeviceToHost, h->stream));
+  if (int rc = check_status(h, NS)) return rc;  // synchronises
+  for (int b = 0; b < h->B; ++b) {
+    float dmax = start;
+    for (int64_t s = h->state_off[b]; s < h->state_off[b + 1]; ++s) dmax = std::max(dmax, per[(size_t)s]);
+    diameter[b] = dmax;
+  }
+  if (per_target) std::memcpy(per_target, per.data(), sizeof(float) * NS);
   return CMDP_OK;
 }
 
@@ -1957,13 +2001,10 @@ static int build_ell_relabelled(cmdp_t* h, int K, int cluster) {
   hipStream_t st = h->stream;
   const int A = h->A;
   const int64_t NR = h->n_rows, NS = h->n_states;
-  std::vector<int64_t> ptr((size_t)NR + 1);
-  std::vector<int32_t> col((size_t)h->n_csr);
-  std::vector<float> val((size_t)h->n_csr);
-  HIP_TRY(hipMemcpyAsync(ptr.data(), h->d_csr_ptr.p, sizeof(int64_t) * ptr.size(), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(col.data(), h->d_csr_col.p, sizeof(int32_t) * col.size(), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(val.data(), h->d_csr_val.p, sizeof(float) * val.size(), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
+  std::vector<int64_t> ptr;
+  std::vector<int32_t> col;
+  std::vector<float> val;
+  if (int rc = fetch_csr(h, &ptr, &col, &val)) return rc;
   const size_t rows_p = (size_t)NR + 64 / K + 1;  // tail padding, as k_build_ell
   std::vector<int32_t> ecol(rows_p * K, 0), new_of((size_t)NS);
   std::vector<float> eval_(rows_p * K, 0.0f);
@@ -2000,23 +2041,16 @@ static int build_ell_relabelled(cmdp_t* h, int K, int cluster) {
   return CMDP_OK;
 }
 
-constexpr int kK5tRmax = 48;  // tile rows per cluster: 6 wavefronts x 48 rows x 256 B = 72 KiB of LDS, two workgroups per CU
-constexpr int kK5tNw = 6;
-
 // Host side of K5T: cuts every instance into clusters of <= K5T_C states whose rows (own + distinct outside successors)
 // fit a tile, and writes the per-cluster row lists and the rows' entries re-indexed to tile positions (original column
 // order kept).  Breadth-first region growing over the undirected transition graph keeps the halo small on grid worlds.
 static int build_tiles(cmdp_t* h, int K) {
   hipStream_t st = h->stream;
-  const int A = h->A, AK = A * K;
-  const int64_t NR = h->n_rows;
-  std::vector<int64_t> ptr((size_t)NR + 1);
-  std::vector<int32_t> col((size_t)h->n_csr);
-  std::vector<float> val((size_t)h->n_csr);
-  HIP_TRY(hipMemcpyAsync(ptr.data(), h->d_csr_ptr.p, sizeof(int64_t) * ptr.size(), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(col.data(), h->d_csr_col.p, sizeof(int32_t) * col.size(), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(val.data(), h->d_csr_val.p, sizeof(float) * val.size(), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
+  const int A = h->A;
+  std::vector<int64_t> ptr;
+  std::vector<int32_t> col;
+  std::vector<float> val;
+  if (int rc = fetch_csr(h, &ptr, &col, &val)) return rc;
   std::vector<int32_t> c0v, nclv, cl_n, cl_R, rows, lcol;
   std::vector<float> lval;
   int64_t total_rows = 0, total_states = 0;
@@ -2133,7 +2167,6 @@ static int build_tiles(cmdp_t* h, int K) {
     nclv.push_back(n_clusters);
   }
   for (int i = 0; i < 64; ++i) { lcol.push_back(0); lval.push_back(0.0f); }  // a 64-entry load past the last cluster
-  (void)AK;
   HIP_TRY(h->d_tl_c0.upload(c0v.data(), c0v.size(), st));
   HIP_TRY(h->d_tl_ncl.upload(nclv.data(), nclv.size(), st));
   HIP_TRY(h->d_tl_n.upload(cl_n.data(), cl_n.size(), st));
@@ -2150,13 +2183,56 @@ static int build_tiles(cmdp_t* h, int K) {
   return CMDP_OK;
 }
 
+// Groups of 64 consecutive targets of one instance for the lanes kernels (K5S / K5T / K5C, K5D), and their packing into launches
+struct DiamGroups {
+  std::vector<int32_t> inst, t0, cnt;
+  std::vector<int64_t> elems;  // value-array elements of a group: 2 x S x 64
+  std::vector<int64_t> voff;   // of the launch `next` returned last: every group's offset into the workspace, in elements
+
+  // the targets [lo, hi) of the flat state space
+  DiamGroups(const std::vector<int64_t>& state_off, int64_t lo, int64_t hi) {
+    const int64_t GW = 64;
+    for (size_t b = 0; b + 1 < state_off.size(); ++b) {
+      const int64_t so = state_off[b], S = state_off[b + 1] - so;
+      const int64_t a = std::max(lo, so) - so, z = std::min(hi, so + S) - so;
+      for (int64_t x = a; x < z; x += GW) {
+        inst.push_back((int32_t)b);
+        t0.push_back((int32_t)x);
+        cnt.push_back((int32_t)std::min(GW, z - x));
+        elems.push_back(2 * S * GW);
+      }
+    }
+  }
+
+  // The launch that starts at group g0: groups while their value arrays (`elem_bytes` per element) and `group_bytes` more
+  // per group fit `ws_cap` bytes, and at least one.  Returns its end g1, fills voff and the launch's elements.
+  size_t next(size_t g0, size_t elem_bytes, size_t group_bytes, size_t ws_cap, size_t* launch_elems) {
+    size_t g1 = g0, total = 0;
+    voff.clear();
+    while (g1 < inst.size() && (g1 == g0 || (total + (size_t)elems[g1]) * elem_bytes + (g1 - g0 + 1) * group_bytes <= ws_cap)) {
+      voff.push_back((int64_t)total);
+      total += (size_t)elems[g1];
+      ++g1;
+    }
+    *launch_elems = total;
+    return g1;
+  }
+};
+
+// The CMDP_K5* switches (tuning aids), read nowhere else.  CMDP_K5C and CMDP_K5C_TIMEOUT_TICKS on every call: the tests
+// switch them inside one process (one tick drives the fall-back from K5C to K5S).  The others once per process.
+static DiamSwitches diam_switches() {
+  auto num = [](const char* name, long long unset) { const char* e = std::getenv(name); return e ? std::atoll(e) : unset; };
+  static const bool agent = [] { const char* e = std::getenv("CMDP_K5C_SCOPE"); return e && !std::strcmp(e, "agent"); }();
+  static const int nw = (int)num("CMDP_K5S_NW", 0), cluster = (int)num("CMDP_K5S_CLUSTER", -1);
+  // 2 s of the 100 MHz wall clock unless CMDP_K5C_TIMEOUT_TICKS says otherwise
+  return {(int)num("CMDP_K5C", -1), nw, agent, num("CMDP_K5C_TIMEOUT_TICKS", 200000000LL), cluster};
+}
+
 // fixed-width rows of the K5S family (k_build_ell / build_ell_relabelled), built once per handle and width
-static int ensure_ell(cmdp_t* h, int K) {
-  hipStream_t st = h->stream;
+static int ensure_ell(cmdp_t* h, int K, const DiamSwitches& sw) {
   if (h->ell_K != K) {
-    // CMDP_K5S_CLUSTER: tuning aid -- states per breadth-first cluster of the locality order, 0 = keep the caller's order
-    static const int cluster_env = std::getenv("CMDP_K5S_CLUSTER") ? std::atoi(std::getenv("CMDP_K5S_CLUSTER")) : -1;
-    const int cluster = cluster_env >= 0 ? cluster_env : kK5sCluster;
+    const int cluster = sw.k5s_cluster >= 0 ? sw.k5s_cluster : kK5sCluster;
     if (cluster > 0 && h->max_S >= h->relabel_min_states) {
       if (int rc = build_ell_relabelled(h, K, cluster)) return rc;
       h->ell_relabelled = true;
@@ -2164,7 +2240,7 @@ static int ensure_ell(cmdp_t* h, int K) {
       const size_t rows_p = (size_t)h->n_rows + 64 / K + 1;
       HIP_TRY(h->d_ell_col.alloc(rows_p * K));
       HIP_TRY(h->d_ell_val.alloc(rows_p * K));
-      hipLaunchKernelGGL(k_build_ell, dim3(grid_for((int64_t)rows_p, 256)), dim3(256), 0, st, h->n_rows, K,
+      hipLaunchKernelGGL(k_build_ell, dim3(grid_for((int64_t)rows_p, 256)), dim3(256), 0, h->stream, h->n_rows, K,
                          h->d_csr_ptr.p, h->d_csr_col.p, h->d_csr_val.p, h->d_ell_col.p, h->d_ell_val.p);
       HIP_TRY(hipGetLastError());
       h->ell_relabelled = false;
@@ -2174,42 +2250,50 @@ static int ensure_ell(cmdp_t* h, int K) {
   return CMDP_OK;
 }
 
-// K5S driver: targets [unit_lo, unit_hi) of the flat state space in groups of 64 consecutive targets of one instance;
-// as many groups per launch as the value-array workspace allows.
+// The compiled lanes kernels by template key; all instantiations of a family share a signature.  The pickers of
+// cmdp_dp_plan.h return listed keys only: the closing `return nullptr` of a table is never taken.
+static auto ell_kernel(int nw, int A, int K) -> void (*)(DpTables, DiamLanesArgs, const int32_t*, const float*, const int32_t*) {
+#define ELL_ROW(NW, AT, KT) if (nw == NW && A == AT && K == KT) return k_diam_lanes_ell<NW, AT, KT>;
+  CMDP_FIXED_WIDTH_SHAPES(ELL_ROW, 4) CMDP_FIXED_WIDTH_SHAPES(ELL_ROW, 8) CMDP_FIXED_WIDTH_SHAPES(ELL_ROW, 16)
+#undef ELL_ROW
+  return nullptr;
+}
+
+static auto cluster_kernel(int CL, int A, int K, bool xcd)
+    -> void (*)(DpTables, DiamLanesArgs, DiamClusterArgs, const int32_t*, const float*, const int32_t*) {
+#define K5C_ROW(CLT, AT, KT) \
+  if (CL == CLT && A == AT && K == KT) return xcd ? k_diam_cluster<CLT, AT, KT, true> : k_diam_cluster<CLT, AT, KT, false>;
+#define K5C_SIZE(CLT) CMDP_FIXED_WIDTH_SHAPES(K5C_ROW, CLT)
+  CMDP_K5C_SIZES(K5C_SIZE)
+#undef K5C_SIZE
+#undef K5C_ROW
+  return nullptr;
+}
+
+static auto tiles_kernel(int A, int K) -> void (*)(DpTables, DiamLanesArgs, TileArgs) {
+#define TILE_ROW(P, AT, KT) if (A == AT && K == KT) return k_diam_tiles<kK5tNw, AT, KT, kK5tRmax>;
+  CMDP_FIXED_WIDTH_SHAPES(TILE_ROW, _)
+#undef TILE_ROW
+  return nullptr;
+}
+
+// Lanes driver: the targets [unit_lo, unit_hi) of the flat state space in groups of 64 consecutive targets of one
+// instance.  First the cluster attempt -- K5C, every group in one persistent launch --, then, where that was not tried or
+// gave up, as many groups per launch of the picked lanes kernel as the value-array workspace allows.
 static int diameter_lanes(cmdp_t* h, DpTables t, int64_t unit_lo, int64_t unit_hi) {
   hipStream_t st = h->stream;
-  std::vector<int32_t> inst, t0, cnt;
-  std::vector<int64_t> vfl;  // floats per group
-  // fixed-width-row kernels when a compiled (A, K) shape fits
+  const DpShape shape = dp_shape(h);
   const int A = h->A, K = fixed_width_K(h->max_row_nnz);
-  const bool fixed_ok = fixed_width_compiled(A, K);
-  const bool ell_ok = fixed_ok && h->dp_kernel != DP_KERNEL_K5S_CSR && h->dp_kernel != DP_KERNEL_K5T;
-  // (two targets per lane -- value rows of 128 floats, the row walk paid once per 128 targets -- measured 2.47 s against
-  // 1.79 s at C5: the wider rows halve every group's window in L2; not kept)
-  // K5C: clusters of workgroups per group (k_diam_cluster) for instances large enough for the value rows to overflow the L2s;
-  // CMDP_K5C = 0 switches it off, = CL (8 | 16 | 32) chooses the cluster size (tuning aid)
-  const int k5c_env = std::getenv("CMDP_K5C") ? std::atoi(std::getenv("CMDP_K5C")) : -1;   // read per call: the tests switch it
-  const int CLs = k5c_env > 0 ? k5c_env : 16;
+  const DiamSwitches sw = diam_switches();
   // (a give-up costs every workgroup its 2-second spin: on a GPU that other streams / ranks keep busy the persistent launch is
   // not tried again at once -- the back-off doubles with every consecutive give-up; CMDP_K5C > 0 overrides it)
-  const bool backing_off = h->k5c_skip > 0 && k5c_env <= 0;
+  const bool backing_off = h->k5c_skip > 0 && sw.k5c <= 0;
   if (backing_off) h->k5c_skip--;
-  const bool use_cluster = ell_ok && k5c_env != 0 && h->cus % (8 * CLs) == 0 && h->max_S >= h->relabel_min_states && !backing_off;
-  const int64_t GW = 64;  // targets per group
-  for (int b = 0; b < h->B; ++b) {
-    const int64_t so = h->state_off[b], S = h->state_off[b + 1] - so;
-    const int64_t lo = std::max<int64_t>(unit_lo, so) - so, hi = std::min<int64_t>(unit_hi, so + S) - so;
-    for (int64_t x = lo; x < hi; x += GW) {
-      inst.push_back(b);
-      t0.push_back((int32_t)x);
-      cnt.push_back((int32_t)std::min<int64_t>(GW, hi - x));
-      vfl.push_back(2 * S * GW);
-    }
-  }
-  const size_t G = inst.size();
-  if (use_cluster && G > 0) {
-    if (int rc = ensure_ell(h, K)) return rc;
-    const int n_clusters = h->cus / CLs;
+  DiamGroups gr(h->state_off, unit_lo, unit_hi);
+  const size_t G = gr.inst.size();
+  if (const int CL = pick_diameter_cluster(shape, h->dp_kernel, h->max_S >= h->relabel_min_states, h->cus, sw, backing_off, G > 0)) {
+    if (int rc = ensure_ell(h, K, sw)) return rc;
+    const int n_clusters = h->cus / CL;
     DiamClusterArgs ca{};
     ca.n_groups = (int)G; ca.n_clusters = n_clusters; ca.vstride = 2 * (int64_t)h->max_S * 64;
     const size_t vfloats = (size_t)n_clusters * (size_t)ca.vstride;
@@ -2217,32 +2301,22 @@ static int diameter_lanes(cmdp_t* h, DpTables t, int64_t unit_lo, int64_t unit_h
       if (hipError_t e = h->d_dl_v.alloc(vfloats); e != hipSuccess)
         return fail(CMDP_ERR_HIP, "K5C workspace of %zu bytes: %s", vfloats * sizeof(float), hipGetErrorString(e));
     }
-    HIP_TRY(h->d_k5c_red.alloc((size_t)n_clusters * 2 * CLs * 2 * 64));
-    HIP_TRY(h->d_k5c_bar.alloc((size_t)n_clusters + 1 + (size_t)n_clusters * CLs));
-    HIP_TRY(h->d_dl_inst.upload(inst.data(), G, st));
-    HIP_TRY(h->d_dl_t0.upload(t0.data(), G, st));
-    HIP_TRY(h->d_dl_cnt.upload(cnt.data(), G, st));
+    HIP_TRY(h->d_k5c_red.alloc((size_t)n_clusters * 2 * CL * 2 * 64));
+    HIP_TRY(h->d_k5c_bar.alloc((size_t)n_clusters + 1 + (size_t)n_clusters * CL));
+    HIP_TRY(h->d_dl_inst.upload(gr.inst.data(), G, st));
+    HIP_TRY(h->d_dl_t0.upload(gr.t0.data(), G, st));
+    HIP_TRY(h->d_dl_cnt.upload(gr.cnt.data(), G, st));
     ca.cred = h->d_k5c_red.p; ca.cbar = h->d_k5c_bar.p; ca.err = reinterpret_cast<int*>(h->d_k5c_bar.p + n_clusters);
     ca.xcc = ca.err + 1;
-    // 2 s of the 100 MHz wall clock; CMDP_K5C_TIMEOUT_TICKS overrides (the test-suite sets 1 to drive the fall-back to K5S)
-    ca.timeout_ticks = std::getenv("CMDP_K5C_TIMEOUT_TICKS") ? std::atoll(std::getenv("CMDP_K5C_TIMEOUT_TICKS")) : 200000000LL;
+    ca.timeout_ticks = sw.timeout_ticks;
     DiamLanesArgs g{h->d_dl_inst.p, h->d_dl_t0.p, h->d_dl_cnt.p, nullptr, h->d_dl_v.p};
     const int32_t* new_of = h->ell_relabelled ? h->d_ell_newof.p : nullptr;
-    const unsigned grid = (unsigned)(n_clusters * CLs);
+    const unsigned grid = (unsigned)(n_clusters * CL);
     // first with the XCD-scope barriers (the members verify that they share an XCD); a cluster spread over XCDs makes the
     // launch end with err = 2 and it is repeated with agent-scope barriers; CMDP_K5C_SCOPE = agent skips the first form
-    static const bool agent_env = std::getenv("CMDP_K5C_SCOPE") && !std::strcmp(std::getenv("CMDP_K5C_SCOPE"), "agent");
-    for (int pass = (agent_env || h->k5c_agent_scope) ? 1 : 0; pass < 2; ++pass) {
+    for (int pass = (sw.agent_scope || h->k5c_agent_scope) ? 1 : 0; pass < 2; ++pass) {
       HIP_TRY(h->d_k5c_bar.zero(st));   // counters, error flag, XCC ids
-      bool launched = true;
-#define K5C_CASE(CLT, AT, KT)                                                                                       \
-  if (CLs == CLT && A == AT && K == KT) {                                                                           \
-    if (pass == 0) hipLaunchKernelGGL((k_diam_cluster<CLT, AT, KT, true>), dim3(grid), dim3(1024), 0, st, t, g, ca, h->d_ell_col.p, h->d_ell_val.p, new_of); \
-    else hipLaunchKernelGGL((k_diam_cluster<CLT, AT, KT, false>), dim3(grid), dim3(1024), 0, st, t, g, ca, h->d_ell_col.p, h->d_ell_val.p, new_of); \
-  } else
-      CMDP_FIXED_WIDTH_SHAPES(K5C_CASE, 8) CMDP_FIXED_WIDTH_SHAPES(K5C_CASE, 16) CMDP_FIXED_WIDTH_SHAPES(K5C_CASE, 32) { launched = false; }
-#undef K5C_CASE
-      if (!launched) break;
+      hipLaunchKernelGGL(cluster_kernel(CL, A, K, pass == 0), dim3(grid), dim3(1024), 0, st, t, g, ca, h->d_ell_col.p, h->d_ell_val.p, new_of);
       HIP_TRY(hipGetLastError());
       int err = 0;
       HIP_TRY(hipMemcpyAsync(&err, ca.err, sizeof(int), hipMemcpyDeviceToHost, st));
@@ -2250,7 +2324,7 @@ static int diameter_lanes(cmdp_t* h, DpTables t, int64_t unit_lo, int64_t unit_h
       if (!err) {
         h->k5c_launches++;
         h->k5c_backoff = 0;
-        h->last_diam_kernel = diam_code(DIAM_K5C, CLs, pass == 0);
+        h->last_diam_kernel = diam_code(DIAM_K5C, CL, pass == 0);
         return CMDP_OK;
       }
       if (err == 2 && pass == 0) { h->k5c_agent_scope = true; continue; }   // this device does not deal workgroups as assumed
@@ -2268,124 +2342,60 @@ static int diameter_lanes(cmdp_t* h, DpTables t, int64_t unit_lo, int64_t unit_h
     if (hipMemGetInfo(&free_b, &total_b) == hipSuccess)
       ws_cap = std::min(ws_cap, h->d_dl_v.n * sizeof(float) + free_b / 5 * 4);
   }
-  size_t g0 = 0;
-  while (g0 < G) {
-    size_t g1 = g0, floats = 0;
-    std::vector<int64_t> voff;
-    while (g1 < G && (g1 == g0 || (floats + (size_t)vfl[g1]) * sizeof(float) <= ws_cap)) {
-      voff.push_back((int64_t)floats);
-      floats += (size_t)vfl[g1];
-      ++g1;
-    }
+  const int family = lanes_family(shape, h->dp_kernel);
+  for (size_t g0 = 0, g1 = 0; g0 < G; g0 = g1) {
+    size_t floats = 0;
+    g1 = gr.next(g0, sizeof(float), 0, ws_cap, &floats);
     const size_t n = g1 - g0;
     if (h->d_dl_v.n < floats) {
       if (hipError_t e = h->d_dl_v.alloc(floats); e != hipSuccess)
         return fail(CMDP_ERR_HIP, "K5S workspace of %zu bytes: %s", floats * sizeof(float), hipGetErrorString(e));
     }
-    HIP_TRY(h->d_dl_inst.upload(inst.data() + g0, n, st));
-    HIP_TRY(h->d_dl_t0.upload(t0.data() + g0, n, st));
-    HIP_TRY(h->d_dl_cnt.upload(cnt.data() + g0, n, st));
-    HIP_TRY(h->d_dl_voff.upload(voff.data(), n, st));
+    HIP_TRY(h->d_dl_inst.upload(gr.inst.data() + g0, n, st));
+    HIP_TRY(h->d_dl_t0.upload(gr.t0.data() + g0, n, st));
+    HIP_TRY(h->d_dl_cnt.upload(gr.cnt.data() + g0, n, st));
+    HIP_TRY(h->d_dl_voff.upload(gr.voff.data(), n, st));
     DiamLanesArgs g{h->d_dl_inst.p, h->d_dl_t0.p, h->d_dl_cnt.p, h->d_dl_voff.p, h->d_dl_v.p};
-    bool ell = false;
-    int ell_nw = 0;  // wavefronts per group of the K5S-ELL launch
-    // K5T (value rows gathered into LDS tiles per cluster of states): on request only (option 6).  At C5 it halves the
-    // HBM traffic of K5S and is bit-equal, but runs 2.3 s against 2.05 s -- see DESIGN.md.
-    bool tiles = false;
-    if (fixed_ok && h->dp_kernel == DP_KERNEL_K5T) {
-      if (h->tile_K != K) {
-        const int rc = build_tiles(h, K);
-        if (rc != CMDP_OK && (rc != CMDP_ERR_UNSUPPORTED || h->dp_kernel == DP_KERNEL_K5T)) return rc;
-      }
-      // worth it only while the halo stays small (two rows gathered per state would equal K5S's traffic at best)
-      tiles = h->tile_K == K && (h->dp_kernel == DP_KERNEL_K5T || h->tile_rows_per_state <= 2.0);
-    }
-    if (tiles) {
+    // the tables of the family, built once per handle and width (build_tiles refuses a state whose own successors exceed a tile)
+    if (family == DIAM_K5T && h->tile_K != K)
+      if (int rc = build_tiles(h, K)) return rc;
+    if (family == DIAM_K5S_ELL)
+      if (int rc = ensure_ell(h, K, sw)) return rc;
+    const LanesChoice c = pick_diameter_lanes(shape, h->dp_kernel, h->ell_relabelled, (int64_t)n, h->cus, sw);
+    const dim3 grid((unsigned)n), block(c.nw * 64);
+    if (c.family == DIAM_K5T) {
       TileArgs ta{h->d_tl_c0.p, h->d_tl_ncl.p, h->d_tl_n.p, h->d_tl_R.p, h->d_tl_rows.p, h->d_tl_lcol.p, h->d_tl_val.p};
       const size_t lds = sizeof(float) * 64 * (size_t)kK5tRmax * kK5tNw;
-      bool launched = true;
-#define TILE_CASE(P, AT, KT)                                                                                     \
-  if (A == AT && K == KT) {                                                                                     \
-    if (int rc = set_lds(k_diam_tiles<kK5tNw, AT, KT, kK5tRmax>, lds)) return rc;                               \
-    hipLaunchKernelGGL((k_diam_tiles<kK5tNw, AT, KT, kK5tRmax>), dim3((unsigned)n), dim3(kK5tNw * 64), lds, st, t, g, ta); \
-  } else
-      CMDP_FIXED_WIDTH_SHAPES(TILE_CASE, _) { launched = false; }
-#undef TILE_CASE
-      if (!launched) tiles = false;
-    }
-    if (tiles) {
-      ell = true;  // handled
-    } else if (fixed_ok && h->dp_kernel != DP_KERNEL_K5S_CSR) {   // option value 4 keeps the generic CSR walker
-      if (int rc = ensure_ell(h, K)) return rc;
+      const auto kernel = tiles_kernel(A, K);
+      if (int rc = set_lds(kernel, lds)) return rc;
+      hipLaunchKernelGGL(kernel, grid, block, lds, st, t, g, ta);
+    } else if (c.family == DIAM_K5S_ELL) {
       const int32_t* new_of = h->ell_relabelled ? h->d_ell_newof.p : nullptr;
-      ell = true;
-      // wavefronts per group: 8 fill the chip when there are at least two groups per CU; with fewer groups than CUs (a
-      // rank's share of C5 on an 8-GPU node: 98 groups) the launch lasts as long as ONE group, so each group gets 16
-      static const int k5s_env = std::getenv("CMDP_K5S_NW") ? std::atoi(std::getenv("CMDP_K5S_NW")) : 0;  // tuning aid
-      // (and 16 with the locality order: half as many groups share an L2, so a row is still there when the next chunk
-      // wants it -- C5 1.83 -> 1.75 s)
-      const int k5s_nw = k5s_env ? k5s_env : (((int64_t)n <= (int64_t)h->cus || h->ell_relabelled) ? 16 : 8);
-      ell_nw = k5s_nw == 16 || k5s_nw == 4 ? k5s_nw : 8;
-#define ELL_CASE(P, AT, KT)                                                                                        \
-  if (A == AT && K == KT) {                                                                                       \
-    if (k5s_nw == 16)                                                                                             \
-      hipLaunchKernelGGL((k_diam_lanes_ell<16, AT, KT>), dim3((unsigned)n), dim3(1024), 0, st, t, g, \
-                         h->d_ell_col.p, h->d_ell_val.p, new_of);                                                 \
-    else if (k5s_nw == 4)                                                                                         \
-      hipLaunchKernelGGL((k_diam_lanes_ell<4, AT, KT>), dim3((unsigned)n), dim3(256), 0, st, t, g, \
-                         h->d_ell_col.p, h->d_ell_val.p, new_of);                                                 \
-    else                                                                                                          \
-      hipLaunchKernelGGL((k_diam_lanes_ell<8, AT, KT>), dim3((unsigned)n), dim3(512), 0, st, t, g, \
-                         h->d_ell_col.p, h->d_ell_val.p, new_of);                                                 \
-  } else
-      CMDP_FIXED_WIDTH_SHAPES(ELL_CASE, _) { ell = false; }
-#undef ELL_CASE
-    }
-    if (!ell) hipLaunchKernelGGL(k_diam_lanes<8>, dim3((unsigned)n), dim3(512), 0, st, t, g);
+      hipLaunchKernelGGL(ell_kernel(c.nw, A, K), grid, block, 0, st, t, g, h->d_ell_col.p, h->d_ell_val.p, new_of);
+    } else hipLaunchKernelGGL(k_diam_lanes<8>, grid, block, 0, st, t, g);
     HIP_TRY(hipGetLastError());
-    h->last_diam_kernel = tiles ? diam_code(DIAM_K5T, kK5tNw, false) : ell ? diam_code(DIAM_K5S_ELL, ell_nw, false)
-                                                                           : diam_code(DIAM_K5S_CSR, 8, false);
-    HIP_TRY(hipStreamSynchronize(st));  // the upload staging vectors die at the end of this iteration
-    g0 = g1;
+    h->last_diam_kernel = c.code;
+    HIP_TRY(hipStreamSynchronize(st));  // the next launch overwrites gr.voff, which the upload may still be staging
   }
   return CMDP_OK;
 }
 
 int cmdp_diameter(cmdp_t* h, double epsilon, int scheme, int64_t max_sweeps, float* per_target, float* diameter) {
-  if (int rc = bind(h)) return rc;
-  if (!h->has_dp) return fail(CMDP_ERR_INVALID, "handle was created without the DP half");
+  if (int rc = diam_check(h)) return rc;
   if (!diameter) return fail(CMDP_ERR_INVALID, "null output");
   if (max_sweeps < 1) return fail(CMDP_ERR_INVALID, "max_sweeps < 1");
   int sch = 0;
   if (int rc = resolve_scheme(h, scheme, false, true, &sch)) return rc;
-  hipStream_t st = h->stream;
-  const int64_t NS = h->n_states;
-  if (h->d_per_target.n < (size_t)NS) HIP_TRY(h->d_per_target.alloc(NS));
-  if (h->d_status.n < (size_t)NS) HIP_TRY(h->d_status.alloc(NS));
-  DpTables t = dp_tables(h);
-  t.unit_off = h->d_state_off.p; t.gamma = 1.0f; t.eps = epsilon; t.max_sweeps = max_sweeps;
-  t.per_target = h->d_per_target.p; t.status = h->d_status.p;
-  // K5S on request, and when the value vectors of an instance do not fit the workgroup kernel's LDS
-  const bool lanes = sch == CMDP_SCHEME_JACOBI && (h->dp_kernel == DP_KERNEL_K5S || h->dp_kernel == DP_KERNEL_K5S_CSR ||
-                                                   h->dp_kernel == DP_KERNEL_K5T || k2_value_lds(h->max_S) > (size_t)kLdsBudget);
-  if (lanes) {
-    if (int rc = diameter_lanes(h, t, 0, NS)) return rc;
-  } else if (int rc = run_sweeps(h, DP_VI, true, sch, t, NS)) return rc;
-  std::vector<float> per((size_t)NS);
-  HIP_TRY(hipMemcpyAsync(per.data(), h->d_per_target.p, sizeof(float) * NS, hipMemcpyDeviceToHost, st));
-  if (int rc = check_status(h, NS)) return rc;
-  for (int b = 0; b < h->B; ++b) {
-    float dmax = 0.0f;  // `diameter = 0` then max(...), diameter.py:99-105
-    for (int64_t s = h->state_off[b]; s < h->state_off[b + 1]; ++s) dmax = std::max(dmax, per[(size_t)s]);
-    diameter[b] = dmax;
-  }
-  if (per_target) std::memcpy(per_target, per.data(), sizeof(float) * NS);
-  return CMDP_OK;
+  DpTables t{};
+  if (int rc = diam_tables(h, 1.0f, epsilon, max_sweeps, &t)) return rc;
+  if (pick_diameter_path(dp_shape(h), sch, h->dp_kernel) == DIAM_PATH_LANES) {
+    if (int rc = diameter_lanes(h, t, 0, h->n_states)) return rc;
+  } else if (int rc = run_sweeps(h, DP_VI, true, sch, t, h->n_states)) return rc;
+  return diam_finish(h, 0.0f, per_target, diameter);
 }
 
 int cmdp_diameter_sparse_f64(cmdp_t* h, double epsilon, int64_t max_sweeps, double* running_max, double* diameter) {
-  if (int rc = bind(h)) return rc;
-  if (!h->has_dp) return fail(CMDP_ERR_INVALID, "handle was created without the DP half");
+  if (int rc = diam_check(h)) return rc;
   if (!diameter) return fail(CMDP_ERR_INVALID, "null output");
   if (max_sweeps < 1) return fail(CMDP_ERR_INVALID, "max_sweeps < 1");
   if (h->H != 0) return fail(CMDP_ERR_INVALID, "the sparse float64 diameter is the continuous setting's (horizon 0)");
@@ -2395,18 +2405,8 @@ int cmdp_diameter_sparse_f64(cmdp_t* h, double epsilon, int64_t max_sweeps, doub
   DpTables t = dp_tables(h);
   t.eps = epsilon; t.max_sweeps = max_sweeps; t.status = h->d_status.p;
   constexpr int kLogCap = 2048;  // sweeps between diff < 0.05 and diff < eps that can be logged per target
-  std::vector<int32_t> inst, t0, cnt;
-  std::vector<int64_t> vdoubles;
-  for (int b = 0; b < h->B; ++b) {
-    const int64_t S = h->state_off[b + 1] - h->state_off[b];
-    for (int64_t x = 0; x < S; x += 64) {
-      inst.push_back(b);
-      t0.push_back((int32_t)x);
-      cnt.push_back((int32_t)std::min<int64_t>(64, S - x));
-      vdoubles.push_back(2 * S * 64);
-    }
-  }
-  const size_t G = inst.size();
+  DiamGroups gr(h->state_off, 0, NS);
+  const size_t G = gr.inst.size();
   size_t ws_cap = h->dl_ws_bytes;
   {
     size_t free_b = 0, total_b = 0;
@@ -2419,23 +2419,17 @@ int cmdp_diameter_sparse_f64(cmdp_t* h, double epsilon, int64_t max_sweeps, doub
   DevBuf<double> d_v, d_log;
   DevBuf<int32_t> d_logn, d_inst, d_t0, d_cnt;
   DevBuf<int64_t> d_voff;
-  size_t g0 = 0;
-  while (g0 < G) {
-    size_t g1 = g0, doubles = 0;
-    std::vector<int64_t> voff;
-    while (g1 < G && (g1 == g0 || (doubles + (size_t)vdoubles[g1]) * sizeof(double) + (g1 - g0 + 1) * 64 * kLogCap * 16 <= ws_cap)) {
-      voff.push_back((int64_t)doubles);
-      doubles += (size_t)vdoubles[g1];
-      ++g1;
-    }
+  for (size_t g0 = 0, g1 = 0; g0 < G; g0 = g1) {
+    size_t doubles = 0;
+    g1 = gr.next(g0, sizeof(double), (size_t)64 * kLogCap * 16, ws_cap, &doubles);   // a group's value arrays and its log
     const size_t n = g1 - g0;
     if (d_v.n < doubles) HIP_TRY(d_v.alloc(doubles));
     if (d_log.n < n * 64 * kLogCap * 2) HIP_TRY(d_log.alloc(n * 64 * kLogCap * 2));
     if (d_logn.n < n * 64) HIP_TRY(d_logn.alloc(n * 64));
-    HIP_TRY(d_inst.upload(inst.data() + g0, n, st));
-    HIP_TRY(d_t0.upload(t0.data() + g0, n, st));
-    HIP_TRY(d_cnt.upload(cnt.data() + g0, n, st));
-    HIP_TRY(d_voff.upload(voff.data(), n, st));
+    HIP_TRY(d_inst.upload(gr.inst.data() + g0, n, st));
+    HIP_TRY(d_t0.upload(gr.t0.data() + g0, n, st));
+    HIP_TRY(d_cnt.upload(gr.cnt.data() + g0, n, st));
+    HIP_TRY(d_voff.upload(gr.voff.data(), n, st));
     DiamF64Args g{d_inst.p, d_t0.p, d_cnt.p, d_voff.p, d_v.p, d_log.p, d_logn.p, kLogCap};
     hipLaunchKernelGGL(k_diam_lanes_f64<8>, dim3((unsigned)n), dim3(512), 0, st, t, g);
     HIP_TRY(hipGetLastError());
@@ -2446,13 +2440,13 @@ int cmdp_diameter_sparse_f64(cmdp_t* h, double epsilon, int64_t max_sweeps, doub
     HIP_TRY(hipStreamSynchronize(st));
     // the reference's loop over the targets, in its order: the first logged sweep at which it would have stopped
     for (size_t gi = 0; gi < n; ++gi) {
-      const int b = inst[g0 + gi];
-      for (int l = 0; l < cnt[g0 + gi]; ++l) {
+      const int b = gr.inst[g0 + gi];
+      for (int l = 0; l < gr.cnt[g0 + gi]; ++l) {
         const int32_t nl = logn_host[gi * 64 + l];
-        if (nl < 0) return fail(CMDP_ERR_MAX_ITER, "target %d of instance %d did not converge within max_sweeps", t0[g0 + gi] + l, b);
+        if (nl < 0) return fail(CMDP_ERR_MAX_ITER, "target %d of instance %d did not converge within max_sweeps", gr.t0[g0 + gi] + l, b);
         if (nl > kLogCap)
           return fail(CMDP_ERR_UNSUPPORTED, "target %d of instance %d needs more than %d sweeps between diff < 0.05 and diff < eps",
-                      t0[g0 + gi] + l, b, kLogCap);
+                      gr.t0[g0 + gi] + l, b, kLogCap);
         const double* lg = log_host.data() + (gi * 64 + l) * (size_t)kLogCap * 2;
         double mx = lg[2 * (nl - 1) + 1];
         for (int32_t j = 0; j < nl; ++j) {
@@ -2460,10 +2454,9 @@ int cmdp_diameter_sparse_f64(cmdp_t* h, double epsilon, int64_t max_sweeps, doub
           if (diff < epsilon || (diff < 0.05 && m - 1 < D[(size_t)b])) { mx = m; break; }
         }
         D[(size_t)b] = std::max(D[(size_t)b], mx);
-        run[(size_t)(h->state_off[b] + t0[g0 + gi] + l)] = D[(size_t)b];
+        run[(size_t)(h->state_off[b] + gr.t0[g0 + gi] + l)] = D[(size_t)b];
       }
     }
-    g0 = g1;
   }
   for (int b = 0; b < h->B; ++b) diameter[b] = D[(size_t)b];
   if (running_max) std::memcpy(running_max, run.data(), sizeof(double) * (size_t)NS);
@@ -2472,20 +2465,16 @@ int cmdp_diameter_sparse_f64(cmdp_t* h, double epsilon, int64_t max_sweeps, doub
 
 int cmdp_diameter_range(cmdp_t* h, double epsilon, int64_t max_sweeps, int64_t target_lo, int64_t target_hi,
                         float* per_target) {
-  if (int rc = bind(h)) return rc;
-  if (!h->has_dp) return fail(CMDP_ERR_INVALID, "handle was created without the DP half");
+  if (int rc = diam_check(h)) return rc;
   if (!per_target) return fail(CMDP_ERR_INVALID, "null output");
   if (max_sweeps < 1) return fail(CMDP_ERR_INVALID, "max_sweeps < 1");
   const int64_t NS = h->n_states;
   if (target_lo < 0 || target_hi > NS || target_lo > target_hi) return fail(CMDP_ERR_INVALID, "target range outside [0, %lld]", (long long)NS);
   if (target_lo == target_hi) return CMDP_OK;
   hipStream_t st = h->stream;
-  if (h->d_per_target.n < (size_t)NS) HIP_TRY(h->d_per_target.alloc(NS));
-  if (h->d_status.n < (size_t)NS) HIP_TRY(h->d_status.alloc(NS));
+  DpTables t{};
+  if (int rc = diam_tables(h, 1.0f, epsilon, max_sweeps, &t)) return rc;
   HIP_TRY(hipMemsetAsync(h->d_status.p, 0, sizeof(int32_t) * NS, st));
-  DpTables t = dp_tables(h);
-  t.unit_off = h->d_state_off.p; t.gamma = 1.0f; t.eps = epsilon; t.max_sweeps = max_sweeps;
-  t.per_target = h->d_per_target.p; t.status = h->d_status.p;
   if (int rc = diameter_lanes(h, t, target_lo, target_hi)) return rc;
   HIP_TRY(hipMemcpyAsync(per_target, h->d_per_target.p + target_lo, sizeof(float) * (target_hi - target_lo),
                          hipMemcpyDeviceToHost, st));
@@ -2495,8 +2484,7 @@ int cmdp_diameter_range(cmdp_t* h, double epsilon, int64_t max_sweeps, int64_t t
 int cmdp_diameter_episodic(cmdp_t* h, int H, const int64_t* start_off, const int32_t* start_state,
                            const float* start_prob, double epsilon, int64_t max_sweeps, float* per_target,
                            float* diameter) {
-  if (int rc = bind(h)) return rc;
-  if (!h->has_dp) return fail(CMDP_ERR_INVALID, "handle was created without the DP half");
+  if (int rc = diam_check(h)) return rc;
   if (!diameter || !start_off || !start_state || !start_prob) return fail(CMDP_ERR_INVALID, "null argument");
   if (H < 2 || max_sweeps < 1) return fail(CMDP_ERR_INVALID, "H < 2 or max_sweeps < 1");
   const int B = h->B, A = h->A;
@@ -2507,12 +2495,10 @@ int cmdp_diameter_episodic(cmdp_t* h, int H, const int64_t* start_off, const int
   if (start_off[0] != 0) return fail(CMDP_ERR_INVALID, "start_off[0] != 0");
   // rows of T_epi that are filled (mdp_creation.py:118-125): layer 0 = starting states, layer h = states with
   // incoming mass in layer h-1, for h <= H-2; layer H-1 is the return to the starting states
-  std::vector<int64_t> ptr((size_t)h->n_rows + 1);
-  std::vector<int32_t> col((size_t)h->n_csr);
+  std::vector<int64_t> ptr;
+  std::vector<int32_t> col;
   hipStream_t st = h->stream;
-  HIP_TRY(hipMemcpyAsync(ptr.data(), h->d_csr_ptr.p, sizeof(int64_t) * ptr.size(), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(col.data(), h->d_csr_col.p, sizeof(int32_t) * col.size(), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
+  if (int rc = fetch_csr(h, &ptr, &col, nullptr)) return rc;
   std::vector<uint8_t> reach((size_t)H * NS, 0);
   for (int b = 0; b < B; ++b) {
     const int64_t so = h->state_off[b], S = h->state_off[b + 1] - so;
@@ -2538,25 +2524,13 @@ int cmdp_diameter_episodic(cmdp_t* h, int H, const int64_t* start_off, const int
   HIP_TRY(d_soff.upload(start_off, B + 1, st));
   HIP_TRY(d_sstate.upload(start_state, start_off[B], st));
   HIP_TRY(d_sprob.upload(start_prob, start_off[B], st));
-  if (h->d_per_target.n < (size_t)NS) HIP_TRY(h->d_per_target.alloc(NS));
-  if (h->d_status.n < (size_t)NS) HIP_TRY(h->d_status.alloc(NS));
-  DpTables t = dp_tables(h);
-  t.unit_off = h->d_state_off.p; t.eps = epsilon; t.max_sweeps = max_sweeps;
-  t.per_target = h->d_per_target.p; t.status = h->d_status.p;
+  DpTables t{};
+  if (int rc = diam_tables(h, 0.0f, epsilon, max_sweeps, &t)) return rc;
   EpiDiamArgs e{H, d_soff.p, d_sstate.p, d_sprob.p, d_reach.p};
   if (int rc = set_lds(k_diam_episodic, lds)) return rc;
   hipLaunchKernelGGL(k_diam_episodic, dim3((unsigned)NS), dim3(256), lds, st, t, e);
   HIP_TRY(hipGetLastError());
-  std::vector<float> per((size_t)NS);
-  HIP_TRY(hipMemcpyAsync(per.data(), h->d_per_target.p, sizeof(float) * NS, hipMemcpyDeviceToHost, st));
-  if (int rc = check_status(h, NS)) return rc;  // synchronises; the upload buffers above die after this
-  for (int b = 0; b < B; ++b) {
-    float dmax = -INFINITY;  // `diameter = -np.inf`, diameter.py:203
-    for (int64_t s = h->state_off[b]; s < h->state_off[b + 1]; ++s) dmax = std::max(dmax, per[(size_t)s]);
-    diameter[b] = dmax;
-  }
-  if (per_target) std::memcpy(per_target, per.data(), sizeof(float) * NS);
-  return CMDP_OK;
+  return diam_finish(h, -INFINITY, per_target, diameter);  // synchronises before the upload buffers above die
 }
 
 // ---- device agents -----------------------------------------------------------------------------------------
@@ -2946,13 +2920,10 @@ static int build_chain_plan(cmdp_t* h) {
   h->chain_plan_built = true;
   const int B = h->B, A = h->A;
   hipStream_t st = h->stream;
-  std::vector<int64_t> ptr((size_t)h->n_rows + 1);
-  std::vector<int32_t> col((size_t)h->n_csr);
-  std::vector<float> val((size_t)h->n_csr);
-  HIP_TRY(hipMemcpyAsync(ptr.data(), h->d_csr_ptr.p, sizeof(int64_t) * ptr.size(), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(col.data(), h->d_csr_col.p, sizeof(int32_t) * col.size(), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(val.data(), h->d_csr_val.p, sizeof(float) * val.size(), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
+  std::vector<int64_t> ptr;
+  std::vector<int32_t> col;
+  std::vector<float> val;
+  if (int rc = fetch_csr(h, &ptr, &col, &val)) return rc;
   constexpr int W = 16, NARROW = K9F_MAXC;
   std::vector<int32_t> rank((size_t)h->n_states, -1), cptr((size_t)h->n_states + B, 0), nrounds((size_t)B, -1), rptr, piv((size_t)h->n_states, 0);
   std::vector<int64_t> cbase((size_t)B, 0), rbase((size_t)B, 0);
@@ -3401,14 +3372,11 @@ int cmdp_mixing_time(cmdp_t* h, const float* pi, const double* stationary, doubl
   const bool dense_path = h->mixing_path == 1 || (h->mixing_path == 0 && (!fits_lds || h->max_S > 1024));
   hipStream_t st = h->stream;
   const int B = h->B, A = h->A;
-  const int64_t NS = h->n_states, NR = h->n_rows;
-  std::vector<int64_t> ptr((size_t)NR + 1);
-  std::vector<int32_t> col((size_t)h->n_csr);
-  std::vector<float> val((size_t)h->n_csr);
-  HIP_TRY(hipMemcpyAsync(ptr.data(), h->d_csr_ptr.p, sizeof(int64_t) * ptr.size(), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(col.data(), h->d_csr_col.p, sizeof(int32_t) * col.size(), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(val.data(), h->d_csr_val.p, sizeof(float) * val.size(), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
+  const int64_t NS = h->n_states;
+  std::vector<int64_t> ptr;
+  std::vector<int32_t> col;
+  std::vector<float> val;
+  if (int rc = fetch_csr(h, &ptr, &col, &val)) return rc;
   // P[s, j] = sum_a pi[s, a] * T[s, a, j] (float64, actions in order), then its CSC with predecessors in index order
   std::vector<int64_t> cptr((size_t)NS + 1, 0), xoff((size_t)B + 1, 0);
   std::vector<int32_t> crow;

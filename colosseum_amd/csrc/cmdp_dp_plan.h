@@ -2,7 +2,11 @@
 //
 // The compiled instantiations of every template family are listed here once, as X-macro lists: the launch switches of
 // cmdp.hip and the predicates "is this shape compiled" below expand the same lists.  pick_sweep decides which kernel
-// serves a batch of a given shape.  Nothing here makes a HIP call.  Included by cmdp.hip after the kernel headers.
+// serves a batch of a given shape.  pick_diameter_path / _cluster / _lanes decide the same for a continuous diameter: the
+// workgroup kernels (then pick_sweep's) or the lanes kernels, whether a call tries K5C first and with which cluster size,
+// and which of K5T / K5S-ELL / K5S-CSR, how wide, takes a launch.  The pickers are pure: the handle's back-off state and
+// the counters stay with diameter_lanes of cmdp.hip.  Nothing here makes a HIP call or reads the environment.  Included by
+// cmdp.hip after the kernel headers.
 #pragma once
 
 namespace { int fail(int code, const char* fmt, ...); }  // cmdp.hip: sets the text of cmdp_last_error, returns `code`
@@ -137,4 +141,71 @@ inline int pick_sweep(const DpShape& s, int mode, bool diam, int scheme, int for
       return fail(CMDP_ERR_UNSUPPORTED, "instance with %d states does not fit the LDS-resident sweep", s.max_S);
   }
   return CMDP_OK;
+}
+
+// ---- the kernels of one continuous diameter: pick_diameter_path / _cluster / _lanes ---------------------------------------------------------------
+// CMDP_STAT_DIAMETER_KERNEL (include/cmdp.h documents the encoding): family, wavefronts per group or workgroups per
+// cluster, and a flag -- K2: the CSR lives in LDS; K5C: the barriers are XCD-scope
+enum DiamFamily { DIAM_K2 = 1, DIAM_K3 = 2, DIAM_K5S_ELL = 3, DIAM_K5S_CSR = 4, DIAM_K5C = 5, DIAM_K5T = 6 };
+constexpr int diam_code(int family, int n, bool flag) { return family * 1000 + n * 10 + (flag ? 1 : 0); }
+
+constexpr int kK5tRmax = 48;  // tile rows per cluster: 6 wavefronts x 48 rows x 256 B = 72 KiB of LDS, two workgroups per CU
+constexpr int kK5tNw = 6;
+constexpr int kK5cCluster = 16;  // workgroups per K5C cluster unless CMDP_K5C names another compiled size
+#define CMDP_K5C_SIZES(X) X(8) X(16) X(32)
+#define CMDP_K5C_IS(CLT) || CL == CLT
+inline bool k5c_compiled(int CL, int A, int K) { return (false CMDP_K5C_SIZES(CMDP_K5C_IS)) && fixed_width_compiled(A, K); }
+
+// The CMDP_K5* environment switches (tuning aids), as diam_switches of cmdp.hip read them
+struct DiamSwitches {
+  int k5c;                  // CMDP_K5C: -1 unset, 0 switches K5C off, CL > 0 chooses the cluster size and overrides the back-off
+  int k5s_nw;               // CMDP_K5S_NW: wavefronts per group of K5S-ELL (0: by rule)
+  bool agent_scope;         // CMDP_K5C_SCOPE=agent: skip the launch with XCD-scope barriers
+  long long timeout_ticks;  // CMDP_K5C_TIMEOUT_TICKS: the barriers' time limit, 100 MHz wall clock (the driver's, no picker reads it)
+  int k5s_cluster;          // CMDP_K5S_CLUSTER: states per cluster of the locality order, 0 keeps the caller's order, -1 unset (ensure_ell's)
+};
+
+// Path of a cmdp_diameter call: the lanes kernels (64 targets per workgroup, value vectors in HBM) on request, and when
+// the value vectors of an instance do not fit the workgroup kernel's LDS; otherwise one workgroup or wavefront per target,
+// which pick_sweep(..., diam = true, ...) chooses.  cmdp_diameter_range always takes the lanes.
+enum DiamPath { DIAM_PATH_WORKGROUP, DIAM_PATH_LANES };
+inline DiamPath pick_diameter_path(const DpShape& s, int scheme, int forced) {
+  const bool lanes = scheme == CMDP_SCHEME_JACOBI && (forced == DP_KERNEL_K5S || forced == DP_KERNEL_K5S_CSR || forced == DP_KERNEL_K5T ||
+                                                      k2_value_lds(s.max_S) > (size_t)kLdsBudget);
+  return lanes ? DIAM_PATH_LANES : DIAM_PATH_WORKGROUP;
+}
+
+// K5C (clusters of workgroups per group, k_diam_cluster) for instances large enough for the value rows to overflow the
+// L2s: the cluster size a lanes call tries first, 0 for none.  `relabel`: the largest instance reaches
+// CMDP_OPT_DIAMETER_RELABEL_MIN_STATES; `backing_off`: an earlier call gave up and the handle still skips (a give-up costs
+// every workgroup its 2-second spin).  Only compiled (CL, A, K) are returned.
+inline int pick_diameter_cluster(const DpShape& s, int forced, bool relabel, int cus, const DiamSwitches& sw, bool backing_off, bool any_group) {
+  const int A = s.A, K = fixed_width_K(s.max_row_nnz), CL = sw.k5c > 0 ? sw.k5c : kK5cCluster;
+  const bool wanted = forced != DP_KERNEL_K5S_CSR && forced != DP_KERNEL_K5T && sw.k5c != 0 && cus % (8 * CL) == 0 && relabel &&
+                      !backing_off && any_group;
+  return wanted && k5c_compiled(CL, A, K) ? CL : 0;
+}
+
+// The lanes kernel that solves the groups K5C did not: K5T (value rows gathered into LDS tiles per cluster of states) on
+// request only -- at C5 it halves the HBM traffic of K5S and is bit-equal, but runs 2.3 s against 2.05 s, see DESIGN.md;
+// K5S over the fixed-width rows when (A, K) is compiled, unless option 4 keeps the generic CSR walker.
+inline int lanes_family(const DpShape& s, int forced) {
+  if (!fixed_width_compiled(s.A, fixed_width_K(s.max_row_nnz)) || forced == DP_KERNEL_K5S_CSR) return DIAM_K5S_CSR;
+  return forced == DP_KERNEL_K5T ? DIAM_K5T : DIAM_K5S_ELL;
+}
+
+struct LanesChoice { int family, nw, code; };  // DIAM_K5T / DIAM_K5S_ELL / DIAM_K5S_CSR, wavefronts per group, diam_code(...)
+
+// ... and its width for a launch of `n_groups` groups.  K5S-ELL: 8 wavefronts fill the chip when there are at least two
+// groups per CU; with fewer groups than CUs (a rank's share of C5 on an 8-GPU node: 98 groups) the launch lasts as long as
+// ONE group, so each group gets 16 -- and 16 with the locality order (`ell_relabelled`: the handle's fixed-width rows are
+// stored relabelled, which CMDP_K5S_CLUSTER = 0 prevents): half as many groups share an L2, so a row is still there when
+// the next chunk wants it (C5 1.83 -> 1.75 s).
+// (two targets per lane -- value rows of 128 floats, the row walk paid once per 128 targets -- measured 2.47 s against
+// 1.79 s at C5: the wider rows halve every group's window in L2; not kept)
+inline LanesChoice pick_diameter_lanes(const DpShape& s, int forced, bool ell_relabelled, int64_t n_groups, int cus, const DiamSwitches& sw) {
+  const int family = lanes_family(s, forced);
+  const int ell_nw = sw.k5s_nw ? sw.k5s_nw : ((n_groups <= (int64_t)cus || ell_relabelled) ? 16 : 8);
+  const int nw = family == DIAM_K5T ? kK5tNw : (family == DIAM_K5S_ELL && (ell_nw == 16 || ell_nw == 4)) ? ell_nw : 8;
+  return {family, nw, diam_code(family, nw, false)};
 }

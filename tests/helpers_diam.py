@@ -1,6 +1,7 @@
 """Generated communicating MDPs for the continuous-diameter kernels (K2 / K3 in DIAM mode, K5S, K5T, K5C, K5D), float64
 references of the per-target solves, the tolerance a float32 solve has to meet against them, and a host mirror of which
-diameter kernel `cmdp_diameter` / `diameter_lanes` (colosseum_amd/csrc/cmdp.hip) launches.  Host only: no GPU is touched."""
+diameter kernel `pick_diameter_path` / `pick_diameter_cluster` / `pick_diameter_lanes` (colosseum_amd/csrc/cmdp_dp_plan.h)
+choose for `cmdp_diameter` / `diameter_lanes` and of the launches `DiamGroups` (cmdp.hip) packs.  Host only: no GPU is touched."""
 import functools
 import re
 
@@ -78,8 +79,9 @@ def all_kernels():
 
 
 def launch_groups(sizes, ws_mb=24576, lo=0, hi=None):
-    """Groups of 64 targets per launch of `diameter_lanes` for the targets [lo, hi) of the flat state space: a launch takes
-    groups while their value arrays (512 bytes per state and group) fit the workspace, and at least one."""
+    """Groups of 64 targets per launch of `diameter_lanes` for the targets [lo, hi) of the flat state space (`DiamGroups` of
+    cmdp.hip with 4 bytes per element and no extra bytes per group): a launch takes groups while their value arrays (512
+    bytes per state and group) fit the workspace, and at least one."""
     off = np.concatenate([[0], np.cumsum(sizes)])
     hi = int(off[-1]) if hi is None else hi
     vb = []
@@ -102,7 +104,10 @@ def select_diam(stats, scheme, forced=OPT_AUTO, relabel=False, n_groups=1, cus=C
     scheme 1 Jacobi / 2 Gauss-Seidel, `forced` the handle's CMDP_OPT_DP_KERNEL, `relabel` whether the largest instance
     reaches CMDP_OPT_DIAMETER_RELABEL_MIN_STATES, `n_groups` the groups of the call's last launch (launch_groups), `env`
     the CMDP_* environment switches.  cmdp_diameter_range always takes the lanes kernels: pass forced >= 3 for it.
-    (H.UNSUPPORTED, reason) when the workgroup kernels cannot hold the instance."""
+    (H.UNSUPPORTED, reason) when the workgroup kernels cannot hold the instance.
+    Mirrors cmdp_dp_plan.h: `lanes` is pick_diameter_path, the K5C line pick_diameter_cluster (of a handle that is not
+    backing off; the flag is the XCD-scope first pass, which diameter_lanes skips under CMDP_K5C_SCOPE=agent), the rest
+    pick_diameter_lanes, where `relabel` stands for the handle's ell_relabelled (equal unless CMDP_K5S_CLUSTER=0)."""
     env = env or {}
     A, nnz, _, S, _ = stats
     lanes = scheme == 1 and (forced in (OPT_K5S, OPT_K5S_CSR, OPT_K5T) or 2 * 4 * S + 4 * 4 * (H.DP_BLOCK // 64) > LDS_BUDGET)

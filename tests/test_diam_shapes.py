@@ -506,6 +506,60 @@ def test_sweep_limit(need_gpu, path, eps):
         dp.close()
 
 
+def _compute_units():
+    """Compute units of the GPUs the kernel driver lists (KFD topology: simd_count / simd_per_cu of every GPU node), as a
+    set; empty where the topology cannot be read."""
+    import glob
+
+    out = set()
+    for path in glob.glob("/sys/class/kfd/kfd/topology/nodes/*/properties"):
+        try:
+            p = dict(line.split()[:2] for line in open(path) if len(line.split()) >= 2)
+        except OSError:
+            continue
+        if int(p.get("simd_count", 0)) > 0:
+            out.add(int(p["simd_count"]) // max(int(p.get("simd_per_cu", 4)), 1))
+    return out
+
+
+@pytest.mark.gpu
+def test_cluster_give_up_backs_off_for_8_then_16_calls(need_gpu):
+    """The back-off of K5C -- pick_diameter_cluster's `backing_off` input, diameter_lanes' skip counter and doubling -- call
+    by call on one handle, with a barrier time limit of one tick (the designed give-up path): call 1 tries K5C and gives
+    up, calls 2-9 do not try, call 10 tries and gives up again, calls 11-26 do not try; with the limit lifted call 27 runs
+    K5C.  8 and 16 are the code's max(8, 2 * back-off).  Every call returns the oracle's per-target values bit for bit."""
+    L = _lib()
+    if _compute_units() != {D.CUS}:
+        pytest.skip(f"K5C's default clusters and this test's counts are the {D.CUS}-CU part's")
+    key = ("shape", 2, 2)
+    want = np.concatenate([p for _, p in D.oracle(key)])
+    dp = _handle(key)
+    old = os.environ.get("CMDP_K5C_TIMEOUT_TICKS")
+    seen, first = [], None
+    try:
+        dp.set_option(L.OPT_DP_KERNEL, D.OPT_K5S)
+        dp.set_option(L.OPT_DIAMETER_RELABEL_MIN_STATES, 1)
+        os.environ["CMDP_K5C_TIMEOUT_TICKS"] = "1"
+        for call in range(1, 28):
+            if call == 27:
+                os.environ.pop("CMDP_K5C_TIMEOUT_TICKS")
+            _, per = dp.diameter(EPS, L.SCHEME_JACOBI)
+            first = per.copy() if first is None else first
+            np.testing.assert_array_equal(per, first, err_msg=f"call {call}")
+            np.testing.assert_array_equal(per, want, err_msg=f"call {call}")
+            seen.append((_stat(dp, L.STAT_DIAMETER_CLUSTER_LAUNCHES), _stat(dp, L.STAT_DIAMETER_CLUSTER_FALLBACKS),
+                         _stat(dp, L.STAT_DIAMETER_KERNEL)))
+    finally:
+        os.environ.pop("CMDP_K5C_TIMEOUT_TICKS", None)
+        if old is not None:
+            os.environ["CMDP_K5C_TIMEOUT_TICKS"] = old
+        dp.close()
+    print("\n(launches, fallbacks, kernel) of calls 1 .. 27:", seen)
+    assert [(l, f) for l, f, _ in seen] == [(0, 1)] * 9 + [(0, 2)] * 17 + [(1, 2)]
+    assert [D.decode(k)[0] for _, _, k in seen[:26]] == [D.K5S_ELL] * 26
+    assert seen[26][2] == D.code(D.K5C, 16, 1)
+
+
 @pytest.mark.gpu
 def test_sparse_float64_diameter_on_a_ragged_generated_batch(need_gpu):
     """K5D over several launches: the float64 diameter and the running maximum after every target, bit for bit."""
