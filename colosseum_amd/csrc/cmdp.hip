@@ -24,6 +24,7 @@ extern char** environ;
 #include <new>
 #include "cmdp_kernels.h"
 #include "cmdp_tracker.h"
+#include "cmdp_logged_loop.h"
 #include "cmdp_k1s.h"
 #include "cmdp_k1t.h"
 #include "cmdp_k1u.h"
@@ -2543,16 +2544,27 @@ int cmdp_diameter_episodic(cmdp_t* h, int H, const int64_t* start_off, const int
 
 namespace {
 
+// ---- what every device agent is (Q-learning, UCRL2, PSRL) ------------------------------------------------------------------
+struct AgentBase {
+  cmdp_t* env = nullptr;     // null once the environment handle has been destroyed (agent_attach)
+  DevBuf<uint32_t> d_mt;     // the actor's MT19937 stream of every instance (seed_actor)
+  DevBuf<int32_t> d_mtpos;
+  DevBuf<double> d_rsum;     // MDPLoop._cumulative_reward per instance
+  DevBuf<int8_t> d_act;      // [n_steps][B] action trace of the last call that asked for one
+  DevBuf<uint8_t> d_mask;    // training mask of the call
+};
+
 // The actor's stream of every instance, numpy RandomState(seeds[b]), on the device; returns once the seeds have been read
-int seed_actor(cmdp_t* env, const int32_t* seeds, DevBuf<uint32_t>& d_mt, DevBuf<int32_t>& d_mtpos) {
+int seed_actor(AgentBase* a, const int32_t* seeds) {
+  cmdp_t* env = a->env;
   const int B = env->B;
-  HIP_TRY(d_mt.alloc((size_t)B * 624));
-  HIP_TRY(d_mtpos.alloc(B));
+  HIP_TRY(a->d_mt.alloc((size_t)B * 624));
+  HIP_TRY(a->d_mtpos.alloc(B));
   std::vector<uint32_t> useeds((size_t)B);
   for (int b = 0; b < B; ++b) useeds[b] = (uint32_t)seeds[b];
   DevBuf<uint32_t> d_seeds;
   HIP_TRY(d_seeds.upload(useeds.data(), B, env->stream));
-  hipLaunchKernelGGL(k_mt_seed_numpy, dim3(grid_for(B, 64)), dim3(64), 0, env->stream, d_mt.p, d_mtpos.p, d_seeds.p, B);
+  hipLaunchKernelGGL(k_mt_seed_numpy, dim3(grid_for(B, 64)), dim3(64), 0, env->stream, a->d_mt.p, a->d_mtpos.p, d_seeds.p, B);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(env->stream));
   return CMDP_OK;
@@ -2564,20 +2576,63 @@ int agent_check_actor(int actor) {
   return CMDP_OK;
 }
 
+// The environment handle clears `env` of the agents attached to it when it is destroyed first (garbage collection picks
+// the order): such an agent frees its own memory and touches nothing of the handle, and every entry point refuses it at
+// bind(a->env) with "null handle"
+template <typename T>
+int agent_attach(std::unique_ptr<T>& a, T** out) {
+  a->env->uc_backrefs.push_back(&a->env);
+  *out = a.release();
+  return CMDP_OK;
+}
+
+template <typename T>
+int agent_destroy(T* a) {
+  if (!a) return CMDP_OK;
+  if (a->env) {   // null once the environment handle has been destroyed (its stream was drained then)
+    (void)hipSetDevice(a->env->device);
+    (void)hipStreamSynchronize(a->env->stream);
+    auto& v = a->env->uc_backrefs;
+    v.erase(std::remove(v.begin(), v.end(), &a->env), v.end());
+  }
+  delete a;
+  return CMDP_OK;
+}
+
+// What a run() call of any agent refuses before anything is stepped
+int agent_run_check(AgentBase* a, int64_t n_steps) {
+  if (!a) return fail(CMDP_ERR_INVALID, "null agent");
+  cmdp_t* h = a->env;
+  if (int rc = bind(h)) return rc;
+  if (n_steps < 0) return fail(CMDP_ERR_INVALID, "n_steps < 0");
+  bool any = false;
+  if (int rc = any_needs_reset(h, &any)) return rc;
+  if (any) return fail(CMDP_ERR_NEEDS_RESET, "the environment needs reset() before the agent can run");
+  return visits_check(h, n_steps);
+}
+
+// ... and what it puts on the device first: room for the action trace of `NB` = n_steps x B actions when the caller wants
+// one, and the training mask (*dmask stays null without one: every instance trains)
+int agent_stage_run(AgentBase* a, size_t NB, bool trace, const uint8_t* train_mask, const uint8_t** dmask) {
+  if (trace && a->d_act.n < NB) HIP_TRY(a->d_act.alloc(NB));
+  *dmask = nullptr;
+  if (train_mask) {
+    HIP_TRY(a->d_mask.upload(train_mask, a->env->B, a->env->stream));
+    *dmask = a->d_mask.p;
+  }
+  return CMDP_OK;
+}
+
 // ---- agents that park their instances for a solve (UCRL2: K11, PSRL: K12) -------------------------------------------------
 // A walk kernel steps every instance until it has taken the call's steps or its (artificial) episode ends; the instances
 // that parked are solved in one round of kernels, released, and walked again.
-struct ParkAgent {
-  cmdp_t* env = nullptr;
+struct ParkAgent : AgentBase {
   int64_t nz = 0;                      // positions of the model's layout
   std::vector<int64_t> steps_total;    // [B] transitions taken since creation: bounds the model's counts
   DevBuf<int64_t> d_row_ptr, d_taken;  // layout: d_row_ptr, d_col, d_slot (build_model_layout)
-  DevBuf<int32_t> d_col, d_slot, d_mtpos, d_park, d_obs;
+  DevBuf<int32_t> d_col, d_slot, d_park, d_obs;
   DevBuf<long long> d_left;
-  DevBuf<uint32_t> d_mt;
-  DevBuf<double> d_rsum, d_rew;
-  DevBuf<int8_t> d_act;
-  DevBuf<uint8_t> d_mask;
+  DevBuf<double> d_rew;
   PinnedBuf<int32_t> pin_park;         // [2 + B]: park count, overflow flag (UCRL2 only), park list
   // a read-back of the agent's own, enqueued after the park list's of every walk (UCRL2: `iteration`)
   void* walk_dst = nullptr;
@@ -2656,7 +2711,7 @@ int park_alloc(ParkAgent* a, const int32_t* seeds) {
   a->steps_total.assign((size_t)B, 0);
   AGENT_ZERO(d_left, B); AGENT_ZERO(d_taken, B); AGENT_ZERO(d_park, B + 2); AGENT_ZERO(d_rsum, B);
   if (int rc = a->pin_park.alloc((size_t)B + 2)) return rc;
-  return seed_actor(a->env, seeds, a->d_mt, a->d_mtpos);
+  return seed_actor(a, seeds);
 }
 
 // Parks every instance: the list of a round that solves the whole batch (before_start_interacting, episode_end_update)
@@ -2668,39 +2723,10 @@ int park_all(ParkAgent* a) {
   return CMDP_OK;
 }
 
-// The environment handle clears `env` of the agents attached to it when it is destroyed first (garbage collection picks
-// the order): such an agent frees its own memory and touches nothing of the handle
-template <typename T>
-int park_attach(std::unique_ptr<T>& a, T** out) {
-  a->env->uc_backrefs.push_back(&a->env);
-  *out = a.release();
-  return CMDP_OK;
-}
-
-template <typename T>
-int park_destroy(T* a) {
-  if (!a) return CMDP_OK;
-  if (a->env) {   // null once the environment handle has been destroyed (its stream was drained then)
-    (void)hipSetDevice(a->env->device);
-    (void)hipStreamSynchronize(a->env->stream);
-    auto& v = a->env->uc_backrefs;
-    v.erase(std::remove(v.begin(), v.end(), &a->env), v.end());
-  }
-  delete a;
-  return CMDP_OK;
-}
-
 // What a run() call refuses before anything is stepped.  `limit_text` prints the instance, its steps so far and n_steps.
 int park_run_check(ParkAgent* a, int64_t n_steps, int64_t limit, const char* limit_text) {
-  if (!a) return fail(CMDP_ERR_INVALID, "null agent");
-  cmdp_t* h = a->env;
-  if (int rc = bind(h)) return rc;
-  if (n_steps < 0) return fail(CMDP_ERR_INVALID, "n_steps < 0");
-  bool any = false;
-  if (int rc = any_needs_reset(h, &any)) return rc;
-  if (any) return fail(CMDP_ERR_NEEDS_RESET, "the environment needs reset() before the agent can run");
-  if (int rc = visits_check(h, n_steps)) return rc;
-  for (int b = 0; b < h->B; ++b)
+  if (int rc = agent_run_check(a, n_steps)) return rc;
+  for (int b = 0; b < a->env->B; ++b)
     if (a->steps_total[b] + n_steps > limit)
       return fail(CMDP_ERR_OVERFLOW, limit_text, b, (long long)a->steps_total[b], (long long)n_steps);
   return CMDP_OK;
@@ -2721,14 +2747,10 @@ int park_run(ParkAgent* a, int64_t n_steps, int stop_at_episode_end, const uint8
   const int B = h->B;
   hipStream_t st = h->stream;
   const size_t NB = (size_t)n_steps * B;
-  if (actions_trace && a->d_act.n < NB) HIP_TRY(a->d_act.alloc(NB));
   if (obs_trace && a->d_obs.n < NB) HIP_TRY(a->d_obs.alloc(NB));
   if (reward_trace && a->d_rew.n < NB) HIP_TRY(a->d_rew.alloc(NB));
   const uint8_t* dmask = nullptr;
-  if (train_mask) {
-    HIP_TRY(a->d_mask.upload(train_mask, B, st));
-    dmask = a->d_mask.p;
-  }
+  if (int rc = agent_stage_run(a, NB, actions_trace != nullptr, train_mask, &dmask)) return rc;
   std::vector<long long> left((size_t)B, (long long)n_steps);
   std::vector<int64_t> taken((size_t)B, n_steps);
   HIP_TRY(hipMemcpyAsync(a->d_left.p, left.data(), sizeof(long long) * B, hipMemcpyHostToDevice, st));
@@ -2771,41 +2793,72 @@ int park_run(ParkAgent* a, int64_t n_steps, int stop_at_episode_end, const uint8
 
 }  // namespace
 
-struct cmdp_agent {
-  cmdp_t* env = nullptr;
+struct cmdp_agent : AgentBase {
   bool continuous = false;
   QlArgs args{};
   QlcArgs cargs{};
   DevBuf<double> d_Hh, d_gamma, d_Qc, d_Qmainc, d_Vc;  // continuous agent: float64 tables
   DevBuf<double> d_ilog, d_s7;
   DevBuf<int64_t> d_qoff, d_voff;
-  DevBuf<int32_t> d_N, d_mtpos;
+  DevBuf<int32_t> d_N;
   DevBuf<float> d_Q, d_V, d_mu, d_sigma, d_beta;
-  DevBuf<uint32_t> d_mt;
-  DevBuf<int8_t> d_act;
-  DevBuf<double> d_rsum;   // MDPLoop._cumulative_reward per instance
-  DevBuf<uint8_t> d_mask;
   DevBuf<float> d_pi;      // greedy policy [H][S][A]
   DevBuf<float> d_v0;      // packed V[0, :] of the evaluated greedy policies
   int64_t n_q = 0, n_v = 0;
 };
 
+// What the two creates ask of their arguments before the hyper-parameters, and the new agent
+static int ql_create_begin(cmdp_agent_t** out, cmdp_t* env, const int32_t* seeds, bool continuous, std::unique_ptr<cmdp_agent>* guard) {
+  if (!out || !env || !seeds) return fail(CMDP_ERR_INVALID, "null argument");
+  *out = nullptr;
+  if (int rc = bind(env)) return rc;
+  if (!env->has_env || (continuous ? env->H != 0 : env->H < 1))
+    return fail(CMDP_ERR_INVALID, continuous ? "the continuous Q-learning agent needs a continuous environment handle"
+                                             : "the episodic Q-learning agent needs an episodic environment handle");
+  if (env->layout != CMDP_LAYOUT_CSR) return fail(CMDP_ERR_UNSUPPORTED, "agents run on the CSR layout");
+  guard->reset(new cmdp_agent);
+  (*guard)->env = env;
+  (*guard)->continuous = continuous;
+  return CMDP_OK;
+}
+
+// ... and what both end with: the reward sums, the actor's stream (synchronises: the creates' staging vectors die after
+// it), the back-reference
+static int ql_create_end(std::unique_ptr<cmdp_agent>& guard, const int32_t* seeds, cmdp_agent_t** out) {
+  cmdp_agent* a = guard.get();
+  hipStream_t st = a->env->stream;
+  AGENT_ZERO(d_rsum, a->env->B);
+  if (int rc = seed_actor(a, seeds)) return rc;
+  a->args.mt = a->cargs.mt = a->d_mt.p;
+  a->args.mt_pos = a->cargs.mt_pos = a->d_mtpos.p;
+  return agent_attach(guard, out);
+}
+
+// the greedy policy of the agent's Q tables into a->d_pi, [H][S][A] (continuous: H = 1), on the handle's stream
+static int ql_enqueue_greedy(cmdp_agent_t* a) {
+  cmdp_t* h = a->env;
+  if (a->d_pi.n < (size_t)a->n_q) HIP_TRY(a->d_pi.alloc(a->n_q));
+  if (a->continuous)
+    hipLaunchKernelGGL(k_greedy_policy_episodic<double>, dim3(h->B), dim3(64), 0, h->stream, h->B, h->A, 1, 1,
+                       h->d_state_off.p, a->d_Qc.p, a->d_pi.p);
+  else
+    hipLaunchKernelGGL(k_greedy_policy_episodic<float>, dim3(h->B), dim3(64), 0, h->stream, h->B, h->A, h->H, h->H,
+                       h->d_state_off.p, a->d_Q.p, a->d_pi.p);
+  HIP_TRY(hipGetLastError());
+  return CMDP_OK;
+}
+
 extern "C" {
 
 int cmdp_qlearning_create(cmdp_agent_t** out, cmdp_t* env, const int32_t* seeds, int64_t optimization_horizon, double p,
                           double c_1, double c_2, double min_at, int ucb_type) {
-  if (!out || !env || !seeds) return fail(CMDP_ERR_INVALID, "null argument");
-  *out = nullptr;
-  if (int rc = bind(env)) return rc;
-  if (!env->has_env || env->H < 1) return fail(CMDP_ERR_INVALID, "the episodic Q-learning agent needs an episodic environment handle");
-  if (env->layout != CMDP_LAYOUT_CSR) return fail(CMDP_ERR_UNSUPPORTED, "agents run on the CSR layout");
+  std::unique_ptr<cmdp_agent> guard;
+  if (int rc = ql_create_begin(out, env, seeds, false, &guard)) return rc;
   if (!(p > 0 && p < 1) || !(c_1 > 0) || !(min_at >= 0 && min_at < 0.99) || (ucb_type != 0 && ucb_type != 1) ||
       (ucb_type == 1 && !(c_2 > 0)) || optimization_horizon < 1)
     return fail(CMDP_ERR_INVALID, "hyper-parameters out of range (0<p<1, c_1>0, 0<=min_at<0.99, bernstein needs c_2>0)");
   const int B = env->B, A = env->A, H = env->H;
-  cmdp_agent_t* a = new cmdp_agent;
-  std::unique_ptr<cmdp_agent> guard(a);
-  a->env = env;
+  cmdp_agent_t* a = guard.get();
   hipStream_t st = env->stream;
   std::vector<double> ilog((size_t)B), s7((size_t)B);
   std::vector<int64_t> qoff((size_t)B), voff((size_t)B);
@@ -2828,32 +2881,22 @@ int cmdp_qlearning_create(cmdp_agent_t** out, cmdp_t* env, const int32_t* seeds,
   AGENT_ZERO(d_V, a->n_v); AGENT_ZERO(d_mu, a->n_q); AGENT_ZERO(d_sigma, a->n_q); AGENT_ZERO(d_beta, a->n_q);
   hipLaunchKernelGGL(k_fill_i32, dim3(grid_for(a->n_q, 256)), dim3(256), 0, st, a->d_N.p, 1, a->n_q);
   hipLaunchKernelGGL(k_fill_f32, dim3(grid_for(a->n_q, 256)), dim3(256), 0, st, a->d_Q.p, (float)H, a->n_q);
-  AGENT_ZERO(d_rsum, B);
-  if (int rc = seed_actor(env, seeds, a->d_mt, a->d_mtpos)) return rc;   // synchronises: the staging vectors die below
   QlArgs& q = a->args;
   q.H = H; q.ucb = ucb_type; q.c1 = c_1; q.c2 = c_2; q.min_at = min_at; q.H3 = (double)H * H * H;
   q.i_log = a->d_ilog.p; q.sqrtH7SA = a->d_s7.p; q.q_off = a->d_qoff.p; q.v_off = a->d_voff.p;
   q.N = a->d_N.p; q.Q = a->d_Q.p; q.V = a->d_V.p; q.mu = a->d_mu.p; q.sigma = a->d_sigma.p; q.beta = a->d_beta.p;
-  q.mt = a->d_mt.p; q.mt_pos = a->d_mtpos.p;
-  *out = guard.release();
-  return CMDP_OK;
+  return ql_create_end(guard, seeds, out);
 }
 
 int cmdp_qlearning_continuous_create(cmdp_agent_t** out, cmdp_t* env, const int32_t* seeds, int64_t optimization_horizon,
                                      double min_at, double confidence, double span_approx_weight, double h_weight) {
-  if (!out || !env || !seeds) return fail(CMDP_ERR_INVALID, "null argument");
-  *out = nullptr;
-  if (int rc = bind(env)) return rc;
-  if (!env->has_env || env->H != 0) return fail(CMDP_ERR_INVALID, "the continuous Q-learning agent needs a continuous environment handle");
-  if (env->layout != CMDP_LAYOUT_CSR) return fail(CMDP_ERR_UNSUPPORTED, "agents run on the CSR layout");
+  std::unique_ptr<cmdp_agent> guard;
+  if (int rc = ql_create_begin(out, env, seeds, true, &guard)) return rc;
   if (!(min_at >= 0 && min_at < 0.99) || !(confidence > 0 && confidence < 1) || !(span_approx_weight > 0) || !(h_weight > 0) ||
       optimization_horizon < 1)
     return fail(CMDP_ERR_INVALID, "hyper-parameters out of range");
   const int B = env->B, A = env->A;
-  cmdp_agent_t* a = new cmdp_agent;
-  std::unique_ptr<cmdp_agent> guard(a);
-  a->env = env;
-  a->continuous = true;
+  cmdp_agent_t* a = guard.get();
   hipStream_t st = env->stream;
   const double T = (double)optimization_horizon;
   std::vector<double> Hh((size_t)B), gm((size_t)B);
@@ -2885,16 +2928,13 @@ int cmdp_qlearning_continuous_create(cmdp_agent_t** out, cmdp_t* env, const int3
   HIP_TRY(hipMemcpyAsync(a->d_Qc.p, q0.data(), sizeof(double) * a->n_q, hipMemcpyHostToDevice, st));
   HIP_TRY(hipMemcpyAsync(a->d_Qmainc.p, q0.data(), sizeof(double) * a->n_q, hipMemcpyHostToDevice, st));
   HIP_TRY(hipMemcpyAsync(a->d_Vc.p, v0.data(), sizeof(double) * a->n_v, hipMemcpyHostToDevice, st));
-  AGENT_ZERO(d_rsum, B);
-  if (int rc = seed_actor(env, seeds, a->d_mt, a->d_mtpos)) return rc;   // synchronises: the staging vectors die below
   QlcArgs& q = a->cargs;
   q.min_at = min_at > 0.009 ? min_at : 0.0;
   q.four_span = 4 * span_approx_weight;
   q.log_term = std::log(2 * T / confidence);
   q.Hh = a->d_Hh.p; q.gamma = a->d_gamma.p; q.q_off = a->d_qoff.p;
-  q.N = a->d_N.p; q.Q = a->d_Qc.p; q.Qmain = a->d_Qmainc.p; q.V = a->d_Vc.p; q.mt = a->d_mt.p; q.mt_pos = a->d_mtpos.p;
-  *out = guard.release();
-  return CMDP_OK;
+  q.N = a->d_N.p; q.Q = a->d_Qc.p; q.Qmain = a->d_Qmainc.p; q.V = a->d_Vc.p;
+  return ql_create_end(guard, seeds, out);
 }
 
 int cmdp_qlearning_policy(cmdp_agent_t* a, float* pi) {
@@ -2903,10 +2943,7 @@ int cmdp_qlearning_policy(cmdp_agent_t* a, float* pi) {
   if (int rc = bind(h)) return rc;
   if (!a->continuous) return fail(CMDP_ERR_INVALID, "cmdp_qlearning_policy is for the continuous agent; use cmdp_qlearning_evaluate");
   hipStream_t st = h->stream;
-  if (a->d_pi.n < (size_t)a->n_q) HIP_TRY(a->d_pi.alloc(a->n_q));
-  hipLaunchKernelGGL(k_greedy_policy_episodic<double>, dim3(h->B), dim3(64), 0, st, h->B, h->A, 1, 1,
-                     h->d_state_off.p, a->d_Qc.p, a->d_pi.p);
-  HIP_TRY(hipGetLastError());
+  if (int rc = ql_enqueue_greedy(a)) return rc;
   HIP_TRY(hipMemcpyAsync(pi, a->d_pi.p, sizeof(float) * a->n_q, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   return CMDP_OK;
@@ -3166,11 +3203,7 @@ int cmdp_qlearning_average_reward(cmdp_agent_t* a, const uint8_t* mask, double* 
   cmdp_t* h = a->env;
   if (int rc = bind(h)) return rc;
   if (!a->continuous) return fail(CMDP_ERR_INVALID, "cmdp_qlearning_average_reward is for the continuous agent");
-  hipStream_t st = h->stream;
-  if (a->d_pi.n < (size_t)a->n_q) HIP_TRY(a->d_pi.alloc(a->n_q));
-  hipLaunchKernelGGL(k_greedy_policy_episodic<double>, dim3(h->B), dim3(64), 0, st, h->B, h->A, 1, 1,
-                     h->d_state_off.p, a->d_Qc.p, a->d_pi.p);
-  HIP_TRY(hipGetLastError());
+  if (int rc = ql_enqueue_greedy(a)) return rc;
   return chain_launch(h, a->d_pi.p, nullptr, h->d_cur.p, mask, avg, kind, nullptr);
 }
 
@@ -3476,12 +3509,7 @@ int cmdp_mixing_time(cmdp_t* h, const float* pi, const double* stationary, doubl
   return CMDP_OK;
 }
 
-int cmdp_qlearning_destroy(cmdp_agent_t* a) {
-  if (!a) return CMDP_OK;
-  if (a->env) { (void)hipSetDevice(a->env->device); (void)hipStreamSynchronize(a->env->stream); }
-  delete a;
-  return CMDP_OK;
-}
+int cmdp_qlearning_destroy(cmdp_agent_t* a) { return agent_destroy(a); }
 
 // the interaction kernel of `n_steps` steps on the handle's stream (no synchronisation, no copies)
 static int ql_launch(cmdp_agent_t* a, int64_t n_steps, const uint8_t* dmask, int8_t* d_actions, int resume, double* cum_host) {
@@ -3514,21 +3542,12 @@ static int ql_enqueue_run(cmdp_agent_t* a, int64_t n_steps, const uint8_t* dmask
 
 int cmdp_qlearning_run(cmdp_agent_t* a, int64_t n_steps, const uint8_t* train_mask, int8_t* actions_trace,
                        double* reward_sum) {
-  if (!a) return fail(CMDP_ERR_INVALID, "null agent");
+  if (int rc = agent_run_check(a, n_steps)) return rc;
   cmdp_t* h = a->env;
-  if (int rc = bind(h)) return rc;
-  if (n_steps < 0) return fail(CMDP_ERR_INVALID, "n_steps < 0");
-  bool any = false;
-  if (int rc = any_needs_reset(h, &any)) return rc;
-  if (any) return fail(CMDP_ERR_NEEDS_RESET, "the environment needs reset() before the agent can run");
   hipStream_t st = h->stream;
   const size_t NB = (size_t)n_steps * h->B;
-  if (actions_trace && a->d_act.n < NB) HIP_TRY(a->d_act.alloc(NB));
   const uint8_t* dmask = nullptr;
-  if (train_mask) {
-    HIP_TRY(a->d_mask.upload(train_mask, h->B, st));
-    dmask = a->d_mask.p;
-  }
+  if (int rc = agent_stage_run(a, NB, actions_trace != nullptr, train_mask, &dmask)) return rc;
   if (int rc = ql_enqueue_run(a, n_steps, dmask, actions_trace ? a->d_act.p : nullptr)) return rc;
   if (actions_trace) HIP_TRY(hipMemcpyAsync(actions_trace, a->d_act.p, NB, hipMemcpyDeviceToHost, st));
   if (reward_sum) HIP_TRY(hipMemcpyAsync(reward_sum, a->d_rsum.p, sizeof(double) * h->B, hipMemcpyDeviceToHost, st));
@@ -3545,9 +3564,7 @@ static int ql_enqueue_evaluate(cmdp_agent_t* a, float* v0_out = nullptr, int32_t
   const int H = h->H;
   const size_t lds = 2 * sizeof(float) * (size_t)h->max_S;
   if (lds > (size_t)kLdsBudget) return fail(CMDP_ERR_UNSUPPORTED, "instance with %d states does not fit LDS", h->max_S);
-  if (a->d_pi.n < (size_t)a->n_q) HIP_TRY(a->d_pi.alloc(a->n_q));
-  hipLaunchKernelGGL(k_greedy_policy_episodic<float>, dim3(h->B), dim3(64), 0, st, h->B, h->A, H, H,
-                     h->d_state_off.p, a->d_Q.p, a->d_pi.p);
+  if (int rc = ql_enqueue_greedy(a)) return rc;
   const size_t nq = (size_t)(H + 1) * h->n_rows, nv = (size_t)(H + 1) * h->n_states;
   if (h->d_Q.n < nq) HIP_TRY(h->d_Q.alloc(nq));
   if (h->d_V.n < nv) HIP_TRY(h->d_V.alloc(nv));
@@ -3574,156 +3591,107 @@ int cmdp_qlearning_evaluate(cmdp_agent_t* a, float* V0) {
   return CMDP_OK;
 }
 
-int cmdp_qlearning_run_logged(cmdp_agent_t* a, const cmdp_loop_desc* d, int64_t n_logs, int64_t* steps, double* values,
-                              uint8_t* kinds, int64_t* last_training_step, uint8_t* is_training) {
-  using namespace cmdp_tracker;
-  if (!a || !d || !steps || !values || !kinds) return fail(CMDP_ERR_INVALID, "null argument");
+// ---- the logged loop: cmdp_logged_loop.h has its rows, its run-ahead rule and a row's host work; here is the device --------
+// The switches of the logged loop, read nowhere else and once per process.
+// CMDP_LOGGED_PIPELINE = 0 | 1 decides whether rows that cannot change the training mask run ahead; unset: on, except under
+// rocprofv3 (its tool library in LD_PRELOAD or its ROCPROF* variables in the environment), whose queue interception faults
+// on a stream that never drains.
+// CMDP_LOGGED_DRAIN_EVERY = n: the stream is drained completely every n rows (0: never).  Only for runs under rocprofv3,
+// whose queue interception faulted in hipLaunchKernel's argument copy once a stream stayed busy long enough for the
+// runtime's kernel-argument pool to wrap (ROCm 7.2; the same run outside the profiler is fine).
+// CMDP_LOGGED_DEBUG (set): where the host thread's time went (stderr, one line per call).
+static const cmdp_tracker::LoggedSwitches& logged_switches() {
+  static const cmdp_tracker::LoggedSwitches sw = [] {
+    cmdp_tracker::LoggedSwitches s{true, false, 0, std::getenv("CMDP_LOGGED_DEBUG") != nullptr};
+    if (const char* e = std::getenv("CMDP_LOGGED_PIPELINE")) {
+      s.pipeline = std::atoi(e) != 0;
+    } else {
+      const char* pre = std::getenv("LD_PRELOAD");
+      if (pre && std::strstr(pre, "rocprof")) s.pipeline = false;
+      for (char** ev = environ; ev && *ev; ++ev)
+        if (!std::strncmp(*ev, "ROCPROF", 7)) s.pipeline = false;
+    }
+    const char* sync = std::getenv("CMDP_SYNC_MODE");
+    s.blocking_sync = sync && !std::strcmp(sync, "block");
+    if (const char* e = std::getenv("CMDP_LOGGED_DRAIN_EVERY")) s.drain_every = std::atoi(e);
+    return s;
+  }();
+  return sw;
+}
+
+// The device side of one cmdp_qlearning_run_logged call.  Two things overlap with the evaluation of row i and with the
+// host's work on it: the agents' NEXT interval (same stream, enqueued before the host waits) and, for the continuous agent,
+// the stationary-distribution solve itself (second stream, on a snapshot of the policy and of the current states).  Rows
+// that could change the training mask are processed in order: the results are the same either way
+// (tests/test_gpu_mdploop.py holds both against the step-by-step loop).
+struct LoggedLoop {
+  cmdp_agent_t* a;
+  const std::vector<cmdp_tracker::LoggedRow>& plan;
+  const cmdp_tracker::Tracker& tr;
   cmdp_t* h = a->env;
-  if (int rc = bind(h)) return rc;
-  const int B = h->B;
-  const int64_t T = d->n_steps, log_every = d->log_every;
-  if (T < 1) return fail(CMDP_ERR_INVALID, "n_steps < 1");
-  std::vector<int64_t> log_ts;
-  if (log_every > 0)
-    for (int64_t t = log_every; t < T; t += log_every) log_ts.push_back(t);
-  if (n_logs != (int64_t)log_ts.size() + 1)
-    return fail(CMDP_ERR_INVALID, "n_logs must be %lld for %lld steps logged every %lld", (long long)log_ts.size() + 1, (long long)T,
-                (long long)log_every);
-  if (!d->base_val || !d->base_kind) return fail(CMDP_ERR_INVALID, "baseline average rewards missing");
-  const bool episodic = !a->continuous;
-  if (episodic && (!d->opt0 || !d->worst0 || !d->start_pos || !d->start_prob || d->kmax < 1))
-    return fail(CMDP_ERR_INVALID, "episodic baselines missing");
-  if (!episodic)
-    for (int b = 0; b < B; ++b)
-      if (!(d->base_val[3 * b] - d->base_val[3 * b + 1] > 0.0002))   // agent_mdp_interaction.py:379-382
-        return fail(CMDP_ERR_INVALID, "instance %d: optimal and worst average reward are closer than 0.0002", b);
-  // refused before anything is stepped or reset: a caller that falls back to another loop must find the agent untouched
-  if (!episodic && log_every > 0 && chain_lds_bytes(h->max_S, h->max_row_nnz) > (size_t)kLdsBudget)
-    return fail(CMDP_ERR_UNSUPPORTED, "instance with %d states (max %d successors per row) exceeds the LDS budget of K9",
-                h->max_S, h->max_row_nnz);
-  if (!episodic && !h->has_dp) return fail(CMDP_ERR_INVALID, "the handle was created without the DP half (CSR transition matrices)");
-  hipStream_t st = h->stream;
-  const int64_t NS = h->n_states;
-  Tracker tr;
-  tr.init(B, d->n_check, d->base_val, d->base_kind);
-  EpisodicInputs ein{h->H, d->opt0, d->worst0, d->start_pos, d->start_prob, d->kmax};
+  hipStream_t st = h->stream, sx = st;   // sx: the continuous solve's -- the second stream when rows run ahead
   // `cum` twice: the next interval's kernel may already be writing its sums while the host reads this row's
   PinnedBuf<double> cum[2], avg;
   PinnedBuf<float> v0;
   PinnedBuf<int32_t> snap, akind;
   PinnedBuf<uint8_t> mask, need;
-  if (int rc = cum[0].alloc(B)) return rc;
-  if (int rc = cum[1].alloc(B)) return rc;
-  if (int rc = avg.alloc(B)) return rc;
-  if (int rc = v0.alloc((size_t)NS)) return rc;
-  if (int rc = snap.alloc((size_t)3 * B)) return rc;
-  if (int rc = akind.alloc(B)) return rc;
-  if (int rc = mask.alloc(B)) return rc;
-  if (int rc = need.alloc(B)) return rc;
-  if (a->d_mask.n < (size_t)B) HIP_TRY(a->d_mask.alloc(B));
-  if (h->d_ch_mask.n < (size_t)B) HIP_TRY(h->d_ch_mask.alloc(B));
-  std::vector<int64_t> start_abs((size_t)B);
-  for (int b = 0; b < B; ++b) { mask.p[b] = 1; cum[0].p[b] = cum[1].p[b] = 0.0; if (last_training_step) last_training_step[b] = -1; }
-  HIP_TRY(hipMemcpyAsync(a->d_mask.p, mask.p, B, hipMemcpyHostToDevice, st));
-  // MDPLoop.run: visitation counts cleared, environment reset (agent_mdp_interaction.py:219-224)
-  if (int rc = cmdp_reset_visits(h)) return rc;
-  if (int rc = cmdp_reset(h, nullptr, nullptr)) return rc;
-  const auto t_start = std::chrono::steady_clock::now();
-  auto elapsed = [&]() { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count(); };
 
-  // The rows of the run.  Row i: `n_run` steps whose reward sums the row logs (the reference reads `_cumulative_reward` at
-  // step t BEFORE adding that step's reward), then -- inside the loop -- step t itself, whose update the logged policy
-  // already contains; then the evaluation of the agents' greedy policies.  log_every == 1 leaves no step between two rows:
-  // the sum through step t-1 is then what the previous row's single step left.
-  struct Row { int64_t t, n_run, n_since; bool in_loop; };
-  std::vector<Row> plan;
-  {
-    int64_t done = 0, n_since = 0;
-    for (int64_t tl : log_ts) {
-      if (tl - done > 0) n_since += tl - done;
-      plan.push_back(Row{tl, tl - done, n_since, true});
-      done = tl + 1;
-      n_since = 1;
+  int setup(const cmdp_tracker::LoggedSwitches& sw) {
+    const int B = h->B;
+    if (int rc = cum[0].alloc(B)) return rc;
+    if (int rc = cum[1].alloc(B)) return rc;
+    if (int rc = avg.alloc(B)) return rc;
+    if (int rc = v0.alloc((size_t)h->n_states)) return rc;
+    if (int rc = snap.alloc((size_t)3 * B)) return rc;
+    if (int rc = akind.alloc(B)) return rc;
+    if (int rc = mask.alloc(B)) return rc;
+    if (int rc = need.alloc(B)) return rc;
+    for (int b = 0; b < B; ++b) cum[0].p[b] = cum[1].p[b] = 0.0;
+    if (a->d_mask.n < (size_t)B) HIP_TRY(a->d_mask.alloc(B));
+    if (h->d_ch_mask.n < (size_t)B) HIP_TRY(h->d_ch_mask.alloc(B));
+    for (int i = 0; i < 2; ++i)
+      if (!h->ev_row[i])
+        HIP_TRY(hipEventCreateWithFlags(&h->ev_row[i], hipEventDisableTiming | (sw.blocking_sync ? hipEventBlockingSync : 0)));
+    if (a->continuous && sw.pipeline) {
+      if (!h->aux.stream) HIP_TRY(hipStreamCreateWithFlags(&h->aux.stream, hipStreamNonBlocking));
+      sx = h->aux.stream;
+      if (h->d_cur_snap.n < (size_t)B) HIP_TRY(h->d_cur_snap.alloc(B));
     }
-    if (T - done > 0) n_since += T - done;
-    plan.push_back(Row{T - 1, T - done, n_since, false});
+    return CMDP_OK;
   }
-  const size_t n_rows = plan.size();
 
-  // Two things overlap with the evaluation of row i and with the host's work on it: the agents' NEXT interval (same stream,
-  // enqueued before the host waits) and, for the continuous agent, the stationary-distribution solve itself (second stream,
-  // on a snapshot of the policy and of the current states).  Both need the training mask of the next interval before row
-  // i's result is known.  The mask changes in two ways only: (a) an instance freezes -- `after_log` requires the last
-  // n_check normalised regrets, this row's included, to be ~0 and t > 0.2 T, so a row whose n_check - 1 predecessors are not
-  // all ~0 cannot freeze anything, and the host knows that BEFORE the row; (b) the time limit -- rows closer than a few
-  // seconds to it are not run ahead.  Rows that could change the mask are processed in order, as before: the results are
-  // the same either way (tests/test_gpu_mdploop.py holds both against the step-by-step loop).
-  // CMDP_LOGGED_PIPELINE = 0 | 1 decides; unset: on, except under rocprofv3 (its tool library in LD_PRELOAD or its ROCPROF*
-  // variables in the environment), whose queue interception faults on a stream that never drains
-  static const bool pipeline_env = [] {
-    if (const char* e = std::getenv("CMDP_LOGGED_PIPELINE")) return std::atoi(e) != 0;
-    const char* pre = std::getenv("LD_PRELOAD");
-    if (pre && std::strstr(pre, "rocprof")) return false;
-    for (char** ev = environ; ev && *ev; ++ev)
-      if (!std::strncmp(*ev, "ROCPROF", 7)) return false;
-    return true;
-  }();
-  static const bool block_env = std::getenv("CMDP_SYNC_MODE") && !std::strcmp(std::getenv("CMDP_SYNC_MODE"), "block");
-  // CMDP_LOGGED_DRAIN_EVERY = n: the stream is drained completely every n rows (0: never).  Only for runs under rocprofv3,
-  // whose queue interception faulted in hipLaunchKernel's argument copy once a stream stayed busy long enough for the
-  // runtime's kernel-argument pool to wrap (ROCm 7.2; the same run outside the profiler is fine).
-  static const int drain_env = std::getenv("CMDP_LOGGED_DRAIN_EVERY") ? std::atoi(std::getenv("CMDP_LOGGED_DRAIN_EVERY")) : 0;
-  for (int i = 0; i < 2; ++i)
-    if (!h->ev_row[i]) HIP_TRY(hipEventCreateWithFlags(&h->ev_row[i], hipEventDisableTiming | (block_env ? hipEventBlockingSync : 0)));
-  hipStream_t sx = st;
-  if (!episodic && pipeline_env) {
-    if (!h->aux.stream) HIP_TRY(hipStreamCreateWithFlags(&h->aux.stream, hipStreamNonBlocking));
-    sx = h->aux.stream;
-    if (h->d_cur_snap.n < (size_t)B) HIP_TRY(h->d_cur_snap.alloc(B));
+  int upload_mask() {
+    HIP_TRY(hipMemcpyAsync(a->d_mask.p, mask.p, h->B, hipMemcpyHostToDevice, st));
+    return CMDP_OK;
   }
-  const double atol = episodic ? 1e-4 : 1e-5;
-  // rows within reach of the time limit run in order: "within reach" follows the longest row seen so far (a park round of
-  // the reward caches, a throttled host, sixteen batches sharing the GPU can make one row take seconds)
-  double longest_row = 0.0, last_row_done = elapsed();
-  bool limit_passed_while_ahead = false;
-  auto mask_may_change = [&](const Row& r) -> bool {
-    if (limit_passed_while_ahead || d->max_time - elapsed() < std::max(5.5, 3.0 * longest_row)) return true;
-    for (int b = 0; b < B; ++b) {
-      const Instance& x = tr.inst[(size_t)b];
-      if (!episodic && !x.training && !x.cached) return true;   // the cached evaluation is taken at this row: `need` changes
-      if (x.training && may_freeze(x, tr.n_check, r.t, T, atol)) return true;
-    }
-    return false;
-  };
 
-  auto enqueue_interval = [&](size_t i) -> int {
-    const Row& r = plan[i];
+  // the steps of row i: those whose reward sums it logs, then -- inside the loop -- step t itself
+  int enqueue_interval(size_t i) {
+    const cmdp_tracker::LoggedRow& r = plan[i];
     double* c = cum[i & 1].p;
     if (r.n_run > 0) {   // the kernel leaves the sums in `c` (page-locked) itself
       if (int rc = ql_enqueue_run(a, r.n_run, a->d_mask.p, nullptr, c)) return rc;
     } else {
-      HIP_TRY(hipMemcpyAsync(c, a->d_rsum.p, sizeof(double) * B, hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipMemcpyAsync(c, a->d_rsum.p, sizeof(double) * h->B, hipMemcpyDeviceToHost, st));
     }
     if (r.in_loop)
       if (int rc = ql_enqueue_run(a, 1, a->d_mask.p, nullptr)) return rc;
     return CMDP_OK;
-  };
+  }
 
   // evaluation of the agents' current greedy policies; everything a row reads comes back WITHOUT copy kernels: the kernels
   // write into page-locked host memory directly (V[0, :], the start states and in-episode times, the average rewards and
-  // their kinds, the reward sums) and read the evaluation mask from it
-  auto enqueue_eval = [&]() -> int {
-    if (episodic) {
+  // their kinds, the reward sums) and read the evaluation mask from it.  ev_row[1] marks its end.
+  int enqueue_eval() {
+    const int B = h->B;
+    if (!a->continuous) {
       if (int rc = ql_enqueue_evaluate(a, v0.p, snap.p)) return rc;
     } else {
-      continuous_need(tr, need.p);
+      cmdp_tracker::continuous_need(tr, need.p);
       bool any = false;
       for (int b = 0; b < B; ++b) any = any || need.p[b];
       if (any) {
-        if (a->d_pi.n < (size_t)a->n_q) HIP_TRY(a->d_pi.alloc(a->n_q));
-        hipLaunchKernelGGL(k_greedy_policy_episodic<double>, dim3(B), dim3(64), 0, st, B, h->A, 1, 1, h->d_state_off.p,
-                           a->d_Qc.p, a->d_pi.p);
-        HIP_TRY(hipGetLastError());
+        if (int rc = ql_enqueue_greedy(a)) return rc;
         const int32_t* start = h->d_cur.p;
         if (sx != st) {
           HIP_TRY(hipMemcpyAsync(h->d_cur_snap.p, h->d_cur.p, sizeof(int32_t) * B, hipMemcpyDeviceToDevice, st));
@@ -3738,26 +3706,77 @@ int cmdp_qlearning_run_logged(cmdp_agent_t* a, const cmdp_loop_desc* d, int64_t 
     }
     HIP_TRY(hipEventRecord(h->ev_row[1], st));
     return CMDP_OK;
-  };
+  }
 
-  // CMDP_LOGGED_DEBUG=1: where the host thread's time went (stderr, one line per call)
-  static const bool debug_env = std::getenv("CMDP_LOGGED_DEBUG") != nullptr;
-  double t_enq = 0.0, t_wait = 0.0, t_host = 0.0;
+  cmdp_tracker::RowReadback readback(size_t i) const { return {cum[i & 1].p, v0.p, snap.p, need.p, avg.p, akind.p}; }
+};
+
+// the rows of (n_steps, log_every), for a caller whose arrays hold n_logs rows
+static int logged_plan(const cmdp_loop_desc* d, int64_t n_logs, std::vector<cmdp_tracker::LoggedRow>* rows) {
+  if (d->n_steps < 1) return fail(CMDP_ERR_INVALID, "n_steps < 1");
+  cmdp_tracker::plan_logged_rows(d->n_steps, d->log_every, rows);
+  if (n_logs != (int64_t)rows->size())
+    return fail(CMDP_ERR_INVALID, "n_logs must be %lld for %lld steps logged every %lld", (long long)rows->size(), (long long)d->n_steps,
+                (long long)d->log_every);
+  return CMDP_OK;
+}
+
+int cmdp_qlearning_run_logged(cmdp_agent_t* a, const cmdp_loop_desc* d, int64_t n_logs, int64_t* steps, double* values,
+                              uint8_t* kinds, int64_t* last_training_step, uint8_t* is_training) {
+  using namespace cmdp_tracker;
+  using clk = std::chrono::steady_clock;
+  if (!a || !d || !steps || !values || !kinds) return fail(CMDP_ERR_INVALID, "null argument");
+  cmdp_t* h = a->env;
+  if (int rc = bind(h)) return rc;
+  const int B = h->B;
+  const int64_t T = d->n_steps;
+  std::vector<LoggedRow> plan;
+  if (int rc = logged_plan(d, n_logs, &plan)) return rc;
+  if (!d->base_val || !d->base_kind) return fail(CMDP_ERR_INVALID, "baseline average rewards missing");
+  const bool episodic = !a->continuous;
+  if (episodic && (!d->opt0 || !d->worst0 || !d->start_pos || !d->start_prob || d->kmax < 1))
+    return fail(CMDP_ERR_INVALID, "episodic baselines missing");
+  if (!episodic)
+    for (int b = 0; b < B; ++b)
+      if (!(d->base_val[3 * b] - d->base_val[3 * b + 1] > 0.0002))   // agent_mdp_interaction.py:379-382
+        return fail(CMDP_ERR_INVALID, "instance %d: optimal and worst average reward are closer than 0.0002", b);
+  // refused before anything is stepped or reset: a caller that falls back to another loop must find the agent untouched
+  if (!episodic && d->log_every > 0 && chain_lds_bytes(h->max_S, h->max_row_nnz) > (size_t)kLdsBudget)
+    return fail(CMDP_ERR_UNSUPPORTED, "instance with %d states (max %d successors per row) exceeds the LDS budget of K9",
+                h->max_S, h->max_row_nnz);
+  if (!episodic && !h->has_dp) return fail(CMDP_ERR_INVALID, "the handle was created without the DP half (CSR transition matrices)");
+  const LoggedSwitches& sw = logged_switches();
+  LoggedRun run;
+  LoggedLoop loop{a, plan, run.tr};
+  if (int rc = loop.setup(sw)) return rc;
+  run.init(B, episodic, T, d, h->H, h->state_off.data(), loop.mask.p, last_training_step);
+  if (int rc = loop.upload_mask()) return rc;
+  // MDPLoop.run: visitation counts cleared, environment reset (agent_mdp_interaction.py:219-224)
+  if (int rc = cmdp_reset_visits(h)) return rc;
+  if (int rc = cmdp_reset(h, nullptr, nullptr)) return rc;
+  const auto t_start = clk::now();
+  auto secs = [](clk::time_point a0, clk::time_point a1) { return std::chrono::duration<double>(a1 - a0).count(); };
+  auto elapsed = [&]() { return secs(t_start, clk::now()); };
+
+  const size_t n_rows = plan.size();
+  double longest_row = 0.0, last_row_done = elapsed();
+  double t_enq = 0.0, t_wait = 0.0, t_host = 0.0;   // the debug line's
   int64_t n_ahead = 0;
-  auto now = [] { return std::chrono::steady_clock::now(); };
-  auto secs = [](std::chrono::steady_clock::time_point a0, std::chrono::steady_clock::time_point a1) { return std::chrono::duration<double>(a1 - a0).count(); };
-  if (int rc = enqueue_interval(0)) return rc;
+  if (int rc = loop.enqueue_interval(0)) return rc;
   for (size_t i = 0; i < n_rows; ++i) {
-    const Row& r = plan[i];
-    const auto c0 = now();
-    if (int rc = enqueue_eval()) return rc;
-    const bool ahead = pipeline_env && i + 1 < n_rows && !(drain_env > 0 && (i + 1) % (size_t)drain_env == 0) && !mask_may_change(r);
+    const LoggedRow& r = plan[i];
+    const auto c0 = clk::now();
+    if (int rc = loop.enqueue_eval()) return rc;
+    const bool drain = sw.drain_every > 0 && (i + 1) % (size_t)sw.drain_every == 0;
+    const bool ahead = sw.pipeline && i + 1 < n_rows && !drain &&
+                       !limit_within_reach(d->max_time - elapsed(), longest_row, run.limit_passed_while_ahead) &&
+                       !row_may_freeze(run.tr, episodic, r.t, T);
     if (ahead)
-      if (int rc = enqueue_interval(i + 1)) return rc;
+      if (int rc = loop.enqueue_interval(i + 1)) return rc;
     n_ahead += ahead;
-    const auto c1 = now();
+    const auto c1 = clk::now();
     HIP_TRY(hipEventSynchronize(h->ev_row[1]));
-    const auto c2 = now();
+    const auto c2 = clk::now();
     {
       const double e = elapsed();
       longest_row = std::max(longest_row, e - last_row_done);
@@ -3765,86 +3784,76 @@ int cmdp_qlearning_run_logged(cmdp_agent_t* a, const cmdp_loop_desc* d, int64_t 
     }
     t_enq += secs(c0, c1);
     t_wait += secs(c1, c2);
-    const double sps = (double)r.t / std::max(elapsed(), 1e-9);
-    double* val = values + i * N_COLUMNS * B;
-    uint8_t* knd = kinds + i * N_COLUMNS * B;
-    const double* cm = cum[i & 1].p;
     steps[i] = r.t;
-    if (episodic) {
-      // the reference logs step t before the reset that follows a termination: if step t ended an episode (in-episode
-      // time back at 0), its `last_starting_node` is still the start of the episode that ended
-      for (int b = 0; b < B; ++b)   // snap: last_start | prev_start | hstep
-        start_abs[(size_t)b] = h->state_off[b] + ((snap.p[2 * B + b] == 0 && r.in_loop) ? snap.p[B + b] : snap.p[b]);
-      episodic_update(tr, ein, r.t, T, v0.p, start_abs.data(), cm, r.n_since, r.in_loop, sps, val, knd);
-    } else {
-      continuous_update(tr, r.t, T, need.p, avg.p, akind.p, cm, r.n_since, r.in_loop, sps, val, knd);
-    }
-    if (!r.in_loop) { t_host += secs(c2, now()); break; }
+    const double sps = (double)r.t / std::max(elapsed(), 1e-9);
     bool changed = false;
-    // `_limit_exceeded` (agent_mdp_interaction.py:172-177) for the batch.  Should the limit pass on a row whose successor is
-    // already running (a row far longer than any before it), the freeze is recorded at the next row -- which then runs in order
-    bool out_of_time = d->max_time - elapsed() < 0.5;
-    if (out_of_time && ahead) { limit_passed_while_ahead = true; out_of_time = false; }
-    for (int b = 0; b < B; ++b) {
-      if (out_of_time && tr.inst[(size_t)b].training) {
-        tr.inst[(size_t)b].training = false;
-        if (last_training_step) last_training_step[b] = r.t;
-      }
-      const uint8_t m = tr.inst[(size_t)b].training ? 1 : 0;
-      changed = changed || m != mask.p[b];
-      mask.p[b] = m;
-    }
-    if (changed && ahead)   // cannot happen (see mask_may_change); a wrong row must not be returned silently
-      return fail(CMDP_ERR_HIP, "logged loop: the training mask changed at step %lld although the next interval was already running",
-                  (long long)r.t);
-    if (changed) HIP_TRY(hipMemcpyAsync(a->d_mask.p, mask.p, B, hipMemcpyHostToDevice, st));
-    const auto c3 = now();
+    if (int rc = log_row(run, r, loop.readback(i), sps, d->max_time - elapsed(), ahead, values + i * N_COLUMNS * B,
+                         kinds + i * N_COLUMNS * B, &changed))
+      return rc;
+    if (!r.in_loop) { t_host += secs(c2, clk::now()); break; }
+    if (changed)
+      if (int rc = loop.upload_mask()) return rc;
+    const auto c3 = clk::now();
     t_host += secs(c2, c3);
     if (!ahead) {
-      if (drain_env > 0 && (i + 1) % (size_t)drain_env == 0) HIP_TRY(hipStreamSynchronize(st));
-      if (int rc = enqueue_interval(i + 1)) return rc;
-      t_enq += secs(c3, now());
+      if (drain) HIP_TRY(hipStreamSynchronize(loop.st));
+      if (int rc = loop.enqueue_interval(i + 1)) return rc;
+      t_enq += secs(c3, clk::now());
     }
   }
-  HIP_TRY(hipStreamSynchronize(st));
-  if (debug_env)
+  HIP_TRY(hipStreamSynchronize(loop.st));
+  if (sw.debug)
     std::fprintf(stderr, "[logged loop] %d instances, %zu rows (%lld with the next interval started early): enqueue %.2f s, waiting for the device %.2f s, "
                  "host row work %.2f s\n", B, n_rows, (long long)n_ahead, t_enq, t_wait, t_host);
   if (is_training)
-    for (int b = 0; b < B; ++b) is_training[b] = tr.inst[(size_t)b].training ? 1 : 0;
+    for (int b = 0; b < B; ++b) is_training[b] = run.tr.inst[(size_t)b].training ? 1 : 0;
   h->known_reset = true;
   return CMDP_OK;
 }
 
-// The indicator code alone, on inputs given by the caller (no device involved): what cmdp_qlearning_run_logged does with
+// The rows' host work alone, on inputs given by the caller (no device involved): what cmdp_qlearning_run_logged does with
 // the values it reads back at every logging step.  Exists so that the CPU test suite can hold the C++ tracker against the
-// reference's own indicator code (golden G15).
+// reference's own indicator code (golden G15), and the schedule and the run-ahead rule against the rows: `ahead` is decided
+// as the driver decides it with a clock that never runs out, so log_row's check meets every freeze of the inputs.
 int cmdp_tracker_replay(const cmdp_loop_desc* d, int32_t B, int32_t episodic, const int64_t* state_off, int64_t n_logs,
                         const int64_t* log_steps, const uint8_t* in_loop, const int64_t* n_since, const double* cum_reward,
                         const float* V0, const int64_t* start_state, const double* avg, const int32_t* avg_kind,
                         double* values, uint8_t* kinds, uint8_t* is_training) {
   using namespace cmdp_tracker;
-  if (!d || !log_steps || !in_loop || !n_since || !cum_reward || !values || !kinds) return fail(CMDP_ERR_INVALID, "null argument");
-  Tracker tr;
-  tr.init(B, d->n_check, d->base_val, d->base_kind);
-  std::vector<uint8_t> need((size_t)B);
-  std::vector<int64_t> start_abs((size_t)B);
+  if (!d || !cum_reward || !values || !kinds) return fail(CMDP_ERR_INVALID, "null argument");
+  std::vector<LoggedRow> rows;
+  if (!log_steps && !in_loop && !n_since) {
+    if (int rc = logged_plan(d, n_logs, &rows)) return rc;
+  } else {
+    if (!log_steps || !in_loop || !n_since) return fail(CMDP_ERR_INVALID, "null argument");
+    for (int64_t i = 0; i < n_logs; ++i) rows.push_back(LoggedRow{log_steps[i], 0, n_since[i], in_loop[i] != 0});
+  }
+  std::vector<uint8_t> mask((size_t)B), need((size_t)B);
+  // last_start | prev_start | hstep, never 0: `start_state` already names the start of the logged episode
+  std::vector<int32_t> snap((size_t)3 * B, 1);
+  LoggedRun run;
+  run.init(B, episodic != 0, d->n_steps, d, d->horizon, state_off, mask.data(), nullptr);
   const int64_t NS = episodic ? state_off[B] : 0;
-  EpisodicInputs ein{d->horizon, d->opt0, d->worst0, d->start_pos, d->start_prob, d->kmax};
   for (int64_t i = 0; i < n_logs; ++i) {
-    double* val = values + (size_t)i * N_COLUMNS * B;
-    uint8_t* knd = kinds + (size_t)i * N_COLUMNS * B;
+    const LoggedRow& r = rows[(size_t)i];
+    RowReadback in{cum_reward + (size_t)i * B, nullptr, nullptr, nullptr, nullptr, nullptr};
     if (episodic) {
-      for (int b = 0; b < B; ++b) start_abs[(size_t)b] = state_off[b] + start_state[(size_t)i * B + b];
-      episodic_update(tr, ein, log_steps[i], d->n_steps, V0 + (size_t)i * NS, start_abs.data(), cum_reward + (size_t)i * B,
-                      n_since[i], in_loop[i] != 0, 0.0, val, knd);
+      for (int b = 0; b < B; ++b) snap[(size_t)b] = (int32_t)start_state[(size_t)i * B + b];
+      in.v0 = V0 + (size_t)i * NS;
+      in.snap = snap.data();
     } else {
-      continuous_need(tr, need.data());
-      continuous_update(tr, log_steps[i], d->n_steps, need.data(), avg + (size_t)i * B, avg_kind + (size_t)i * B,
-                        cum_reward + (size_t)i * B, n_since[i], in_loop[i] != 0, 0.0, val, knd);
+      continuous_need(run.tr, need.data());
+      in.need = need.data();
+      in.avg = avg + (size_t)i * B;
+      in.akind = avg_kind + (size_t)i * B;
     }
+    const bool ahead = i + 1 < n_logs && !row_may_freeze(run.tr, episodic != 0, r.t, d->n_steps);
+    bool changed = false;
+    if (int rc = log_row(run, r, in, 0.0, std::numeric_limits<double>::infinity(), ahead, values + (size_t)i * N_COLUMNS * B,
+                         kinds + (size_t)i * N_COLUMNS * B, &changed))
+      return rc;
     if (is_training)
-      for (int b = 0; b < B; ++b) is_training[(size_t)i * B + b] = tr.inst[(size_t)b].training ? 1 : 0;
+      for (int b = 0; b < B; ++b) is_training[(size_t)i * B + b] = run.tr.inst[(size_t)b].training ? 1 : 0;
   }
   return CMDP_OK;
 }
@@ -4224,10 +4233,10 @@ int cmdp_ucrl2_create(cmdp_ucrl2_t** out, cmdp_t* env, const int32_t* seeds, int
   if (int rc = park_all(a)) return rc;
   if (int rc = ucrl2_round(a, B, 0, 0)) return rc;
   HIP_TRY(hipStreamSynchronize(st));
-  return park_attach(guard, out);
+  return agent_attach(guard, out);
 }
 
-int cmdp_ucrl2_destroy(cmdp_ucrl2_t* a) { return park_destroy(a); }
+int cmdp_ucrl2_destroy(cmdp_ucrl2_t* a) { return agent_destroy(a); }
 
 int cmdp_ucrl2_set_option(cmdp_ucrl2_t* a, int option, int64_t value) {
   if (!a || !a->env) return fail(CMDP_ERR_INVALID, "null agent, or its environment handle has been destroyed");
@@ -4481,10 +4490,10 @@ int cmdp_psrl_create(cmdp_psrl_t** out, cmdp_t* env, const int32_t* seeds, int64
   if (int rc = psrl_round(a, B, 0, 0, 0)) return rc;
   HIP_TRY(hipStreamSynchronize(st));
   psrl_times(a);
-  return park_attach(guard, out);
+  return agent_attach(guard, out);
 }
 
-int cmdp_psrl_destroy(cmdp_psrl_t* a) { return park_destroy(a); }
+int cmdp_psrl_destroy(cmdp_psrl_t* a) { return agent_destroy(a); }
 
 int cmdp_psrl_run(cmdp_psrl_t* a, int64_t n_steps, int stop_at_episode_end, const uint8_t* train_mask, int8_t* actions_trace,
                   int32_t* obs_trace, double* reward_trace, double* cumulative_reward, int64_t* steps_taken) {

@@ -63,38 +63,31 @@ class _BatchedLoop:
     def _run_python(self, T: int, log_every: int = -1, max_time: float = np.inf) -> List[List[Dict[str, float]]]:
         from time import time
 
+        from .vector_tracker import log_schedule
+
         env, agent = self.env, self.agent
         self.vt.reset()
         self.last_training_step = np.full(env.B, -1, np.int64)
         timer = time()
         env.reset_visits()
         env.reset()
-        done, n_since = 0, 0
         mask = np.ones(env.B, bool)
-        cum = np.zeros(env.B)
-        log_ts = [t for t in range(log_every, T, log_every)] if log_every and log_every > 0 else []
-        for tl in log_ts:
-            # the reference reads `_cumulative_reward` at step tl BEFORE adding that step's reward: stop after step
-            # tl-1 to read the sum, then execute step tl (whose update the logged policy already contains); when no step
-            # lies between two rows (log_every == 1) that sum is what the previous row's single step returned
-            if tl - done > 0:
-                cum = agent.run(tl - done, train=mask)["cumulative_reward"]
-                n_since += tl - done
-            elif done > 0:
-                cum = cum_after
+        cum_after = None
+        for t, n_run, n_since, in_loop in log_schedule(T, log_every):
+            # the reference reads `_cumulative_reward` at step t BEFORE adding that step's reward: stop after step t-1
+            # to read the sum, then execute step t (whose update the logged policy already contains); when no step lies
+            # between two rows (log_every == 1) that sum is what the previous row's single step returned
+            cum = agent.run(n_run, train=mask)["cumulative_reward"] if n_run > 0 or not in_loop else cum_after
+            if not in_loop:
+                self._log(t, cum, n_since, T, in_loop=False)
+                break
             cum_after = agent.run(1, train=mask)["cumulative_reward"]
-            done = tl + 1
-            self._log(tl, cum, n_since, T, in_loop=True)
+            self._log(t, cum, n_since, T, in_loop=True)
             if max_time - (time() - timer) < 0.5:  # `_limit_exceeded` (agent_mdp_interaction.py:172-177) for the batch
                 hit = self.vt.is_training.copy()
-                self.last_training_step[hit] = tl
+                self.last_training_step[hit] = t
                 self.vt.is_training[:] = False
             mask = self.vt.is_training.copy()
-            n_since = 1
-        if T - done > 0:
-            n_since += T - done
-        cum = agent.run(T - done, train=mask)["cumulative_reward"]
-        self._log(T - 1, cum, n_since, T, in_loop=False)
         return self.vt.tables()
 
 

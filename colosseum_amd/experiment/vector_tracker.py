@@ -470,8 +470,24 @@ def loop_desc(T: int, log_every: int, n_check: int, baselines: Sequence[MP], max
     return d, keep
 
 
+def log_schedule(T: int, log_every: int):
+    """The rows of `MDPLoop.run(T, log_every)` as (t, n_run, n_since, in_loop): `n_run` steps whose reward sum the row
+    logs (the reference reads `_cumulative_reward` at step t BEFORE adding that step's reward), then -- inside the loop
+    -- step t itself, whose update the logged policy already contains; `n_since` steps lie between the previous row and
+    this one.  log_every == 1 leaves no step between two rows (n_run == 0): the sum through step t - 1 is then what the
+    previous row's single step left.  The last row, at T - 1, is outside the loop.  plan_logged_rows of
+    csrc/cmdp_logged_loop.h is the same schedule."""
+    rows, done, n_since = [], 0, 0
+    for tl in range(log_every, T, log_every) if log_every and log_every > 0 else ():
+        n_since += max(tl - done, 0)
+        rows.append((tl, tl - done, n_since, True))
+        done, n_since = tl + 1, 1
+    rows.append((T - 1, T - done, n_since + max(T - done, 0), False))
+    return rows
+
+
 def n_log_rows(T: int, log_every: int) -> int:
-    return (len(range(log_every, T, log_every)) if log_every and log_every > 0 else 0) + 1
+    return len(log_schedule(T, log_every))
 
 
 def native_log(B: int, steps: np.ndarray, values: np.ndarray, kinds: np.ndarray) -> BatchLog:

@@ -460,11 +460,15 @@ typedef struct cmdp_loop_desc {
 } cmdp_loop_desc;
 int cmdp_qlearning_run_logged(cmdp_agent_t* a, const cmdp_loop_desc* desc, int64_t n_logs, int64_t* steps, double* values,
                               uint8_t* kinds, int64_t* last_training_step, uint8_t* is_training);
-/* The indicator code of cmdp_qlearning_run_logged alone, on caller-supplied inputs (host only, no device): per row the
-   step, whether it lies inside the loop (the final row does not run the freeze check), the steps since the previous row,
-   cumulative rewards [n_logs][B], and -- episodic: V0 [n_logs][state_off[B]] of the policies and the logged episode's
-   start state [n_logs][B] (instance-relative); continuous: avg / avg_kind [n_logs][B] (kind != 0: np.float32).
-   is_training [n_logs][B] receives the flags after every row.  For tests against the reference's indicator code. */
+/* What cmdp_qlearning_run_logged does on the host at every row (csrc/cmdp_logged_loop.h), on caller-supplied inputs
+   (host only, no device): per row the step, whether it lies inside the loop (the final row does not run the freeze
+   check), the steps since the previous row, cumulative rewards [n_logs][B], and -- episodic: V0 [n_logs][state_off[B]] of
+   the policies and the logged episode's start state [n_logs][B] (instance-relative); continuous: avg / avg_kind
+   [n_logs][B] (kind != 0: np.float32).  is_training [n_logs][B] receives the flags after every row.
+   With log_steps, in_loop and n_since all NULL the rows are those of cmdp_qlearning_run_logged for desc->n_steps and
+   desc->log_every, and an n_logs that is not their number is CMDP_ERR_INVALID, as there.  Every row is also held to the
+   rule by which the loop starts an interval before the previous row's result is known: inputs that freeze an instance at
+   a row the rule lets run ahead fail with CMDP_ERR_HIP.  For tests against the reference's indicator code. */
 int cmdp_tracker_replay(const cmdp_loop_desc* desc, int32_t B, int32_t episodic, const int64_t* state_off, int64_t n_logs,
                         const int64_t* log_steps, const uint8_t* in_loop, const int64_t* n_since, const double* cum_reward,
                         const float* V0, const int64_t* start_state, const double* avg, const int32_t* avg_kind,

@@ -5,6 +5,9 @@ training.  A second test runs a batch of different instances and seeds against t
 (tests/helpers_agents.py, itself pinned to G7) stepping the CPU oracle environment."""
 import json
 import os
+import re
+import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -236,3 +239,79 @@ def test_log_every_one_reads_the_reward_sum_of_the_previous_step(need_gpu):
             if k != "steps_per_second":
                 assert float(got[k]) == pytest.approx(float(ref[k]), rel=1e-6, abs=1e-5), (k, got["steps"])
     mdp.close()
+
+
+# ---- the smallest pairs: the orphaned agent, and the logged loop with and without rows that run ahead -----------------
+def _small_pair(setting, B, horizon, with_dp):
+    """B DeepSea instances of size 4 (seeds 0 .. B-1) and their Q-learning agents."""
+    from colosseum_amd.agents import BatchedQLearningContinuous
+
+    env = BatchedMDP([make_model("DeepSea" + setting, seed=s, size=4) for s in range(B)], rng_mode=L.RNG_MT_COMPAT, with_dp=with_dp)
+    if setting == "Episodic":
+        return env, BatchedQLearningEpisodic(env, list(range(B)), optimization_horizon=horizon, p=0.05, c_1=0.5)
+    return env, BatchedQLearningContinuous(env, list(range(B)), optimization_horizon=horizon)
+
+
+@pytest.mark.parametrize("setting", ["Episodic", "Continuous"])
+def test_agent_destroyed_after_its_environment(need_gpu, setting):
+    """Garbage collection picks the order: cmdp_destroy orphans the handle's agents, which then refuse to run and free
+    only their own memory (the path tests/test_gpu_ucrl2.py and tests/test_gpu_psrl.py hold the other agents to)."""
+    env, agent = _small_pair(setting, 1, 50, False)
+    env.reset()
+    agent.run(50)
+    env._agents = []   # as when the weak references are already dead
+    env.close()
+    with pytest.raises(L.CmdpError) as ei:
+        agent.run(10)
+    assert ei.value.code == L.ERR_INVALID
+    agent.close()
+
+
+LOGGED_T, LOGGED_EVERY = 600, 50   # 12 rows; those at t <= 0.2 T cannot freeze anything, so at least two may run ahead
+
+
+def child():
+    """Runs in a fresh process whose environment carries CMDP_LOGGED_PIPELINE (the library reads it once): per setting
+    the rows of the one-call loop and of the Python-driven loop, one line each, every value with its type."""
+    from colosseum_amd.experiment.batched_loop import BatchedContinuousLoop, BatchedEpisodicLoop
+
+    for setting, Loop in (("Episodic", BatchedEpisodicLoop), ("Continuous", BatchedContinuousLoop)):
+        for native in (True, False):
+            env, agent = _small_pair(setting, 2, LOGGED_T, True)
+            loop = Loop(env, agent)
+            loop.native = native
+            tables = loop.run(T=LOGGED_T, log_every=LOGGED_EVERY)
+            rows = [[{k: [type(v).__name__, v if k == "steps" else float(v).hex()] for k, v in row.items() if k != "steps_per_second"}
+                     for row in table] for table in tables]
+            print("ROWS " + json.dumps([setting, native, rows]), flush=True)
+            agent.close()
+            env.close()
+
+
+def test_logged_loop_rows_do_not_depend_on_running_ahead(need_gpu):
+    """CMDP_LOGGED_PIPELINE=0 and =1, each in a child process: the debug line counts no row started early without the
+    pipeline and at least one with it, and the rows of both one-call loops and both Python-driven loops are the same in
+    value and numpy type.  One child at a time; after a child that exits non-zero nothing else is started."""
+    sets = {}
+    for pipeline in ("0", "1"):
+        r = subprocess.run([sys.executable, os.path.abspath(__file__)], capture_output=True, text=True, timeout=600,
+                           env=dict(os.environ, CMDP_LOGGED_PIPELINE=pipeline, CMDP_LOGGED_DEBUG="1"))
+        assert r.returncode == 0, (pipeline, r.returncode, r.stdout[-2000:], r.stderr[-4000:])
+        early = [int(n) for n in re.findall(r"\[logged loop\] 2 instances, 12 rows \((\d+) with the next interval started early\)", r.stderr)]
+        assert len(early) == 2, r.stderr[-4000:]   # the one-call loop of either setting
+        assert all(n == 0 for n in early) if pipeline == "0" else all(n >= 1 for n in early), (pipeline, early)
+        for line in r.stdout.splitlines():
+            if line.startswith("ROWS "):
+                setting, native, rows = json.loads(line[5:])
+                sets[(setting, pipeline, native)] = rows
+    assert len(sets) == 8
+    for setting in ("Episodic", "Continuous"):
+        first = sets[(setting, "0", True)]
+        assert len(first) == 2 and all(len(table) == 12 for table in first)
+        assert {row["steps"][1] for row in first[0]} == set(range(50, 600, 50)) | {599}
+        for key in (("0", False), ("1", True), ("1", False)):
+            assert sets[(setting,) + key] == first, (setting, key)
+
+
+if __name__ == "__main__":
+    child()

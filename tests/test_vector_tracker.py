@@ -11,7 +11,9 @@ import numpy as np
 import pytest
 
 from conftest import load_golden
-from colosseum_amd.experiment.vector_tracker import (F32, F64, WEAK, MP, ContinuousVectorTracker, EpisodicVectorTracker)
+from colosseum_amd import _lib as L
+from colosseum_amd.experiment.vector_tracker import (F32, F64, WEAK, MP, ContinuousVectorTracker, EpisodicVectorTracker,
+                                                    log_schedule, loop_desc, n_log_rows, native_log)
 
 
 def _same(a, b, key):
@@ -169,63 +171,153 @@ def _check_native(z, members, log, flags):
     assert set(LOG_COLUMNS) | {"steps"} == set(members[0][1]["keys"]) | {"steps_per_second"}
 
 
-def test_native_tracker_equals_reference_indicator_code():
-    """cmdp_tracker_replay (host-only entry point of libcmdp.so) on the inputs of golden G15: the rows, numpy types and
-    training flags the reference's own indicator code produced."""
-    import ctypes as C
-
-    from colosseum_amd import _lib as L
-    from colosseum_amd.experiment.vector_tracker import loop_desc, native_log
-
-    lib = L.load()
-    n_frozen = 0
+def _g15_replay_inputs():
+    """Every G15 group as the arguments of cmdp_tracker_replay: (z, members, B, episodic, desc, inputs) with inputs = ts,
+    in_loop, n_since (the golden's schedule arrays) and off, cum, V0, start, avg, akind (None where the setting has none)."""
     z, by = _groups("episodic")
     for g, members in by.items():
         c0 = members[0][1]
-        B = len(members)
         sizes = [len(z[k + "opt0"]) for k, _ in members]
         off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
         flat = [np.concatenate([z[k + n] for k, _ in members]) for n in ("opt0", "worst0", "rand0")]
         starts = [(z[k + "start_states"], z[k + "start_probs"]) for k, _ in members]
         vt = EpisodicVectorTracker(c0["H"], off, *flat, starts, c0["n_check"])  # prepares baselines and start tables
-        d, keep = loop_desc(c0["T"], 100, c0["n_check"], (vt.opt, vt.worst, vt.rand), H=c0["H"], opt0=flat[0], worst0=flat[1],
-                            start_pos=vt._ss, start_prob=vt._sp)
-        ts = z[members[0][0] + "t"].astype(np.int64)
-        n = len(ts)
+        desc = loop_desc(c0["T"], 100, c0["n_check"], (vt.opt, vt.worst, vt.rand), H=c0["H"], opt0=flat[0], worst0=flat[1],
+                         start_pos=vt._ss, start_prob=vt._sp)
+        n = len(z[members[0][0] + "t"])
         V0 = np.ascontiguousarray(np.stack([np.concatenate([z[k + "V0"][i] for k, _ in members]) for i in range(n)]), np.float32)
         start = np.ascontiguousarray(np.stack([[z[k + "last_start"][i] for k, _ in members] for i in range(n)]), np.int64)
-        cum = np.ascontiguousarray(np.stack([[z[k + "cum"][i] for k, _ in members] for i in range(n)]), np.float64)
-        in_loop = np.ascontiguousarray(z[members[0][0] + "in_loop"], np.uint8)
-        n_since = np.ascontiguousarray(z[members[0][0] + "n_since"], np.int64)
-        values = np.zeros((n, len(L.LOG_COLUMNS), B))
-        kinds = np.zeros((n, len(L.LOG_COLUMNS), B), np.uint8)
-        flags = np.zeros((n, B), np.uint8)
-        L.check(lib.cmdp_tracker_replay(C.byref(d), B, 1, L.ptr(off), n, L.ptr(ts), L.ptr(in_loop), L.ptr(n_since), L.ptr(cum),
-                                        L.ptr(V0), L.ptr(start), None, None, L.ptr(values), L.ptr(kinds), L.ptr(flags)))
-        _check_native(z, members, native_log(B, ts, values, kinds), flags)
-        n_frozen += int((flags[-1] == 0).sum())
+        yield z, members, len(members), 1, desc, dict(off=off, V0=V0, start=start, avg=None, akind=None, **_g15_rows(z, members, n))
     z, by = _groups("continuous")
     for g, members in by.items():
         c0 = members[0][1]
-        B = len(members)
 
         def mp(j):
             return MP.from_scalars([np.float32(z[k + "baselines"][j]) if z[k + "baseline_kinds"][j] == 1
                                     else np.float64(z[k + "baselines"][j]) for k, _ in members])
 
-        d, keep = loop_desc(c0["T"], 100, c0["n_check"], (mp(0), mp(1), mp(2)))
-        ts = z[members[0][0] + "t"].astype(np.int64)
-        n = len(ts)
+        desc = loop_desc(c0["T"], 100, c0["n_check"], (mp(0), mp(1), mp(2)))
+        n = len(z[members[0][0] + "t"])
         avg = np.ascontiguousarray(np.stack([[z[k + "avg"][i] for k, _ in members] for i in range(n)]), np.float64)
         akind = np.ascontiguousarray(np.stack([[1 if z[k + "avg_kinds"][i] == 1 else 0 for k, _ in members] for i in range(n)]), np.int32)
-        cum = np.ascontiguousarray(np.stack([[z[k + "cum"][i] for k, _ in members] for i in range(n)]), np.float64)
-        in_loop = np.ascontiguousarray(z[members[0][0] + "in_loop"], np.uint8)
-        n_since = np.ascontiguousarray(z[members[0][0] + "n_since"], np.int64)
-        values = np.zeros((n, len(L.LOG_COLUMNS), B))
-        kinds = np.zeros((n, len(L.LOG_COLUMNS), B), np.uint8)
-        flags = np.zeros((n, B), np.uint8)
-        L.check(lib.cmdp_tracker_replay(C.byref(d), B, 0, None, n, L.ptr(ts), L.ptr(in_loop), L.ptr(n_since), L.ptr(cum),
-                                        None, None, L.ptr(avg), L.ptr(akind), L.ptr(values), L.ptr(kinds), L.ptr(flags)))
-        _check_native(z, members, native_log(B, ts, values, kinds), flags)
+        yield z, members, len(members), 0, desc, dict(off=None, V0=None, start=None, avg=avg, akind=akind, **_g15_rows(z, members, n))
+
+
+def _g15_rows(z, members, n):
+    k0 = members[0][0]
+    return dict(ts=z[k0 + "t"].astype(np.int64), in_loop=np.ascontiguousarray(z[k0 + "in_loop"], np.uint8),
+                n_since=np.ascontiguousarray(z[k0 + "n_since"], np.int64),
+                cum=np.ascontiguousarray(np.stack([[z[k + "cum"][i] for k, _ in members] for i in range(n)]), np.float64))
+
+
+def _replay(desc, B, episodic, inp, n, schedule=True, check=True):
+    """cmdp_tracker_replay on `inp`; schedule=False passes NULL for the three schedule arrays, so that the library plans
+    the rows itself.  Returns (return code, values, kinds, flags)."""
+    import ctypes as C
+
+    lib = L.load()
+    ptr = L.ptr
+    values = np.zeros((n, len(L.LOG_COLUMNS), B))
+    kinds = np.zeros((n, len(L.LOG_COLUMNS), B), np.uint8)
+    flags = np.zeros((n, B), np.uint8)
+    sched = [ptr(inp[k]) if schedule else None for k in ("ts", "in_loop", "n_since")]
+    rc = lib.cmdp_tracker_replay(C.byref(desc[0]), B, episodic, ptr(inp["off"]), n, *sched, ptr(inp["cum"]), ptr(inp["V0"]),
+                                 ptr(inp["start"]), ptr(inp["avg"]), ptr(inp["akind"]), L.ptr(values), L.ptr(kinds), L.ptr(flags))
+    if check:
+        L.check(rc)
+    return rc, values, kinds, flags
+
+
+def test_native_tracker_equals_reference_indicator_code():
+    """cmdp_tracker_replay (host-only entry point of libcmdp.so) on the inputs of golden G15: the rows, numpy types and
+    training flags the reference's own indicator code produced."""
+    n_frozen = 0
+    for z, members, B, episodic, desc, inp in _g15_replay_inputs():
+        n = len(inp["ts"])
+        _, values, kinds, flags = _replay(desc, B, episodic, inp, n)
+        _check_native(z, members, native_log(B, inp["ts"], values, kinds), flags)
         n_frozen += int((flags[-1] == 0).sum())
     assert n_frozen >= 8
+
+
+def test_native_replay_plans_the_rows_of_g15_itself():
+    """With the three schedule arrays NULL cmdp_tracker_replay takes its rows from plan_logged_rows (the planner of
+    cmdp_qlearning_run_logged): G15 is T = 4000 / 3000 with a row every 100 steps, so values, kinds and training flags
+    must equal those of the golden's own arrays.  Every row also passes log_row's check that a row the run-ahead rule
+    lets start early does not change the training mask -- on inputs that freeze at least eight instances."""
+    n_groups = n_frozen = 0
+    for z, members, B, episodic, desc, inp in _g15_replay_inputs():
+        n = len(inp["ts"])
+        assert n == n_log_rows(desc[0].n_steps, desc[0].log_every)
+        want = [(int(t), int(ns), bool(il)) for t, ns, il in zip(inp["ts"], inp["n_since"], inp["in_loop"])]
+        assert [(t, ns, il) for t, _, ns, il in log_schedule(desc[0].n_steps, desc[0].log_every)] == want
+        given, planned = _replay(desc, B, episodic, inp, n), _replay(desc, B, episodic, inp, n, schedule=False)
+        for a, b in zip(given[1:], planned[1:]):
+            np.testing.assert_array_equal(a, b)
+        n_frozen += int((planned[3][-1] == 0).sum())
+        n_groups += 1
+    assert n_groups == 6 and n_frozen >= 8
+
+
+SCHEDULES = [(1, 1), (2, 1), (60, 1), (7, 3), (9, 3), (10, 3), (5, 5), (5, 6), (50, 0), (50, -1)]
+
+
+def _synthetic_inputs(rng, n, B, episodic):
+    """Random inputs of n rows (values inside the ranges of G15's: rewards in [0, 1]), and the loop description without T and
+    log_every.  Episodic: 3 + b states per instance, one start state."""
+    mk = lambda T, log_every, **kw: loop_desc(T, log_every, 3, **kw)
+    cum = np.cumsum(rng.random((n, B)), 0)
+    if episodic:
+        sizes = 3 + np.arange(B)
+        off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+        NS, H = int(off[-1]), 4
+        worst0 = rng.random(NS).astype(np.float32)
+        opt0 = (worst0 + 1 + rng.random(NS)).astype(np.float32)
+        rand0 = ((worst0 + opt0) / 2).astype(np.float32)
+        vt = EpisodicVectorTracker(H, off, opt0, worst0, rand0, [([0], [1.0])] * B, 3)
+        kw = dict(baselines=(vt.opt, vt.worst, vt.rand), H=H, opt0=opt0, worst0=worst0, start_pos=vt._ss, start_prob=vt._sp)
+        V0 = np.where(rng.random((n, NS)) < 0.5, opt0, worst0 + (opt0 - worst0) * rng.random((n, NS))).astype(np.float32)
+        start = rng.integers(0, 3, (n, B)).astype(np.int64)
+        return mk, kw, dict(off=off, V0=V0, start=start, avg=None, akind=None, cum=cum)
+    opt = rng.random(B) + 1.0
+    base = [MP.from_scalars([np.float64(x) for x in v]) for v in (opt, opt - 1.0, opt - 0.5)]
+    avg = np.where(rng.random((n, B)) < 0.5, opt, opt - rng.random((n, B)))
+    akind = rng.integers(0, 2, (n, B)).astype(np.int32)
+    return mk, dict(baselines=base), dict(off=None, V0=None, start=None, avg=avg, akind=akind, cum=cum)
+
+
+@pytest.mark.parametrize("T,log_every", SCHEDULES)
+def test_native_replay_plans_the_rows_log_schedule_gives(T, log_every):
+    """plan_logged_rows (C++) against log_schedule (Python) through their effect: replay with the schedule arrays NULL
+    equals replay with the arrays of log_schedule, on random inputs, in both settings; and n_log_rows is its length.
+    n_check = 3 and evaluations that are optimal half of the time make instances freeze where the schedule has the rows."""
+    rows = log_schedule(T, log_every)
+    n, B = len(rows), 4
+    assert n == n_log_rows(T, log_every) == (len(range(log_every, T, log_every)) if log_every > 0 else 0) + 1
+    assert rows[-1][0] == T - 1 and not rows[-1][3] and all(r[3] for r in rows[:-1])
+    assert sum(r[1] for r in rows) + (n - 1) == T  # every step runs once: n_run before each row, one more inside the loop
+    rng = np.random.default_rng(1000 * T + log_every + 7)
+    for episodic in (1, 0):
+        mk, kw, inp = _synthetic_inputs(rng, n, B, episodic)
+        desc = mk(T, log_every, **kw)
+        inp.update(ts=np.array([r[0] for r in rows], np.int64), n_since=np.array([r[2] for r in rows], np.int64),
+                   in_loop=np.array([r[3] for r in rows], np.uint8))
+        given, planned = _replay(desc, B, episodic, inp, n), _replay(desc, B, episodic, inp, n, schedule=False)
+        for a, b in zip(given[1:], planned[1:]):
+            np.testing.assert_array_equal(a, b)
+        assert np.isfinite(planned[1]).all()
+
+
+def test_native_replay_refuses_a_wrong_number_of_rows():
+    """A planned replay whose arrays are sized for another number of rows is CMDP_ERR_INVALID, as for
+    cmdp_qlearning_run_logged; so is one that gives only some of the three schedule arrays."""
+    rng = np.random.default_rng(5)
+    mk, kw, inp = _synthetic_inputs(rng, 4, 2, 0)
+    desc = mk(10, 3, **kw)  # rows at 3, 6, 9 and the final one
+    assert _replay(desc, 2, 0, inp, 4, schedule=False)[0] == L.OK
+    for n in (3, 5, 0):
+        rc = _replay(desc, 2, 0, dict(inp, cum=np.zeros((max(n, 1), 2))), n, schedule=False, check=False)[0]
+        assert rc == L.ERR_INVALID
+        assert "n_logs must be 4 for 10 steps logged every 3" in L.load().cmdp_last_error().decode()
+    inp.update(ts=np.array([3, 6, 9, 9], np.int64), n_since=None, in_loop=None)
+    assert _replay(desc, 2, 0, inp, 4, check=False)[0] == L.ERR_INVALID
