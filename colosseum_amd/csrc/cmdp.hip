@@ -740,6 +740,10 @@ const char* cmdp_build_id(void) { return k_build_id + 14; }
 
 const char* cmdp_last_error(void) { return g_err.c_str(); }
 
+int cmdp_k1e_round_interior(int e_lo, int horizon, int64_t n_steps, int n_instances) {
+  return k1e_round_interior(e_lo, horizon, n_steps, n_instances) ? 1 : 0;
+}
+
 int cmdp_device_count(void) {
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess) return 0;
@@ -1162,6 +1166,7 @@ static int launch_k1e(cmdp_t* h, const RolloutCall& c) {
     e.cnts = h->d_k1e_cnts[i].p;
     e.seg_h0 = i ? h->d_k1e_h0b.p : h->d_k1e_h0.p;
     e.n_pass = (int)((k1e_max_episodes(n, e.H) + K1E_EPP - 1) / K1E_EPP);
+    e.fast = !(e.debug & 16) && need * sizeof(uint2) < ((size_t)1 << 31);   // interior rounds: 32-bit byte offsets into codes / cnts
     if (ov && h->aux.used[i]) HIP_TRY(hipStreamWaitEvent(st, h->aux.scan[i], 0));   // its last scan has read this set
     const bool last = s0 + seg >= c.n;
     if (last) HIP_TRY(hipEventRecord(h->ev_time[0], st));

@@ -39,6 +39,13 @@
 //         is used (cmdp_device.h: the packed domain-2 stream): 0.8 VALU instructions per transition instead of the 25 a whole
 //         block per four one-bit actions cost K1U.  LDS operations of one wavefront are performed in order, so the walk of a
 //         group needs NO workgroup barrier (a ring shared by the workgroup needed two per 128 episodes: 0.04 ms of 0.6).
+//   inner a round whose eight episodes are all full, none the segment's first and none with its last transition (123 of a
+//         wavefront's 125 working rounds at 30 000 transitions of H = 30) is INTERIOR (k1e_round_interior, wave-uniform, SALU):
+//         it takes a path of its own that asks nothing per chain -- constant start word and count, the four chains' bit
+//         windows fetched by eight ring reads behind ONE wait, the code / count words stored unpredicated through scalar bases
+//         and one 32-bit lane offset, no partial episode, no last transition.  About 668 VALU instructions per lane and round
+//         at H = 30 (5.6 per transition) against the general path's 782 (6.5); the step loops are the same 480.  Every other
+//         round takes the general path; CMDP_K1E_DEBUG=16 sends all of them there (results unchanged).
 //   next  the table image of the workgroup's NEXT group is loaded into registers during the last round of the walk (and the
 //         instance scalars under the flush): the staging's HBM round trips run under the walk.
 //   flush the table dwords hold DEPARTURE counts; they are added to a launch-spanning departure image in HBM (layout of the
@@ -73,7 +80,10 @@ struct K1ePlan {
   int32_t n_pass;            // rounds per wavefront in this segment: ceil(episodes / 128)
   int32_t gdw;               // dwords of a group's table image in HBM: S * 32 rounded up to whole rounds of 1024 (the workgroup's
                              // loads and returnless adds need no bounds test; the padding is zero and stays zero)
-  int32_t debug;             // CMDP_K1E_DEBUG (timing experiments, results INVALID): 1 no walk, 2 no flush, 4 no Philox, 8 no code stores
+  int32_t debug;             // CMDP_K1E_DEBUG (timing experiments, results INVALID): 1 no walk, 2 no flush, 4 no Philox, 8 no code stores;
+                             // 16 no round is interior (every round takes the general path; results VALID)
+  int32_t fast;              // interior rounds take the short path (k1e_round_interior): set per launch, when bit 16 of `debug` is
+                             // clear and every byte offset into codes / cnts stays below 2^31 (32-bit lane offsets)
   const uint32_t* etab;      // [group of 32 instances][gdw >= S * 32]: one dword per state, successor words of action 0 (low half)
                              // and 1 (high half), s' << 7 | code; interleaved by instance like the LDS image
   const double* rvals;       // [n_codes]
@@ -91,6 +101,17 @@ __host__ __device__ inline size_t k1e_ring_bytes(const K1ePlan& p) { return (siz
 __host__ __device__ inline size_t k1e_lds_bytes(const K1ePlan& p) { return k1e_tab_bytes(p) + k1e_ring_bytes(p); }
 __host__ __device__ inline size_t k1e_fold_lds_bytes(const K1ePlan& p) { return (size_t)2 * K1E_NI * (size_t)p.S * 4; }
 __host__ __device__ inline int64_t k1e_max_episodes(int64_t n_steps, int H) { return (n_steps + 2 * (int64_t)H - 2) / H; }
+
+// Is the round of eight episodes e_lo .. e_lo + 7 of a segment of n_steps transitions INTERIOR -- whatever the in-episode
+// time h0 in [0, H) the segment starts at, every one of the eight is walked at full length H, none is episode 0 of the
+// segment (which starts from the instance's current state, h0 steps in) and none contains transition n_steps - 1 (whose
+// chain leaves the instance's state behind)?  Episode e > 0 covers transitions [e H - h0, (e + 1) H - h0): the last of the
+// round ends at (e_lo + 8) H - h0 <= (e_lo + 8) H, which has to stay BELOW n_steps.  Wave-uniform inputs only (the
+// kernel evaluates it in SALU); nb = instances of the group (lanes that own none are masked off as a whole, so a ragged group
+// has interior rounds too).  Exported as cmdp_k1e_round_interior: the tests check the function the kernel uses.
+__host__ __device__ inline bool k1e_round_interior(int e_lo, int H, int64_t n_steps, int nb) {
+  return nb > 0 && H > 0 && e_lo >= 2 * K1E_EPL && ((int64_t)e_lo + 2 * K1E_EPL) * (int64_t)H < n_steps;
+}
 
 // steps of a code word (2-bit fields, unused fields zero) with code 1, 2, 3: n1 | n2 << 11 | n3 << 22 (11-bit fields: the
 // packed words of a 16-word tile add up without carries into the neighbouring field)
@@ -114,8 +135,9 @@ typedef __attribute__((address_space(3))) uint32_t* k1e_lds_u32;
 // what a workgroup needs of a group of 32 instances before it can walk it: the table image (<= 16 dwords per thread) and the
 // lane's instance scalars.  A workgroup owns SEVERAL groups, one after the other, and loads the next group's set during the
 // last pass of the walk of the current one: the HBM round trips of the staging run under the walk
-// (the table image itself travels in plain local arrays of sixteen, indexed by constants only: scalars after SROA -- a struct
-// that is copied as a whole ends up in scratch, a 16-wide vector value is spilled as a whole)
+// (the table image itself travels in ONE plain local array of sixteen, indexed by constants only: scalars after SROA -- a
+// struct that is copied as a whole ends up in scratch, a 16-wide vector value is spilled as a whole.  The staging is the only
+// reader and comes before the walk, so the last pass loads the next image into the very registers the staging has emptied)
 struct K1eGroupRegs {
   uint32_t key_x, key_y, ntr_lo, ntr_hi;
   uint32_t hcs;   // in-episode time << 18 | current state << 9 | start state (S <= 512, H < 2^14: one register instead of three)
@@ -154,11 +176,12 @@ __global__ void __launch_bounds__(K1E_THREADS) __attribute__((amdgpu_waves_per_e
   auto fetch_table = [&](int g, uint32_t (&pair)[16]) {
     const uint32_t* src = p.etab + (size_t)g * (size_t)p.gdw;
     uint32_t tid_o = (uint32_t)tid;
-    asm volatile("" : "+s"(src), "+v"(tid_o));
+    int nj_o = nj;   // (pinned too: the sixteen tests j < nj, kept for staging, fetch and flush alike, cost 32 SGPRs under the walk)
+    asm volatile("" : "+s"(src), "+v"(tid_o), "+s"(nj_o));
     // (uniform base + 32-bit lane offset: no 64-bit address per load)
 #pragma unroll
     for (int j = 0; j < 16; ++j)
-      pair[j] = j < nj ? __builtin_nontemporal_load(&src[tid_o + (uint32_t)(j * K1E_THREADS)]) : 0u;
+      pair[j] = j < nj_o ? __builtin_nontemporal_load(&src[tid_o + (uint32_t)(j * K1E_THREADS)]) : 0u;
   };
   auto fetch_scalars = [&](int g, K1eGroupRegs& r) {
     int bb = min(g * K1E_NI + inst, t.B - 1);   // (lanes past the batch repeat its last instance; they own nothing)
@@ -182,10 +205,12 @@ __global__ void __launch_bounds__(K1E_THREADS) __attribute__((amdgpu_waves_per_e
     const int b = g0 + (owner ? inst : 0);
     const bool more = g + (int)gridDim.x < n_groups;
     // ---- stage: {count 0 | successor word} from the registers the previous group's last pass (or the prologue) filled ----
+    int nj_s = nj;
+    asm volatile("" : "+s"(nj_s));   // (as in fetch_table: the tests j < nj are made here, not kept under the walk)
 #pragma unroll
     for (int j = 0; j < 16; ++j) {
       const uint32_t k = (uint32_t)tid + (uint32_t)(j * K1E_THREADS);
-      if (j < nj) {   // (gdw <= 2^ash / 4: the padding of the image lands in the padding of the LDS table)
+      if (j < nj_s) {   // (gdw <= 2^ash / 4: the padding of the image lands in the padding of the LDS table)
         tab[k] = cur_pair[j] & 0xffffu;
         tab[a_words + k] = cur_pair[j] >> 16;
       }
@@ -232,14 +257,110 @@ __global__ void __launch_bounds__(K1E_THREADS) __attribute__((amdgpu_waves_per_e
       return __builtin_amdgcn_alignbit(d1, d0, a0 & 31u);
     };
 
-    uint32_t next_pair[16];
+    // The step loops of an INTERIOR round (below): the general path's `steps` and its two loops, word for word, on the interior
+    // path's own registers.  (One pair of lambdas shared by both paths compiles, but the general path then keeps five values
+    // more across the walk and the kernel no longer fits 96 VGPRs without scratch.)
+    auto steps_int = [&](uint32_t (&bits)[K1E_EPL], uint32_t (&w)[K1E_EPL], uint32_t addv, uint32_t (&cw)[K1E_EPL]) {
+      uint32_t ra[K1E_EPL];
+#pragma unroll
+      for (int c = 0; c < K1E_EPL; ++c) {
+        uint32_t ax;
+        asm("v_add_co_u32 %0, vcc, %0, %0\n\tv_cndmask_b32 %1, %2, %3, vcc" : "+v"(bits[c]), "=v"(ax) : "v"(lbase), "v"(lbase1) : "vcc");
+        asm("v_and_or_b32 %0, %1, %2, %3" : "=v"(ra[c]) : "v"(w[c]), "s"(K1E_SMASK), "v"(ax));
+      }
+#pragma unroll
+      for (int c = 0; c < K1E_EPL; ++c)
+        w[c] = __hip_atomic_fetch_add((k1e_lds_u32)(uintptr_t)ra[c], addv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+#pragma unroll
+      for (int c = 0; c < K1E_EPL; ++c) cw[c] = __builtin_amdgcn_alignbit(w[c], cw[c], 2u);
+    };
+    // the L (<= 32, wave-uniform) steps of a chunk: the first L0 = min(L, 16) reward codes into clo, the others into chi
+    auto walk_int = [&](int L0, int L, uint32_t (&bits)[K1E_EPL], uint32_t (&w)[K1E_EPL], uint32_t addv,
+                        uint32_t (&clo)[K1E_EPL], uint32_t (&chi)[K1E_EPL]) {
+      int j = 0;
+      for (; j + 1 < L0; j += 2) { steps_int(bits, w, addv, clo); steps_int(bits, w, addv, clo); }
+      if (j < L0) steps_int(bits, w, addv, clo);
+      j = 16;
+      for (; j + 1 < L; j += 2) { steps_int(bits, w, addv, chi); steps_int(bits, w, addv, chi); }
+      if (j < L) steps_int(bits, w, addv, chi);
+    };
+    // this wavefront's ring as LDS byte addresses: dword d of the lane's instance at lbase + ring_sbase + (128 d & ring_mask)
+    const uint32_t ring_sbase = tab_bytes + (uint32_t)wave * RD * (4u * K1E_NI);
+    const uint32_t ring_mask = (RD - 1u) << 7;
+
     const int R = p.n_pass;   // rounds per wavefront: wavefront w owns episodes [8 R w, 8 R (w + 1)) of the segment
     for (int pass = 0; pass < R; ++pass) {
       const int e_lo = (wave * R + pass) * 2 * K1E_EPL;
       if (!(p.debug & 4)) produce(e_lo);
       // the next group's table image and scalars: in flight under the whole of this wavefront's last round
-      if (pass == R - 1 && more) fetch_table(g + (int)gridDim.x, next_pair);
+      if (pass == R - 1 && more) fetch_table(g + (int)gridDim.x, cur_pair);
       __builtin_amdgcn_wave_barrier();
+      // ---- an INTERIOR round (k1e_round_interior: eight full episodes, none the segment's first, none with its last
+      // transition -- 123 of a wavefront group's 125 working rounds at 30 000 transitions of H = 30): what the general path
+      // below asks per chain and lane is known for the whole wavefront.  Every chain starts from the start state and counts,
+      // the four chains' first transitions are H apart, the code / count words go out unpredicated through a uniform base and
+      // ONE 32-bit lane offset, and there is neither a partial episode nor a last transition to look for ----
+      if (p.fast && k1e_round_interior(e_lo, H, n_steps, nb)) {
+        if (owner && !(p.debug & 1)) {
+          // (pinned to the round like fetch_table's addresses: hoisted out of the pass loop -- the group is invariant there --
+          // the lane's parts of the stream position, the ring address and the word index would sit in registers under the
+          // whole walk, where the next group's table image needs them)
+          int e0 = sub * K1E_EPL;
+          uint32_t ring_base = ring_sbase;
+          asm volatile("" : "+v"(e0), "+s"(ring_base));
+          e0 += e_lo;
+          const uint32_t ring_lane = lbase + ring_base;
+          const uint32_t a00 = ntr_lo + (uint32_t)(e0 * H - h0);   // chain 0's first transition, as a stream position
+          uint32_t addv = 0x10000u, hcs = cur_regs.hcs;   // every chain counts ...
+          asm volatile("" : "+v"(addv), "+v"(hcs));
+          uint32_t w[K1E_EPL];
+#pragma unroll
+          for (int c = 0; c < K1E_EPL; ++c) w[c] = (hcs & 511u) << 7;   // ... and starts from the start state
+          for (int ch = 0; ch < nch; ++ch) {
+            const int L = __builtin_amdgcn_readfirstlane(min(32, H - 32 * ch));
+            // all eight ring reads of the four chains, then ONE wait (ring dword d at ring_lane + 128 d)
+            uint32_t a0[K1E_EPL], d0[K1E_EPL], d1[K1E_EPL], bits[K1E_EPL], clo[K1E_EPL], chi[K1E_EPL];
+#pragma unroll
+            for (int c = 0; c < K1E_EPL; ++c) {
+              a0[c] = a00 + (uint32_t)(c * H + 32 * ch);
+              const uint32_t o = a0[c] << 2;
+              d0[c] = *(k1e_lds_u32)(uintptr_t)(ring_lane + (o & ring_mask));
+              d1[c] = *(k1e_lds_u32)(uintptr_t)(ring_lane + ((o + 128u) & ring_mask));
+            }
+#pragma unroll
+            for (int c = 0; c < K1E_EPL; ++c) {
+              bits[c] = __builtin_bitreverse32(__builtin_amdgcn_alignbit(d1[c], d0[c], a0[c]));   // (the shift is a0 mod 32)
+              clo[c] = 0u; chi[c] = 0u;
+            }
+            const int L0 = __builtin_amdgcn_readfirstlane(min(L, 16));
+            walk_int(L0, L, bits, w, addv, clo, chi);
+            if (!(p.debug & 8)) {
+              const uint32_t wi = ((uint32_t)e0 * (uint32_t)nch + (uint32_t)ch) * (uint32_t)t.B + (uint32_t)b;
+              const uint32_t o8 = wi << 3, o4 = wi << 2;                 // (< 2^31: p.fast)
+              const uint32_t cstride = (uint32_t)nch * (uint32_t)t.B;   // words between two consecutive episodes
+#pragma unroll
+              for (int c = 0; c < K1E_EPL; ++c) {
+                const uint32_t lo = L0 < 16 ? clo[c] >> (32 - 2 * L0) : clo[c];
+                const uint32_t hi = L > 16 ? (L < 32 ? chi[c] >> (32 - 2 * (L - 16)) : chi[c]) : 0u;
+                typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+                u32x2 v;
+                v.x = lo; v.y = hi;
+                // (the uniform bases pinned to scalar registers: regrouped as (base + lane offset) + chain offset they cost two
+                // 64-bit vector additions per chain)
+                typedef __attribute__((address_space(1))) unsigned char* k1e_glb_u8;   // (global, not flat, stores)
+                k1e_glb_u8 cb = (k1e_glb_u8)(uintptr_t)p.codes + (size_t)((uint32_t)c * cstride) * 8;
+                k1e_glb_u8 nb4 = (k1e_glb_u8)(uintptr_t)p.cnts + (size_t)((uint32_t)c * cstride) * 4;
+                asm volatile("" : "+s"(cb), "+s"(nb4));
+                __builtin_nontemporal_store(v, (__attribute__((address_space(1))) u32x2*)(cb + (size_t)o8));
+                __builtin_nontemporal_store(FEW ? k1e_code_counts3(lo, hi) : k1e_code_counts(lo, hi),
+                                            (__attribute__((address_space(1))) uint32_t*)(nb4 + (size_t)o4));
+              }
+            }
+          }
+        }
+        __builtin_amdgcn_wave_barrier();
+        continue;
+      }
       // ---- the lane's chains of this round (everything relative to the segment fits an int: n_steps <= K1E_SEG) ----
       // (first transition, length and kind of chain c are recomputed where they are needed, not kept in registers across
       // the walk: the next group's table image waits in registers under the last pass)
@@ -377,12 +498,13 @@ __global__ void __launch_bounds__(K1E_THREADS) __attribute__((amdgpu_waves_per_e
       typedef __attribute__((address_space(1))) unsigned long long* k1e_glb_u64;
       unsigned long long* dep = reinterpret_cast<unsigned long long*>(p.dep) + (size_t)g * (size_t)p.gdw;
       uint32_t tid_o = (uint32_t)tid;
-      asm volatile("" : "+s"(dep), "+v"(tid_o));   // (as in fetch_group: no hoisted 64-bit offsets)
+      int nj_f = nj;
+      asm volatile("" : "+s"(dep), "+v"(tid_o), "+s"(nj_f));   // (as in fetch_group: no hoisted 64-bit offsets)
       const k1e_glb_u64 gdep = (k1e_glb_u64)(uintptr_t)dep;
 #pragma unroll
       for (int j = 0; j < 16; ++j) {
         const uint32_t k = tid_o + (uint32_t)(j * K1E_THREADS);
-        if (j < nj) {
+        if (j < nj_f) {
           const uint32_t c0 = tab[k] >> 16, c1 = tab[a_words + k] >> 16;
           if (c0 | c1)
             __hip_atomic_fetch_add(gdep + k, (unsigned long long)c0 | ((unsigned long long)c1 << 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -394,8 +516,6 @@ __global__ void __launch_bounds__(K1E_THREADS) __attribute__((amdgpu_waves_per_e
     // round trip runs under the flush's LDS reads and the barrier)
     fetch_scalars(g + (int)gridDim.x, cur_regs);
     __syncthreads();   // the counts are read: the next group's image may overwrite them
-#pragma unroll
-    for (int j = 0; j < 16; ++j) cur_pair[j] = next_pair[j];
   }
 }
 

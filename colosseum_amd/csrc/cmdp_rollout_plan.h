@@ -301,7 +301,8 @@ inline K1eChoice plan_k1e(const PlanInput& in, const DetTables& t, const PlanKno
   e.ash = 12;   // (at least 32 padded states: an action's image then holds whole rounds of the workgroup's 1024 lanes)
   while ((1 << (e.ash - 7)) < S) ++e.ash;   // action stride: states padded to a power of two, 128 B per state
   e.debug = k.k1e_debug;
-  if (e.debug) std::fprintf(stderr, "libcmdp: CMDP_K1E_DEBUG=%d switches phases of k_rollout_epi off -- results are INVALID (timing experiments only)\n", e.debug);
+  // (bit 16 only sends the interior rounds the general way: results stay valid)
+  if (e.debug & 15) std::fprintf(stderr, "libcmdp: CMDP_K1E_DEBUG=%d switches phases of k_rollout_epi off -- results are INVALID (timing experiments only)\n", e.debug);
   e.gdw = (int32_t)((((int64_t)S * K1E_NI + K1E_THREADS - 1) / K1E_THREADS) * K1E_THREADS);   // a group's image: whole rounds of the workgroup's loads
   if (S > 512 || k1e_lds_bytes(e) > (size_t)kLdsBudget) return c;
   // interleaved by instance like the LDS image: [group of 32][state][instance in group]

@@ -162,6 +162,12 @@ int cmdp_version(void);
    stale prebuilt .so cannot pass for the sources next to it.  No reference counterpart. */
 const char* cmdp_build_id(void);
 const char* cmdp_last_error(void);
+/* K1E (csrc/cmdp_k1e.h): 1 when the round of eight episodes e_lo .. e_lo + 7 of a segment of n_steps transitions is INTERIOR
+   for a group of n_instances (1 .. 32) instances -- whatever in-episode time in [0, horizon) the segment starts at, all
+   eight are walked at full length, none is the segment's first episode and none contains its last transition -- else 0.
+   The very predicate k_rollout_epi branches on (such rounds skip the per-chain bookkeeping); needs no handle and no device.
+   No reference counterpart. */
+int cmdp_k1e_round_interior(int e_lo, int horizon, int64_t n_steps, int n_instances);
 int cmdp_device_count(void);
 int cmdp_set_device(int device);
 
