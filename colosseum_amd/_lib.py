@@ -59,6 +59,7 @@ EXPORTS = [
     "cmdp_ucrl2_set_option",
     "cmdp_psrl_create", "cmdp_psrl_destroy", "cmdp_psrl_run", "cmdp_psrl_layout", "cmdp_psrl_model", "cmdp_psrl_last_sample",
     "cmdp_psrl_reference_sample", "cmdp_vi_episodic_dense", "cmdp_psrl_episode_end_update", "cmdp_k1e_round_interior",
+    "cmdp_k1e_code_counts",
 ]
 
 
@@ -222,6 +223,8 @@ def load():
         L.cmdp_psrl_reference_sample.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, f32, vp, vp, vp]
         L.cmdp_vi_episodic_dense.argtypes = [i32, vp, vp, i32, vp, vp, vp, vp]
         L.cmdp_k1e_round_interior.argtypes = [i32, i32, i64, i32]
+        L.cmdp_k1e_code_counts.argtypes = [C.c_uint32, C.c_uint32, i32]
+        L.cmdp_k1e_code_counts.restype = C.c_uint32
         _lib = L
     return _lib
 

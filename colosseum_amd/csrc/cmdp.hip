@@ -214,7 +214,6 @@ struct cmdp {
   size_t k1e_lds = 0;
   DevBuf<uint32_t> d_etab;
   DevBuf<uint2> d_k1e_codes[2];    // two sets: the reward scan of one segment runs (second stream) under the walk of the next
-  DevBuf<uint32_t> d_k1e_cnts[2];
   DevBuf<int32_t> d_k1e_h0b;       // second seg_h0 buffer
   struct {                         // the second stream: K1E's reward scans (scan of code set i after the walk that wrote it)
     hipStream_t stream = nullptr;
@@ -744,6 +743,10 @@ int cmdp_k1e_round_interior(int e_lo, int horizon, int64_t n_steps, int n_instan
   return k1e_round_interior(e_lo, horizon, n_steps, n_instances) ? 1 : 0;
 }
 
+uint32_t cmdp_k1e_code_counts(uint32_t lo, uint32_t hi, int few) {
+  return few ? k1e_code_counts_few(lo, hi) : k1e_code_counts(lo, hi);
+}
+
 int cmdp_device_count(void) {
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess) return 0;
@@ -1138,35 +1141,35 @@ static int launch_k1e(cmdp_t* h, const RolloutCall& c) {
       HIP_TRY(hipEventCreateWithFlags(&h->aux.scan[i], hipEventDisableTiming | hipEventDisableSystemFence));
     }
   if (!ov) { if (int rc = k1e_scan_join(h)) return rc; }
-  // segment length: the code words of a segment (12 bytes per episode chunk and instance, two sets) stay within ~1.5 GB
-  const int64_t budget_words = std::max<int64_t>(4, (int64_t)((768ll << 20) / (12 * (int64_t)h->B * e.nch)));
+  // segment length: the code words of a segment (8 bytes per episode chunk and instance, two sets) stay within ~1.5 GB
+  const int64_t budget_words = std::max<int64_t>(4, (int64_t)((768ll << 20) / (8 * (int64_t)h->B * e.nch)));
   const int64_t seg = std::max<int64_t>(e.H, std::min<int64_t>(K1E_SEG, (budget_words - 2) * e.H));
   const int64_t epi_cap = k1e_max_episodes(std::min<int64_t>(c.n, seg), e.H);
   const size_t need = (size_t)epi_cap * (size_t)e.nch * (size_t)h->B;
   if (h->d_k1e_h0.n < (size_t)h->B) HIP_TRY(h->d_k1e_h0.alloc(h->B));
   if (h->d_k1e_h0b.n < (size_t)h->B) HIP_TRY(h->d_k1e_h0b.alloc(h->B));
-  if (int rc = set_lds(k_rollout_epi<true>, h->k1e_lds)) return rc;
-  if (int rc = set_lds(k_rollout_epi<false>, h->k1e_lds)) return rc;
+  if (int rc = set_lds(k_rollout_epi, h->k1e_lds)) return rc;
   for (int64_t s0 = 0; s0 < c.n; s0 += seg) {
     const int64_t n = std::min<int64_t>(seg, c.n - s0);
     const int i = ov ? (int)(h->aux.seq & 1) : 0;
-    if (h->d_k1e_codes[i].n < need || h->d_k1e_cnts[i].n < need) {
-      if (h->aux.stream) HIP_TRY(hipStreamSynchronize(h->aux.stream));   // a scan may still read the buffers
-      if (h->d_k1e_codes[i].alloc(need) != hipSuccess || h->d_k1e_cnts[i].alloc(need) != hipSuccess) {
-        // no room for the code words (12 bytes per episode and instance): possible before the first segment only (the
+    if (h->d_k1e_codes[i].n < need) {
+      if (h->aux.stream) HIP_TRY(hipStreamSynchronize(h->aux.stream));   // a scan may still read the buffer
+      if (h->d_k1e_codes[i].alloc(need) != hipSuccess) {
+        // no room for the code words (8 bytes per episode chunk and instance): possible before the first segment only (the
         // buffers never shrink)
         (void)hipGetLastError();
         if (s0 > 0) return fail(CMDP_ERR_HIP, "K1E: out of device memory for the code words of a later segment");
         h->d_k1e_codes[i].release();
-        h->d_k1e_cnts[i].release();
         return fail(kNoWorkspace, "K1E: out of device memory for %zu code words", need);
       }
     }
     e.codes = h->d_k1e_codes[i].p;
-    e.cnts = h->d_k1e_cnts[i].p;
     e.seg_h0 = i ? h->d_k1e_h0b.p : h->d_k1e_h0.p;
     e.n_pass = (int)((k1e_max_episodes(n, e.H) + K1E_EPP - 1) / K1E_EPP);
-    e.fast = !(e.debug & 16) && need * sizeof(uint2) < ((size_t)1 << 31);   // interior rounds: 32-bit byte offsets into codes / cnts
+    // interior rounds: 32-bit byte offsets into codes, and a wavefront's ring starts at a multiple of its own size (the ring
+    // address is then formed by OR).  Sixteen rings larger than the tables do not fit the LDS budget, so the rings of every
+    // plan are aligned today; were one not, all its rounds would go the general way
+    e.fast = !(e.debug & 16) && need * sizeof(uint2) < ((size_t)1 << 31) && k1e_ring_aligned(e);
     if (ov && h->aux.used[i]) HIP_TRY(hipStreamWaitEvent(st, h->aux.scan[i], 0));   // its last scan has read this set
     const bool last = s0 + seg >= c.n;
     if (last) HIP_TRY(hipEventRecord(h->ev_time[0], st));
@@ -1174,8 +1177,7 @@ static int launch_k1e(cmdp_t* h, const RolloutCall& c) {
     // group's table image in flight under the walk; CMDP_K1E_GRID = workgroups (timing experiments; any value is correct)
     int k1e_grid = std::min(grid_for(h->B, K1E_NI), h->cus);
     if (const char* gs = std::getenv("CMDP_K1E_GRID")) k1e_grid = std::max(1, std::min(grid_for(h->B, K1E_NI), std::atoi(gs)));
-    if (e.n_codes <= 3) hipLaunchKernelGGL(k_rollout_epi<true>, dim3(k1e_grid), dim3(K1E_THREADS), h->k1e_lds, st, t, e, (int)n, c.last);
-    else hipLaunchKernelGGL(k_rollout_epi<false>, dim3(k1e_grid), dim3(K1E_THREADS), h->k1e_lds, st, t, e, (int)n, c.last);
+    hipLaunchKernelGGL(k_rollout_epi, dim3(k1e_grid), dim3(K1E_THREADS), h->k1e_lds, st, t, e, (int)n, c.last);
     if (last) HIP_TRY(hipEventRecord(h->ev_time[1], st));
     if (ov) {
       HIP_TRY(hipEventRecord(h->aux.walk[i], st));

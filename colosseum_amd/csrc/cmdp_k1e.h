@@ -42,9 +42,11 @@
 //   inner a round whose eight episodes are all full, none the segment's first and none with its last transition (123 of a
 //         wavefront's 125 working rounds at 30 000 transitions of H = 30) is INTERIOR (k1e_round_interior, wave-uniform, SALU):
 //         it takes a path of its own that asks nothing per chain -- constant start word and count, the four chains' bit
-//         windows fetched by eight ring reads behind ONE wait, the code / count words stored unpredicated through scalar bases
-//         and one 32-bit lane offset, no partial episode, no last transition.  About 668 VALU instructions per lane and round
-//         at H = 30 (5.6 per transition) against the general path's 782 (6.5); the step loops are the same 480.  Every other
+//         windows fetched by eight ring reads behind ONE wait (a wavefront's ring starts at a multiple of its own size --
+//         k1e_ring_aligned, checked by the host -- so a ring address is one v_and_or_b32, and chain c's stream position is
+//         chain 0's plus a scalar: 7 VALU instructions per chain), the code words stored unpredicated through scalar bases
+//         and one 32-bit lane offset, no partial episode, no last transition.  At H = 30 per lane and round: bit fetch 29,
+//         step loops 480, code words 15 and 4 stores, entry and clearing 22, plus the round's Philox block.  Every other
 //         round takes the general path; CMDP_K1E_DEBUG=16 sends all of them there (results unchanged).
 //   next  the table image of the workgroup's NEXT group is loaded into registers during the last round of the walk (and the
 //         instance scalars under the flush): the staging's HBM round trips run under the walk.
@@ -53,10 +55,18 @@
 //         reference counts the ARRIVAL state under the action taken (base.py:1302-1303): a linear function of the departure
 //         counts, formed by k_epi_fold when somebody needs the counters.
 //   out   the reward codes of an episode (2 bits per step) go to HBM, 8 bytes per (episode, 32-step chunk), layout
-//         codes[episode][chunk][instance], with the number of steps per code next to them; state, in-episode time and the
-//         Philox counters are advanced as if the transitions had been taken one by one.
+//         codes[episode][chunk][instance], and nothing else: the walk is bound by VALU issue, and the steps per code, which
+//         only make a tile of the scan cheap, are counted by the scan (the walk once stored them next to the codes: 9 VALU
+//         instructions and a 4-byte store per word).  State, in-episode time and the Philox counters are advanced as if the
+//         transitions had been taken one by one.
+//   bytes LDS per workgroup at DeepSea(30): 131 072 B of tables + 16 x 2 048 B of rings = 163 840 B, the whole CU.  HBM per
+//         launch of 65 536 x 30 000 transitions: 122 MB table image in, 524 MB code words out (8 B per episode chunk and
+//         instance), 488 MB departure image.
 // k_reward_scan -- lane = instance: the float64 reward sum in TRANSITION ORDER from the code words (bit-equal to the
-//         oracle's and every other kernel's sequential sum).  No LDS at all and <= 128 VGPRs: k_rollout_epi holds every byte
+//         oracle's and every other kernel's sequential sum).  It loads the code words in tiles of eight, three tiles in
+//         registers, and forms the packed step counts n1 | n2 << 11 | n3 << 22 of a word itself (k1e_code_counts_few for
+//         at most three reward codes, k1e_code_counts for four: one wave-uniform branch per tile); the words a lane has to add
+//         step by step are already in its registers.  No LDS at all and <= 128 VGPRs: k_rollout_epi holds every byte
 //         of the CU's LDS and 4 x 96 VGPRs per SIMD, and a wavefront of the scan still fits beside it.
 // Results: visit counts, final states, in-episode times, Philox counters and reward sums bit-equal to K1 / K1T / K1U and the
 // CPU oracle (tests/test_gpu_parity.py, tests/test_gpu_fullsize.py, tools/stress_k1t.py k1e, tools/fuzz_parity.py).
@@ -83,12 +93,12 @@ struct K1ePlan {
   int32_t debug;             // CMDP_K1E_DEBUG (timing experiments, results INVALID): 1 no walk, 2 no flush, 4 no Philox, 8 no code stores;
                              // 16 no round is interior (every round takes the general path; results VALID)
   int32_t fast;              // interior rounds take the short path (k1e_round_interior): set per launch, when bit 16 of `debug` is
-                             // clear and every byte offset into codes / cnts stays below 2^31 (32-bit lane offsets)
+                             // clear, every byte offset into codes stays below 2^31 (32-bit lane offsets) and the rings are
+                             // aligned (k1e_ring_aligned)
   const uint32_t* etab;      // [group of 32 instances][gdw >= S * 32]: one dword per state, successor words of action 0 (low half)
                              // and 1 (high half), s' << 7 | code; interleaved by instance like the LDS image
   const double* rvals;       // [n_codes]
   uint2* codes;              // [episode][chunk][B] 2-bit reward codes of the chunk's steps, step j at bits 2 j
-  uint32_t* cnts;            // [episode][chunk][B] steps of the chunk with reward code 1 | code 2 << 11 | code 3 << 22
   int32_t* seg_h0;           // [B] in-episode time at the start of the segment (k_reward_scan decodes the episodes with it)
   int2* dep;                 // [group][gdw] DEPARTURE counts (action 0, action 1) accumulated over launches, interleaved like
                              // the LDS image; k_epi_fold turns them into the reference's arrival counts when they are needed
@@ -101,6 +111,11 @@ __host__ __device__ inline size_t k1e_ring_bytes(const K1ePlan& p) { return (siz
 __host__ __device__ inline size_t k1e_lds_bytes(const K1ePlan& p) { return k1e_tab_bytes(p) + k1e_ring_bytes(p); }
 __host__ __device__ inline size_t k1e_fold_lds_bytes(const K1ePlan& p) { return (size_t)2 * K1E_NI * (size_t)p.S * 4; }
 __host__ __device__ inline int64_t k1e_max_episodes(int64_t n_steps, int H) { return (n_steps + 2 * (int64_t)H - 2) / H; }
+// Does every wavefront's ring start at a multiple of its own size (ring_blocks x 512 B)?  The rings follow the tables, both are
+// powers of two and the dynamic LDS starts at byte 0 (the kernel has no static LDS), so: when a ring is no larger than the
+// tables.  The lane's bank offset 4 i lies below bit 7, under every ring dword's address bits: an interior round then forms
+// a ring address as (128 d & ring mask) | (ring base + 4 i) -- one v_and_or_b32 -- where the general path masks and adds.
+__host__ __device__ inline bool k1e_ring_aligned(const K1ePlan& p) { return k1e_tab_bytes(p) % ((size_t)p.ring_blocks * 512) == 0; }
 
 // Is the round of eight episodes e_lo .. e_lo + 7 of a segment of n_steps transitions INTERIOR -- whatever the in-episode
 // time h0 in [0, H) the segment starts at, every one of the eight is walked at full length H, none is episode 0 of the
@@ -114,19 +129,23 @@ __host__ __device__ inline bool k1e_round_interior(int e_lo, int H, int64_t n_st
 }
 
 // steps of a code word (2-bit fields, unused fields zero) with code 1, 2, 3: n1 | n2 << 11 | n3 << 22 (11-bit fields: the
-// packed words of a 16-word tile add up without carries into the neighbouring field)
-// (at most three reward codes -- DeepSea: no field is 3, so the two bit planes ARE the counts of codes 1 and 2)
-__device__ __forceinline__ uint32_t k1e_code_counts3(uint32_t lo, uint32_t hi) {
-  const uint32_t n1 = __popc(lo & 0x55555555u) + __popc(hi & 0x55555555u);
-  const uint32_t n2 = __popc(lo & 0xaaaaaaaau) + __popc(hi & 0xaaaaaaaau);
-  return n1 | (n2 << 11);
+// packed words of a tile of the scan add up without carries into the neighbouring field).  k_reward_scan forms them from
+// the code words it loads -- the walk stores no counts.  Exported as cmdp_k1e_code_counts: the tests check the functions
+// the kernel uses.
+// (at most three reward codes -- DeepSea: no field is 3, so every set bit is a step of code 1 or 2 and the 0xaaaaaaaa planes
+// hold the steps of code 2: n1 + n2 = all bits, in the accumulating form of v_bcnt_u32_b32, and n1 | n2 << 11 =
+// (n1 + n2) + 2047 n2 -- six or seven instructions per word)
+__host__ __device__ __forceinline__ uint32_t k1e_code_counts_few(uint32_t lo, uint32_t hi) {
+  const uint32_t n12 = (uint32_t)__builtin_popcount(lo) + (uint32_t)__builtin_popcount(hi);
+  const uint32_t n2 = (uint32_t)__builtin_popcount(lo & 0xaaaaaaaau) + (uint32_t)__builtin_popcount(hi & 0xaaaaaaaau);
+  return n12 + 2047u * n2;
 }
-__device__ __forceinline__ uint32_t k1e_code_counts(uint32_t lo, uint32_t hi) {
+__host__ __device__ __forceinline__ uint32_t k1e_code_counts(uint32_t lo, uint32_t hi) {
   const uint32_t l0 = lo & 0x55555555u, l1 = (lo >> 1) & 0x55555555u;
   const uint32_t h0 = hi & 0x55555555u, h1 = (hi >> 1) & 0x55555555u;
-  const uint32_t n3 = __popc(l0 & l1) + __popc(h0 & h1);
-  const uint32_t n1 = __popc(l0 & ~l1) + __popc(h0 & ~h1);
-  const uint32_t n2 = __popc(~l0 & l1) + __popc(~h0 & h1);
+  const uint32_t n3 = (uint32_t)__builtin_popcount(l0 & l1) + (uint32_t)__builtin_popcount(h0 & h1);
+  const uint32_t n1 = (uint32_t)__builtin_popcount(l0 & ~l1) + (uint32_t)__builtin_popcount(h0 & ~h1);
+  const uint32_t n2 = (uint32_t)__builtin_popcount(~l0 & l1) + (uint32_t)__builtin_popcount(~h0 & h1);
   return n1 | (n2 << 11) | (n3 << 22);
 }
 
@@ -143,9 +162,6 @@ struct K1eGroupRegs {
   uint32_t hcs;   // in-episode time << 18 | current state << 9 | start state (S <= 512, H < 2^14: one register instead of three)
 };
 
-// FEW: at most three reward codes (the count word is then four population counts; computing both forms and selecting -- what
-// a run-time switch compiles to -- cost 1.5 VALU instructions per transition)
-template <bool FEW>
 __global__ void __launch_bounds__(K1E_THREADS) __attribute__((amdgpu_waves_per_eu(5, 5))) k_rollout_epi(EnvTables t, K1ePlan p, int n_steps,
                                                             int32_t* __restrict__ last_obs) {
   extern __shared__ __align__(16) unsigned char smem[];
@@ -309,8 +325,9 @@ __global__ void __launch_bounds__(K1E_THREADS) __attribute__((amdgpu_waves_per_e
           uint32_t ring_base = ring_sbase;
           asm volatile("" : "+v"(e0), "+s"(ring_base));
           e0 += e_lo;
-          const uint32_t ring_lane = lbase + ring_base;
+          const uint32_t ring_lane = lbase + ring_base;          // (a multiple of the ring's size + 4 i: p.fast)
           const uint32_t a00 = ntr_lo + (uint32_t)(e0 * H - h0);   // chain 0's first transition, as a stream position
+          const uint32_t o00 = a00 << 2;                            // ... and as 128 x its ring dword (+ bits below 7, masked off)
           uint32_t addv = 0x10000u, hcs = cur_regs.hcs;   // every chain counts ...
           asm volatile("" : "+v"(addv), "+v"(hcs));
           uint32_t w[K1E_EPL];
@@ -318,25 +335,26 @@ __global__ void __launch_bounds__(K1E_THREADS) __attribute__((amdgpu_waves_per_e
           for (int c = 0; c < K1E_EPL; ++c) w[c] = (hcs & 511u) << 7;   // ... and starts from the start state
           for (int ch = 0; ch < nch; ++ch) {
             const int L = __builtin_amdgcn_readfirstlane(min(32, H - 32 * ch));
-            // all eight ring reads of the four chains, then ONE wait (ring dword d at ring_lane + 128 d)
-            uint32_t a0[K1E_EPL], d0[K1E_EPL], d1[K1E_EPL], bits[K1E_EPL], clo[K1E_EPL], chi[K1E_EPL];
+            // all eight ring reads of the four chains, then ONE wait (ring dword d at ring_lane | (128 d & ring_mask)).
+            // Chain c's position is chain 0's plus a wave-uniform c H + 32 ch: per chain two additions of a scalar and two
+            // v_and_or_b32 for the addresses, one addition for the funnel shift (a0 mod 32: the chunk drops out)
+            uint32_t d0[K1E_EPL], d1[K1E_EPL], bits[K1E_EPL], clo[K1E_EPL], chi[K1E_EPL];
 #pragma unroll
             for (int c = 0; c < K1E_EPL; ++c) {
-              a0[c] = a00 + (uint32_t)(c * H + 32 * ch);
-              const uint32_t o = a0[c] << 2;
-              d0[c] = *(k1e_lds_u32)(uintptr_t)(ring_lane + (o & ring_mask));
-              d1[c] = *(k1e_lds_u32)(uintptr_t)(ring_lane + ((o + 128u) & ring_mask));
+              const uint32_t so = (uint32_t)__builtin_amdgcn_readfirstlane(4 * (c * H + 32 * ch));
+              d0[c] = *(k1e_lds_u32)(uintptr_t)(((o00 + so) & ring_mask) | ring_lane);
+              d1[c] = *(k1e_lds_u32)(uintptr_t)(((o00 + (so + 128u)) & ring_mask) | ring_lane);
             }
 #pragma unroll
             for (int c = 0; c < K1E_EPL; ++c) {
-              bits[c] = __builtin_bitreverse32(__builtin_amdgcn_alignbit(d1[c], d0[c], a0[c]));   // (the shift is a0 mod 32)
+              bits[c] = __builtin_bitreverse32(__builtin_amdgcn_alignbit(d1[c], d0[c], a00 + (uint32_t)(c * H)));
               clo[c] = 0u; chi[c] = 0u;
             }
             const int L0 = __builtin_amdgcn_readfirstlane(min(L, 16));
             walk_int(L0, L, bits, w, addv, clo, chi);
             if (!(p.debug & 8)) {
               const uint32_t wi = ((uint32_t)e0 * (uint32_t)nch + (uint32_t)ch) * (uint32_t)t.B + (uint32_t)b;
-              const uint32_t o8 = wi << 3, o4 = wi << 2;                 // (< 2^31: p.fast)
+              const uint32_t o8 = wi << 3;                               // (< 2^31: p.fast)
               const uint32_t cstride = (uint32_t)nch * (uint32_t)t.B;   // words between two consecutive episodes
 #pragma unroll
               for (int c = 0; c < K1E_EPL; ++c) {
@@ -349,11 +367,8 @@ __global__ void __launch_bounds__(K1E_THREADS) __attribute__((amdgpu_waves_per_e
                 // 64-bit vector additions per chain)
                 typedef __attribute__((address_space(1))) unsigned char* k1e_glb_u8;   // (global, not flat, stores)
                 k1e_glb_u8 cb = (k1e_glb_u8)(uintptr_t)p.codes + (size_t)((uint32_t)c * cstride) * 8;
-                k1e_glb_u8 nb4 = (k1e_glb_u8)(uintptr_t)p.cnts + (size_t)((uint32_t)c * cstride) * 4;
-                asm volatile("" : "+s"(cb), "+s"(nb4));
+                asm volatile("" : "+s"(cb));
                 __builtin_nontemporal_store(v, (__attribute__((address_space(1))) u32x2*)(cb + (size_t)o8));
-                __builtin_nontemporal_store(FEW ? k1e_code_counts3(lo, hi) : k1e_code_counts(lo, hi),
-                                            (__attribute__((address_space(1))) uint32_t*)(nb4 + (size_t)o4));
               }
             }
           }
@@ -435,7 +450,6 @@ __global__ void __launch_bounds__(K1E_THREADS) __attribute__((amdgpu_waves_per_e
                 u32x2 v;
                 v.x = lo; v.y = hi;
                 __builtin_nontemporal_store(v, reinterpret_cast<u32x2*>(p.codes) + wi);
-                __builtin_nontemporal_store(FEW ? k1e_code_counts3(lo, hi) : k1e_code_counts(lo, hi), p.cnts + wi);
               }
               wi += (uint32_t)nch * (uint32_t)t.B;
             }
@@ -460,7 +474,6 @@ __global__ void __launch_bounds__(K1E_THREADS) __attribute__((amdgpu_waves_per_e
             }
             const uint32_t wi = ((uint32_t)(e0 + c) * (uint32_t)nch + (uint32_t)(j0 >> 5)) * (uint32_t)t.B + (uint32_t)b;
             p.codes[wi] = make_uint2(lo, hi);
-            p.cnts[wi] = k1e_code_counts(lo, hi);
           }
           w[c] = ws;
         }
@@ -472,9 +485,11 @@ __global__ void __launch_bounds__(K1E_THREADS) __attribute__((amdgpu_waves_per_e
           const int hend = ((e0 + c) == 0 ? h0 : 0) + len_of(c);
           const bool term = hend >= H;
           const int32_t cur = term ? start : (int32_t)((w[c] & K1E_SMASK) >> 7);
-          t.cur[b] = cur;
-          t.hstep[b] = term ? 0 : hend;
-          if (last_obs) last_obs[b] = cur;
+          int b_o = b;
+          asm volatile("" : "+v"(b_o));   // (as in fetch_table: hoisted out of the pass loop the three 64-bit addresses sit under the whole walk)
+          t.cur[b_o] = cur;
+          t.hstep[b_o] = term ? 0 : hend;
+          if (last_obs) last_obs[b_o] = cur;
         }
       }
       __builtin_amdgcn_wave_barrier();
@@ -588,22 +603,26 @@ __global__ void __launch_bounds__(K1E_THREADS) k_epi_fold(EnvTables t, K1ePlan p
 // negative or a tie case -- the chunk is added step by step in float64, exactly as the oracle does, and (k, m, q) are
 // re-derived from the result.  An episode's code word holds the 2-bit reward codes of its steps, step j of a 32-step
 // chunk at bits 2 j of the 64-bit word (unused fields zero).
-// element `i` (run-time, per lane) of a register array of 16: a select tree instead of an LDS round trip -- the reward scan
+// element `i` (run-time, per lane) of a register array of 8: a select tree instead of an LDS round trip -- the reward scan
 // keeps NO tile in LDS, so that its wavefronts fit beside k_rollout_epi's workgroups (whose tables take the CU's LDS)
-typedef uint32_t k1r_u32x16 __attribute__((ext_vector_type(16)));   // (a vector value, not an array: it cannot end up in scratch)
-__device__ __forceinline__ uint32_t k1r_sel16(const k1r_u32x16 a, int i) {
-  const bool i0 = (i & 1) != 0, i1 = (i & 2) != 0, i2 = (i & 4) != 0, i3 = (i & 8) != 0;
+typedef uint32_t k1r_u32x8 __attribute__((ext_vector_type(8)));   // (a vector value, not an array: it cannot end up in scratch)
+__device__ __forceinline__ uint32_t k1r_sel8(const k1r_u32x8 a, int i) {
+  const bool i0 = (i & 1) != 0, i1 = (i & 2) != 0, i2 = (i & 4) != 0;
   const uint32_t b0 = i0 ? a[1] : a[0], b1 = i0 ? a[3] : a[2], b2 = i0 ? a[5] : a[4], b3 = i0 ? a[7] : a[6];
-  const uint32_t b4 = i0 ? a[9] : a[8], b5 = i0 ? a[11] : a[10], b6 = i0 ? a[13] : a[12], b7 = i0 ? a[15] : a[14];
-  const uint32_t c0 = i1 ? b1 : b0, c1 = i1 ? b3 : b2, c2 = i1 ? b5 : b4, c3 = i1 ? b7 : b6;
-  const uint32_t d0 = i2 ? c1 : c0, d1 = i2 ? c3 : c2;
-  return i3 ? d1 : d0;
+  const uint32_t c0 = i1 ? b1 : b0, c1 = i1 ? b3 : b2;
+  return i2 ? c1 : c0;
 }
 
 #define K1R_THREADS 64
-#define K1R_T 16   // code words per tile: the next tile's loads are in flight while a tile is summed
-// (<= 128 VGPRs and 32 B of LDS: a wavefront of the scan fits on every SIMD beside k_rollout_epi's workgroup -- 4 x 96 VGPRs
-// per SIMD, 147 840 B of LDS per CU -- so that the scan of one segment runs under the walk of the next)
+// The scan loads the CODE words (8 B) and counts the steps per code itself (k1e_code_counts_few / k1e_code_counts): the walk
+// is bound by VALU issue and the scan -- one wavefront per SIMD, hidden under the next walk -- takes the slots the walk leaves.
+// THREE tiles of EIGHT words: while one is summed, two are in flight (128 B per lane, what two tiles of sixteen 4-byte count
+// words were), and the tile being summed stays in registers for the step-by-step path: 3 x 16 registers of code words + 2 x 8
+// of prefix sums, where the count words took 2 x 16 + 2 x 16.
+#define K1R_T 8    // code words per tile
+#define K1R_D 3    // tiles in registers: one being summed, the others' loads in flight
+// (<= 128 VGPRs and NO LDS: a wavefront of the scan fits on every SIMD beside k_rollout_epi's workgroup -- 4 x 96 VGPRs
+// per SIMD, 163 840 B of LDS per CU -- so that the scan of one segment runs under the walk of the next)
 __global__ void __launch_bounds__(K1R_THREADS) __attribute__((amdgpu_waves_per_eu(4, 8))) k_reward_scan(EnvTables t, K1ePlan p, int64_t n_steps,
                                                             double* __restrict__ reward_sum, int accumulate) {
   const int lane = threadIdx.x;
@@ -633,7 +652,7 @@ __global__ void __launch_bounds__(K1R_THREADS) __attribute__((amdgpu_waves_per_e
   const int W = (int)(E * nch);   // code words of this instance, in order (a segment: < 2^31)
   typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
   const u32x2* csrc = reinterpret_cast<const u32x2*>(p.codes) + b;
-  const uint32_t* nsrc = p.cnts + b;
+  const bool few = p.n_codes <= 3;   // (wave-uniform: no field of a code word is 3)
   // integer form of the sum, valid while `kvalid`: S = m * 2^(kb - 1075) with 2^52 <= m < 2^53 (kb = biased exponent);
   // q[c] = round(rv[c] / spacing) as (low, high) halves; `tie`: codes whose presence forces the float64 path (a tie case in
   // this binade, a subnormal reward, a reward at or above 2^(k+1))
@@ -688,23 +707,40 @@ __global__ void __launch_bounds__(K1R_THREADS) __attribute__((amdgpu_waves_per_e
   int ep_left = e_len;                                 // ... not yet covered by earlier chunks
   int64_t tot_left = n_steps;                          // steps from the current episode's first one on
 
-  // two tiles of count words in flight (rnA, rnB alternate): one tile's sums cover about a third of an HBM round trip
-  uint32_t rnA[K1R_T], rnB[K1R_T];
+  // the code words w0 .. w0 + K1R_T - 1 of the lane's instance (low and high halves; past the end: zero, not loaded)
+  auto fetch = [&](k1r_u32x8& clo, k1r_u32x8& chi, const int w0) {
+    const u32x2* src = csrc + (size_t)w0 * t.B;
 #pragma unroll
-  for (int k = 0; k < K1R_T; ++k) {
-    rnA[k] = k < W ? __builtin_nontemporal_load(&nsrc[(size_t)k * t.B]) : 0u;
-    rnB[k] = K1R_T + k < W ? __builtin_nontemporal_load(&nsrc[(size_t)(K1R_T + k) * t.B]) : 0u;
-  }
-  auto tile = [&](uint32_t (&rn)[K1R_T], const int w0) {
+    for (int k = 0; k < K1R_T; ++k) {
+      u32x2 v = {0u, 0u};
+      if (w0 + k < W) v = __builtin_nontemporal_load(&src[(size_t)k * t.B]);
+      clo[k] = v.x; chi[k] = v.y;
+    }
+  };
+  // three tiles of code words (A, B, C in turn)
+  k1r_u32x8 loA, hiA, loB, hiB, loC, hiC;
+  fetch(loA, hiA, 0);
+  fetch(loB, hiB, K1R_T);
+  fetch(loC, hiC, 2 * K1R_T);
+  auto tile = [&](const k1r_u32x8& clo, const k1r_u32x8& chi, const int w0) {
+    // the packed counts of the tile's words
+    uint32_t rn[K1R_T];
+    if (few) {
+#pragma unroll
+      for (int k = 0; k < K1R_T; ++k) rn[k] = k1e_code_counts_few(clo[k], chi[k]);
+    } else {
+#pragma unroll
+      for (int k = 0; k < K1R_T; ++k) rn[k] = k1e_code_counts(clo[k], chi[k]);
+    }
     // prefix sums of the tile's packed counts and steps (0 steps: a chunk a partial episode does not reach, or past the end)
-    k1r_u32x16 P, SP;
+    k1r_u32x8 P, SP;
     // interior tiles of single-chunk episodes (all lanes): every word holds H steps
     const bool interior = nch == 1 && __all(w0 >= 1 && w0 + K1R_T <= W - 1);
     if (interior) {
       uint32_t acc = 0u;
 #pragma unroll
       for (int k = 0; k < K1R_T; ++k) { acc += rn[k]; P[k] = acc; SP[k] = (uint32_t)((k + 1) * H); }
-      tot_left -= (int64_t)K1R_T * H;   // sixteen full episodes on: the next one may be the segment's last, partial one
+      tot_left -= (int64_t)K1R_T * H;   // eight full episodes on: the next one may be the segment's last, partial one
       e_len = (int)min((int64_t)H, tot_left);
       ep_left = e_len;
     } else {
@@ -727,13 +763,6 @@ __global__ void __launch_bounds__(K1R_THREADS) __attribute__((amdgpu_waves_per_e
     const uint32_t Pt = P[K1R_T - 1], St = SP[K1R_T - 1];
     unsigned long long m2;
     const bool whole = advance(Pt, St, m2);
-    // the count words of the tile after the next (the code words of a word are fetched only when that word has to be added
-    // step by step)
-    {
-      const uint32_t* nn = nsrc + (size_t)(w0 + 2 * K1R_T) * t.B;
-#pragma unroll
-      for (int k = 0; k < K1R_T; ++k) rn[k] = (w0 + 2 * K1R_T + k < W) ? __builtin_nontemporal_load(&nn[(size_t)k * t.B]) : 0u;
-    }
     if (whole) { m = m2; return; }
     // ---- this lane: the first word that does not advance (binary search over the prefix sums: advancing is monotone --
     // q >= 0, and a forcing code stays present), everything before it in one piece, that word in float64 step by step
@@ -744,18 +773,19 @@ __global__ void __launch_bounds__(K1R_THREADS) __attribute__((amdgpu_waves_per_e
       if (advance(Pt - base_n, St - base_s, m2)) { m = m2; break; }
       int lo = from, hi = K1R_T - 1;
 #pragma unroll
-      for (int it = 0; it < 4; ++it) {   // 2^4 = K1R_T
+      for (int it = 0; it < 3; ++it) {   // 2^3 = K1R_T
         const int mid = (lo + hi) >> 1;
-        const bool ok = advance(k1r_sel16(P, mid) - base_n, k1r_sel16(SP, mid) - base_s, m2);
+        const bool ok = advance(k1r_sel8(P, mid) - base_n, k1r_sel8(SP, mid) - base_s, m2);
         if (lo < hi) { if (ok) lo = mid + 1; else hi = mid; }
       }
       const int k = lo;
-      const uint32_t Sk1 = k > 0 ? k1r_sel16(SP, k - 1) : 0u;
-      if (k > from && advance(k1r_sel16(P, k - 1) - base_n, Sk1 - base_s, m2)) m = m2;
-      const uint32_t Sk = k1r_sel16(SP, k);
+      const uint32_t Sk1 = k > 0 ? k1r_sel8(SP, k - 1) : 0u;
+      if (k > from && advance(k1r_sel8(P, k - 1) - base_n, Sk1 - base_s, m2)) m = m2;
+      const uint32_t Sk = k1r_sel8(SP, k);
       const uint32_t L = Sk - Sk1;
       if (L) {
-        const u32x2 c = csrc[(size_t)(w0 + k) * t.B];
+        u32x2 c;   // (the word is in registers: the tile is reloaded only when it is done)
+        c.x = k1r_sel8(clo, k); c.y = k1r_sel8(chi, k);
         if (kvalid) S = compose();
         // (step by step exactly as the oracle adds, but for the steps whose reward is +0.0 -- x + 0.0 == x, the sum is never
         // -0.0 -- which are skipped: the scaled minimum reward is 0, half of DeepSea's steps.  The reward of a code by a
@@ -785,14 +815,23 @@ __global__ void __launch_bounds__(K1R_THREADS) __attribute__((amdgpu_waves_per_e
         }
         rebase();
       }
-      base_n = k1r_sel16(P, k);
+      base_n = k1r_sel8(P, k);
       base_s = Sk;
       from = k + 1;
     }
   };
-  for (int w0 = 0; w0 < W; w0 += 2 * K1R_T) {
-    tile(rnA, w0);
-    if (w0 + K1R_T < W) tile(rnB, w0 + K1R_T);
+  // (a tile's registers take the words K1R_D tiles on as soon as it is summed)
+  for (int w0 = 0; w0 < W; w0 += K1R_D * K1R_T) {
+    tile(loA, hiA, w0);
+    fetch(loA, hiA, w0 + K1R_D * K1R_T);
+    if (w0 + K1R_T < W) {
+      tile(loB, hiB, w0 + K1R_T);
+      fetch(loB, hiB, w0 + (K1R_D + 1) * K1R_T);
+    }
+    if (w0 + 2 * K1R_T < W) {
+      tile(loC, hiC, w0 + 2 * K1R_T);
+      fetch(loC, hiC, w0 + (K1R_D + 2) * K1R_T);
+    }
   }
   if (kvalid) S = compose();
   if (mine) reward_sum[b] = S;

@@ -168,6 +168,11 @@ const char* cmdp_last_error(void);
    The very predicate k_rollout_epi branches on (such rounds skip the per-chain bookkeeping); needs no handle and no device.
    No reference counterpart. */
 int cmdp_k1e_round_interior(int e_lo, int horizon, int64_t n_steps, int n_instances);
+/* K1E: the packed step counts n1 | n2 << 11 | n3 << 22 of a 64-bit code word (lo, hi): 32 two-bit reward codes, unused fields
+   zero; n_c = fields equal to c.  few != 0: the form k_reward_scan uses for batches with at most three reward codes (valid
+   only when no field is 3), else its four-code form.  The very functions the kernel calls; needs no handle and no device.
+   No reference counterpart. */
+uint32_t cmdp_k1e_code_counts(uint32_t lo, uint32_t hi, int few);
 int cmdp_device_count(void);
 int cmdp_set_device(int device);
 

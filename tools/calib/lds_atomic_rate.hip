@@ -3,7 +3,10 @@
 //      i & 31), 16 wavefronts per CU, EPL independent operations in flight per wavefront;
 //  (2) the walk's step itself -- v_bfe_u32 . v_lshl_or_b32 . v_and_or_b32 . ds_add_rtn_u32 . v_alignbit_b32, EPL chains per lane,
 //      16 wavefronts of 1024 threads per CU on a 128-KB table -- as cycles per wave-transition per SIMD: the rate
-//      k_rollout_epi's fast loop could reach if nothing else ran.
+//      k_rollout_epi's fast loop could reach if nothing else ran;
+//  (3) the same step written chain after chain (alignbit . add_co . cndmask . and_or . ds_add_rtn, a scheduling barrier after
+//      each atomic): same instructions, but a chain's next atomic goes out as soon as ITS previous one is back (s_waitcnt
+//      lgkmcnt(EPL - 1)) instead of after all EPL (lgkmcnt(0)).  Both forms are run three times in turn: the spread.
 //   hipcc --offload-arch=gfx950 -O3 -o lds_atomic_rate lds_atomic_rate.hip && ./lds_atomic_rate
 #include <hip/hip_runtime.h>
 #include <cstdio>
@@ -47,6 +50,18 @@ __global__ void __launch_bounds__(1024) k_walk(uint32_t* out, int iters, uint32_
     for (int j = 0; j < 32; j += 2) {
 #pragma unroll
       for (int u = 0; u < 2; ++u) {
+        if (FORM == 3) {   // (3): chain after chain; the code of a chain's PREVIOUS step is taken when its next one is formed
+#pragma unroll
+          for (int c = 0; c < EPL; ++c) {
+            uint32_t t, ra1;
+            cw[c] = __builtin_amdgcn_alignbit(w[c], cw[c], 2u);
+            asm volatile("v_add_co_u32 %0, vcc, %0, %0\n\tv_cndmask_b32 %1, %2, %3, vcc" : "+v"(bits[c]), "=v"(t) : "v"(x0), "v"(x1) : "vcc");
+            asm("v_and_or_b32 %0, %1, %2, %3" : "=v"(ra1) : "v"(w[c]), "s"(0xff80u), "v"(t));
+            w[c] = __hip_atomic_fetch_add((lds_u32)(uintptr_t)ra1, 0x10000u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            __builtin_amdgcn_sched_barrier(0);
+          }
+          continue;
+        }
         uint32_t ra[EPL];
 #pragma unroll
         for (int c = 0; c < EPL; ++c) {
@@ -100,6 +115,7 @@ int main() {
   hipFuncSetAttribute((const void*)k_walk<4, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
   hipFuncSetAttribute((const void*)k_walk<4, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
   hipFuncSetAttribute((const void*)k_walk<4, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+  hipFuncSetAttribute((const void*)k_walk<4, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
   hipFuncSetAttribute((const void*)k_walk<2, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
   hipFuncSetAttribute((const void*)k_walk<6, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
   hipFuncSetAttribute((const void*)k_walk<8, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
@@ -122,6 +138,10 @@ int main() {
   report("walk step, 4 chains, bfe.lshl_or.and_or", timed([&] { hipLaunchKernelGGL((k_walk<4, 0>), dim3(cus), dim3(1024), lds, 0, out, it2, 16u); }), 4);
   report("walk step, 4 chains, compiler's choice", timed([&] { hipLaunchKernelGGL((k_walk<4, 1>), dim3(cus), dim3(1024), lds, 0, out, it2, 16u); }), 4);
   report("walk step, 4 chains, add_co.cndmask.and_or", timed([&] { hipLaunchKernelGGL((k_walk<4, 2>), dim3(cus), dim3(1024), lds, 0, out, it2, 16u); }), 4);
+  for (int rep = 0; rep < 3; ++rep) {
+    report("walk step, 4 chains, add_co.cndmask.and_or", timed([&] { hipLaunchKernelGGL((k_walk<4, 2>), dim3(cus), dim3(1024), lds, 0, out, it2, 16u); }), 4);
+    report("walk step, 4 chains, the same per chain", timed([&] { hipLaunchKernelGGL((k_walk<4, 3>), dim3(cus), dim3(1024), lds, 0, out, it2, 16u); }), 4);
+  }
   report("walk step, 2 chains, bfe.lshl_or.and_or", timed([&] { hipLaunchKernelGGL((k_walk<2, 0>), dim3(cus), dim3(1024), lds, 0, out, it2, 16u); }), 2);
   report("walk step, 6 chains, bfe.lshl_or.and_or", timed([&] { hipLaunchKernelGGL((k_walk<6, 0>), dim3(cus), dim3(1024), lds, 0, out, it2, 16u); }), 6);
   report("walk step, 8 chains, bfe.lshl_or.and_or", timed([&] { hipLaunchKernelGGL((k_walk<8, 0>), dim3(cus), dim3(1024), lds, 0, out, it2, 16u); }), 8);
