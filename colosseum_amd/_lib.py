@@ -46,6 +46,12 @@ ROLLOUT_AUTO, ROLLOUT_GLOBAL, ROLLOUT_LDS, ROLLOUT_LDS_STOCHASTIC = 0, 1, 2, 3
 ROLLOUT_LDS_TEMPLATE = 4  # K1T: K1P with one successor table per workgroup (batches of action-permuted copies of one MDP)
 ROLLOUT_LDS_TEMPLATE_STREAM = 5  # K1U: K1T with the trace streamed to HBM and histogrammed afterwards (256 instances per CU)
 ROLLOUT_EPISODE_PARALLEL = 6  # K1E: lane = (instance, episode): episodic batches with two actions walk their episodes in parallel
+# cmdp_k1s_plan / cmdp_k1s_plan_desc: the fields in the order of include/cmdp.h, and the names of `form` (the compiled form of
+# K1S's walk loop: generic, or team * 4 + reward source)
+K1S_PLAN_FIELDS = ("ok", "G", "nw", "gw", "team", "U", "n_pat", "n_codes", "reward_mode", "rc_packed", "n_shapes", "shape_bytes",
+                   "ch", "form")
+K1S_REWARD_SOURCES = ("packed", "state_table", "row")
+K1S_FORMS = {0: "generic", **{t * 4 + i: f"team{t}_{src}" for t in (16, 8, 1) for i, src in enumerate(K1S_REWARD_SOURCES)}}
 
 EXPORTS = [
     "cmdp_version", "cmdp_build_id", "cmdp_last_error", "cmdp_device_count", "cmdp_set_device", "cmdp_create", "cmdp_destroy",
@@ -59,7 +65,7 @@ EXPORTS = [
     "cmdp_ucrl2_set_option",
     "cmdp_psrl_create", "cmdp_psrl_destroy", "cmdp_psrl_run", "cmdp_psrl_layout", "cmdp_psrl_model", "cmdp_psrl_last_sample",
     "cmdp_psrl_reference_sample", "cmdp_vi_episodic_dense", "cmdp_psrl_episode_end_update", "cmdp_k1e_round_interior",
-    "cmdp_k1e_code_counts",
+    "cmdp_k1e_code_counts", "cmdp_k1s_plan", "cmdp_k1s_plan_desc",
 ]
 
 
@@ -224,6 +230,8 @@ def load():
         L.cmdp_vi_episodic_dense.argtypes = [i32, vp, vp, i32, vp, vp, vp, vp]
         L.cmdp_k1e_round_interior.argtypes = [i32, i32, i64, i32]
         L.cmdp_k1e_code_counts.argtypes = [C.c_uint32, C.c_uint32, i32]
+        L.cmdp_k1s_plan.argtypes = [vp, vp]
+        L.cmdp_k1s_plan_desc.argtypes = [C.POINTER(CmdpDesc), i32, i32, vp]
         L.cmdp_k1e_code_counts.restype = C.c_uint32
         _lib = L
     return _lib

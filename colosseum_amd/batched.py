@@ -59,6 +59,51 @@ def tables_from_models(models: Sequence[TabularModel], with_env: bool = True, wi
     return t
 
 
+def desc_from_tables(tables: dict, rng_mode: int, philox_keys=None, layout: int = L.LAYOUT_CSR, flags: int = 0):
+    """The `cmdp_desc` of concatenated tables, and the arrays it points into (to be kept alive as long as it is used)."""
+    B, A = int(tables["B"]), int(tables["A"])
+    rr = tables["rewards_range"]
+    keep = {}
+    d = L.CmdpDesc()
+    d.n_instances, d.n_actions, d.horizon, d.rng_mode, d.layout = B, A, int(tables["H"]), rng_mode, layout
+    d.flags = int(flags)
+    d.reward_min, d.reward_max = float(rr[0]), float(rr[1])
+    keep["state_off"] = np.ascontiguousarray(tables["state_off"], np.int64)
+    if "sp_ptr" in tables:
+        for k, dt in _ENV_FIELDS:
+            if k in ("sp_rp0", "sp_rp1") and k not in tables:
+                continue  # optional: only read for Beta entries
+            keep[k] = np.ascontiguousarray(tables[k], dt)
+        if philox_keys is None:
+            philox_keys = np.arange(B, dtype=np.uint64)
+        keep["philox_key"] = np.ascontiguousarray(philox_keys, np.uint64)
+        assert len(keep["philox_key"]) == B
+    if "csr_ptr" in tables:
+        for k, dt in _DP_FIELDS:
+            keep[k] = np.ascontiguousarray(tables[k], dt)
+    for k, v in keep.items():
+        setattr(d, k, L.ptr(v))
+    return d, keep
+
+
+def _k1s_plan_dict(out) -> dict:
+    plan = {k: int(v) for k, v in zip(L.K1S_PLAN_FIELDS, out)}
+    plan["ok"] = bool(plan["ok"])
+    plan["form"] = L.K1S_FORMS[plan["form"]] if plan["ok"] else None
+    return plan
+
+
+def k1s_plan_of_tables(tables: dict, cus: int = 256, instances_per_workgroup: int = 0, rng_mode: int = L.RNG_PHILOX,
+                       layout: int = L.LAYOUT_CSR, flags: int = 0) -> dict:
+    """The K1S plan a `BatchedMDP(tables=tables, ...)` would get on a device of `cus` compute units (cmdp_k1s_plan_desc: host
+    only, needs no GPU); instances_per_workgroup stands for CMDP_K1S_G (0: planned).  Keys as `BatchedMDP.k1s_plan`."""
+    d, keep = desc_from_tables(tables, rng_mode, None, layout, flags)
+    out = np.zeros(len(L.K1S_PLAN_FIELDS), np.int32)
+    L.check(L.load().cmdp_k1s_plan_desc(C.byref(d), int(cus), int(instances_per_workgroup), L.ptr(out)))
+    del keep
+    return _k1s_plan_dict(out)
+
+
 class BatchedMDP:
     def __init__(self, models: Optional[Sequence[TabularModel]] = None, rng_mode: int = L.RNG_MT_COMPAT,
                  philox_keys: Optional[Sequence[int]] = None, with_env: bool = True, with_dp: bool = True,
@@ -79,26 +124,7 @@ class BatchedMDP:
         self.n_states = np.diff(self.state_off)
         self.row_off = self.state_off * A
         self.rng_mode = rng_mode
-        keep = {}
-        d = L.CmdpDesc()
-        d.n_instances, d.n_actions, d.horizon, d.rng_mode, d.layout = self.B, A, self.H, rng_mode, layout
-        d.flags = int(flags)
-        d.reward_min, d.reward_max = float(rr[0]), float(rr[1])
-        keep["state_off"] = self.state_off
-        if "sp_ptr" in tables:
-            for k, dt in _ENV_FIELDS:
-                if k in ("sp_rp0", "sp_rp1") and k not in tables:
-                    continue  # optional: only read for Beta entries
-                keep[k] = np.ascontiguousarray(tables[k], dt)
-            if philox_keys is None:
-                philox_keys = np.arange(self.B, dtype=np.uint64)
-            keep["philox_key"] = np.ascontiguousarray(philox_keys, np.uint64)
-            assert len(keep["philox_key"]) == self.B
-        if "csr_ptr" in tables:
-            for k, dt in _DP_FIELDS:
-                keep[k] = np.ascontiguousarray(tables[k], dt)
-        for k, v in keep.items():
-            setattr(d, k, L.ptr(v))
+        d, keep = desc_from_tables(tables, rng_mode, philox_keys, layout, flags)
         self._keep = keep
         self._h = C.c_void_p()
         L.check(lib.cmdp_create(C.byref(self._h), C.byref(d)))
@@ -214,6 +240,14 @@ class BatchedMDP:
         return dict(eligible=bool(plan[0]), kernel={0: "k_rollout_lds", 1: "k_rollout_pipe", 2: "k_rollout_stoch", 3: "k_rollout_tmpl",
                                                        4: "k_rollout_tmpl_stream", 5: "k_rollout_epi"}[int(plan[1])],
                     instances_per_workgroup=int(plan[2]), chunk=int(plan[3]))
+
+    def k1s_plan(self) -> dict:
+        """The plan of the stochastic-dynamics rollout K1S made for this batch (cmdp_k1s_plan): ok, G, nw, gw, team, U, n_pat,
+        n_codes, reward_mode, rc_packed, n_shapes, shape_bytes, ch and `form`, the compiled form of the walk loop the kernel
+        takes ("generic" or "team<16|8|1>_<packed|state_table|row>"; None when the batch is not eligible)."""
+        out = np.zeros(len(L.K1S_PLAN_FIELDS), np.int32)
+        L.check(self._lib.cmdp_k1s_plan(self._h, L.ptr(out)))
+        return _k1s_plan_dict(out)
 
     def set_option(self, option: int, value: int):
         L.check(self._lib.cmdp_set_option(self._h, int(option), int(value)))

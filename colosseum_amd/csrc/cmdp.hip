@@ -593,7 +593,7 @@ static int install_rollout_plans(cmdp_t* h, const cmdp_desc* d, const std::vecto
   if (table_rewards && h->n_slots == 0 && det_tables(in, &t)) lp = plan_k1lp(in, t, knobs);
   if (!lp.ok) {
     if (!table_rewards || h->rng_mode != CMDP_RNG_PHILOX || h->layout != CMDP_LAYOUT_CSR) return CMDP_OK;
-    K1sChoice ks = plan_k1s(in);
+    K1sChoice ks = plan_k1s(in, knobs);
     return ks.ok ? install_k1s(h, &ks) : CMDP_OK;
   }
   K1tChoice kt = plan_k1t(in, t, lp, knobs);
@@ -1476,6 +1476,68 @@ int cmdp_lds_plan(cmdp_t* h, int32_t plan[4]) {
                      : h->lds_ok ? k1lp : h->k1s_ok ? k1s : none;   // (K1L / K1P / K1S: the batch's only LDS-resident kernel)
   plan[0] = (h->lds_ok || h->k1s_ok) ? 1 : 0;
   std::copy(p, p + 3, plan + 1);
+  return CMDP_OK;
+}
+
+// cmdp_k1s_plan / cmdp_k1s_plan_desc: the fields of a K1S plan in the order include/cmdp.h gives
+static void k1s_plan_report(bool ok, const K1sPlan& p, int32_t out[CMDP_K1S_PLAN_FIELDS]) {
+  std::fill(out, out + CMDP_K1S_PLAN_FIELDS, 0);
+  if (!ok) return;
+  const int32_t v[CMDP_K1S_PLAN_FIELDS] = {1, p.G, p.nw, p.gw, p.team, p.U, p.n_pat, p.n_codes, p.reward_mode, p.rc_packed, p.n_shapes,
+                                           p.shape_bytes, p.ch, k1s_walk_form(p.n_pat, p.shape_bytes, p.team, p.rc_packed, p.reward_mode)};
+  std::copy(v, v + CMDP_K1S_PLAN_FIELDS, out);
+}
+
+int cmdp_k1s_plan(cmdp_t* h, int32_t out[CMDP_K1S_PLAN_FIELDS]) {
+  if (!h || !out) return fail(CMDP_ERR_INVALID, "bad argument");
+  k1s_plan_report(h->k1s_ok, h->k1s, out);
+  return CMDP_OK;
+}
+
+int cmdp_k1s_plan_desc(const cmdp_desc* d, int cus, int instances_per_workgroup, int32_t out[CMDP_K1S_PLAN_FIELDS]) {
+  if (!d || !out || cus < 1 || instances_per_workgroup < 0) return fail(CMDP_ERR_INVALID, "bad argument");
+  if (d->n_instances < 1 || d->n_actions < 1 || !d->state_off || !d->sp_ptr || !d->sp_next || !d->sp_cum || !d->sp_reward ||
+      !d->start_off)
+    return fail(CMDP_ERR_INVALID, "cmdp_k1s_plan_desc needs the sampler half of the description");
+  // as much of cmdp_create's validation as the planners index by
+  const int B = d->n_instances, A = d->n_actions;
+  int max_S = 0;
+  if (d->state_off[0] != 0 || d->sp_ptr[0] != 0 || d->start_off[0] != 0) return fail(CMDP_ERR_INVALID, "offsets do not start at 0");
+  for (int b = 0; b < B; ++b) {
+    const int64_t S = d->state_off[b + 1] - d->state_off[b];
+    if (S < 1 || S > (1 << 28)) return fail(CMDP_ERR_INVALID, "instance %d has %lld states", b, (long long)S);
+    if (d->start_off[b + 1] - d->start_off[b] < 1) return fail(CMDP_ERR_INVALID, "instance %d has no starting state", b);
+    max_S = std::max<int>(max_S, (int)S);
+  }
+  const int64_t R = d->state_off[B] * A;
+  std::vector<RowDesc> rows((size_t)R);
+  bool any_beta = false;
+  for (int b = 0; b < B; ++b) {
+    const int64_t S = d->state_off[b + 1] - d->state_off[b];
+    for (int64_t r = d->state_off[b] * A; r < d->state_off[b + 1] * A; ++r) {
+      const int64_t lo = d->sp_ptr[r], n = d->sp_ptr[r + 1] - lo;
+      if (n < 1 || n > 4096) return fail(CMDP_ERR_INVALID, "row %lld has %lld successors", (long long)r, (long long)n);
+      for (int64_t e = lo; e < lo + n; ++e) {
+        if (d->sp_next[e] < 0 || d->sp_next[e] >= S) return fail(CMDP_ERR_INVALID, "successor index out of range at entry %lld", (long long)e);
+        any_beta |= d->sp_rkind && d->sp_rkind[e] != 0;
+      }
+      RowDesc rd{};
+      rd.n = (int32_t)n;
+      rd.next_if_det = d->sp_next[lo];
+      rd.reward_if_det = d->sp_reward[lo];
+      rows[(size_t)r] = rd;
+    }
+  }
+  // cmdp_create plans K1S for the Philox batches with table rewards that K1L / K1P refuse (install_rollout_plans)
+  const PlanInput in{d, rows.data(), B, A, d->horizon, max_S, cus};
+  PlanKnobs knobs;
+  knobs.k1s_G = instances_per_workgroup;
+  K1sChoice ks;
+  const bool table_rewards = !any_beta || (d->flags & (CMDP_FLAG_REWARD_MEANS | CMDP_FLAG_REWARD_CACHE)) == CMDP_FLAG_REWARD_MEANS;
+  DetTables t;
+  if (table_rewards && d->rng_mode == CMDP_RNG_PHILOX && d->layout == CMDP_LAYOUT_CSR && !(det_tables(in, &t) && plan_k1lp(in, t, knobs).ok))
+    ks = plan_k1s(in, knobs);
+  k1s_plan_report(ks.ok, ks.p, out);
   return CMDP_OK;
 }
 

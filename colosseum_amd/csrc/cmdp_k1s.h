@@ -59,6 +59,17 @@ __host__ __device__ inline size_t k1s_fixed_bytes(int n_pat, int n_shapes) {
 }
 __host__ __device__ inline size_t k1s_ring_bytes(int ch) { return (size_t)2 * (8 * ch + ch); }  // per instance: uniforms + actions, 2 buffers
 
+// Which compiled form of the walk loop a plan takes: K1S_FORM_GENERIC, or team * 4 + reward source (0: code packed into the
+// successor-set entries, 1: per-state table, 2: per row, from the shape's dictionary entry) for the nine specialised forms
+// -- one pattern, one shape byte, teams of 16, 8 or 1.  The kernel's dispatch and the host's plan query (cmdp_k1s_plan)
+// both call it.
+#define K1S_FORM_GENERIC 0
+__host__ __device__ inline int k1s_reward_source(int rc_packed, int reward_mode) { return rc_packed ? 0 : (reward_mode == 0 ? 1 : 2); }
+__host__ __device__ inline int k1s_walk_form(int n_pat, int shape_bytes, int team, int rc_packed, int reward_mode) {
+  if (n_pat != 1 || shape_bytes != 1 || !(team == 16 || team == 8 || team == 1)) return K1S_FORM_GENERIC;
+  return team * 4 + k1s_reward_source(rc_packed, reward_mode);
+}
+
 __global__ void __launch_bounds__(K1S_THREADS) k_rollout_stoch(EnvTables t, K1sPlan p, int64_t n_steps,
                                                               double* __restrict__ reward_sum, int32_t* __restrict__ last_obs) {
   extern __shared__ __align__(16) unsigned char k1s_smem[];
@@ -200,7 +211,7 @@ __global__ void __launch_bounds__(K1S_THREADS) k_rollout_stoch(EnvTables t, K1sP
         const int Tn = TT ? TT : T;
         const int En = K1S_MAXE / Tn;
         const bool one_pat = OPc < 0 ? (p.n_pat == 1) : (OPc != 0);
-        const int rmode = RMc < 0 ? (p.rc_packed ? 0 : (p.reward_mode == 0 ? 1 : 2)) : RMc;   // 0 packed, 1 per state, 2 per row
+        const int rmode = RMc < 0 ? k1s_reward_source(p.rc_packed, p.reward_mode) : RMc;   // 0 packed, 1 per state, 2 per row
         const int sby = (TT && OPc >= 0) ? 1 : SBY;   // the specialised forms are instantiated for one shape byte
         const unsigned long long tmask = (Tn == 64) ? ~0ull : ((1ull << Tn) - 1ull);
         const int tshift = team * Tn;
@@ -289,13 +300,17 @@ __global__ void __launch_bounds__(K1S_THREADS) k_rollout_stoch(EnvTables t, K1sP
       using I8 = std::integral_constant<int, 8>;
       using I16 = std::integral_constant<int, 16>;
       using IR = std::integral_constant<int, -1>;
-      const int rm = p.rc_packed ? 0 : (p.reward_mode == 0 ? 1 : 2);
-      if (p.n_pat == 1 && SBY == 1 && (T == 16 || T == 8 || T == 1)) {
-        if (T == 16) { if (rm == 0) walk(I16{}, I1{}, I0{}); else if (rm == 1) walk(I16{}, I1{}, I1{}); else walk(I16{}, I1{}, I2{}); }
-        else if (T == 8) { if (rm == 0) walk(I8{}, I1{}, I0{}); else if (rm == 1) walk(I8{}, I1{}, I1{}); else walk(I8{}, I1{}, I2{}); }
-        else { if (rm == 0) walk(I1{}, I1{}, I0{}); else if (rm == 1) walk(I1{}, I1{}, I1{}); else walk(I1{}, I1{}, I2{}); }
-      } else {
-        walk(I0{}, IR{}, IR{});
+      switch (k1s_walk_form(p.n_pat, SBY, T, p.rc_packed, p.reward_mode)) {
+        case 16 * 4 + 0: walk(I16{}, I1{}, I0{}); break;
+        case 16 * 4 + 1: walk(I16{}, I1{}, I1{}); break;
+        case 16 * 4 + 2: walk(I16{}, I1{}, I2{}); break;
+        case 8 * 4 + 0: walk(I8{}, I1{}, I0{}); break;
+        case 8 * 4 + 1: walk(I8{}, I1{}, I1{}); break;
+        case 8 * 4 + 2: walk(I8{}, I1{}, I2{}); break;
+        case 1 * 4 + 0: walk(I1{}, I1{}, I0{}); break;
+        case 1 * 4 + 1: walk(I1{}, I1{}, I1{}); break;
+        case 1 * 4 + 2: walk(I1{}, I1{}, I2{}); break;
+        default: walk(I0{}, IR{}, IR{}); break;
       }
     }
     done += len;

@@ -37,6 +37,7 @@ struct PlanInput {
 struct PlanKnobs {
   int pipe = -1;               // CMDP_K1L_PIPE: 0 plans K1L only, 1 K1P only
   int k1t_G = 0, k1u_G = 0;    // CMDP_K1T_G / CMDP_K1U_G: instances per workgroup (0: planned)
+  int k1s_G = 0;               // CMDP_K1S_G: likewise for K1S (walker wavefronts and team size follow from it)
   int k1t_debug = 0, k1e_debug = 0;   // CMDP_K1T_DEBUG / CMDP_K1E_DEBUG: stages switched off (timing experiments only)
 };
 inline PlanKnobs plan_knobs() {
@@ -45,6 +46,7 @@ inline PlanKnobs plan_knobs() {
   k.pipe = num("CMDP_K1L_PIPE", -1);
   k.k1t_G = std::getenv("CMDP_K1T_G") ? std::max(1, num("CMDP_K1T_G", 0)) : 0;
   k.k1u_G = std::getenv("CMDP_K1U_G") ? std::max(1, num("CMDP_K1U_G", 0)) : 0;
+  k.k1s_G = std::getenv("CMDP_K1S_G") ? std::max(1, num("CMDP_K1S_G", 0)) : 0;
   k.k1t_debug = num("CMDP_K1T_DEBUG", 0);
   k.k1e_debug = num("CMDP_K1E_DEBUG", 0);
   return k;
@@ -335,7 +337,7 @@ struct K1sChoice {
   std::vector<double> patterns, rvals;
 };
 
-inline K1sChoice plan_k1s(const PlanInput& in) {
+inline K1sChoice plan_k1s(const PlanInput& in, const PlanKnobs& knobs) {
   K1sChoice c;
   const cmdp_desc* d = in.d;
   const int B = in.B, A = in.A;
@@ -439,7 +441,7 @@ inline K1sChoice plan_k1s(const PlanInput& in) {
   const size_t per = (size_t)p.slot_bytes + k1s_ring_bytes(p.ch);
   if (fixed + 4 * per > (size_t)kLdsBudget) return c;   // fewer than four instances per CU: not worth it
   const int cap = (int)std::min<size_t>(64, ((size_t)kLdsBudget - fixed) / per);
-  p.G = even_groups(B, cap, in.cus).G;
+  p.G = knobs.k1s_G ? std::min(cap, knobs.k1s_G) : even_groups(B, cap, in.cus).G;
   // walker wavefronts and lanes per instance in them.  Round 2 (ONE walker wavefront; FrozenLake-20 / MiniGrid-8 /
   // DeepSea-20 with p_rand, G = 8 / 11 / 22): teams of 8 (two entries per lane, two ballots) +19 %; teams of 4 (four
   // ballots) -3 %; of 2 -31 % against a lane per instance counting its 16 entries itself -- so teams only where a lane

@@ -347,6 +347,25 @@ int cmdp_set_option(cmdp_t* h, int option, int64_t value);
    rounds of workgroups x measured time per transition). */
 int cmdp_lds_plan(cmdp_t* h, int32_t plan[4]);
 
+/* The plan of the stochastic-dynamics rollout K1S (csrc/cmdp_k1s.h) that cmdp_create made for this handle (introspection for
+   tests; makes no HIP call; no reference counterpart).  out, in this order: ok (1 when the batch is eligible for K1S: every
+   other field is 0 otherwise), G (instances per workgroup), nw (walker wavefronts), gw (instances per walker wavefront), team
+   (lanes per instance), U (successor-set slots per state), n_pat (cumulative-probability patterns), n_codes (distinct reward
+   values), reward_mode (0: the reward is a function of the successor state, 1: of the row), rc_packed (mode 0: the code
+   travels in the successor-set entries, no per-state table), n_shapes (row shapes), shape_bytes (1 or 2 per row), ch
+   (transitions per chunk), form (the compiled form of the walk loop the kernel's dispatch takes: 0 the generic form, else
+   team * 4 + reward source for the nine specialised ones -- one pattern, one shape byte, team 16 / 8 / 1; source 0: packed
+   code, 1: per-state table, 2: per row -- computed by the very function the kernel branches on).
+   The environment variable CMDP_K1S_G, read by cmdp_create like CMDP_K1T_G and CMDP_K1U_G, sets G to min(LDS capacity, value);
+   nw, gw and team follow from G as they do for a planned G. */
+#define CMDP_K1S_PLAN_FIELDS 14
+int cmdp_k1s_plan(cmdp_t* h, int32_t out[CMDP_K1S_PLAN_FIELDS]);
+/* The same for a bare description, without a handle and without a device: what cmdp_create would plan for `desc` on a device
+   of `cus` compute units (only the sampler half is read; philox_key and the seeds are not).  instances_per_workgroup: 0 for
+   the planned G, else what CMDP_K1S_G would be set to (the environment is not read).  CMDP_ERR_INVALID for a description
+   cmdp_create would reject before planning (offsets, successor indices, row lengths). */
+int cmdp_k1s_plan_desc(const cmdp_desc* desc, int cus, int instances_per_workgroup, int32_t out[CMDP_K1S_PLAN_FIELDS]);
+
 /* BaseMDP.get_visitation_counts / reset_visitation_counts (colosseum/mdp/base.py:1357-1382).
    state_counts [state_off[B]], sa_counts [state_off[B]*A]; either may be NULL. */
 int cmdp_visits(cmdp_t* h, int64_t* state_counts, int64_t* sa_counts);
