@@ -65,7 +65,7 @@ EXPORTS = [
     "cmdp_ucrl2_set_option",
     "cmdp_psrl_create", "cmdp_psrl_destroy", "cmdp_psrl_run", "cmdp_psrl_layout", "cmdp_psrl_model", "cmdp_psrl_last_sample",
     "cmdp_psrl_reference_sample", "cmdp_vi_episodic_dense", "cmdp_psrl_episode_end_update", "cmdp_k1e_round_interior",
-    "cmdp_k1e_code_counts", "cmdp_k1s_plan", "cmdp_k1s_plan_desc",
+    "cmdp_k1e_code_counts", "cmdp_k1s_plan", "cmdp_k1s_plan_desc", "cmdp_chain_plan_desc", "cmdp_chain_choice",
 ]
 
 
@@ -232,6 +232,8 @@ def load():
         L.cmdp_k1e_code_counts.argtypes = [C.c_uint32, C.c_uint32, i32]
         L.cmdp_k1s_plan.argtypes = [vp, vp]
         L.cmdp_k1s_plan_desc.argtypes = [C.POINTER(CmdpDesc), i32, i32, vp]
+        L.cmdp_chain_plan_desc.argtypes = [C.POINTER(CmdpDesc), vp, vp, vp, vp, i64, vp, vp, vp, vp, vp]
+        L.cmdp_chain_choice.argtypes = [i32, i32, i32, i32, i32, vp]
         L.cmdp_k1e_code_counts.restype = C.c_uint32
         _lib = L
     return _lib

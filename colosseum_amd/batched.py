@@ -104,6 +104,33 @@ def k1s_plan_of_tables(tables: dict, cus: int = 256, instances_per_workgroup: in
     return _k1s_plan_dict(out)
 
 
+def chain_plan_of_tables(tables: dict) -> dict:
+    """K9F's plan of a continuous batch with its DP half (cmdp_chain_plan_desc: host only, needs no GPU): the eight arrays
+    the first `average_reward` call uploads, under ChainFast's names (csrc/cmdp_chain.h); `rptr` cut to the offsets written."""
+    d, keep = desc_from_tables(tables, L.RNG_PHILOX)
+    sizes = np.diff(keep["state_off"])
+    NS, B = int(sizes.sum()), len(sizes)
+    p = dict(rank=np.zeros(NS, np.int32), cptr=np.zeros(NS + B, np.int32), cbase=np.zeros(B, np.int64),
+             cand=np.zeros(int((sizes * np.minimum(sizes, 128)).sum()) + 1, np.uint16), nrounds=np.zeros(B, np.int32),
+             rbase=np.zeros(B, np.int64), rptr=np.zeros(NS + B, np.int32), piv=np.zeros(NS, np.int32))
+    n_cand = C.c_int64()
+    L.check(L.load().cmdp_chain_plan_desc(C.byref(d), L.ptr(p["rank"]), L.ptr(p["cptr"]), L.ptr(p["cbase"]), L.ptr(p["cand"]),
+                                          len(p["cand"]), C.byref(n_cand), L.ptr(p["nrounds"]), L.ptr(p["rbase"]), L.ptr(p["rptr"]),
+                                          L.ptr(p["piv"])))
+    del keep
+    p["cand"] = p["cand"][:n_cand.value]
+    p["rptr"] = p["rptr"][:int((p["nrounds"][p["nrounds"] >= 0] + 1).sum())]
+    return p
+
+
+def chain_choice(max_S: int, max_row_nnz: int, exact_order: bool = False, fast_enabled: bool = True, any_plan: bool = True) -> dict:
+    """Which kernels an `average_reward` call launches for a batch of that shape (cmdp_chain_choice: host only).
+    fast_enabled False stands for CMDP_CHAIN_FAST=0."""
+    out = np.zeros(4, np.int64)
+    L.check(L.load().cmdp_chain_choice(int(max_S), int(max_row_nnz), int(exact_order), int(fast_enabled), int(any_plan), L.ptr(out)))
+    return dict(refusal=int(out[0]), k9_lds=int(out[1]), fast=bool(out[2]), fast_lds=int(out[3]))
+
+
 class BatchedMDP:
     def __init__(self, models: Optional[Sequence[TabularModel]] = None, rng_mode: int = L.RNG_MT_COMPAT,
                  philox_keys: Optional[Sequence[int]] = None, with_env: bool = True, with_dp: bool = True,

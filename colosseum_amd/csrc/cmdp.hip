@@ -33,6 +33,7 @@ extern char** environ;
 #include "cmdp_dp_plan.h"
 #include "cmdp_agent.h"
 #include "cmdp_chain.h"
+#include "cmdp_chain_plan.h"
 #include "cmdp_evi.h"
 #include "cmdp_ucrl2.h"
 #include "cmdp_psrl.h"
@@ -260,13 +261,16 @@ struct cmdp {
   DevBuf<int64_t> d_ch_off;
   DevBuf<int32_t> d_ch_kind, d_ch_ncls, d_ch_act, d_ch_start, d_ch_idx;
   DevBuf<uint8_t> d_ch_mask;
-  // K9F: fill-reducing elimination plan of every instance (build_chain_plan), built at the first average-reward call
-  bool chain_plan_built = false, chain_plan_any = false;
-  bool chain_fast_ran = false;  // K9F was launched by the last average-reward call (its `slow` flags are that call's)
-  DevBuf<int32_t> d_cf_rank, d_cf_cptr, d_cf_nrounds, d_cf_rptr, d_cf_piv;
-  DevBuf<int64_t> d_cf_cbase, d_cf_rbase;
-  DevBuf<uint16_t> d_cf_cand;
-  DevBuf<uint8_t> d_cf_slow;
+  // K9F: the plan of every instance (plan_chains of cmdp_chain_plan.h), built at the first average-reward call that wants it
+  struct ChainFastState {
+    bool built = false, any = false;  // any: some instance has a plan
+    bool ran = false;                 // K9F was launched by the last average-reward call (its `slow` flags are that call's)
+    DevBuf<int32_t> rank, cptr, nrounds, rptr, piv;
+    DevBuf<int64_t> cbase, rbase;
+    DevBuf<uint16_t> cand;
+    DevBuf<uint8_t> slow;
+    ChainFast args() const { return {rank.p, cptr.p, cbase.p, cand.p, nrounds.p, rbase.p, rptr.p, piv.p, slow.p}; }
+  } cf;
   // UCRL2 agents on this handle (cmdp_ucrl2_*): CMDP_STAT_UCRL2_*
   // ... their `env` fields: cleared by cmdp_destroy, so that an agent destroyed AFTER its environment (garbage collection
   // picks the order) frees its own memory and touches nothing of the handle
@@ -1575,9 +1579,9 @@ int cmdp_stat(cmdp_t* h, int which, double* out) {
     return CMDP_OK;
   }
   if (which == CMDP_STAT_CHAIN_FAST_INSTANCES) {
-    if (!h->chain_fast_ran) { *out = 0.0; return CMDP_OK; }   // K9 alone: no plan, K9F beyond the LDS budget, exact order
+    if (!h->cf.ran) { *out = 0.0; return CMDP_OK; }   // K9 alone: no plan, K9F beyond the LDS budget, exact order
     std::vector<uint8_t> slow((size_t)h->B);
-    HIP_TRY(hipMemcpyAsync(slow.data(), h->d_cf_slow.p, (size_t)h->B, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(slow.data(), h->cf.slow.p, (size_t)h->B, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     int n = 0;
     for (uint8_t x : slow) n += x == 0;
@@ -3018,136 +3022,72 @@ int cmdp_qlearning_policy(cmdp_agent_t* a, float* pi) {
   return CMDP_OK;
 }
 
-// K9F's host side (cmdp_chain.h): per instance a minimum-degree elimination order of the MDP's transition graph (union over
-// the actions, symmetrised), every pivot's candidate list in the filled graph, and a schedule of rounds of up to 16 pivots
-// that are pairwise non-adjacent and share at most one candidate.  Instances without a plan (a pivot with more than
-// K9F_MAXC = 128 candidates, fewer than 2 or more than 65 535 states) keep K9.
-static int build_chain_plan(cmdp_t* h) {
-  h->chain_plan_built = true;
-  const int B = h->B, A = h->A;
+static_assert(kChainMaxCand == K9F_MAXC && kChainRoundWidth == 16 && kChainLdsBudget == kLdsBudget,
+              "cmdp_chain_plan.h plans for another kernel than cmdp_chain.h compiles and chain_launch launches");
+
+// CMDP_CHAIN_FAST = 0 keeps K9 alone; CMDP_CHAIN_DEBUG prints K9's phase times.  Read nowhere else, once per process.
+struct ChainSwitches { bool fast, debug; };
+static ChainSwitches chain_switches() {
+  static const ChainSwitches sw = {std::getenv("CMDP_CHAIN_FAST") ? std::atoi(std::getenv("CMDP_CHAIN_FAST")) != 0 : true,
+                                   std::getenv("CMDP_CHAIN_DEBUG") != nullptr};
+  return sw;
+}
+
+// K9F's plan (plan_chains of cmdp_chain_plan.h) on the device, built once per handle
+static int ensure_chain_plan(cmdp_t* h) {
+  auto& cf = h->cf;
+  if (cf.built) return CMDP_OK;
+  cf.built = true;
   hipStream_t st = h->stream;
   std::vector<int64_t> ptr;
   std::vector<int32_t> col;
   std::vector<float> val;
   if (int rc = fetch_csr(h, &ptr, &col, &val)) return rc;
-  constexpr int W = 16, NARROW = K9F_MAXC;
-  std::vector<int32_t> rank((size_t)h->n_states, -1), cptr((size_t)h->n_states + B, 0), nrounds((size_t)B, -1), rptr, piv((size_t)h->n_states, 0);
-  std::vector<int64_t> cbase((size_t)B, 0), rbase((size_t)B, 0);
-  std::vector<uint16_t> cand;
-  std::vector<std::vector<int>> plans;
+  const ChainPlan p = plan_chains(h->B, h->A, h->state_off.data(), ptr.data(), col.data(), val.data());
+  cf.any = p.any;
+  if (!p.any) return CMDP_OK;
+  HIP_TRY(cf.rank.upload(p.rank.data(), p.rank.size(), st));
+  HIP_TRY(cf.cptr.upload(p.cptr.data(), p.cptr.size(), st));
+  HIP_TRY(cf.nrounds.upload(p.nrounds.data(), p.nrounds.size(), st));
+  HIP_TRY(cf.rptr.upload(p.rptr.data(), p.rptr.size(), st));
+  HIP_TRY(cf.piv.upload(p.piv.data(), p.piv.size(), st));
+  HIP_TRY(cf.cbase.upload(p.cbase.data(), p.cbase.size(), st));
+  HIP_TRY(cf.rbase.upload(p.rbase.data(), p.rbase.size(), st));
+  HIP_TRY(cf.cand.upload(p.cand.data(), p.cand.size(), st));
+  HIP_TRY(cf.slow.alloc(h->B));
+  HIP_TRY(hipStreamSynchronize(st));   // `p` is a local
+  return CMDP_OK;
+}
+
+// K9's workspace, allocated by the first average-reward call: an S x S work matrix and index matrix per instance, the results
+static int ensure_chain_workspace(cmdp_t* h, hipStream_t st) {
+  const int B = h->B;
+  if (h->d_ch_off.n >= (size_t)B + 1) return CMDP_OK;
+  std::vector<int64_t> off(B + 1, 0);
   for (int b = 0; b < B; ++b) {
-    const int64_t so = h->state_off[b];
-    const int S = (int)(h->state_off[b + 1] - so);
-    cbase[(size_t)b] = (int64_t)cand.size();
-    rbase[(size_t)b] = (int64_t)rptr.size();
-    if (S < 2 || S > 65535) continue;
-    const int NWD = (S + 63) / 64;
-    std::vector<uint64_t> g((size_t)S * NWD, 0);   // adjacency bitsets of the elimination graph
-    auto setbit = [&](int u, int v) { g[(size_t)u * NWD + (v >> 6)] |= 1ull << (v & 63); };
-    for (int s2 = 0; s2 < S; ++s2)
-      for (int a = 0; a < A; ++a) {
-        const int64_t r = (so + s2) * A + a;
-        for (int64_t k = ptr[(size_t)r]; k < ptr[(size_t)r + 1]; ++k)
-          if (val[(size_t)k] > 0.0f && col[(size_t)k] != s2) { setbit(s2, col[(size_t)k]); setbit(col[(size_t)k], s2); }
-      }
-    std::vector<int> degree((size_t)S, 0), order((size_t)S), rk((size_t)S, -1);
-    std::vector<char> alive((size_t)S, 1);
-    for (int u = 0; u < S; ++u)
-      for (int w = 0; w < NWD; ++w) degree[(size_t)u] += __builtin_popcountll(g[(size_t)u * NWD + w]);
-    std::vector<std::vector<int>> cands((size_t)S);
-    bool ok = true;
-    for (int step = 0; step < S; ++step) {
-      int v = -1;
-      for (int u = 0; u < S; ++u)
-        if (alive[(size_t)u] && (v < 0 || degree[(size_t)u] < degree[(size_t)v])) v = u;   // ties: the smallest state
-      order[(size_t)step] = v;
-      rk[(size_t)v] = step;
-      alive[(size_t)v] = 0;
-      std::vector<int>& nb = cands[(size_t)step];
-      for (int w = 0; w < NWD; ++w) {
-        uint64_t x = g[(size_t)v * NWD + w];
-        while (x) { nb.push_back(64 * w + __builtin_ctzll(x)); x &= x - 1; }
-      }
-      if (step < S - 1 && (int)nb.size() > NARROW) { ok = false; break; }
-      for (int u : nb) {   // the neighbours become a clique; v leaves the graph
-        uint64_t* gu = &g[(size_t)u * NWD];
-        const uint64_t* gv = &g[(size_t)v * NWD];
-        int d = 0;
-        for (int w = 0; w < NWD; ++w) { gu[w] |= gv[w]; }
-        gu[u >> 6] &= ~(1ull << (u & 63));
-        gu[v >> 6] &= ~(1ull << (v & 63));
-        for (int w = 0; w < NWD; ++w) d += __builtin_popcountll(gu[w]);
-        degree[(size_t)u] = d;
-      }
-    }
-    if (!ok) continue;
-    // candidate lists as positions, ascending; bitsets of them for the conflict test of the schedule
-    std::vector<uint64_t> cb((size_t)S * NWD, 0);
-    for (int i = 0; i < S; ++i) {
-      std::vector<int>& nb = cands[(size_t)i];
-      for (int& x : nb) x = rk[(size_t)x];
-      std::sort(nb.begin(), nb.end());
-      for (int x : nb) cb[(size_t)i * NWD + (x >> 6)] |= 1ull << (x & 63);
-    }
-    // rounds: pivots whose lower-ranked neighbours are all done, pairwise sharing at most one candidate
-    std::vector<int> pending((size_t)S, 0);
-    for (int i = 0; i < S; ++i)
-      for (int x : cands[(size_t)i]) pending[(size_t)x]++;
-    std::vector<char> done((size_t)S, 0);
-    std::vector<int> ready;
-    for (int i = 0; i < S - 1; ++i)
-      if (!pending[(size_t)i]) ready.push_back(i);
-    int remaining = S - 1, nr = 0;
-    int32_t* pv = piv.data() + so;
-    int filled = 0;
-    while (remaining > 0) {
-      std::sort(ready.begin(), ready.end());
-      std::vector<int> rnd, rest;
-      for (int pidx : ready) {
-        bool fits = (int)rnd.size() < W;
-        for (size_t q = 0; fits && q < rnd.size(); ++q) {
-          int common = 0;
-          for (int w = 0; w < NWD; ++w) common += __builtin_popcountll(cb[(size_t)pidx * NWD + w] & cb[(size_t)rnd[q] * NWD + w]);
-          fits = common <= 1;
-        }
-        if (fits) rnd.push_back(pidx); else rest.push_back(pidx);
-      }
-      if (rnd.empty()) { ok = false; break; }
-      rptr.push_back(filled);
-      for (int pidx : rnd) {
-        pv[filled++] = pidx;
-        --remaining;
-        for (int x : cands[(size_t)pidx])
-          if (--pending[(size_t)x] == 0 && x < S - 1) rest.push_back(x);
-      }
-      ready.swap(rest);
-      ++nr;
-    }
-    if (!ok) { rptr.resize((size_t)rbase[(size_t)b]); continue; }
-    rptr.push_back(filled);
-    nrounds[(size_t)b] = nr;
-    for (int s2 = 0; s2 < S; ++s2) rank[(size_t)(so + s2)] = rk[(size_t)s2];
-    int32_t* cp = cptr.data() + so + b;
-    cp[0] = 0;
-    for (int i = 0; i < S; ++i) {
-      for (int x : cands[(size_t)i]) cand.push_back((uint16_t)x);
-      cp[i + 1] = cp[i] + (int)cands[(size_t)i].size();
-    }
-    h->chain_plan_any = true;
+    const int64_t S = h->state_off[b + 1] - h->state_off[b];
+    off[b + 1] = off[b] + S * S;
   }
-  if (!h->chain_plan_any) return CMDP_OK;
-  if (cand.empty()) cand.push_back(0);
-  if (rptr.empty()) rptr.push_back(0);
-  HIP_TRY(h->d_cf_rank.upload(rank.data(), rank.size(), st));
-  HIP_TRY(h->d_cf_cptr.upload(cptr.data(), cptr.size(), st));
-  HIP_TRY(h->d_cf_nrounds.upload(nrounds.data(), nrounds.size(), st));
-  HIP_TRY(h->d_cf_rptr.upload(rptr.data(), rptr.size(), st));
-  HIP_TRY(h->d_cf_piv.upload(piv.data(), piv.size(), st));
-  HIP_TRY(h->d_cf_cbase.upload(cbase.data(), cbase.size(), st));
-  HIP_TRY(h->d_cf_rbase.upload(rbase.data(), rbase.size(), st));
-  HIP_TRY(h->d_cf_cand.upload(cand.data(), cand.size(), st));
-  HIP_TRY(h->d_cf_slow.alloc(B));
+  HIP_TRY(h->d_ch_off.upload(off.data(), off.size(), st));
+  HIP_TRY(hipStreamSynchronize(st));  // `off` is a local
+  HIP_TRY(h->d_ch_work.alloc((size_t)off[B]));
+  HIP_TRY(h->d_ch_idx.alloc((size_t)off[B]));
+  HIP_TRY(h->d_ch_avg.alloc(B));
+  HIP_TRY(h->d_ch_kind.alloc(B));
+  HIP_TRY(h->d_ch_ncls.alloc(B));
+  return CMDP_OK;
+}
+
+// CMDP_CHAIN_DEBUG: K9's phase times from the clock words the kernel left in `d_dbg`
+static int report_chain_phases(int B, const long long* d_dbg, hipStream_t st) {
+  std::vector<long long> t((size_t)B * 8);
+  HIP_TRY(hipMemcpyAsync(t.data(), d_dbg, sizeof(long long) * t.size(), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
+  double ph[7] = {0, 0, 0, 0, 0, 0, 0};
+  for (int b = 0; b < B; ++b)
+    for (int k = 0; k < 7; ++k) ph[k] = std::max(ph[k], (double)(t[(size_t)b * 8 + k + 1] - t[(size_t)b * 8 + k]) / 100.0);
+  std::fprintf(stderr, "[K9 us, max over instances] A %.0f  B(tarjan) %.0f  C %.0f  D %.0f  E(gth) %.0f  F(backsub) %.0f  sum %.0f\n",
+               ph[0], ph[1], ph[2], ph[3], ph[4], ph[5], ph[6]);
   return CMDP_OK;
 }
 
@@ -3161,26 +3101,18 @@ static int chain_launch(cmdp_t* h, const float* d_pi, const int32_t* d_act, cons
                         hipStream_t on_stream = nullptr) {
   if (!h->has_dp) return fail(CMDP_ERR_INVALID, "the handle was created without the DP half (CSR transition matrices)");
   if (h->H != 0) return fail(CMDP_ERR_INVALID, "average rewards are defined for continuous instances (horizon 0)");
-  const size_t lds = chain_lds_bytes(h->max_S, h->max_row_nnz);
-  if (lds > (size_t)kLdsBudget)
-    return fail(CMDP_ERR_UNSUPPORTED, "instance with %d states (max %d successors per row) exceeds the LDS budget of K9",
-                h->max_S, h->max_row_nnz);
+  const ChainSwitches sw = chain_switches();
+  // the LDS formulas of cmdp_chain.h (16 wavefronts: the k_chain_fast<16> launched below)
+  const size_t k9_lds = chain_lds_bytes(h->max_S, h->max_row_nnz), fast_lds = chain_fast_lds_bytes(h->max_S, h->max_row_nnz, 16);
+  // the plan is built by the first call that K9F is not switched off for, whether K9F then fits LDS or not; a call that
+  // pick_chain refuses builds none
+  if (!h->chain_exact && sw.fast && k9_lds <= (size_t)kLdsBudget)
+    if (int rc = ensure_chain_plan(h)) return rc;
+  const ChainChoice k = pick_chain(h->max_S, h->max_row_nnz, k9_lds, fast_lds, h->chain_exact, sw.fast, h->cf.any);
+  if (k.refusal) return k.refusal;
   hipStream_t st = on_stream ? on_stream : h->stream;   // the logged loop runs the solve beside the agents' next interval
   const int B = h->B;
-  if (h->d_ch_off.n < (size_t)B + 1) {
-    std::vector<int64_t> off(B + 1, 0);
-    for (int b = 0; b < B; ++b) {
-      const int64_t S = h->state_off[b + 1] - h->state_off[b];
-      off[b + 1] = off[b] + S * S;
-    }
-    HIP_TRY(h->d_ch_off.upload(off.data(), off.size(), st));
-    HIP_TRY(hipStreamSynchronize(st));  // `off` is a local
-    HIP_TRY(h->d_ch_work.alloc((size_t)off[B]));
-    HIP_TRY(h->d_ch_idx.alloc((size_t)off[B]));
-    HIP_TRY(h->d_ch_avg.alloc(B));
-    HIP_TRY(h->d_ch_kind.alloc(B));
-    HIP_TRY(h->d_ch_ncls.alloc(B));
-  }
+  if (int rc = ensure_chain_workspace(h, st)) return rc;
   const uint8_t* dmask = nullptr;
   if (mask && mask_on_device) {
     dmask = mask;
@@ -3196,51 +3128,30 @@ static int chain_launch(cmdp_t* h, const float* d_pi, const int32_t* d_act, cons
   c.avg = (!copy_back && avg) ? avg : h->d_ch_avg.p;
   c.kind = (!copy_back && kind) ? kind : h->d_ch_kind.p;
   c.n_classes = h->d_ch_ncls.p;
-  if (lds > 64 * 1024)
-  {
+  if (k.k9_lds > 64 * 1024) {
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_chain_average_reward<16, false>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.k9_lds));
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_chain_average_reward<16, true>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.k9_lds));
   }
-  static const bool chain_debug = std::getenv("CMDP_CHAIN_DEBUG") != nullptr;
   DevBuf<long long> d_dbg;
-  if (chain_debug) {
+  if (sw.debug) {
     HIP_TRY(d_dbg.alloc((size_t)B * 8));
     HIP_TRY(d_dbg.zero(st));
     c.dbg = d_dbg.p;
   }
-  // K9F first (irreducible chains, fill-reducing elimination order, rounds of independent pivots); it flags the instances
-  // it leaves to K9.  The reference's summation order (CMDP_OPT_CHAIN_EXACT_ORDER) keeps K9 alone.
-  static const int fast_env = std::getenv("CMDP_CHAIN_FAST") ? std::atoi(std::getenv("CMDP_CHAIN_FAST")) : 1;
-  h->chain_fast_ran = false;
-  if (!h->chain_exact && fast_env) {
-    if (!h->chain_plan_built)
-      if (int rc = build_chain_plan(h)) return rc;
-    const size_t flds = chain_fast_lds_bytes(h->max_S, h->max_row_nnz, 16);
-    if (h->chain_plan_any && flds <= (size_t)kLdsBudget) {
-      ChainFast f{};
-      f.rank = h->d_cf_rank.p; f.cptr = h->d_cf_cptr.p; f.cbase = h->d_cf_cbase.p; f.cand = h->d_cf_cand.p;
-      f.nrounds = h->d_cf_nrounds.p; f.rbase = h->d_cf_rbase.p; f.rptr = h->d_cf_rptr.p; f.piv = h->d_cf_piv.p;
-      f.slow = h->d_cf_slow.p;
-      if (int rc = set_lds(k_chain_fast<16>, flds)) return rc;
-      hipLaunchKernelGGL((k_chain_fast<16>), dim3(B), dim3(1024), flds, st, c, f);
-      c.mask = h->d_cf_slow.p;
-      h->chain_fast_ran = true;
-    }
+  // K9F first; it flags the instances it leaves to K9, which then runs under that mask
+  h->cf.ran = false;
+  if (k.fast) {
+    if (int rc = set_lds(k_chain_fast<16>, k.fast_lds)) return rc;
+    hipLaunchKernelGGL((k_chain_fast<16>), dim3(B), dim3(1024), k.fast_lds, st, c, h->cf.args());
+    c.mask = h->cf.slow.p;
+    h->cf.ran = true;
   }
-  if (h->chain_exact) hipLaunchKernelGGL((k_chain_average_reward<16, true>), dim3(B), dim3(1024), lds, st, c);
-  else hipLaunchKernelGGL((k_chain_average_reward<16, false>), dim3(B), dim3(1024), lds, st, c);
-  if (chain_debug) {
-    std::vector<long long> t((size_t)B * 8);
-    HIP_TRY(hipMemcpyAsync(t.data(), d_dbg.p, sizeof(long long) * t.size(), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    double ph[7] = {0, 0, 0, 0, 0, 0, 0};
-    for (int b = 0; b < B; ++b)
-      for (int k = 0; k < 7; ++k) ph[k] = std::max(ph[k], (double)(t[(size_t)b * 8 + k + 1] - t[(size_t)b * 8 + k]) / 100.0);
-    std::fprintf(stderr, "[K9 us, max over instances] A %.0f  B(tarjan) %.0f  C %.0f  D %.0f  E(gth) %.0f  F(backsub) %.0f  sum %.0f\n",
-                 ph[0], ph[1], ph[2], ph[3], ph[4], ph[5], ph[6]);
-  }
+  if (h->chain_exact) hipLaunchKernelGGL((k_chain_average_reward<16, true>), dim3(B), dim3(1024), k.k9_lds, st, c);
+  else hipLaunchKernelGGL((k_chain_average_reward<16, false>), dim3(B), dim3(1024), k.k9_lds, st, c);
+  if (sw.debug)
+    if (int rc = report_chain_phases(B, d_dbg.p, st)) return rc;
   HIP_TRY(hipGetLastError());
   if (!copy_back) return CMDP_OK;  // the caller reads d_ch_avg / d_ch_kind itself
   HIP_TRY(hipMemcpyAsync(avg, h->d_ch_avg.p, sizeof(double) * B, hipMemcpyDeviceToHost, st));
@@ -3274,6 +3185,48 @@ int cmdp_qlearning_average_reward(cmdp_agent_t* a, const uint8_t* mask, double* 
   if (!a->continuous) return fail(CMDP_ERR_INVALID, "cmdp_qlearning_average_reward is for the continuous agent");
   if (int rc = ql_enqueue_greedy(a)) return rc;
   return chain_launch(h, a->d_pi.p, nullptr, h->d_cur.p, mask, avg, kind, nullptr);
+}
+
+// cmdp_chain_plan_desc / cmdp_chain_choice: the planner and the picker of cmdp_chain_plan.h without a handle or a device
+int cmdp_chain_plan_desc(const cmdp_desc* d, int32_t* rank, int32_t* cptr, int64_t* cbase, uint16_t* cand, int64_t cand_capacity,
+                         int64_t* n_cand, int32_t* nrounds, int64_t* rbase, int32_t* rptr, int32_t* piv) {
+  if (!d || !rank || !cptr || !cbase || !cand || !n_cand || !nrounds || !rbase || !rptr || !piv || cand_capacity < 0)
+    return fail(CMDP_ERR_INVALID, "bad argument");
+  if (d->n_instances < 1 || d->n_actions < 1 || !d->state_off || !d->csr_ptr || !d->csr_col || !d->csr_val)
+    return fail(CMDP_ERR_INVALID, "cmdp_chain_plan_desc needs the DP half of the description");
+  // as much of cmdp_create's validation as the planner indexes by
+  const int B = d->n_instances, A = d->n_actions;
+  if (d->state_off[0] != 0 || d->csr_ptr[0] != 0) return fail(CMDP_ERR_INVALID, "offsets do not start at 0");
+  for (int b = 0; b < B; ++b) {
+    const int64_t S = d->state_off[b + 1] - d->state_off[b];
+    if (S < 1 || S > (1 << 28)) return fail(CMDP_ERR_INVALID, "instance %d has %lld states", b, (long long)S);
+    for (int64_t r = d->state_off[b] * A; r < d->state_off[b + 1] * A; ++r) {
+      if (d->csr_ptr[r + 1] < d->csr_ptr[r]) return fail(CMDP_ERR_INVALID, "csr_ptr decreasing at row %lld", (long long)r);
+      for (int64_t k = d->csr_ptr[r]; k < d->csr_ptr[r + 1]; ++k)
+        if (d->csr_col[k] < 0 || d->csr_col[k] >= S) return fail(CMDP_ERR_INVALID, "csr_col out of range at %lld", (long long)k);
+    }
+  }
+  const ChainPlan p = plan_chains(B, A, d->state_off, d->csr_ptr, d->csr_col, d->csr_val);
+  *n_cand = (int64_t)p.cand.size();
+  if (*n_cand > cand_capacity) return fail(CMDP_ERR_INVALID, "the plan has %lld candidates, room for %lld", (long long)*n_cand, (long long)cand_capacity);
+  std::copy(p.rank.begin(), p.rank.end(), rank);
+  std::copy(p.cptr.begin(), p.cptr.end(), cptr);
+  std::copy(p.cbase.begin(), p.cbase.end(), cbase);
+  std::copy(p.cand.begin(), p.cand.end(), cand);
+  std::copy(p.nrounds.begin(), p.nrounds.end(), nrounds);
+  std::copy(p.rbase.begin(), p.rbase.end(), rbase);
+  std::copy(p.rptr.begin(), p.rptr.end(), rptr);
+  std::copy(p.piv.begin(), p.piv.end(), piv);
+  return CMDP_OK;
+}
+
+int cmdp_chain_choice(int max_S, int max_row_nnz, int exact_order, int fast_enabled, int any_plan, int64_t out[4]) {
+  if (!out || max_S < 1 || max_row_nnz < 1) return fail(CMDP_ERR_INVALID, "bad argument");
+  const ChainChoice k = pick_chain(max_S, max_row_nnz, chain_lds_bytes(max_S, max_row_nnz), chain_fast_lds_bytes(max_S, max_row_nnz, kChainRoundWidth),
+                                   exact_order != 0, fast_enabled != 0, any_plan != 0);
+  const int64_t v[4] = {k.refusal, (int64_t)k.k9_lds, k.fast, (int64_t)k.fast_lds};
+  std::copy(v, v + 4, out);
+  return CMDP_OK;
 }
 
 int cmdp_set_observation_table(cmdp_t* h, const float* table, int32_t F, int time_indexed) {
@@ -3359,15 +3312,19 @@ static int mixing_time_dense(cmdp_t* h, int b, const int64_t* d_cptr, const int3
   DevBuf<unsigned long long> d_tv;
   HIP_TRY(d_tv.alloc(1));
   MixDense m{S, so, d_cptr, d_crow, d_cval, d_stat, d_tv.p};
-  auto tv_of = [&](const double* X, double* out) -> int {
+  // the total-variation word a kernel leaves in d_tv (the bits of a double, raised by atomic max): cleared, `launch`, read
+  auto tv_after = [&](auto launch, double* out) -> int {
     HIP_TRY(d_tv.zero(st));
-    hipLaunchKernelGGL(k_mixd_tv, dim3((unsigned)S), dim3(256), 0, st, m, X);
+    launch();
     HIP_TRY(hipGetLastError());
     unsigned long long bits = 0;
     HIP_TRY(hipMemcpyAsync(&bits, d_tv.p, sizeof bits, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     std::memcpy(out, &bits, sizeof(double));
     return CMDP_OK;
+  };
+  auto tv_of = [&](const double* X, double* out) -> int {
+    return tv_after([&] { hipLaunchKernelGGL(k_mixd_tv, dim3((unsigned)S), dim3(256), 0, st, m, X); }, out);
   };
   rocblas_handle blas = nullptr;
   if (rocblas_create_handle(&blas) != rocblas_status_success) return fail(CMDP_ERR_HIP, "rocblas_create_handle failed");
@@ -3439,13 +3396,8 @@ static int mixing_time_dense(cmdp_t* h, int b, const int64_t* d_cptr, const int3
     if (i == last) {  // lo + 2^r is known to be mixed
       d = d_hi;
     } else {
-      HIP_TRY(d_tv.zero(st));
-      hipLaunchKernelGGL(k_mixd_step, dim3((unsigned)S), dim3(256), 0, st, m, pool[(size_t)cur].p, pool[(size_t)cand].p);
-      HIP_TRY(hipGetLastError());
-      unsigned long long bits = 0;
-      HIP_TRY(hipMemcpyAsync(&bits, d_tv.p, sizeof bits, hipMemcpyDeviceToHost, st));
-      HIP_TRY(hipStreamSynchronize(st));
-      std::memcpy(&d, &bits, sizeof(double));
+      const auto step = [&] { hipLaunchKernelGGL(k_mixd_step, dim3((unsigned)S), dim3(256), 0, st, m, pool[(size_t)cur].p, pool[(size_t)cand].p); };
+      if (int rc = tv_after(step, &d)) return rc;
       std::swap(cur, cand);
     }
     if (d <= threshold) {
@@ -3468,74 +3420,35 @@ int cmdp_mixing_time(cmdp_t* h, const float* pi, const double* stationary, doubl
   if (!h->has_dp) return fail(CMDP_ERR_INVALID, "handle was created without the DP half");
   if (!stationary || !t_mix) return fail(CMDP_ERR_INVALID, "null argument");
   if (!(threshold > 0.0) || max_steps < 1) return fail(CMDP_ERR_INVALID, "threshold <= 0 or max_steps < 1");
-  const bool fits_lds = sizeof(double) * (size_t)h->max_S <= (size_t)kLdsBudget - 1024;
-  if (h->mixing_path == 2 && !fits_lds)
-    return fail(CMDP_ERR_UNSUPPORTED, "a row of X (%d states, float64) does not fit LDS: the stepping path cannot run", h->max_S);
-  const bool dense_path = h->mixing_path == 1 || (h->mixing_path == 0 && (!fits_lds || h->max_S > 1024));
+  MixingPath path;
+  if (int rc = pick_mixing_path(h->mixing_path, h->max_S, &path)) return rc;
   hipStream_t st = h->stream;
-  const int B = h->B, A = h->A;
+  const int B = h->B;
   const int64_t NS = h->n_states;
   std::vector<int64_t> ptr;
   std::vector<int32_t> col;
   std::vector<float> val;
   if (int rc = fetch_csr(h, &ptr, &col, &val)) return rc;
-  // P[s, j] = sum_a pi[s, a] * T[s, a, j] (float64, actions in order), then its CSC with predecessors in index order
-  std::vector<int64_t> cptr((size_t)NS + 1, 0), xoff((size_t)B + 1, 0);
-  std::vector<int32_t> crow;
-  std::vector<double> cval;
-  {
-    std::vector<std::vector<std::pair<int32_t, double>>> incoming((size_t)NS);
-    std::vector<double> rowacc;
-    std::vector<int32_t> touched;
-    for (int b = 0; b < B; ++b) {
-      const int64_t so = h->state_off[b], S = h->state_off[b + 1] - so;
-      xoff[b + 1] = xoff[b] + S * S;
-      rowacc.assign((size_t)S, 0.0);
-      for (int64_t s = 0; s < S; ++s) {
-        touched.clear();
-        for (int a = 0; a < A; ++a) {
-          const int64_t r = (so + s) * A + a;
-          const double w = pi ? (double)pi[r] : 1.0 / A;
-          if (w == 0.0) continue;
-          for (int64_t k = ptr[r]; k < ptr[r + 1]; ++k) {
-            if (rowacc[col[k]] == 0.0) touched.push_back(col[k]);
-            rowacc[col[k]] += w * (double)val[k];
-          }
-        }
-        // the float32 probabilities of a row sum to 1 only within ~1e-7: without this, X_t would lose or gain that much
-        // mass per step (1e-2 over the 1e5 steps a slow chain needs).  The chain is DEFINED with normalised rows.
-        double rowsum = 0.0;
-        for (int32_t j : touched) rowsum += rowacc[j];
-        for (int32_t j : touched) {
-          if (rowacc[j] != 0.0) incoming[(size_t)(so + j)].push_back({(int32_t)s, rowacc[j] / rowsum});
-          rowacc[j] = 0.0;
-        }
-      }
-    }
-    for (int64_t j = 0; j < NS; ++j) {
-      cptr[j + 1] = cptr[j] + (int64_t)incoming[j].size();
-      for (auto& e : incoming[j]) { crow.push_back(e.first); cval.push_back(e.second); }  // s ascending by construction
-    }
-  }
+  const PolicyCsc csc = policy_chain_csc(B, h->A, h->state_off.data(), ptr.data(), col.data(), val.data(), pi);
   constexpr int CH = 256;
   DevBuf<int64_t> d_cptr, d_xoff;
   DevBuf<int32_t> d_crow;
   DevBuf<double> d_cval, d_stat, d_X, d_Xn;
   DevBuf<unsigned long long> d_dl;
-  HIP_TRY(d_cptr.upload(cptr.data(), cptr.size(), st));
-  HIP_TRY(d_xoff.upload(xoff.data(), xoff.size(), st));
-  HIP_TRY(d_crow.upload(crow.data(), crow.size(), st));
-  HIP_TRY(d_cval.upload(cval.data(), cval.size(), st));
+  HIP_TRY(d_cptr.upload(csc.cptr.data(), csc.cptr.size(), st));
+  HIP_TRY(d_xoff.upload(csc.xoff.data(), csc.xoff.size(), st));
+  HIP_TRY(d_crow.upload(csc.crow.data(), csc.crow.size(), st));
+  HIP_TRY(d_cval.upload(csc.cval.data(), csc.cval.size(), st));
   HIP_TRY(d_stat.upload(stationary, (size_t)NS, st));
-  if (dense_path) {
+  if (path == MIXING_POWERS) {
     for (int b = 0; b < B; ++b)
       if (int rc = mixing_time_dense(h, b, d_cptr.p, d_crow.p, d_cval.p, d_stat.p, threshold, max_steps, t_mix + b,
                                      tv_at ? tv_at + b : nullptr))
         return rc;
     return CMDP_OK;
   }
-  HIP_TRY(d_X.alloc((size_t)xoff[B]));
-  HIP_TRY(d_Xn.alloc((size_t)xoff[B]));
+  HIP_TRY(d_X.alloc((size_t)csc.xoff[B]));
+  HIP_TRY(d_Xn.alloc((size_t)csc.xoff[B]));
   HIP_TRY(d_dl.alloc((size_t)B * CH));
   MixArgs m{};
   m.B = B; m.state_off = h->d_state_off.p; m.x_off = d_xoff.p; m.csc_ptr = d_cptr.p; m.csc_row = d_crow.p;

@@ -493,7 +493,7 @@ __global__ void __launch_bounds__(NW * 64) k_chain_average_reward(ChainArgs c) {
 // same stationary distribution up to rounding (the SURVEY's tolerance for this row is 1e-6 on the average reward; K9's
 // default already replaces the reference's index-ordered sums by wave butterflies).  The policy's chain is a sub-graph of
 // the MDP's transition graph (union over the actions), which is fixed per instance, so the host computes ONCE per instance
-// (cmdp.hip: build_chain_plan):
+// (cmdp_chain_plan.h: plan_chains):
 //   * a minimum-degree elimination order of that graph (symmetrised) -- S = 784: 10 332 candidate entries in the filled
 //     graph instead of ~75 000 in state order, at most 59 per pivot;
 //   * per pivot its CANDIDATE list (the higher-ranked neighbours in the filled graph: a superset of the non-zeros of its

@@ -366,6 +366,21 @@ int cmdp_k1s_plan(cmdp_t* h, int32_t out[CMDP_K1S_PLAN_FIELDS]);
    cmdp_create would reject before planning (offsets, successor indices, row lengths). */
 int cmdp_k1s_plan_desc(const cmdp_desc* desc, int cus, int instances_per_workgroup, int32_t out[CMDP_K1S_PLAN_FIELDS]);
 
+/* K9F's plan (csrc/cmdp_chain_plan.h; the arrays are ChainFast's of csrc/cmdp_chain.h) for a bare description, without a
+   handle and without a device: what the first cmdp_average_reward call on a handle of `desc` uploads (introspection for
+   tests; only the DP half is read; no reference counterpart).  The caller sizes the arrays: rank and piv [state_off[B]],
+   cptr and rptr [state_off[B] + B] (rptr: the round offsets of the planned instances, packed; the rest is left as it is),
+   cbase, rbase and nrounds [B] (nrounds -1: no plan, the instance keeps K9), cand [cand_capacity].  *n_cand receives the
+   number of entries of cand; CMDP_ERR_INVALID when cand_capacity is smaller, and for a description cmdp_create would
+   reject before planning (offsets, column indices). */
+int cmdp_chain_plan_desc(const cmdp_desc* desc, int32_t* rank, int32_t* cptr, int64_t* cbase, uint16_t* cand, int64_t cand_capacity,
+                         int64_t* n_cand, int32_t* nrounds, int64_t* rbase, int32_t* rptr, int32_t* piv);
+/* Which kernels a cmdp_average_reward call launches for a batch whose largest instance has max_S states and whose longest row
+   max_row_nnz entries (host only).  exact_order: CMDP_OPT_CHAIN_EXACT_ORDER; fast_enabled: 0 stands for CMDP_CHAIN_FAST = 0
+   (the environment is not read); any_plan: some instance has a K9F plan.  out: the refusal (CMDP_OK, or CMDP_ERR_UNSUPPORTED
+   when not even K9 fits LDS), K9's dynamic LDS bytes, 1 if K9F runs first, K9F's LDS bytes. */
+int cmdp_chain_choice(int max_S, int max_row_nnz, int exact_order, int fast_enabled, int any_plan, int64_t out[4]);
+
 /* BaseMDP.get_visitation_counts / reset_visitation_counts (colosseum/mdp/base.py:1357-1382).
    state_counts [state_off[B]], sa_counts [state_off[B]*A]; either may be NULL. */
 int cmdp_visits(cmdp_t* h, int64_t* state_counts, int64_t* sa_counts);

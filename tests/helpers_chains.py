@@ -1,6 +1,7 @@
 """Synthetic continuous MDPs whose chain under one deterministic policy has a prescribed structure, for the Markov-chain
 kernels K7 (k_gth), K9 (k_chain_average_reward) and K9F (k_chain_fast); host mirrors of the two LDS formulas of
-colosseum_amd/csrc/cmdp_chain.h and of the minimum-degree order of build_chain_plan (cmdp.hip); and the two CPU references
+colosseum_amd/csrc/cmdp_chain.h and of K9F's planner, plan_chains (colosseum_amd/csrc/cmdp_chain_plan.h): the minimum-degree
+order with its candidate lists, the round schedule and the packing; and the two CPU references
 of the average reward: the reference's own bookkeeping (colosseum_amd.markov_chain) over the oracle's GTH, and float64 GTH
 in numpy under any elimination order.  Host only: no GPU is touched here."""
 import contextlib
@@ -307,8 +308,23 @@ SUITE = {
 REFUSED = (_sp(5, S_MAX4 + 1), 26, 2, None)   # one state more than K9's LDS admits
 
 
+def two_components():
+    """For the planner alone (one action, no policy): a transition graph of two components, a 10-cycle on states 0 .. 9 and
+    a triangle on states 10 .. 12, then an instance of 2 states.  Every degree is 2, so the minimum-degree order is the
+    index order and the triangle holds the last two positions; it is eliminated in the first two rounds, beside the
+    cycle's first pivots: the only lister of the last position, pivot 11, goes eight rounds before the last one."""
+    succ = [(s + 1) % 10 for s in range(10)] + [11, 12, 10] + [1, 0]
+    n = len(succ)
+    t = dict(B=2, A=1, H=0, rewards_range=(0.0, 1.0), state_off=np.array([0, 13, 15], np.int64),
+             csr_ptr=np.arange(n + 1, dtype=np.int64), csr_col=np.asarray(succ, np.int32), csr_val=np.ones(n, np.float32),
+             R=np.zeros(n, np.float32))
+    return dict(t=t, meta=[dict(name="two_components", S=13, fast=None), dict(name="two_components", S=2, fast=None)])
+
+
 @functools.lru_cache(maxsize=None)
 def suite(name):
+    if name == "two_components":
+        return two_components()
     return generate(*(SUITE[name] if name != "refused" else REFUSED))
 
 
@@ -336,32 +352,99 @@ def policy_chain(t, b, act):
     return np.minimum(np.float32(1), T[np.arange(len(act)), act])
 
 
-def min_degree_max_candidates(t, b, stop=None):
-    """Largest candidate list of a pivot in the minimum-degree elimination of build_chain_plan: the transition graph of all
-    actions (positive entries, no self-loops), symmetrised; the live state of lowest degree goes next (ties: the smallest
-    state), its neighbours become a clique.  Also returns the first pivot's count.  stop: give up above this count."""
+def transition_graph(t, b):
+    """Adjacency [S, S] of the graph K9F's plan eliminates: the transitions of all actions (positive entries, no
+    self-loops), symmetrised."""
     T, _ = dense_TR(t, b)
     g = (T > 0).any(1)
     np.fill_diagonal(g, False)
-    g = g | g.T
+    return g | g.T
+
+
+def min_degree_order(t, b, stop=None):
+    """The minimum-degree elimination of plan_chains: the live state of lowest degree goes next (ties: the smallest state),
+    its neighbours become a clique.  Returns (order = the states in elimination order, per pivot position its candidates:
+    the positions of the neighbours it had when it went, ascending, sizes = those lists' lengths as far as the elimination
+    got).  stop: give up once a pivot has more candidates than this; the lists are then None."""
+    g = transition_graph(t, b)
     S = len(g)
     deg = g.sum(1)
     alive = np.ones(S, bool)
-    worst, first = 0, None
+    order, nbs = [], []
     for step in range(S - 1):
         v = int(np.argmin(np.where(alive, deg, S + 1)))
         nb = np.flatnonzero(g[v])
-        first = len(nb) if first is None else first
-        worst = max(worst, len(nb))
-        if stop is not None and worst > stop:
-            break
+        order.append(v)
+        nbs.append(nb)
+        if stop is not None and len(nb) > stop:
+            return order, None, [len(x) for x in nbs]
         alive[v] = False
         g[np.ix_(nb, nb)] = True
         g[nb, nb] = False
         g[v, :] = False
         g[:, v] = False
         deg[nb] = g[nb].sum(1)
-    return worst, first
+    order.append(int(np.flatnonzero(alive)[0]))
+    pos = np.empty(S, np.int64)
+    pos[order] = np.arange(S)
+    return order, [sorted(pos[nb].tolist()) for nb in nbs] + [[]], [len(x) for x in nbs]
+
+
+def min_degree_max_candidates(t, b, stop=None):
+    """(largest candidate list of a pivot in the minimum-degree elimination, the first pivot's count).  stop: give up above
+    this count."""
+    sizes = min_degree_order(t, b, stop)[2]
+    return max(sizes, default=0), (sizes[0] if sizes else None)
+
+
+def schedule_rounds(cands, width=K9F_NW):
+    """The rounds of K9F's plan as cmdp_chain.h describes them: a pivot may go once every lower pivot that lists it as a
+    candidate has gone; of those that may, lowest position first, a round takes up to `width` that share at most one
+    candidate with every pivot already in it.  The last position is no pivot.  Returns the rounds as lists of positions."""
+    S = len(cands)
+    sets = [set(c) for c in cands]
+    waiting = np.zeros(S, np.int64)   # lower pivots that list this position and have not gone
+    for c in cands:
+        waiting[np.asarray(c, np.int64)] += 1
+    todo, rounds = set(range(S - 1)), []
+    while todo:
+        rnd = []
+        for p in sorted(x for x in todo if waiting[x] == 0):
+            if len(rnd) < width and all(len(sets[p] & sets[q]) <= 1 for q in rnd):
+                rnd.append(p)
+        for p in rnd:
+            todo.remove(p)
+            waiting[np.asarray(cands[p], np.int64)] -= 1
+        rounds.append(rnd)
+    return rounds
+
+
+def plan_mirror(t):
+    """The eight arrays of plan_chains for the batch `t`, from the two mirrors above and ChainFast's layout (cmdp_chain.h):
+    cptr of instance b at state_off[b] + b, rank and piv at state_off[b], cbase / rbase the starts of its blocks in cand /
+    rptr; an instance without a plan (fewer than 2 states, a pivot with more than K9F_MAXC candidates) takes no room."""
+    off, B = t["state_off"], int(t["B"])
+    NS = int(off[-1])
+    p = dict(rank=np.full(NS, -1, np.int32), cptr=np.zeros(NS + B, np.int32), cbase=np.zeros(B, np.int64), cand=[],
+             nrounds=np.full(B, -1, np.int32), rbase=np.zeros(B, np.int64), rptr=[], piv=np.zeros(NS, np.int32))
+    for b in range(B):
+        so, S = int(off[b]), int(off[b + 1] - off[b])
+        p["cbase"][b], p["rbase"][b] = len(p["cand"]), len(p["rptr"])
+        if S < 2:
+            continue
+        order, cands, _ = min_degree_order(t, b, stop=K9F_MAXC)
+        if cands is None:
+            continue
+        rounds = schedule_rounds(cands)
+        p["nrounds"][b] = len(rounds)
+        p["rank"][so + np.asarray(order)] = np.arange(S)
+        p["cptr"][so + b: so + b + S + 1] = np.concatenate([[0], np.cumsum([len(c) for c in cands])])
+        p["cand"] += [x for c in cands for x in c]
+        p["piv"][so: so + S - 1] = [x for r in rounds for x in r]
+        p["rptr"] += np.concatenate([[0], np.cumsum([len(r) for r in rounds])]).tolist()
+    p["cand"] = np.asarray(p["cand"], np.uint16)
+    p["rptr"] = np.asarray(p["rptr"], np.int32)
+    return p
 
 
 # ---- references -----------------------------------------------------------------------------------------------------------

@@ -1,5 +1,6 @@
 """The Markov-chain kernels on generated chains: K7 (k_gth), K9 (k_chain_average_reward) and K9F (k_chain_fast with its
-host planner build_chain_plan) against CPU references only -- the reference's own class bookkeeping over the oracle's GTH
+host planner plan_chains of cmdp_chain_plan.h, which is also held against a Python mirror and the promises k_chain_fast
+relies on, without a GPU) against CPU references only -- the reference's own class bookkeeping over the oracle's GTH
 (bit for bit, K7 and K9 in the reference's order) and float64 GTH in numpy (the reordered sums of the default order).
 
 The chains (helpers_chains.SUITE) are built to reach what the family MDPs never do: packed columns of more than 256
@@ -90,7 +91,7 @@ def test_generator_tables_are_well_formed(name):
 @pytest.mark.parametrize("name,b", H.instances())
 def test_generator_makes_the_intended_structure(name, b):
     """Class count, kind of the result, the class the start state is sent to, periodicity, and -- where the structure decides
-    it -- whether build_chain_plan has a plan (the minimum-degree mirror)."""
+    it -- whether plan_chains has a plan (the minimum-degree mirror)."""
     d = H.suite(name)
     m = d["meta"][b]
     t, act, start = d["t"], d["acts"][b], d["starts"][b]
@@ -207,6 +208,145 @@ def test_order_sensitivity_of_the_suite():
     print(f"measured G64 = {g[np.float64]:.3e}, G32 = {g[np.float32]:.3e}")
     assert g[np.float64] <= G64 and g[np.float32] <= G32
     assert 0 < REL64 <= CAP64 and 0 < REL32 <= CAP32
+
+
+# ---- K9F's planner and the kernel choice, through the host-only entry points ------------------------------------------------
+PLAN_ARRAYS = ("rank", "cptr", "cbase", "cand", "nrounds", "rbase", "rptr", "piv")
+
+
+@pytest.mark.parametrize("name", ["one_state", "sparse_small", "periodic", "dense_planned", "dense_unplanned", "multi_class", "mixed",
+                                  "two_components"])
+def test_plan_equals_the_python_mirror(name):
+    """All eight arrays of cmdp_chain_plan_desc equal the mirror's: S = 1 (no plan) and S = 2, 128 candidates against 129,
+    planned instances beside unplanned ones (the packing of cbase / rbase), planned or not as the generator meant, and a
+    graph of two components whose last position is listed for the last time long before the last round."""
+    from colosseum_amd.batched import chain_plan_of_tables
+
+    d = H.suite(name)
+    got, want = chain_plan_of_tables(d["t"]), H.plan_mirror(d["t"])
+    for k in PLAN_ARRAYS:
+        assert got[k].dtype == want[k].dtype, k
+        np.testing.assert_array_equal(got[k], want[k], err_msg=f"{name}: {k}")
+    for b, m in enumerate(d["meta"]):
+        if m["S"] == 1:
+            assert got["nrounds"][b] == -1
+        if m["fast"] is not None:
+            assert (got["nrounds"][b] >= 0 and m["n_classes"] == 1 and m["kind"] is np.float64) == m["fast"], (name, b)
+    planned = got["nrounds"] >= 0
+    if name in ("dense_planned", "dense_unplanned"):
+        assert planned.all() == (name == "dense_planned") and planned.any() == (name == "dense_planned")
+    if name == "mixed":
+        assert planned[0] and not planned[1] and planned[2] and not planned[3]   # a planned instance after unplanned ones
+    if name == "two_components":   # what helpers_chains.two_components says of itself
+        assert got["rank"][:13].tolist() == list(range(13)) and got["nrounds"].tolist() == [10, 1]
+        assert got["piv"][:12].tolist() == [0, 10, 1, 11, 2, 3, 4, 5, 6, 7, 8, 9]
+
+
+@pytest.mark.parametrize("name", sorted(H.SUITE) + ["refused", "two_components"])
+def test_plan_keeps_what_the_kernel_takes_on_trust(name):
+    """From the arrays of cmdp_chain_plan_desc alone, what k_chain_fast relies on (the K9F comment of cmdp_chain.h)."""
+    from colosseum_amd.batched import chain_plan_of_tables
+
+    t = H.suite(name)["t"]
+    p = chain_plan_of_tables(t)
+    off, B = t["state_off"], int(t["B"])
+    n_planned = 0
+    for b in range(B):
+        so, S = int(off[b]), int(off[b + 1] - off[b])
+        c_end = int(p["cbase"][b + 1]) if b + 1 < B else len(p["cand"])
+        r_end = int(p["rbase"][b + 1]) if b + 1 < B else len(p["rptr"])
+        nr = int(p["nrounds"][b])
+        if nr < 0:   # no plan: no room taken, nothing written
+            assert nr == -1 and c_end == p["cbase"][b] and r_end == p["rbase"][b]
+            assert (p["rank"][so: so + S] == -1).all() and not p["cptr"][so + b: so + b + S + 1].any()
+            continue
+        n_planned += 1
+        rank = p["rank"][so: so + S].astype(np.int64)
+        assert sorted(rank.tolist()) == list(range(S))
+        cp = p["cptr"][so + b: so + b + S + 1].astype(np.int64)
+        n = np.diff(cp)
+        assert cp[0] == 0 and (n >= 0).all() and n.max() <= H.K9F_MAXC and p["cbase"][b] + cp[S] == c_end
+        cand = p["cand"][int(p["cbase"][b]): c_end].astype(np.int64)
+        owner = np.repeat(np.arange(S), n)
+        assert (cand > owner).all() and (cand < S).all()                   # strictly above the pivot's position
+        assert (np.diff(cand)[np.diff(owner) == 0] > 0).all()              # ascending within a list
+        lists = np.zeros((S, S), bool)
+        lists[owner, cand] = True
+        u, v = np.nonzero(H.transition_graph(t, b))
+        up = rank[u] < rank[v]
+        assert lists[rank[u][up], rank[v][up]].all()                       # every neighbour that ranks higher is listed
+        rp = p["rptr"][int(p["rbase"][b]): r_end].astype(np.int64)
+        width = np.diff(rp)
+        assert len(rp) == nr + 1 and rp[0] == 0 and rp[-1] == S - 1 and (width >= 1).all() and (width <= H.K9F_NW).all()
+        piv = p["piv"][so: so + S - 1].astype(np.int64)
+        assert sorted(piv.tolist()) == list(range(S - 1))                  # every pivot scheduled exactly once
+        round_of = np.full(S, nr, np.int64)                                # (the last position is eliminated by nobody)
+        round_of[piv] = np.repeat(np.arange(nr), width)
+        assert (round_of[cand] > round_of[owner]).all()                    # after every lower pivot that lists it
+        f = lists.astype(np.float32)
+        for r in range(nr):
+            rnd = piv[rp[r]: rp[r + 1]]
+            assert not lists[np.ix_(rnd, rnd)].any()                       # not each other's candidates
+            common = f[rnd] @ f[rnd].T
+            assert (common[~np.eye(len(rnd), dtype=bool)] <= 1).all()      # at most one shared candidate
+    print(f"{name}: {n_planned} of {B} planned, {len(p['cand'])} candidates, {len(p['rptr'])} round offsets")
+    assert n_planned >= sum(m["fast"] is True for m in H.suite(name)["meta"])   # the checks above had something to check
+    assert n_planned == B or name != "two_components"
+
+
+def test_chain_choice_follows_the_lds_formulas():
+    from colosseum_amd import _lib as L
+    from colosseum_amd.batched import chain_choice
+
+    def shape(name):
+        t = H.suite(name)["t"]
+        return int(np.diff(t["state_off"]).max()), H.max_row_nnz(t)
+
+    for name in ("lds_gap", "at_lds_limit", "sparse_small", "dense_unplanned"):
+        S, deg = shape(name)
+        c = chain_choice(S, deg)
+        assert (c["refusal"], c["k9_lds"], c["fast_lds"]) == (L.OK, H.chain_lds_bytes(S, deg), H.chain_fast_lds_bytes(S, deg)), name
+        assert c["fast"] == (H.chain_fast_lds_bytes(S, deg) <= H.LDS_BUDGET), name
+        assert c["fast"] == {"lds_gap": False, "at_lds_limit": True}.get(name, c["fast"])   # K9 alone; both kernels
+        for kw in (dict(exact_order=True), dict(fast_enabled=False), dict(any_plan=False)):
+            c = chain_choice(S, deg, **kw)
+            assert c["refusal"] == L.OK and not c["fast"] and c["k9_lds"] == H.chain_lds_bytes(S, deg), (name, kw)
+    assert shape("at_lds_limit") == (H.S_MAX4, 4) and shape("refused") == (H.S_MAX4 + 1, 4)
+    for kw in ({}, dict(exact_order=True), dict(fast_enabled=False)):
+        assert chain_choice(*shape("refused"), **kw)["refusal"] == L.ERR_UNSUPPORTED
+
+
+def test_plan_entry_points_reject_bad_arguments():
+    from colosseum_amd import _lib as L
+    from colosseum_amd.batched import chain_plan_of_tables, desc_from_tables
+
+    lib = L.load()
+    t = H.suite("sparse_small")["t"]
+    NS, B = int(t["state_off"][-1]), int(t["B"])
+    n_cand = len(chain_plan_of_tables(t)["cand"])
+    d, keep = desc_from_tables(t, L.RNG_PHILOX)
+    arr = dict(rank=np.zeros(NS, np.int32), cptr=np.zeros(NS + B, np.int32), cbase=np.zeros(B, np.int64), cand=np.zeros(n_cand, np.uint16),
+               nrounds=np.zeros(B, np.int32), rbase=np.zeros(B, np.int64), rptr=np.zeros(NS + B, np.int32), piv=np.zeros(NS, np.int32))
+    n = C.c_int64()
+
+    def call(desc, capacity=n_cand, n_out=C.byref(n), **nulls):
+        a = {k: None if k in nulls else L.ptr(v) for k, v in arr.items()}
+        return lib.cmdp_chain_plan_desc(desc, a["rank"], a["cptr"], a["cbase"], a["cand"], capacity, n_out, a["nrounds"], a["rbase"],
+                                        a["rptr"], a["piv"])
+
+    assert call(C.byref(d)) == L.OK and n.value == n_cand            # exactly enough room
+    n.value = 0
+    assert call(C.byref(d), capacity=n_cand - 1) == L.ERR_INVALID and n.value == n_cand   # one short: says how many
+    for k in arr:
+        assert call(C.byref(d), **{k: True}) == L.ERR_INVALID, k
+    assert call(C.byref(d), n_out=None) == L.ERR_INVALID and call(None) == L.ERR_INVALID
+    bare, keep2 = desc_from_tables({k: v for k, v in t.items() if not k.startswith("csr_")}, L.RNG_PHILOX)
+    assert call(C.byref(bare)) == L.ERR_INVALID and b"DP half" in lib.cmdp_last_error()
+    bad = dict(t, csr_col=np.where(np.arange(len(t["csr_col"])) == 5, 99, t["csr_col"]).astype(np.int32))
+    d3, keep3 = desc_from_tables(bad, L.RNG_PHILOX)
+    assert call(C.byref(d3)) == L.ERR_INVALID
+    out = np.zeros(4, np.int64)
+    assert lib.cmdp_chain_choice(10, 4, 0, 1, 1, None) == L.ERR_INVALID and lib.cmdp_chain_choice(0, 4, 0, 1, 1, L.ptr(out)) == L.ERR_INVALID
 
 
 # ---- device tests -----------------------------------------------------------------------------------------------------------
