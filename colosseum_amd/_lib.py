@@ -52,6 +52,17 @@ K1S_PLAN_FIELDS = ("ok", "G", "nw", "gw", "team", "U", "n_pat", "n_codes", "rewa
                    "ch", "form")
 K1S_REWARD_SOURCES = ("packed", "state_table", "row")
 K1S_FORMS = {0: "generic", **{t * 4 + i: f"team{t}_{src}" for t in (16, 8, 1) for i, src in enumerate(K1S_REWARD_SOURCES)}}
+# cmdp_det_plan / cmdp_det_plan_desc: the fields of K1L / K1P, K1T and K1U in the order of include/cmdp.h, the names of the two
+# `form` fields (what launch_k1lp / launch_k1u branch on) and the order of the knobs cmdp_det_plan_desc takes
+DET_PLAN_FIELDS = {
+    "k1lp": ("ok", "pipe", "packed", "code_shift", "succ_bits", "n_codes", "ch", "G", "per_cu", "capacity", "slot_bytes", "lds_bytes",
+             "form"),
+    "k1t": ("ok", "automatic", "ch", "G", "capacity", "slot_bytes", "tmpl_bytes", "lds_bytes"),
+    "k1u": ("ok", "automatic", "pack10", "ch", "G", "capacity", "lds_bytes", "hist_lds_bytes", "form"),
+}
+K1LP_FORMS = {0: "k1l_unpacked", 1: "k1l_packed", 2: "k1p"}
+K1U_FORMS = {0: "pack10", 1: "wide"}
+DET_PLAN_KNOBS = ("pipe", "k1l_G", "k1t_G", "k1u_G", "k1t_ch")   # CMDP_K1L_PIPE, CMDP_K1L_G, CMDP_K1T_G, CMDP_K1U_G, CMDP_K1T_CH
 
 EXPORTS = [
     "cmdp_version", "cmdp_build_id", "cmdp_last_error", "cmdp_device_count", "cmdp_set_device", "cmdp_create", "cmdp_destroy",
@@ -65,7 +76,7 @@ EXPORTS = [
     "cmdp_ucrl2_set_option",
     "cmdp_psrl_create", "cmdp_psrl_destroy", "cmdp_psrl_run", "cmdp_psrl_layout", "cmdp_psrl_model", "cmdp_psrl_last_sample",
     "cmdp_psrl_reference_sample", "cmdp_vi_episodic_dense", "cmdp_psrl_episode_end_update", "cmdp_k1e_round_interior",
-    "cmdp_k1e_code_counts", "cmdp_k1s_plan", "cmdp_k1s_plan_desc", "cmdp_chain_plan_desc", "cmdp_chain_choice",
+    "cmdp_k1e_code_counts", "cmdp_k1s_plan", "cmdp_k1s_plan_desc", "cmdp_det_plan", "cmdp_det_plan_desc", "cmdp_chain_plan_desc", "cmdp_chain_choice",
 ]
 
 
@@ -232,6 +243,8 @@ def load():
         L.cmdp_k1e_code_counts.argtypes = [C.c_uint32, C.c_uint32, i32]
         L.cmdp_k1s_plan.argtypes = [vp, vp]
         L.cmdp_k1s_plan_desc.argtypes = [C.POINTER(CmdpDesc), i32, i32, vp]
+        L.cmdp_det_plan.argtypes = [vp, vp]
+        L.cmdp_det_plan_desc.argtypes = [C.POINTER(CmdpDesc), i32, vp, vp]
         L.cmdp_chain_plan_desc.argtypes = [C.POINTER(CmdpDesc), vp, vp, vp, vp, i64, vp, vp, vp, vp, vp]
         L.cmdp_chain_choice.argtypes = [i32, i32, i32, i32, i32, vp]
         L.cmdp_k1e_code_counts.restype = C.c_uint32

@@ -104,6 +104,33 @@ def k1s_plan_of_tables(tables: dict, cus: int = 256, instances_per_workgroup: in
     return _k1s_plan_dict(out)
 
 
+def _det_plan_dict(out) -> dict:
+    plan, i = {}, 0
+    for kernel, fields in L.DET_PLAN_FIELDS.items():
+        d = {k: int(v) for k, v in zip(fields, out[i:i + len(fields)])}
+        i += len(fields)
+        for k in ("ok", "pipe", "packed", "automatic", "pack10"):
+            if k in d:
+                d[k] = bool(d[k])
+        if "form" in d:
+            d["form"] = (L.K1LP_FORMS if kernel == "k1lp" else L.K1U_FORMS)[d["form"]] if d["ok"] else None
+        plan[kernel] = d
+    return plan
+
+
+def det_plan_of_tables(tables: dict, cus: int = 256, pipe: Optional[int] = None, k1l_G: int = 0, k1t_G: int = 0, k1u_G: int = 0,
+                       k1t_ch: int = 0, rng_mode: int = L.RNG_PHILOX, layout: int = L.LAYOUT_CSR, flags: int = 0) -> dict:
+    """The plans of K1L / K1P, K1T and K1U a `BatchedMDP(tables=tables, ...)` would get on a device of `cus` compute units
+    (cmdp_det_plan_desc: host only, needs no GPU).  The knobs stand for CMDP_K1L_PIPE (None: planned), CMDP_K1L_G, CMDP_K1T_G,
+    CMDP_K1U_G and CMDP_K1T_CH (0: planned); the environment is not read.  Keys as `BatchedMDP.det_plan`."""
+    d, keep = desc_from_tables(tables, rng_mode, None, layout, flags)
+    knobs = np.array([-1 if pipe is None else int(pipe), k1l_G, k1t_G, k1u_G, k1t_ch], np.int32)
+    out = np.zeros(sum(len(f) for f in L.DET_PLAN_FIELDS.values()), np.int32)
+    L.check(L.load().cmdp_det_plan_desc(C.byref(d), int(cus), L.ptr(knobs), L.ptr(out)))
+    del keep
+    return _det_plan_dict(out)
+
+
 def chain_plan_of_tables(tables: dict) -> dict:
     """K9F's plan of a continuous batch with its DP half (cmdp_chain_plan_desc: host only, needs no GPU): the eight arrays
     the first `average_reward` call uploads, under ChainFast's names (csrc/cmdp_chain.h); `rptr` cut to the offsets written."""
@@ -275,6 +302,14 @@ class BatchedMDP:
         out = np.zeros(len(L.K1S_PLAN_FIELDS), np.int32)
         L.check(self._lib.cmdp_k1s_plan(self._h, L.ptr(out)))
         return _k1s_plan_dict(out)
+
+    def det_plan(self) -> dict:
+        """The plans of the deterministic LDS-resident rollouts made for this batch (cmdp_det_plan): {"k1lp": ..., "k1t": ...,
+        "k1u": ...} with the fields of `_lib.DET_PLAN_FIELDS`; `form` is what the launcher branches on ("k1l_unpacked" /
+        "k1l_packed" / "k1p", and "pack10" / "wide"; None when the batch is not eligible for the kernel)."""
+        out = np.zeros(sum(len(f) for f in L.DET_PLAN_FIELDS.values()), np.int32)
+        L.check(self._lib.cmdp_det_plan(self._h, L.ptr(out)))
+        return _det_plan_dict(out)
 
     def set_option(self, option: int, value: int):
         L.check(self._lib.cmdp_set_option(self._h, int(option), int(value)))

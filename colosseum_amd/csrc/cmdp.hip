@@ -189,6 +189,8 @@ struct cmdp {
   // LDS-resident rollout (K1L)
   bool lds_ok = false;
   int lds_G1 = 0, lds_G2 = 0;  // LDS capacity in instances per workgroup at one / two workgroups per CU
+  int lds_succ_bits = 0, lds_per_cu = 0;   // (cmdp_det_plan) bits of a row base; workgroups per CU of the chosen candidate
+  int tmpl_cap = 0, k1u_cap = 0;           // (cmdp_det_plan) LDS capacity in instances per workgroup of K1T / K1U
   int cus = 256;
   int rollout_kernel = 0;  // CMDP_OPT_ROLLOUT_KERNEL
   LdsPlan lds_plan{};
@@ -612,6 +614,8 @@ static int install_rollout_plans(cmdp_t* h, const cmdp_desc* d, const std::vecto
   h->lds_bytes = k1l_lds_bytes(lp.p, lp.p.G);
   h->lds_G1 = lp.G1;
   h->lds_G2 = lp.G2;
+  h->lds_succ_bits = lp.succ_bits;
+  h->lds_per_cu = lp.per_cu;
   h->lds_ok = true;
   if (kt.ok) {   // eligible: CMDP_OPT_ROLLOUT_KERNEL 4 may force it, and the automatic choice when it needs fewer rounds x time
     HIP_TRY(h->d_tmpl_words.upload(kt.words.data(), kt.words.size(), st));
@@ -621,6 +625,7 @@ static int install_rollout_plans(cmdp_t* h, const cmdp_desc* d, const std::vecto
     h->tmpl_lds = k1t_lds_bytes(kt.q, kt.q.G);
     h->tmpl_ok = true;
     h->tmpl_auto = kt.autos;
+    h->tmpl_cap = kt.cap;
   }
   if (ku.ok) {
     h->k1u = ku.u;
@@ -628,6 +633,7 @@ static int install_rollout_plans(cmdp_t* h, const cmdp_desc* d, const std::vecto
     h->k1u_lds = k1u_lds_bytes(ku.u, ku.u.G);
     h->k1u_ok = true;
     h->k1u_auto = ku.autos;
+    h->k1u_cap = ku.cap;
   }
   if (ke.ok) {
     HIP_TRY(h->d_etab.upload(ke.etab.data(), ke.etab.size(), st));
@@ -1211,11 +1217,12 @@ static int launch_k1u(cmdp_t* h, const RolloutCall& c) {
   if (!h->ev_time[0])   // (timestamps only: no host-visibility cache flush per launch)
     for (int i = 0; i < 5; ++i) HIP_TRY(hipEventCreateWithFlags(&h->ev_time[i], hipEventDisableSystemFence));
   K1uPlan u = h->k1u;
-  const int epp = K1U_EPP(u.pack10);
+  const bool pack10 = k1u_form(u) == K1U_FORM_PACK10;
+  const int epp = K1U_EPP(pack10);
   const size_t need = (size_t)((std::min<int64_t>(c.n, K1U_SEG) + epp - 1) / epp) * (size_t)h->B;
   const size_t hist_lds = k1h_lds_bytes(h->max_S, 64);
-  if (int rc = u.pack10 ? set_lds(k_rollout_tmpl_stream<true>, h->k1u_lds) : set_lds(k_rollout_tmpl_stream<false>, h->k1u_lds)) return rc;
-  if (int rc = u.pack10 ? set_lds(k_trace_hist<64, 1024, true>, hist_lds) : set_lds(k_trace_hist<64, 1024, false>, hist_lds)) return rc;
+  if (int rc = pack10 ? set_lds(k_rollout_tmpl_stream<true>, h->k1u_lds) : set_lds(k_rollout_tmpl_stream<false>, h->k1u_lds)) return rc;
+  if (int rc = pack10 ? set_lds(k_trace_hist<64, 1024, true>, hist_lds) : set_lds(k_trace_hist<64, 1024, false>, hist_lds)) return rc;
   if (h->d_k1u_trace.n < need && h->d_k1u_trace.alloc(need) != hipSuccess) {
     // no room for the trace (16 bytes per 8-12 transitions and instance; every segment of a launch uses the one buffer)
     (void)hipGetLastError();
@@ -1229,10 +1236,10 @@ static int launch_k1u(cmdp_t* h, const RolloutCall& c) {
     const int64_t n = std::min<int64_t>(K1U_SEG, c.n - s0);
     const bool last = s0 + K1U_SEG >= c.n;
     if (last) HIP_TRY(hipEventRecord(h->ev_time[0], st));
-    if (u.pack10) hipLaunchKernelGGL(k_rollout_tmpl_stream<true>, rgrid, rblock, h->k1u_lds, st, t, u, n, c.rsum, c.last, s0 > 0 ? 1 : 0);
+    if (pack10) hipLaunchKernelGGL(k_rollout_tmpl_stream<true>, rgrid, rblock, h->k1u_lds, st, t, u, n, c.rsum, c.last, s0 > 0 ? 1 : 0);
     else hipLaunchKernelGGL(k_rollout_tmpl_stream<false>, rgrid, rblock, h->k1u_lds, st, t, u, n, c.rsum, c.last, s0 > 0 ? 1 : 0);
     if (last) HIP_TRY(hipEventRecord(h->ev_time[1], st));
-    if (u.pack10) hipLaunchKernelGGL((k_trace_hist<64, 1024, true>), hgrid, hblock, hist_lds, st, t, u.trace, u.seg_resets, n, u.code_shift);
+    if (pack10) hipLaunchKernelGGL((k_trace_hist<64, 1024, true>), hgrid, hblock, hist_lds, st, t, u.trace, u.seg_resets, n, u.code_shift);
     else hipLaunchKernelGGL((k_trace_hist<64, 1024, false>), hgrid, hblock, hist_lds, st, t, u.trace, u.seg_resets, n, u.code_shift);
     if (last) HIP_TRY(hipEventRecord(h->ev_time[2], st));
   }
@@ -1252,10 +1259,11 @@ static int launch_k1t(cmdp_t* h, const RolloutCall& c) {
 static int launch_k1lp(cmdp_t* h, const RolloutCall& c) {
   hipStream_t st = h->stream; EnvTables t = h->env();
   const dim3 lgrid(grid_for(h->B, h->lds_plan.G)), lblock(K1L_THREADS);
-  if (h->lds_plan.pipe) {
+  const int form = k1lp_form(h->lds_plan);
+  if (form == K1LP_FORM_PIPE) {
     if (int rc = set_lds(k_rollout_pipe, h->lds_bytes)) return rc;
     hipLaunchKernelGGL(k_rollout_pipe, lgrid, dim3(K1P_THREADS), h->lds_bytes, st, t, h->lds_plan, c.n, c.rsum, c.last);
-  } else if (h->lds_plan.code_shift) {
+  } else if (form == K1LP_FORM_PACKED) {
     if (int rc = set_lds(k_rollout_lds<true>, h->lds_bytes)) return rc;
     hipLaunchKernelGGL(k_rollout_lds<true>, lgrid, lblock, h->lds_bytes, st, t, h->lds_plan, c.n, c.rsum, c.last);
   } else {
@@ -1439,6 +1447,7 @@ int cmdp_set_option(cmdp_t* h, int option, int64_t value) {
     const int cap = value == 1 ? h->lds_G1 : h->lds_G2;
     if (cap < 1) return fail(CMDP_ERR_INVALID, "no room for %lld workgroups per CU", (long long)value);
     h->lds_plan.G = even_groups(h->B, cap, (int64_t)h->cus * value).G;   // (as cmdp_create plans it)
+    h->lds_per_cu = (int)value;
     h->lds_bytes = k1l_lds_bytes(h->lds_plan, h->lds_plan.G);
     return CMDP_OK;
   }
@@ -1498,12 +1507,12 @@ int cmdp_k1s_plan(cmdp_t* h, int32_t out[CMDP_K1S_PLAN_FIELDS]) {
   return CMDP_OK;
 }
 
-int cmdp_k1s_plan_desc(const cmdp_desc* d, int cus, int instances_per_workgroup, int32_t out[CMDP_K1S_PLAN_FIELDS]) {
-  if (!d || !out || cus < 1 || instances_per_workgroup < 0) return fail(CMDP_ERR_INVALID, "bad argument");
+// As much of cmdp_create's validation of a bare description as the planners index by, and their input: row descriptors,
+// the largest state count, whether any reward is a Beta entry.  `who` names the caller in the message.
+static int plan_input_of_desc(const cmdp_desc* d, int cus, const char* who, std::vector<RowDesc>* rows, PlanInput* in, bool* any_beta) {
   if (d->n_instances < 1 || d->n_actions < 1 || !d->state_off || !d->sp_ptr || !d->sp_next || !d->sp_cum || !d->sp_reward ||
       !d->start_off)
-    return fail(CMDP_ERR_INVALID, "cmdp_k1s_plan_desc needs the sampler half of the description");
-  // as much of cmdp_create's validation as the planners index by
+    return fail(CMDP_ERR_INVALID, "%s needs the sampler half of the description", who);
   const int B = d->n_instances, A = d->n_actions;
   int max_S = 0;
   if (d->state_off[0] != 0 || d->sp_ptr[0] != 0 || d->start_off[0] != 0) return fail(CMDP_ERR_INVALID, "offsets do not start at 0");
@@ -1514,8 +1523,8 @@ int cmdp_k1s_plan_desc(const cmdp_desc* d, int cus, int instances_per_workgroup,
     max_S = std::max<int>(max_S, (int)S);
   }
   const int64_t R = d->state_off[B] * A;
-  std::vector<RowDesc> rows((size_t)R);
-  bool any_beta = false;
+  rows->resize((size_t)R);
+  *any_beta = false;
   for (int b = 0; b < B; ++b) {
     const int64_t S = d->state_off[b + 1] - d->state_off[b];
     for (int64_t r = d->state_off[b] * A; r < d->state_off[b + 1] * A; ++r) {
@@ -1523,25 +1532,78 @@ int cmdp_k1s_plan_desc(const cmdp_desc* d, int cus, int instances_per_workgroup,
       if (n < 1 || n > 4096) return fail(CMDP_ERR_INVALID, "row %lld has %lld successors", (long long)r, (long long)n);
       for (int64_t e = lo; e < lo + n; ++e) {
         if (d->sp_next[e] < 0 || d->sp_next[e] >= S) return fail(CMDP_ERR_INVALID, "successor index out of range at entry %lld", (long long)e);
-        any_beta |= d->sp_rkind && d->sp_rkind[e] != 0;
+        *any_beta |= d->sp_rkind && d->sp_rkind[e] != 0;
       }
       RowDesc rd{};
       rd.n = (int32_t)n;
       rd.next_if_det = d->sp_next[lo];
       rd.reward_if_det = d->sp_reward[lo];
-      rows[(size_t)r] = rd;
+      (*rows)[(size_t)r] = rd;
     }
   }
+  *in = PlanInput{d, rows->data(), B, A, d->horizon, max_S, cus};
+  return CMDP_OK;
+}
+
+// the rewards are the table's values (install_rollout_plans: neither sampled Beta rewards nor reward caches)
+static bool desc_table_rewards(const cmdp_desc* d, bool any_beta) {
+  return !any_beta || (d->flags & (CMDP_FLAG_REWARD_MEANS | CMDP_FLAG_REWARD_CACHE)) == CMDP_FLAG_REWARD_MEANS;
+}
+
+int cmdp_k1s_plan_desc(const cmdp_desc* d, int cus, int instances_per_workgroup, int32_t out[CMDP_K1S_PLAN_FIELDS]) {
+  if (!d || !out || cus < 1 || instances_per_workgroup < 0) return fail(CMDP_ERR_INVALID, "bad argument");
+  std::vector<RowDesc> rows;
+  PlanInput in{};
+  bool any_beta = false;
+  if (int rc = plan_input_of_desc(d, cus, "cmdp_k1s_plan_desc", &rows, &in, &any_beta)) return rc;
   // cmdp_create plans K1S for the Philox batches with table rewards that K1L / K1P refuse (install_rollout_plans)
-  const PlanInput in{d, rows.data(), B, A, d->horizon, max_S, cus};
   PlanKnobs knobs;
   knobs.k1s_G = instances_per_workgroup;
   K1sChoice ks;
-  const bool table_rewards = !any_beta || (d->flags & (CMDP_FLAG_REWARD_MEANS | CMDP_FLAG_REWARD_CACHE)) == CMDP_FLAG_REWARD_MEANS;
+  const bool table_rewards = desc_table_rewards(d, any_beta);
   DetTables t;
   if (table_rewards && d->rng_mode == CMDP_RNG_PHILOX && d->layout == CMDP_LAYOUT_CSR && !(det_tables(in, &t) && plan_k1lp(in, t, knobs).ok))
     ks = plan_k1s(in, knobs);
   k1s_plan_report(ks.ok, ks.p, out);
+  return CMDP_OK;
+}
+
+int cmdp_det_plan(cmdp_t* h, int32_t out[CMDP_DET_PLAN_FIELDS]) {
+  if (!h || !out) return fail(CMDP_ERR_INVALID, "bad argument");
+  DetPlans d;
+  d.lds_ok = h->lds_ok; d.lp = h->lds_plan; d.succ_bits = h->lds_succ_bits; d.per_cu = h->lds_per_cu;
+  d.lp_cap = h->lds_per_cu == 2 ? h->lds_G2 : h->lds_G1;
+  d.tmpl_ok = h->tmpl_ok; d.tmpl_auto = h->tmpl_auto; d.kt = h->tmpl_plan; d.kt_cap = h->tmpl_cap;
+  d.k1u_ok = h->k1u_ok; d.k1u_auto = h->k1u_auto; d.ku = h->k1u; d.ku_cap = h->k1u_cap; d.max_S = h->max_S;
+  det_plan_report(d, out);
+  return CMDP_OK;
+}
+
+int cmdp_det_plan_desc(const cmdp_desc* d, int cus, const int32_t knobs_in[5], int32_t out[CMDP_DET_PLAN_FIELDS]) {
+  if (!d || !out || cus < 1) return fail(CMDP_ERR_INVALID, "bad argument");
+  std::vector<RowDesc> rows;
+  PlanInput in{};
+  bool any_beta = false;
+  if (int rc = plan_input_of_desc(d, cus, "cmdp_det_plan_desc", &rows, &in, &any_beta)) return rc;
+  PlanKnobs knobs;
+  if (knobs_in) {
+    knobs.pipe = knobs_in[0] < 0 ? -1 : knobs_in[0];
+    knobs.k1l_G = std::max(0, knobs_in[1]);
+    knobs.k1t_G = std::max(0, knobs_in[2]);
+    knobs.k1u_G = std::max(0, knobs_in[3]);
+    knobs.k1t_ch = std::max(0, knobs_in[4]);
+  }
+  // as install_rollout_plans (a batch that passes det_tables has no MT19937 slots: its rows and starts draw nothing)
+  DetTables t;
+  K1lpChoice lp;
+  if (desc_table_rewards(d, any_beta) && det_tables(in, &t)) lp = plan_k1lp(in, t, knobs);
+  K1tChoice kt;
+  K1uChoice ku;
+  if (lp.ok) {
+    kt = plan_k1t(in, t, lp, knobs);
+    ku = plan_k1u(in, kt, knobs);
+  }
+  det_plan_report(det_plans_of(lp, kt, ku, in.max_S), out);
   return CMDP_OK;
 }
 

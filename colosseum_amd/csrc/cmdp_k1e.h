@@ -500,6 +500,7 @@ __global__ void __launch_bounds__(K1E_THREADS) __attribute__((amdgpu_waves_per_e
       const unsigned long long resets = (unsigned long long)(((int64_t)h0 + n_steps) / H);
       t.n_trans[b] = ntr + (unsigned long long)n_steps;
       t.n_reset[b] += resets;
+      if (resets) t.prev_start[b] = t.last_start[b];   // (as K1L: env_reset's bookkeeping of the one start state)
       p.seg_h0[b] = h0;
       if (!(p.debug & 2)) p.dep_res[b] += (int32_t)resets;   // episode resets: they count the start state (k_epi_fold)
     }

@@ -368,6 +368,7 @@ __global__ void __launch_bounds__(K1T_THREADS) k_rollout_tmpl(EnvTables t, TmplP
     t.hstep[bo] = h;
     t.n_trans[bo] = my_ntr + (unsigned long long)n_steps;
     t.n_reset[bo] += (unsigned long long)n_resets_total;
+    if (n_resets_total) t.prev_start[bo] = t.last_start[bo];   // (as K1L)
     if (last_obs) last_obs[bo] = cur;  // the state after the last transition (the start state after a termination)
   }
   if (wave >= 4 && wave < 6 && owner && reward_sum) reward_sum[b] = sum;

@@ -52,7 +52,8 @@ __host__ __device__ inline size_t k1u_lds_bytes(const K1uPlan& p, int g) {
   return (size_t)K1U_FIXED + (size_t)p.tmpl_bytes + (size_t)g * (size_t)(p.slot_bytes + 2 * K1P_ACT_STRIDE(p.ch) + 2 * K1P_TR_STRIDE(p.ch));
 }
 __host__ __device__ inline int k1h_stride_dwords(int S) { return S | 1; }   // one dword per state (two 16-bit counters), odd stride
-__host__ __device__ inline size_t k1h_lds_bytes(int S, int G) { return (size_t)G * 4 * (size_t)k1h_stride_dwords(S); }
+__host__ __device__ inline size_t k1h_lds_bytes(int S, int G) { return (size_t)G * 4 * (size_t)k1h_stride_dwords(S); }   // dynamic LDS
+#define K1H_STATIC_BYTES(G) (2 * (G) * 4)   // start_of[G], resets_of[G] of k_trace_hist: static LDS on top of the counters
 
 template <bool PACK10>
 __global__ void __launch_bounds__(K1U_THREADS) k_rollout_tmpl_stream(EnvTables t, K1uPlan p, int64_t n_steps,
@@ -263,6 +264,7 @@ __global__ void __launch_bounds__(K1U_THREADS) k_rollout_tmpl_stream(EnvTables t
     t.hstep[b] = h;
     t.n_trans[b] = my_ntr + (unsigned long long)n_steps;
     t.n_reset[b] += (unsigned long long)n_resets;
+    if (n_resets) t.prev_start[b] = t.last_start[b];   // (as K1L)
     p.seg_resets[b] = n_resets;
     if (last_obs) last_obs[b] = cur;
   }

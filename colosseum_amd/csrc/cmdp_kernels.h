@@ -704,6 +704,7 @@ __global__ void __launch_bounds__(K1L_THREADS) k_rollout_lds(EnvTables t, LdsPla
     t.hstep[b] = h;
     t.n_trans[b] = nt0 + (unsigned long long)n_steps;
     t.n_reset[b] = nr + (unsigned long long)n_resets_total;
+    if (n_resets_total) t.prev_start[b] = t.last_start[b];   // as env_reset at every termination: the start before the latest one is this (only) start state too
     if (reward_sum) reward_sum[b] = sum;
     if (last_obs) last_obs[b] = cur;  // the state after the last transition (the start state after a termination)
   }
@@ -1012,6 +1013,7 @@ __global__ void __launch_bounds__(K1P_THREADS) k_rollout_pipe(EnvTables t, LdsPl
     t.hstep[b] = h;
     t.n_trans[b] = my_ntr + (unsigned long long)n_steps;
     t.n_reset[b] += (unsigned long long)n_resets_total;
+    if (n_resets_total) t.prev_start[b] = t.last_start[b];   // (as K1L)
     if (last_obs) last_obs[b] = cur;  // the state after the last transition (the start state after a termination)
   }
   if (wave == 4 && owner && reward_sum) reward_sum[b] = sum;

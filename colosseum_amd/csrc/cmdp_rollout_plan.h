@@ -38,6 +38,8 @@ struct PlanKnobs {
   int pipe = -1;               // CMDP_K1L_PIPE: 0 plans K1L only, 1 K1P only
   int k1t_G = 0, k1u_G = 0;    // CMDP_K1T_G / CMDP_K1U_G: instances per workgroup (0: planned)
   int k1s_G = 0;               // CMDP_K1S_G: likewise for K1S (walker wavefronts and team size follow from it)
+  int k1l_G = 0;               // CMDP_K1L_G: likewise for K1L / K1P, at the candidate the planner chose
+  int k1t_ch = 0;              // CMDP_K1T_CH: 64 | 32 | 16 plans K1T at that chunk length only (0: planned)
   int k1t_debug = 0, k1e_debug = 0;   // CMDP_K1T_DEBUG / CMDP_K1E_DEBUG: stages switched off (timing experiments only)
 };
 inline PlanKnobs plan_knobs() {
@@ -47,6 +49,8 @@ inline PlanKnobs plan_knobs() {
   k.k1t_G = std::getenv("CMDP_K1T_G") ? std::max(1, num("CMDP_K1T_G", 0)) : 0;
   k.k1u_G = std::getenv("CMDP_K1U_G") ? std::max(1, num("CMDP_K1U_G", 0)) : 0;
   k.k1s_G = std::getenv("CMDP_K1S_G") ? std::max(1, num("CMDP_K1S_G", 0)) : 0;
+  k.k1l_G = std::getenv("CMDP_K1L_G") ? std::max(1, num("CMDP_K1L_G", 0)) : 0;
+  k.k1t_ch = std::max(0, num("CMDP_K1T_CH", 0));
   k.k1t_debug = num("CMDP_K1T_DEBUG", 0);
   k.k1e_debug = num("CMDP_K1E_DEBUG", 0);
   return k;
@@ -101,6 +105,7 @@ struct K1lpChoice {
   LdsPlan p{};
   double cost = -1.0;    // rounds x time per transition of the chosen candidate
   int G1 = 0, G2 = 0;    // LDS capacity in instances per workgroup at one / two workgroups per CU
+  int per_cu = 0;        // workgroups per CU of the chosen candidate
   int succ_bits = 1;     // bits of a row base (successor * A)
   bool pipe_ok = false;  // the packed words have room for K1P's byte offsets (one more bit)
 };
@@ -155,9 +160,10 @@ inline K1lpChoice plan_k1lp(const PlanInput& in, const DetTables& t, const PlanK
       c.cost = cost;
       p.ch = cd.ch;
       p.pipe = cd.pipe;
-      p.G = eg.G;
+      p.G = k.k1l_G ? std::min(g, k.k1l_G) : eg.G;
       c.G1 = g1;
       c.G2 = g2;
+      c.per_cu = per_cu;
     }
   }
   c.ok = c.cost >= 0;
@@ -189,6 +195,7 @@ struct K1tChoice {
   bool ok = false;
   bool autos = false;               // the automatic choice: fewer rounds x time than K1L / K1P
   TmplPlan q{};
+  int cap = 0;                      // LDS capacity in instances per workgroup at the chosen chunk length
   std::vector<uint16_t> words;      // [tmpl_bytes / 2] the template: instance 0's words
   std::vector<uint8_t> swap_bits;   // [B][mask_bytes]
 };
@@ -225,6 +232,7 @@ inline K1tChoice plan_k1t(const PlanInput& in, const DetTables& t, const K1lpCho
   // instructions than K1P's: ~1.3 x its time per transition), as for K1L / K1P
   double best = -1.0;
   for (int ch : {64, 32, 16}) {
+    if (k.k1t_ch && ch != k.k1t_ch) continue;
     const int per = q.slot_bytes + 2 * K1P_ACT_STRIDE(ch) + 2 * K1P_TR_STRIDE(ch);
     const int cap = std::min<int>(128, (kLdsBudget - K1T_FIXED - q.tmpl_bytes) / per);
     if (cap < 16) continue;
@@ -234,6 +242,7 @@ inline K1tChoice plan_k1t(const PlanInput& in, const DetTables& t, const K1lpCho
     best = cost;
     q.ch = ch;
     q.G = k.k1t_G ? std::min(cap, k.k1t_G) : eg.G;
+    c.cap = cap;
   }
   if (best < 0) return c;
   c.ok = true;
@@ -253,6 +262,7 @@ inline K1tChoice plan_k1t(const PlanInput& in, const DetTables& t, const K1lpCho
 struct K1uChoice {
   bool ok = false, autos = false;
   K1uPlan u{};
+  int cap = 0;   // LDS capacity in instances per workgroup
 };
 
 inline K1uChoice plan_k1u(const PlanInput& in, const K1tChoice& kt, const PlanKnobs& k) {
@@ -268,9 +278,12 @@ inline K1uChoice plan_k1u(const PlanInput& in, const K1tChoice& kt, const PlanKn
   u.ch = u.pack10 ? 72 : 64;
   const int per = u.slot_bytes + 2 * K1P_ACT_STRIDE(u.ch) + 2 * K1P_TR_STRIDE(u.ch);
   const int cap = std::min<int>(256, (kLdsBudget - K1U_FIXED - u.tmpl_bytes) / per);
-  if (cap < 64 || k1h_lds_bytes(in.max_S, 64) > (size_t)kLdsBudget) return c;
+  // (the histogram kernel's workgroup: its counters and its static arrays -- without the latter 638 and 639 states were
+  // planned and every launch of theirs failed)
+  if (cap < 64 || k1h_lds_bytes(in.max_S, 64) + K1H_STATIC_BYTES(64) > (size_t)kLdsBudget) return c;
   const EvenGroups eg = even_groups(in.B, cap, in.cus);
   u.G = k.k1u_G ? std::min(cap, k.k1u_G) : eg.G;
+  c.cap = cap;
   c.ok = true;
   c.autos = kt.autos && eg.rounds < even_groups(in.B, q.G, in.cus).rounds;
   return c;
@@ -468,3 +481,52 @@ inline K1sChoice plan_k1s(const PlanInput& in, const PlanKnobs& knobs) {
   c.ok = true;
   return c;
 }
+
+// ---- cmdp_det_plan / cmdp_det_plan_desc: the plans of the deterministic kernels, as tests read them ----------------
+// The compiled form a launch takes.  launch_k1lp / launch_k1u branch on these very functions, and the plan report names
+// what they return.
+enum { K1LP_FORM_UNPACKED = 0, K1LP_FORM_PACKED = 1, K1LP_FORM_PIPE = 2 };
+inline int k1lp_form(const LdsPlan& p) { return p.pipe ? K1LP_FORM_PIPE : (p.code_shift ? K1LP_FORM_PACKED : K1LP_FORM_UNPACKED); }
+enum { K1U_FORM_PACK10 = 0, K1U_FORM_WIDE = 1 };
+inline int k1u_form(const K1uPlan& u) { return u.pack10 ? K1U_FORM_PACK10 : K1U_FORM_WIDE; }
+
+struct DetPlans {
+  bool lds_ok = false, tmpl_ok = false, tmpl_auto = false, k1u_ok = false, k1u_auto = false;
+  LdsPlan lp{};
+  int succ_bits = 0, per_cu = 0, lp_cap = 0;   // of the chosen K1L / K1P candidate
+  TmplPlan kt{};
+  int kt_cap = 0;
+  K1uPlan ku{};
+  int ku_cap = 0, max_S = 0;
+};
+
+inline DetPlans det_plans_of(const K1lpChoice& lp, const K1tChoice& kt, const K1uChoice& ku, int max_S) {
+  DetPlans d;
+  d.lds_ok = lp.ok; d.lp = lp.p; d.succ_bits = lp.succ_bits; d.per_cu = lp.per_cu; d.lp_cap = lp.per_cu == 2 ? lp.G2 : lp.G1;
+  d.tmpl_ok = kt.ok; d.tmpl_auto = kt.autos; d.kt = kt.q; d.kt_cap = kt.cap;
+  d.k1u_ok = ku.ok; d.k1u_auto = ku.autos; d.ku = ku.u; d.ku_cap = ku.cap; d.max_S = max_S;
+  return d;
+}
+
+// the fields in the order include/cmdp.h gives; those of a kernel the batch is not eligible for are 0
+inline void det_plan_report(const DetPlans& d, int32_t out[CMDP_DET_PLAN_FIELDS]) {
+  std::fill(out, out + CMDP_DET_PLAN_FIELDS, 0);
+  if (d.lds_ok) {
+    const LdsPlan& p = d.lp;
+    const int32_t v[13] = {1, p.pipe, p.code_shift ? 1 : 0, p.code_shift, d.succ_bits, p.n_codes, p.ch, p.G, d.per_cu, d.lp_cap,
+                           p.slot_bytes, (int32_t)k1l_lds_bytes(p, p.G), k1lp_form(p)};
+    std::copy(v, v + 13, out);
+  }
+  if (d.lds_ok && d.tmpl_ok) {
+    const TmplPlan& q = d.kt;
+    const int32_t v[8] = {1, d.tmpl_auto ? 1 : 0, q.ch, q.G, d.kt_cap, q.slot_bytes, q.tmpl_bytes, (int32_t)k1t_lds_bytes(q, q.G)};
+    std::copy(v, v + 8, out + 13);
+  }
+  if (d.lds_ok && d.k1u_ok) {
+    const K1uPlan& u = d.ku;
+    const int32_t v[9] = {1, d.k1u_auto ? 1 : 0, u.pack10, u.ch, u.G, d.ku_cap, (int32_t)k1u_lds_bytes(u, u.G),
+                          (int32_t)(k1h_lds_bytes(d.max_S, 64) + K1H_STATIC_BYTES(64)), k1u_form(u)};
+    std::copy(v, v + 9, out + 21);
+  }
+}
+static_assert(CMDP_DET_PLAN_FIELDS == 30, "det_plan_report writes 13 + 8 + 9 fields");

@@ -366,6 +366,30 @@ int cmdp_k1s_plan(cmdp_t* h, int32_t out[CMDP_K1S_PLAN_FIELDS]);
    cmdp_create would reject before planning (offsets, successor indices, row lengths). */
 int cmdp_k1s_plan_desc(const cmdp_desc* desc, int cus, int instances_per_workgroup, int32_t out[CMDP_K1S_PLAN_FIELDS]);
 
+/* The plans of the deterministic LDS-resident rollouts K1L / K1P, K1T and K1U that cmdp_create made for this handle
+   (introspection for tests; makes no HIP call; no reference counterpart).  The fields of a kernel the batch is not eligible
+   for are 0.  out, in this order:
+     K1L / K1P [0..12]   ok, pipe (1: K1P), packed (reward code in the successor word), code_shift, succ_bits (bits of a row
+                         base), n_codes (distinct reward values), ch (transitions per chunk), G (instances per workgroup),
+                         per_cu (workgroups per CU of the chosen candidate), capacity (instances per workgroup that fit LDS at
+                         that candidate, at most 64), slot_bytes, lds_bytes (of a workgroup of G), form (0: k_rollout_lds<false>,
+                         1: k_rollout_lds<true>, 2: k_rollout_pipe)
+     K1T [13..20]        ok, automatic (the automatic choice prefers it to K1L / K1P), ch, G, capacity (at most 128), slot_bytes,
+                         tmpl_bytes, lds_bytes
+     K1U [21..29]        ok, automatic (... prefers it to K1T), pack10, ch, G, capacity (at most 256), lds_bytes (of the chain
+                         kernel), hist_lds_bytes (of the histogram kernel, static arrays included), form (0: the PACK10 kernels, 1: the wide trace)
+   The two `form` fields are computed by the functions the launchers branch on.
+   Environment read by cmdp_create, for tests: CMDP_K1L_G=n sets G of K1L / K1P to min(capacity, n) at the candidate the
+   planner chose; CMDP_K1T_CH=64|32|16 plans K1T at that chunk length only (not eligible when it has no room).  Neither
+   changes a result. */
+#define CMDP_DET_PLAN_FIELDS 30
+int cmdp_det_plan(cmdp_t* h, int32_t out[CMDP_DET_PLAN_FIELDS]);
+/* The same for a bare description on a device of `cus` compute units, without a handle and without a device (only the
+   sampler half is read; the environment is not).  knobs[5] stand for CMDP_K1L_PIPE, CMDP_K1L_G, CMDP_K1T_G, CMDP_K1U_G and
+   CMDP_K1T_CH, 0 or -1 each for "planned" (pipe: -1 for planned, 0 K1L only, 1 K1P only); NULL: all planned.
+   CMDP_ERR_INVALID as for cmdp_k1s_plan_desc. */
+int cmdp_det_plan_desc(const cmdp_desc* desc, int cus, const int32_t knobs[5], int32_t out[CMDP_DET_PLAN_FIELDS]);
+
 /* K9F's plan (csrc/cmdp_chain_plan.h; the arrays are ChainFast's of csrc/cmdp_chain.h) for a bare description, without a
    handle and without a device: what the first cmdp_average_reward call on a handle of `desc` uploads (introspection for
    tests; only the DP half is read; no reference counterpart).  The caller sizes the arrays: rank and piv [state_off[B]],

@@ -18,7 +18,7 @@ from colosseum_amd.mdp.fast_batch import deepsea_episodic_tables
 pytestmark = pytest.mark.gpu
 
 KERNELS = (0, 2, 3, 4, 5, 6)   # CMDP_OPT_ROLLOUT_KERNEL: automatic and every forced LDS-resident kernel
-KNOBS = ("CMDP_K1L_PIPE", "CMDP_K1T_G", "CMDP_K1U_G", "CMDP_K1S_G")   # the environment cmdp_create reads
+KNOBS = ("CMDP_K1L_PIPE", "CMDP_K1T_G", "CMDP_K1U_G", "CMDP_K1S_G", "CMDP_K1L_G", "CMDP_K1T_CH")   # the environment cmdp_create reads
 
 
 def _det(B, S, A=2, H=16, n_rew=2, permuted=True, seed=0):

@@ -18,7 +18,7 @@ from colosseum_amd import _lib as L
 from colosseum_amd.batched import BatchedMDP, k1s_plan_of_tables
 from oracle import oracle as O
 
-KNOBS = ("CMDP_K1L_PIPE", "CMDP_K1T_G", "CMDP_K1U_G", "CMDP_K1S_G")   # the environment cmdp_create reads
+KNOBS = ("CMDP_K1L_PIPE", "CMDP_K1T_G", "CMDP_K1U_G", "CMDP_K1S_G", "CMDP_K1L_G", "CMDP_K1T_CH")   # the environment cmdp_create reads
 CUS = 256   # the MI355X; the planned G of the knob-less batch holds for it only
 GEOMETRY = {1: (1, 1, 16), 2: (2, 1, 16), 3: (2, 2, 16), 5: (4, 2, 16), 16: (4, 4, 16), 17: (4, 5, 8), 32: (4, 8, 8),
             33: (4, 9, 1), 64: (4, 16, 1)}   # G -> walker wavefronts, instances per walker, team
