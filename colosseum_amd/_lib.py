@@ -62,6 +62,9 @@ DET_PLAN_FIELDS = {
 }
 K1LP_FORMS = {0: "k1l_unpacked", 1: "k1l_packed", 2: "k1p"}
 K1U_FORMS = {0: "pack10", 1: "wide"}
+# cmdp_k1e_pair_plan / cmdp_k1e_pair_plan_desc: the fields in the order of include/cmdp.h and the names of `last_form`
+K1E_PAIR_PLAN_FIELDS = ("ok", "H", "SP2", "n_even", "lds_bytes", "last_form")
+K1E_FORMS = {0: None, 1: "single", 2: "pair"}
 DET_PLAN_KNOBS = ("pipe", "k1l_G", "k1t_G", "k1u_G", "k1t_ch")   # CMDP_K1L_PIPE, CMDP_K1L_G, CMDP_K1T_G, CMDP_K1U_G, CMDP_K1T_CH
 
 EXPORTS = [
@@ -77,6 +80,7 @@ EXPORTS = [
     "cmdp_psrl_create", "cmdp_psrl_destroy", "cmdp_psrl_run", "cmdp_psrl_layout", "cmdp_psrl_model", "cmdp_psrl_last_sample",
     "cmdp_psrl_reference_sample", "cmdp_vi_episodic_dense", "cmdp_psrl_episode_end_update", "cmdp_k1e_round_interior",
     "cmdp_k1e_code_counts", "cmdp_k1s_plan", "cmdp_k1s_plan_desc", "cmdp_det_plan", "cmdp_det_plan_desc", "cmdp_chain_plan_desc", "cmdp_chain_choice",
+    "cmdp_k1e_pair_plan", "cmdp_k1e_pair_plan_desc",
 ]
 
 
@@ -245,6 +249,8 @@ def load():
         L.cmdp_k1s_plan_desc.argtypes = [C.POINTER(CmdpDesc), i32, i32, vp]
         L.cmdp_det_plan.argtypes = [vp, vp]
         L.cmdp_det_plan_desc.argtypes = [C.POINTER(CmdpDesc), i32, vp, vp]
+        L.cmdp_k1e_pair_plan.argtypes = [vp, vp]
+        L.cmdp_k1e_pair_plan_desc.argtypes = [C.POINTER(CmdpDesc), i32, i32, vp, vp, vp, vp, vp]
         L.cmdp_chain_plan_desc.argtypes = [C.POINTER(CmdpDesc), vp, vp, vp, vp, i64, vp, vp, vp, vp, vp]
         L.cmdp_chain_choice.argtypes = [i32, i32, i32, i32, i32, vp]
         L.cmdp_k1e_code_counts.restype = C.c_uint32

@@ -131,6 +131,35 @@ def det_plan_of_tables(tables: dict, cus: int = 256, pipe: Optional[int] = None,
     return _det_plan_dict(out)
 
 
+def _k1e_plan_dict(out) -> dict:
+    plan = {k: int(v) for k, v in zip(L.K1E_PAIR_PLAN_FIELDS, out)}
+    plan["ok"] = bool(plan["ok"])
+    plan["last_form"] = L.K1E_FORMS[plan["last_form"]]
+    return plan
+
+
+def k1e_pair_plan_of_tables(tables: dict, instance: int = 0, cus: int = 256, rng_mode: int = L.RNG_PHILOX,
+                            layout: int = L.LAYOUT_CSR, flags: int = 0) -> dict:
+    """The pair plan of K1E a `BatchedMDP(tables=tables, ...)` would get on a device of `cus` compute units
+    (cmdp_k1e_pair_plan_desc: host only, needs no GPU; the environment is not read), keys as `BatchedMDP.k1e_plan`, and when ok
+    the tables of instance `instance`: n_even_instance, index [S] (compact index of a state, -1 outside the even-time states),
+    inverse [n_even_instance] and words [n_even_instance][4] (pair q = a0 | a1 << 1)."""
+    d, keep = desc_from_tables(tables, rng_mode, None, layout, flags)
+    S = int(np.diff(keep["state_off"]).max())
+    out = np.zeros(len(L.K1E_PAIR_PLAN_FIELDS), np.int32)
+    n_even = np.zeros(1, np.int32)
+    index, inverse, words = np.full(S, -1, np.int32), np.full(512, -1, np.int32), np.zeros((512, 4), np.uint16)
+    L.check(L.load().cmdp_k1e_pair_plan_desc(C.byref(d), int(cus), int(instance), L.ptr(out), L.ptr(n_even), L.ptr(index),
+                                             L.ptr(inverse), L.ptr(words)))
+    del keep
+    plan = _k1e_plan_dict(out)
+    if plan["ok"]:
+        n = int(n_even[0])
+        assert (inverse[n:plan["SP2"]] == -1).all() and not words[n:].any()
+        plan.update(n_even_instance=n, index=index, inverse=inverse[:n].copy(), words=words[:n].copy())
+    return plan
+
+
 def chain_plan_of_tables(tables: dict) -> dict:
     """K9F's plan of a continuous batch with its DP half (cmdp_chain_plan_desc: host only, needs no GPU): the eight arrays
     the first `average_reward` call uploads, under ChainFast's names (csrc/cmdp_chain.h); `rptr` cut to the offsets written."""
@@ -302,6 +331,13 @@ class BatchedMDP:
         out = np.zeros(len(L.K1S_PLAN_FIELDS), np.int32)
         L.check(self._lib.cmdp_k1s_plan(self._h, L.ptr(out)))
         return _k1s_plan_dict(out)
+
+    def k1e_plan(self) -> dict:
+        """The pair plan of the episode-parallel rollout K1E made for this batch (cmdp_k1e_pair_plan): ok, H, SP2, n_even,
+        lds_bytes, and `last_form`, the form the last K1E launch took ("pair", "single"; None before the first)."""
+        out = np.zeros(len(L.K1E_PAIR_PLAN_FIELDS), np.int32)
+        L.check(self._lib.cmdp_k1e_pair_plan(self._h, L.ptr(out)))
+        return _k1e_plan_dict(out)
 
     def det_plan(self) -> dict:
         """The plans of the deterministic LDS-resident rollouts made for this batch (cmdp_det_plan): {"k1lp": ..., "k1t": ...,

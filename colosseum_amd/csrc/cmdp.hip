@@ -29,6 +29,7 @@ extern char** environ;
 #include "cmdp_k1t.h"
 #include "cmdp_k1u.h"
 #include "cmdp_k1e.h"
+#include "cmdp_k1e_pair.h"
 #include "cmdp_rollout_plan.h"
 #include "cmdp_dp_plan.h"
 #include "cmdp_agent.h"
@@ -231,6 +232,17 @@ struct cmdp {
   bool k1e_pending = false;        // d_k1e_dep holds counts the visit counters do not have yet
   int64_t k1e_pending_steps = 0;   // transitions per instance since the last fold (the departure image is int32)
   DevBuf<int32_t> d_k1e_h0;
+  // K1E's pair form (cmdp_k1e_pair.h): two transitions per step, for launches of whole episodes walked from reset
+  bool k1e_pair_ok = false;        // the batch has a pair plan (plan_k1e_pair) and CMDP_K1E_PAIR is not 0
+  int k1e_sp2 = 0, k1e_n_even = 0;
+  size_t k1e_pair_lds = 0;
+  int k1e_last_form = 0;           // the form the last K1E launch took: 0 none yet, 1 single, 2 pair
+  DevBuf<uint32_t> d_ptab;
+  DevBuf<uint16_t> d_pinv;
+  DevBuf<int2> d_k1e_dep2;         // pair counts of the pair-form launches since the last fold
+  // every instance is at its start state with in-episode time 0: set by an unmasked cmdp_reset, kept by a rollout of a
+  // multiple of H transitions, cleared by whoever takes the mutable tables (env()) for anything else
+  bool at_start = false;
   DevBuf<float> d_gp_q, d_gp_p;  // cmdp_greedy_policy_episodic workspace
   // K5S workspace (large-instance diameter)
   DevBuf<float> d_dl_v, d_ell_val;
@@ -290,6 +302,7 @@ struct cmdp {
   DevBuf<double> d_rvals;
 
   EnvTables env() {
+    at_start = false;   // (the kernel that gets these pointers may move an instance: whoever knows better sets the flag again)
     EnvTables t{};
     t.B = B; t.A = A; t.H = H; t.rng_mode = rng_mode;
     t.rscale = rmax - rmin; t.rmin = rmin; t.beta_gammas = beta_gammas ? 1 : 0;
@@ -337,9 +350,12 @@ int k1e_fold(cmdp_t* h) {
   K1ePlan e = h->k1e;
   e.dep = h->d_k1e_dep.p;
   e.dep_res = h->d_k1e_dep_res.p;
+  e.dep2 = h->d_k1e_dep2.p;   // (null: no launch took the pair form)
   const size_t lds = k1e_fold_lds_bytes(e);
   if (int rc = set_lds(k_epi_fold, lds)) return rc;
+  const bool at_start = h->at_start;   // (the fold moves no instance)
   hipLaunchKernelGGL(k_epi_fold, dim3(grid_for(h->B, K1E_NI)), dim3(K1E_THREADS), lds, h->stream, h->env(), e, h->d_vis_ovf.p);
+  h->at_start = at_start;
   HIP_TRY(hipGetLastError());
   h->k1e_pending = false;
   h->k1e_pending_steps = 0;
@@ -638,6 +654,15 @@ static int install_rollout_plans(cmdp_t* h, const cmdp_desc* d, const std::vecto
   if (ke.ok) {
     HIP_TRY(h->d_etab.upload(ke.etab.data(), ke.etab.size(), st));
     ke.e.etab = h->d_etab.p; ke.e.rvals = h->d_rvals.p;
+    if (ke.pair.ok) {
+      HIP_TRY(h->d_ptab.upload(ke.pair.ptab.data(), ke.pair.ptab.size(), st));
+      HIP_TRY(h->d_pinv.upload(ke.pair.inv.data(), ke.pair.inv.size(), st));
+      ke.e.ptab = h->d_ptab.p; ke.e.pinv = h->d_pinv.p;
+      h->k1e_pair_ok = knobs.k1e_pair != 0;
+      h->k1e_sp2 = ke.pair.SP2;
+      h->k1e_n_even = ke.pair.n_even;
+      h->k1e_pair_lds = k1e_pair_lds_bytes(ke.e, ke.e.ash2);
+    }
     h->k1e = ke.e;
     h->k1e_lds = k1e_lds_bytes(ke.e);
     h->k1e_ok = true;
@@ -873,6 +898,7 @@ int cmdp_reset(cmdp_t* h, const uint8_t* mask, int32_t* obs_out) {
   if (obs_out) HIP_TRY(hipMemcpyAsync(obs_out, h->d_last_obs.p, sizeof(int32_t) * h->B, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   if (!mask) h->known_reset = true;
+  h->at_start = !mask;   // (a masked reset leaves the other instances where they are)
   return CMDP_OK;
 }
 
@@ -1122,7 +1148,10 @@ constexpr int kNoWorkspace = 1;
 // K1E: per segment of <= K1E_SEG transitions (16-bit counts in the table dwords; the code buffer) the walk kernel, then the
 // reward scan over the code words it left in HBM.  The walk accumulates DEPARTURE counts over launches (cmdp_k1e.h), which
 // k1e_settle folds into the visit counters before any other kernel or read.
-static int launch_k1e(cmdp_t* h, const RolloutCall& c) {
+// The form: the pair form (k_rollout_epi<1>, cmdp_k1e_pair.h) when the batch has a pair plan, every instance is at its start
+// state with in-episode time 0 (`from_start`: the handle's flag before this call), n is a multiple of H and bit 16 of
+// CMDP_K1E_DEBUG ("every round the general way") is clear; its segments are whole episodes.  Else the single form.
+static int launch_k1e(cmdp_t* h, const RolloutCall& c, bool from_start) {
   hipStream_t st = h->stream; EnvTables t = h->env();
   if (!h->ev_time[0])   // (timestamps only: no host-visibility cache flush per launch)
     for (int i = 0; i < 5; ++i) HIP_TRY(hipEventCreateWithFlags(&h->ev_time[i], hipEventDisableSystemFence));
@@ -1139,6 +1168,12 @@ static int launch_k1e(cmdp_t* h, const RolloutCall& c) {
   if (h->k1e_pending_steps + c.n > 0x7fff0000LL) { if (int rc = k1e_fold(h)) return rc; }   // the departure image is int32
   e.dep = h->d_k1e_dep.p;
   e.dep_res = h->d_k1e_dep_res.p;
+  bool pair = h->k1e_pair_ok && from_start && c.n % e.H == 0 && !(e.debug & 16);
+  if (pair && !h->d_k1e_dep2.p) {
+    HIP_TRY(h->d_k1e_dep2.alloc((size_t)grid_for(h->B, K1E_NI) * (size_t)e.pgdw));
+    HIP_TRY(h->d_k1e_dep2.zero(st));
+  }
+  e.dep2 = h->d_k1e_dep2.p;
   // The reward scan of a segment runs on the second stream under the walk of the next segment / launch (two sets of code
   // buffers): it is one wavefront per SIMD of sequential sums, the walk fills the rest of the chip (CMDP_K1E_OVERLAP=0: one
   // stream).  cmdp_rollout / cmdp_synchronize / every call that reads the sums waits for it.
@@ -1153,12 +1188,16 @@ static int launch_k1e(cmdp_t* h, const RolloutCall& c) {
   if (!ov) { if (int rc = k1e_scan_join(h)) return rc; }
   // segment length: the code words of a segment (8 bytes per episode chunk and instance, two sets) stay within ~1.5 GB
   const int64_t budget_words = std::max<int64_t>(4, (int64_t)((768ll << 20) / (8 * (int64_t)h->B * e.nch)));
-  const int64_t seg = std::max<int64_t>(e.H, std::min<int64_t>(K1E_SEG, (budget_words - 2) * e.H));
+  int64_t seg = std::max<int64_t>(e.H, std::min<int64_t>(K1E_SEG, (budget_words - 2) * e.H));
   const int64_t epi_cap = k1e_max_episodes(std::min<int64_t>(c.n, seg), e.H);
   const size_t need = (size_t)epi_cap * (size_t)e.nch * (size_t)h->B;
   if (h->d_k1e_h0.n < (size_t)h->B) HIP_TRY(h->d_k1e_h0.alloc(h->B));
   if (h->d_k1e_h0b.n < (size_t)h->B) HIP_TRY(h->d_k1e_h0b.alloc(h->B));
-  if (int rc = set_lds(k_rollout_epi, h->k1e_lds)) return rc;
+  // (the pair form stores its code words through 32-bit byte offsets, like the single form's interior rounds)
+  pair = pair && need * sizeof(uint2) < ((size_t)1 << 31);
+  if (pair) seg -= seg % e.H;   // whole episodes (seg >= H)
+  if (int rc = pair ? set_lds(k_rollout_epi<1>, h->k1e_pair_lds) : set_lds(k_rollout_epi<0>, h->k1e_lds)) return rc;
+  h->k1e_last_form = pair ? 2 : 1;
   for (int64_t s0 = 0; s0 < c.n; s0 += seg) {
     const int64_t n = std::min<int64_t>(seg, c.n - s0);
     const int i = ov ? (int)(h->aux.seq & 1) : 0;
@@ -1175,7 +1214,7 @@ static int launch_k1e(cmdp_t* h, const RolloutCall& c) {
     }
     e.codes = h->d_k1e_codes[i].p;
     e.seg_h0 = i ? h->d_k1e_h0b.p : h->d_k1e_h0.p;
-    e.n_pass = (int)((k1e_max_episodes(n, e.H) + K1E_EPP - 1) / K1E_EPP);
+    e.n_pass = (int)(((pair ? n / e.H : k1e_max_episodes(n, e.H)) + K1E_EPP - 1) / K1E_EPP);
     // interior rounds: 32-bit byte offsets into codes, and a wavefront's ring starts at a multiple of its own size (the ring
     // address is then formed by OR).  Sixteen rings larger than the tables do not fit the LDS budget, so the rings of every
     // plan are aligned today; were one not, all its rounds would go the general way
@@ -1187,7 +1226,8 @@ static int launch_k1e(cmdp_t* h, const RolloutCall& c) {
     // group's table image in flight under the walk; CMDP_K1E_GRID = workgroups (timing experiments; any value is correct)
     int k1e_grid = std::min(grid_for(h->B, K1E_NI), h->cus);
     if (const char* gs = std::getenv("CMDP_K1E_GRID")) k1e_grid = std::max(1, std::min(grid_for(h->B, K1E_NI), std::atoi(gs)));
-    hipLaunchKernelGGL(k_rollout_epi, dim3(k1e_grid), dim3(K1E_THREADS), h->k1e_lds, st, t, e, (int)n, c.last);
+    if (pair) hipLaunchKernelGGL(k_rollout_epi<1>, dim3(k1e_grid), dim3(K1E_THREADS), h->k1e_pair_lds, st, t, e, (int)n, c.last);
+    else hipLaunchKernelGGL(k_rollout_epi<0>, dim3(k1e_grid), dim3(K1E_THREADS), h->k1e_lds, st, t, e, (int)n, c.last);
     if (last) HIP_TRY(hipEventRecord(h->ev_time[1], st));
     if (ov) {
       HIP_TRY(hipEventRecord(h->aux.walk[i], st));
@@ -1343,6 +1383,8 @@ static int launch_k1(cmdp_t* h, RolloutKernel k, const RolloutCall& c) {
 // reads and writes the sums and counters itself), launch.  The caller commits the visit bound.
 static int launch_rollout(cmdp_t* h, const RolloutCall& c) {
   using K = RolloutKernel;
+  // whole episodes walked from reset end at reset again, whichever kernel walks them (only K1E's pair form asks)
+  const bool from_start = h->at_start, stays = from_start && h->k1e_pair_ok && h->H > 0 && c.n % h->H == 0;
   for (;;) {
     K k = K::K1;
     if (int rc = pick_rollout(h, c.policy, c.trace(), c.n, &k)) return rc;
@@ -1350,7 +1392,7 @@ static int launch_rollout(cmdp_t* h, const RolloutCall& c) {
     if (k != K::K1E) { if (int rc = k1e_settle(h)) return rc; }
     int rc = CMDP_OK;
     switch (k) {
-      case K::K1E: rc = launch_k1e(h, c); break;
+      case K::K1E: rc = launch_k1e(h, c, from_start); break;
       case K::K1U: rc = launch_k1u(h, c); break;
       case K::K1T: rc = launch_k1t(h, c); break;
       case K::K1L: case K::K1P: rc = launch_k1lp(h, c); break;
@@ -1358,6 +1400,7 @@ static int launch_rollout(cmdp_t* h, const RolloutCall& c) {
       case K::K1D: rc = launch_k1d(h, c); break;
       default: rc = launch_k1(h, k, c); break;
     }
+    if (rc == CMDP_OK) h->at_start = stays;
     if (rc != kNoWorkspace) return rc;
     // the chain kernels need no workspace: this handle takes them from now on, unless K1E / K1U was forced
     (k == K::K1E ? h->k1e_ok : h->k1u_ok) = false;
@@ -1501,6 +1544,12 @@ static void k1s_plan_report(bool ok, const K1sPlan& p, int32_t out[CMDP_K1S_PLAN
   std::copy(v, v + CMDP_K1S_PLAN_FIELDS, out);
 }
 
+int cmdp_k1e_pair_plan(cmdp_t* h, int32_t out[CMDP_K1E_PAIR_PLAN_FIELDS]) {
+  if (!h || !out) return fail(CMDP_ERR_INVALID, "bad argument");
+  k1e_pair_plan_report(h->k1e_ok && h->k1e_pair_ok, h->k1e, h->k1e_sp2, h->k1e_n_even, h->k1e_last_form, out);
+  return CMDP_OK;
+}
+
 int cmdp_k1s_plan(cmdp_t* h, int32_t out[CMDP_K1S_PLAN_FIELDS]) {
   if (!h || !out) return fail(CMDP_ERR_INVALID, "bad argument");
   k1s_plan_report(h->k1s_ok, h->k1s, out);
@@ -1604,6 +1653,32 @@ int cmdp_det_plan_desc(const cmdp_desc* d, int cus, const int32_t knobs_in[5], i
     ku = plan_k1u(in, kt, knobs);
   }
   det_plan_report(det_plans_of(lp, kt, ku, in.max_S), out);
+  return CMDP_OK;
+}
+
+int cmdp_k1e_pair_plan_desc(const cmdp_desc* d, int cus, int instance, int32_t out[CMDP_K1E_PAIR_PLAN_FIELDS], int32_t* n_even,
+                            int32_t* index, int32_t* inverse, uint16_t* words) {
+  if (!d || !out || cus < 1) return fail(CMDP_ERR_INVALID, "bad argument");
+  std::vector<RowDesc> rows;
+  PlanInput in{};
+  bool any_beta = false;
+  if (int rc = plan_input_of_desc(d, cus, "cmdp_k1e_pair_plan_desc", &rows, &in, &any_beta)) return rc;
+  if (instance < 0 || instance >= in.B) return fail(CMDP_ERR_INVALID, "instance %d of %d", instance, in.B);
+  // as install_rollout_plans: K1E is planned for the batches K1L / K1P take
+  const PlanKnobs knobs;
+  DetTables t;
+  K1eChoice ke;
+  if (desc_table_rewards(d, any_beta) && d->start_state && det_tables(in, &t) && plan_k1lp(in, t, knobs).ok) ke = plan_k1e(in, t, knobs);
+  const K1ePairChoice& pc = ke.pair;
+  k1e_pair_plan_report(ke.ok && pc.ok, ke.e, pc.SP2, pc.n_even, 0, out);
+  if (n_even) *n_even = 0;
+  if (!(ke.ok && pc.ok)) return CMDP_OK;
+  const size_t b = (size_t)instance;
+  if (n_even) *n_even = pc.n_even_of[b];
+  if (index) std::copy(pc.index.begin() + b * in.max_S, pc.index.begin() + (b + 1) * in.max_S, index);
+  if (inverse)
+    for (int x = 0; x < pc.SP2; ++x) inverse[x] = x < pc.n_even_of[b] ? (int32_t)pc.inv[b * pc.SP2 + x] : -1;
+  if (words) std::copy(pc.words.begin() + b * pc.SP2 * 4, pc.words.begin() + (b + 1) * pc.SP2 * 4, words);
   return CMDP_OK;
 }
 

@@ -62,6 +62,11 @@
 //   bytes LDS per workgroup at DeepSea(30): 131 072 B of tables + 16 x 2 048 B of rings = 163 840 B, the whole CU.  HBM per
 //         launch of 65 536 x 30 000 transitions: 122 MB table image in, 524 MB code words out (8 B per episode chunk and
 //         instance), 488 MB departure image.
+//   pair  k_rollout_epi<1> (cmdp_k1e_pair.h) is a second form of this walk for launches of WHOLE EPISODES WALKED FROM RESET on a
+//         batch with an even horizon: one table row per (state at an even in-episode time, action pair), so one step -- one
+//         address, one returning atomic, one v_alignbit -- covers TWO transitions.  It writes the same code words and leaves the
+//         same state; its counts go to a second departure image, which k_epi_fold folds with this one's.  launch_k1e (cmdp.hip)
+//         chooses per launch; everything else takes the form below, k_rollout_epi<0>.
 // k_reward_scan -- lane = instance: the float64 reward sum in TRANSITION ORDER from the code words (bit-equal to the
 //         oracle's and every other kernel's sequential sum).  It loads the code words in tiles of eight, three tiles in
 //         registers, and forms the packed step counts n1 | n2 << 11 | n3 << 22 of a word itself (k1e_code_counts_few for
@@ -103,6 +108,13 @@ struct K1ePlan {
   int2* dep;                 // [group][gdw] DEPARTURE counts (action 0, action 1) accumulated over launches, interleaved like
                              // the LDS image; k_epi_fold turns them into the reference's arrival counts when they are needed
   int32_t* dep_res;          // [B] episode resets not yet added to visits_s of the start state
+  // ---- the pair form (cmdp_k1e_pair.h); ash2 == 0: the batch has no pair plan ----
+  int32_t ash2;              // log2 of an image's bytes in the pair table: 7 + log2(SP2), SP2 = even-time states padded to a power of two
+  int32_t pgdw;              // dwords of a group's pair image in HBM: 2 * SP2 * 32 (whole rounds of the workgroup's 1024 lanes)
+  const uint32_t* ptab;      // [group of 32 instances][pgdw]: dword (a1 * SP2 + x) * 32 + i = pair words (a0 = 0 | a0 = 1 << 16) of row x
+  const uint16_t* pinv;      // [B][SP2] the state of compact index x
+  int2* dep2;                // [group][pgdw] pair counts accumulated over launches, in ptab's layout (a0 = 0, a0 = 1); null in a fold
+                             // when no launch of the handle took the pair form
 };
 
 // LDS: tables (2 actions x SP states x 32 instances x 4 B) | one ring per wavefront (ring_blocks x 4 dwords x 32 instances)
@@ -162,6 +174,9 @@ struct K1eGroupRegs {
   uint32_t hcs;   // in-episode time << 18 | current state << 9 | start state (S <= 512, H < 2^14: one register instead of three)
 };
 
+// FORM 0: the single form, below -- one transition per step, any segment.  FORM 1: the pair form (cmdp_k1e_pair.h, a
+// specialisation of its own) -- two transitions per step, segments of whole episodes walked from reset.
+template <int FORM>
 __global__ void __launch_bounds__(K1E_THREADS) __attribute__((amdgpu_waves_per_eu(5, 5))) k_rollout_epi(EnvTables t, K1ePlan p, int n_steps,
                                                             int32_t* __restrict__ last_obs) {
   extern __shared__ __align__(16) unsigned char smem[];
@@ -560,6 +575,32 @@ __global__ void __launch_bounds__(K1E_THREADS) k_epi_fold(EnvTables t, K1ePlan p
       if (c.x) atomicAdd(&arr0[i * S + (int)((pair & K1E_SMASK) >> 7)], (uint32_t)c.x);
       if (c.y) atomicAdd(&arr1[i * S + (int)(((pair >> 16) & K1E_SMASK) >> 7)], (uint32_t)c.y);
       dep[k] = make_int2(0, 0);
+    }
+  }
+  // the pair image (cmdp_k1e_pair.h), when a launch of the handle took the pair form: dword k = (a1 * SP2 + x) * 32 + i holds
+  // the counts of the pairs (a0 = 0, a1) and (a0 = 1, a1) of the even-time state s with compact index x.  A pair count c adds
+  // c to the arrivals of (s', a0) and of (s'', a1), s' = next(s, a0), s'' = next(s', a1)
+  if (p.dep2) {
+    int2* dep2 = p.dep2 + (size_t)blockIdx.x * (size_t)p.pgdw;
+    const int i_words = (1 << p.ash2) >> 2, SP2 = i_words >> 5;
+    for (int k = tid; k < p.pgdw; k += K1E_THREADS) {
+      const int2 c = dep2[k];
+      if (c.x | c.y) {   // (lanes past the batch never count)
+        const int i = k & 31, a1 = k >= i_words ? 1 : 0, x = (k - a1 * i_words) >> 5;
+        const int s = (int)p.pinv[(size_t)(g0 + i) * SP2 + x];
+        const uint32_t w1 = et[s * K1E_NI + i];
+#pragma unroll
+        for (int a0 = 0; a0 < 2; ++a0) {
+          const uint32_t cnt = (uint32_t)(a0 ? c.y : c.x);
+          if (cnt) {
+            const int s1 = (int)(((w1 >> (16 * a0)) & K1E_SMASK) >> 7);
+            const int s2 = (int)(((et[s1 * K1E_NI + i] >> (16 * a1)) & K1E_SMASK) >> 7);
+            atomicAdd(&(a0 ? arr1 : arr0)[i * S + s1], cnt);
+            atomicAdd(&(a1 ? arr1 : arr0)[i * S + s2], cnt);
+          }
+        }
+        dep2[k] = make_int2(0, 0);
+      }
     }
   }
   __syncthreads();

@@ -41,6 +41,7 @@ struct PlanKnobs {
   int k1l_G = 0;               // CMDP_K1L_G: likewise for K1L / K1P, at the candidate the planner chose
   int k1t_ch = 0;              // CMDP_K1T_CH: 64 | 32 | 16 plans K1T at that chunk length only (0: planned)
   int k1t_debug = 0, k1e_debug = 0;   // CMDP_K1T_DEBUG / CMDP_K1E_DEBUG: stages switched off (timing experiments only)
+  int k1e_pair = 1;            // CMDP_K1E_PAIR: 0 keeps every K1E launch in the single form (results unchanged)
 };
 inline PlanKnobs plan_knobs() {
   auto num = [](const char* name, int unset) { const char* e = std::getenv(name); return e ? std::atoi(e) : unset; };
@@ -53,6 +54,7 @@ inline PlanKnobs plan_knobs() {
   k.k1t_ch = std::max(0, num("CMDP_K1T_CH", 0));
   k.k1t_debug = num("CMDP_K1T_DEBUG", 0);
   k.k1e_debug = num("CMDP_K1E_DEBUG", 0);
+  k.k1e_pair = num("CMDP_K1E_PAIR", 1);
   return k;
 }
 
@@ -293,11 +295,99 @@ inline K1uChoice plan_k1u(const PlanInput& in, const K1tChoice& kt, const PlanKn
 // Episodic batches with two actions and at most four distinct rewards walk their EPISODES in parallel (private
 // {successor word | count} tables of 32 instances per workgroup): throughput- instead of latency-bound, and the tables
 // need not be action-permuted copies of one MDP.  It reads the K1L / K1P reward values: plan it only when they exist.
+// The PAIR plan of a K1E batch with an even horizon (cmdp_k1e_pair.h): one table row per (even-time state s, actions a0 a1).
+// E is the set of states an instance can be in at an even in-episode time t < H: breadth-first search from its start state
+// over both actions, two transitions a hop, fewer than H / 2 hops (a state is expanded once, at the hop it is first found
+// at: what a later occurrence reaches within the horizon the first one reaches too).  The states of E get compact indices
+// in the order they are found, so the start state has index 0.  Pair q = a0 | a1 << 1 of the state with index x:
+//   word = index(s'') << 7 | code(s, a0) | code(s', a1) << 2,   s' = next(s, a0), s'' = next(s', a1);
+// the successor field is 0 where s'' is not in E (only after the last pair of an episode: never followed).  Shifting the four
+// code bits of pair j in at bits 4 j gives the code-word layout of the single walk (step j at bits 2 j).
+struct K1ePairChoice {
+  bool ok = false;
+  int SP2 = 0;                    // rows of an image: a power of two >= 32 and >= every instance's |E|
+  int ash2 = 0;                   // log2 of an image's bytes: 7 + log2(SP2)
+  int n_even = 0;                 // the largest |E|
+  int pgdw = 0;                   // dwords of a group's image in HBM: 2 * SP2 * 32
+  std::vector<int32_t> n_even_of; // [B] |E|
+  std::vector<int32_t> index;     // [B][S] compact index of a state, -1 outside E
+  std::vector<uint16_t> inv;      // [B][SP2] state of a compact index (0 past |E|)
+  std::vector<uint16_t> words;    // [B][SP2][4] the pair words, q = a0 | a1 << 1
+  std::vector<uint32_t> ptab;     // [group of 32][pgdw]: dword (a1 * SP2 + x) * 32 + i = word(x, a0 = 0, a1) | word(x, 1, a1) << 16
+};
+
 struct K1eChoice {
   bool ok = false;
   K1ePlan e{};
   std::vector<uint32_t> etab;   // [group of 32][gdw]
+  K1ePairChoice pair;           // e.ash2 / e.pgdw are set when pair.ok
 };
+
+// LDS of the pair form: four images of SP2 rows x 32 instances x 4 B, then the single form's rings
+inline size_t k1e_pair_lds_bytes(const K1ePlan& e, int ash2) { return ((size_t)4 << ash2) + k1e_ring_bytes(e); }
+
+inline K1ePairChoice plan_k1e_pair(const PlanInput& in, const DetTables& t, const K1ePlan& e) {
+  K1ePairChoice c;
+  if (in.H <= 0 || (in.H & 1)) return c;
+  const int S = in.max_S, B = in.B, hops = in.H / 2;
+  c.n_even_of.assign((size_t)B, 0);
+  c.index.assign((size_t)B * S, -1);
+  std::vector<int32_t> order, depth;
+  std::vector<std::vector<int32_t>> found((size_t)B);
+  for (int b = 0; b < B; ++b) {
+    int32_t* idx = c.index.data() + (size_t)b * S;
+    const int32_t s0 = in.d->start_state[in.d->start_off[b]];
+    if (s0 < 0 || s0 >= S) return c;
+    order.assign(1, s0);
+    depth.assign(1, 0);
+    idx[s0] = 0;
+    for (size_t k = 0; k < order.size(); ++k) {
+      if (depth[k] + 1 >= hops) continue;   // its successors are past the last even time below H
+      for (int q = 0; q < 4; ++q) {
+        const int32_t s1 = t.next16[(size_t)2 * ((size_t)b * S + order[k]) + (q & 1)];
+        const int32_t s2 = t.next16[(size_t)2 * ((size_t)b * S + s1) + (q >> 1)];
+        if (idx[s2] < 0) {
+          idx[s2] = (int32_t)order.size();
+          order.push_back(s2);
+          depth.push_back(depth[k] + 1);
+        }
+      }
+    }
+    c.n_even_of[(size_t)b] = (int32_t)order.size();
+    c.n_even = std::max(c.n_even, (int)order.size());
+    found[(size_t)b] = order;
+  }
+  c.SP2 = 32;
+  c.ash2 = 12;
+  while (c.SP2 < c.n_even) { c.SP2 <<= 1; ++c.ash2; }
+  // the successor field of a 16-bit word is bits 15:7 (K1E_SMASK): at most 512 rows
+  if (c.SP2 > 512 || k1e_pair_lds_bytes(e, c.ash2) > (size_t)kLdsBudget) return c;
+  if (((size_t)4 << c.ash2) % ((size_t)e.ring_blocks * 512) != 0) return c;   // the rings are aligned as k1e_ring_aligned requires
+  c.pgdw = 2 * c.SP2 * K1E_NI;
+  const int64_t groups = ((int64_t)B + K1E_NI - 1) / K1E_NI;
+  c.inv.assign((size_t)B * c.SP2, 0);
+  c.words.assign((size_t)B * c.SP2 * 4, 0);
+  c.ptab.assign((size_t)groups * (size_t)c.pgdw, 0u);
+  for (int b = 0; b < B; ++b) {
+    const int32_t* idx = c.index.data() + (size_t)b * S;
+    const std::vector<int32_t>& ord = found[(size_t)b];
+    uint32_t* img = c.ptab.data() + (size_t)(b / K1E_NI) * (size_t)c.pgdw + (size_t)(b % K1E_NI);
+    for (size_t x = 0; x < ord.size(); ++x) {
+      c.inv[(size_t)b * c.SP2 + x] = (uint16_t)ord[x];
+      uint16_t* w = c.words.data() + ((size_t)b * c.SP2 + x) * 4;
+      for (int q = 0; q < 4; ++q) {
+        const size_t r1 = (size_t)2 * ((size_t)b * S + ord[x]) + (q & 1);
+        const size_t r2 = (size_t)2 * ((size_t)b * S + t.next16[r1]) + (q >> 1);
+        const int32_t x2 = idx[t.next16[r2]];
+        w[q] = (uint16_t)(((uint32_t)(x2 < 0 ? 0 : x2) << 7) | t.codes[r1] | ((uint32_t)t.codes[r2] << 2));
+      }
+      for (int a1 = 0; a1 < 2; ++a1)
+        img[((size_t)a1 * c.SP2 + x) * K1E_NI] = (uint32_t)w[2 * a1] | ((uint32_t)w[2 * a1 + 1] << 16);
+    }
+  }
+  c.ok = true;
+  return c;
+}
 
 inline K1eChoice plan_k1e(const PlanInput& in, const DetTables& t, const PlanKnobs& k) {
   K1eChoice c;
@@ -330,8 +420,21 @@ inline K1eChoice plan_k1e(const PlanInput& in, const DetTables& t, const PlanKno
       c.etab[(size_t)(b / K1E_NI) * (size_t)e.gdw + (size_t)s * K1E_NI + (size_t)(b % K1E_NI)] = word(r) | (word(r + 1) << 16);
     }
   c.ok = true;
+  c.pair = plan_k1e_pair(in, t, e);
+  if (c.pair.ok) { e.ash2 = c.pair.ash2; e.pgdw = c.pair.pgdw; }
   return c;
 }
+
+// cmdp_k1e_pair_plan / cmdp_k1e_pair_plan_desc: the fields in the order include/cmdp.h gives (last_form: 0 no K1E launch yet,
+// 1 the single form, 2 the pair form); all 0 but last_form when the batch has no pair plan
+inline void k1e_pair_plan_report(bool ok, const K1ePlan& e, int SP2, int n_even, int last_form, int32_t out[CMDP_K1E_PAIR_PLAN_FIELDS]) {
+  std::fill(out, out + CMDP_K1E_PAIR_PLAN_FIELDS, 0);
+  out[5] = last_form;
+  if (!ok) return;
+  const int32_t v[5] = {1, e.H, SP2, n_even, (int32_t)k1e_pair_lds_bytes(e, e.ash2)};
+  std::copy(v, v + 5, out);
+}
+static_assert(CMDP_K1E_PAIR_PLAN_FIELDS == 6, "k1e_pair_plan_report writes 6 fields");
 
 // ---- K1S (cmdp_k1s.h) ----------------------------------------------------------------------------------------------
 // Compresses the sampler tables of a batch with stochastic dynamics into shared cumulative-probability patterns,

@@ -390,6 +390,30 @@ int cmdp_det_plan(cmdp_t* h, int32_t out[CMDP_DET_PLAN_FIELDS]);
    CMDP_ERR_INVALID as for cmdp_k1s_plan_desc. */
 int cmdp_det_plan_desc(const cmdp_desc* desc, int cus, const int32_t knobs[5], int32_t out[CMDP_DET_PLAN_FIELDS]);
 
+/* The PAIR plan of the episode-parallel rollout K1E (csrc/cmdp_k1e_pair.h, plan_k1e_pair in csrc/cmdp_rollout_plan.h) that
+   cmdp_create made for this handle (introspection for tests; makes no HIP call; no reference counterpart): the walk of a
+   launch of whole episodes from reset takes two transitions per step, on a table with one row per (state at an even in-episode
+   time, action pair).  out, in this order: ok (1 when the batch is eligible for K1E, its horizon is even, every instance has at
+   most SP2 even-time states and four images of SP2 x 128 B plus the action-bit rings fit LDS -- and CMDP_K1E_PAIR is not 0; the
+   next four fields are 0 otherwise), H, SP2 (rows of an image: a power of two >= 32), n_even (the largest number of even-time
+   states of an instance), lds_bytes (of a workgroup), last_form (the form the last K1E launch of the handle took: 0 none yet,
+   1 single, 2 pair).  A launch takes the pair form when ok, every instance is at its start state with in-episode time 0
+   (after an unmasked cmdp_reset, or after rollouts of multiples of H transitions since), n is a multiple of H, the policy is
+   random without trace and bit 16 of CMDP_K1E_DEBUG is clear; results are those of the single form.
+   The environment variable CMDP_K1E_PAIR, read by cmdp_create, 0: every launch takes the single form. */
+#define CMDP_K1E_PAIR_PLAN_FIELDS 6
+int cmdp_k1e_pair_plan(cmdp_t* h, int32_t out[CMDP_K1E_PAIR_PLAN_FIELDS]);
+/* The same for a bare description on a device of `cus` compute units, without a handle and without a device (only the sampler
+   half is read; the environment is not; last_form is 0), and the tables of instance `instance` (each pointer may be NULL;
+   nothing is written to them when ok is 0): *n_even its number of even-time states; index [S]: the compact index of every
+   state, -1 for a state that is no even-time state (the start state has index 0); inverse [SP2]: the state of every compact
+   index, -1 past n_even; words [SP2][4]: the pair words, pair q = a0 | a1 << 1 of row x at words[4 x + q] =
+   index(s'') << 7 | code(s, a0) | code(s', a1) << 2 with s' = next(s, a0), s'' = next(s', a1), the successor field 0 where s''
+   is no even-time state; rows past n_even are 0.  The reward codes are indices into the distinct reward values in order of
+   first appearance over the rows of the batch.  CMDP_ERR_INVALID as for cmdp_k1s_plan_desc. */
+int cmdp_k1e_pair_plan_desc(const cmdp_desc* desc, int cus, int instance, int32_t out[CMDP_K1E_PAIR_PLAN_FIELDS], int32_t* n_even,
+                            int32_t* index, int32_t* inverse, uint16_t* words);
+
 /* K9F's plan (csrc/cmdp_chain_plan.h; the arrays are ChainFast's of csrc/cmdp_chain.h) for a bare description, without a
    handle and without a device: what the first cmdp_average_reward call on a handle of `desc` uploads (introspection for
    tests; only the DP half is read; no reference counterpart).  The caller sizes the arrays: rank and piv [state_off[B]],
