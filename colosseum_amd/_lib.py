@@ -32,11 +32,13 @@ STAT_UCRL2_UNCONVERGED, STAT_UCRL2_ROUNDS, STAT_UCRL2_SOLVES, STAT_UCRL2_ROUND_M
 STAT_UCRL2_WAIT_MS = 16
 STAT_PSRL_ROUNDS, STAT_PSRL_SOLVES, STAT_PSRL_SAMPLE_KERNEL_MS, STAT_PSRL_VI_KERNEL_MS, STAT_PSRL_REFERENCE_MS = 17, 18, 19, 20, 21
 STAT_DIAMETER_KERNEL = 22  # family * 1000 + n * 10 + flag, see include/cmdp.h
+STAT_UCRL2_POLICY_KERNEL_MS = 23
 PSRL_SAMPLER_REFERENCE, PSRL_SAMPLER_PHILOX = 0, 1
 PSRL_KEY_HI = 0x5053524C
 BOUND_CHERNOFF, BOUND_BERNSTEIN = 0, 1
 ACTOR_GREEDY, ACTOR_EPSILON_GREEDY, ACTOR_BOLTZMANN = 0, 1, 2
 UCRL2_OPT_MAX_SWEEPS = 1
+UCRL2_OPT_POLICY_SIZE_THRESHOLD = 2
 NOISE_NONE, NOISE_GAUSSIAN, NOISE_GAUSSIAN_CORRELATED, NOISE_STUDENT_T, NOISE_STUDENT_T_CORRELATED = 0, 1, 2, 3, 4
 CALIB_LDS_READ, CALIB_LDS_CHAIN, CALIB_LDS_CHAIN_SHARED = 0, 1, 2
 DP_AUTO, DP_WORKGROUP, DP_REGISTER = 0, 1, 2
@@ -76,7 +78,7 @@ EXPORTS = [
     "cmdp_qlearning_policy", "cmdp_qlearning_average_reward", "cmdp_qlearning_run_logged", "cmdp_tracker_replay", "cmdp_average_reward", "cmdp_diameter_range", "cmdp_diameter_sparse_f64", "cmdp_mixing_time", "cmdp_set_observation_table", "cmdp_observe", "cmdp_observe_noise",
     "cmdp_set_reward_streams", "cmdp_legacy_beta", "cmdp_extended_vi",
     "cmdp_ucrl2_create", "cmdp_ucrl2_destroy", "cmdp_ucrl2_run", "cmdp_ucrl2_layout", "cmdp_ucrl2_model", "cmdp_ucrl2_last_solve",
-    "cmdp_ucrl2_set_option",
+    "cmdp_ucrl2_set_option", "cmdp_ucrl2_policy", "cmdp_ucrl2_average_reward", "cmdp_model_vi_scheme", "cmdp_vi_discounted_model",
     "cmdp_psrl_create", "cmdp_psrl_destroy", "cmdp_psrl_run", "cmdp_psrl_layout", "cmdp_psrl_model", "cmdp_psrl_last_sample",
     "cmdp_psrl_reference_sample", "cmdp_vi_episodic_dense", "cmdp_psrl_episode_end_update", "cmdp_k1e_round_interior",
     "cmdp_k1e_code_counts", "cmdp_k1s_plan", "cmdp_k1s_plan_desc", "cmdp_det_plan", "cmdp_det_plan_desc", "cmdp_chain_plan_desc", "cmdp_chain_choice",
@@ -234,6 +236,10 @@ def load():
         L.cmdp_ucrl2_model.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         L.cmdp_ucrl2_last_solve.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         L.cmdp_ucrl2_set_option.argtypes = [vp, i32, i64]
+        L.cmdp_ucrl2_policy.argtypes = [vp, vp, vp, vp, vp, vp]
+        L.cmdp_ucrl2_average_reward.argtypes = [vp, vp, vp, vp]
+        L.cmdp_model_vi_scheme.argtypes = [i32, i32, i64, i64, f64]
+        L.cmdp_vi_discounted_model.argtypes = [i32, vp, vp, vp, vp, vp, vp, vp, f32, f64, i32, i64, f64, i64, vp, vp, vp, vp, vp]
         L.cmdp_psrl_create.argtypes = [C.POINTER(vp), vp, vp, i64, vp, vp, i32, i32]
         L.cmdp_psrl_destroy.argtypes = [vp]
         L.cmdp_psrl_run.argtypes = [vp, i64, i32, vp, vp, vp, vp, vp, vp]

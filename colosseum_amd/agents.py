@@ -197,7 +197,8 @@ class BatchedUCRL2Continuous(_ParkAndSolveAgent):
 
     _DESTROY, _PREFIX = "cmdp_ucrl2_destroy", "cmdp_ucrl2"
     _STATS = (("rounds", L.STAT_UCRL2_ROUNDS), ("solves", L.STAT_UCRL2_SOLVES), ("unconverged", L.STAT_UCRL2_UNCONVERGED),
-              ("round_ms", L.STAT_UCRL2_ROUND_MS), ("wait_ms", L.STAT_UCRL2_WAIT_MS))
+              ("round_ms", L.STAT_UCRL2_ROUND_MS), ("wait_ms", L.STAT_UCRL2_WAIT_MS),
+              ("policy_kernel_ms", L.STAT_UCRL2_POLICY_KERNEL_MS))
     _BOUNDS = {"_chernoff": L.BOUND_CHERNOFF, "bernstein": L.BOUND_BERNSTEIN}
 
     def __init__(self, env: BatchedMDP, seeds: Sequence[int], optimization_horizon: int, alpha_r=1.0, alpha_p=1.0,
@@ -254,24 +255,54 @@ class BatchedUCRL2Continuous(_ParkAndSolveAgent):
         return dict(P=self._dense(P, np.float32, uniform=uni), estimated_rewards=sa(er), beta_r=sa(br), beta_p0=sa(bp), Q=sa(Q),
                     span=span, sweeps=sweeps, status=status)
 
-    def current_optimal_stochastic_policy(self):
-        """ucrl2.py:80-83 per instance: argmax_2d of discounted value iteration on the estimated model (host side: it is
-        called per log row only)."""
-        from .dynamic_programming import argmax_2d, discounted_value_iteration
+    def _mask(self, mask):
+        m = None if mask is None else np.ascontiguousarray(mask, np.uint8)
+        assert m is None or m.shape == (self.env.B,)
+        return m, (range(self.env.B) if m is None else np.flatnonzero(m))
 
-        m, out = self.model(), []
-        for P, R in zip(m["P"], m["estimated_rewards"]):
-            res = discounted_value_iteration(P, R)
-            if res is None:   # only with max_abs_value, which is not passed; the reference would fail to unpack None too
-                raise RuntimeError("discounted value iteration returned no solution for the estimated model")
-            out.append(argmax_2d(res[0]))
-        return out
+    def policy(self, mask=None):
+        """ucrl2.py:80-83 on the device: argmax_2d (RandomState(42) tie-break) of discounted value iteration on the estimated
+        model (kernel K14), per instance [S, A]; with `mask`, for the selected instances only, in their order."""
+        env = self.env
+        m, sel = self._mask(mask)
+        pi = np.zeros(int(env.row_off[-1]), np.float32)
+        L.check(self._lib.cmdp_ucrl2_policy(self._h, L.ptr(m), L.ptr(pi), None, None, None))
+        rows = env.split_rows(pi)
+        return [rows[b].reshape(-1, env.A) for b in sel]
+
+    def policy_solve(self, mask=None):
+        """The solve behind `policy()`: `Q` per instance [S, A] float32, `sweeps` and `scheme` (L.SCHEME_JACOBI /
+        L.SCHEME_GAUSS_SEIDEL, the reference's rule on the estimated model) [B]; with `mask`, zeros elsewhere."""
+        env = self.env
+        m, _ = self._mask(mask)
+        Q = np.zeros(int(env.row_off[-1]), np.float32)
+        sweeps, scheme = np.zeros(env.B, np.int64), np.zeros(env.B, np.int32)
+        L.check(self._lib.cmdp_ucrl2_policy(self._h, L.ptr(m), None, L.ptr(Q), L.ptr(sweeps), L.ptr(scheme)))
+        return dict(Q=[x.reshape(-1, env.A) for x in env.split_rows(Q)], sweeps=sweeps, scheme=scheme)
+
+    def average_reward(self, mask=None) -> list:
+        """`get_average_reward` of `policy()` from the environments' current states, on the device (K14, then kernel K9): a
+        list of numpy scalars (np.float32 where the reference's value is one) for the instances selected by `mask`."""
+        B = self.env.B
+        m, sel = self._mask(mask)
+        avg = np.zeros(B, np.float64)
+        kind = np.zeros(B, np.int32)
+        L.check(self._lib.cmdp_ucrl2_average_reward(self._h, L.ptr(m), L.ptr(avg), L.ptr(kind)))
+        return [np.float32(avg[b]) if kind[b] else np.float64(avg[b]) for b in sel]
+
+    def current_optimal_stochastic_policy(self):
+        """ucrl2.py:80-83 per instance: `policy()`."""
+        return self.policy()
 
     def stats(self) -> dict:
         """Rounds of parked instances, instances solved in them, solves that did not converge, host time of the rounds
         (park list, logarithms, enqueue) and time spent waiting for the device in them.  Kept per ENVIRONMENT handle:
         agents created on the same environment share these counters."""
         return self._stats()
+
+    def _set_policy_size_threshold(self, n: int):
+        """Test hook: the size threshold of the scheme rule in the policy solve (the reference's default 300 * 3 * 300)."""
+        L.check(self._lib.cmdp_ucrl2_set_option(self._h, L.UCRL2_OPT_POLICY_SIZE_THRESHOLD, int(n)))
 
     def _set_max_sweeps(self, n: int):
         """Test hook: the sweeps a solve may take (the not-converged path keeps the previous Q)."""

@@ -36,6 +36,7 @@ extern char** environ;
 #include "cmdp_chain.h"
 #include "cmdp_chain_plan.h"
 #include "cmdp_evi.h"
+#include "cmdp_model_vi.h"
 #include "cmdp_ucrl2.h"
 #include "cmdp_psrl.h"
 
@@ -291,6 +292,7 @@ struct cmdp {
   std::vector<cmdp_t**> uc_backrefs;
   int64_t uc_rounds = 0, uc_solves = 0;
   double uc_round_ms = 0.0, uc_wait_ms = 0.0;
+  double uc_policy_ms = 0.0;   // CMDP_STAT_UCRL2_POLICY_KERNEL_MS: the last K14 launch of an agent of this handle
   DevBuf<int32_t> d_uc_unconverged;
   // PSRL agents on this handle (cmdp_psrl_*): CMDP_STAT_PSRL_*
   int64_t ps_rounds = 0, ps_solves = 0;
@@ -1752,6 +1754,10 @@ int cmdp_stat(cmdp_t* h, int which, double* out) {
   if (which >= CMDP_STAT_PSRL_ROUNDS && which <= CMDP_STAT_PSRL_REFERENCE_MS) {
     *out = which == CMDP_STAT_PSRL_ROUNDS ? (double)h->ps_rounds : which == CMDP_STAT_PSRL_SOLVES ? (double)h->ps_solves
            : which == CMDP_STAT_PSRL_SAMPLE_KERNEL_MS ? h->ps_sample_ms : which == CMDP_STAT_PSRL_VI_KERNEL_MS ? h->ps_vi_ms : h->ps_ref_ms;
+    return CMDP_OK;
+  }
+  if (which == CMDP_STAT_UCRL2_POLICY_KERNEL_MS) {
+    *out = h->uc_policy_ms;
     return CMDP_OK;
   }
   if (which == CMDP_STAT_UCRL2_UNCONVERGED) {
@@ -4168,6 +4174,130 @@ int cmdp_extended_vi(int count, const int32_t* n_states, const int32_t* n_action
   return CMDP_OK;
 }
 
+// K14's launch on device-resident arguments: what cmdp_vi_discounted_model does after its uploads and what the UCRL2 agent
+// does for its policy (cmdp_ucrl2_policy), block b solving instance b
+static int mvi_launch(const ModelViArgs& a, int count, int max_S, hipStream_t st) {
+  const size_t lds = model_vi_lds_bytes(max_S);
+  if (int rc = set_lds(k_vi_model, lds)) return rc;
+  hipLaunchKernelGGL(k_vi_model, dim3(count), dim3(MVI_THREADS), lds, st, a);
+  HIP_TRY(hipGetLastError());
+  return CMDP_OK;
+}
+
+int cmdp_model_vi_scheme(int n_states, int n_actions, int64_t nnz, int64_t size_threshold, double density_threshold) {
+  return model_vi_scheme(n_states, n_actions, nnz, size_threshold, density_threshold);
+}
+
+int cmdp_vi_discounted_model(int count, const int32_t* n_states, const int32_t* n_actions, const int64_t* csr_ptr,
+                             const int32_t* csr_col, const float* csr_val, const float* uniform, const float* rewards,
+                             float gamma, double epsilon, int scheme, int64_t size_threshold, double density_threshold,
+                             int64_t max_sweeps, float* Q, float* V, int64_t* sweeps, int32_t* scheme_used, int32_t* status) {
+  if (count < 0) return fail(CMDP_ERR_INVALID, "count %d is negative", count);
+  if (count == 0) return CMDP_OK;
+  if (!n_states || !n_actions || !csr_ptr || !rewards || !Q || !V || !sweeps || !scheme_used || !status)
+    return fail(CMDP_ERR_INVALID, "null argument");
+  if (!std::isfinite(gamma)) return fail(CMDP_ERR_INVALID, "gamma %g is not finite", (double)gamma);
+  if (!(epsilon >= 0.0) || !std::isfinite(epsilon)) return fail(CMDP_ERR_INVALID, "epsilon %g is not a finite value >= 0", epsilon);
+  if (max_sweeps < 1) return fail(CMDP_ERR_INVALID, "max_sweeps %lld < 1", (long long)max_sweeps);
+  if (scheme != CMDP_SCHEME_AUTO && scheme != CMDP_SCHEME_JACOBI && scheme != CMDP_SCHEME_GAUSS_SEIDEL)
+    return fail(CMDP_ERR_INVALID, "scheme %d: CMDP_SCHEME_AUTO, CMDP_SCHEME_JACOBI or CMDP_SCHEME_GAUSS_SEIDEL", scheme);
+  if (std::isnan(density_threshold)) return fail(CMDP_ERR_INVALID, "density_threshold is not a number");
+  std::vector<int64_t> soff((size_t)count), roff((size_t)count);
+  int64_t ns = 0, nr = 0;
+  int max_S = 0;
+  for (int b = 0; b < count; ++b) {
+    const int S = n_states[b], A = n_actions[b];
+    if (S < 1) return fail(CMDP_ERR_INVALID, "n_states[%d] = %d < 1", b, S);
+    if (A < 1) return fail(CMDP_ERR_INVALID, "n_actions[%d] = %d < 1", b, A);
+    soff[b] = ns; roff[b] = nr;
+    ns += S;
+    nr += (int64_t)S * A;
+    max_S = std::max(max_S, S);
+  }
+  for (int b = 0; b < count; ++b) {
+    if (n_states[b] > MVI_MAX_STATES)
+      return fail(CMDP_ERR_UNSUPPORTED, "instance %d has %d states: value iteration on a model keeps V, Vold and the shared "
+                  "products in LDS for at most %d states", b, n_states[b], MVI_MAX_STATES);
+    if (n_actions[b] > MVI_MAX_ACTIONS)
+      return fail(CMDP_ERR_UNSUPPORTED, "instance %d has %d actions: a wavefront takes the rows of a state, at most %d", b,
+                  n_actions[b], MVI_MAX_ACTIONS);
+  }
+  if (csr_ptr[0] != 0) return fail(CMDP_ERR_INVALID, "csr_ptr[0] = %lld, not 0", (long long)csr_ptr[0]);
+  for (int64_t r = 0; r < nr; ++r)
+    if (csr_ptr[r + 1] < csr_ptr[r]) return fail(CMDP_ERR_INVALID, "csr_ptr decreases at row %lld", (long long)r);
+  const int64_t nnz = csr_ptr[nr];
+  if (nnz > 0 && (!csr_col || !csr_val)) return fail(CMDP_ERR_INVALID, "null csr_col / csr_val");
+  std::vector<float> uni((size_t)nr, 0.0f);
+  for (int b = 0; b < count; ++b) {
+    const int S = n_states[b], A = n_actions[b];
+    for (int64_t r = roff[b]; r < roff[b] + (int64_t)S * A; ++r) {
+      const int64_t rb = csr_ptr[r], re = csr_ptr[r + 1];
+      for (int64_t k = rb; k < re; ++k) {
+        if (csr_col[k] < 0 || csr_col[k] >= S || (k > rb && csr_col[k] <= csr_col[k - 1]))
+          return fail(CMDP_ERR_INVALID, "csr_col of row %lld is not ascending within [0, %d)", (long long)r, S);
+        if (!(csr_val[k] >= 0.0f) || !std::isfinite(csr_val[k]))
+          return fail(CMDP_ERR_INVALID, "csr_val[%lld] = %g is not a finite probability >= 0", (long long)k, (double)csr_val[k]);
+      }
+      if (!std::isfinite(rewards[r])) return fail(CMDP_ERR_INVALID, "rewards[%lld] is not finite", (long long)r);
+      if (uniform && uniform[r] != 0.0f) {
+        if (!(uniform[r] > 0.0f) || !std::isfinite(uniform[r]) || re != rb)
+          return fail(CMDP_ERR_INVALID, "uniform[%lld] = %g: must be finite > 0 on a row without CSR entries",
+                      (long long)r, (double)uniform[r]);
+        uni[(size_t)r] = uniform[r];
+      } else if (re - rb == S && csr_val[rb] > 0.0f) {  // a full row of one value is taken as uniform too
+        bool same = true;
+        for (int64_t k = rb + 1; k < re && same; ++k) same = csr_val[k] == csr_val[rb];
+        if (same) uni[(size_t)r] = csr_val[rb];
+      }
+    }
+  }
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(CMDP_ERR_NO_DEVICE, "no HIP device visible");
+  // a workspace per device, reused across calls and leaked at exit, calls serialised: as cmdp_extended_vi
+  struct Ws {
+    DevBuf<int32_t> S, A, col, scheme, status;
+    DevBuf<int64_t> soff, roff, ptr, sweeps;
+    DevBuf<float> val, uni, R, Q, V;
+    hipStream_t st = nullptr;
+  };
+  static std::mutex mu;
+  static std::map<int, Ws*>* all = new std::map<int, Ws*>;
+  std::lock_guard<std::mutex> lock(mu);
+  int dev = 0;
+  HIP_TRY(hipGetDevice(&dev));
+  Ws*& ws = (*all)[dev];
+  if (!ws) {
+    ws = new Ws;
+    HIP_TRY(hipStreamCreateWithFlags(&ws->st, hipStreamNonBlocking));
+  }
+  hipStream_t st = ws->st;
+  HIP_TRY(ws->S.upload(n_states, count, st));
+  HIP_TRY(ws->A.upload(n_actions, count, st));
+  HIP_TRY(ws->soff.upload(soff.data(), count, st));
+  HIP_TRY(ws->roff.upload(roff.data(), count, st));
+  HIP_TRY(ws->ptr.upload(csr_ptr, (size_t)nr + 1, st));
+  HIP_TRY(ws->col.upload(csr_col, (size_t)nnz, st));
+  HIP_TRY(ws->val.upload(csr_val, (size_t)nnz, st));
+  HIP_TRY(ws->uni.upload(uni.data(), (size_t)nr, st));
+  HIP_TRY(ws->R.upload(rewards, (size_t)nr, st));
+  HIP_TRY(ws->Q.alloc((size_t)nr));
+  HIP_TRY(ws->V.alloc((size_t)ns));
+  HIP_TRY(ws->sweeps.alloc(count));
+  HIP_TRY(ws->scheme.alloc(count));
+  HIP_TRY(ws->status.alloc(count));
+  ModelViArgs a{ws->S.p, ws->A.p, ws->soff.p, ws->roff.p, ws->ptr.p, ws->col.p, ws->val.p, ws->uni.p, ws->R.p, nullptr,
+                gamma, epsilon, scheme, size_threshold, density_threshold, max_sweeps, ws->Q.p, ws->V.p, ws->sweeps.p,
+                ws->scheme.p, ws->status.p};
+  if (int rc = mvi_launch(a, count, max_S, st)) return rc;
+  HIP_TRY(hipMemcpyAsync(Q, ws->Q.p, sizeof(float) * (size_t)nr, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(V, ws->V.p, sizeof(float) * (size_t)ns, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(sweeps, ws->sweeps.p, sizeof(int64_t) * count, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(scheme_used, ws->scheme.p, sizeof(int32_t) * count, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(status, ws->status.p, sizeof(int32_t) * count, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return CMDP_OK;
+}
+
 int cmdp_value_norm(cmdp_t* h, const float* V, float* out) {
   if (int rc = bind(h)) return rc;
   if (!h->has_dp) return fail(CMDP_ERR_INVALID, "handle was created without the DP half");
@@ -4199,6 +4329,17 @@ struct cmdp_ucrl2 : ParkAgent {
   DevBuf<double> d_delta, d_tr_rew, d_beta_r, d_beta_p0, d_span, d_e_rmax, d_e_span, d_host;
   PinnedBuf<int64_t> pin_iter;   // [B]
   PinnedBuf<double> pin_host;    // [3][B]: the round's scalars per parked instance
+  // the policy solve (K14, cmdp_ucrl2_policy): buffers of its own, allocated by the first call
+  int64_t policy_size_threshold = 300 * 3 * 300;   // CMDP_UCRL2_OPT_POLICY_SIZE_THRESHOLD
+  DevBuf<int32_t> d_pS, d_pA, d_p_scheme, d_p_status;
+  DevBuf<int64_t> d_p_roff, d_p_sweeps;
+  DevBuf<float> d_pQ, d_pV, d_ppi;
+  DevBuf<uint8_t> d_p_mask;
+  hipEvent_t p_ev[2] = {nullptr, nullptr};
+  ~cmdp_ucrl2() {
+    for (hipEvent_t e : p_ev)
+      if (e) (void)hipEventDestroy(e);
+  }
 };
 
 namespace {
@@ -4364,6 +4505,10 @@ int cmdp_ucrl2_set_option(cmdp_ucrl2_t* a, int option, int64_t value) {
     a->max_sweeps = value;
     return CMDP_OK;
   }
+  if (option == CMDP_UCRL2_OPT_POLICY_SIZE_THRESHOLD) {
+    a->policy_size_threshold = value;
+    return CMDP_OK;
+  }
   return fail(CMDP_ERR_INVALID, "unknown option %d", option);
 }
 
@@ -4386,6 +4531,99 @@ int cmdp_ucrl2_run(cmdp_ucrl2_t* a, int64_t n_steps, int stop_at_episode_end, co
                     "not hold (a defect of the library); the instance's last transition was taken and not counted, destroy the agent");
       },
       [&](int count) { return ucrl2_round(a, count, stop, n_steps); }, &h->uc_wait_ms, &h->uc_round_ms);
+}
+
+// discounted_value_iteration(self.P, self.estimated_rewards) (K14) and argmax_2d of its Q for the instances of `mask`, on the
+// handle's stream over the agent's own tables; waits for it and fails when an instance hit max_sweeps, as the reference
+// raises.  Leaves the one-hot policy in d_ppi and Q in d_pQ; reads nothing but the model and writes nothing of the agent's.
+static int ucrl2_policy_solve(cmdp_ucrl2_t* a, const uint8_t* mask, std::vector<int64_t>* sweeps_out, std::vector<int32_t>* scheme_out) {
+  cmdp_t* h = a->env;
+  hipStream_t st = h->stream;
+  const int B = h->B;
+  const int64_t R = h->n_rows;
+  if (h->A > MVI_MAX_ACTIONS)
+    return fail(CMDP_ERR_UNSUPPORTED, "%d actions: value iteration on a model (K14) takes at most %d", h->A, MVI_MAX_ACTIONS);
+  if (!a->d_pS.p) {
+    std::vector<int32_t> S((size_t)B), A((size_t)B, h->A);
+    std::vector<int64_t> roff((size_t)B);
+    for (int b = 0; b < B; ++b) {
+      S[b] = (int32_t)(h->state_off[b + 1] - h->state_off[b]);
+      roff[b] = h->state_off[b] * h->A;
+    }
+    HIP_TRY(a->d_pA.upload(A.data(), B, st));
+    HIP_TRY(a->d_p_roff.upload(roff.data(), B, st));
+    AGENT_ZERO(d_pQ, R); AGENT_ZERO(d_pV, h->n_states); AGENT_ZERO(d_ppi, R); AGENT_ZERO(d_p_sweeps, B);
+    AGENT_ZERO(d_p_scheme, B); AGENT_ZERO(d_p_status, B);
+    HIP_TRY(a->d_p_mask.alloc(B));
+    for (hipEvent_t& e : a->p_ev) HIP_TRY(hipEventCreate(&e));
+    HIP_TRY(a->d_pS.upload(S.data(), B, st));
+    HIP_TRY(hipStreamSynchronize(st));  // the vectors are locals
+  }
+  const uint8_t* dmask = nullptr;
+  if (mask) {
+    HIP_TRY(a->d_p_mask.upload(mask, B, st));
+    dmask = a->d_p_mask.p;
+  }
+  ModelViArgs g{a->d_pS.p, a->d_pA.p, h->d_state_off.p, a->d_p_roff.p, a->d_row_ptr.p, a->d_col.p, a->d_val.p, a->d_uni.p,
+                a->d_ER.p, dmask, 0.99f, 1e-3, CMDP_SCHEME_AUTO, a->policy_size_threshold, 0.2, 1000000, a->d_pQ.p, a->d_pV.p,
+                a->d_p_sweeps.p, a->d_p_scheme.p, a->d_p_status.p};
+  HIP_TRY(hipEventRecord(a->p_ev[0], st));
+  if (int rc = mvi_launch(g, B, h->max_S, st)) return rc;
+  HIP_TRY(hipEventRecord(a->p_ev[1], st));
+  hipLaunchKernelGGL(k_greedy_policy_episodic<float>, dim3(B), dim3(64), 0, st, B, h->A, 1, 1, h->d_state_off.p, a->d_pQ.p,
+                     a->d_ppi.p);
+  HIP_TRY(hipGetLastError());
+  std::vector<int32_t> status((size_t)B);
+  HIP_TRY(hipMemcpyAsync(status.data(), a->d_p_status.p, sizeof(int32_t) * B, hipMemcpyDeviceToHost, st));
+  if (sweeps_out) {
+    sweeps_out->resize((size_t)B);
+    HIP_TRY(hipMemcpyAsync(sweeps_out->data(), a->d_p_sweeps.p, sizeof(int64_t) * B, hipMemcpyDeviceToHost, st));
+  }
+  if (scheme_out) {
+    scheme_out->resize((size_t)B);
+    HIP_TRY(hipMemcpyAsync(scheme_out->data(), a->d_p_scheme.p, sizeof(int32_t) * B, hipMemcpyDeviceToHost, st));
+  }
+  HIP_TRY(hipStreamSynchronize(st));
+  float ms = 0.0f;
+  HIP_TRY(hipEventElapsedTime(&ms, a->p_ev[0], a->p_ev[1]));
+  h->uc_policy_ms = (double)ms;
+  for (int b = 0; b < B; ++b)
+    if ((!mask || mask[b]) && status[b] != 0)
+      return fail(CMDP_ERR_MAX_ITER, "discounted value iteration on the estimated model of instance %d did not converge in "
+                  "%d sweeps", b, 1000000);
+  return CMDP_OK;
+}
+
+int cmdp_ucrl2_policy(cmdp_ucrl2_t* a, const uint8_t* mask, float* pi, float* Q, int64_t* sweeps, int32_t* scheme_used) {
+  if (!a || !a->env) return fail(CMDP_ERR_INVALID, "null agent, or its environment handle has been destroyed");
+  cmdp_t* h = a->env;
+  if (int rc = bind(h)) return rc;
+  std::vector<int64_t> sw;
+  std::vector<int32_t> sc;
+  if (int rc = ucrl2_policy_solve(a, mask, sweeps ? &sw : nullptr, scheme_used ? &sc : nullptr)) return rc;
+  if (!mask) {
+    if (pi) HIP_TRY(hipMemcpyAsync(pi, a->d_ppi.p, sizeof(float) * (size_t)h->n_rows, hipMemcpyDeviceToHost, h->stream));
+    if (Q) HIP_TRY(hipMemcpyAsync(Q, a->d_pQ.p, sizeof(float) * (size_t)h->n_rows, hipMemcpyDeviceToHost, h->stream));
+  }
+  // the instances of the mask only: what the call leaves of the others is what it found
+  for (int b = 0; b < h->B; ++b) {
+    if (mask && !mask[b]) continue;
+    const int64_t r0 = h->state_off[b] * h->A, n = (h->state_off[b + 1] - h->state_off[b]) * h->A;
+    if (mask && pi) HIP_TRY(hipMemcpyAsync(pi + r0, a->d_ppi.p + r0, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
+    if (mask && Q) HIP_TRY(hipMemcpyAsync(Q + r0, a->d_pQ.p + r0, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
+    if (sweeps) sweeps[b] = sw[(size_t)b];
+    if (scheme_used) scheme_used[b] = sc[(size_t)b];
+  }
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  return CMDP_OK;
+}
+
+int cmdp_ucrl2_average_reward(cmdp_ucrl2_t* a, const uint8_t* mask, double* avg, int32_t* kind) {
+  if (!a || !a->env || !avg || !kind) return fail(CMDP_ERR_INVALID, "null argument, or the agent's environment handle has been destroyed");
+  cmdp_t* h = a->env;
+  if (int rc = bind(h)) return rc;
+  if (int rc = ucrl2_policy_solve(a, mask, nullptr, nullptr)) return rc;
+  return chain_launch(h, a->d_ppi.p, nullptr, h->d_cur.p, mask, avg, kind, nullptr);
 }
 
 int cmdp_ucrl2_layout(cmdp_ucrl2_t* a, int64_t* n_positions, int64_t* row_ptr, int32_t* col) {

@@ -6,6 +6,9 @@
 // K3  k_dp_wave_gs<...>            : Gauss-Seidel sweeps, one wavefront per (instance[, target]), V in LDS
 // K4  k_episodic                   : backward induction, one workgroup per instance
 // K6  k_value_norm                 : value-norm reduction
+// K14 k_vi_model (cmdp_model_vi.h) : discounted VI on estimated models in K10's row form (CSR rows, or one value for a
+//                                    row that holds it everywhere), either scheme, one wavefront per instance, every
+//                                    sweep in one launch; the serial sums of the uniform rows shared
 //
 // No MFMA anywhere: rows have <= ~8 non-zeros; everything is gather / scan / max-reduce.
 // Float32 DP arithmetic uses __fmul_rn/__fadd_rn (never contracted into FMA): the reference's

@@ -133,11 +133,10 @@ def discounted_policy_iteration(T, R, gamma=0.99, epsilon=1e-7):
     raise DynamicProgrammingMaxIterationExceeded()
 
 
-# ---- extended value iteration (reference infinite_horizon.py:67-118, _max_proba :222-251), kernel K10 --------------
-def _evi_problem(T, estimated_rewards, beta_r, beta_p, r_max):
-    """One (T, estimated_rewards, beta_r, beta_p, r_max) 5-tuple -> (S, A, ptr, col, val, uniform, R, beta_r, beta_p0,
-    r_max) in the C ABI's types.  beta_p is [S, A, 1] (Chernoff) or [S, A, S] (Bernstein); only element 0 of each row
-    is read, as in the reference."""
+# ---- the row form of kernels K10 and K14: CSR rows, or one value for a row that holds it at every state -------------
+def _row_form(T):
+    """Dense T [S, A, S] -> (S, A, ptr, col, val, uniform): `uniform[r]` = c > 0 for a row that is c at every state (such a
+    row has no CSR entries), the other rows as CSR with ascending columns and no explicit zeros."""
     T = np.asarray(T)
     if T.ndim != 3 or T.shape[0] != T.shape[2] or T.shape[0] < 1 or T.shape[1] < 1:
         raise ValueError(f"T must be [S, A, S] with S, A >= 1, got shape {T.shape}")
@@ -145,6 +144,82 @@ def _evi_problem(T, estimated_rewards, beta_r, beta_p, r_max):
     T = np.ascontiguousarray(T, np.float32)
     if not np.isfinite(T).all() or (T < 0).any():
         raise ValueError("T must hold finite probabilities >= 0")
+    T2 = T.reshape(S * A, S)
+    uniform = np.where((T2[:, 0] > 0) & (T2 == T2[:, :1]).all(axis=1), T2[:, 0], np.float32(0)).astype(np.float32)
+    rows, cols = np.nonzero(T2 * (uniform == 0)[:, None])
+    ptr = np.concatenate([[0], np.cumsum(np.bincount(rows, minlength=S * A))]).astype(np.int64)
+    return S, A, ptr, cols.astype(np.int32), T2[rows, cols], uniform
+
+
+def _pack_rows(P):
+    """Row forms `(S, A, ptr, col, val, uniform, ...)` of a batch -> the concatenated (S, A, ptr, col, val, uniform) of the
+    C ABI, the row pointers shifted by the entries of the instances before."""
+    S = np.array([p[0] for p in P], np.int32)
+    A = np.array([p[1] for p in P], np.int32)
+    nz_off = np.concatenate([[0], np.cumsum([len(p[3]) for p in P])])
+    ptr = np.concatenate([[0]] + [p[2][1:] + nz_off[b] for b, p in enumerate(P)]).astype(np.int64)
+    cat = lambda i, dt: np.ascontiguousarray(np.concatenate([p[i] for p in P]), dt)  # noqa: E731
+    return S, A, ptr, cat(3, np.int32), cat(4, np.float32), cat(5, np.float32)
+
+
+def _split_rows(B, S, A, status, Q, V):
+    """[(Q [S, A], V [S]) or None where status is not OK] per instance of a packed batch."""
+    out, q0, v0 = [], 0, 0
+    for b in range(B):
+        s, a = int(S[b]), int(A[b])
+        out.append((Q[q0:q0 + s * a].reshape(s, a).copy(), V[v0:v0 + s].copy()) if status[b] == L.OK else None)
+        q0 += s * a
+        v0 += s
+    return out
+
+
+# ---- discounted value iteration on the row form (reference infinite_horizon.py:14-44), kernel K14 -------------------
+def _vi_problem(T, R):
+    """One (T, R) pair -> (S, A, ptr, col, val, uniform, R, nnz) in the C ABI's types; nnz as `sparse.COO(T).nnz`."""
+    S, A, ptr, col, val, uniform = _row_form(T)
+    R = np.ascontiguousarray(R, np.float32)
+    if R.shape != (S, A):
+        raise ValueError(f"R must be [S, A] = {(S, A)}, got {R.shape}")
+    return S, A, ptr, col, val, uniform, R.ravel(), int(len(col) + S * np.count_nonzero(uniform))
+
+
+def discounted_value_iteration_batch(problems, gamma=0.99, epsilon=1e-3, sparse_n_states_threshold=300 * 3 * 300,
+                                     sparse_nnz_per_threshold=0.2, scheme=None, max_sweeps=DP_MAX_ITERATION):
+    """`discounted_value_iteration` for many dense (T, R) problems in one launch (kernel K14); the problems may differ in S
+    and A.  Rows that hold one value at every state (an estimated model's unvisited pairs) cost one shared chain of
+    additions instead of one each.  scheme None: the reference's rule per problem, else L.SCHEME_JACOBI /
+    L.SCHEME_GAUSS_SEIDEL for all.  Returns ([(Q, V) or None per problem], sweeps [B] int64, schemes [B] int32): None where a
+    problem did not converge within max_sweeps, which leaves the others unaffected.  Q, V and sweeps are bit for bit those
+    of `discounted_value_iteration` on each problem."""
+    eps = float(epsilon)
+    if not np.isfinite(eps) or eps < 0:
+        raise ValueError(f"epsilon must be finite and >= 0, got {epsilon}")
+    if int(max_sweeps) < 1:
+        raise ValueError(f"max_sweeps must be >= 1, got {max_sweeps}")
+    if scheme not in (None, L.SCHEME_AUTO, L.SCHEME_JACOBI, L.SCHEME_GAUSS_SEIDEL):
+        raise ValueError(f"scheme must be None, SCHEME_JACOBI or SCHEME_GAUSS_SEIDEL, got {scheme}")
+    P = [_vi_problem(*p) for p in problems]
+    B = len(P)
+    if B == 0:
+        return [], np.zeros(0, np.int64), np.zeros(0, np.int32)
+    S, A, ptr, col, val, uni = _pack_rows(P)
+    R = np.ascontiguousarray(np.concatenate([p[6] for p in P]), np.float32)
+    Q = np.empty(int((S.astype(np.int64) * A).sum()), np.float32)
+    V = np.empty(int(S.sum()), np.float32)
+    sweeps, schemes, status = np.empty(B, np.int64), np.empty(B, np.int32), np.empty(B, np.int32)
+    L.check(L.load().cmdp_vi_discounted_model(B, L.ptr(S), L.ptr(A), L.ptr(ptr), L.ptr(col), L.ptr(val), L.ptr(uni), L.ptr(R),
+                                              float(gamma), eps, int(scheme or L.SCHEME_AUTO), int(sparse_n_states_threshold),
+                                              float(sparse_nnz_per_threshold), int(max_sweeps), L.ptr(Q), L.ptr(V),
+                                              L.ptr(sweeps), L.ptr(schemes), L.ptr(status)))
+    return _split_rows(B, S, A, status, Q, V), sweeps, schemes
+
+
+# ---- extended value iteration (reference infinite_horizon.py:67-118, _max_proba :222-251), kernel K10 --------------
+def _evi_problem(T, estimated_rewards, beta_r, beta_p, r_max):
+    """One (T, estimated_rewards, beta_r, beta_p, r_max) 5-tuple -> (S, A, ptr, col, val, uniform, R, beta_r, beta_p0,
+    r_max) in the C ABI's types.  beta_p is [S, A, 1] (Chernoff) or [S, A, S] (Bernstein); only element 0 of each row
+    is read, as in the reference."""
+    S, A, ptr, col, val, uniform = _row_form(T)
     R = np.ascontiguousarray(estimated_rewards, np.float32)
     br = np.ascontiguousarray(beta_r, np.float64)  # float32 bounds are widened: the one precision difference
     bp = np.asarray(beta_p, np.float64)
@@ -154,13 +229,8 @@ def _evi_problem(T, estimated_rewards, beta_r, beta_p, r_max):
         raise ValueError(f"beta_r must be [S, A] = {(S, A)}, got {br.shape}")
     if bp.ndim != 3 or bp.shape[:2] != (S, A) or bp.shape[2] not in (1, S):
         raise ValueError(f"beta_p must be [S, A, 1] or [S, A, S] with S, A = {(S, A)}, got {bp.shape}")
-    rm = float(r_max)
-    T2 = T.reshape(S * A, S)
-    uniform = np.where((T2[:, 0] > 0) & (T2 == T2[:, :1]).all(axis=1), T2[:, 0], np.float32(0)).astype(np.float32)
-    rows, cols = np.nonzero(T2 * (uniform == 0)[:, None])
-    ptr = np.concatenate([[0], np.cumsum(np.bincount(rows, minlength=S * A))]).astype(np.int64)
-    return (S, A, ptr, cols.astype(np.int32), T2[rows, cols], uniform, R.ravel(), br.ravel(),
-            np.ascontiguousarray(bp[:, :, 0], np.float64).ravel(), rm)
+    return (S, A, ptr, col, val, uniform, R.ravel(), br.ravel(), np.ascontiguousarray(bp[:, :, 0], np.float64).ravel(),
+            float(r_max))
 
 
 def _evi_run(problems, epsilon, max_sweeps):
@@ -174,14 +244,9 @@ def _evi_run(problems, epsilon, max_sweeps):
     B = len(P)
     if B == 0:
         return [], np.zeros(0, np.int64)
-    S = np.array([p[0] for p in P], np.int32)
-    A = np.array([p[1] for p in P], np.int32)
-    nnz = np.array([len(p[3]) for p in P], np.int64)
-    nz_off = np.concatenate([[0], np.cumsum(nnz)])
-    ptr = np.concatenate([[0]] + [p[2][1:] + nz_off[b] for b, p in enumerate(P)]).astype(np.int64)
+    S, A, ptr, col, val, uni = _pack_rows(P)
     cat = lambda i, dt: np.ascontiguousarray(np.concatenate([p[i] for p in P]), dt)  # noqa: E731
-    col, val, uni, R, br, bp0 = (cat(3, np.int32), cat(4, np.float32), cat(5, np.float32), cat(6, np.float32),
-                                 cat(7, np.float64), cat(8, np.float64))
+    R, br, bp0 = cat(6, np.float32), cat(7, np.float64), cat(8, np.float64)
     rmax = np.array([p[9] for p in P], np.float64)
     rows = (S.astype(np.int64) * A).sum()
     Q = np.empty(rows, np.float32)

@@ -270,7 +270,9 @@ enum { CMDP_STAT_DP_KERNEL_MS = 1, CMDP_STAT_DP_KERNEL = 2,
                                                 -- e.g. 3160 = K5S-ELL with 16 wavefronts, 5081 = K5C with clusters of 8 at XCD
                                                 scope.  A K5C launch that gave up reports the K5S kernel that solved the targets
                                                 instead.  When the workspace limit splits a call into several launches of
-                                                different widths, the last launch is reported.  Set on the host; read-only.        */ };
+                                                different widths, the last launch is reported.  Set on the host; read-only.        */,
+       CMDP_STAT_UCRL2_POLICY_KERNEL_MS = 23 /* UCRL2 agents of this handle: HIP-event time of the last K14 launch (the solve of
+                                                cmdp_ucrl2_policy / cmdp_ucrl2_average_reward)                                     */ };
 /* The UCRL2 and PSRL statistics belong to the environment handle: agents created on the same handle share them. */
 int cmdp_stat(cmdp_t* h, int which, double* out);
 /* Latency floor of the LDS-resident rollout kernels, measured on the current device: one wavefront per CU follows
@@ -656,6 +658,26 @@ int cmdp_extended_vi(int count, const int32_t* n_states, const int32_t* n_action
                      const double* beta_r, const double* beta_p0, const double* r_max, double epsilon,
                      int64_t max_sweeps, float* Q, float* V, double* span, int64_t* sweeps, int32_t* status);
 
+/* The rule discounted_value_iteration picks its scheme by (infinite_horizon.py:28-36) as kernel K14 applies it:
+   CMDP_SCHEME_JACOBI when n_states * n_actions * n_states > size_threshold and nnz / (n_states * n_actions * n_states) <
+   density_threshold, else CMDP_SCHEME_GAUSS_SEIDEL.  Host only: no device is looked for. */
+int cmdp_model_vi_scheme(int n_states, int n_actions, int64_t nnz, int64_t size_threshold, double density_threshold);
+
+/* discounted_value_iteration (infinite_horizon.py:14-44) for `count` models in cmdp_extended_vi's row form at once on the
+   current device (kernel K14); one launch runs every instance to convergence or to max_sweeps.  n_states[b] <= 4096,
+   n_actions[b] <= 64 (else CMDP_ERR_UNSUPPORTED); csr_ptr / csr_col / csr_val / uniform / rewards as for cmdp_extended_vi,
+   a uniform row counting as its S entries c in column order.  scheme: CMDP_SCHEME_JACOBI or CMDP_SCHEME_GAUSS_SEIDEL for
+   every instance, or CMDP_SCHEME_AUTO: per instance cmdp_model_vi_scheme on nnz = entries with csr_val > 0 plus n_states
+   per uniform row (the reference's defaults: size_threshold 300 * 3 * 300, density_threshold 0.2).  Q [n_rows], V [n_states]
+   and sweeps [count] are bit for bit those of cmdp_vi_discounted with the same scheme on the CSR of the dense model;
+   scheme_used [count] the scheme taken; status [count] 0 or CMDP_ERR_MAX_ITER -- an instance that does not converge does not
+   fail the call.  Arguments are checked on the host before a device is looked for.  A per-device workspace is reused across
+   calls; calls are serialised. */
+int cmdp_vi_discounted_model(int count, const int32_t* n_states, const int32_t* n_actions, const int64_t* csr_ptr,
+                             const int32_t* csr_col, const float* csr_val, const float* uniform, const float* rewards,
+                             float gamma, double epsilon, int scheme, int64_t size_threshold, double density_threshold,
+                             int64_t max_sweeps, float* Q, float* V, int64_t* sweeps, int32_t* scheme_used, int32_t* status);
+
 /* ---- UCRL2 on the device (kernel K11) ------------------------------------------------------------------------- */
 /* One UCRL2Continuous (colosseum/agent/agents/infinite_horizon/ucrl2.py:33-357) per instance of a CONTINUOUS environment
    handle on the CSR layout, driven as MDPLoop.run drives it (colosseum/experiment/agent_mdp_interaction.py:224-263):
@@ -704,8 +726,18 @@ int cmdp_ucrl2_last_solve(cmdp_ucrl2_t* a, float* P_val, float* uniform, float* 
                           float* Q, double* span, int64_t* sweeps, int32_t* status);
 /* CMDP_UCRL2_OPT_MAX_SWEEPS: sweeps a solve may take (default 10**6, the reference's DP_MAX_ITERATION); for tests of the
    not-converged path. */
-enum { CMDP_UCRL2_OPT_MAX_SWEEPS = 1 };
+/* CMDP_UCRL2_OPT_POLICY_SIZE_THRESHOLD: the size threshold of the scheme rule in cmdp_ucrl2_policy's solve (default
+   300 * 3 * 300, the reference's); a test hook that lets small instances take the Jacobi scheme. */
+enum { CMDP_UCRL2_OPT_MAX_SWEEPS = 1, CMDP_UCRL2_OPT_POLICY_SIZE_THRESHOLD = 2 };
 int cmdp_ucrl2_set_option(cmdp_ucrl2_t* a, int option, int64_t value);
+/* UCRL2Continuous.current_optimal_stochastic_policy (ucrl2.py:80-83) of the instances with mask[b] != 0 (NULL: all), on the
+   device: kernel K14 on the agent's own tables (gamma 0.99, epsilon 1e-3, the reference's scheme rule), then argmax_2d with
+   the RandomState(42) tie-break.  pi [R] one-hot float32, Q [R], sweeps [B], scheme_used [B]; each may be NULL, and what
+   belongs to an instance outside the mask is left as it was.  CMDP_ERR_MAX_ITER names an instance whose solve took 10**6
+   sweeps (the reference raises there).  The actor's Q and streams, the counts and the environment are not touched. */
+int cmdp_ucrl2_policy(cmdp_ucrl2_t* a, const uint8_t* mask, float* pi, float* Q, int64_t* sweeps, int32_t* scheme_used);
+/* ... and get_average_reward of that policy from the environments' current states (as cmdp_qlearning_average_reward). */
+int cmdp_ucrl2_average_reward(cmdp_ucrl2_t* a, const uint8_t* mask, double* avg, int32_t* kind);
 
 /* One PSRLEpisodic (colosseum/agent/agents/episodic/posterior_sampling.py with BayesianMDPModel, N_NIG rewards and M_DIR
    transitions) per instance of an EPISODIC environment handle, driven as MDPLoop.run drives it
