@@ -33,6 +33,7 @@ STAT_UCRL2_WAIT_MS = 16
 STAT_PSRL_ROUNDS, STAT_PSRL_SOLVES, STAT_PSRL_SAMPLE_KERNEL_MS, STAT_PSRL_VI_KERNEL_MS, STAT_PSRL_REFERENCE_MS = 17, 18, 19, 20, 21
 STAT_DIAMETER_KERNEL = 22  # family * 1000 + n * 10 + flag, see include/cmdp.h
 STAT_UCRL2_POLICY_KERNEL_MS = 23
+STAT_PSRL_POLICY_KERNEL_MS = 24
 PSRL_SAMPLER_REFERENCE, PSRL_SAMPLER_PHILOX = 0, 1
 PSRL_KEY_HI = 0x5053524C
 BOUND_CHERNOFF, BOUND_BERNSTEIN = 0, 1
@@ -83,6 +84,7 @@ EXPORTS = [
     "cmdp_psrl_reference_sample", "cmdp_vi_episodic_dense", "cmdp_psrl_episode_end_update", "cmdp_k1e_round_interior",
     "cmdp_k1e_code_counts", "cmdp_k1s_plan", "cmdp_k1s_plan_desc", "cmdp_det_plan", "cmdp_det_plan_desc", "cmdp_chain_plan_desc", "cmdp_chain_choice",
     "cmdp_k1e_pair_plan", "cmdp_k1e_pair_plan_desc",
+    "cmdp_psrl_map_rows", "cmdp_vi_episodic_map", "cmdp_psrl_policy", "cmdp_psrl_evaluate",
 ]
 
 
@@ -249,6 +251,10 @@ def load():
         L.cmdp_psrl_last_sample.argtypes = [vp, vp, vp, vp]
         L.cmdp_psrl_reference_sample.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, f32, vp, vp, vp]
         L.cmdp_vi_episodic_dense.argtypes = [i32, vp, vp, i32, vp, vp, vp, vp]
+        L.cmdp_psrl_map_rows.argtypes = [i32, i32, vp, vp, vp, f32, vp, vp, vp]
+        L.cmdp_vi_episodic_map.argtypes = [i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.cmdp_psrl_policy.argtypes = [vp, vp, vp, vp]
+        L.cmdp_psrl_evaluate.argtypes = [vp, vp, vp]
         L.cmdp_k1e_round_interior.argtypes = [i32, i32, i64, i32]
         L.cmdp_k1e_code_counts.argtypes = [C.c_uint32, C.c_uint32, i32]
         L.cmdp_k1s_plan.argtypes = [vp, vp]

@@ -180,6 +180,11 @@ class _ParkAndSolveAgent(_DeviceAgent):
             out.append(M.reshape(S, env.A, S))
         return out
 
+    def _mask(self, mask):
+        m = None if mask is None else np.ascontiguousarray(mask, np.uint8)
+        assert m is None or m.shape == (self.env.B,)
+        return m, (range(self.env.B) if m is None else np.flatnonzero(m))
+
     def _stats(self) -> dict:
         v, out = C.c_double(), {}
         for k, w in self._STATS:
@@ -255,11 +260,6 @@ class BatchedUCRL2Continuous(_ParkAndSolveAgent):
         return dict(P=self._dense(P, np.float32, uniform=uni), estimated_rewards=sa(er), beta_r=sa(br), beta_p0=sa(bp), Q=sa(Q),
                     span=span, sweeps=sweeps, status=status)
 
-    def _mask(self, mask):
-        m = None if mask is None else np.ascontiguousarray(mask, np.uint8)
-        assert m is None or m.shape == (self.env.B,)
-        return m, (range(self.env.B) if m is None else np.flatnonzero(m))
-
     def policy(self, mask=None):
         """ucrl2.py:80-83 on the device: argmax_2d (RandomState(42) tie-break) of discounted value iteration on the estimated
         model (kernel K14), per instance [S, A]; with `mask`, for the selected instances only, in their order."""
@@ -320,7 +320,8 @@ class BatchedPSRLEpisodic(_ParkAndSolveAgent):
 
     _DESTROY, _PREFIX = "cmdp_psrl_destroy", "cmdp_psrl"
     _STATS = (("rounds", L.STAT_PSRL_ROUNDS), ("solves", L.STAT_PSRL_SOLVES), ("sample_kernel_ms", L.STAT_PSRL_SAMPLE_KERNEL_MS),
-              ("vi_kernel_ms", L.STAT_PSRL_VI_KERNEL_MS), ("reference_ms", L.STAT_PSRL_REFERENCE_MS))
+              ("vi_kernel_ms", L.STAT_PSRL_VI_KERNEL_MS), ("reference_ms", L.STAT_PSRL_REFERENCE_MS),
+              ("policy_kernel_ms", L.STAT_PSRL_POLICY_KERNEL_MS))
     _SAMPLERS = {"reference": L.PSRL_SAMPLER_REFERENCE, "philox": L.PSRL_SAMPLER_PHILOX}
 
     def __init__(self, env: BatchedMDP, seeds: Sequence[int], optimization_horizon: int, reward_prior_model=None,
@@ -414,15 +415,46 @@ class BatchedPSRLEpisodic(_ParkAndSolveAgent):
         m = self.model()
         return [(t / t.sum(-1, keepdims=True), r[:, :, 0]) for t, r in zip(m["transitions"], m["rewards"])]
 
-    def current_optimal_stochastic_policy(self):
-        """posterior_sampling.py:78-82 per instance: argmax_3d of episodic value iteration on the MAP estimate (host side:
-        it is called per log row only)."""
-        from .dynamic_programming import argmax_3d, episodic_value_iteration
+    def _layers(self, x):
+        """A per-instance [H + 1][S][A] array of the library's -> list of [H + 1, S, A]."""
+        env, H = self.env, int(self.env.H)
+        out = []
+        for b in range(env.B):
+            q0, n = (H + 1) * int(env.row_off[b]), (H + 1) * int(env.n_states[b]) * env.A
+            out.append(x[q0:q0 + n].reshape(H + 1, -1, env.A))
+        return out
 
-        return [argmax_3d(episodic_value_iteration(int(self.env.H), np.ascontiguousarray(T), np.ascontiguousarray(R))[0])
-                for T, R in self.map_estimate()]
+    def policy(self, mask=None):
+        """posterior_sampling.py:78-82 on the device: argmax_3d (RandomState(42) tie-break) of episodic value iteration on
+        the MAP estimate of the model (kernel K15, no dense array), per instance [H + 1, S, A]; with `mask`, for the
+        selected instances only, in their order.  Touches nothing the agent acts or learns with."""
+        m, sel = self._mask(mask)
+        pi = np.zeros((int(self.env.H) + 1) * int(self.env.row_off[-1]), np.float32)
+        L.check(self._lib.cmdp_psrl_policy(self._h, L.ptr(m), L.ptr(pi), None))
+        rows = self._layers(pi)
+        return [rows[b] for b in sel]
+
+    def policy_solve(self, mask=None):
+        """The solve behind `policy()`: `Q` per instance [H + 1, S, A] float32; with `mask`, zeros elsewhere."""
+        m, _ = self._mask(mask)
+        Q = np.zeros((int(self.env.H) + 1) * int(self.env.row_off[-1]), np.float32)
+        L.check(self._lib.cmdp_psrl_policy(self._h, L.ptr(m), None, L.ptr(Q)))
+        return dict(Q=self._layers(Q))
+
+    def evaluate(self, mask=None) -> np.ndarray:
+        """V[0, :] (concatenated over instances) of `policy()` on the true MDP -- what the episodic regret needs -- solve,
+        policy and evaluation on the device; with `mask`, zeros for the other instances."""
+        m, _ = self._mask(mask)
+        V0 = np.zeros(int(self.env.state_off[-1]), np.float32)
+        L.check(self._lib.cmdp_psrl_evaluate(self._h, L.ptr(m), L.ptr(V0)))
+        return V0
+
+    def current_optimal_stochastic_policy(self):
+        """posterior_sampling.py:78-82 per instance: `policy()`."""
+        return self.policy()
 
     def stats(self) -> dict:
         """Rounds of parked instances, instances solved in them, HIP-event times of the last round's sample and solve
-        kernels, host time of the reference sampler's draws.  Kept per ENVIRONMENT handle."""
+        kernels, host time of the reference sampler's draws, HIP-event time of K15 in the last policy() / policy_solve() /
+        evaluate().  Kept per ENVIRONMENT handle."""
         return self._stats()

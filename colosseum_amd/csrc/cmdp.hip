@@ -39,6 +39,7 @@ extern char** environ;
 #include "cmdp_model_vi.h"
 #include "cmdp_ucrl2.h"
 #include "cmdp_psrl.h"
+#include "cmdp_map_vi.h"
 
 namespace {
 
@@ -297,6 +298,7 @@ struct cmdp {
   // PSRL agents on this handle (cmdp_psrl_*): CMDP_STAT_PSRL_*
   int64_t ps_rounds = 0, ps_solves = 0;
   double ps_sample_ms = 0.0, ps_vi_ms = 0.0, ps_ref_ms = 0.0;
+  double ps_policy_ms = 0.0;   // CMDP_STAT_PSRL_POLICY_KERNEL_MS: the last K15 launch of an agent of this handle
   DevBuf<float> d_dense;  // CMDP_LAYOUT_DENSE: [R][dense_spad]
   int dense_spad = 0;
   DevBuf<uint16_t> d_next16;
@@ -1756,8 +1758,8 @@ int cmdp_stat(cmdp_t* h, int which, double* out) {
            : which == CMDP_STAT_PSRL_SAMPLE_KERNEL_MS ? h->ps_sample_ms : which == CMDP_STAT_PSRL_VI_KERNEL_MS ? h->ps_vi_ms : h->ps_ref_ms;
     return CMDP_OK;
   }
-  if (which == CMDP_STAT_UCRL2_POLICY_KERNEL_MS) {
-    *out = h->uc_policy_ms;
+  if (which == CMDP_STAT_UCRL2_POLICY_KERNEL_MS || which == CMDP_STAT_PSRL_POLICY_KERNEL_MS) {
+    *out = which == CMDP_STAT_UCRL2_POLICY_KERNEL_MS ? h->uc_policy_ms : h->ps_policy_ms;
     return CMDP_OK;
   }
   if (which == CMDP_STAT_UCRL2_UNCONVERGED) {
@@ -4674,8 +4676,15 @@ struct cmdp_psrl : ParkAgent {
   DevBuf<uint2> d_key;
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};   // around k_psrl_sample and k_vi_episodic_dense of the last round
   bool ev_sample = false, ev_vi = false;
+  // the MAP-policy solve (K15, cmdp_psrl_policy / cmdp_psrl_evaluate): buffers of its own, allocated by the first call
+  DevBuf<float> d_mapt, d_mapc, d_mQ, d_mV, d_mpi, d_mpiH, d_mv0;
+  DevBuf<int32_t> d_mlist;
+  hipEvent_t m_ev[2] = {nullptr, nullptr};
+  size_t map_lds = 0;   // dynamic LDS of a K15 launch on this batch
   ~cmdp_psrl() {
     for (hipEvent_t e : ev)
+      if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : m_ev)
       if (e) (void)hipEventDestroy(e);
   }
 };
@@ -4688,6 +4697,86 @@ int dvi_launch(const DviArgs& g, int count, size_t lds, hipStream_t st) {
   if (int rc = set_lds(k_vi_episodic_dense, lds)) return rc;
   hipLaunchKernelGGL(k_vi_episodic_dense, dim3(count), dim3(PSRL_VI_THREADS), lds, st, g);
   HIP_TRY(hipGetLastError());
+  return CMDP_OK;
+}
+
+// K15's launch on device-resident arguments: what cmdp_vi_episodic_map does after its uploads and what the PSRL agent does
+// for its MAP policy (cmdp_psrl_policy / cmdp_psrl_evaluate)
+int mapvi_launch(MapViArgs g, int count, int max_S, size_t lds, hipStream_t st) {
+  if (max_S > MAPVI_MAX_STATES)
+    return fail(CMDP_ERR_UNSUPPORTED, "%d states: value iteration on a MAP model (K15) keeps two value layers in LDS for at most %d",
+                max_S, MAPVI_MAX_STATES);
+  if (count == 0) return CMDP_OK;
+  g.lds_bytes = (unsigned)lds;   // the largest map_vi_lds_bytes of the launch's instances
+  if (int rc = set_lds(k_vi_episodic_map, lds)) return rc;
+  hipLaunchKernelGGL(k_vi_episodic_map, dim3(count), dim3(MAPVI_THREADS), lds, st, g);
+  HIP_TRY(hipGetLastError());
+  return CMDP_OK;
+}
+
+// episodic_value_iteration(H, *get_map_estimate()) (K15) for the instances of `mask` on the handle's stream, over the agent's
+// posterior tables; Q in d_mQ.  Reads nothing but the model and writes nothing of the agent's but these buffers.  The
+// instances it solved are left in `sel`; the caller waits for the stream and then calls psrl_map_time.
+int psrl_map_solve(cmdp_psrl_t* a, const uint8_t* mask, std::vector<int32_t>& sel) {
+  cmdp_t* h = a->env;
+  hipStream_t st = h->stream;
+  const int B = h->B, H = h->H;
+  const int64_t R = h->n_rows;
+  if (!a->d_mQ.p) {
+    HIP_TRY(a->d_mapt.alloc((size_t)a->nz));
+    HIP_TRY(a->d_mapc.alloc((size_t)R));
+    HIP_TRY(a->d_mV.alloc((size_t)(H + 1) * h->n_states));
+    HIP_TRY(a->d_mpi.alloc((size_t)(H + 1) * R));
+    HIP_TRY(a->d_mpiH.alloc((size_t)H * R));
+    HIP_TRY(a->d_mv0.alloc((size_t)h->n_states));
+    HIP_TRY(a->d_mlist.alloc((size_t)B));
+    for (hipEvent_t& e : a->m_ev) HIP_TRY(hipEventCreate(&e));
+    a->map_lds = 0;
+    for (int b = 0; b < B; ++b) {
+      const int64_t s0 = h->state_off[b], s1 = h->state_off[b + 1];
+      a->map_lds = std::max(a->map_lds, map_vi_lds_bytes((int)(s1 - s0), h->A, a->h_ptr[(size_t)(s1 * h->A)] - a->h_ptr[(size_t)(s0 * h->A)]));
+    }
+    HIP_TRY(a->d_mQ.alloc((size_t)(H + 1) * R));
+  }
+  sel.clear();
+  for (int b = 0; b < B; ++b)
+    if (!mask || mask[b]) sel.push_back(b);
+  const int32_t* list = nullptr;
+  if (mask) {
+    HIP_TRY(a->d_mQ.zero(st));   // the greedy kernel walks every instance: those outside the mask keep no Q of an earlier call
+    HIP_TRY(a->d_mlist.upload(sel.data(), sel.size(), st));
+    HIP_TRY(hipStreamSynchronize(st));   // `sel` may be reallocated by the caller
+    list = a->d_mlist.p;
+  }
+  MapViArgs g{list, a->d_S.p, a->d_A.p, a->d_roff.p, h->d_state_off.p, a->d_row_ptr.p, a->d_col.p, a->d_tp.p, a->d_tprior.p,
+              a->d_rp.p, 4, a->d_mapt.p, a->d_mapc.p, a->d_mQ.p, a->d_mV.p, H, 0};
+  HIP_TRY(hipEventRecord(a->m_ev[0], st));
+  if (int rc = mapvi_launch(g, (int)sel.size(), h->max_S, a->map_lds, st)) return rc;
+  HIP_TRY(hipEventRecord(a->m_ev[1], st));
+  return CMDP_OK;
+}
+
+int psrl_map_time(cmdp_psrl_t* a) {   // after a stream synchronisation
+  float ms = 0.0f;
+  HIP_TRY(hipEventElapsedTime(&ms, a->m_ev[0], a->m_ev[1]));
+  a->env->ps_policy_ms = (double)ms;
+  return CMDP_OK;
+}
+
+// the selected instances' segments of a per-instance device array ([lead * rows or states]) into a zeroed host array
+template <typename OffsetOf>
+int psrl_map_fetch(cmdp_psrl_t* a, const std::vector<int32_t>& sel, float* dst, const float* src, size_t total, OffsetOf&& span) {
+  if (!dst) return CMDP_OK;
+  hipStream_t st = a->env->stream;
+  if ((int)sel.size() == a->env->B) {
+    HIP_TRY(hipMemcpyAsync(dst, src, sizeof(float) * total, hipMemcpyDeviceToHost, st));
+    return CMDP_OK;
+  }
+  std::memset(dst, 0, sizeof(float) * total);
+  for (int32_t b : sel) {
+    const std::pair<int64_t, int64_t> s = span(b);   // (first element, count)
+    HIP_TRY(hipMemcpyAsync(dst + s.first, src + s.first, sizeof(float) * (size_t)s.second, hipMemcpyDeviceToHost, st));
+  }
   return CMDP_OK;
 }
 
@@ -5014,6 +5103,162 @@ int cmdp_vi_episodic_dense(int count, const int32_t* n_states, const int32_t* n_
   HIP_TRY(hipMemcpyAsync(V, ws->V.p, sizeof(float) * (size_t)(H + 1) * ns, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   return CMDP_OK;
+}
+
+// ---- the MAP model's solve (K15, cmdp_map_vi.h) -----------------------------------------------------------------------
+static int map_check_layout(int b, int64_t S, int64_t A, const int64_t* row_ptr, const int32_t* col, const float* hp, float prior) {
+  if (!(prior > 0.0f) || !std::isfinite(prior)) return fail(CMDP_ERR_INVALID, "prior[%d] = %g is not a finite value > 0", b, (double)prior);
+  for (int64_t r = 0; r < S * A; ++r) {
+    if (row_ptr[r + 1] < row_ptr[r]) return fail(CMDP_ERR_INVALID, "instance %d: row_ptr decreases at row %lld", b, (long long)r);
+    for (int64_t z = row_ptr[r]; z < row_ptr[r + 1]; ++z)
+      if (col[z] < 0 || col[z] >= S || (z > row_ptr[r] && col[z] <= col[z - 1]) || !(hp[z] >= 0.0f) || !std::isfinite(hp[z]))
+        return fail(CMDP_ERR_INVALID, "instance %d, row %lld of the layout: columns ascending within [0, %d), values finite and >= 0",
+                    b, (long long)r, (int)S);
+  }
+  return CMDP_OK;
+}
+
+int cmdp_psrl_map_rows(int n_states, int n_actions, const int64_t* row_ptr, const int32_t* col, const float* hp, float prior,
+                       float* rowsum, float* c, float* t) {
+  if (n_states < 1 || n_actions < 1) return fail(CMDP_ERR_INVALID, "n_states and n_actions must be >= 1");
+  if (!row_ptr || (row_ptr[(int64_t)n_states * n_actions] > row_ptr[0] && (!col || !hp))) return fail(CMDP_ERR_INVALID, "null argument");
+  if (int rc = map_check_layout(0, n_states, n_actions, row_ptr, col, hp, prior)) return rc;
+  map_vi_host::map_rows(n_states, n_actions, row_ptr, col, hp, prior, psrl_host::pairwise_sum_f32, rowsum, c, t);
+  return CMDP_OK;
+}
+
+int cmdp_vi_episodic_map(int count, const int32_t* n_states, const int32_t* n_actions, int H, const int64_t* row_ptr,
+                         const int32_t* col, const float* hp, const float* prior, const float* mu, float* Q, float* V,
+                         float* t_layout_out, float* c_out) {
+  if (count < 0) return fail(CMDP_ERR_INVALID, "count %d is negative", count);
+  if (count == 0) return CMDP_OK;
+  if (!n_states || !n_actions || !row_ptr || !prior || !mu || !Q || !V) return fail(CMDP_ERR_INVALID, "null argument");
+  if (H < 1) return fail(CMDP_ERR_INVALID, "H %d < 1", H);
+  std::vector<int64_t> soff((size_t)count + 1), roff((size_t)count);
+  int64_t ns = 0, nr = 0;
+  int max_S = 1;
+  for (int b = 0; b < count; ++b) {
+    const int64_t S = n_states[b], A = n_actions[b];
+    if (S < 1) return fail(CMDP_ERR_INVALID, "n_states[%d] = %d < 1", b, (int)S);
+    if (A < 1) return fail(CMDP_ERR_INVALID, "n_actions[%d] = %d < 1", b, (int)A);
+    if (S > MAPVI_MAX_STATES)
+      return fail(CMDP_ERR_UNSUPPORTED, "instance %d has %d states: value iteration on a MAP model (K15) keeps two value layers in "
+                  "LDS for at most %d states", b, (int)S, MAPVI_MAX_STATES);
+    soff[b] = ns; roff[b] = nr;
+    ns += S; nr += S * A;
+    max_S = std::max(max_S, (int)S);
+  }
+  soff[count] = ns;
+  if (row_ptr[0] != 0) return fail(CMDP_ERR_INVALID, "row_ptr[0] = %lld, not 0", (long long)row_ptr[0]);
+  const int64_t nz = row_ptr[nr];
+  if (nz > 0 && (!col || !hp)) return fail(CMDP_ERR_INVALID, "null argument");
+  size_t lds = 0;
+  for (int b = 0; b < count; ++b) {
+    if (int rc = map_check_layout(b, n_states[b], n_actions[b], row_ptr + roff[b], col, hp, prior[b])) return rc;
+    lds = std::max(lds, map_vi_lds_bytes(n_states[b], n_actions[b], row_ptr[roff[b] + (int64_t)n_states[b] * n_actions[b]] - row_ptr[roff[b]]));
+  }
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(CMDP_ERR_NO_DEVICE, "no HIP device visible");
+  // Workspace reused across calls, one per device, deliberately leaked at exit; calls are serialised by a mutex
+  struct Ws {
+    DevBuf<int32_t> S, A, col;
+    DevBuf<int64_t> soff, roff, ptr;
+    DevBuf<float> hp, prior, mu, t, c, Q, V;
+    hipStream_t st = nullptr;
+  };
+  static std::mutex mtx;
+  static std::map<int, Ws*>* all = new std::map<int, Ws*>;
+  std::lock_guard<std::mutex> lock(mtx);
+  int dev = 0;
+  HIP_TRY(hipGetDevice(&dev));
+  Ws*& ws = (*all)[dev];
+  if (!ws) {
+    ws = new Ws;
+    HIP_TRY(hipStreamCreateWithFlags(&ws->st, hipStreamNonBlocking));
+  }
+  hipStream_t st = ws->st;
+  HIP_TRY(ws->S.upload(n_states, count, st));
+  HIP_TRY(ws->A.upload(n_actions, count, st));
+  HIP_TRY(ws->soff.upload(soff.data(), count + 1, st));
+  HIP_TRY(ws->roff.upload(roff.data(), count, st));
+  HIP_TRY(ws->ptr.upload(row_ptr, (size_t)nr + 1, st));
+  HIP_TRY(ws->col.upload(col, (size_t)nz, st));
+  HIP_TRY(ws->hp.upload(hp, (size_t)nz, st));
+  HIP_TRY(ws->prior.upload(prior, count, st));
+  HIP_TRY(ws->mu.upload(mu, (size_t)nr, st));
+  HIP_TRY(ws->t.alloc((size_t)nz));
+  HIP_TRY(ws->c.alloc((size_t)nr));
+  HIP_TRY(ws->Q.alloc((size_t)(H + 1) * nr));
+  HIP_TRY(ws->V.alloc((size_t)(H + 1) * ns));
+  MapViArgs g{nullptr, ws->S.p, ws->A.p, ws->roff.p, ws->soff.p, ws->ptr.p, ws->col.p, ws->hp.p, ws->prior.p, ws->mu.p, 1,
+              ws->t.p, ws->c.p, ws->Q.p, ws->V.p, H, 0};
+  if (int rc = mapvi_launch(g, count, max_S, lds, st)) return rc;
+  HIP_TRY(hipMemcpyAsync(Q, ws->Q.p, sizeof(float) * (size_t)(H + 1) * nr, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(V, ws->V.p, sizeof(float) * (size_t)(H + 1) * ns, hipMemcpyDeviceToHost, st));
+  if (t_layout_out && nz) HIP_TRY(hipMemcpyAsync(t_layout_out, ws->t.p, sizeof(float) * (size_t)nz, hipMemcpyDeviceToHost, st));
+  if (c_out) HIP_TRY(hipMemcpyAsync(c_out, ws->c.p, sizeof(float) * (size_t)nr, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return CMDP_OK;
+}
+
+int cmdp_psrl_policy(cmdp_psrl_t* a, const uint8_t* mask, float* pi, float* Q) {
+  if (!a || !a->env) return fail(CMDP_ERR_INVALID, "null agent, or its environment handle has been destroyed");
+  cmdp_t* h = a->env;
+  if (int rc = bind(h)) return rc;
+  hipStream_t st = h->stream;
+  const int H = h->H;
+  std::vector<int32_t> sel;
+  if (int rc = psrl_map_solve(a, mask, sel)) return rc;
+  // get_policy_from_q_values(Q, True) = argmax_3d over all H + 1 layers (posterior_sampling.py:82)
+  if (pi) {
+    hipLaunchKernelGGL(k_greedy_policy_episodic<float>, dim3(h->B), dim3(64), 0, st, h->B, h->A, H + 1, H + 1, h->d_state_off.p,
+                       a->d_mQ.p, a->d_mpi.p);
+    HIP_TRY(hipGetLastError());
+  }
+  const size_t total = (size_t)(H + 1) * h->n_rows;
+  auto span = [&](int b) {
+    return std::make_pair((int64_t)(H + 1) * h->state_off[b] * h->A, (int64_t)(H + 1) * (h->state_off[b + 1] - h->state_off[b]) * h->A);
+  };
+  if (int rc = psrl_map_fetch(a, sel, pi, a->d_mpi.p, total, span)) return rc;
+  if (int rc = psrl_map_fetch(a, sel, Q, a->d_mQ.p, total, span)) return rc;
+  HIP_TRY(hipStreamSynchronize(st));
+  return psrl_map_time(a);
+}
+
+int cmdp_psrl_evaluate(cmdp_psrl_t* a, const uint8_t* mask, float* V0) {
+  if (!a || !a->env || !V0) return fail(CMDP_ERR_INVALID, "null argument, or the agent's environment handle has been destroyed");
+  cmdp_t* h = a->env;
+  if (int rc = bind(h)) return rc;
+  if (!h->has_dp)
+    return fail(CMDP_ERR_UNSUPPORTED, "cmdp_psrl_evaluate evaluates the policy on the true MDP: the environment handle was created "
+                "without the DP half (CSR transition matrices)");
+  hipStream_t st = h->stream;
+  const int H = h->H;
+  const size_t lds = 2 * sizeof(float) * (size_t)h->max_S;
+  if (lds > (size_t)kLdsBudget) return fail(CMDP_ERR_UNSUPPORTED, "instance with %d states does not fit LDS", h->max_S);
+  std::vector<int32_t> sel;
+  if (int rc = psrl_map_solve(a, mask, sel)) return rc;
+  // the first H layers of argmax_3d's walk: the same draws of its tie-break stream, laid out as the evaluation reads them
+  hipLaunchKernelGGL(k_greedy_policy_episodic<float>, dim3(h->B), dim3(64), 0, st, h->B, h->A, H, H + 1, h->d_state_off.p,
+                     a->d_mQ.p, a->d_mpiH.p);
+  HIP_TRY(hipGetLastError());
+  const size_t nq = (size_t)(H + 1) * h->n_rows, nv = (size_t)(H + 1) * h->n_states;
+  if (h->d_Q.n < nq) HIP_TRY(h->d_Q.alloc(nq));
+  if (h->d_V.n < nv) HIP_TRY(h->d_V.alloc(nv));
+  DpTables t = dp_tables(h);
+  t.pi = a->d_mpiH.p;
+  if (int rc = set_lds(k_episodic<DP_PE>, lds)) return rc;
+  hipLaunchKernelGGL((k_episodic<DP_PE>), dim3(h->B), dim3(kDpBlock), lds, st, t, H, h->d_Q.p, h->d_V.p);
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(k_gather_v0, dim3(h->B), dim3(256), 0, st, h->B, H, h->d_state_off.p, h->d_V.p, a->d_mv0.p, h->d_last_start.p,
+                     h->d_prev_start.p, h->d_h.p, (int32_t*)nullptr);
+  HIP_TRY(hipGetLastError());
+  if (int rc = psrl_map_fetch(a, sel, V0, a->d_mv0.p, (size_t)h->n_states, [&](int b) {
+        return std::make_pair((int64_t)h->state_off[b], (int64_t)(h->state_off[b + 1] - h->state_off[b]));
+      }))
+    return rc;
+  HIP_TRY(hipStreamSynchronize(st));
+  return psrl_map_time(a);
 }
 
 }  // extern "C"

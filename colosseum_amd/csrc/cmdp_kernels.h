@@ -9,6 +9,8 @@
 // K14 k_vi_model (cmdp_model_vi.h) : discounted VI on estimated models in K10's row form (CSR rows, or one value for a
 //                                    row that holds it everywhere), either scheme, one wavefront per instance, every
 //                                    sweep in one launch; the serial sums of the uniform rows shared
+// K15 k_vi_episodic_map (cmdp_map_vi.h) : episodic VI on the MAP estimate of a Bayesian model from its tables (layout
+//                                    positions over a prior), one workgroup per instance, no dense array
 //
 // No MFMA anywhere: rows have <= ~8 non-zeros; everything is gather / scan / max-reduce.
 // Float32 DP arithmetic uses __fmul_rn/__fadd_rn (never contracted into FMA): the reference's

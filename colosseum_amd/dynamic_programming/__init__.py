@@ -111,6 +111,103 @@ def episodic_value_iteration_dense_batch(problems, H):
     return out
 
 
+def map_layout_from_dense(transition_hp, prior, keep=None):
+    """Table form of dense M_DIR hyper-parameters [S, A, S] over `prior`: the positions that differ from the prior, plus
+    those `keep` (bool [S, A, S]) names, per row in ascending column order -> (row_ptr [S * A + 1], col, hp)."""
+    thp = np.ascontiguousarray(transition_hp, np.float32)
+    S, A, S2 = thp.shape
+    assert S == S2, thp.shape
+    m = thp != np.float32(prior)
+    if keep is not None:
+        m = m | np.asarray(keep, bool).reshape(thp.shape)
+    m = m.reshape(S * A, S)
+    rows, cols = np.nonzero(m)
+    row_ptr = np.concatenate([[0], np.cumsum(m.sum(-1))]).astype(np.int64)
+    return row_ptr, cols.astype(np.int32), thp.reshape(S * A, S)[rows, cols]
+
+
+def map_layout_to_dense(row_ptr, col, hp, prior, S, A):
+    """The dense [S, A, S] float32 hyper-parameters of a table form."""
+    row_ptr = np.asarray(row_ptr, np.int64)
+    M = np.full((S * A, S), prior, np.float32)
+    M[np.repeat(np.arange(S * A), np.diff(row_ptr)), np.asarray(col, np.int64)] = np.asarray(hp, np.float32)
+    return M.reshape(S, A, S)
+
+
+def psrl_map_rows(row_ptr, col, hp, prior, S, A):
+    """M_DIR.get_map_estimate of one instance in table form, on the host (cmdp_psrl_map_rows; no device needed):
+    (rowsum [S, A], c [S, A], t per layout position) float32 -- numpy's pairwise float32 row sums of the dense array, the
+    MAP value of every element outside the layout and of the layout's elements."""
+    row_ptr = np.ascontiguousarray(row_ptr, np.int64)
+    col, hp = np.ascontiguousarray(col, np.int32), np.ascontiguousarray(hp, np.float32)
+    S, A = int(S), int(A)
+    if S < 1 or A < 1 or row_ptr.shape != (S * A + 1,) or col.shape != hp.shape or len(col) < int(row_ptr[-1]) or row_ptr[0] < 0:
+        raise ValueError("row_ptr must have S * A + 1 entries that index col and hp, S and A must be >= 1")
+    rowsum, c, t = np.zeros(S * A, np.float32), np.zeros(S * A, np.float32), np.zeros(len(hp), np.float32)
+    L.check(L.load().cmdp_psrl_map_rows(S, A, L.ptr(row_ptr), L.ptr(col), L.ptr(hp), float(prior), L.ptr(rowsum), L.ptr(c), L.ptr(t)))
+    return rowsum.reshape(S, A), c.reshape(S, A), t
+
+
+def _map_problem(p):
+    if len(p) == 5:
+        row_ptr, col, hp, prior, mu = p
+        mu = np.ascontiguousarray(mu, np.float32)
+        if mu.ndim != 2:
+            raise ValueError("mu must be [S, A]")
+        row_ptr = np.ascontiguousarray(row_ptr, np.int64)
+        col, hp = np.ascontiguousarray(col, np.int32), np.ascontiguousarray(hp, np.float32)
+        if row_ptr.shape != (mu.size + 1,) or row_ptr[0] != 0 or col.shape != (int(row_ptr[-1]),) or hp.shape != col.shape:
+            raise ValueError("table form: row_ptr [S * A + 1] from 0, col and hp with row_ptr[-1] entries")
+    elif len(p) in (3, 4):
+        thp, mu, prior = p[:3]
+        mu = np.ascontiguousarray(mu, np.float32)
+        if np.ndim(thp) != 3 or mu.shape != np.shape(thp)[:2]:
+            raise ValueError("dense form: transition_hp [S, A, S], reward_mu [S, A], prior")
+        row_ptr, col, hp = map_layout_from_dense(thp, prior, p[3] if len(p) == 4 else None)
+    else:
+        raise ValueError("a problem is (row_ptr, col, hp, prior, mu) or (transition_hp, reward_mu, prior[, keep])")
+    return row_ptr, col, hp, np.float32(prior), mu
+
+
+def episodic_value_iteration_map_batch(problems, H, return_map=False):
+    """`episodic_value_iteration(H, *get_map_estimate())` for many Bayesian models in one launch of kernel K15, without
+    the dense MAP array.  A problem is the table form (row_ptr, col, hp, prior, mu [S, A]) -- per row the ascending columns
+    `col` where the M_DIR hyper-parameters are `hp`, `prior` everywhere else -- or the dense form (transition_hp
+    [S, A, S], reward_mu [S, A], prior[, keep]), packed by `map_layout_from_dense`.  The problems may differ in S and A.
+    Returns [(Q [H + 1, S, A], V [H + 1, S])]; with `return_map` [(Q, V, t, c)]: the MAP transition estimate at the
+    layout's positions and, per row [S, A], elsewhere."""
+    ps = [_map_problem(p) for p in problems]
+    H = int(H)
+    if H < 1:
+        raise ValueError("H < 1")
+    if not ps:
+        return []
+    S = np.array([p[4].shape[0] for p in ps], np.int32)
+    A = np.array([p[4].shape[1] for p in ps], np.int32)
+    nz = np.array([len(p[1]) for p in ps], np.int64)
+    nz_off = np.concatenate([[0], np.cumsum(nz)])
+    ptr = np.concatenate([p[0][:-1] + nz_off[i] for i, p in enumerate(ps)] + [nz_off[-1:]]).astype(np.int64)
+    col = np.concatenate([p[1] for p in ps]).astype(np.int32)
+    hp = np.concatenate([p[2] for p in ps]).astype(np.float32)
+    prior = np.array([p[3] for p in ps], np.float32)
+    mu = np.concatenate([p[4].ravel() for p in ps]).astype(np.float32)
+    Q = np.zeros((H + 1) * int((S.astype(np.int64) * A).sum()), np.float32)
+    V = np.zeros((H + 1) * int(S.sum()), np.float32)
+    t, c = np.zeros(len(hp), np.float32), np.zeros(len(mu), np.float32)
+    L.check(L.load().cmdp_vi_episodic_map(len(ps), L.ptr(S), L.ptr(A), H, L.ptr(ptr), L.ptr(col), L.ptr(hp), L.ptr(prior),
+                                          L.ptr(mu), L.ptr(Q), L.ptr(V), L.ptr(t) if return_map else None,
+                                          L.ptr(c) if return_map else None))
+    out, q0, v0, r0 = [], 0, 0, 0
+    for i, (s, a) in enumerate(zip(S.tolist(), A.tolist())):
+        nq, nv = (H + 1) * s * a, (H + 1) * s
+        one = (Q[q0:q0 + nq].reshape(H + 1, s, a), V[v0:v0 + nv].reshape(H + 1, s))
+        if return_map:
+            one += (t[nz_off[i]:nz_off[i + 1]], c[r0:r0 + s * a].reshape(s, a))
+        out.append(one)
+        q0, v0, r0 = q0 + nq, v0 + nv, r0 + s * a
+    return out
+
+
 def episodic_policy_evaluation(H, T, R, policy):
     """reference finite_horizon.py:29-42; policy [H,S,A]."""
     S, A, _ = T.shape

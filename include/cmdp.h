@@ -272,7 +272,9 @@ enum { CMDP_STAT_DP_KERNEL_MS = 1, CMDP_STAT_DP_KERNEL = 2,
                                                 instead.  When the workspace limit splits a call into several launches of
                                                 different widths, the last launch is reported.  Set on the host; read-only.        */,
        CMDP_STAT_UCRL2_POLICY_KERNEL_MS = 23 /* UCRL2 agents of this handle: HIP-event time of the last K14 launch (the solve of
-                                                cmdp_ucrl2_policy / cmdp_ucrl2_average_reward)                                     */ };
+                                                cmdp_ucrl2_policy / cmdp_ucrl2_average_reward)                                     */,
+       CMDP_STAT_PSRL_POLICY_KERNEL_MS = 24  /* PSRL agents of this handle: HIP-event time of the last K15 launch (the solve of
+                                                cmdp_psrl_policy / cmdp_psrl_evaluate)                                             */ };
 /* The UCRL2 and PSRL statistics belong to the environment handle: agents created on the same handle share them. */
 int cmdp_stat(cmdp_t* h, int which, double* out);
 /* Latency floor of the LDS-resident rollout kernels, measured on the current device: one wavefront per CU follows
@@ -792,6 +794,32 @@ int cmdp_psrl_reference_sample(uint32_t* t_key, int32_t* t_pos, int32_t* t_has_g
    order.  The kernel the PSRL agent solves with.  CMDP_ERR_UNSUPPORTED beyond 4096 states. */
 int cmdp_vi_episodic_dense(int count, const int32_t* n_states, const int32_t* n_actions, int H, const float* T, const float* R,
                            float* Q, float* V);
+/* Host only (no HIP call): the MAP estimate of one instance's M_DIR model in table form.  Row r of the dense hyper-parameter
+   array holds hp[e] at the ascending columns col[e], e in row_ptr[r] .. row_ptr[r + 1] (row_ptr [S * A + 1] indexes col / hp /
+   t directly), and `prior` > 0 at every other state.  rowsum [S * A] = numpy's pairwise float32 sum of the dense row,
+   c [S * A] = prior / rowsum, t[e] = hp[e] / rowsum (float32): hyper_params / hyper_params.sum(-1, keepdims=True) bit for
+   bit.  Each output may be NULL.  The definition of K15's prologue. */
+int cmdp_psrl_map_rows(int n_states, int n_actions, const int64_t* row_ptr, const int32_t* col, const float* hp, float prior,
+                       float* rowsum, float* c, float* t);
+/* episodic_value_iteration(H, T_map, mu) on `count` MAP models in table form (K15, csrc/cmdp_map_vi.h), one launch, no dense
+   array: row_ptr [sum S * A + 1] over the rows of all problems (row_ptr[0] = 0), col instance-relative and ascending within a
+   row, hp per position, prior [count], mu [sum S * A].  With T_map as cmdp_psrl_map_rows defines it,
+     Q[h, s, a] = float(double(mu[s, a]) + double(c) * (SV - sum_e double(V[h + 1, col_e])) + sum_e double(t_e) * double(V[h + 1, col_e]))
+   where SV is the float64 sum of V[h + 1, :] in a fixed order and V[h, s] = max_a Q[h, s, a].  Q receives [H + 1][S][A] and V
+   [H + 1][S] per instance, layer H zero; t_layout_out (per position) and c_out (per row) receive T_map and may be NULL.
+   CMDP_ERR_UNSUPPORTED beyond 4096 states. */
+int cmdp_vi_episodic_map(int count, const int32_t* n_states, const int32_t* n_actions, int H, const int64_t* row_ptr,
+                         const int32_t* col, const float* hp, const float* prior, const float* mu, float* Q, float* V,
+                         float* t_layout_out, float* c_out);
+/* PSRLEpisodic.current_optimal_stochastic_policy (posterior_sampling.py:78-82) for the instances selected by mask [B] (NULL:
+   all), on the device from the agent's posterior tables: K15 on the MAP estimate, then argmax_3d (RandomState(42) tie-break)
+   over all H + 1 layers.  pi and Q receive [H + 1][S][A] per instance (pi one-hot), zeros for unselected instances; each may
+   be NULL.  The actor's Q, the last sample, the posterior tables, the episode counters, both RNG streams and the environment
+   are left untouched. */
+int cmdp_psrl_policy(cmdp_psrl_t* a, const uint8_t* mask, float* pi, float* Q);
+/* V[0, :] of that policy on the TRUE MDP (the handle's episodic policy evaluation), V0 [state_off[B]], zeros for unselected
+   instances: what MDPLoop's episodic regret needs.  CMDP_ERR_UNSUPPORTED when the environment handle has no DP half. */
+int cmdp_psrl_evaluate(cmdp_psrl_t* a, const uint8_t* mask, float* V0);
 
 #ifdef __cplusplus
 }
