@@ -34,12 +34,14 @@ STAT_PSRL_ROUNDS, STAT_PSRL_SOLVES, STAT_PSRL_SAMPLE_KERNEL_MS, STAT_PSRL_VI_KER
 STAT_DIAMETER_KERNEL = 22  # family * 1000 + n * 10 + flag, see include/cmdp.h
 STAT_UCRL2_POLICY_KERNEL_MS = 23
 STAT_PSRL_POLICY_KERNEL_MS = 24
+STAT_UCRL2_POLICY_SOLVED, STAT_UCRL2_POLICY_REUSED = 25, 26  # instances K14 solved / kept their stored policy
 PSRL_SAMPLER_REFERENCE, PSRL_SAMPLER_PHILOX = 0, 1
 PSRL_KEY_HI = 0x5053524C
 BOUND_CHERNOFF, BOUND_BERNSTEIN = 0, 1
 ACTOR_GREEDY, ACTOR_EPSILON_GREEDY, ACTOR_BOLTZMANN = 0, 1, 2
 UCRL2_OPT_MAX_SWEEPS = 1
 UCRL2_OPT_POLICY_SIZE_THRESHOLD = 2
+UCRL2_OPT_POLICY_REUSE = 3
 NOISE_NONE, NOISE_GAUSSIAN, NOISE_GAUSSIAN_CORRELATED, NOISE_STUDENT_T, NOISE_STUDENT_T_CORRELATED = 0, 1, 2, 3, 4
 CALIB_LDS_READ, CALIB_LDS_CHAIN, CALIB_LDS_CHAIN_SHARED = 0, 1, 2
 DP_AUTO, DP_WORKGROUP, DP_REGISTER = 0, 1, 2
@@ -85,6 +87,7 @@ EXPORTS = [
     "cmdp_k1e_code_counts", "cmdp_k1s_plan", "cmdp_k1s_plan_desc", "cmdp_det_plan", "cmdp_det_plan_desc", "cmdp_chain_plan_desc", "cmdp_chain_choice",
     "cmdp_k1e_pair_plan", "cmdp_k1e_pair_plan_desc",
     "cmdp_psrl_map_rows", "cmdp_vi_episodic_map", "cmdp_psrl_policy", "cmdp_psrl_evaluate",
+    "cmdp_ucrl2_run_logged", "cmdp_psrl_run_logged",
 ]
 
 
@@ -216,6 +219,8 @@ def load():
         L.cmdp_qlearning_run.argtypes = [vp, i64, vp, vp, vp]
         L.cmdp_qlearning_evaluate.argtypes = [vp, vp]
         L.cmdp_qlearning_run_logged.argtypes = [vp, C.POINTER(CmdpLoopDesc), i64, vp, vp, vp, vp, vp]
+        L.cmdp_ucrl2_run_logged.argtypes = [vp, C.POINTER(CmdpLoopDesc), i64, vp, vp, vp, vp, vp]
+        L.cmdp_psrl_run_logged.argtypes = [vp, C.POINTER(CmdpLoopDesc), i64, vp, vp, vp, vp, vp]
         L.cmdp_tracker_replay.argtypes = [C.POINTER(CmdpLoopDesc), i32, i32, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         L.cmdp_qlearning_continuous_create.argtypes = [C.POINTER(vp), vp, vp, i64, f64, f64, f64, f64]
         L.cmdp_qlearning_policy.argtypes = [vp, vp]

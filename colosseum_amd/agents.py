@@ -164,6 +164,21 @@ class _ParkAndSolveAgent(_DeviceAgent):
                                                           L.ptr(acts), L.ptr(obs), L.ptr(rew), L.ptr(rsum), L.ptr(taken)))
         return dict(cumulative_reward=rsum, steps_taken=taken, actions=acts, observations=obs, rewards=rew)
 
+    def run_logged(self, desc, n_logs: int):
+        """`MDPLoop.run` for the whole batch in one library call (cmdp_ucrl2_run_logged / cmdp_psrl_run_logged): the rows
+        strictly in order, interaction, evaluation and indicators without returning to Python.  `desc` from
+        `vector_tracker.loop_desc`; the agent must not have taken a step yet.  Returns what
+        `BatchedQLearningEpisodic.run_logged` returns."""
+        B = self.env.B
+        steps = np.zeros(n_logs, np.int64)
+        values = np.zeros((n_logs, len(L.LOG_COLUMNS), B), np.float64)
+        kinds = np.zeros((n_logs, len(L.LOG_COLUMNS), B), np.uint8)
+        last = np.zeros(B, np.int64)
+        training = np.zeros(B, np.uint8)
+        L.check(getattr(self._lib, self._PREFIX + "_run_logged")(self._h, C.byref(desc), int(n_logs), L.ptr(steps), L.ptr(values),
+                                                                 L.ptr(kinds), L.ptr(last), L.ptr(training)))
+        return steps, values, kinds, last, training.astype(bool)
+
     def _dense(self, values, dtype, fill=None, uniform=None):
         """Layout values as dense [S, A, S] arrays per instance; elsewhere `fill[b]` (default 0), and rows with
         `uniform` > 0 hold that value at every state."""
@@ -203,7 +218,8 @@ class BatchedUCRL2Continuous(_ParkAndSolveAgent):
     _DESTROY, _PREFIX = "cmdp_ucrl2_destroy", "cmdp_ucrl2"
     _STATS = (("rounds", L.STAT_UCRL2_ROUNDS), ("solves", L.STAT_UCRL2_SOLVES), ("unconverged", L.STAT_UCRL2_UNCONVERGED),
               ("round_ms", L.STAT_UCRL2_ROUND_MS), ("wait_ms", L.STAT_UCRL2_WAIT_MS),
-              ("policy_kernel_ms", L.STAT_UCRL2_POLICY_KERNEL_MS))
+              ("policy_kernel_ms", L.STAT_UCRL2_POLICY_KERNEL_MS), ("policy_solved", L.STAT_UCRL2_POLICY_SOLVED),
+              ("policy_reused", L.STAT_UCRL2_POLICY_REUSED))
     _BOUNDS = {"_chernoff": L.BOUND_CHERNOFF, "bernstein": L.BOUND_BERNSTEIN}
 
     def __init__(self, env: BatchedMDP, seeds: Sequence[int], optimization_horizon: int, alpha_r=1.0, alpha_p=1.0,
@@ -296,13 +312,19 @@ class BatchedUCRL2Continuous(_ParkAndSolveAgent):
 
     def stats(self) -> dict:
         """Rounds of parked instances, instances solved in them, solves that did not converge, host time of the rounds
-        (park list, logarithms, enqueue) and time spent waiting for the device in them.  Kept per ENVIRONMENT handle:
-        agents created on the same environment share these counters."""
+        (park list, logarithms, enqueue) and time spent waiting for the device in them; `policy_solved` / `policy_reused`:
+        instances the policy solve (K14) has run for, and instances that kept their stored policy because their estimated
+        model had not changed.  Kept per ENVIRONMENT handle: agents created on the same environment share these counters."""
         return self._stats()
 
     def _set_policy_size_threshold(self, n: int):
         """Test hook: the size threshold of the scheme rule in the policy solve (the reference's default 300 * 3 * 300)."""
         L.check(self._lib.cmdp_ucrl2_set_option(self._h, L.UCRL2_OPT_POLICY_SIZE_THRESHOLD, int(n)))
+
+    def _set_policy_reuse(self, on: bool):
+        """Whether an instance whose `episode` has not moved keeps the policy of its last solve (default) or every
+        `policy()` / `average_reward()` / logged row solves again.  The results are identical either way."""
+        L.check(self._lib.cmdp_ucrl2_set_option(self._h, L.UCRL2_OPT_POLICY_REUSE, int(bool(on))))
 
     def _set_max_sweeps(self, n: int):
         """Test hook: the sweeps a solve may take (the not-converged path keeps the previous Q)."""

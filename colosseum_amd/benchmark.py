@@ -24,7 +24,7 @@ from typing import Any, Dict, List, Optional, Sequence
 import numpy as np
 
 from . import _lib as L
-from .agents import BatchedQLearningContinuous, BatchedQLearningEpisodic
+from .agents import BatchedPSRLEpisodic, BatchedQLearningContinuous, BatchedQLearningEpisodic, BatchedUCRL2Continuous
 from .batched import BatchedMDP
 from .experiment.batched_loop import BatchedContinuousLoop, BatchedEpisodicLoop
 from .mdp import make_model
@@ -37,7 +37,21 @@ DEFAULT_AGENT_CONFIGS = {
     "QLearningEpisodic": dict(p=0.05, UCB_type="bernstein", c_1=0.9415278732894797, c_2=0.013873778519317169,
                               min_at=0.07263563483119442),
     "QLearningContinuous": dict(h_weight=0.942, span_approx_weight=0.014, min_at=0.073),
+    "PSRLEpisodic": dict(reward_prior_model="N_NIG", transitions_prior_model="M_DIR",
+                         rewards_prior_prms=[0.41854463543357456, 1, 1, 1], transitions_prior_prms=[0.32345772625210756]),
+    "UCRL2Continuous": dict(bound_type_p="bernstein", alpha_p=0.9883750006754203, alpha_r=0.10294276593728004),
 }
+
+# the agents built on the device: class name -> (episodic, agent class, loop class)
+DEVICE_AGENTS = {
+    "QLearningEpisodic": (True, BatchedQLearningEpisodic, BatchedEpisodicLoop),
+    "PSRLEpisodic": (True, BatchedPSRLEpisodic, BatchedEpisodicLoop),
+    "QLearningContinuous": (False, BatchedQLearningContinuous, BatchedContinuousLoop),
+    "UCRL2Continuous": (False, BatchedUCRL2Continuous, BatchedContinuousLoop),
+}
+# ... of which these park their instances for a solve: their walk kernels do not park for reward blocks as well, so they
+# refuse CMDP_FLAG_REWARD_CACHE handles (the reference's own Beta-reward caches)
+_NO_REWARD_CACHE = ("PSRLEpisodic", "UCRL2Continuous")
 
 
 def parse_gin(text: str) -> Dict[str, Dict[str, Dict[str, Any]]]:
@@ -78,10 +92,17 @@ class Instance:
 
 
 def enumerate_instances(mdp_configs: Dict[str, Dict[str, Dict[str, Any]]], n_seeds: int,
-                        supported_only: bool = True) -> List[Instance]:
-    """Seed-major enumeration of folder_structuring.py:76-104 with one tabular Q-learning agent per setting."""
+                        supported_only: bool = True, agents: Optional[Sequence[str]] = None) -> List[Instance]:
+    """Seed-major enumeration of folder_structuring.py:76-104: seed, then MDP class and scope, then agent.  `agents`: class
+    names of `DEVICE_AGENTS`, each with its one scope `prms_0`; an agent of the other setting than the MDP class is skipped
+    for it.  None: one tabular Q-learning agent per setting."""
     from .mdp.registry import FAMILIES
 
+    if agents is None:
+        agents = ("QLearningEpisodic", "QLearningContinuous")
+    for a in agents:
+        if a not in DEVICE_AGENTS:
+            raise KeyError(f"agent {a!r}: one of {sorted(DEVICE_AGENTS)}")
     out = []
     for seed in range(n_seeds):
         for cls, scopes in mdp_configs.items():
@@ -90,9 +111,10 @@ def enumerate_instances(mdp_configs: Dict[str, Dict[str, Dict[str, Any]]], n_see
                 if supported_only:
                     continue
                 raise KeyError(cls)
-            agent = "QLearningEpisodic" if cls.endswith("Episodic") else "QLearningContinuous"
+            matching = [a for a in agents if DEVICE_AGENTS[a][0] == cls.endswith("Episodic")]
             for scope in sorted(scopes, key=lambda s: int(s.split("_")[1])):
-                out.append(Instance(seed, cls, scope, dict(scopes[scope]), agent))
+                for agent in matching:
+                    out.append(Instance(seed, cls, scope, dict(scopes[scope]), agent))
     return out
 
 
@@ -141,8 +163,20 @@ def _run_group(models, seeds, agent_cls, agent_kwargs, n_steps, log_every, rng_m
     return rows
 
 
+def check_group(agent_cls: str, stochastic: bool, beta_rewards: str):
+    """What a device batch refuses before any handle is created.  PSRL and UCRL2 cannot run on the reference's own
+    Beta-reward caches; nothing falls back silently to another reward stream."""
+    if agent_cls not in DEVICE_AGENTS:
+        raise KeyError(f"agent {agent_cls!r}: one of {sorted(DEVICE_AGENTS)}")
+    if stochastic and beta_rewards == "reference" and agent_cls in _NO_REWARD_CACHE:
+        raise ValueError(f"{agent_cls} on MDPs with stochastic rewards: beta_rewards='reference' needs CMDP_FLAG_REWARD_CACHE "
+                         f"handles, which this agent's kernels do not support -- run with --beta-rewards philox "
+                         f"(beta_rewards='philox': Beta rewards sampled on the device, distribution-exact)")
+
+
 def _setup_group(models, seeds, agent_cls, agent_kwargs, n_steps, rng_mode, beta_rewards):
     stochastic = any(not m.deterministic_rewards for m in models)
+    check_group(agent_cls, stochastic, beta_rewards)
     # Beta rewards, "reference": the reference's own per-triple caches of 5000 samples from the MDP's numpy stream
     # (CMDP_FLAG_REWARD_CACHE: blocks in HBM, drawn by the library on the host whenever an instance needs one), next to
     # the reference's transition streams -- rows equal the reference's for that seed.  "philox": sampled on the device
@@ -152,12 +186,12 @@ def _setup_group(models, seeds, agent_cls, agent_kwargs, n_steps, rng_mode, beta
     env = BatchedMDP(models, rng_mode=L.RNG_PHILOX if stochastic and not exact else rng_mode,
                      philox_keys=np.asarray(seeds, np.uint64) * np.uint64(0x9E3779B1) + np.uint64(17),
                      flags=L.FLAG_REWARD_CACHE if exact else (L.FLAG_BETA_GAMMAS if beta_rewards == "philox-gammas" else 0))
-    if agent_cls == "QLearningEpisodic":
-        agent = BatchedQLearningEpisodic(env, seeds, optimization_horizon=n_steps, **agent_kwargs)
-        loop = BatchedEpisodicLoop(env, agent)
-    else:
-        agent = BatchedQLearningContinuous(env, seeds, optimization_horizon=n_steps, **agent_kwargs)
-        loop = BatchedContinuousLoop(env, agent)
+    _, make_agent, make_loop = DEVICE_AGENTS[agent_cls]
+    kw = dict(agent_kwargs)
+    if agent_cls == "PSRLEpisodic":  # the posterior is sampled where the rewards are
+        kw.setdefault("sampler", "philox" if stochastic else "reference")
+    agent = make_agent(env, seeds, optimization_horizon=n_steps, **kw)
+    loop = make_loop(env, agent)
     return env, agent, loop, exact, t0, time.time()
 
 
@@ -192,8 +226,11 @@ def run_instances(instances: Sequence[Instance], n_steps: int, log_every: int, r
         # deterministic- and Beta-reward instances never share a device batch: in "philox" mode the two run different
         # transition streams (MT_COMPAT / Philox), and what an instance produces must not depend on which other
         # instances the benchmark holds
-        groups.setdefault((instances[i].mdp_cls, m.H, m.n_actions, tuple(m.rewards_range), scheme, m.deterministic_rewards),
-                          []).append(i)
+        # ... nor do the instances of two agents
+        groups.setdefault((instances[i].mdp_cls, m.H, m.n_actions, tuple(m.rewards_range), scheme, m.deterministic_rewards,
+                           instances[i].agent_cls, instances[i].agent_scope), []).append(i)
+    for idx in groups.values():  # refused for the whole run before the first handle is created
+        check_group(instances[idx[0]].agent_cls, not models[idx[0]].deterministic_rewards, beta_rewards)
     results: Dict[int, list] = {}
 
     def work(idx):

@@ -294,6 +294,7 @@ struct cmdp {
   int64_t uc_rounds = 0, uc_solves = 0;
   double uc_round_ms = 0.0, uc_wait_ms = 0.0;
   double uc_policy_ms = 0.0;   // CMDP_STAT_UCRL2_POLICY_KERNEL_MS: the last K14 launch of an agent of this handle
+  int64_t uc_policy_solved = 0, uc_policy_reused = 0;   // CMDP_STAT_UCRL2_POLICY_SOLVED / _REUSED: instances, all requests together
   DevBuf<int32_t> d_uc_unconverged;
   // PSRL agents on this handle (cmdp_psrl_*): CMDP_STAT_PSRL_*
   int64_t ps_rounds = 0, ps_solves = 0;
@@ -1760,6 +1761,10 @@ int cmdp_stat(cmdp_t* h, int which, double* out) {
   }
   if (which == CMDP_STAT_UCRL2_POLICY_KERNEL_MS || which == CMDP_STAT_PSRL_POLICY_KERNEL_MS) {
     *out = which == CMDP_STAT_UCRL2_POLICY_KERNEL_MS ? h->uc_policy_ms : h->ps_policy_ms;
+    return CMDP_OK;
+  }
+  if (which == CMDP_STAT_UCRL2_POLICY_SOLVED || which == CMDP_STAT_UCRL2_POLICY_REUSED) {
+    *out = (double)(which == CMDP_STAT_UCRL2_POLICY_SOLVED ? h->uc_policy_solved : h->uc_policy_reused);
     return CMDP_OK;
   }
   if (which == CMDP_STAT_UCRL2_UNCONVERGED) {
@@ -4338,6 +4343,12 @@ struct cmdp_ucrl2 : ParkAgent {
   DevBuf<float> d_pQ, d_pV, d_ppi;
   DevBuf<uint8_t> d_p_mask;
   hipEvent_t p_ev[2] = {nullptr, nullptr};
+  // The estimated model changes in model_update only, which ends an artificial episode: while `episode` stands, the solve
+  // and its greedy policy are what they were.  p_stamp[b]: `episode` of instance b when d_pQ / d_ppi were last computed
+  // for it by a solve that converged (-1: never, or invalidated by an option).  CMDP_UCRL2_OPT_POLICY_REUSE switches it.
+  bool policy_reuse = true;
+  std::vector<int64_t> p_stamp, p_episode;   // [B]
+  std::vector<uint8_t> p_todo;               // [B] the instances of a request that K14 has to solve
   ~cmdp_ucrl2() {
     for (hipEvent_t e : p_ev)
       if (e) (void)hipEventDestroy(e);
@@ -4505,10 +4516,17 @@ int cmdp_ucrl2_set_option(cmdp_ucrl2_t* a, int option, int64_t value) {
   if (option == CMDP_UCRL2_OPT_MAX_SWEEPS) {
     if (value < 1) return fail(CMDP_ERR_INVALID, "max_sweeps %lld < 1", (long long)value);
     a->max_sweeps = value;
+    std::fill(a->p_stamp.begin(), a->p_stamp.end(), -1);   // an option may change what a solve returns: none is reused
     return CMDP_OK;
   }
   if (option == CMDP_UCRL2_OPT_POLICY_SIZE_THRESHOLD) {
     a->policy_size_threshold = value;
+    std::fill(a->p_stamp.begin(), a->p_stamp.end(), -1);
+    return CMDP_OK;
+  }
+  if (option == CMDP_UCRL2_OPT_POLICY_REUSE) {
+    if (value != 0 && value != 1) return fail(CMDP_ERR_INVALID, "policy_reuse %lld: 0 or 1", (long long)value);
+    a->policy_reuse = value != 0;
     return CMDP_OK;
   }
   return fail(CMDP_ERR_INVALID, "unknown option %d", option);
@@ -4558,12 +4576,40 @@ static int ucrl2_policy_solve(cmdp_ucrl2_t* a, const uint8_t* mask, std::vector<
     AGENT_ZERO(d_p_scheme, B); AGENT_ZERO(d_p_status, B);
     HIP_TRY(a->d_p_mask.alloc(B));
     for (hipEvent_t& e : a->p_ev) HIP_TRY(hipEventCreate(&e));
+    a->p_stamp.assign((size_t)B, -1);
+    a->p_episode.assign((size_t)B, 0);
+    a->p_todo.assign((size_t)B, 0);
     HIP_TRY(a->d_pS.upload(S.data(), B, st));
     HIP_TRY(hipStreamSynchronize(st));  // the vectors are locals
   }
+  // the instances of the request whose model has changed since their stored solve: the others keep d_pQ / d_ppi
+  HIP_TRY(hipMemcpyAsync(a->p_episode.data(), a->d_episode.p, sizeof(int64_t) * B, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  int n_asked = 0, n_todo = 0;
+  for (int b = 0; b < B; ++b) {
+    const bool asked = !mask || mask[b];
+    const bool todo = asked && !(a->policy_reuse && a->p_stamp[(size_t)b] == a->p_episode[(size_t)b]);
+    a->p_todo[(size_t)b] = todo ? 1 : 0;
+    n_asked += asked;
+    n_todo += todo;
+  }
+  h->uc_policy_solved += n_todo;
+  h->uc_policy_reused += n_asked - n_todo;
+  if (n_todo == 0) {   // nothing to launch; sweeps and scheme are those of the stored solves
+    if (sweeps_out) {
+      sweeps_out->resize((size_t)B);
+      HIP_TRY(hipMemcpyAsync(sweeps_out->data(), a->d_p_sweeps.p, sizeof(int64_t) * B, hipMemcpyDeviceToHost, st));
+    }
+    if (scheme_out) {
+      scheme_out->resize((size_t)B);
+      HIP_TRY(hipMemcpyAsync(scheme_out->data(), a->d_p_scheme.p, sizeof(int32_t) * B, hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    return CMDP_OK;
+  }
   const uint8_t* dmask = nullptr;
-  if (mask) {
-    HIP_TRY(a->d_p_mask.upload(mask, B, st));
+  if (n_todo < B) {
+    HIP_TRY(a->d_p_mask.upload(a->p_todo.data(), B, st));
     dmask = a->d_p_mask.p;
   }
   ModelViArgs g{a->d_pS.p, a->d_pA.p, h->d_state_off.p, a->d_p_roff.p, a->d_row_ptr.p, a->d_col.p, a->d_val.p, a->d_uni.p,
@@ -4589,10 +4635,16 @@ static int ucrl2_policy_solve(cmdp_ucrl2_t* a, const uint8_t* mask, std::vector<
   float ms = 0.0f;
   HIP_TRY(hipEventElapsedTime(&ms, a->p_ev[0], a->p_ev[1]));
   h->uc_policy_ms = (double)ms;
-  for (int b = 0; b < B; ++b)
-    if ((!mask || mask[b]) && status[b] != 0)
-      return fail(CMDP_ERR_MAX_ITER, "discounted value iteration on the estimated model of instance %d did not converge in "
-                  "%d sweeps", b, 1000000);
+  int unconverged = -1;
+  for (int b = 0; b < B; ++b) {
+    if (!a->p_todo[(size_t)b]) continue;
+    // a solve that hit max_sweeps is never reused: the next request solves (and fails) again
+    a->p_stamp[(size_t)b] = status[b] == 0 ? a->p_episode[(size_t)b] : -1;
+    if (status[b] != 0 && unconverged < 0) unconverged = b;
+  }
+  if (unconverged >= 0)
+    return fail(CMDP_ERR_MAX_ITER, "discounted value iteration on the estimated model of instance %d did not converge in "
+                "%d sweeps", unconverged, 1000000);
   return CMDP_OK;
 }
 
@@ -5225,18 +5277,27 @@ int cmdp_psrl_policy(cmdp_psrl_t* a, const uint8_t* mask, float* pi, float* Q) {
   return psrl_map_time(a);
 }
 
-int cmdp_psrl_evaluate(cmdp_psrl_t* a, const uint8_t* mask, float* V0) {
-  if (!a || !a->env || !V0) return fail(CMDP_ERR_INVALID, "null argument, or the agent's environment handle has been destroyed");
-  cmdp_t* h = a->env;
-  if (int rc = bind(h)) return rc;
+}  // extern "C"
+
+// What the evaluation of the MAP policy on the true MDP refuses (after bind)
+static int psrl_evaluate_check(cmdp_t* h) {
   if (!h->has_dp)
     return fail(CMDP_ERR_UNSUPPORTED, "cmdp_psrl_evaluate evaluates the policy on the true MDP: the environment handle was created "
                 "without the DP half (CSR transition matrices)");
+  if (2 * sizeof(float) * (size_t)h->max_S > (size_t)kLdsBudget)
+    return fail(CMDP_ERR_UNSUPPORTED, "instance with %d states does not fit LDS", h->max_S);
+  return CMDP_OK;
+}
+
+// K15 -> greedy policy of the first H layers -> episodic policy evaluation on the true MDP -> V[0, :] packed into `v0`
+// (device-accessible; null: a->d_mv0), all enqueued on the handle's stream after psrl_evaluate_check.  `snap` (nullable,
+// device-accessible [3][B]) receives last_start | prev_start | hstep from the same gather.  The instances solved are left
+// in `sel`; the caller waits for the stream and then calls psrl_map_time.
+static int psrl_enqueue_evaluate(cmdp_psrl_t* a, const uint8_t* mask, std::vector<int32_t>& sel, float* v0, int32_t* snap) {
+  cmdp_t* h = a->env;
   hipStream_t st = h->stream;
   const int H = h->H;
   const size_t lds = 2 * sizeof(float) * (size_t)h->max_S;
-  if (lds > (size_t)kLdsBudget) return fail(CMDP_ERR_UNSUPPORTED, "instance with %d states does not fit LDS", h->max_S);
-  std::vector<int32_t> sel;
   if (int rc = psrl_map_solve(a, mask, sel)) return rc;
   // the first H layers of argmax_3d's walk: the same draws of its tie-break stream, laid out as the evaluation reads them
   hipLaunchKernelGGL(k_greedy_policy_episodic<float>, dim3(h->B), dim3(64), 0, st, h->B, h->A, H, H + 1, h->d_state_off.p,
@@ -5250,15 +5311,161 @@ int cmdp_psrl_evaluate(cmdp_psrl_t* a, const uint8_t* mask, float* V0) {
   if (int rc = set_lds(k_episodic<DP_PE>, lds)) return rc;
   hipLaunchKernelGGL((k_episodic<DP_PE>), dim3(h->B), dim3(kDpBlock), lds, st, t, H, h->d_Q.p, h->d_V.p);
   HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(k_gather_v0, dim3(h->B), dim3(256), 0, st, h->B, H, h->d_state_off.p, h->d_V.p, a->d_mv0.p, h->d_last_start.p,
-                     h->d_prev_start.p, h->d_h.p, (int32_t*)nullptr);
+  hipLaunchKernelGGL(k_gather_v0, dim3(h->B), dim3(256), 0, st, h->B, H, h->d_state_off.p, h->d_V.p, v0 ? v0 : a->d_mv0.p,
+                     h->d_last_start.p, h->d_prev_start.p, h->d_h.p, snap);
   HIP_TRY(hipGetLastError());
+  return CMDP_OK;
+}
+
+extern "C" {
+
+int cmdp_psrl_evaluate(cmdp_psrl_t* a, const uint8_t* mask, float* V0) {
+  if (!a || !a->env || !V0) return fail(CMDP_ERR_INVALID, "null argument, or the agent's environment handle has been destroyed");
+  cmdp_t* h = a->env;
+  if (int rc = bind(h)) return rc;
+  if (int rc = psrl_evaluate_check(h)) return rc;
+  hipStream_t st = h->stream;
+  std::vector<int32_t> sel;
+  if (int rc = psrl_enqueue_evaluate(a, mask, sel, nullptr, nullptr)) return rc;
   if (int rc = psrl_map_fetch(a, sel, V0, a->d_mv0.p, (size_t)h->n_states, [&](int b) {
         return std::make_pair((int64_t)h->state_off[b], (int64_t)(h->state_off[b + 1] - h->state_off[b]));
       }))
     return rc;
   HIP_TRY(hipStreamSynchronize(st));
   return psrl_map_time(a);
+}
+
+}  // extern "C"
+
+// ---- the logged loop of the agents that park (UCRL2, PSRL): one in-order driver ------------------------------------------
+// MDPLoop.run for the batch, as cmdp_qlearning_run_logged, on the rows, the tracker and log_row of cmdp_logged_loop.h.
+// park_run synchronises in every round, so no interval can start before its row is known: the rows are processed strictly in
+// order (`ahead` is false throughout), on the handle's stream alone.  The agent supplies three hooks:
+//   pre()                     the agent's own refusals and allocations for the whole of desc->n_steps; steps nothing
+//   run_steps(n, mask, cum)   n steps under the training mask; the reward sums afterwards into `cum` (page-locked); waits
+//   evaluate(row buffers)     the row's evaluation into page-locked memory; waits
+namespace {
+
+struct ParkRowBuffers {
+  // `cum` twice: row i reads slot i & 1; the single step a row takes inside the loop leaves its sums in the other slot, which
+  // is what the next row logs when no step lies between the two
+  PinnedBuf<double> cum[2], avg;
+  PinnedBuf<float> v0;
+  PinnedBuf<int32_t> snap, akind;
+  PinnedBuf<uint8_t> mask, need;
+  int alloc(int B, size_t n_states) {
+    if (int rc = cum[0].alloc(B)) return rc;
+    if (int rc = cum[1].alloc(B)) return rc;
+    if (int rc = avg.alloc(B)) return rc;
+    if (int rc = v0.alloc(n_states)) return rc;
+    if (int rc = snap.alloc((size_t)3 * B)) return rc;
+    if (int rc = akind.alloc(B)) return rc;
+    if (int rc = mask.alloc(B)) return rc;
+    if (int rc = need.alloc(B)) return rc;
+    for (int b = 0; b < B; ++b) cum[0].p[b] = cum[1].p[b] = 0.0;
+    return CMDP_OK;
+  }
+};
+
+template <typename Pre, typename RunSteps, typename Evaluate>
+int park_run_logged(ParkAgent* a, bool episodic, int64_t step_limit, const char* limit_text, const cmdp_loop_desc* d, int64_t n_logs,
+                    int64_t* steps, double* values, uint8_t* kinds, int64_t* last_training_step, uint8_t* is_training, Pre&& pre,
+                    RunSteps&& run_steps, Evaluate&& evaluate) {
+  using namespace cmdp_tracker;
+  using clk = std::chrono::steady_clock;
+  if (!a || !d || !steps || !values || !kinds) return fail(CMDP_ERR_INVALID, "null argument");
+  cmdp_t* h = a->env;
+  if (int rc = bind(h)) return rc;
+  const int B = h->B;
+  const int64_t T = d->n_steps;
+  // everything below is refused before anything is reset or stepped: a caller that falls back to another loop must find the
+  // agent untouched
+  std::vector<LoggedRow> plan;
+  if (int rc = logged_plan(d, n_logs, &plan)) return rc;
+  if (int rc = check_logged_baselines(d, B, episodic)) return rc;
+  if (!episodic && !h->has_dp) return fail(CMDP_ERR_INVALID, "the handle was created without the DP half (CSR transition matrices)");
+  if (!episodic && d->log_every > 0 && chain_lds_bytes(h->max_S, h->max_row_nnz) > (size_t)kLdsBudget)
+    return fail(CMDP_ERR_UNSUPPORTED, "instance with %d states (max %d successors per row) exceeds the LDS budget of K9",
+                h->max_S, h->max_row_nnz);
+  // MDPLoop._cumulative_reward starts at zero with the run; the agent's sums count from its creation
+  for (int b = 0; b < B; ++b)
+    if (a->steps_total[(size_t)b] != 0)
+      return fail(CMDP_ERR_INVALID, "instance %d has already taken %lld steps: a logged run starts from a new agent", b,
+                  (long long)a->steps_total[(size_t)b]);
+  // what every run() call of the loop would check, once for all of the run's steps (the counters start from the reset below)
+  if (T > step_limit) return fail(CMDP_ERR_OVERFLOW, limit_text, 0, 0LL, (long long)T);
+  if (2 + 2 * T > 0x7fffffffLL)
+    return fail(CMDP_ERR_OVERFLOW, "a visit counter (int32 on the device) could wrap in a run of %lld steps", (long long)T);
+  if (int rc = pre()) return rc;
+  ParkRowBuffers buf;
+  if (int rc = buf.alloc(B, (size_t)h->n_states)) return rc;
+  LoggedRun run;
+  run.init(B, episodic, T, d, h->H, h->state_off.data(), buf.mask.p, last_training_step);
+  const auto t_start = clk::now();
+  auto elapsed = [&]() { return std::chrono::duration<double>(clk::now() - t_start).count(); };
+  // MDPLoop.run: visitation counts cleared, environment reset (agent_mdp_interaction.py:219-224)
+  if (int rc = cmdp_reset_visits(h)) return rc;
+  if (int rc = cmdp_reset(h, nullptr, nullptr)) return rc;
+  for (size_t i = 0; i < plan.size(); ++i) {
+    const LoggedRow& r = plan[i];
+    // the reward sums through step t - 1, then -- inside the loop -- step t itself
+    if (r.n_run > 0 || i == 0)
+      if (int rc = run_steps(r.n_run, buf.mask.p, buf.cum[i & 1].p)) return rc;
+    if (r.in_loop)
+      if (int rc = run_steps(1, buf.mask.p, buf.cum[(i + 1) & 1].p)) return rc;
+    RowReadback in{buf.cum[i & 1].p, buf.v0.p, buf.snap.p, buf.need.p, buf.avg.p, buf.akind.p};
+    if (!episodic) continuous_need(run.tr, buf.need.p);
+    if (int rc = evaluate(buf)) return rc;
+    steps[i] = r.t;
+    const double sps = (double)r.t / std::max(elapsed(), 1e-9);
+    bool changed = false;   // the hooks read the mask from buf.mask at every call: nothing to upload here
+    if (int rc = log_row(run, r, in, sps, d->max_time - elapsed(), false, values + i * N_COLUMNS * B, kinds + i * N_COLUMNS * B, &changed))
+      return rc;
+    if (!r.in_loop) break;
+  }
+  if (is_training)
+    for (int b = 0; b < B; ++b) is_training[b] = run.tr.inst[(size_t)b].training ? 1 : 0;
+  return CMDP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int cmdp_ucrl2_run_logged(cmdp_ucrl2_t* a, const cmdp_loop_desc* d, int64_t n_logs, int64_t* steps, double* values, uint8_t* kinds,
+                          int64_t* last_training_step, uint8_t* is_training) {
+  return park_run_logged(
+      a, false, 0x7fffffffLL, "a transition count of the model (int32, as the reference's N) could wrap: instance %d has taken "
+      "%lld steps, %lld asked for", d, n_logs, steps, values, kinds, last_training_step, is_training,
+      [&]() { return ucrl2_ensure_trace(a, d->n_steps); },
+      [&](int64_t n, const uint8_t* mask, double* cum) { return cmdp_ucrl2_run(a, n, 0, mask, nullptr, nullptr, nullptr, cum, nullptr); },
+      [&](ParkRowBuffers& buf) -> int {
+        cmdp_t* h = a->env;
+        bool any = false;
+        for (int b = 0; b < h->B; ++b) any = any || buf.need.p[b];
+        if (!any) return CMDP_OK;
+        // cmdp_ucrl2_average_reward(a, need, .): K14 where the model has changed, then the chain kernels on the stored policies
+        if (int rc = ucrl2_policy_solve(a, buf.need.p, nullptr, nullptr)) return rc;
+        if (int rc = chain_launch(h, a->d_ppi.p, nullptr, h->d_cur.p, buf.need.p, buf.avg.p, buf.akind.p, nullptr, true, false)) return rc;
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        return CMDP_OK;
+      });
+}
+
+int cmdp_psrl_run_logged(cmdp_psrl_t* a, const cmdp_loop_desc* d, int64_t n_logs, int64_t* steps, double* values, uint8_t* kinds,
+                         int64_t* last_training_step, uint8_t* is_training) {
+  std::vector<int32_t> sel;
+  return park_run_logged(
+      a, true, 1LL << 24, "a transition count of the model (float32, as the reference's hyper-parameters) would stop counting at "
+      "2^24: instance %d has taken %lld steps, %lld asked for", d, n_logs, steps, values, kinds, last_training_step, is_training,
+      [&]() { return psrl_evaluate_check(a->env); },
+      [&](int64_t n, const uint8_t* mask, double* cum) { return cmdp_psrl_run(a, n, 0, mask, nullptr, nullptr, nullptr, cum, nullptr); },
+      [&](ParkRowBuffers& buf) -> int {
+        // what cmdp_psrl_evaluate(a, NULL, .) enqueues; the gather writes V[0, :] and the start states straight into the row's memory
+        if (int rc = psrl_enqueue_evaluate(a, nullptr, sel, buf.v0.p, buf.snap.p)) return rc;
+        HIP_TRY(hipStreamSynchronize(a->env->stream));
+        return psrl_map_time(a);
+      });
 }
 
 }  // extern "C"

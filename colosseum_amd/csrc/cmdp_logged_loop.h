@@ -147,4 +147,22 @@ inline int log_row(LoggedRun& run, const LoggedRow& r, const RowReadback& in, do
   return CMDP_OK;
 }
 
+// ---- the in-order driver (cmdp_ucrl2_run_logged, cmdp_psrl_run_logged) -------------------------------------------------------
+// The agents that park their instances for a solve synchronise in every round of a run, so there is nothing to start early:
+// their driver (park_run_logged of cmdp.hip) walks the same rows strictly in order -- interval, step t, evaluation,
+// log_row with `ahead` false, the next interval's mask -- and uses neither the second stream nor LoggedSwitches.
+
+// What that driver refuses of a description before anything is reset or stepped: the baselines a row needs, and the
+// continuous setting's `optimal - worst > 0.0002` (agent_mdp_interaction.py:379-382)
+inline int check_logged_baselines(const cmdp_loop_desc* d, int B, bool episodic) {
+  if (!d->base_val || !d->base_kind) return fail(CMDP_ERR_INVALID, "baseline average rewards missing");
+  if (episodic && (!d->opt0 || !d->worst0 || !d->start_pos || !d->start_prob || d->kmax < 1))
+    return fail(CMDP_ERR_INVALID, "episodic baselines missing");
+  if (!episodic)
+    for (int b = 0; b < B; ++b)
+      if (!(d->base_val[3 * b] - d->base_val[3 * b + 1] > 0.0002))
+        return fail(CMDP_ERR_INVALID, "instance %d: optimal and worst average reward are closer than 0.0002", b);
+  return CMDP_OK;
+}
+
 }  // namespace cmdp_tracker

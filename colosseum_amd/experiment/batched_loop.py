@@ -14,11 +14,11 @@ float32/float64 scalar arithmetic.
 share one clock -- the batch's wall time -- so the limit freezes every instance still training at the first logging
 step after `max_time - 0.5` seconds; `last_training_step[b]` records where (the reference's return value, -1 when the
 limit was not hit)."""
-from typing import Dict, List
+from typing import Dict, List, Union
 
 import numpy as np
 
-from ..agents import BatchedQLearningEpisodic
+from ..agents import BatchedPSRLEpisodic, BatchedQLearningContinuous, BatchedQLearningEpisodic, BatchedUCRL2Continuous
 from .. import _lib as L
 from ..batched import BatchedMDP
 from .vector_tracker import MP, ContinuousVectorTracker, EpisodicVectorTracker
@@ -33,7 +33,9 @@ class _BatchedLoop:
     def _log(self, t: int, cum: np.ndarray, n_since: int, T: int, in_loop: bool):
         raise NotImplementedError
 
-    native = True  # the whole run in one library call (cmdp_qlearning_run_logged); False: the Python-driven loop below
+    # the whole run in one library call (`agent.run_logged`: cmdp_qlearning_run_logged, cmdp_psrl_run_logged,
+    # cmdp_ucrl2_run_logged); False: the Python-driven loop below
+    native = True
 
     def _desc(self, T: int, log_every: int, max_time: float):
         raise NotImplementedError
@@ -43,7 +45,7 @@ class _BatchedLoop:
             try:
                 return self._run_native(T, log_every, max_time)
             except L.CmdpError as e:  # e.g. a continuous instance beyond the LDS budget of the chain kernel K9
-                # cmdp_qlearning_run_logged refuses such a batch BEFORE it resets or steps anything, so the agent the
+                # every run_logged refuses such a batch BEFORE it resets or steps anything, so the agent the
                 # Python-driven loop starts from is the untouched one
                 if e.code != L.ERR_UNSUPPORTED:
                     raise
@@ -92,7 +94,11 @@ class _BatchedLoop:
 
 
 class BatchedEpisodicLoop(_BatchedLoop):
-    def __init__(self, env: BatchedMDP, agent: BatchedQLearningEpisodic,
+    """`MDPLoop.run` for a batch of episodic (environment, agent) pairs.  The agent is a `BatchedQLearningEpisodic` or a
+    `BatchedPSRLEpisodic`: the loop needs `run(n, train=mask)["cumulative_reward"]`, `evaluate()` (V[0, :] of the agent's
+    `current_optimal_stochastic_policy` on the true MDP) and `run_logged`."""
+
+    def __init__(self, env: BatchedMDP, agent: Union[BatchedQLearningEpisodic, BatchedPSRLEpisodic],
                  n_log_intervals_to_check_for_agent_optimality: int = 10):
         assert env.H > 0 and env.models is not None
         self.env, self.agent = env, agent
@@ -127,11 +133,13 @@ class BatchedEpisodicLoop(_BatchedLoop):
 
 
 class BatchedContinuousLoop(_BatchedLoop):
-    """`MDPLoop.run` for a batch of continuous (environment, QLearningContinuous) pairs: interaction on the device,
-    regrets from the average rewards of the agents' greedy policies (kernel K9; host class bookkeeping + the GTH kernel
-    above its LDS budget)."""
+    """`MDPLoop.run` for a batch of continuous (environment, agent) pairs, the agent a `BatchedQLearningContinuous` or a
+    `BatchedUCRL2Continuous`: interaction on the device, regrets from the average rewards of the agents' greedy policies
+    (`average_reward(need)`: kernel K9; above its LDS budget `policy()` for all B instances, host class bookkeeping and the
+    GTH kernel)."""
 
-    def __init__(self, env: BatchedMDP, agent, n_log_intervals_to_check_for_agent_optimality: int = 10):
+    def __init__(self, env: BatchedMDP, agent: Union[BatchedQLearningContinuous, BatchedUCRL2Continuous],
+                 n_log_intervals_to_check_for_agent_optimality: int = 10):
         from ..dynamic_programming import get_policy_from_q_values
         from ..markov_chain import AverageRewardCache, get_average_reward_batch
 

@@ -274,7 +274,11 @@ enum { CMDP_STAT_DP_KERNEL_MS = 1, CMDP_STAT_DP_KERNEL = 2,
        CMDP_STAT_UCRL2_POLICY_KERNEL_MS = 23 /* UCRL2 agents of this handle: HIP-event time of the last K14 launch (the solve of
                                                 cmdp_ucrl2_policy / cmdp_ucrl2_average_reward)                                     */,
        CMDP_STAT_PSRL_POLICY_KERNEL_MS = 24  /* PSRL agents of this handle: HIP-event time of the last K15 launch (the solve of
-                                                cmdp_psrl_policy / cmdp_psrl_evaluate)                                             */ };
+                                                cmdp_psrl_policy / cmdp_psrl_evaluate)                                             */,
+       CMDP_STAT_UCRL2_POLICY_SOLVED = 25,   /* UCRL2 agents of this handle: instances K14 has solved for cmdp_ucrl2_policy /
+                                                cmdp_ucrl2_average_reward / cmdp_ucrl2_run_logged, all requests together       */
+       CMDP_STAT_UCRL2_POLICY_REUSED = 26    /* ... and instances of those requests that kept their stored policy instead
+                                                (CMDP_UCRL2_OPT_POLICY_REUSE)                                                     */ };
 /* The UCRL2 and PSRL statistics belong to the environment handle: agents created on the same handle share them. */
 int cmdp_stat(cmdp_t* h, int which, double* out);
 /* Latency floor of the LDS-resident rollout kernels, measured on the current device: one wavefront per CU follows
@@ -730,7 +734,11 @@ int cmdp_ucrl2_last_solve(cmdp_ucrl2_t* a, float* P_val, float* uniform, float* 
    not-converged path. */
 /* CMDP_UCRL2_OPT_POLICY_SIZE_THRESHOLD: the size threshold of the scheme rule in cmdp_ucrl2_policy's solve (default
    300 * 3 * 300, the reference's); a test hook that lets small instances take the Jacobi scheme. */
-enum { CMDP_UCRL2_OPT_MAX_SWEEPS = 1, CMDP_UCRL2_OPT_POLICY_SIZE_THRESHOLD = 2 };
+/* CMDP_UCRL2_OPT_POLICY_REUSE: 1 (default) an instance whose `episode` has not moved since its last converged policy solve
+   keeps that solve's Q and greedy policy -- the estimated model changes in model_update only, which ends an episode -- and
+   cmdp_ucrl2_policy / cmdp_ucrl2_average_reward / cmdp_ucrl2_run_logged skip K14 for it; 0: every request solves.  The
+   results are bit-identical either way.  Setting either of the other two options discards the stored solves. */
+enum { CMDP_UCRL2_OPT_MAX_SWEEPS = 1, CMDP_UCRL2_OPT_POLICY_SIZE_THRESHOLD = 2, CMDP_UCRL2_OPT_POLICY_REUSE = 3 };
 int cmdp_ucrl2_set_option(cmdp_ucrl2_t* a, int option, int64_t value);
 /* UCRL2Continuous.current_optimal_stochastic_policy (ucrl2.py:80-83) of the instances with mask[b] != 0 (NULL: all), on the
    device: kernel K14 on the agent's own tables (gamma 0.99, epsilon 1e-3, the reference's scheme rule), then argmax_2d with
@@ -740,6 +748,16 @@ int cmdp_ucrl2_set_option(cmdp_ucrl2_t* a, int option, int64_t value);
 int cmdp_ucrl2_policy(cmdp_ucrl2_t* a, const uint8_t* mask, float* pi, float* Q, int64_t* sweeps, int32_t* scheme_used);
 /* ... and get_average_reward of that policy from the environments' current states (as cmdp_qlearning_average_reward). */
 int cmdp_ucrl2_average_reward(cmdp_ucrl2_t* a, const uint8_t* mask, double* avg, int32_t* kind);
+/* MDPLoop.run as one call for the UCRL2 agents: arguments, outputs and rows as cmdp_qlearning_run_logged on a continuous
+   handle.  The interaction is cmdp_ucrl2_run's, a row's evaluation cmdp_ucrl2_average_reward's for the instances that
+   still need one.  The rows are processed strictly in order on the handle's stream (the agent synchronises in every round of
+   parked instances, so no interval starts early).  Refused before anything is reset or stepped: null arguments, an n_logs
+   that is not the schedule's, missing baselines, optimal - worst <= 0.0002, a handle without the DP half (all
+   CMDP_ERR_INVALID); an instance beyond K9's LDS budget when log_every > 0 (CMDP_ERR_UNSUPPORTED); an agent that has
+   already taken steps (CMDP_ERR_INVALID: the reward sums count from creation, MDPLoop's from zero); n_steps beyond what
+   cmdp_ucrl2_run would take in one call (CMDP_ERR_OVERFLOW). */
+int cmdp_ucrl2_run_logged(cmdp_ucrl2_t* a, const cmdp_loop_desc* desc, int64_t n_logs, int64_t* steps, double* values,
+                          uint8_t* kinds, int64_t* last_training_step, uint8_t* is_training);
 
 /* One PSRLEpisodic (colosseum/agent/agents/episodic/posterior_sampling.py with BayesianMDPModel, N_NIG rewards and M_DIR
    transitions) per instance of an EPISODIC environment handle, driven as MDPLoop.run drives it
@@ -820,6 +838,11 @@ int cmdp_psrl_policy(cmdp_psrl_t* a, const uint8_t* mask, float* pi, float* Q);
 /* V[0, :] of that policy on the TRUE MDP (the handle's episodic policy evaluation), V0 [state_off[B]], zeros for unselected
    instances: what MDPLoop's episodic regret needs.  CMDP_ERR_UNSUPPORTED when the environment handle has no DP half. */
 int cmdp_psrl_evaluate(cmdp_psrl_t* a, const uint8_t* mask, float* V0);
+/* MDPLoop.run as one call for the PSRL agents: as cmdp_ucrl2_run_logged, on an episodic handle with the episodic baselines of
+   cmdp_qlearning_run_logged.  The interaction is cmdp_psrl_run's, a row's evaluation cmdp_psrl_evaluate(a, NULL, .)'s.  The
+   same refusals; a handle without the DP half or beyond the evaluation's LDS budget is CMDP_ERR_UNSUPPORTED. */
+int cmdp_psrl_run_logged(cmdp_psrl_t* a, const cmdp_loop_desc* desc, int64_t n_logs, int64_t* steps, double* values,
+                         uint8_t* kinds, int64_t* last_training_step, uint8_t* is_training);
 
 #ifdef __cplusplus
 }

@@ -45,6 +45,11 @@ def main():
                     help="stochastic (Beta) rewards: 'reference' = the reference's per-triple caches of 5000 samples from the MDP's own "
                          "numpy stream (rows equal the reference's); 'philox' = sampled on the device (distribution-exact, no host work); "
                          "'philox-gammas' = the same with the two-gamma sampler of rounds 1-2 for every shape (reproduces their numbers)")
+    ap.add_argument("--agents", nargs="+", metavar="NAME", choices=sorted(bm.DEVICE_AGENTS),
+                    help="agent classes to run on every MDP of their setting (" + ", ".join(sorted(bm.DEVICE_AGENTS)) + "), with the tuned "
+                         "hyper-parameters the reference ships; default: the Q-learning agent of the benchmark's setting.  "
+                         "PSRLEpisodic and UCRL2Continuous do not run on the reference's Beta-reward caches: a benchmark with "
+                         "stochastic rewards needs --beta-rewards philox for them, and is refused otherwise")
     ap.add_argument("--overwrite", action="store_true",
                     help="run every instance; default: skip those whose log file exists, as the reference's resume does")
     args = ap.parse_args()
@@ -65,7 +70,7 @@ def main():
     max_time = args.max_time if args.max_time is not None else float(cfg.get("max_interaction_time_s", float("inf")))
     instances = []
     for k, mdp_cfg in enumerate(benchmarks):
-        for ins in bm.enumerate_instances(mdp_cfg, n_seeds):
+        for ins in bm.enumerate_instances(mdp_cfg, n_seeds, agents=args.agents):
             ins.mdp_scope = f"b{k}_{ins.mdp_scope}" if len(benchmarks) > 1 else ins.mdp_scope
             instances.append(ins)
     todo = set(range(len(instances)) if args.overwrite else bm.unfinished_instances(args.out, instances))
