@@ -12,6 +12,7 @@ OK, ERR_INVALID, ERR_HIP, ERR_NEEDS_RESET, ERR_UNSUPPORTED, ERR_MAX_ITER, ERR_NO
     0, -1, -2, -3, -4, -5, -6, -7, -8)
 RNG_MT_COMPAT, RNG_PHILOX = 0, 1
 POLICY_RANDOM, POLICY_HOST_ACTIONS, POLICY_GREEDY_Q = 0, 1, 2
+POLICY_RANDOM_REFERENCE = 3  # RandomActor's stream: RandomState(seed).randint(0, A, .) per instance, generated on the device (K16)
 SCHEME_AUTO, SCHEME_JACOBI, SCHEME_GAUSS_SEIDEL = 0, 1, 2
 LAYOUT_CSR, LAYOUT_DENSE = 0, 1
 FLAG_REWARD_MEANS = 1
@@ -35,6 +36,7 @@ STAT_DIAMETER_KERNEL = 22  # family * 1000 + n * 10 + flag, see include/cmdp.h
 STAT_UCRL2_POLICY_KERNEL_MS = 23
 STAT_PSRL_POLICY_KERNEL_MS = 24
 STAT_UCRL2_POLICY_SOLVED, STAT_UCRL2_POLICY_REUSED = 25, 26  # instances K14 solved / kept their stored policy
+STAT_ACTIONS_KERNEL_MS = 27  # K16 before the last K1E walk under POLICY_RANDOM_REFERENCE
 PSRL_SAMPLER_REFERENCE, PSRL_SAMPLER_PHILOX = 0, 1
 PSRL_KEY_HI = 0x5053524C
 BOUND_CHERNOFF, BOUND_BERNSTEIN = 0, 1
@@ -88,6 +90,7 @@ EXPORTS = [
     "cmdp_k1e_pair_plan", "cmdp_k1e_pair_plan_desc",
     "cmdp_psrl_map_rows", "cmdp_vi_episodic_map", "cmdp_psrl_policy", "cmdp_psrl_evaluate",
     "cmdp_ucrl2_run_logged", "cmdp_psrl_run_logged",
+    "cmdp_set_action_streams", "cmdp_action_stream_state", "cmdp_set_action_stream_state", "cmdp_mt_randint", "cmdp_mt_action_bits",
 ]
 
 
@@ -236,6 +239,11 @@ def load():
         L.cmdp_qlearning_tables.argtypes = [vp, vp, vp]
         L.cmdp_set_reward_streams.argtypes = [vp, vp, vp, vp, vp]
         L.cmdp_legacy_beta.argtypes = [vp, vp, vp, vp, f64, f64, i64, vp]
+        L.cmdp_set_action_streams.argtypes = [vp, vp]
+        L.cmdp_action_stream_state.argtypes = [vp, vp, vp]
+        L.cmdp_set_action_stream_state.argtypes = [vp, vp, vp]
+        L.cmdp_mt_randint.argtypes = [vp, vp, i32, i64, vp]
+        L.cmdp_mt_action_bits.argtypes = [vp, vp, i64, i64, vp]
         L.cmdp_ucrl2_create.argtypes = [C.POINTER(vp), vp, vp, i64, f64, f64, i32, i32, i32]
         L.cmdp_ucrl2_destroy.argtypes = [vp]
         L.cmdp_ucrl2_run.argtypes = [vp, i64, i32, vp, vp, vp, vp, vp, vp]

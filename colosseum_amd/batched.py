@@ -227,6 +227,30 @@ class BatchedMDP:
         cached = np.ascontiguousarray([float(s[4]) for s in states], np.float64)
         L.check(self._lib.cmdp_set_reward_streams(self._h, L.ptr(key), L.ptr(pos), L.ptr(has), L.ptr(cached)))
 
+    def set_action_streams(self, seeds):
+        """POLICY_RANDOM_REFERENCE: instance b takes the actions of the reference's RandomActor seeded with seeds[b],
+        `RandomState(seeds[b]).randint(0, A, .)` in order (colosseum/agent/actors/random.py:34-47).  Seeds are uint32; calling
+        it again reseeds."""
+        s = np.asarray(seeds)
+        assert s.shape == (self.B,) and np.all(s >= 0) and np.all(s <= 0xFFFFFFFF), "seeds: B values in [0, 2**32)"
+        s = np.ascontiguousarray(s.astype(np.uint32))
+        L.check(self._lib.cmdp_set_action_streams(self._h, L.ptr(s)))
+
+    def set_action_stream_states(self, states):
+        """Continues the action streams from B `RandomState.get_state()` tuples (their Gaussian cache plays no part)."""
+        assert len(states) == self.B
+        key = np.ascontiguousarray(np.stack([np.asarray(s[1], np.uint32) for s in states]))
+        pos = np.ascontiguousarray([int(s[2]) for s in states], np.int32)
+        L.check(self._lib.cmdp_set_action_stream_state(self._h, L.ptr(key), L.ptr(pos)))
+
+    def action_streams(self):
+        """The action streams of POLICY_RANDOM_REFERENCE as a list of B tuples that `RandomState.set_state` accepts: what
+        `get_state()` of the reference's generator gives after the same draws."""
+        key = np.zeros((self.B, 624), np.uint32)
+        pos = np.zeros(self.B, np.int32)
+        L.check(self._lib.cmdp_action_stream_state(self._h, L.ptr(key), L.ptr(pos)))
+        return [("MT19937", key[b].copy(), int(pos[b]), 0, 0.0) for b in range(self.B)]
+
     def reward_cache_stats(self) -> dict:
         """Blocks of 5000 samples drawn so far and park / fill / relaunch rounds (CMDP_FLAG_REWARD_CACHE)."""
         v = C.c_double()
@@ -282,17 +306,23 @@ class BatchedMDP:
         L.check(self._lib.cmdp_step(self._h, L.ptr(a), int(auto_reset), L.ptr(obs), L.ptr(rew), L.ptr(st)))
         return obs, rew, st
 
-    def rollout(self, n_steps: int, actions=None, trace: bool = False, greedy_q=None):
+    def rollout(self, n_steps: int, actions=None, trace: bool = False, greedy_q=None, policy=None):
         """n_steps transitions per instance (episodic terminations are followed by reset()).
         actions: None -> on-device uniform random policy; else int array [n_steps, B].  greedy_q: per-instance Q
-        tables ([S, A], or [H, S, A] for episodic handles): the fixed policy "first maximiser of the current row"."""
+        tables ([S, A], or [H, S, A] for episodic handles): the fixed policy "first maximiser of the current row".
+        policy="reference": the reference's random agent, on-device from the streams of `set_action_streams` (the default
+        random policy draws this project's own Philox stream)."""
         n_steps = int(n_steps)
         last = np.zeros(self.B, np.int32)
         rsum = np.zeros(self.B, np.float64)
         tr_obs = np.zeros((n_steps, self.B), np.int32) if trace else None
         tr_rew = np.zeros((n_steps, self.B), np.float64) if trace else None
         tr_ty = np.zeros((n_steps, self.B), np.uint8) if trace else None
-        if greedy_q is not None:
+        assert policy in (None, "reference"), policy
+        if policy == "reference":
+            assert actions is None and greedy_q is None
+            policy, arg = L.POLICY_RANDOM_REFERENCE, None
+        elif greedy_q is not None:
             assert actions is None
             policy, arg = L.POLICY_GREEDY_Q, np.ascontiguousarray(self._flat_rows(greedy_q, lead=max(self.H, 1)), np.float32)
         elif actions is None:
@@ -308,8 +338,9 @@ class BatchedMDP:
             out.update(obs=tr_obs, rew=tr_rew, stype=tr_ty)
         return out
 
-    def rollout_async(self, n_steps: int):
-        L.check(self._lib.cmdp_rollout_async(self._h, L.POLICY_RANDOM, int(n_steps)))
+    def rollout_async(self, n_steps: int, policy=None):
+        assert policy in (None, "reference"), policy
+        L.check(self._lib.cmdp_rollout_async(self._h, L.POLICY_RANDOM_REFERENCE if policy == "reference" else L.POLICY_RANDOM, int(n_steps)))
 
     def set_rollout_kernel(self, which: int):
         """L.ROLLOUT_AUTO | L.ROLLOUT_GLOBAL | L.ROLLOUT_LDS (tuning only; results are identical)."""

@@ -33,6 +33,7 @@ extern char** environ;
 #include "cmdp_rollout_plan.h"
 #include "cmdp_dp_plan.h"
 #include "cmdp_agent.h"
+#include "cmdp_actions.h"
 #include "cmdp_chain.h"
 #include "cmdp_chain_plan.h"
 #include "cmdp_evi.h"
@@ -178,6 +179,13 @@ struct cmdp {
   DevBuf<float> d_csr_val, d_R, d_Rov, d_pi, d_Q, d_V, d_per_target, d_Ev, d_out;
   DevBuf<int64_t> d_sweeps;
   DevBuf<int8_t> d_actions8;
+  // CMDP_POLICY_RANDOM_REFERENCE (cmdp_actions.h): RandomState(seed) of every instance in numpy's representation, the action
+  // bits of a K1E segment, and K16's failure flag (raised on the device, read at the next synchronisation)
+  DevBuf<uint32_t> d_as_key;
+  DevBuf<int32_t> d_as_pos, d_as_fail;
+  DevBuf<uint4> d_abits;
+  bool as_set = false, as_unchecked = false;
+  hipEvent_t ev_as[2] = {nullptr, nullptr};   // around K16 of the last segment of the last K1E launch under that policy
   DevBuf<int32_t> d_tr_obs, d_last_obs;
   DevBuf<double> d_tr_rew, d_rsum;
   DevBuf<uint8_t> d_tr_type, d_mask;
@@ -831,6 +839,8 @@ int cmdp_destroy(cmdp_t* h) {
     if (h->ev_time[i]) (void)hipEventDestroy(h->ev_time[i]);
   for (int i = 0; i < 2; ++i)
     if (h->ev_row[i]) (void)hipEventDestroy(h->ev_row[i]);
+  for (int i = 0; i < 2; ++i)
+    if (h->ev_as[i]) (void)hipEventDestroy(h->ev_as[i]);
   for (cmdp_t** back : h->uc_backrefs) *back = nullptr;
   for (double* c : h->rc_chunks) (void)hipFree(c);
   if (h->rc_stage_h) (void)hipHostFree(h->rc_stage_h);
@@ -1087,6 +1097,101 @@ int cmdp_step(cmdp_t* h, const int32_t* actions, int auto_reset, int32_t* obs, d
   return CMDP_OK;
 }
 
+// ---- CMDP_POLICY_RANDOM_REFERENCE: the reference's action streams (cmdp_actions.h) ------------------------------------
+static int action_streams_alloc(cmdp_t* h) {
+  HIP_TRY(h->d_as_key.alloc((size_t)h->B * MTA_N));
+  HIP_TRY(h->d_as_pos.alloc(h->B));
+  if (!h->d_as_fail.p) {
+    HIP_TRY(h->d_as_fail.alloc(1));
+    HIP_TRY(h->d_as_fail.zero(h->stream));
+  }
+  return CMDP_OK;
+}
+
+int cmdp_set_action_streams(cmdp_t* h, const uint32_t* seeds) {
+  if (int rc = bind(h, false)) return rc;
+  if (!h->has_env) return fail(CMDP_ERR_INVALID, "handle was created without the sampler half");
+  if (!seeds) return fail(CMDP_ERR_INVALID, "null argument");
+  hipStream_t st = h->stream;
+  if (int rc = action_streams_alloc(h)) return rc;
+  DevBuf<uint32_t> d_seeds;
+  HIP_TRY(d_seeds.upload(seeds, h->B, st));
+  // init_genrand, then numpy's position right after seeding: the first draw twists the block
+  hipLaunchKernelGGL(k_mt_seed_numpy, dim3(grid_for(h->B, 64)), dim3(64), 0, st, h->d_as_key.p, h->d_as_pos.p, d_seeds.p, h->B);
+  hipLaunchKernelGGL(k_fill_i32, dim3(grid_for(h->B, 256)), dim3(256), 0, st, h->d_as_pos.p, MTA_N, (int64_t)h->B);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(st));   // (the seeds leave scope)
+  h->as_set = true;
+  return CMDP_OK;
+}
+
+int cmdp_set_action_stream_state(cmdp_t* h, const uint32_t* mt_key, const int32_t* mt_pos) {
+  if (int rc = bind(h, false)) return rc;
+  if (!h->has_env) return fail(CMDP_ERR_INVALID, "handle was created without the sampler half");
+  if (!mt_key || !mt_pos) return fail(CMDP_ERR_INVALID, "null argument");
+  for (int b = 0; b < h->B; ++b)
+    if (mt_pos[b] < 0 || mt_pos[b] > MTA_N) return fail(CMDP_ERR_INVALID, "instance %d: MT19937 position %d outside [0, 624]", b, mt_pos[b]);
+  if (int rc = action_streams_alloc(h)) return rc;
+  HIP_TRY(hipMemcpyAsync(h->d_as_key.p, mt_key, sizeof(uint32_t) * (size_t)h->B * MTA_N, hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(hipMemcpyAsync(h->d_as_pos.p, mt_pos, sizeof(int32_t) * (size_t)h->B, hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  h->as_set = true;
+  return CMDP_OK;
+}
+
+int cmdp_action_stream_state(cmdp_t* h, uint32_t* mt_key, int32_t* mt_pos) {
+  if (int rc = bind(h, false)) return rc;
+  if (!mt_key || !mt_pos) return fail(CMDP_ERR_INVALID, "null argument");
+  if (!h->as_set) return fail(CMDP_ERR_INVALID, "no action streams: call cmdp_set_action_streams first");
+  HIP_TRY(hipMemcpyAsync(mt_key, h->d_as_key.p, sizeof(uint32_t) * (size_t)h->B * MTA_N, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipMemcpyAsync(mt_pos, h->d_as_pos.p, sizeof(int32_t) * (size_t)h->B, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  return CMDP_OK;
+}
+
+int cmdp_mt_randint(uint32_t* mt_key, int32_t* mt_pos, int n_actions, int64_t n, int8_t* out) {
+  if (!mt_key || !mt_pos || (!out && n > 0) || n < 0) return fail(CMDP_ERR_INVALID, "null argument");
+  if (n_actions < 1 || n_actions > 128) return fail(CMDP_ERR_INVALID, "n_actions outside [1, 128] (actions are int8)");
+  if (*mt_pos < 0 || *mt_pos > MTA_N) return fail(CMDP_ERR_INVALID, "MT19937 position outside [0, 624]");
+  if (!mta_randint_host(mt_key, mt_pos, n_actions, n, out))
+    return fail(CMDP_ERR_HIP, "randint: more than %lld words for %lld actions", mta_word_bound(n), (long long)n);
+  return CMDP_OK;
+}
+
+int cmdp_mt_action_bits(uint32_t* mt_key, int32_t* mt_pos, int64_t n, int64_t bit_offset, uint32_t* out) {
+  if (!mt_key || !mt_pos || (!out && n > 0) || n < 0 || bit_offset < 0) return fail(CMDP_ERR_INVALID, "bad argument");
+  if (*mt_pos < 0 || *mt_pos > MTA_N) return fail(CMDP_ERR_INVALID, "MT19937 position outside [0, 624]");
+  mta_action_bits_host(mt_key, mt_pos, n, bit_offset, out);
+  return CMDP_OK;
+}
+
+// K16's byte form: the call's n_steps x B actions into d_actions8, in the layout of CMDP_POLICY_HOST_ACTIONS (every kernel but
+// K1E takes them as such).  Once per call: reward-cache handles relaunch the rollout kernel, never this.
+static int reference_actions(cmdp_t* h, int64_t n_steps, const int8_t** d_act) {
+  if (n_steps > 0x7fffffffLL) return fail(CMDP_ERR_INVALID, "CMDP_POLICY_RANDOM_REFERENCE: more than 2^31 - 1 transitions in one call");
+  HIP_TRY(h->d_actions8.alloc((size_t)n_steps * (size_t)h->B));
+  if (n_steps > 0) {
+    hipLaunchKernelGGL(k_mt_actions<false>, dim3(h->B), dim3(K16_THREADS), 0, h->stream, h->d_as_key.p, h->d_as_pos.p,
+                       (const unsigned long long*)nullptr, h->B, h->A, (int)n_steps, 0, (uint4*)nullptr, h->d_actions8.p, h->d_as_fail.p);
+    HIP_TRY(hipGetLastError());
+    h->as_unchecked = true;
+  }
+  *d_act = h->d_actions8.p;
+  return CMDP_OK;
+}
+
+// K16 raises its flag on the device when a draw exceeds its word bound; the host looks after a synchronisation of the stream
+static int action_streams_check(cmdp_t* h) {
+  if (!h->as_unchecked) return CMDP_OK;
+  h->as_unchecked = false;
+  int32_t f = 0;
+  HIP_TRY(hipMemcpy(&f, h->d_as_fail.p, sizeof f, hipMemcpyDeviceToHost));
+  if (!f) return CMDP_OK;
+  HIP_TRY(hipMemset(h->d_as_fail.p, 0, sizeof f));
+  return fail(CMDP_ERR_HIP, "CMDP_POLICY_RANDOM_REFERENCE: an action stream rejected more words than its bound allows; the "
+                            "remaining actions of that launch were 0 (reseed the streams and reset the handle)");
+}
+
 // ---- rollout: the kernel a launch takes, then one launcher per kernel -----------------------------------
 enum class RolloutKernel { K1, K1_REWARD_CACHE, K1_GREEDY, K1D, K1L, K1P, K1T, K1U, K1E, K1S };
 
@@ -1113,7 +1218,12 @@ static int pick_rollout(const cmdp_t* h, int policy, bool trace, int64_t n_steps
   if (*out == K::K1_GREEDY && dense) return fail(CMDP_ERR_UNSUPPORTED, "CMDP_POLICY_GREEDY_Q runs on the CSR layout");
   if (*out == K::K1D && trace) return fail(CMDP_ERR_UNSUPPORTED, "the dense-layout rollout does not record traces");
   if (*out != K::K1) return CMDP_OK;
-  const bool lds = h->lds_ok && policy == CMDP_POLICY_RANDOM && !trace, k1s = h->k1s_ok && policy == CMDP_POLICY_RANDOM && !trace;
+  // CMDP_POLICY_RANDOM_REFERENCE: K1E consumes K16's bit blocks; the chain kernels K1L / K1P / K1T / K1U / K1S draw Philox only
+  const bool ref = policy == CMDP_POLICY_RANDOM_REFERENCE;
+  if (ref && rk >= 2 && rk <= 5)
+    return fail(CMDP_ERR_UNSUPPORTED, "CMDP_POLICY_RANDOM_REFERENCE runs on the episode-parallel rollout K1E (CMDP_OPT_ROLLOUT_KERNEL 6 or 0) and on "
+                                      "the lane-per-instance kernel K1 (1 or 0); kernel %d draws the Philox stream only", rk);
+  const bool lds = h->lds_ok && (policy == CMDP_POLICY_RANDOM || ref) && !trace, k1s = h->k1s_ok && policy == CMDP_POLICY_RANDOM && !trace;
   if (rk == 2 && !lds)
     return fail(CMDP_ERR_UNSUPPORTED, "LDS-resident rollout needs deterministic dynamics, one start state, <= 65535 "
                                       "states, <= 256 distinct rewards, the random policy and no trace");
@@ -1140,6 +1250,7 @@ static int pick_rollout(const cmdp_t* h, int policy, bool trace, int64_t n_steps
   const double k1_rate = (double)h->B * 2.5e5 / (1.0 + (double)h->B / 4.0e4);
   const double k1s_rate = (double)h->cus * (double)h->k1s.G / 450e-9;
   if (lds && h->k1e_ok && n_steps > 0 && (rk == 6 || wide)) *out = K::K1E;
+  else if (ref) *out = K::K1;
   else if (lds && h->k1u_ok && (rk == 5 || (wide && h->k1u_auto))) *out = K::K1U;
   else if (lds && h->tmpl_ok && (rk == 4 || (wide && h->tmpl_auto))) *out = K::K1T;
   else if (lds && (rk == 2 || wide)) *out = h->lds_plan.pipe ? K::K1P : K::K1L;
@@ -1201,7 +1312,17 @@ static int launch_k1e(cmdp_t* h, const RolloutCall& c, bool from_start) {
   // (the pair form stores its code words through 32-bit byte offsets, like the single form's interior rounds)
   pair = pair && need * sizeof(uint2) < ((size_t)1 << 31);
   if (pair) seg -= seg % e.H;   // whole episodes (seg >= H)
-  if (int rc = pair ? set_lds(k_rollout_epi<1>, h->k1e_pair_lds) : set_lds(k_rollout_epi<0>, h->k1e_lds)) return rc;
+  // CMDP_POLICY_RANDOM_REFERENCE: forms 2 / 3 load the action bits K16 makes before each segment's walk (<= 482 blocks of
+  // 16 bytes per instance); one buffer, K16 and the walk follow each other on the handle's stream
+  const bool ref = c.policy == CMDP_POLICY_RANDOM_REFERENCE;
+  if (ref) {
+    const size_t nblk_max = (size_t)((std::min<int64_t>(c.n, seg) + 126) >> 7) + 1;
+    if (h->d_abits.n < nblk_max * (size_t)h->B) HIP_TRY(h->d_abits.alloc(nblk_max * (size_t)h->B));
+    if (!h->ev_as[0])
+      for (int i = 0; i < 2; ++i) HIP_TRY(hipEventCreateWithFlags(&h->ev_as[i], hipEventDisableSystemFence));
+    e.abits = h->d_abits.p;
+    if (int rc = pair ? set_lds(k_rollout_epi<3>, h->k1e_pair_lds) : set_lds(k_rollout_epi<2>, h->k1e_lds)) return rc;
+  } else if (int rc = pair ? set_lds(k_rollout_epi<1>, h->k1e_pair_lds) : set_lds(k_rollout_epi<0>, h->k1e_lds)) return rc;
   h->k1e_last_form = pair ? 2 : 1;
   for (int64_t s0 = 0; s0 < c.n; s0 += seg) {
     const int64_t n = std::min<int64_t>(seg, c.n - s0);
@@ -1226,12 +1347,22 @@ static int launch_k1e(cmdp_t* h, const RolloutCall& c, bool from_start) {
     e.fast = !(e.debug & 16) && need * sizeof(uint2) < ((size_t)1 << 31) && k1e_ring_aligned(e);
     if (ov && h->aux.used[i]) HIP_TRY(hipStreamWaitEvent(st, h->aux.scan[i], 0));   // its last scan has read this set
     const bool last = s0 + seg >= c.n;
+    if (ref) {   // the segment's action bits, aligned on the instances' transition counters as the walk will read them
+      const int nblk = (int)((n + 126) >> 7) + 1;
+      if (last) HIP_TRY(hipEventRecord(h->ev_as[0], st));
+      hipLaunchKernelGGL(k_mt_actions<true>, dim3(h->B), dim3(K16_THREADS), 0, st, h->d_as_key.p, h->d_as_pos.p, t.n_trans, h->B, h->A,
+                         (int)n, nblk, h->d_abits.p, (int8_t*)nullptr, h->d_as_fail.p);
+      if (last) HIP_TRY(hipEventRecord(h->ev_as[1], st));
+      h->as_unchecked = true;
+    }
     if (last) HIP_TRY(hipEventRecord(h->ev_time[0], st));
     // one workgroup per CU (the tables take the CU's LDS), each walking its groups one after the other with the next
     // group's table image in flight under the walk; CMDP_K1E_GRID = workgroups (timing experiments; any value is correct)
     int k1e_grid = std::min(grid_for(h->B, K1E_NI), h->cus);
     if (const char* gs = std::getenv("CMDP_K1E_GRID")) k1e_grid = std::max(1, std::min(grid_for(h->B, K1E_NI), std::atoi(gs)));
-    if (pair) hipLaunchKernelGGL(k_rollout_epi<1>, dim3(k1e_grid), dim3(K1E_THREADS), h->k1e_pair_lds, st, t, e, (int)n, c.last);
+    if (ref && pair) hipLaunchKernelGGL(k_rollout_epi<3>, dim3(k1e_grid), dim3(K1E_THREADS), h->k1e_pair_lds, st, t, e, (int)n, c.last);
+    else if (ref) hipLaunchKernelGGL(k_rollout_epi<2>, dim3(k1e_grid), dim3(K1E_THREADS), h->k1e_lds, st, t, e, (int)n, c.last);
+    else if (pair) hipLaunchKernelGGL(k_rollout_epi<1>, dim3(k1e_grid), dim3(K1E_THREADS), h->k1e_pair_lds, st, t, e, (int)n, c.last);
     else hipLaunchKernelGGL(k_rollout_epi<0>, dim3(k1e_grid), dim3(K1E_THREADS), h->k1e_lds, st, t, e, (int)n, c.last);
     if (last) HIP_TRY(hipEventRecord(h->ev_time[1], st));
     if (ov) {
@@ -1386,8 +1517,9 @@ static int launch_k1(cmdp_t* h, RolloutKernel k, const RolloutCall& c) {
 
 // Pick, check the visit bound, settle what K1E left on the second stream and in its departure image (every other kernel
 // reads and writes the sums and counters itself), launch.  The caller commits the visit bound.
-static int launch_rollout(cmdp_t* h, const RolloutCall& c) {
+static int launch_rollout(cmdp_t* h, const RolloutCall& c0) {
   using K = RolloutKernel;
+  RolloutCall c = c0;
   // whole episodes walked from reset end at reset again, whichever kernel walks them (only K1E's pair form asks)
   const bool from_start = h->at_start, stays = from_start && h->k1e_pair_ok && h->H > 0 && c.n % h->H == 0;
   for (;;) {
@@ -1395,6 +1527,11 @@ static int launch_rollout(cmdp_t* h, const RolloutCall& c) {
     if (int rc = pick_rollout(h, c.policy, c.trace(), c.n, &k)) return rc;
     if (int rc = visits_check(h, c.n)) return rc;
     if (k != K::K1E) { if (int rc = k1e_settle(h)) return rc; }
+    if (k != K::K1E && c.policy == CMDP_POLICY_RANDOM_REFERENCE) {
+      // K1E had no workspace (the callers hand every other kernel CMDP_POLICY_HOST_ACTIONS themselves): the byte form now
+      if (int rc = reference_actions(h, c.n, &c.actions)) return rc;
+      c.policy = CMDP_POLICY_HOST_ACTIONS;
+    }
     int rc = CMDP_OK;
     switch (k) {
       case K::K1E: rc = launch_k1e(h, c, from_start); break;
@@ -1418,9 +1555,13 @@ int cmdp_rollout(cmdp_t* h, int policy, const void* policy_arg, int64_t n_steps,
   if (int rc = bind(h, false)) return rc;   // (launch_rollout settles K1E unless it takes K1E again)
   if (!h->has_env) return fail(CMDP_ERR_INVALID, "handle was created without the sampler half");
   if (n_steps < 0) return fail(CMDP_ERR_INVALID, "n_steps < 0");
-  if (policy != CMDP_POLICY_RANDOM && policy != CMDP_POLICY_HOST_ACTIONS && policy != CMDP_POLICY_GREEDY_Q)
+  const bool ref = policy == CMDP_POLICY_RANDOM_REFERENCE;
+  if (policy != CMDP_POLICY_RANDOM && policy != CMDP_POLICY_HOST_ACTIONS && policy != CMDP_POLICY_GREEDY_Q && !ref)
     return fail(CMDP_ERR_INVALID, "policy");
-  if (policy != CMDP_POLICY_RANDOM && !policy_arg && n_steps > 0) return fail(CMDP_ERR_INVALID, "policy_arg missing");
+  if (policy != CMDP_POLICY_RANDOM && !ref && !policy_arg && n_steps > 0) return fail(CMDP_ERR_INVALID, "policy_arg missing");
+  if (ref && !h->as_set) return fail(CMDP_ERR_INVALID, "CMDP_POLICY_RANDOM_REFERENCE: cmdp_set_action_streams has not been called on this handle");
+  RolloutKernel ref_kernel = RolloutKernel::K1;
+  if (ref) { if (int rc = pick_rollout(h, policy, trace_obs || trace_reward || trace_type, n_steps, &ref_kernel)) return rc; }
   bool any = false;
   if (int rc = any_needs_reset(h, &any)) return rc;
   if (any) return fail(CMDP_ERR_NEEDS_RESET, "rollout() on an instance that needs reset()");
@@ -1435,6 +1576,10 @@ int cmdp_rollout(cmdp_t* h, int policy, const void* policy_arg, int64_t n_steps,
       if (a[i] < 0 || a[i] >= h->A) return fail(CMDP_ERR_INVALID, "action out of range [0, %d)", h->A);
     HIP_TRY(h->d_actions8.upload(a, NB, st));
     d_act = h->d_actions8.p;
+  }
+  if (ref && ref_kernel != RolloutKernel::K1E) {
+    if (int rc = reference_actions(h, n_steps, &d_act)) return rc;
+    policy = CMDP_POLICY_HOST_ACTIONS;
   }
   const float* d_q = nullptr;
   if (policy == CMDP_POLICY_GREEDY_Q) {
@@ -1458,14 +1603,19 @@ int cmdp_rollout(cmdp_t* h, int policy, const void* policy_arg, int64_t n_steps,
   if (trace_reward) HIP_TRY(hipMemcpyAsync(trace_reward, h->d_tr_rew.p, sizeof(double) * NB, hipMemcpyDeviceToHost, st));
   if (trace_type) HIP_TRY(hipMemcpyAsync(trace_type, h->d_tr_type.p, NB, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
-  return CMDP_OK;
+  return action_streams_check(h);
 }
 
 int cmdp_rollout_async(cmdp_t* h, int policy, int64_t n_steps) {
   if (int rc = bind(h, false)) return rc;   // (launch_rollout settles K1E unless it takes K1E again)
   if (!h->has_env) return fail(CMDP_ERR_INVALID, "handle was created without the sampler half");
-  if (policy != CMDP_POLICY_RANDOM) return fail(CMDP_ERR_INVALID, "rollout_async supports CMDP_POLICY_RANDOM only");
+  const bool ref = policy == CMDP_POLICY_RANDOM_REFERENCE;
+  if (policy != CMDP_POLICY_RANDOM && !ref)
+    return fail(CMDP_ERR_INVALID, "rollout_async supports CMDP_POLICY_RANDOM and CMDP_POLICY_RANDOM_REFERENCE only");
   if (n_steps < 0) return fail(CMDP_ERR_INVALID, "n_steps < 0");
+  if (ref && !h->as_set) return fail(CMDP_ERR_INVALID, "CMDP_POLICY_RANDOM_REFERENCE: cmdp_set_action_streams has not been called on this handle");
+  RolloutKernel ref_kernel = RolloutKernel::K1;
+  if (ref) { if (int rc = pick_rollout(h, policy, false, n_steps, &ref_kernel)) return rc; }
   if (!h->known_reset) {  // one 4-byte read-back on the first call after create / cmdp_step, none afterwards
     bool any = false;
     if (int rc = any_needs_reset(h, &any)) return rc;
@@ -1474,8 +1624,13 @@ int cmdp_rollout_async(cmdp_t* h, int policy, int64_t n_steps) {
   }
   if (h->d_rsum.n < (size_t)h->B) HIP_TRY(h->d_rsum.alloc(h->B));
   if (h->d_last_obs.n < (size_t)h->B) HIP_TRY(h->d_last_obs.alloc(h->B));
+  const int8_t* d_act = nullptr;
+  if (ref && ref_kernel != RolloutKernel::K1E) {
+    if (int rc = reference_actions(h, n_steps, &d_act)) return rc;
+    policy = CMDP_POLICY_HOST_ACTIONS;
+  }
   auto launch = [&](int resume) -> int {
-    return launch_rollout(h, {policy, nullptr, nullptr, n_steps, h->d_rsum.p, h->d_last_obs.p, nullptr, nullptr, nullptr, resume});
+    return launch_rollout(h, {policy, d_act, nullptr, n_steps, h->d_rsum.p, h->d_last_obs.p, nullptr, nullptr, nullptr, resume});
   };
   // (reward caches: the park / fill / relaunch loop needs the host -- synchronous in this mode)
   return visits_commit(h, n_steps, h->reward_cache ? rc_drive(h, launch) : launch(0));
@@ -1691,7 +1846,7 @@ int cmdp_synchronize(cmdp_t* h) {
   if (int rc = bind(h, false)) return rc;   // (the departure image of K1E stays as it is: nothing here reads the counters)
   if (int rc = k1e_scan_join(h)) return rc;
   HIP_TRY(hipStreamSynchronize(h->stream));
-  return CMDP_OK;
+  return action_streams_check(h);
 }
 
 int cmdp_stat(cmdp_t* h, int which, double* out) {
@@ -1717,6 +1872,14 @@ int cmdp_stat(cmdp_t* h, int which, double* out) {
     HIP_TRY(hipEventSynchronize(e1));
     float ms = 0;
     HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
+    *out = ms;
+    return CMDP_OK;
+  }
+  if (which == CMDP_STAT_ACTIONS_KERNEL_MS) {
+    if (!h->ev_as[0]) return fail(CMDP_ERR_INVALID, "no K1E rollout under CMDP_POLICY_RANDOM_REFERENCE has run on this handle");
+    HIP_TRY(hipEventSynchronize(h->ev_as[1]));
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, h->ev_as[0], h->ev_as[1]));
     *out = ms;
     return CMDP_OK;
   }

@@ -115,6 +115,8 @@ struct K1ePlan {
   const uint16_t* pinv;      // [B][SP2] the state of compact index x
   int2* dep2;                // [group][pgdw] pair counts accumulated over launches, in ptab's layout (a0 = 0, a0 = 1); null in a fold
                              // when no launch of the handle took the pair form
+  // ---- forms 2 and 3: the action bits of the segment, made by K16 ----
+  const uint4* abits;        // [block relative to the segment's first][B]: bit (n_trans + j) & 127 of block ((n_trans & 127) + j) >> 7
 };
 
 // LDS: tables (2 actions x SP states x 32 instances x 4 B) | one ring per wavefront (ring_blocks x 4 dwords x 32 instances)
@@ -176,6 +178,8 @@ struct K1eGroupRegs {
 
 // FORM 0: the single form, below -- one transition per step, any segment.  FORM 1: the pair form (cmdp_k1e_pair.h, a
 // specialisation of its own) -- two transitions per step, segments of whole episodes walked from reset.
+// FORM 2 and 3: the same two walks with the action bits of CMDP_POLICY_RANDOM_REFERENCE -- `produce` loads the four dwords of
+// a block from p.abits (K16, cmdp_actions.h) where forms 0 and 1 make the Philox block; nothing else differs.
 template <int FORM>
 __global__ void __launch_bounds__(K1E_THREADS) __attribute__((amdgpu_waves_per_eu(5, 5))) k_rollout_epi(EnvTables t, K1ePlan p, int n_steps,
                                                             int32_t* __restrict__ last_obs) {
@@ -273,7 +277,12 @@ __global__ void __launch_bounds__(K1E_THREADS) __attribute__((amdgpu_waves_per_e
       for (int rb = max(blo, next_blk) + sub_o; rb <= bhi; rb += 2) {
         const unsigned long long blk = blk0 + (unsigned long long)rb;
         uint32_t w[4];
-        philox4x32_10((uint32_t)blk, (uint32_t)(blk >> 32), 2u, 0u, key.x, key.y, w);
+        if constexpr (FORM == 2) {   // the reference's stream: K16 has left the segment's blocks in HBM (cmdp_actions.h)
+          const uint4 v = p.abits[(size_t)rb * (size_t)t.B + (size_t)b];
+          w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
+        } else {
+          philox4x32_10((uint32_t)blk, (uint32_t)(blk >> 32), 2u, 0u, key.x, key.y, w);
+        }
         const uint32_t d0 = ((uint32_t)blk & ((uint32_t)p.ring_blocks - 1u)) << 2;
 #pragma unroll
         for (int j = 0; j < 4; ++j) ring[(size_t)(d0 + j) * K1E_NI + inst] = w[j];

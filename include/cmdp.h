@@ -53,9 +53,9 @@ enum {
   CMDP_RNG_MT_COMPAT = 0,
   /* Philox-4x32-10 keyed by the instance (counter-based, nothing stored per sampler):
      counter (n, domain): domain 0, n = transition index -> 53-bit transition uniform (stochastic rows);
-     domain 1, n = reset index -> start-state uniform; domain 2 -> random-policy actions (the reference's
-     RandomActor, colosseum/agent/actors/random.py:34-47, draws numpy blocks of 50 000; this is the
-     throughput stream): for A in {2, 4, 16, 256} the PACKED form -- block n / apb holds apb = 128 / log2(A)
+     domain 1, n = reset index -> start-state uniform; domain 2 -> the actions of CMDP_POLICY_RANDOM: this project's OWN
+     stream, the throughput stream -- NOT the reference's (RandomActor, colosseum/agent/actors/random.py:34-47, pops
+     numpy blocks of 50 000 from RandomState(seed); that stream is CMDP_POLICY_RANDOM_REFERENCE, in either rng_mode): for A in {2, 4, 16, 256} the PACKED form -- block n / apb holds apb = 128 / log2(A)
      actions, action k = n % apb in bits [lg (k % apw), +lg) of word k / apw, apw = 32 / lg (A = 2: 128
      one-bit actions per block, least significant bit of word 0 first); for any other A, block n >> 2,
      word (n & 3), a = (word * A) >> 32. */
@@ -66,9 +66,17 @@ enum {
 enum {
   CMDP_POLICY_RANDOM = 0,       /* uniform over A from the instance's Philox stream (config C2)      */
   CMDP_POLICY_HOST_ACTIONS = 1, /* policy_arg = const int8_t actions[n_steps][B]                      */
-  CMDP_POLICY_GREEDY_Q = 2      /* policy_arg = const float Q: per instance [S_b][A] (continuous) or
+  CMDP_POLICY_GREEDY_Q = 2,     /* policy_arg = const float Q: per instance [S_b][A] (continuous) or
                                    [H][S_b][A] at H*state_off[b]*A (episodic, row = in-episode time);
                                    the action is the first maximiser of the current row            */
+  /* The reference's random agent: instance b takes the actions RandomState(seeds[b]).randint(0, A, .) yields, one after the
+     other across calls (RandomActor, colosseum/agent/actors/random.py:34-47: its blocks of 50 000 are consecutive pieces of
+     that stream).  Generated on the device from the streams cmdp_set_action_streams seeded (CMDP_ERR_INVALID before that);
+     policy_arg is ignored.  CMDP_POLICY_RANDOM is the Philox stream of domain 2 instead: equally distributed, other actions.
+     Runs on the episode-parallel kernel K1E when the batch is eligible (automatically from 64 transitions, or
+     CMDP_OPT_ROLLOUT_KERNEL 6) and on the lane-per-instance kernel K1 otherwise; CMDP_OPT_ROLLOUT_KERNEL 2-5 are
+     CMDP_ERR_UNSUPPORTED with this policy. */
+  CMDP_POLICY_RANDOM_REFERENCE = 3
 };
 
 /* Sweep scheme of the discounted solvers. */
@@ -197,6 +205,21 @@ int cmdp_set_reward_streams(cmdp_t* h, const uint32_t* mt_key, const int32_t* mt
 int cmdp_legacy_beta(uint32_t* mt_key, int32_t* mt_pos, int32_t* has_gauss, double* cached_gaussian, double a, double b,
                      int64_t n, double* out);
 
+/* CMDP_POLICY_RANDOM_REFERENCE: seeds [B]; instance b's action stream becomes numpy.random.RandomState(seeds[b]) as seeding
+   leaves it.  Calling it again reseeds. */
+int cmdp_set_action_streams(cmdp_t* h, const uint32_t* seeds);
+/* The action streams as RandomState.get_state() gives and set_state() takes them: mt_key [B][624], mt_pos [B] (0..624; the
+   setter refuses anything else with CMDP_ERR_INVALID).  The setter also creates the streams, like cmdp_set_action_streams. */
+int cmdp_action_stream_state(cmdp_t* h, uint32_t* mt_key, int32_t* mt_pos);
+int cmdp_set_action_stream_state(cmdp_t* h, const uint32_t* mt_key, const int32_t* mt_pos);
+/* `RandomState.randint(0, n_actions, n)` on a caller-held stream state (mt_key [624], *mt_pos; updated in place): out [n].
+   n_actions in 1..128 (actions are int8).  Host only, built from the very functions the device generator K16 (csrc/cmdp_actions.h) draws with;
+   exists so that the CPU test suite can hold them against numpy itself, action for action. */
+int cmdp_mt_randint(uint32_t* mt_key, int32_t* mt_pos, int n_actions, int64_t n, int8_t* out);
+/* `RandomState.randint(0, 2, n)` packed as K16 packs it for K1E: action j becomes bit (bit_offset + j) & 31 of word
+   (bit_offset + j) >> 5 of out; no other bit of out is changed.  Host only, as cmdp_mt_randint. */
+int cmdp_mt_action_bits(uint32_t* mt_key, int32_t* mt_pos, int64_t n, int64_t bit_offset, uint32_t* out);
+
 /* ---- interaction: BaseMDP.reset / BaseMDP.step -------------------------------------------------- */
 /* BaseMDP.reset (colosseum/mdp/base.py:1268-1277) on every instance with mask[b] != 0 (all when mask
    is NULL): h = 0, start state sampled, its state-visit count bumped.  obs_out[b] = start state index
@@ -218,7 +241,8 @@ int cmdp_step(cmdp_t* h, const int32_t* actions, int auto_reset,
 int cmdp_rollout(cmdp_t* h, int policy, const void* policy_arg, int64_t n_steps,
                  int32_t* last_obs, double* reward_sum,
                  int32_t* trace_obs, double* trace_reward, uint8_t* trace_type);
-/* Same launch without the final synchronisation or any copy-back (for back-to-back timing). */
+/* Same launch without the final synchronisation or any copy-back (for back-to-back timing): CMDP_POLICY_RANDOM or
+   CMDP_POLICY_RANDOM_REFERENCE. */
 int cmdp_rollout_async(cmdp_t* h, int policy, int64_t n_steps);
 int cmdp_synchronize(cmdp_t* h);
 
@@ -278,7 +302,9 @@ enum { CMDP_STAT_DP_KERNEL_MS = 1, CMDP_STAT_DP_KERNEL = 2,
        CMDP_STAT_UCRL2_POLICY_SOLVED = 25,   /* UCRL2 agents of this handle: instances K14 has solved for cmdp_ucrl2_policy /
                                                 cmdp_ucrl2_average_reward / cmdp_ucrl2_run_logged, all requests together       */
        CMDP_STAT_UCRL2_POLICY_REUSED = 26    /* ... and instances of those requests that kept their stored policy instead
-                                                (CMDP_UCRL2_OPT_POLICY_REUSE)                                                     */ };
+                                                (CMDP_UCRL2_OPT_POLICY_REUSE)                                                     */,
+       CMDP_STAT_ACTIONS_KERNEL_MS = 27      /* CMDP_POLICY_RANDOM_REFERENCE on K1E: HIP-event time, on the handle's stream, of K16
+                                                (k_mt_actions, the action bits) before the walk CMDP_STAT_ROLLOUT_KERNEL_MS times  */ };
 /* The UCRL2 and PSRL statistics belong to the environment handle: agents created on the same handle share them. */
 int cmdp_stat(cmdp_t* h, int which, double* out);
 /* Latency floor of the LDS-resident rollout kernels, measured on the current device: one wavefront per CU follows
