@@ -36,6 +36,7 @@ extern char** environ;
 #include "cmdp_actions.h"
 #include "cmdp_chain.h"
 #include "cmdp_chain_plan.h"
+#include "cmdp_batch.h"
 #include "cmdp_evi.h"
 #include "cmdp_model_vi.h"
 #include "cmdp_ucrl2.h"
@@ -86,6 +87,9 @@ struct DevBuf {
     if (e != hipSuccess || count == 0) return e;
     return hipMemcpyAsync(p, src, count * sizeof(T), hipMemcpyHostToDevice, s);
   }
+  hipError_t download(T* dst, size_t count, hipStream_t s) const {
+    return count ? hipMemcpyAsync(dst, p, count * sizeof(T), hipMemcpyDeviceToHost, s) : hipSuccess;
+  }
   hipError_t zero(hipStream_t s) { return n ? hipMemsetAsync(p, 0, n * sizeof(T), s) : hipSuccess; }
   void swap(DevBuf& o) { std::swap(p, o.p); std::swap(n, o.n); std::swap(cap, o.cap); }
   void release() {
@@ -95,6 +99,41 @@ struct DevBuf {
     cap = 0;
   }
   ~DevBuf() { release(); }
+};
+
+// Lease of the workspace of a batch solver that takes no environment handle (cmdp_gth, cmdp_extended_vi,
+// cmdp_vi_discounted_model, cmdp_vi_episodic_dense, cmdp_vi_episodic_map): the solver's own struct `Ws` of DevBufs and a
+// non-blocking stream, one pair per device.  acquire() takes the solver's mutex, refuses when no device is visible, and
+// finds or creates the pair of the current device; the mutex is held until the lease goes out of scope, so the calls of one
+// solver are serialised.  Every solver names a Ws type of its own and so has its own pool, mutex and streams: host threads
+// in different solvers do not wait for each other.  The workspaces are reused across calls (no per-call hipMalloc / hipFree:
+// both synchronise the device) and deliberately leaked at exit (a static destructor's hipFree would run while the runtime
+// is being torn down).  A pair whose stream cannot be created is not kept: that call fails and the next one tries again.
+template <typename Ws>
+struct DeviceWorkspace {
+  Ws* ws = nullptr;
+  hipStream_t st = nullptr;
+  std::unique_lock<std::mutex> lock;
+  Ws* operator->() const { return ws; }
+  int acquire() {
+    struct Slot { Ws ws; hipStream_t st = nullptr; };
+    static std::mutex mu;
+    static std::map<int, Slot*>* all = new std::map<int, Slot*>;
+    lock = std::unique_lock<std::mutex>(mu);
+    int ndev = 0, dev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(CMDP_ERR_NO_DEVICE, "no HIP device visible");
+    HIP_TRY(hipGetDevice(&dev));
+    Slot*& slot = (*all)[dev];
+    if (!slot) {
+      hipStream_t created = nullptr;
+      HIP_TRY(hipStreamCreateWithFlags(&created, hipStreamNonBlocking));
+      slot = new Slot;
+      slot->st = created;
+    }
+    ws = &slot->ws;
+    st = slot->st;
+    return CMDP_OK;
+  }
 };
 
 // Page-locked host memory for the per-log read-backs of the logged loop.  Only grows, like DevBuf.
@@ -4183,8 +4222,6 @@ int cmdp_qlearning_tables(cmdp_agent_t* a, float* Q, int32_t* N) {
 int cmdp_gth(int count, const int32_t* dims, const double* mats, double* out) {
   if (count < 0 || (count > 0 && (!dims || !mats || !out))) return fail(CMDP_ERR_INVALID, "bad argument");
   if (count == 0) return CMDP_OK;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(CMDP_ERR_NO_DEVICE, "no HIP device visible");
   std::vector<int64_t> moff((size_t)count), xoff((size_t)count);
   int64_t mt = 0, xt = 0;
   for (int m = 0; m < count; ++m) {
@@ -4193,31 +4230,18 @@ int cmdp_gth(int count, const int32_t* dims, const double* mats, double* out) {
     mt += (int64_t)dims[m] * dims[m];
     xt += dims[m];
   }
-  // Workspace that is reused across calls (no per-call hipMalloc/hipFree: both synchronise the device) and deliberately
-  // leaked at exit; calls are serialised by a mutex.  One workspace per device.
-  struct Ws { DevBuf<int64_t> moff, xoff; DevBuf<int32_t> dims; DevBuf<double> mats, x; hipStream_t st = nullptr; };
-  static std::mutex mu;
-  static std::map<int, Ws*>* all = new std::map<int, Ws*>;
-  std::lock_guard<std::mutex> lock(mu);
-  int dev = 0;
-  HIP_TRY(hipGetDevice(&dev));
-  Ws*& ws = (*all)[dev];
-  if (!ws) {
-    ws = new Ws;
-    HIP_TRY(hipStreamCreateWithFlags(&ws->st, hipStreamNonBlocking));
-  }
-  DevBuf<int64_t>&d_moff = ws->moff, &d_xoff = ws->xoff;
-  DevBuf<int32_t>& d_dims = ws->dims;
-  DevBuf<double>&d_mats = ws->mats, &d_x = ws->x;
-  hipStream_t st = ws->st;
-  HIP_TRY(d_moff.upload(moff.data(), count, st));
-  HIP_TRY(d_xoff.upload(xoff.data(), count, st));
-  HIP_TRY(d_dims.upload(dims, count, st));
-  HIP_TRY(d_mats.upload(mats, (size_t)mt, st));
-  HIP_TRY(d_x.alloc((size_t)xt));
-  hipLaunchKernelGGL(k_gth, dim3(count), dim3(256), 0, st, d_moff.p, d_dims.p, d_xoff.p, d_mats.p, d_x.p);
+  struct Ws { DevBuf<int64_t> moff, xoff; DevBuf<int32_t> dims; DevBuf<double> mats, x; };
+  DeviceWorkspace<Ws> ws;
+  if (int rc = ws.acquire()) return rc;
+  hipStream_t st = ws.st;
+  HIP_TRY(ws->moff.upload(moff.data(), count, st));
+  HIP_TRY(ws->xoff.upload(xoff.data(), count, st));
+  HIP_TRY(ws->dims.upload(dims, count, st));
+  HIP_TRY(ws->mats.upload(mats, (size_t)mt, st));
+  HIP_TRY(ws->x.alloc((size_t)xt));
+  hipLaunchKernelGGL(k_gth, dim3(count), dim3(256), 0, st, ws->moff.p, ws->dims.p, ws->xoff.p, ws->mats.p, ws->x.p);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(out, d_x.p, sizeof(double) * (size_t)xt, hipMemcpyDeviceToHost, st));
+  HIP_TRY(ws->x.download(out, (size_t)xt, st));
   HIP_TRY(hipStreamSynchronize(st));
   return CMDP_OK;
 }
@@ -4242,82 +4266,34 @@ int cmdp_extended_vi(int count, const int32_t* n_states, const int32_t* n_action
     return fail(CMDP_ERR_INVALID, "null argument");
   if (!(epsilon >= 0.0) || !std::isfinite(epsilon)) return fail(CMDP_ERR_INVALID, "epsilon %g is not a finite value >= 0", epsilon);
   if (max_sweeps < 1) return fail(CMDP_ERR_INVALID, "max_sweeps %lld < 1", (long long)max_sweeps);
-  std::vector<int64_t> soff((size_t)count), roff((size_t)count);
-  int64_t ns = 0, nr = 0;
-  size_t lds = 0;
-  for (int b = 0; b < count; ++b) {
-    const int S = n_states[b], A = n_actions[b];
-    if (S < 1) return fail(CMDP_ERR_INVALID, "n_states[%d] = %d < 1", b, S);
-    if (A < 1) return fail(CMDP_ERR_INVALID, "n_actions[%d] = %d < 1", b, A);
-    if (!std::isfinite(r_max[b])) return fail(CMDP_ERR_INVALID, "r_max[%d] is not finite", b);
-    soff[b] = ns; roff[b] = nr;
-    ns += S;
-    nr += (int64_t)S * A;
-  }
+  BatchLayout L;
+  if (int rc = L.build(count, n_states, n_actions,
+                       {EVI_MAX_STATES, "instance %d has %d states: extended value iteration keeps u1, u2 and the order in "
+                                        "LDS for at most %d states"}))
+    return rc;
   for (int b = 0; b < count; ++b)
-    if (n_states[b] > EVI_MAX_STATES)
-      return fail(CMDP_ERR_UNSUPPORTED, "instance %d has %d states: extended value iteration keeps u1, u2 and the order in "
-                  "LDS for at most %d states", b, n_states[b], EVI_MAX_STATES);
-  if (csr_ptr[0] != 0) return fail(CMDP_ERR_INVALID, "csr_ptr[0] = %lld, not 0", (long long)csr_ptr[0]);
-  for (int64_t r = 0; r < nr; ++r)
-    if (csr_ptr[r + 1] < csr_ptr[r]) return fail(CMDP_ERR_INVALID, "csr_ptr decreases at row %lld", (long long)r);
-  const int64_t nnz = csr_ptr[nr];
-  if (nnz > 0 && (!csr_col || !csr_val)) return fail(CMDP_ERR_INVALID, "null csr_col / csr_val");
-  std::vector<float> uni((size_t)nr, 0.0f);
-  for (int b = 0; b < count; ++b) {
-    const int S = n_states[b], A = n_actions[b];
-    int P = 1;
-    while (P < S) P <<= 1;
-    lds = std::max(lds, (size_t)P * 8 + (size_t)S * 10);
-    for (int64_t r = roff[b]; r < roff[b] + (int64_t)S * A; ++r) {
-      const int64_t rb = csr_ptr[r], re = csr_ptr[r + 1];
-      for (int64_t k = rb; k < re; ++k) {
-        if (csr_col[k] < 0 || csr_col[k] >= S || (k > rb && csr_col[k] <= csr_col[k - 1]))
-          return fail(CMDP_ERR_INVALID, "csr_col of row %lld is not ascending within [0, %d)", (long long)r, S);
-        if (!(csr_val[k] >= 0.0f) || !std::isfinite(csr_val[k]))
-          return fail(CMDP_ERR_INVALID, "csr_val[%lld] = %g is not a finite probability >= 0", (long long)k, (double)csr_val[k]);
-      }
-      if (!std::isfinite(rewards[r])) return fail(CMDP_ERR_INVALID, "rewards[%lld] is not finite", (long long)r);
-      if (!std::isfinite(beta_r[r])) return fail(CMDP_ERR_INVALID, "beta_r[%lld] is not finite", (long long)r);
-      if (!std::isfinite(beta_p0[r])) return fail(CMDP_ERR_INVALID, "beta_p0[%lld] is not finite", (long long)r);
-      if (uniform && uniform[r] != 0.0f) {
-        if (!(uniform[r] > 0.0f) || !std::isfinite(uniform[r]) || re != rb)
-          return fail(CMDP_ERR_INVALID, "uniform[%lld] = %g: must be finite > 0 on a row without CSR entries",
-                      (long long)r, (double)uniform[r]);
-        uni[(size_t)r] = uniform[r];
-      } else if (re - rb == S && csr_val[rb] > 0.0f) {  // a full row of one value is taken as uniform too
-        bool same = true;
-        for (int64_t k = rb + 1; k < re && same; ++k) same = csr_val[k] == csr_val[rb];
-        if (same) uni[(size_t)r] = csr_val[rb];
-      }
-    }
-  }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(CMDP_ERR_NO_DEVICE, "no HIP device visible");
-  // Workspace reused across calls (UCRL2 solves once per episode; hipMalloc / hipFree synchronise the device) and
-  // deliberately leaked at exit; calls are serialised by a mutex.  One workspace per device.
+    if (!std::isfinite(r_max[b])) return fail(CMDP_ERR_INVALID, "r_max[%d] is not finite", b);
+  std::vector<float> uni;
+  if (int rc = check_row_form(L, {csr_ptr, csr_col, csr_val, uniform, rewards}, &uni, [&](int64_t r) -> int {
+        if (!std::isfinite(beta_r[r])) return fail(CMDP_ERR_INVALID, "beta_r[%lld] is not finite", (long long)r);
+        if (!std::isfinite(beta_p0[r])) return fail(CMDP_ERR_INVALID, "beta_p0[%lld] is not finite", (long long)r);
+        return CMDP_OK;
+      }))
+    return rc;
+  const int64_t ns = L.ns, nr = L.nr, nnz = csr_ptr[nr];
   struct Ws {
     DevBuf<int32_t> S, A, col, status;
     DevBuf<int64_t> soff, roff, ptr, sweeps;
     DevBuf<float> val, uni, R, Q, V;
     DevBuf<double> beta_r, beta_p0, r_max, span;
-    hipStream_t st = nullptr;
   };
-  static std::mutex mu;
-  static std::map<int, Ws*>* all = new std::map<int, Ws*>;
-  std::lock_guard<std::mutex> lock(mu);
-  int dev = 0;
-  HIP_TRY(hipGetDevice(&dev));
-  Ws*& ws = (*all)[dev];
-  if (!ws) {
-    ws = new Ws;
-    HIP_TRY(hipStreamCreateWithFlags(&ws->st, hipStreamNonBlocking));
-  }
-  hipStream_t st = ws->st;
+  DeviceWorkspace<Ws> ws;
+  if (int rc = ws.acquire()) return rc;
+  hipStream_t st = ws.st;
   HIP_TRY(ws->S.upload(n_states, count, st));
   HIP_TRY(ws->A.upload(n_actions, count, st));
-  HIP_TRY(ws->soff.upload(soff.data(), count, st));
-  HIP_TRY(ws->roff.upload(roff.data(), count, st));
+  HIP_TRY(ws->soff.upload(L.soff.data(), L.soff.size(), st));
+  HIP_TRY(ws->roff.upload(L.roff.data(), count, st));
   HIP_TRY(ws->ptr.upload(csr_ptr, (size_t)nr + 1, st));
   HIP_TRY(ws->col.upload(csr_col, (size_t)nnz, st));
   HIP_TRY(ws->val.upload(csr_val, (size_t)nnz, st));
@@ -4334,12 +4310,12 @@ int cmdp_extended_vi(int count, const int32_t* n_states, const int32_t* n_action
   EviArgs a{ws->S.p, ws->A.p, ws->soff.p, ws->roff.p, ws->ptr.p, ws->col.p, ws->val.p, ws->uni.p, ws->R.p,
             ws->beta_r.p, ws->beta_p0.p, ws->r_max.p, epsilon, max_sweeps, ws->Q.p, ws->V.p, ws->span.p,
             ws->sweeps.p, ws->status.p};
-  if (int rc = evi_launch(a, count, lds, st)) return rc;
-  HIP_TRY(hipMemcpyAsync(Q, ws->Q.p, sizeof(float) * (size_t)nr, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(V, ws->V.p, sizeof(float) * (size_t)ns, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(span, ws->span.p, sizeof(double) * count, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(sweeps, ws->sweeps.p, sizeof(int64_t) * count, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(status, ws->status.p, sizeof(int32_t) * count, hipMemcpyDeviceToHost, st));
+  if (int rc = evi_launch(a, count, evi_lds_bytes(L.max_S), st)) return rc;
+  HIP_TRY(ws->Q.download(Q, (size_t)nr, st));
+  HIP_TRY(ws->V.download(V, (size_t)ns, st));
+  HIP_TRY(ws->span.download(span, count, st));
+  HIP_TRY(ws->sweeps.download(sweeps, count, st));
+  HIP_TRY(ws->status.download(status, count, st));
   HIP_TRY(hipStreamSynchronize(st));
   return CMDP_OK;
 }
@@ -4372,79 +4348,28 @@ int cmdp_vi_discounted_model(int count, const int32_t* n_states, const int32_t* 
   if (scheme != CMDP_SCHEME_AUTO && scheme != CMDP_SCHEME_JACOBI && scheme != CMDP_SCHEME_GAUSS_SEIDEL)
     return fail(CMDP_ERR_INVALID, "scheme %d: CMDP_SCHEME_AUTO, CMDP_SCHEME_JACOBI or CMDP_SCHEME_GAUSS_SEIDEL", scheme);
   if (std::isnan(density_threshold)) return fail(CMDP_ERR_INVALID, "density_threshold is not a number");
-  std::vector<int64_t> soff((size_t)count), roff((size_t)count);
-  int64_t ns = 0, nr = 0;
-  int max_S = 0;
-  for (int b = 0; b < count; ++b) {
-    const int S = n_states[b], A = n_actions[b];
-    if (S < 1) return fail(CMDP_ERR_INVALID, "n_states[%d] = %d < 1", b, S);
-    if (A < 1) return fail(CMDP_ERR_INVALID, "n_actions[%d] = %d < 1", b, A);
-    soff[b] = ns; roff[b] = nr;
-    ns += S;
-    nr += (int64_t)S * A;
-    max_S = std::max(max_S, S);
-  }
-  for (int b = 0; b < count; ++b) {
-    if (n_states[b] > MVI_MAX_STATES)
-      return fail(CMDP_ERR_UNSUPPORTED, "instance %d has %d states: value iteration on a model keeps V, Vold and the shared "
-                  "products in LDS for at most %d states", b, n_states[b], MVI_MAX_STATES);
-    if (n_actions[b] > MVI_MAX_ACTIONS)
-      return fail(CMDP_ERR_UNSUPPORTED, "instance %d has %d actions: a wavefront takes the rows of a state, at most %d", b,
-                  n_actions[b], MVI_MAX_ACTIONS);
-  }
-  if (csr_ptr[0] != 0) return fail(CMDP_ERR_INVALID, "csr_ptr[0] = %lld, not 0", (long long)csr_ptr[0]);
-  for (int64_t r = 0; r < nr; ++r)
-    if (csr_ptr[r + 1] < csr_ptr[r]) return fail(CMDP_ERR_INVALID, "csr_ptr decreases at row %lld", (long long)r);
-  const int64_t nnz = csr_ptr[nr];
-  if (nnz > 0 && (!csr_col || !csr_val)) return fail(CMDP_ERR_INVALID, "null csr_col / csr_val");
-  std::vector<float> uni((size_t)nr, 0.0f);
-  for (int b = 0; b < count; ++b) {
-    const int S = n_states[b], A = n_actions[b];
-    for (int64_t r = roff[b]; r < roff[b] + (int64_t)S * A; ++r) {
-      const int64_t rb = csr_ptr[r], re = csr_ptr[r + 1];
-      for (int64_t k = rb; k < re; ++k) {
-        if (csr_col[k] < 0 || csr_col[k] >= S || (k > rb && csr_col[k] <= csr_col[k - 1]))
-          return fail(CMDP_ERR_INVALID, "csr_col of row %lld is not ascending within [0, %d)", (long long)r, S);
-        if (!(csr_val[k] >= 0.0f) || !std::isfinite(csr_val[k]))
-          return fail(CMDP_ERR_INVALID, "csr_val[%lld] = %g is not a finite probability >= 0", (long long)k, (double)csr_val[k]);
-      }
-      if (!std::isfinite(rewards[r])) return fail(CMDP_ERR_INVALID, "rewards[%lld] is not finite", (long long)r);
-      if (uniform && uniform[r] != 0.0f) {
-        if (!(uniform[r] > 0.0f) || !std::isfinite(uniform[r]) || re != rb)
-          return fail(CMDP_ERR_INVALID, "uniform[%lld] = %g: must be finite > 0 on a row without CSR entries",
-                      (long long)r, (double)uniform[r]);
-        uni[(size_t)r] = uniform[r];
-      } else if (re - rb == S && csr_val[rb] > 0.0f) {  // a full row of one value is taken as uniform too
-        bool same = true;
-        for (int64_t k = rb + 1; k < re && same; ++k) same = csr_val[k] == csr_val[rb];
-        if (same) uni[(size_t)r] = csr_val[rb];
-      }
-    }
-  }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(CMDP_ERR_NO_DEVICE, "no HIP device visible");
-  // a workspace per device, reused across calls and leaked at exit, calls serialised: as cmdp_extended_vi
+  BatchLayout L;
+  if (int rc = L.build(count, n_states, n_actions,
+                       {MVI_MAX_STATES, "instance %d has %d states: value iteration on a model keeps V, Vold and the shared "
+                                        "products in LDS for at most %d states",
+                        MVI_MAX_ACTIONS, "instance %d has %d actions: a wavefront takes the rows of a state, at most %d"}))
+    return rc;
+  std::vector<float> uni;
+  if (int rc = check_row_form(L, {csr_ptr, csr_col, csr_val, uniform, rewards}, &uni, [](int64_t) -> int { return CMDP_OK; }))
+    return rc;
+  const int64_t ns = L.ns, nr = L.nr, nnz = csr_ptr[nr];
   struct Ws {
     DevBuf<int32_t> S, A, col, scheme, status;
     DevBuf<int64_t> soff, roff, ptr, sweeps;
     DevBuf<float> val, uni, R, Q, V;
-    hipStream_t st = nullptr;
   };
-  static std::mutex mu;
-  static std::map<int, Ws*>* all = new std::map<int, Ws*>;
-  std::lock_guard<std::mutex> lock(mu);
-  int dev = 0;
-  HIP_TRY(hipGetDevice(&dev));
-  Ws*& ws = (*all)[dev];
-  if (!ws) {
-    ws = new Ws;
-    HIP_TRY(hipStreamCreateWithFlags(&ws->st, hipStreamNonBlocking));
-  }
-  hipStream_t st = ws->st;
+  DeviceWorkspace<Ws> ws;
+  if (int rc = ws.acquire()) return rc;
+  hipStream_t st = ws.st;
   HIP_TRY(ws->S.upload(n_states, count, st));
   HIP_TRY(ws->A.upload(n_actions, count, st));
-  HIP_TRY(ws->soff.upload(soff.data(), count, st));
-  HIP_TRY(ws->roff.upload(roff.data(), count, st));
+  HIP_TRY(ws->soff.upload(L.soff.data(), L.soff.size(), st));
+  HIP_TRY(ws->roff.upload(L.roff.data(), count, st));
   HIP_TRY(ws->ptr.upload(csr_ptr, (size_t)nr + 1, st));
   HIP_TRY(ws->col.upload(csr_col, (size_t)nnz, st));
   HIP_TRY(ws->val.upload(csr_val, (size_t)nnz, st));
@@ -4458,12 +4383,12 @@ int cmdp_vi_discounted_model(int count, const int32_t* n_states, const int32_t* 
   ModelViArgs a{ws->S.p, ws->A.p, ws->soff.p, ws->roff.p, ws->ptr.p, ws->col.p, ws->val.p, ws->uni.p, ws->R.p, nullptr,
                 gamma, epsilon, scheme, size_threshold, density_threshold, max_sweeps, ws->Q.p, ws->V.p, ws->sweeps.p,
                 ws->scheme.p, ws->status.p};
-  if (int rc = mvi_launch(a, count, max_S, st)) return rc;
-  HIP_TRY(hipMemcpyAsync(Q, ws->Q.p, sizeof(float) * (size_t)nr, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(V, ws->V.p, sizeof(float) * (size_t)ns, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(sweeps, ws->sweeps.p, sizeof(int64_t) * count, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(scheme_used, ws->scheme.p, sizeof(int32_t) * count, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(status, ws->status.p, sizeof(int32_t) * count, hipMemcpyDeviceToHost, st));
+  if (int rc = mvi_launch(a, count, L.max_S, st)) return rc;
+  HIP_TRY(ws->Q.download(Q, (size_t)nr, st));
+  HIP_TRY(ws->V.download(V, (size_t)ns, st));
+  HIP_TRY(ws->sweeps.download(sweeps, count, st));
+  HIP_TRY(ws->scheme.download(scheme_used, count, st));
+  HIP_TRY(ws->status.download(status, count, st));
   HIP_TRY(hipStreamSynchronize(st));
   return CMDP_OK;
 }
@@ -4630,9 +4555,7 @@ int cmdp_ucrl2_create(cmdp_ucrl2_t** out, cmdp_t* env, const int32_t* seeds, int
   std::vector<int32_t> col;
   if (int rc = build_model_layout(a, ptr, col)) return rc;
   const int64_t NZ = a->nz;
-  int P = 1;
-  while (P < env->max_S) P <<= 1;
-  a->evi_lds = (size_t)P * 8 + (size_t)env->max_S * 10;
+  a->evi_lds = evi_lds_bytes(env->max_S);
   // tables as UCRL2Continuous.__init__ leaves them (ucrl2.py:140-159)
   std::vector<float> uni((size_t)R), er((size_t)R, (float)env->rmax), ht((size_t)R, 1.0f);
   for (int b = 0; b < B; ++b) {
@@ -5111,7 +5034,7 @@ int cmdp_psrl_create(cmdp_psrl_t** out, cmdp_t* env, const int32_t* seeds, int64
   }
   a->t_total = tt;
   a->sample_lds = (size_t)(PSRL_SAMPLE_THREADS / 64) * env->max_S * sizeof(float);
-  a->vi_lds = (size_t)2 * ((env->max_S + 3) & ~3) * sizeof(float);
+  a->vi_lds = dense_vi_lds_bytes(env->max_S);
   if (tt > (int64_t)1 << 40 || a->d_T.alloc((size_t)tt) != hipSuccess) {
     (void)hipGetLastError();
     return fail(CMDP_ERR_OVERFLOW, "the dense workspace of the sampled transition models cannot be allocated: %lld bytes for the "
@@ -5261,61 +5184,45 @@ int cmdp_vi_episodic_dense(int count, const int32_t* n_states, const int32_t* n_
   if (count == 0) return CMDP_OK;
   if (!n_states || !n_actions || !T || !R || !Q || !V) return fail(CMDP_ERR_INVALID, "null argument");
   if (H < 1) return fail(CMDP_ERR_INVALID, "H %d < 1", H);
-  std::vector<int64_t> soff((size_t)count + 1), roff((size_t)count), toff((size_t)count), tsrc((size_t)count);
-  int64_t ns = 0, nr = 0, nt = 0, nsrc = 0;
-  int max_S = 1;
+  BatchLayout L;
+  if (int rc = L.build(count, n_states, n_actions,
+                       {PSRL_MAX_STATES, "instance %d has %d states: the dense episodic solver keeps two value layers in LDS for at "
+                                         "most %d states"}))
+    return rc;
+  const int64_t ns = L.ns, nr = L.nr;
+  std::vector<int64_t> toff((size_t)count), tsrc((size_t)count);   // T[S, A, S] of an instance: padded on the device, packed in T
+  int64_t nt = 0, nsrc = 0;
   for (int b = 0; b < count; ++b) {
-    const int64_t S = n_states[b], A = n_actions[b];
-    if (S < 1) return fail(CMDP_ERR_INVALID, "n_states[%d] = %d < 1", b, (int)S);
-    if (A < 1) return fail(CMDP_ERR_INVALID, "n_actions[%d] = %d < 1", b, (int)A);
-    if (S > PSRL_MAX_STATES)
-      return fail(CMDP_ERR_UNSUPPORTED, "instance %d has %d states: the dense episodic solver keeps two value layers in LDS for at "
-                  "most %d states", b, (int)S, PSRL_MAX_STATES);
-    soff[b] = ns; roff[b] = nr; toff[b] = nt; tsrc[b] = nsrc;
-    ns += S; nr += S * A; nsrc += S * A * S;
-    nt += (S * A * S + 3) & ~(int64_t)3;
-    max_S = std::max(max_S, (int)S);
+    toff[b] = nt; tsrc[b] = nsrc;
+    nsrc += L.rows(b) * n_states[b];
+    nt += (L.rows(b) * n_states[b] + 3) & ~(int64_t)3;
   }
-  soff[count] = ns;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(CMDP_ERR_NO_DEVICE, "no HIP device visible");
-  // Workspace reused across calls, one per device, deliberately leaked at exit; calls are serialised by a mutex
   struct Ws {
     DevBuf<int32_t> S, A;
     DevBuf<int64_t> soff, roff, toff;
     DevBuf<float> T, R, Q, V;
-    hipStream_t st = nullptr;
   };
-  static std::mutex mu;
-  static std::map<int, Ws*>* all = new std::map<int, Ws*>;
-  std::lock_guard<std::mutex> lock(mu);
-  int dev = 0;
-  HIP_TRY(hipGetDevice(&dev));
-  Ws*& ws = (*all)[dev];
-  if (!ws) {
-    ws = new Ws;
-    HIP_TRY(hipStreamCreateWithFlags(&ws->st, hipStreamNonBlocking));
-  }
-  hipStream_t st = ws->st;
+  DeviceWorkspace<Ws> ws;
+  if (int rc = ws.acquire()) return rc;
+  hipStream_t st = ws.st;
   HIP_TRY(ws->S.upload(n_states, count, st));
   HIP_TRY(ws->A.upload(n_actions, count, st));
-  HIP_TRY(ws->soff.upload(soff.data(), count + 1, st));
-  HIP_TRY(ws->roff.upload(roff.data(), count, st));
+  HIP_TRY(ws->soff.upload(L.soff.data(), L.soff.size(), st));
+  HIP_TRY(ws->roff.upload(L.roff.data(), count, st));
   HIP_TRY(ws->toff.upload(toff.data(), count, st));
   if (ws->T.alloc((size_t)nt) != hipSuccess) {
     (void)hipGetLastError();
     return fail(CMDP_ERR_OVERFLOW, "the dense transition models cannot be held on the device: %lld bytes", (long long)(nt * 4));
   }
   for (int b = 0; b < count; ++b)
-    HIP_TRY(hipMemcpyAsync(ws->T.p + toff[b], T + tsrc[b], sizeof(float) * (size_t)n_states[b] * n_actions[b] * n_states[b],
-                           hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(ws->T.p + toff[b], T + tsrc[b], sizeof(float) * (size_t)(L.rows(b) * n_states[b]), hipMemcpyHostToDevice, st));
   HIP_TRY(ws->R.upload(R, (size_t)nr, st));
   HIP_TRY(ws->Q.alloc((size_t)(H + 1) * nr));
   HIP_TRY(ws->V.alloc((size_t)(H + 1) * ns));
   DviArgs g{nullptr, ws->S.p, ws->A.p, ws->toff.p, ws->roff.p, ws->soff.p, ws->T.p, ws->R.p, ws->Q.p, ws->V.p, H};
-  if (int rc = dvi_launch(g, count, (size_t)2 * ((max_S + 3) & ~3) * sizeof(float), st)) return rc;
-  HIP_TRY(hipMemcpyAsync(Q, ws->Q.p, sizeof(float) * (size_t)(H + 1) * nr, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(V, ws->V.p, sizeof(float) * (size_t)(H + 1) * ns, hipMemcpyDeviceToHost, st));
+  if (int rc = dvi_launch(g, count, dense_vi_lds_bytes(L.max_S), st)) return rc;
+  HIP_TRY(ws->Q.download(Q, (size_t)(H + 1) * nr, st));
+  HIP_TRY(ws->V.download(V, (size_t)(H + 1) * ns, st));
   HIP_TRY(hipStreamSynchronize(st));
   return CMDP_OK;
 }
@@ -5349,53 +5256,33 @@ int cmdp_vi_episodic_map(int count, const int32_t* n_states, const int32_t* n_ac
   if (count == 0) return CMDP_OK;
   if (!n_states || !n_actions || !row_ptr || !prior || !mu || !Q || !V) return fail(CMDP_ERR_INVALID, "null argument");
   if (H < 1) return fail(CMDP_ERR_INVALID, "H %d < 1", H);
-  std::vector<int64_t> soff((size_t)count + 1), roff((size_t)count);
-  int64_t ns = 0, nr = 0;
-  int max_S = 1;
-  for (int b = 0; b < count; ++b) {
-    const int64_t S = n_states[b], A = n_actions[b];
-    if (S < 1) return fail(CMDP_ERR_INVALID, "n_states[%d] = %d < 1", b, (int)S);
-    if (A < 1) return fail(CMDP_ERR_INVALID, "n_actions[%d] = %d < 1", b, (int)A);
-    if (S > MAPVI_MAX_STATES)
-      return fail(CMDP_ERR_UNSUPPORTED, "instance %d has %d states: value iteration on a MAP model (K15) keeps two value layers in "
-                  "LDS for at most %d states", b, (int)S, MAPVI_MAX_STATES);
-    soff[b] = ns; roff[b] = nr;
-    ns += S; nr += S * A;
-    max_S = std::max(max_S, (int)S);
-  }
-  soff[count] = ns;
+  BatchLayout L;
+  if (int rc = L.build(count, n_states, n_actions,
+                       {MAPVI_MAX_STATES, "instance %d has %d states: value iteration on a MAP model (K15) keeps two value layers in "
+                                          "LDS for at most %d states"}))
+    return rc;
+  const int64_t ns = L.ns, nr = L.nr;
   if (row_ptr[0] != 0) return fail(CMDP_ERR_INVALID, "row_ptr[0] = %lld, not 0", (long long)row_ptr[0]);
   const int64_t nz = row_ptr[nr];
   if (nz > 0 && (!col || !hp)) return fail(CMDP_ERR_INVALID, "null argument");
   size_t lds = 0;
   for (int b = 0; b < count; ++b) {
-    if (int rc = map_check_layout(b, n_states[b], n_actions[b], row_ptr + roff[b], col, hp, prior[b])) return rc;
-    lds = std::max(lds, map_vi_lds_bytes(n_states[b], n_actions[b], row_ptr[roff[b] + (int64_t)n_states[b] * n_actions[b]] - row_ptr[roff[b]]));
+    const int64_t* ptr = row_ptr + L.roff[b];
+    if (int rc = map_check_layout(b, n_states[b], n_actions[b], ptr, col, hp, prior[b])) return rc;
+    lds = std::max(lds, map_vi_lds_bytes(n_states[b], n_actions[b], ptr[L.rows(b)] - ptr[0]));
   }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(CMDP_ERR_NO_DEVICE, "no HIP device visible");
-  // Workspace reused across calls, one per device, deliberately leaked at exit; calls are serialised by a mutex
   struct Ws {
     DevBuf<int32_t> S, A, col;
     DevBuf<int64_t> soff, roff, ptr;
     DevBuf<float> hp, prior, mu, t, c, Q, V;
-    hipStream_t st = nullptr;
   };
-  static std::mutex mtx;
-  static std::map<int, Ws*>* all = new std::map<int, Ws*>;
-  std::lock_guard<std::mutex> lock(mtx);
-  int dev = 0;
-  HIP_TRY(hipGetDevice(&dev));
-  Ws*& ws = (*all)[dev];
-  if (!ws) {
-    ws = new Ws;
-    HIP_TRY(hipStreamCreateWithFlags(&ws->st, hipStreamNonBlocking));
-  }
-  hipStream_t st = ws->st;
+  DeviceWorkspace<Ws> ws;
+  if (int rc = ws.acquire()) return rc;
+  hipStream_t st = ws.st;
   HIP_TRY(ws->S.upload(n_states, count, st));
   HIP_TRY(ws->A.upload(n_actions, count, st));
-  HIP_TRY(ws->soff.upload(soff.data(), count + 1, st));
-  HIP_TRY(ws->roff.upload(roff.data(), count, st));
+  HIP_TRY(ws->soff.upload(L.soff.data(), L.soff.size(), st));
+  HIP_TRY(ws->roff.upload(L.roff.data(), count, st));
   HIP_TRY(ws->ptr.upload(row_ptr, (size_t)nr + 1, st));
   HIP_TRY(ws->col.upload(col, (size_t)nz, st));
   HIP_TRY(ws->hp.upload(hp, (size_t)nz, st));
@@ -5407,11 +5294,11 @@ int cmdp_vi_episodic_map(int count, const int32_t* n_states, const int32_t* n_ac
   HIP_TRY(ws->V.alloc((size_t)(H + 1) * ns));
   MapViArgs g{nullptr, ws->S.p, ws->A.p, ws->roff.p, ws->soff.p, ws->ptr.p, ws->col.p, ws->hp.p, ws->prior.p, ws->mu.p, 1,
               ws->t.p, ws->c.p, ws->Q.p, ws->V.p, H, 0};
-  if (int rc = mapvi_launch(g, count, max_S, lds, st)) return rc;
-  HIP_TRY(hipMemcpyAsync(Q, ws->Q.p, sizeof(float) * (size_t)(H + 1) * nr, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(V, ws->V.p, sizeof(float) * (size_t)(H + 1) * ns, hipMemcpyDeviceToHost, st));
-  if (t_layout_out && nz) HIP_TRY(hipMemcpyAsync(t_layout_out, ws->t.p, sizeof(float) * (size_t)nz, hipMemcpyDeviceToHost, st));
-  if (c_out) HIP_TRY(hipMemcpyAsync(c_out, ws->c.p, sizeof(float) * (size_t)nr, hipMemcpyDeviceToHost, st));
+  if (int rc = mapvi_launch(g, count, L.max_S, lds, st)) return rc;
+  HIP_TRY(ws->Q.download(Q, (size_t)(H + 1) * nr, st));
+  HIP_TRY(ws->V.download(V, (size_t)(H + 1) * ns, st));
+  if (t_layout_out) HIP_TRY(ws->t.download(t_layout_out, (size_t)nz, st));
+  if (c_out) HIP_TRY(ws->c.download(c_out, (size_t)nr, st));
   HIP_TRY(hipStreamSynchronize(st));
   return CMDP_OK;
 }

@@ -53,6 +53,13 @@ struct EviArgs {
   int32_t* status;           // [count] 0 or CMDP_ERR_MAX_ITER
 };
 
+// Dynamic LDS of a launch whose largest instance has S states: k_evi's carve-up below (keys, u1, u2, rank)
+inline size_t evi_lds_bytes(int S) {
+  int P = 1;
+  while (P < S) P <<= 1;
+  return (size_t)P * 8 + (size_t)S * 10;
+}
+
 __device__ __forceinline__ uint32_t evi_sortable(float f) {
   uint32_t b = __float_as_uint(__fadd_rn(f, 0.0f));  // -0 -> +0: argsort sees them equal
   return (b & 0x80000000u) ? ~b : (b | 0x80000000u);

@@ -203,6 +203,9 @@ struct DviArgs {
   int H;
 };
 
+// Dynamic LDS of a launch whose largest instance has max_S states: the two value layers of k_vi_episodic_dense
+inline size_t dense_vi_lds_bytes(int max_S) { return (size_t)2 * ((max_S + 3) & ~3) * sizeof(float); }
+
 __global__ void __launch_bounds__(PSRL_VI_THREADS) k_vi_episodic_dense(DviArgs g) {
   extern __shared__ __align__(16) float dv_lds[];
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;

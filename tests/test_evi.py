@@ -116,18 +116,13 @@ def test_c_abi_argument_checks():
     assert "r_max[0]" in call(rmax=np.array([np.inf]))[1]
     rc, msg = call(n_states=np.array([5000], np.int32))
     assert rc == L.ERR_UNSUPPORTED and "4096" in msg
-    assert "csr_ptr[0]" in call(ptr=np.ones(S * A + 1, np.int64))[1]
-    dec = np.zeros(S * A + 1, np.int64)
-    dec[1] = 1
-    assert "csr_ptr decreases" in call(ptr=dec)[1]
-    one = np.zeros(S * A + 1, np.int64)
-    one[1:] = 1
-    no_uni = np.zeros(S * A, np.float32)
-    assert "csr_col" in call(ptr=one, uni=no_uni, col=np.array([3], np.int32), val=np.array([1], np.float32))[1]
-    assert "csr_val[0]" in call(ptr=one, uni=no_uni, col=np.array([0], np.int32), val=np.array([-1], np.float32))[1]
-    assert "uniform[0]" in call(ptr=one, col=np.array([0], np.int32), val=np.array([1], np.float32))[1]
-    assert "uniform[0]" in call(uni=np.full(S * A, -0.5, np.float32))[1]
-    assert "rewards[2]" in call(R=np.array([0, 0, np.nan, 0, 0, 0], np.float32))[1]
+    # the row form itself (csr_ptr, csr_col, csr_val, rewards, uniform): tests/test_row_form.py, shared with kernel K14
     assert "beta_r[1]" in call(br=np.array([0, np.inf, 0, 0, 0, 0]))[1]
     assert "beta_p0[5]" in call(bp=np.array([0, 0, 0, 0, 0, np.nan]))[1]
+    # a row's bounds are checked after its reward and before its uniform value
+    nan2 = np.array([0, 0, np.nan, 0, 0, 0])
+    assert "rewards[2]" in call(R=nan2.astype(np.float32), br=nan2, bp=nan2)[1]
+    assert "beta_r[2]" in call(br=nan2, bp=nan2, uni=np.array([1 / 3, 1 / 3, -0.5, 1 / 3, 1 / 3, 1 / 3], np.float32))[1]
+    assert "beta_p0[0]" in call(bp=np.full(S * A, np.nan), uni=np.full(S * A, -0.5, np.float32))[1]
+    assert "uniform[0]" in call(bp=np.array([0, 0, 0, 0, 0, np.nan]), uni=np.full(S * A, -0.5, np.float32))[1]
     assert call(count=0)[0] == L.OK

@@ -70,35 +70,12 @@ def test_argument_checks_without_a_device():
                    scheme=np.zeros(1, np.int32), status=np.zeros(1, np.int32))
         out[k] = None
         invalid("null argument", out=out)
-    invalid("null csr_col / csr_val", col=None)
-    invalid("null csr_col / csr_val", val=None)
     invalid("n_states[0]", n_states=np.array([0], np.int32))
     invalid("n_actions[0]", n_actions=np.array([0], np.int32))
-    bad = args["ptr"].copy(); bad[3] = bad[2] - 1
-    invalid("csr_ptr decreases at row 2", ptr=bad)
-    bad = args["ptr"].copy(); bad[0] = 1
-    invalid("csr_ptr[0]", ptr=bad)
-    multi = next(r for r in range(2, 6) if args["ptr"][r + 1] - args["ptr"][r] >= 2)
-    k0 = int(args["ptr"][multi])
-    bad = args["col"].copy(); bad[k0 + 1] = bad[k0]
-    invalid(f"csr_col of row {multi} is not ascending", col=bad)
-    bad = args["col"].copy(); bad[k0] = 3
-    invalid(f"csr_col of row {multi}", col=bad)
-    bad = args["col"].copy(); bad[k0] = -1
-    invalid(f"csr_col of row {multi}", col=bad)
-    for v in (-0.5, np.inf, np.nan):
-        bad = args["val"].copy(); bad[1] = v
-        invalid("csr_val[1]", val=bad)
-    bad = args["uni"].copy(); bad[multi] = 0.25
-    invalid(f"uniform[{multi}]", uni=bad)
-    for v in (-0.5, np.inf, np.nan):
-        bad = args["uni"].copy(); bad[0] = v
-        invalid("uniform[0]", uni=bad)
+    # the row form itself (csr_ptr, csr_col, csr_val, rewards, uniform): tests/test_row_form.py, shared with kernel K10
     for v in (np.inf, np.nan):
         invalid("gamma", gamma=v)
         invalid("epsilon", eps=v)
-        bad = args["R"].copy(); bad[4] = v
-        invalid("rewards[4]", R=bad)
     invalid("epsilon", eps=-1.0)
     invalid("max_sweeps", max_sweeps=0)
     invalid("scheme 3", scheme=3)
