@@ -229,6 +229,21 @@ def diameter_episodic(model, eps=1e-3, use_running_max=True, max_sweeps=1_000_00
     return float(d.value), per
 
 
+def diameter_episodic_csr(S, A, H, csr, start_state, start_prob, eps=1e-3, use_running_max=False, max_sweeps=1_000_000):
+    """`diameter_episodic` on raw arrays: the CSR of one instance, its starting states and their float32 weights.
+    Returns (diameter, per-target values, return code): -5 when a target did not reach diff < eps within max_sweeps."""
+    L = lib()
+    ptr, col, val = _csr64(csr)
+    per = np.zeros(S, np.float32)
+    d = C.c_double()
+    st = np.ascontiguousarray(start_state, np.int32)
+    sp = np.ascontiguousarray(start_prob, np.float32)
+    assert len(st) == len(sp) >= 1
+    rc = L.oracle_diameter_episodic(S, A, H, ptr, col, val, len(st), st, sp, eps, int(use_running_max), max_sweeps,
+                                    _ptr(per), C.byref(d))
+    return float(d.value), per, int(rc)
+
+
 def value_norm(S, A, csr, V):
     ptr, col, val = _csr64(csr)
     return float(lib().oracle_value_norm(S, A, ptr, col, val, np.ascontiguousarray(V, np.float32)))
