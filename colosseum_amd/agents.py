@@ -331,16 +331,10 @@ class BatchedUCRL2Continuous(_ParkAndSolveAgent):
         L.check(self._lib.cmdp_ucrl2_set_option(self._h, L.UCRL2_OPT_MAX_SWEEPS, int(n)))
 
 
-class BatchedPSRLEpisodic(_ParkAndSolveAgent):
-    """One reference `PSRLEpisodic` (colosseum/agent/agents/episodic/posterior_sampling.py) per instance of an episodic
-    `BatchedMDP`, driven as `MDPLoop.run` drives it: interaction, the N_NIG / M_DIR posterior tables, the posterior sample,
-    the solve (k_vi_episodic_dense) and the actor's Q stay on the device (kernel K12, csrc/cmdp_psrl.h).  The keyword
-    names and defaults are the reference's.  `sampler="reference"` draws the reference's own numbers (numpy's legacy
-    samplers on the host, one RandomState(seed) per conjugate model); `sampler="philox"` draws on the device: the same
-    distributions from a counter-based stream, a pure function of (seed, episode, tables).  Per-pair prior lists, the
-    N_N reward model and the exploration actors are refused."""
+class _PosteriorSamplingAgent(_ParkAndSolveAgent):
+    """What the two PSRL agents share: the BayesianMDPModel's priors as the library takes them (one N_NIG parameter list and
+    one M_DIR prior per instance), the samplers, episode_end_update() and the MAP estimate."""
 
-    _DESTROY, _PREFIX = "cmdp_psrl_destroy", "cmdp_psrl"
     _STATS = (("rounds", L.STAT_PSRL_ROUNDS), ("solves", L.STAT_PSRL_SOLVES), ("sample_kernel_ms", L.STAT_PSRL_SAMPLE_KERNEL_MS),
               ("vi_kernel_ms", L.STAT_PSRL_VI_KERNEL_MS), ("reference_ms", L.STAT_PSRL_REFERENCE_MS),
               ("policy_kernel_ms", L.STAT_PSRL_POLICY_KERNEL_MS))
@@ -384,10 +378,37 @@ class BatchedPSRLEpisodic(_ParkAndSolveAgent):
         else:
             tprior = np.full(env.B, np.tile(transitions_prior_prms, (1, 1, 1)).astype(np.float32)[0, 0, 0], np.float32)
         self._h = C.c_void_p()
-        L.check(self._lib.cmdp_psrl_create(C.byref(self._h), env._h, L.ptr(seeds), int(optimization_horizon), L.ptr(rprior),
-                                           L.ptr(tprior), self._SAMPLERS[sampler], L.ACTOR_GREEDY))
+        L.check(getattr(self._lib, self._PREFIX + "_create")(C.byref(self._h), env._h, L.ptr(seeds), int(optimization_horizon),
+                                                             L.ptr(rprior), L.ptr(tprior), self._SAMPLERS[sampler], L.ACTOR_GREEDY))
         env._register_agent(self)
         self._fetch_layout()
+
+    def episode_end_update(self):
+        """The reference agent's `episode_end_update()` for every instance: a new posterior sample on the tables as they are,
+        its solve and the new Q; no step is taken, the environment is not reset."""
+        L.check(getattr(self._lib, self._PREFIX + "_episode_end_update")(self._h))
+
+    def map_estimate(self):
+        """BayesianMDPModel.get_map_estimate per instance: (hyper_params / hyper_params.sum(-1, keepdims=True),
+        hyper_params[:, :, 0])."""
+        m = self.model()
+        return [(t / t.sum(-1, keepdims=True), r[:, :, 0]) for t, r in zip(m["transitions"], m["rewards"])]
+
+    def current_optimal_stochastic_policy(self):
+        """The reference agent's `current_optimal_stochastic_policy` per instance: `policy()`."""
+        return self.policy()
+
+
+class BatchedPSRLEpisodic(_PosteriorSamplingAgent):
+    """One reference `PSRLEpisodic` (colosseum/agent/agents/episodic/posterior_sampling.py) per instance of an episodic
+    `BatchedMDP`, driven as `MDPLoop.run` drives it: interaction, the N_NIG / M_DIR posterior tables, the posterior sample,
+    the solve (k_vi_episodic_dense) and the actor's Q stay on the device (kernel K12, csrc/cmdp_psrl.h).  The keyword
+    names and defaults are the reference's.  `sampler="reference"` draws the reference's own numbers (numpy's legacy
+    samplers on the host, one RandomState(seed) per conjugate model); `sampler="philox"` draws on the device: the same
+    distributions from a counter-based stream, a pure function of (seed, episode, tables).  Per-pair prior lists, the
+    N_N reward model and the exploration actors are refused."""
+
+    _DESTROY, _PREFIX = "cmdp_psrl_destroy", "cmdp_psrl"
 
     def run(self, n_steps: int, train=True, trace: bool = False, stop_at_episode_end: bool = False):
         """n_steps of select_action -> step -> step_update -> (episode_end_update, reset) per instance; with
@@ -395,11 +416,6 @@ class BatchedPSRLEpisodic(_ParkAndSolveAgent):
         creation), `steps_taken` [B] and, with `trace`, `actions`, `observations` (after the step; -1 at an episode's last
         step) and float64 `rewards`, each [n_steps, B] with row t of instance b valid for t < steps_taken[b]."""
         return self._run(n_steps, train, trace, stop_at_episode_end)
-
-    def episode_end_update(self):
-        """`PSRLEpisodic.episode_end_update()` for every instance: a new posterior sample on the tables as they are, its
-        solve and the new Q; no step is taken, the environment is not reset."""
-        L.check(self._lib.cmdp_psrl_episode_end_update(self._h))
 
     def model(self):
         """Per instance the reference model's tables: `transitions` dense [S, A, S] float32 (M_DIR.hyper_params) and
@@ -430,12 +446,6 @@ class BatchedPSRLEpisodic(_ParkAndSolveAgent):
             q0 = (H + 1) * int(env.row_off[b])
             Qs.append(Q[q0:q0 + (H + 1) * S * env.A].reshape(H + 1, S, env.A))
         return dict(T=Ts, R=[x.reshape(-1, env.A) for x in env.split_rows(Rs)], Q=Qs)
-
-    def map_estimate(self):
-        """BayesianMDPModel.get_map_estimate per instance: (hyper_params / hyper_params.sum(-1, keepdims=True),
-        hyper_params[:, :, 0])."""
-        m = self.model()
-        return [(t / t.sum(-1, keepdims=True), r[:, :, 0]) for t, r in zip(m["transitions"], m["rewards"])]
 
     def _layers(self, x):
         """A per-instance [H + 1][S][A] array of the library's -> list of [H + 1, S, A]."""
@@ -471,12 +481,127 @@ class BatchedPSRLEpisodic(_ParkAndSolveAgent):
         L.check(self._lib.cmdp_psrl_evaluate(self._h, L.ptr(m), L.ptr(V0)))
         return V0
 
-    def current_optimal_stochastic_policy(self):
-        """posterior_sampling.py:78-82 per instance: `policy()`."""
-        return self.policy()
-
     def stats(self) -> dict:
         """Rounds of parked instances, instances solved in them, HIP-event times of the last round's sample and solve
         kernels, host time of the reference sampler's draws, HIP-event time of K15 in the last policy() / policy_solve() /
         evaluate().  Kept per ENVIRONMENT handle."""
         return self._stats()
+
+
+class BatchedPSRLContinuous(_PosteriorSamplingAgent):
+    """One reference `PSRLContinuous` (colosseum/agent/agents/infinite_horizon/posterior_sampling.py) with PLAIN posterior
+    sampling -- the reference's own `no_optimistic_sampling=True` path -- per instance of a continuous `BatchedMDP`, driven as
+    `MDPLoop.run` drives it: interaction, the N_NIG / M_DIR posterior tables (K12's), the artificial-episode rule, the
+    posterior sample, the solve (k_vi_discounted_dense: the reference's Jacobi / Gauss-Seidel rule per sample) and the actor's
+    Q stay on the device (kernel K13, csrc/cmdp_psrlc.h).  The keyword names and defaults are the reference's; the four weights
+    and `max_psi` only shape optimistic sampling and are accepted and unused, as on the reference's plain path.  Refused, each
+    by name: optimistic sampling (`no_optimistic_sampling=False` unless every instance has S^2 * A > 6 000 000, where the
+    reference switches by itself), `truncate_reward_with_max=True`, `min_steps_before_new_episode != 0`, the exploration
+    actors, and what `BatchedPSRLEpisodic` refuses of the priors.  `run_logged` is not built."""
+
+    _DESTROY, _PREFIX = "cmdp_psrlc_destroy", "cmdp_psrlc"
+    _STATS = _PosteriorSamplingAgent._STATS + (("unconverged", L.STAT_PSRL_UNCONVERGED), ("sweeps", L.STAT_PSRL_SWEEPS))
+
+    def __init__(self, env: BatchedMDP, seeds: Sequence[int], optimization_horizon: int, reward_prior_model=None,
+                 transitions_prior_model=None, rewards_prior_prms=None, transitions_prior_prms=None, epsilon_greedy=None,
+                 boltzmann_temperature=None, psi_weight=1.0, omega_weight=1.0, kappa_weight=1.0, eta_weight=1.0, p=0.05,
+                 no_optimistic_sampling=False, truncate_reward_with_max=False, min_steps_before_new_episode=0, max_psi=60,
+                 sampler="reference"):
+        # posterior_sampling.py:272-275: the reference takes the plain path by itself for large instances
+        plain = no_optimistic_sampling or all(int(S) ** 2 * env.A > 6_000_000 for S in env.n_states)
+        if not plain:
+            raise NotImplementedError("optimistic sampling (psi extended actions) is not built: pass no_optimistic_sampling=True "
+                                      "for the reference's plain posterior sampling")
+        if truncate_reward_with_max:
+            raise NotImplementedError("truncate_reward_with_max=True is not built")
+        if min_steps_before_new_episode != 0:
+            raise NotImplementedError("min_steps_before_new_episode != 0 is not built")
+        super().__init__(env, seeds, optimization_horizon, reward_prior_model=reward_prior_model,
+                         transitions_prior_model=transitions_prior_model, rewards_prior_prms=rewards_prior_prms,
+                         transitions_prior_prms=transitions_prior_prms, epsilon_greedy=epsilon_greedy,
+                         boltzmann_temperature=boltzmann_temperature, sampler=sampler)
+
+    def run(self, n_steps: int, train=True, trace: bool = False, stop_at_episode_end: bool = False):
+        """n_steps of select_action -> step -> step_update -> (episode_end_update) per instance; the environment is never
+        reset.  With `stop_at_episode_end` every instance stops after its next episode_end_update.  Returns as
+        `BatchedPSRLEpisodic.run` (observations are never -1)."""
+        return self._run(n_steps, train, trace, stop_at_episode_end)
+
+    def run_logged(self, desc, n_logs: int):
+        raise NotImplementedError("the logged loop of BatchedPSRLContinuous is not built")
+
+    def model(self):
+        """Per instance the reference's tables: `transitions` dense [S, A, S] float32 (M_DIR.hyper_params), `rewards`
+        [S, A, 4] float32 (N_NIG.hyper_params), `N_sa` [S, A] int32 (N.sum(-1)), `nu_k` [S, A] int32 (visits since the last
+        episode_end_update); `episode` [B]: posterior samples drawn so far."""
+        env = self.env
+        R = int(env.row_off[-1])
+        rp, tp = np.zeros(R * 4, np.float32), np.zeros(self._nz, np.float32)
+        prior, ep = np.zeros(env.B, np.float32), np.zeros(env.B, np.int64)
+        nsa, nu = np.zeros(R, np.int32), np.zeros(R, np.int32)
+        L.check(self._lib.cmdp_psrlc_model(self._h, L.ptr(rp), L.ptr(tp), L.ptr(prior), L.ptr(nsa), L.ptr(nu), L.ptr(ep)))
+        sa = lambda x: [y.reshape(-1, env.A) for y in env.split_rows(x)]  # noqa: E731
+        return dict(transitions=self._dense(tp, np.float32, fill=prior),
+                    rewards=[x.reshape(-1, env.A, 4) for x in env.split_rows(rp.reshape(R, 4))], N_sa=sa(nsa), nu_k=sa(nu),
+                    episode=ep)
+
+    def last_sample(self):
+        """The last posterior sample of every instance, `T` [S, A, S] and `R` [S, A] float32, the `Q` [S, A] the actor holds
+        (solved on them), and of that solve `sweeps`, `scheme` (L.SCHEME_JACOBI / L.SCHEME_GAUSS_SEIDEL) and `status`
+        (0, or L.ERR_MAX_ITER: Q is then the last sweep's) [B]."""
+        env = self.env
+        R = int(env.row_off[-1])
+        nT = int(sum(int(S) * env.A * int(S) for S in env.n_states))
+        T, Rs, Q = np.zeros(nT, np.float32), np.zeros(R, np.float32), np.zeros(R, np.float32)
+        sweeps, scheme, status = np.zeros(env.B, np.int64), np.zeros(env.B, np.int32), np.zeros(env.B, np.int32)
+        L.check(self._lib.cmdp_psrlc_last_sample(self._h, L.ptr(T), L.ptr(Rs), L.ptr(Q), L.ptr(sweeps), L.ptr(scheme),
+                                                 L.ptr(status)))
+        Ts, o = [], 0
+        for b in range(env.B):
+            S = int(env.n_states[b])
+            Ts.append(T[o:o + S * env.A * S].reshape(S, env.A, S))
+            o += S * env.A * S
+        sa = lambda x: [y.reshape(-1, env.A) for y in env.split_rows(x)]  # noqa: E731
+        return dict(T=Ts, R=sa(Rs), Q=sa(Q), sweeps=sweeps, scheme=scheme, status=status)
+
+    def policy(self, mask=None):
+        """posterior_sampling.py:174-178 on the device: argmax_2d (RandomState(42) tie-break) of discounted value iteration
+        on the MAP estimate of the model, per instance [S, A]; with `mask`, for the selected instances only, in their order.
+        Touches nothing the agent acts or learns with."""
+        env = self.env
+        m, sel = self._mask(mask)
+        pi = np.zeros(int(env.row_off[-1]), np.float32)
+        L.check(self._lib.cmdp_psrlc_policy(self._h, L.ptr(m), L.ptr(pi), None, None, None))
+        rows = env.split_rows(pi)
+        return [rows[b].reshape(-1, env.A) for b in sel]
+
+    def policy_solve(self, mask=None):
+        """The solve behind `policy()`: `Q` per instance [S, A] float32, `sweeps` and `scheme` [B]; with `mask`, zeros
+        elsewhere."""
+        env = self.env
+        m, _ = self._mask(mask)
+        Q = np.zeros(int(env.row_off[-1]), np.float32)
+        sweeps, scheme = np.zeros(env.B, np.int64), np.zeros(env.B, np.int32)
+        L.check(self._lib.cmdp_psrlc_policy(self._h, L.ptr(m), None, L.ptr(Q), L.ptr(sweeps), L.ptr(scheme)))
+        return dict(Q=[x.reshape(-1, env.A) for x in env.split_rows(Q)], sweeps=sweeps, scheme=scheme)
+
+    def average_reward(self, mask=None) -> list:
+        """`get_average_reward` of `policy()` from the environments' current states, on the device: a list of numpy scalars
+        (np.float32 where the reference's value is one) for the instances selected by `mask`."""
+        m, sel = self._mask(mask)
+        avg, kind = np.zeros(self.env.B, np.float64), np.zeros(self.env.B, np.int32)
+        L.check(self._lib.cmdp_psrlc_average_reward(self._h, L.ptr(m), L.ptr(avg), L.ptr(kind)))
+        return [np.float32(avg[b]) if kind[b] else np.float64(avg[b]) for b in sel]
+
+    def stats(self) -> dict:
+        """As `BatchedPSRLEpisodic.stats`, with `unconverged` (solves that reached the sweep limit; the actor then holds the
+        last sweep's Q) and `sweeps` (of the last round's solves, summed)."""
+        return self._stats()
+
+    def _set_size_threshold(self, n: int):
+        """Test hook: the size threshold of the scheme rule in the agent's solves (the reference's default 300 * 3 * 300)."""
+        L.check(self._lib.cmdp_psrlc_set_option(self._h, L.PSRLC_OPT_SIZE_THRESHOLD, int(n)))
+
+    def _set_max_sweeps(self, n: int):
+        """Test hook: the sweeps a solve may take (the reference's DP_MAX_ITERATION = 10^6)."""
+        L.check(self._lib.cmdp_psrlc_set_option(self._h, L.PSRLC_OPT_MAX_SWEEPS, int(n)))

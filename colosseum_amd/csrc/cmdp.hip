@@ -41,6 +41,7 @@ extern char** environ;
 #include "cmdp_model_vi.h"
 #include "cmdp_ucrl2.h"
 #include "cmdp_psrl.h"
+#include "cmdp_psrlc.h"
 #include "cmdp_map_vi.h"
 
 namespace {
@@ -347,6 +348,7 @@ struct cmdp {
   int64_t ps_rounds = 0, ps_solves = 0;
   double ps_sample_ms = 0.0, ps_vi_ms = 0.0, ps_ref_ms = 0.0;
   double ps_policy_ms = 0.0;   // CMDP_STAT_PSRL_POLICY_KERNEL_MS: the last K15 launch of an agent of this handle
+  DevBuf<unsigned long long> d_ps_tally;   // continuous PSRL (K13): solves that did not converge, sweeps of the last round
   DevBuf<float> d_dense;  // CMDP_LAYOUT_DENSE: [R][dense_spad]
   int dense_spad = 0;
   DevBuf<uint16_t> d_next16;
@@ -1967,6 +1969,15 @@ int cmdp_stat(cmdp_t* h, int which, double* out) {
   }
   if (which == CMDP_STAT_UCRL2_POLICY_SOLVED || which == CMDP_STAT_UCRL2_POLICY_REUSED) {
     *out = (double)(which == CMDP_STAT_UCRL2_POLICY_SOLVED ? h->uc_policy_solved : h->uc_policy_reused);
+    return CMDP_OK;
+  }
+  if (which == CMDP_STAT_PSRL_UNCONVERGED || which == CMDP_STAT_PSRL_SWEEPS) {
+    unsigned long long n[2] = {0, 0};
+    if (h->d_ps_tally.p) {
+      HIP_TRY(hipMemcpyAsync(n, h->d_ps_tally.p, sizeof n, hipMemcpyDeviceToHost, h->stream));
+      HIP_TRY(hipStreamSynchronize(h->stream));
+    }
+    *out = (double)n[which == CMDP_STAT_PSRL_UNCONVERGED ? 0 : 1];
     return CMDP_OK;
   }
   if (which == CMDP_STAT_UCRL2_UNCONVERGED) {
@@ -4925,9 +4936,9 @@ void psrl_times(cmdp_psrl_t* a) {   // after a stream synchronisation: the last 
   (void)hipGetLastError();
 }
 
-// sample -> solve (straight into the actor's Q) -> reset -> release for the `count` instances of pin_park's list (already on
-// the device at d_park + 2)
-int psrl_round(cmdp_psrl_t* a, int count, int do_reset, int stop, int64_t n_steps) {
+// The posterior sample of the `count` instances of pin_park's list (already on the device at d_park + 2) into d_T / d_Rs:
+// what a round of the episodic and of the continuous agent begins with
+int psrl_sample(cmdp_psrl_t* a, int count) {
   cmdp_t* h = a->env;
   hipStream_t st = h->stream;
   const int A = h->A;
@@ -4963,6 +4974,16 @@ int psrl_round(cmdp_psrl_t* a, int count, int do_reset, int stop, int64_t n_step
       HIP_TRY(hipMemcpyAsync(a->d_Rs.p + soff * A, a->h_R.data() + soff * A, sizeof(float) * S * A, hipMemcpyHostToDevice, st));
     }
   }
+  return CMDP_OK;
+}
+
+// sample -> solve (straight into the actor's Q) -> reset -> release for the `count` instances of pin_park's list (already on
+// the device at d_park + 2)
+int psrl_round(cmdp_psrl_t* a, int count, int do_reset, int stop, int64_t n_steps) {
+  cmdp_t* h = a->env;
+  hipStream_t st = h->stream;
+  const int32_t* list = a->d_park.p + 2;
+  if (int rc = psrl_sample(a, count)) return rc;
   DviArgs g{list, a->d_S.p, a->d_A.p, a->d_toff.p, a->d_roff.p, h->d_state_off.p, a->d_T.p, a->d_Rs.p, a->d_Q.p, a->d_V.p, h->H};
   HIP_TRY(hipEventRecord(a->ev[2], st));
   if (int rc = dvi_launch(g, count, a->vi_lds, st)) return rc;
@@ -4976,23 +4997,24 @@ int psrl_round(cmdp_psrl_t* a, int count, int do_reset, int stop, int64_t n_step
   return CMDP_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int cmdp_psrl_create(cmdp_psrl_t** out, cmdp_t* env, const int32_t* seeds, int64_t optimization_horizon,
-                     const float* reward_prior, const float* transition_prior, int sampler, int actor) {
-  if (!out) return fail(CMDP_ERR_INVALID, "null output");
-  *out = nullptr;
+// What the creates of both PSRL agents (K12 episodic, K13 continuous) refuse of their arguments, up to binding the handle
+int psrl_create_check(cmdp_t* env, const int32_t* seeds, int64_t optimization_horizon, const float* reward_prior,
+                      const float* transition_prior, int sampler, int actor) {
   if (sampler != CMDP_PSRL_SAMPLER_REFERENCE && sampler != CMDP_PSRL_SAMPLER_PHILOX)
     return fail(CMDP_ERR_INVALID, "sampler %d: CMDP_PSRL_SAMPLER_REFERENCE or CMDP_PSRL_SAMPLER_PHILOX", sampler);
   if (int rc = agent_check_actor(actor)) return rc;
   if (!env || !seeds || !reward_prior || !transition_prior)
     return fail(CMDP_ERR_INVALID, "null argument (environment handle, seeds or priors)");
   if (optimization_horizon < 1) return fail(CMDP_ERR_INVALID, "optimization_horizon < 1");
-  if (int rc = bind(env)) return rc;
-  if (int rc = park_check_env(env, true, "PSRLEpisodic is the episodic setting's agent (PSRLContinuous is not built): the "
-                              "environment handle is continuous", "PSRL", "the dense solver (K12)", PSRL_MAX_STATES)) return rc;
+  return bind(env);
+}
+
+// ... and what both build after park_check_env: the priors' checks, the model's layout, the posterior tables, the dense
+// workspace of the sample, the actor's Q ([H + 1] layers; continuous: one) and stream, the samplers' state.  a->env and
+// a->sampler are set.
+int psrl_build(cmdp_psrl_t* a, const int32_t* seeds, const float* reward_prior, const float* transition_prior) {
+  cmdp_t* env = a->env;
+  const int sampler = a->sampler;
   const int B = env->B, A = env->A, H = env->H;
   const int64_t R = env->n_rows;
   if ((int64_t)env->max_S * A * env->max_S > 0xffffffffLL)
@@ -5006,10 +5028,6 @@ int cmdp_psrl_create(cmdp_psrl_t** out, cmdp_t* env, const int32_t* seeds, int64
       return fail(CMDP_ERR_INVALID, "reward_prior[%d]: mu finite, lambda, alpha and beta finite and > 0", b);
   }
   hipStream_t st = env->stream;
-  cmdp_psrl_t* a = new cmdp_psrl;
-  std::unique_ptr<cmdp_psrl> guard(a);
-  a->env = env;
-  a->sampler = sampler;
   if (int rc = build_model_layout(a, a->h_ptr, a->h_col)) return rc;
   const int64_t NZ = a->nz;
   std::vector<float> tp((size_t)NZ);   // the prior at every position of the instance's rows
@@ -5069,10 +5087,30 @@ int cmdp_psrl_create(cmdp_psrl_t** out, cmdp_t* env, const int32_t* seeds, int64
   p.t_off = a->d_toff.p; p.T = a->d_T.p; p.Rs = a->d_Rs.p; p.Q = a->d_Q.p; p.V = a->d_V.p;
   p.mt = a->d_mt.p; p.mt_pos = a->d_mtpos.p;
   p.call = a->call();
+  return CMDP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int cmdp_psrl_create(cmdp_psrl_t** out, cmdp_t* env, const int32_t* seeds, int64_t optimization_horizon,
+                     const float* reward_prior, const float* transition_prior, int sampler, int actor) {
+  if (!out) return fail(CMDP_ERR_INVALID, "null output");
+  *out = nullptr;
+  if (int rc = psrl_create_check(env, seeds, optimization_horizon, reward_prior, transition_prior, sampler, actor)) return rc;
+  if (int rc = park_check_env(env, true, "PSRLEpisodic is the episodic setting's agent: the environment handle is continuous "
+                              "(cmdp_psrlc_create builds PSRLContinuous with plain posterior sampling)", "PSRL",
+                              "the dense solver (K12)", PSRL_MAX_STATES)) return rc;
+  cmdp_psrl_t* a = new cmdp_psrl;
+  std::unique_ptr<cmdp_psrl> guard(a);
+  a->env = env;
+  a->sampler = sampler;
+  if (int rc = psrl_build(a, seeds, reward_prior, transition_prior)) return rc;
   // before_start_interacting (posterior_sampling.py:146-147): one episode_end_update on the prior -- every instance
   if (int rc = park_all(a)) return rc;
-  if (int rc = psrl_round(a, B, 0, 0, 0)) return rc;
-  HIP_TRY(hipStreamSynchronize(st));
+  if (int rc = psrl_round(a, env->B, 0, 0, 0)) return rc;
+  HIP_TRY(hipStreamSynchronize(env->stream));
   psrl_times(a);
   return agent_attach(guard, out);
 }
@@ -5383,6 +5421,353 @@ int cmdp_psrl_evaluate(cmdp_psrl_t* a, const uint8_t* mask, float* V0) {
     return rc;
   HIP_TRY(hipStreamSynchronize(st));
   return psrl_map_time(a);
+}
+
+}  // extern "C"
+
+// ---- PSRL for the continuous setting, plain posterior sampling (K13, cmdp_psrlc.h) ---------------------------------------
+// The posterior tables, the samplers and their state are the episodic agent's (psrl_build, psrl_sample); H = 0 here, so its Q
+// and V are the one layer [S][A] / [S] the actor and the solver share.
+struct cmdp_psrlc : cmdp_psrl {
+  int64_t size_threshold = 300 * 3 * 300;   // the reference's defaults (infinite_horizon.py:20-21)
+  double density_threshold = 0.2;
+  int64_t max_sweeps = 1000000;             // DP_MAX_ITERATION of the reference
+  PcCounters cnt{};
+  DevBuf<int32_t> d_nsa, d_nu, d_stamp, d_scheme, d_status;
+  DevBuf<int64_t> d_sweeps;
+  // the MAP-policy solve (cmdp_psrlc_policy / cmdp_psrlc_average_reward): buffers of its own, allocated by the first call;
+  // the list and the events are d_mlist and m_ev of the base
+  DevBuf<float> d_Tmap, d_Rmap, d_mrs, d_pQ, d_pV, d_ppi;
+  DevBuf<int32_t> d_pscheme, d_pstatus;
+  DevBuf<int64_t> d_psweeps;
+};
+
+namespace {
+
+// Host-only picker of k_vi_discounted_dense's form: how many wavefronts share an instance.  The results do not depend on it
+// (cmdp_psrlc.h); CMDP_DDV_WAVES=1 forces the single wavefront for measurements.
+int ddv_waves() {
+  const char* e = std::getenv("CMDP_DDV_WAVES");
+  return e && e[0] == '1' && e[1] == '\0' ? 1 : DDV_MAX_WAVES;
+}
+
+// K13's solver on device-resident arguments: what cmdp_vi_discounted_dense does after its uploads and what the continuous
+// PSRL agent does for the instances of a round
+int ddv_launch(const DdvArgs& g, int count, int max_S, hipStream_t st) {
+  if (count == 0) return CMDP_OK;
+  const size_t lds = ddv_lds_bytes(max_S);
+  if (ddv_waves() == 1) {
+    if (int rc = set_lds(k_vi_discounted_dense<1>, lds)) return rc;
+    hipLaunchKernelGGL(k_vi_discounted_dense<1>, dim3(count), dim3(64), lds, st, g);
+  } else {
+    if (int rc = set_lds(k_vi_discounted_dense<DDV_MAX_WAVES>, lds)) return rc;
+    hipLaunchKernelGGL(k_vi_discounted_dense<DDV_MAX_WAVES>, dim3(count), dim3(DDV_MAX_WAVES * 64), lds, st, g);
+  }
+  HIP_TRY(hipGetLastError());
+  return CMDP_OK;
+}
+
+// sample -> solve (straight into the actor's Q) -> tally -> release for the `count` instances of pin_park's list (already on
+// the device at d_park + 2).  The environment is not reset.  An instance that does not converge keeps the last sweep's Q.
+int psrlc_round(cmdp_psrlc_t* a, int count, int stop, int64_t n_steps) {
+  cmdp_t* h = a->env;
+  hipStream_t st = h->stream;
+  const int32_t* list = a->d_park.p + 2;
+  if (int rc = psrl_sample(a, count)) return rc;
+  DdvArgs g{list, a->d_S.p, a->d_A.p, a->d_toff.p, a->d_roff.p, h->d_state_off.p, a->d_T.p, a->d_Rs.p, 0.99f, 1e-3,
+            CMDP_SCHEME_AUTO, a->size_threshold, a->density_threshold, a->max_sweeps, a->d_Q.p, a->d_V.p, a->d_sweeps.p,
+            a->d_scheme.p, a->d_status.p};
+  HIP_TRY(hipEventRecord(a->ev[2], st));
+  if (int rc = ddv_launch(g, count, h->max_S, st)) return rc;
+  HIP_TRY(hipEventRecord(a->ev[3], st));
+  a->ev_vi = true;
+  HIP_TRY(hipMemsetAsync(h->d_ps_tally.p + 1, 0, sizeof(unsigned long long), st));
+  hipLaunchKernelGGL(k_psrlc_tally, dim3(grid_for(count, 256)), dim3(256), 0, st, list, count, a->d_status.p, a->d_sweeps.p,
+                     h->d_ps_tally.p);
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(k_psrl_resume, dim3(grid_for(count, 256)), dim3(256), 0, st, h->env(), a->args, list, count, 0, stop, n_steps);
+  HIP_TRY(hipGetLastError());
+  h->ps_rounds += 1;
+  h->ps_solves += count;
+  return CMDP_OK;
+}
+
+int psrlc_bind(cmdp_psrlc_t* a) {
+  if (!a) return fail(CMDP_ERR_INVALID, "null agent");
+  return bind(a->env);
+}
+
+}  // namespace
+
+extern "C" {
+
+int cmdp_psrlc_create(cmdp_psrlc_t** out, cmdp_t* env, const int32_t* seeds, int64_t optimization_horizon,
+                      const float* reward_prior, const float* transition_prior, int sampler, int actor) {
+  if (!out) return fail(CMDP_ERR_INVALID, "null output");
+  *out = nullptr;
+  if (int rc = psrl_create_check(env, seeds, optimization_horizon, reward_prior, transition_prior, sampler, actor)) return rc;
+  if (int rc = park_check_env(env, false, "PSRLContinuous is the continuous setting's agent: the environment handle is episodic "
+                              "(horizon %d; cmdp_psrl_create builds PSRLEpisodic)", "PSRLContinuous", "the dense solver (K13)",
+                              PSRL_MAX_STATES)) return rc;
+  cmdp_psrlc_t* a = new cmdp_psrlc;
+  std::unique_ptr<cmdp_psrlc> guard(a);
+  a->env = env;
+  a->sampler = sampler;
+  if (int rc = psrl_build(a, seeds, reward_prior, transition_prior)) return rc;
+  hipStream_t st = env->stream;
+  const int B = env->B;
+  const int64_t R = env->n_rows;
+  AGENT_ZERO(d_nsa, R); AGENT_ZERO(d_nu, R); AGENT_ZERO(d_stamp, R);
+  AGENT_ZERO(d_scheme, B); AGENT_ZERO(d_status, B); AGENT_ZERO(d_sweeps, B);
+  a->cnt = PcCounters{a->d_nsa.p, a->d_nu.p, a->d_stamp.p};
+  if (!env->d_ps_tally.p) {
+    HIP_TRY(env->d_ps_tally.alloc(2));
+    HIP_TRY(env->d_ps_tally.zero(st));
+  }
+  // before_start_interacting (infinite_horizon/posterior_sampling.py:379-383): one episode_end_update on the prior
+  if (int rc = park_all(a)) return rc;
+  if (int rc = psrlc_round(a, B, 0, 0)) return rc;
+  HIP_TRY(hipStreamSynchronize(st));
+  psrl_times(a);
+  return agent_attach(guard, out);
+}
+
+int cmdp_psrlc_destroy(cmdp_psrlc_t* a) { return agent_destroy(a); }
+
+int cmdp_psrlc_run(cmdp_psrlc_t* a, int64_t n_steps, int stop_at_episode_end, const uint8_t* train_mask, int8_t* actions_trace,
+                   int32_t* obs_trace, double* reward_trace, double* cumulative_reward, int64_t* steps_taken) {
+  if (int rc = park_run_check(a, n_steps, 1LL << 24, "a transition count of the model (float32, as the reference's "
+                              "hyper-parameters) would stop counting at 2^24: instance %d has taken %lld steps, %lld more asked for"))
+    return rc;
+  cmdp_t* h = a->env;
+  const int stop = stop_at_episode_end ? 1 : 0;
+  const int rc = park_run(
+      a, n_steps, stop, train_mask, actions_trace, obs_trace, reward_trace, cumulative_reward, steps_taken,
+      [&](const uint8_t* dmask, int8_t* act, int32_t* obs, double* rew) {
+        hipLaunchKernelGGL(k_psrlc_walk, dim3(grid_for(h->B, 256)), dim3(256), 0, h->stream, h->env(), a->args, a->cnt, n_steps,
+                           dmask, act, obs, rew, a->d_rsum.p);
+      },
+      [&]() -> int { psrl_times(a); return CMDP_OK; }, [&](int count) { return psrlc_round(a, count, stop, n_steps); });
+  psrl_times(a);   // after the call's last synchronisation
+  return rc;
+}
+
+int cmdp_psrlc_episode_end_update(cmdp_psrlc_t* a) {
+  if (int rc = psrlc_bind(a)) return rc;
+  cmdp_t* h = a->env;
+  if (int rc = park_all(a)) return rc;
+  if (int rc = psrlc_round(a, h->B, 0, 0)) return rc;
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  psrl_times(a);
+  return CMDP_OK;
+}
+
+int cmdp_psrlc_layout(cmdp_psrlc_t* a, int64_t* n_positions, int64_t* row_ptr, int32_t* col) {
+  return park_layout(a, n_positions, row_ptr, col);
+}
+
+int cmdp_psrlc_set_option(cmdp_psrlc_t* a, int option, int64_t value) {
+  if (int rc = psrlc_bind(a)) return rc;
+  if (option == CMDP_PSRLC_OPT_SIZE_THRESHOLD) {
+    if (value < 0) return fail(CMDP_ERR_INVALID, "the size threshold of the scheme rule must be >= 0");
+    a->size_threshold = value;
+    return CMDP_OK;
+  }
+  if (option == CMDP_PSRLC_OPT_MAX_SWEEPS) {
+    if (value < 1) return fail(CMDP_ERR_INVALID, "max_sweeps %lld < 1", (long long)value);
+    a->max_sweeps = value;
+    return CMDP_OK;
+  }
+  return fail(CMDP_ERR_INVALID, "unknown option %d", option);
+}
+
+int cmdp_psrlc_model(cmdp_psrlc_t* a, float* reward_hp, float* transition_hp, float* transition_prior, int32_t* n_sa,
+                     int32_t* nu_k, int64_t* episodes) {
+  if (int rc = psrlc_bind(a)) return rc;
+  cmdp_t* h = a->env;
+  const int64_t R = h->n_rows;
+  std::vector<int32_t> stamp(nu_k ? (size_t)R : 0);
+  std::vector<int64_t> ep((size_t)h->B);
+  AGENT_FETCH(reward_hp, d_rp, 4 * R); AGENT_FETCH(transition_hp, d_tp, a->nz); AGENT_FETCH(n_sa, d_nsa, R); AGENT_FETCH(nu_k, d_nu, R);
+  if (nu_k) HIP_TRY(hipMemcpyAsync(stamp.data(), a->d_stamp.p, sizeof(int32_t) * R, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipMemcpyAsync(ep.data(), a->d_episode.p, sizeof(int64_t) * h->B, hipMemcpyDeviceToHost, h->stream));
+  if (transition_prior) std::memcpy(transition_prior, a->h_prior.data(), sizeof(float) * h->B);
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  if (nu_k)   // a count written in an earlier episode is 0 now (cmdp_psrlc.h)
+    for (int b = 0; b < h->B; ++b)
+      for (int64_t r = h->state_off[b] * h->A; r < h->state_off[b + 1] * h->A; ++r)
+        if (stamp[(size_t)r] != (int32_t)ep[b]) nu_k[r] = 0;
+  if (episodes) std::memcpy(episodes, ep.data(), sizeof(int64_t) * h->B);
+  return CMDP_OK;
+}
+
+int cmdp_psrlc_last_sample(cmdp_psrlc_t* a, float* T, float* R, float* Q, int64_t* sweeps, int32_t* scheme, int32_t* status) {
+  if (int rc = psrlc_bind(a)) return rc;
+  cmdp_t* h = a->env;
+  hipStream_t st = h->stream;
+  if (T) {
+    int64_t o = 0;
+    for (int b = 0; b < h->B; ++b) {   // the workspace pads every instance to 16 bytes; the caller's array is dense
+      const int64_t S = h->state_off[b + 1] - h->state_off[b], n = S * h->A * S;
+      HIP_TRY(hipMemcpyAsync(T + o, a->d_T.p + a->h_toff[b], sizeof(float) * n, hipMemcpyDeviceToHost, st));
+      o += n;
+    }
+  }
+  AGENT_FETCH(R, d_Rs, h->n_rows); AGENT_FETCH(Q, d_Q, h->n_rows); AGENT_FETCH(sweeps, d_sweeps, h->B);
+  AGENT_FETCH(scheme, d_scheme, h->B); AGENT_FETCH(status, d_status, h->B);
+  HIP_TRY(hipStreamSynchronize(st));
+  return CMDP_OK;
+}
+
+// discounted_value_iteration(*get_map_estimate()) and argmax_2d for the instances of `mask` on the handle's stream: the dense
+// MAP model into d_Tmap / d_Rmap (k_psrlc_map_fill), K13's solver on it, the greedy policy of its Q in d_ppi.  Reads nothing
+// but the model and writes nothing of the agent's but these buffers: the last sample and the actor's Q stay what they were.
+// Returns after the stream has drained, with the instances it solved in `sel`; CMDP_ERR_MAX_ITER when one did not converge.
+static int psrlc_policy_solve(cmdp_psrlc_t* a, const uint8_t* mask, std::vector<int32_t>& sel) {
+  cmdp_t* h = a->env;
+  hipStream_t st = h->stream;
+  const int B = h->B;
+  const int64_t R = h->n_rows;
+  if (!a->d_pQ.p) {
+    if (a->d_Tmap.alloc((size_t)a->t_total) != hipSuccess) {
+      (void)hipGetLastError();
+      return fail(CMDP_ERR_OVERFLOW, "the dense workspace of the MAP models cannot be allocated: %lld bytes for the batch",
+                  (long long)(a->t_total * 4));
+    }
+    HIP_TRY(a->d_Rmap.alloc((size_t)R)); HIP_TRY(a->d_mrs.alloc((size_t)R)); HIP_TRY(a->d_pV.alloc((size_t)h->n_states));
+    HIP_TRY(a->d_ppi.alloc((size_t)R)); HIP_TRY(a->d_psweeps.alloc((size_t)B)); HIP_TRY(a->d_pscheme.alloc((size_t)B));
+    HIP_TRY(a->d_pstatus.alloc((size_t)B)); HIP_TRY(a->d_mlist.alloc((size_t)B));
+    for (hipEvent_t& e : a->m_ev) HIP_TRY(hipEventCreate(&e));
+    HIP_TRY(a->d_pQ.alloc((size_t)R));
+  }
+  sel.clear();
+  for (int b = 0; b < B; ++b)
+    if (!mask || mask[b]) sel.push_back(b);
+  const int32_t* list = nullptr;
+  if (mask) {
+    HIP_TRY(a->d_pQ.zero(st));   // the greedy kernel walks every instance: those outside the mask keep no Q of an earlier call
+    HIP_TRY(a->d_psweeps.zero(st)); HIP_TRY(a->d_pscheme.zero(st)); HIP_TRY(a->d_pstatus.zero(st));
+    HIP_TRY(a->d_mlist.upload(sel.data(), sel.size(), st));
+    list = a->d_mlist.p;
+  }
+  const int count = (int)sel.size();
+  HIP_TRY(hipEventRecord(a->m_ev[0], st));
+  if (count > 0) {
+    PcMapArgs m{list, a->d_S.p, a->d_A.p, a->d_roff.p, a->d_toff.p, a->d_row_ptr.p, a->d_col.p, a->d_tp.p, a->d_tprior.p, a->d_rp.p,
+                a->d_mrs.p, a->d_Tmap.p, a->d_Rmap.p};
+    hipLaunchKernelGGL(k_psrlc_map_fill, dim3(count), dim3(MAPVI_THREADS), 0, st, m);
+    HIP_TRY(hipGetLastError());
+    DdvArgs g{list, a->d_S.p, a->d_A.p, a->d_toff.p, a->d_roff.p, h->d_state_off.p, a->d_Tmap.p, a->d_Rmap.p, 0.99f, 1e-3,
+              CMDP_SCHEME_AUTO, a->size_threshold, a->density_threshold, a->max_sweeps, a->d_pQ.p, a->d_pV.p, a->d_psweeps.p,
+              a->d_pscheme.p, a->d_pstatus.p};
+    if (int rc = ddv_launch(g, count, h->max_S, st)) return rc;
+  }
+  HIP_TRY(hipEventRecord(a->m_ev[1], st));
+  hipLaunchKernelGGL(k_greedy_policy_episodic<float>, dim3(B), dim3(64), 0, st, B, h->A, 1, 1, h->d_state_off.p, a->d_pQ.p,
+                     a->d_ppi.p);
+  HIP_TRY(hipGetLastError());
+  std::vector<int32_t> status((size_t)B);
+  HIP_TRY(hipMemcpyAsync(status.data(), a->d_pstatus.p, sizeof(int32_t) * B, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if (int rc = psrl_map_time(a)) return rc;
+  for (int32_t b : sel)
+    if (status[(size_t)b] != 0)
+      return fail(CMDP_ERR_MAX_ITER, "discounted value iteration on the MAP model of instance %d did not converge in %lld sweeps",
+                  (int)b, (long long)a->max_sweeps);
+  return CMDP_OK;
+}
+
+int cmdp_psrlc_policy(cmdp_psrlc_t* a, const uint8_t* mask, float* pi, float* Q, int64_t* sweeps, int32_t* scheme) {
+  if (!a || !a->env) return fail(CMDP_ERR_INVALID, "null agent, or its environment handle has been destroyed");
+  cmdp_t* h = a->env;
+  if (int rc = bind(h)) return rc;
+  std::vector<int32_t> sel;
+  if (int rc = psrlc_policy_solve(a, mask, sel)) return rc;
+  auto span = [&](int b) {
+    return std::make_pair((int64_t)h->state_off[b] * h->A, (int64_t)(h->state_off[b + 1] - h->state_off[b]) * h->A);
+  };
+  if (int rc = psrl_map_fetch(a, sel, pi, a->d_ppi.p, (size_t)h->n_rows, span)) return rc;
+  if (int rc = psrl_map_fetch(a, sel, Q, a->d_pQ.p, (size_t)h->n_rows, span)) return rc;
+  AGENT_FETCH(sweeps, d_psweeps, h->B); AGENT_FETCH(scheme, d_pscheme, h->B);   // zeros outside the mask
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  return CMDP_OK;
+}
+
+int cmdp_psrlc_average_reward(cmdp_psrlc_t* a, const uint8_t* mask, double* avg, int32_t* kind) {
+  if (!a || !a->env || !avg || !kind) return fail(CMDP_ERR_INVALID, "null argument, or the agent's environment handle has been destroyed");
+  cmdp_t* h = a->env;
+  if (int rc = bind(h)) return rc;
+  std::vector<int32_t> sel;
+  if (int rc = psrlc_policy_solve(a, mask, sel)) return rc;
+  return chain_launch(h, a->d_ppi.p, nullptr, h->d_cur.p, mask, avg, kind, nullptr);
+}
+
+int cmdp_vi_discounted_dense(int count, const int32_t* n_states, const int32_t* n_actions, const float* T, const float* R,
+                             float gamma, double epsilon, int scheme, int64_t size_threshold, double density_threshold,
+                             int64_t max_sweeps, float* Q, float* V, int64_t* sweeps, int32_t* scheme_used, int32_t* status) {
+  if (count < 0) return fail(CMDP_ERR_INVALID, "count %d is negative", count);
+  if (count == 0) return CMDP_OK;
+  if (!n_states || !n_actions || !T || !R || !Q || !V || !sweeps || !scheme_used || !status)
+    return fail(CMDP_ERR_INVALID, "null argument");
+  if (!std::isfinite(gamma)) return fail(CMDP_ERR_INVALID, "gamma %g is not finite", (double)gamma);
+  if (!(epsilon >= 0.0) || !std::isfinite(epsilon)) return fail(CMDP_ERR_INVALID, "epsilon %g is not a finite value >= 0", epsilon);
+  if (max_sweeps < 1) return fail(CMDP_ERR_INVALID, "max_sweeps %lld < 1", (long long)max_sweeps);
+  if (scheme != CMDP_SCHEME_AUTO && scheme != CMDP_SCHEME_JACOBI && scheme != CMDP_SCHEME_GAUSS_SEIDEL)
+    return fail(CMDP_ERR_INVALID, "scheme %d: CMDP_SCHEME_AUTO, CMDP_SCHEME_JACOBI or CMDP_SCHEME_GAUSS_SEIDEL", scheme);
+  if (size_threshold < 0) return fail(CMDP_ERR_INVALID, "size_threshold %lld is negative", (long long)size_threshold);
+  if (std::isnan(density_threshold)) return fail(CMDP_ERR_INVALID, "density_threshold is not a number");
+  BatchLayout L;
+  if (int rc = L.build(count, n_states, n_actions,
+                       {PSRL_MAX_STATES, "instance %d has %d states: the dense discounted solver keeps V and V_old in LDS for at "
+                                         "most %d states"}))
+    return rc;
+  const int64_t ns = L.ns, nr = L.nr;
+  std::vector<int64_t> toff((size_t)count), tsrc((size_t)count);   // T[S, A, S] of an instance: padded on the device, packed in T
+  int64_t nt = 0, nsrc = 0;
+  for (int b = 0; b < count; ++b) {
+    toff[b] = nt; tsrc[b] = nsrc;
+    nsrc += L.rows(b) * n_states[b];
+    nt += (L.rows(b) * n_states[b] + 3) & ~(int64_t)3;
+  }
+  for (int64_t i = 0; i < nsrc; ++i)   // a value that is not finite would keep a solve sweeping to max_sweeps
+    if (!std::isfinite(T[i])) return fail(CMDP_ERR_INVALID, "T[%lld] is not finite", (long long)i);
+  for (int64_t i = 0; i < nr; ++i)
+    if (!std::isfinite(R[i])) return fail(CMDP_ERR_INVALID, "R[%lld] is not finite", (long long)i);
+  struct Ws {
+    DevBuf<int32_t> S, A, scheme, status;
+    DevBuf<int64_t> soff, roff, toff, sweeps;
+    DevBuf<float> T, R, Q, V;
+  };
+  DeviceWorkspace<Ws> ws;
+  if (int rc = ws.acquire()) return rc;
+  hipStream_t st = ws.st;
+  HIP_TRY(ws->S.upload(n_states, count, st));
+  HIP_TRY(ws->A.upload(n_actions, count, st));
+  HIP_TRY(ws->soff.upload(L.soff.data(), L.soff.size(), st));
+  HIP_TRY(ws->roff.upload(L.roff.data(), count, st));
+  HIP_TRY(ws->toff.upload(toff.data(), count, st));
+  if (ws->T.alloc((size_t)nt) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(CMDP_ERR_OVERFLOW, "the dense transition models cannot be held on the device: %lld bytes", (long long)(nt * 4));
+  }
+  for (int b = 0; b < count; ++b)
+    HIP_TRY(hipMemcpyAsync(ws->T.p + toff[b], T + tsrc[b], sizeof(float) * (size_t)(L.rows(b) * n_states[b]), hipMemcpyHostToDevice, st));
+  HIP_TRY(ws->R.upload(R, (size_t)nr, st));
+  HIP_TRY(ws->Q.alloc((size_t)nr));
+  HIP_TRY(ws->V.alloc((size_t)ns));
+  HIP_TRY(ws->sweeps.alloc(count));
+  HIP_TRY(ws->scheme.alloc(count));
+  HIP_TRY(ws->status.alloc(count));
+  DdvArgs g{nullptr, ws->S.p, ws->A.p, ws->toff.p, ws->roff.p, ws->soff.p, ws->T.p, ws->R.p, gamma, epsilon, scheme, size_threshold,
+            density_threshold, max_sweeps, ws->Q.p, ws->V.p, ws->sweeps.p, ws->scheme.p, ws->status.p};
+  if (int rc = ddv_launch(g, count, L.max_S, st)) return rc;
+  HIP_TRY(ws->Q.download(Q, (size_t)nr, st));
+  HIP_TRY(ws->V.download(V, (size_t)ns, st));
+  HIP_TRY(ws->sweeps.download(sweeps, count, st));
+  HIP_TRY(ws->scheme.download(scheme_used, count, st));
+  HIP_TRY(ws->status.download(status, count, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return CMDP_OK;
 }
 
 }  // extern "C"

@@ -126,6 +126,29 @@ __device__ inline int mapvi_plan(int n, int* work, short* run, signed char* merg
   }
 }
 
+// numpy's pairwise float32 sum of the dense row `r`: one lane replays the plan of mapvi_plan with its partial sums in registers.
+// K15's prologue and the MAP fill of the continuous PSRL agent (cmdp_psrlc.h) share it.
+__device__ __forceinline__ float mapvi_rowsum(MapViRow& r, int n_runs, const short* plan_run, const signed char* plan_merges) {
+  float st[MAPVI_DEPTH + 1];   // the partial sums waiting for their right-hand halves, st[0] the newest
+#pragma unroll
+  for (int k = 0; k <= MAPVI_DEPTH; ++k) st[k] = 0.0f;
+  int j0 = 0;
+  for (int k = 0; k < n_runs; ++k) {
+    const int n = plan_run[k];
+    const float x = mapvi_run(r, j0, n);
+    j0 += n;
+#pragma unroll
+    for (int d = MAPVI_DEPTH; d > 0; --d) st[d] = st[d - 1];
+    st[0] = x;
+    for (int m = plan_merges[k]; m > 0; --m) {
+      st[0] = __fadd_rn(st[1], st[0]);
+#pragma unroll
+      for (int d = 1; d < MAPVI_DEPTH; ++d) st[d] = st[d + 1];
+    }
+  }
+  return st[0];
+}
+
 __device__ __forceinline__ double mapvi_wave_sum(double x) {
   for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
   return x;
@@ -171,24 +194,7 @@ __global__ void __launch_bounds__(MAPVI_THREADS) k_vi_episodic_map(MapViArgs g) 
   for (int row = tid; row < nrows; row += MAPVI_THREADS) {
     const int64_t zb = ptr[row], ze = ptr[row + 1];
     MapViRow r{col, hp, zb, ze, prior};
-    float st[MAPVI_DEPTH + 1];   // the partial sums waiting for their right-hand halves, st[0] the newest
-#pragma unroll
-    for (int k = 0; k <= MAPVI_DEPTH; ++k) st[k] = 0.0f;
-    int j0 = 0;
-    for (int k = 0; k < n_runs; ++k) {
-      const int n = plan_run[k];
-      const float x = mapvi_run(r, j0, n);
-      j0 += n;
-#pragma unroll
-      for (int d = MAPVI_DEPTH; d > 0; --d) st[d] = st[d - 1];
-      st[0] = x;
-      for (int m = plan_merges[k]; m > 0; --m) {
-        st[0] = __fadd_rn(st[1], st[0]);
-#pragma unroll
-        for (int d = 1; d < MAPVI_DEPTH; ++d) st[d] = st[d + 1];
-      }
-    }
-    const float rowsum = st[0];
+    const float rowsum = mapvi_rowsum(r, n_runs, plan_run, plan_merges);
     const float c = __fdiv_rn(prior, rowsum);
     cmap[row] = c;
     for (int64_t e = zb; e < ze; ++e) tmap[e] = __fdiv_rn(hp[e], rowsum);

@@ -53,6 +53,20 @@ struct PsArgs {
   ParkCall call;           // state of the call
 };
 
+// N_NIG.update_sa for the one-element list [reward] (conjugate_rewards.py:65-82) on the row's (mu, lambda, alpha, beta): n = 1,
+// y_bar = np.mean -> float64, np.var of one sample = 0; the unpacked prior values are np.float32 scalars, the results are
+// stored as float32.  The walks of K12 and K13 share it.
+__device__ __forceinline__ void psrl_nnig_update(float* hp, double reward) {
+  const float mu0 = hp[0], l0 = hp[1], a0 = hp[2], b0 = hp[3];
+  const float l1 = __fadd_rn(l0, 1.0f);                                       // lambda0 + n
+  const double mu1 = ((double)__fmul_rn(l0, mu0) + reward) / (double)l1;      // (lambda0 * mu0 + n * y_bar) / lambda1
+  const float a1 = __fadd_rn(a0, 0.5f);                                       // alpha0 + n * 0.5
+  const double d = reward - (double)mu0;
+  const double pd = __ddiv_rn(__dmul_rn((double)l0, __dmul_rn(d, d)), (double)l1);  // lambda0 * n * (y_bar - mu0)**2 / lambda1
+  const double b1 = (double)b0 + 0.5 * pd;                                    // beta0 + 0.5 * (ssq + prior_disc), ssq = 0.0
+  hp[0] = (float)mu1; hp[1] = l1; hp[2] = a1; hp[3] = (float)b1;
+}
+
 __global__ void __launch_bounds__(256) k_psrl_walk(EnvTables t, PsArgs p, int64_t n_steps, const uint8_t* __restrict__ train_mask,
                                                    int8_t* __restrict__ act_trace, int32_t* __restrict__ obs_trace,
                                                    double* __restrict__ rew_trace, double* __restrict__ cum_reward) {
@@ -95,17 +109,7 @@ __global__ void __launch_bounds__(256) k_psrl_walk(EnvTables t, PsArgs p, int64_
     if (rew_trace) rew_trace[step * t.B + b] = reward;
     --left;
     if (train) {
-      // ---- N_NIG.update_sa for the one-element list [reward] (conjugate_rewards.py:65-82): n = 1, y_bar = np.mean -> float64,
-      // np.var of one sample = 0; the unpacked prior values are np.float32 scalars, the results are stored as float32
-      float* hp = RP + (int64_t)idx * 4;
-      const float mu0 = hp[0], l0 = hp[1], a0 = hp[2], b0 = hp[3];
-      const float l1 = __fadd_rn(l0, 1.0f);                                       // lambda0 + n
-      const double mu1 = ((double)__fmul_rn(l0, mu0) + reward) / (double)l1;      // (lambda0 * mu0 + n * y_bar) / lambda1
-      const float a1 = __fadd_rn(a0, 0.5f);                                       // alpha0 + n * 0.5
-      const double d = reward - (double)mu0;
-      const double pd = __ddiv_rn(__dmul_rn((double)l0, __dmul_rn(d, d)), (double)l1);  // lambda0 * n * (y_bar - mu0)**2 / lambda1
-      const double b1 = (double)b0 + 0.5 * pd;                                    // beta0 + 0.5 * (ssq + prior_disc), ssq = 0.0
-      hp[0] = (float)mu1; hp[1] = l1; hp[2] = a1; hp[3] = (float)b1;
+      psrl_nnig_update(RP + (int64_t)idx * 4, reward);
       // ---- M_DIR.update_sa: hyper_params[s, a, s'] += 1 unless the step was the episode's last (bayesian_model.py:90) ----
       if (ty != 2) {
         float* c = p.tp + p.slot[e];

@@ -111,6 +111,38 @@ def episodic_value_iteration_dense_batch(problems, H):
     return out
 
 
+def discounted_value_iteration_dense_batch(problems, gamma=0.99, epsilon=1e-3, sparse_n_states_threshold=300 * 3 * 300,
+                                           sparse_nnz_per_threshold=0.2, scheme=None, max_sweeps=DP_MAX_ITERATION):
+    """`discounted_value_iteration(T, R)` for many dense (T [S, A, S], R [S, A]) float32 problems in one launch of
+    k_vi_discounted_dense (the continuous PSRL agent's solver; the problems may differ in S and A).  The reference's rule
+    picks Jacobi or Gauss-Seidel per problem from its count of non-zero elements unless `scheme` (L.SCHEME_JACOBI /
+    L.SCHEME_GAUSS_SEIDEL) forces one; the row sums are accumulated in float64 in a fixed order.  A problem that takes
+    `max_sweeps` sweeps returns the last sweep's values.  Returns [(Q [S, A], V [S], sweeps, scheme) per problem]; `status`
+    of the last call (0 or L.ERR_MAX_ITER per problem) is left in `discounted_value_iteration_dense_batch.status`."""
+    problems = [(np.ascontiguousarray(T, np.float32), np.ascontiguousarray(R, np.float32)) for T, R in problems]
+    if not problems:
+        return []
+    S = np.array([T.shape[0] for T, _ in problems], np.int32)
+    A = np.array([T.shape[1] for T, _ in problems], np.int32)
+    for (T, R), s, a in zip(problems, S, A):
+        assert T.shape == (s, a, s) and R.shape == (s, a), (T.shape, R.shape)
+    n = len(problems)
+    Tc = np.concatenate([T.ravel() for T, _ in problems])
+    Rc = np.concatenate([R.ravel() for _, R in problems])
+    Q, V = np.zeros(int((S * A).sum()), np.float32), np.zeros(int(S.sum()), np.float32)
+    sweeps, used, status = np.zeros(n, np.int64), np.zeros(n, np.int32), np.zeros(n, np.int32)
+    L.check(L.load().cmdp_vi_discounted_dense(n, L.ptr(S), L.ptr(A), L.ptr(Tc), L.ptr(Rc), float(gamma), float(epsilon),
+                                              L.SCHEME_AUTO if scheme is None else int(scheme), int(sparse_n_states_threshold),
+                                              float(sparse_nnz_per_threshold), int(max_sweeps), L.ptr(Q), L.ptr(V), L.ptr(sweeps),
+                                              L.ptr(used), L.ptr(status)))
+    discounted_value_iteration_dense_batch.status = status
+    out, q0, v0 = [], 0, 0
+    for b, (s, a) in enumerate(zip(S.tolist(), A.tolist())):
+        out.append((Q[q0:q0 + s * a].reshape(s, a), V[v0:v0 + s], int(sweeps[b]), int(used[b])))
+        q0, v0 = q0 + s * a, v0 + s
+    return out
+
+
 def map_layout_from_dense(transition_hp, prior, keep=None):
     """Table form of dense M_DIR hyper-parameters [S, A, S] over `prior`: the positions that differ from the prior, plus
     those `keep` (bool [S, A, S]) names, per row in ascending column order -> (row_ptr [S * A + 1], col, hp)."""

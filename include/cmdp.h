@@ -304,7 +304,10 @@ enum { CMDP_STAT_DP_KERNEL_MS = 1, CMDP_STAT_DP_KERNEL = 2,
        CMDP_STAT_UCRL2_POLICY_REUSED = 26    /* ... and instances of those requests that kept their stored policy instead
                                                 (CMDP_UCRL2_OPT_POLICY_REUSE)                                                     */,
        CMDP_STAT_ACTIONS_KERNEL_MS = 27      /* CMDP_POLICY_RANDOM_REFERENCE on K1E: HIP-event time, on the handle's stream, of K16
-                                                (k_mt_actions, the action bits) before the walk CMDP_STAT_ROLLOUT_KERNEL_MS times  */ };
+                                                (k_mt_actions, the action bits) before the walk CMDP_STAT_ROLLOUT_KERNEL_MS times  */,
+       CMDP_STAT_PSRL_UNCONVERGED = 28,      /* continuous PSRL agents of this handle (K13): solves that reached max_sweeps; the
+                                                actor then holds the last sweep's Q                                                */
+       CMDP_STAT_PSRL_SWEEPS = 29            /* ... sweeps of the last round's solves, summed over its instances                  */ };
 /* The UCRL2 and PSRL statistics belong to the environment handle: agents created on the same handle share them. */
 int cmdp_stat(cmdp_t* h, int which, double* out);
 /* Latency floor of the LDS-resident rollout kernels, measured on the current device: one wavefront per CU follows
@@ -869,6 +872,62 @@ int cmdp_psrl_evaluate(cmdp_psrl_t* a, const uint8_t* mask, float* V0);
    same refusals; a handle without the DP half or beyond the evaluation's LDS budget is CMDP_ERR_UNSUPPORTED. */
 int cmdp_psrl_run_logged(cmdp_psrl_t* a, const cmdp_loop_desc* desc, int64_t n_logs, int64_t* steps, double* values,
                          uint8_t* kinds, int64_t* last_training_step, uint8_t* is_training);
+
+/* One PSRLContinuous (colosseum/agent/agents/infinite_horizon/posterior_sampling.py) with PLAIN posterior sampling -- the
+   reference's no_optimistic_sampling=True path -- per instance of a CONTINUOUS environment handle, driven as MDPLoop.run
+   drives it (K13, csrc/cmdp_psrlc.h).  Arguments, samplers and refusals as cmdp_psrl_create (an episodic handle is
+   CMDP_ERR_UNSUPPORTED here).  The posterior tables and both samplers are K12's; an artificial episode ends after the step
+   with N[s, a].sum() >= 2 * (N[s, a].sum() - nu_k[s, a]); the solve is discounted_value_iteration(T, R) with gamma = 0.99,
+   epsilon = 1e-3 and the reference's scheme rule per sample (cmdp_vi_discounted_dense).  Creation performs
+   before_start_interacting: the first sample and solve, on the prior.  The statistics are CMDP_STAT_PSRL_*.  Optimistic
+   sampling, truncate_reward_with_max and min_steps_before_new_episode != 0 are not built. */
+typedef struct cmdp_psrlc cmdp_psrlc_t;
+int cmdp_psrlc_create(cmdp_psrlc_t** out, cmdp_t* env, const int32_t* seeds, int64_t optimization_horizon,
+                      const float* reward_prior, const float* transition_prior, int sampler, int actor);
+int cmdp_psrlc_destroy(cmdp_psrlc_t* a);
+/* As cmdp_psrl_run, without resets: an instance whose step ended an artificial episode gets its episode_end_update (sample ->
+   solve -> the new Q) and walks on from where it stands.  train_mask 0 = the instance acts on the Q it holds, updates nothing
+   and never ends an episode.  An instance whose solve reaches max_sweeps keeps the last sweep's Q
+   (CMDP_STAT_PSRL_UNCONVERGED). */
+int cmdp_psrlc_run(cmdp_psrlc_t* a, int64_t n_steps, int stop_at_episode_end, const uint8_t* train_mask, int8_t* actions_trace,
+                   int32_t* obs_trace, double* reward_trace, double* cumulative_reward, int64_t* steps_taken);
+/* PSRLContinuous.episode_end_update() for EVERY instance, outside the loop: sample, solve, the new Q, every nu_k back to 0. */
+int cmdp_psrlc_episode_end_update(cmdp_psrlc_t* a);
+int cmdp_psrlc_layout(cmdp_psrlc_t* a, int64_t* n_positions, int64_t* row_ptr, int32_t* col);
+/* As cmdp_psrl_model, with the agent's visit counters per row: n_sa [R] = N[s, a].sum(), nu_k [R] = visits since the last
+   episode_end_update.  Each may be NULL. */
+int cmdp_psrlc_model(cmdp_psrlc_t* a, float* reward_hp, float* transition_hp, float* transition_prior, int32_t* n_sa,
+                     int32_t* nu_k, int64_t* episodes);
+/* The last posterior sample of every instance, T dense [sum S * A * S] and R [R], the Q [R] the actor holds, and of its solve
+   the sweeps [B], the scheme [B] (CMDP_SCHEME_JACOBI / CMDP_SCHEME_GAUSS_SEIDEL) and the status [B] (0 or CMDP_ERR_MAX_ITER).
+   Each may be NULL. */
+int cmdp_psrlc_last_sample(cmdp_psrlc_t* a, float* T, float* R, float* Q, int64_t* sweeps, int32_t* scheme, int32_t* status);
+/* PSRLContinuous.current_optimal_stochastic_policy (infinite_horizon/posterior_sampling.py:174-178) for the instances selected
+   by mask [B] (NULL: all), on the device from the agent's posterior tables: the dense MAP model (T_map as cmdp_psrl_map_rows
+   defines it, R_map = mu) in a workspace of its own, cmdp_vi_discounted_dense's kernel on it, then argmax_2d (RandomState(42)
+   tie-break).  pi and Q receive [S][A] per instance (pi one-hot), sweeps and scheme [B]; zeros for unselected instances; each
+   may be NULL.  CMDP_ERR_MAX_ITER when a solve does not converge.  The actor's Q, the last sample, the posterior tables, the
+   counters, both RNG streams and the environment are left untouched. */
+int cmdp_psrlc_policy(cmdp_psrlc_t* a, const uint8_t* mask, float* pi, float* Q, int64_t* sweeps, int32_t* scheme);
+/* get_average_reward of that policy from the environments' current states (as cmdp_ucrl2_average_reward). */
+int cmdp_psrlc_average_reward(cmdp_psrlc_t* a, const uint8_t* mask, double* avg, int32_t* kind);
+/* Test hooks: the size threshold of the scheme rule (the reference's default 300 * 3 * 300) and the sweeps a solve may take
+   (DP_MAX_ITERATION = 10^6). */
+enum { CMDP_PSRLC_OPT_SIZE_THRESHOLD = 1, CMDP_PSRLC_OPT_MAX_SWEEPS = 2 };
+int cmdp_psrlc_set_option(cmdp_psrlc_t* a, int option, int64_t value);
+/* discounted_value_iteration(T, R) (colosseum/dynamic_programming/infinite_horizon.py:14-44) on `count` dense float32 problems
+   in one launch (k_vi_discounted_dense, csrc/cmdp_psrlc.h): T concatenated [S, A, S] per instance, R [S, A]; Q receives [S][A]
+   and V [S] per instance.  scheme: CMDP_SCHEME_AUTO applies the reference's rule per instance on its count of non-zero
+   elements (cmdp_model_vi_scheme with size_threshold and density_threshold).  Every row sum is taken in float64 in a fixed
+   order:
+     Gauss-Seidel  Q[s, a] = float(double(R[s, a]) + sum_j double(fl32(gamma * T[s, a, j])) * double(V[j])), V[s] = max_a at once
+     Jacobi        Q[s, a] = R[s, a] + gamma * float(sum_j double(T[s, a, j]) * double(V_old[j])) in float32
+   from V = 0 until max_s |V_old[s] - V[s]| < epsilon after a sweep.  sweeps [count], scheme_used [count], status [count]: 0,
+   or CMDP_ERR_MAX_ITER when max_sweeps were taken (Q and V are then the last sweep's; the call still returns CMDP_OK).
+   CMDP_ERR_UNSUPPORTED beyond 4096 states; values of T or R that are not finite are CMDP_ERR_INVALID. */
+int cmdp_vi_discounted_dense(int count, const int32_t* n_states, const int32_t* n_actions, const float* T, const float* R,
+                             float gamma, double epsilon, int scheme, int64_t size_threshold, double density_threshold,
+                             int64_t max_sweeps, float* Q, float* V, int64_t* sweeps, int32_t* scheme_used, int32_t* status);
 
 #ifdef __cplusplus
 }
