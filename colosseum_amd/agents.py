@@ -493,7 +493,8 @@ class BatchedPSRLContinuous(_PosteriorSamplingAgent):
     sampling -- the reference's own `no_optimistic_sampling=True` path -- per instance of a continuous `BatchedMDP`, driven as
     `MDPLoop.run` drives it: interaction, the N_NIG / M_DIR posterior tables (K12's), the artificial-episode rule, the
     posterior sample, the solve (k_vi_discounted_dense: the reference's Jacobi / Gauss-Seidel rule per sample) and the actor's
-    Q stay on the device (kernel K13, csrc/cmdp_psrlc.h).  The keyword names and defaults are the reference's; the four weights
+    Q stay on the device (kernel K13, csrc/cmdp_psrlc.h).  `policy()` / `policy_solve()` / `average_reward()` solve the MAP
+    model by one of two routes, `set_policy_solver("dense" | "tables")`.  The keyword names and defaults are the reference's; the four weights
     and `max_psi` only shape optimistic sampling and are accepted and unused, as on the reference's plain path.  Refused, each
     by name: optimistic sampling (`no_optimistic_sampling=False` unless every instance has S^2 * A > 6 000 000, where the
     reference switches by itself), `truncate_reward_with_max=True`, `min_steps_before_new_episode != 0`, the exploration
@@ -564,10 +565,28 @@ class BatchedPSRLContinuous(_PosteriorSamplingAgent):
         sa = lambda x: [y.reshape(-1, env.A) for y in env.split_rows(x)]  # noqa: E731
         return dict(T=Ts, R=sa(Rs), Q=sa(Q), sweeps=sweeps, scheme=scheme, status=status)
 
+    _POLICY_SOLVERS = ("dense", "tables")
+
+    def set_policy_solver(self, route: str):
+        """The route behind `policy()` / `policy_solve()` / `average_reward()`.  "dense" (the default): the dense MAP model
+        [S, A, S] of every selected instance in a workspace of its own, then the agent's solver k_vi_discounted_dense on it.
+        "tables": kernel K17 (csrc/cmdp_map_dvi.h) straight on the posterior tables, O(layout + S) per sweep instead of
+        O(S * A * S) and no dense workspace; its Q agrees with the dense route's within the two kernels' rounding bounds and
+        the sweep either may stop earlier, not bit for bit.  Anything else is a ValueError."""
+        routes = BatchedPSRLContinuous._POLICY_SOLVERS
+        if route not in routes:   # before the handle is touched
+            raise ValueError(f"policy solver {route!r}: one of {routes}")
+        L.check(self._lib.cmdp_psrlc_set_option(self._h, L.PSRLC_OPT_POLICY_SOLVER, routes.index(route)))
+        self._policy_solver = route
+
+    @property
+    def policy_solver(self) -> str:
+        return getattr(self, "_policy_solver", "dense")
+
     def policy(self, mask=None):
         """posterior_sampling.py:174-178 on the device: argmax_2d (RandomState(42) tie-break) of discounted value iteration
         on the MAP estimate of the model, per instance [S, A]; with `mask`, for the selected instances only, in their order.
-        Touches nothing the agent acts or learns with."""
+        The solve takes the route of `policy_solver`.  Touches nothing the agent acts or learns with."""
         env = self.env
         m, sel = self._mask(mask)
         pi = np.zeros(int(env.row_off[-1]), np.float32)
@@ -576,8 +595,8 @@ class BatchedPSRLContinuous(_PosteriorSamplingAgent):
         return [rows[b].reshape(-1, env.A) for b in sel]
 
     def policy_solve(self, mask=None):
-        """The solve behind `policy()`: `Q` per instance [S, A] float32, `sweeps` and `scheme` [B]; with `mask`, zeros
-        elsewhere."""
+        """The solve behind `policy()`, by the route of `policy_solver` (k_vi_discounted_dense on the dense MAP model, or K17
+        on the tables): `Q` per instance [S, A] float32, `sweeps` and `scheme` [B]; with `mask`, zeros elsewhere."""
         env = self.env
         m, _ = self._mask(mask)
         Q = np.zeros(int(env.row_off[-1]), np.float32)
@@ -586,8 +605,9 @@ class BatchedPSRLContinuous(_PosteriorSamplingAgent):
         return dict(Q=[x.reshape(-1, env.A) for x in env.split_rows(Q)], sweeps=sweeps, scheme=scheme)
 
     def average_reward(self, mask=None) -> list:
-        """`get_average_reward` of `policy()` from the environments' current states, on the device: a list of numpy scalars
-        (np.float32 where the reference's value is one) for the instances selected by `mask`."""
+        """`get_average_reward` of `policy()` (solved by the route of `policy_solver`) from the environments' current states,
+        on the device: a list of numpy scalars (np.float32 where the reference's value is one) for the instances selected by
+        `mask`."""
         m, sel = self._mask(mask)
         avg, kind = np.zeros(self.env.B, np.float64), np.zeros(self.env.B, np.int32)
         L.check(self._lib.cmdp_psrlc_average_reward(self._h, L.ptr(m), L.ptr(avg), L.ptr(kind)))

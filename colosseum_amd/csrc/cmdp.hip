@@ -43,6 +43,7 @@ extern char** environ;
 #include "cmdp_psrl.h"
 #include "cmdp_psrlc.h"
 #include "cmdp_map_vi.h"
+#include "cmdp_map_dvi.h"
 
 namespace {
 
@@ -5432,11 +5433,13 @@ struct cmdp_psrlc : cmdp_psrl {
   int64_t size_threshold = 300 * 3 * 300;   // the reference's defaults (infinite_horizon.py:20-21)
   double density_threshold = 0.2;
   int64_t max_sweeps = 1000000;             // DP_MAX_ITERATION of the reference
+  int policy_solver = 0;                    // CMDP_PSRLC_OPT_POLICY_SOLVER: 0 the dense route, 1 the tables route (K17)
   PcCounters cnt{};
   DevBuf<int32_t> d_nsa, d_nu, d_stamp, d_scheme, d_status;
   DevBuf<int64_t> d_sweeps;
   // the MAP-policy solve (cmdp_psrlc_policy / cmdp_psrlc_average_reward): buffers of its own, allocated by the first call;
-  // the list and the events are d_mlist and m_ev of the base
+  // the list and the events are d_mlist and m_ev of the base.  d_Tmap, d_Rmap and d_mrs are the dense route's alone and
+  // allocated by its first call; the tables route keeps T_map in d_mapt [NZ] and d_mapc [R] of the base instead.
   DevBuf<float> d_Tmap, d_Rmap, d_mrs, d_pQ, d_pV, d_ppi;
   DevBuf<int32_t> d_pscheme, d_pstatus;
   DevBuf<int64_t> d_psweeps;
@@ -5463,6 +5466,35 @@ int ddv_launch(const DdvArgs& g, int count, int max_S, hipStream_t st) {
     if (int rc = set_lds(k_vi_discounted_dense<DDV_MAX_WAVES>, lds)) return rc;
     hipLaunchKernelGGL(k_vi_discounted_dense<DDV_MAX_WAVES>, dim3(count), dim3(DDV_MAX_WAVES * 64), lds, st, g);
   }
+  HIP_TRY(hipGetLastError());
+  return CMDP_OK;
+}
+
+// Host-only picker of k_vi_discounted_map's form and launch geometry (one wavefront per instance, `count` workgroups).  An
+// instance may keep its tables in LDS next to its value arrays when they take at most MAPDVI_STAGE_MAX_BYTES (two such
+// workgroups share a CU's 160 KB); `staged` is the launch's dynamic LDS in that form, `plain` with every instance's tables
+// left in global memory.  The staged form is taken when all its workgroups are resident at once: a launch that would need
+// a second round of workgroups keeps the tables in global memory, where the CU holds every instance of the launch.  The
+// results do not depend on the form (cmdp_map_dvi.h); CMDP_MAPDVI_STAGE=0 / 1 forces one of them, for measurements.
+constexpr size_t MAPDVI_STAGE_MAX_BYTES = (size_t)80 * 1024;
+size_t mapdvi_pick_lds(int count, int cus, size_t staged, size_t plain) {
+  const char* e = std::getenv("CMDP_MAPDVI_STAGE");
+  if (e && (e[0] == '0' || e[0] == '1') && e[1] == '\0') return e[0] == '1' ? staged : plain;
+  const size_t per_cu = (size_t)kLdsBudget / std::max<size_t>(staged, 1);
+  return (size_t)count <= (size_t)std::max(cus, 1) * per_cu ? staged : plain;
+}
+
+// K17's launch on device-resident arguments: what cmdp_vi_discounted_map does after its uploads and what the continuous PSRL
+// agent does for its MAP policy on the tables route.  One wavefront per instance; `lds` is the largest map_dvi_lds_bytes of
+// the launch's instances.
+int mapdvi_launch(MapDviArgs g, int count, int max_S, size_t lds, hipStream_t st) {
+  if (max_S > MAPVI_MAX_STATES)
+    return fail(CMDP_ERR_UNSUPPORTED, "%d states: value iteration on a MAP model (K17) keeps V and V_old in LDS for at most %d",
+                max_S, MAPVI_MAX_STATES);
+  if (count == 0) return CMDP_OK;
+  g.lds_bytes = (unsigned)lds;
+  if (int rc = set_lds(k_vi_discounted_map, lds)) return rc;
+  hipLaunchKernelGGL(k_vi_discounted_map, dim3(count), dim3(MAPDVI_THREADS), lds, st, g);
   HIP_TRY(hipGetLastError());
   return CMDP_OK;
 }
@@ -5578,6 +5610,12 @@ int cmdp_psrlc_set_option(cmdp_psrlc_t* a, int option, int64_t value) {
     a->max_sweeps = value;
     return CMDP_OK;
   }
+  if (option == CMDP_PSRLC_OPT_POLICY_SOLVER) {
+    if (value != 0 && value != 1)
+      return fail(CMDP_ERR_INVALID, "policy solver %lld: 0 (the dense route) or 1 (the tables route, K17)", (long long)value);
+    a->policy_solver = (int)value;
+    return CMDP_OK;
+  }
   return fail(CMDP_ERR_INVALID, "unknown option %d", option);
 }
 
@@ -5619,8 +5657,10 @@ int cmdp_psrlc_last_sample(cmdp_psrlc_t* a, float* T, float* R, float* Q, int64_
   return CMDP_OK;
 }
 
-// discounted_value_iteration(*get_map_estimate()) and argmax_2d for the instances of `mask` on the handle's stream: the dense
-// MAP model into d_Tmap / d_Rmap (k_psrlc_map_fill), K13's solver on it, the greedy policy of its Q in d_ppi.  Reads nothing
+// discounted_value_iteration(*get_map_estimate()) and argmax_2d for the instances of `mask` on the handle's stream.  The dense
+// route: the dense MAP model into d_Tmap / d_Rmap (k_psrlc_map_fill), K13's solver on it.  The tables route
+// (CMDP_PSRLC_OPT_POLICY_SOLVER = 1): K17 straight on the posterior tables, no dense workspace.  Then, for both, the greedy
+// policy of Q in d_ppi.  Reads nothing
 // but the model and writes nothing of the agent's but these buffers: the last sample and the actor's Q stay what they were.
 // Returns after the stream has drained, with the instances it solved in `sel`; CMDP_ERR_MAX_ITER when one did not converge.
 static int psrlc_policy_solve(cmdp_psrlc_t* a, const uint8_t* mask, std::vector<int32_t>& sel) {
@@ -5628,13 +5668,20 @@ static int psrlc_policy_solve(cmdp_psrlc_t* a, const uint8_t* mask, std::vector<
   hipStream_t st = h->stream;
   const int B = h->B;
   const int64_t R = h->n_rows;
-  if (!a->d_pQ.p) {
+  const bool tables = a->policy_solver == 1;
+  if (!tables && !a->d_mrs.p) {
     if (a->d_Tmap.alloc((size_t)a->t_total) != hipSuccess) {
       (void)hipGetLastError();
       return fail(CMDP_ERR_OVERFLOW, "the dense workspace of the MAP models cannot be allocated: %lld bytes for the batch",
                   (long long)(a->t_total * 4));
     }
-    HIP_TRY(a->d_Rmap.alloc((size_t)R)); HIP_TRY(a->d_mrs.alloc((size_t)R)); HIP_TRY(a->d_pV.alloc((size_t)h->n_states));
+    HIP_TRY(a->d_Rmap.alloc((size_t)R)); HIP_TRY(a->d_mrs.alloc((size_t)R));
+  }
+  if (tables && !a->d_mapc.p) {
+    HIP_TRY(a->d_mapt.alloc((size_t)a->nz)); HIP_TRY(a->d_mapc.alloc((size_t)R));
+  }
+  if (!a->d_pQ.p) {
+    HIP_TRY(a->d_pV.alloc((size_t)h->n_states));
     HIP_TRY(a->d_ppi.alloc((size_t)R)); HIP_TRY(a->d_psweeps.alloc((size_t)B)); HIP_TRY(a->d_pscheme.alloc((size_t)B));
     HIP_TRY(a->d_pstatus.alloc((size_t)B)); HIP_TRY(a->d_mlist.alloc((size_t)B));
     for (hipEvent_t& e : a->m_ev) HIP_TRY(hipEventCreate(&e));
@@ -5651,8 +5698,24 @@ static int psrlc_policy_solve(cmdp_psrlc_t* a, const uint8_t* mask, std::vector<
     list = a->d_mlist.p;
   }
   const int count = (int)sel.size();
+  size_t map_lds = 0;   // of a K17 launch on this batch, by the picker's form
+  if (tables) {
+    size_t staged = 0, plain = 0;
+    for (int b = 0; b < B; ++b) {
+      const int64_t s0 = h->state_off[b], s1 = h->state_off[b + 1];
+      staged = std::max(staged, map_dvi_lds_bytes((int)(s1 - s0), h->A, a->h_ptr[(size_t)(s1 * h->A)] - a->h_ptr[(size_t)(s0 * h->A)],
+                                                  MAPDVI_STAGE_MAX_BYTES));
+      plain = std::max(plain, map_dvi_value_bytes((int)(s1 - s0)));
+    }
+    map_lds = mapdvi_pick_lds((int)sel.size(), h->cus, staged, plain);
+  }
   HIP_TRY(hipEventRecord(a->m_ev[0], st));
-  if (count > 0) {
+  if (count > 0 && tables) {
+    MapDviArgs g{list, nullptr, a->d_S.p, a->d_A.p, a->d_roff.p, h->d_state_off.p, a->d_row_ptr.p, a->d_col.p, a->d_tp.p,
+                 a->d_tprior.p, a->d_rp.p, 4, a->d_mapt.p, a->d_mapc.p, 0.99f, 1e-3, CMDP_SCHEME_AUTO, a->size_threshold,
+                 a->density_threshold, a->max_sweeps, a->d_pQ.p, a->d_pV.p, a->d_psweeps.p, a->d_pscheme.p, a->d_pstatus.p, 0};
+    if (int rc = mapdvi_launch(g, count, h->max_S, map_lds, st)) return rc;
+  } else if (count > 0) {
     PcMapArgs m{list, a->d_S.p, a->d_A.p, a->d_roff.p, a->d_toff.p, a->d_row_ptr.p, a->d_col.p, a->d_tp.p, a->d_tprior.p, a->d_rp.p,
                 a->d_mrs.p, a->d_Tmap.p, a->d_Rmap.p};
     hipLaunchKernelGGL(k_psrlc_map_fill, dim3(count), dim3(MAPVI_THREADS), 0, st, m);
@@ -5766,6 +5829,86 @@ int cmdp_vi_discounted_dense(int count, const int32_t* n_states, const int32_t* 
   HIP_TRY(ws->sweeps.download(sweeps, count, st));
   HIP_TRY(ws->scheme.download(scheme_used, count, st));
   HIP_TRY(ws->status.download(status, count, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return CMDP_OK;
+}
+
+int cmdp_vi_discounted_map(int count, const int32_t* n_states, const int32_t* n_actions, const int64_t* row_ptr,
+                           const int32_t* col, const float* hp, const float* prior, const float* mu, float gamma, double epsilon,
+                           int scheme, int64_t size_threshold, double density_threshold, int64_t max_sweeps, float* Q, float* V,
+                           int64_t* sweeps, int32_t* scheme_used, int32_t* status, float* t_layout_out, float* c_out) {
+  if (count < 0) return fail(CMDP_ERR_INVALID, "count %d is negative", count);
+  if (count == 0) return CMDP_OK;
+  const std::pair<const void*, const char*> needed[] = {{n_states, "n_states"}, {n_actions, "n_actions"}, {row_ptr, "row_ptr"},
+      {prior, "prior"}, {mu, "mu"}, {Q, "Q"}, {V, "V"}, {sweeps, "sweeps"}, {scheme_used, "scheme_used"}, {status, "status"}};
+  for (const auto& n : needed)
+    if (!n.first) return fail(CMDP_ERR_INVALID, "%s is null", n.second);
+  if (!std::isfinite(gamma)) return fail(CMDP_ERR_INVALID, "gamma %g is not finite", (double)gamma);
+  if (!(epsilon >= 0.0) || !std::isfinite(epsilon)) return fail(CMDP_ERR_INVALID, "epsilon %g is not a finite value >= 0", epsilon);
+  if (max_sweeps < 1) return fail(CMDP_ERR_INVALID, "max_sweeps %lld < 1", (long long)max_sweeps);
+  if (scheme != CMDP_SCHEME_AUTO && scheme != CMDP_SCHEME_JACOBI && scheme != CMDP_SCHEME_GAUSS_SEIDEL)
+    return fail(CMDP_ERR_INVALID, "scheme %d: CMDP_SCHEME_AUTO, CMDP_SCHEME_JACOBI or CMDP_SCHEME_GAUSS_SEIDEL", scheme);
+  if (size_threshold < 0) return fail(CMDP_ERR_INVALID, "size_threshold %lld is negative", (long long)size_threshold);
+  if (std::isnan(density_threshold)) return fail(CMDP_ERR_INVALID, "density_threshold is not a number");
+  BatchLayout L;
+  if (int rc = L.build(count, n_states, n_actions,
+                       {MAPVI_MAX_STATES, "instance %d has %d states: value iteration on a MAP model (K17) keeps V and V_old in LDS "
+                                          "for at most %d states"}))
+    return rc;
+  const int64_t ns = L.ns, nr = L.nr;
+  if (row_ptr[0] != 0) return fail(CMDP_ERR_INVALID, "row_ptr[0] = %lld, not 0", (long long)row_ptr[0]);
+  for (int64_t r = 0; r < nr; ++r)
+    if (row_ptr[r + 1] < row_ptr[r]) return fail(CMDP_ERR_INVALID, "row_ptr decreases at row %lld", (long long)r);
+  const int64_t nz = row_ptr[nr];
+  if (nz > 0 && !col) return fail(CMDP_ERR_INVALID, "col is null");
+  if (nz > 0 && !hp) return fail(CMDP_ERR_INVALID, "hp is null");
+  size_t staged = 0, plain = 0;
+  for (int b = 0; b < count; ++b) {
+    const int64_t* ptr = row_ptr + L.roff[b];
+    if (int rc = map_check_layout(b, n_states[b], n_actions[b], ptr, col, hp, prior[b])) return rc;
+    staged = std::max(staged, map_dvi_lds_bytes(n_states[b], n_actions[b], ptr[L.rows(b)] - ptr[0], MAPDVI_STAGE_MAX_BYTES));
+    plain = std::max(plain, map_dvi_value_bytes(n_states[b]));
+  }
+  for (int64_t i = 0; i < nr; ++i)   // a value that is not finite would keep a solve sweeping to max_sweeps
+    if (!std::isfinite(mu[i])) return fail(CMDP_ERR_INVALID, "mu[%lld] is not finite", (long long)i);
+  struct Ws {
+    DevBuf<int32_t> S, A, col, scheme, status;
+    DevBuf<int64_t> soff, roff, ptr, sweeps;
+    DevBuf<float> hp, prior, mu, t, c, Q, V;
+  };
+  DeviceWorkspace<Ws> ws;
+  if (int rc = ws.acquire()) return rc;
+  hipStream_t st = ws.st;
+  HIP_TRY(ws->S.upload(n_states, count, st));
+  HIP_TRY(ws->A.upload(n_actions, count, st));
+  HIP_TRY(ws->soff.upload(L.soff.data(), L.soff.size(), st));
+  HIP_TRY(ws->roff.upload(L.roff.data(), count, st));
+  HIP_TRY(ws->ptr.upload(row_ptr, (size_t)nr + 1, st));
+  HIP_TRY(ws->col.upload(col, (size_t)nz, st));
+  HIP_TRY(ws->hp.upload(hp, (size_t)nz, st));
+  HIP_TRY(ws->prior.upload(prior, count, st));
+  HIP_TRY(ws->mu.upload(mu, (size_t)nr, st));
+  HIP_TRY(ws->t.alloc((size_t)nz));
+  HIP_TRY(ws->c.alloc((size_t)nr));
+  HIP_TRY(ws->Q.alloc((size_t)nr));
+  HIP_TRY(ws->V.alloc((size_t)ns));
+  HIP_TRY(ws->sweeps.alloc(count));
+  HIP_TRY(ws->scheme.alloc(count));
+  HIP_TRY(ws->status.alloc(count));
+  MapDviArgs g{nullptr, nullptr, ws->S.p, ws->A.p, ws->roff.p, ws->soff.p, ws->ptr.p, ws->col.p, ws->hp.p, ws->prior.p, ws->mu.p, 1,
+               ws->t.p, ws->c.p, gamma, epsilon, scheme, size_threshold, density_threshold, max_sweeps, ws->Q.p, ws->V.p,
+               ws->sweeps.p, ws->scheme.p, ws->status.p, 0};
+  int dev = 0, cus = 0;
+  HIP_TRY(hipGetDevice(&dev));
+  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 256;
+  if (int rc = mapdvi_launch(g, count, L.max_S, mapdvi_pick_lds(count, cus, staged, plain), st)) return rc;
+  HIP_TRY(ws->Q.download(Q, (size_t)nr, st));
+  HIP_TRY(ws->V.download(V, (size_t)ns, st));
+  HIP_TRY(ws->sweeps.download(sweeps, count, st));
+  HIP_TRY(ws->scheme.download(scheme_used, count, st));
+  HIP_TRY(ws->status.download(status, count, st));
+  if (t_layout_out) HIP_TRY(ws->t.download(t_layout_out, (size_t)nz, st));
+  if (c_out) HIP_TRY(ws->c.download(c_out, (size_t)nr, st));
   HIP_TRY(hipStreamSynchronize(st));
   return CMDP_OK;
 }

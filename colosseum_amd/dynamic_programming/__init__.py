@@ -193,7 +193,7 @@ def _map_problem(p):
     elif len(p) in (3, 4):
         thp, mu, prior = p[:3]
         mu = np.ascontiguousarray(mu, np.float32)
-        if np.ndim(thp) != 3 or mu.shape != np.shape(thp)[:2]:
+        if np.ndim(thp) != 3 or mu.shape != np.shape(thp)[:2] or np.shape(thp)[0] != np.shape(thp)[2]:
             raise ValueError("dense form: transition_hp [S, A, S], reward_mu [S, A], prior")
         row_ptr, col, hp = map_layout_from_dense(thp, prior, p[3] if len(p) == 4 else None)
     else:
@@ -237,6 +237,60 @@ def episodic_value_iteration_map_batch(problems, H, return_map=False):
             one += (t[nz_off[i]:nz_off[i + 1]], c[r0:r0 + s * a].reshape(s, a))
         out.append(one)
         q0, v0, r0 = q0 + nq, v0 + nv, r0 + s * a
+    return out
+
+
+def discounted_value_iteration_map_batch(problems, gamma=0.99, epsilon=1e-3, sparse_n_states_threshold=300 * 3 * 300,
+                                         sparse_nnz_per_threshold=0.2, scheme=None, max_sweeps=DP_MAX_ITERATION, return_map=False):
+    """`discounted_value_iteration(*get_map_estimate())` for many Bayesian models in one launch of kernel K17, without the
+    dense MAP array.  A problem is the table form (row_ptr, col, hp, prior, mu [S, A]) or the dense form (transition_hp
+    [S, A, S], reward_mu [S, A], prior[, keep]), as for `episodic_value_iteration_map_batch`; the problems may differ in S
+    and A.  The solver's arguments are `discounted_value_iteration_dense_batch`'s: the reference's rule picks Jacobi or
+    Gauss-Seidel per problem from the count of non-zero elements of its dense MAP array unless `scheme` forces one, and a
+    problem that takes `max_sweeps` sweeps returns the last sweep's values.  Returns [(Q [S, A], V [S], sweeps, scheme)];
+    with `return_map` [(Q, V, sweeps, scheme, t, c)]: the MAP transition estimate at the layout's positions and, per row
+    [S, A], elsewhere.  `status` of the last call (0 or L.ERR_MAX_ITER per problem) is left in
+    `discounted_value_iteration_map_batch.status`."""
+    ps = [_map_problem(p) for p in problems]
+    gamma, epsilon = float(gamma), float(epsilon)
+    if not np.isfinite(gamma):
+        raise ValueError("gamma must be finite")
+    if not (np.isfinite(epsilon) and epsilon >= 0.0):
+        raise ValueError("epsilon must be a finite value >= 0")
+    if int(max_sweeps) < 1:
+        raise ValueError("max_sweeps < 1")
+    if scheme is not None and int(scheme) not in (L.SCHEME_JACOBI, L.SCHEME_GAUSS_SEIDEL):
+        raise ValueError("scheme is None, L.SCHEME_JACOBI or L.SCHEME_GAUSS_SEIDEL")
+    if int(sparse_n_states_threshold) < 0 or np.isnan(float(sparse_nnz_per_threshold)):
+        raise ValueError("sparse_n_states_threshold must be >= 0 and sparse_nnz_per_threshold a number")
+    if not ps:
+        return []
+    S = np.array([p[4].shape[0] for p in ps], np.int32)
+    A = np.array([p[4].shape[1] for p in ps], np.int32)
+    n = len(ps)
+    nz = np.array([len(p[1]) for p in ps], np.int64)
+    nz_off = np.concatenate([[0], np.cumsum(nz)])
+    ptr = np.concatenate([p[0][:-1] + nz_off[i] for i, p in enumerate(ps)] + [nz_off[-1:]]).astype(np.int64)
+    col = np.concatenate([p[1] for p in ps]).astype(np.int32)
+    hp = np.concatenate([p[2] for p in ps]).astype(np.float32)
+    prior = np.array([p[3] for p in ps], np.float32)
+    mu = np.concatenate([p[4].ravel() for p in ps]).astype(np.float32)
+    Q, V = np.zeros(int((S.astype(np.int64) * A).sum()), np.float32), np.zeros(int(S.sum()), np.float32)
+    sweeps, used, status = np.zeros(n, np.int64), np.zeros(n, np.int32), np.zeros(n, np.int32)
+    t, c = np.zeros(len(hp), np.float32), np.zeros(len(mu), np.float32)
+    L.check(L.load().cmdp_vi_discounted_map(n, L.ptr(S), L.ptr(A), L.ptr(ptr), L.ptr(col), L.ptr(hp), L.ptr(prior), L.ptr(mu),
+                                            gamma, epsilon, L.SCHEME_AUTO if scheme is None else int(scheme),
+                                            int(sparse_n_states_threshold), float(sparse_nnz_per_threshold), int(max_sweeps),
+                                            L.ptr(Q), L.ptr(V), L.ptr(sweeps), L.ptr(used), L.ptr(status),
+                                            L.ptr(t) if return_map else None, L.ptr(c) if return_map else None))
+    discounted_value_iteration_map_batch.status = status
+    out, q0, v0 = [], 0, 0
+    for i, (s, a) in enumerate(zip(S.tolist(), A.tolist())):
+        one = (Q[q0:q0 + s * a].reshape(s, a), V[v0:v0 + s], int(sweeps[i]), int(used[i]))
+        if return_map:
+            one += (t[nz_off[i]:nz_off[i + 1]], c[q0:q0 + s * a].reshape(s, a))
+        out.append(one)
+        q0, v0 = q0 + s * a, v0 + s
     return out
 
 

@@ -912,8 +912,11 @@ int cmdp_psrlc_policy(cmdp_psrlc_t* a, const uint8_t* mask, float* pi, float* Q,
 /* get_average_reward of that policy from the environments' current states (as cmdp_ucrl2_average_reward). */
 int cmdp_psrlc_average_reward(cmdp_psrlc_t* a, const uint8_t* mask, double* avg, int32_t* kind);
 /* Test hooks: the size threshold of the scheme rule (the reference's default 300 * 3 * 300) and the sweeps a solve may take
-   (DP_MAX_ITERATION = 10^6). */
-enum { CMDP_PSRLC_OPT_SIZE_THRESHOLD = 1, CMDP_PSRLC_OPT_MAX_SWEEPS = 2 };
+   (DP_MAX_ITERATION = 10^6).  CMDP_PSRLC_OPT_POLICY_SOLVER picks the route behind cmdp_psrlc_policy and
+   cmdp_psrlc_average_reward: 0 (the default) the dense route described above, 1 the tables route -- K17
+   (cmdp_vi_discounted_map's kernel) straight on the posterior tables, which never allocates the dense workspace; any other
+   value is CMDP_ERR_INVALID.  Both routes fill the same outputs and CMDP_STAT_PSRL_POLICY_KERNEL_MS. */
+enum { CMDP_PSRLC_OPT_SIZE_THRESHOLD = 1, CMDP_PSRLC_OPT_MAX_SWEEPS = 2, CMDP_PSRLC_OPT_POLICY_SOLVER = 3 };
 int cmdp_psrlc_set_option(cmdp_psrlc_t* a, int option, int64_t value);
 /* discounted_value_iteration(T, R) (colosseum/dynamic_programming/infinite_horizon.py:14-44) on `count` dense float32 problems
    in one launch (k_vi_discounted_dense, csrc/cmdp_psrlc.h): T concatenated [S, A, S] per instance, R [S, A]; Q receives [S][A]
@@ -928,6 +931,23 @@ int cmdp_psrlc_set_option(cmdp_psrlc_t* a, int option, int64_t value);
 int cmdp_vi_discounted_dense(int count, const int32_t* n_states, const int32_t* n_actions, const float* T, const float* R,
                              float gamma, double epsilon, int scheme, int64_t size_threshold, double density_threshold,
                              int64_t max_sweeps, float* Q, float* V, int64_t* sweeps, int32_t* scheme_used, int32_t* status);
+
+/* discounted_value_iteration(T_map, mu) on `count` MAP models in table form (K17, csrc/cmdp_map_dvi.h), one launch, no dense
+   array.  The problem is cmdp_vi_episodic_map's: row_ptr [sum S * A + 1] over the rows of all problems (row_ptr[0] = 0), col
+   instance-relative and ascending within a row, hp per position, prior [count], mu [sum S * A]; the solver's arguments, their
+   refusals and the outputs Q [S][A], V [S], sweeps, scheme_used and status are cmdp_vi_discounted_dense's.  With T_map = (t, c)
+   as cmdp_psrl_map_rows defines it, sub = sum_e double(V[col_e]) and SV the float64 sum of V in a fixed order:
+     Gauss-Seidel  Q[s, a] = float(double(mu) + (double(fl32(gamma c)) * (SV - sub) + sum_e double(fl32(gamma t_e)) * double(V[col_e]))),
+                   V[s] = max_a at once, SV = SV + (double(V_new) - double(V[s]))
+     Jacobi        Q[s, a] = mu + gamma * float(double(c) * (SV - sub) + sum_e double(t_e) * double(V_old[col_e])) in float32
+   from V = 0 until max_s |V_old[s] - V[s]| < epsilon after a sweep; a row whose layout covers every column leaves the c term
+   out.  CMDP_SCHEME_AUTO counts the positions with t_e != 0 plus S - len for every row with c != 0: the dense MAP array's
+   non-zero elements.  t_layout_out (per position) and c_out (per row) receive T_map and may be NULL.  CMDP_ERR_UNSUPPORTED
+   beyond 4096 states; every other null or invalid argument is CMDP_ERR_INVALID, by name. */
+int cmdp_vi_discounted_map(int count, const int32_t* n_states, const int32_t* n_actions, const int64_t* row_ptr,
+                           const int32_t* col, const float* hp, const float* prior, const float* mu, float gamma, double epsilon,
+                           int scheme, int64_t size_threshold, double density_threshold, int64_t max_sweeps, float* Q, float* V,
+                           int64_t* sweeps, int32_t* scheme_used, int32_t* status, float* t_layout_out, float* c_out);
 
 #ifdef __cplusplus
 }
