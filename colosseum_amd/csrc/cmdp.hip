@@ -837,6 +837,27 @@ uint32_t cmdp_k1e_code_counts(uint32_t lo, uint32_t hi, int few) {
   return few ? k1e_code_counts_few(lo, hi) : k1e_code_counts(lo, hi);
 }
 
+int cmdp_k1e_scan_words(const uint64_t* words, int64_t n_words, int H, int h0, int64_t n_steps, int nch, int n_codes,
+                        const double rv[4], double s0, double* sum, int32_t stats[4]) {
+  if (!words || !rv || !sum || !stats) return fail(CMDP_ERR_INVALID, "cmdp_k1e_scan_words: null argument");
+  // (a segment: the lane counts its steps in an int)
+  if (H < 1 || h0 < 0 || h0 >= H || n_steps < 1 || n_steps >= ((int64_t)1 << 31) || nch != (H + 31) / 32 || n_codes < 1 || n_codes > 4)
+    return fail(CMDP_ERR_INVALID, "cmdp_k1e_scan_words: H %d, h0 %d, n_steps %lld, nch %d, n_codes %d", H, h0, (long long)n_steps, nch, n_codes);
+  if ((((int64_t)h0 + n_steps + H - 1) / H) * nch != n_words || n_words >= ((int64_t)1 << 31))
+    return fail(CMDP_ERR_INVALID, "cmdp_k1e_scan_words: %lld words do not hold %lld steps from in-episode time %d", (long long)n_words,
+                (long long)n_steps, h0);
+  double r[4];
+  for (int c = 0; c < 4; ++c) r[c] = c < n_codes ? rv[c] : 0.0;
+  K1rLane L;
+  k1r_init(L, r, n_codes, H, nch, h0, n_steps, s0);
+  K1rHostLoader ld{words, L.W};
+  K1rStats st;
+  k1r_scan(L, ld, st);
+  *sum = k1r_sum(L);
+  for (int i = 0; i < 4; ++i) stats[i] = st.n[i];
+  return CMDP_OK;
+}
+
 int cmdp_device_count(void) {
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess) return 0;
@@ -1354,6 +1375,8 @@ static int launch_k1e(cmdp_t* h, const RolloutCall& c, bool from_start) {
   // (the pair form stores its code words through 32-bit byte offsets, like the single form's interior rounds)
   pair = pair && need * sizeof(uint2) < ((size_t)1 << 31);
   if (pair) seg -= seg % e.H;   // whole episodes (seg >= H)
+  // (the scan's lane keeps its byte offset 8 b in 32 bits for every batch that fits a device: K1rDeviceLoader says what that buys)
+  const auto scan = (size_t)h->B * sizeof(uint2) < ((size_t)1 << 31) ? k_reward_scan<true> : k_reward_scan<false>;
   // CMDP_POLICY_RANDOM_REFERENCE: forms 2 / 3 load the action bits K16 makes before each segment's walk (<= 482 blocks of
   // 16 bytes per instance); one buffer, K16 and the walk follow each other on the handle's stream
   const bool ref = c.policy == CMDP_POLICY_RANDOM_REFERENCE;
@@ -1411,14 +1434,14 @@ static int launch_k1e(cmdp_t* h, const RolloutCall& c, bool from_start) {
       HIP_TRY(hipEventRecord(h->aux.walk[i], st));
       HIP_TRY(hipStreamWaitEvent(h->aux.stream, h->aux.walk[i], 0));
       if (last) HIP_TRY(hipEventRecord(h->ev_time[3], h->aux.stream));
-      hipLaunchKernelGGL(k_reward_scan, dim3(grid_for(h->B, K1R_THREADS)), dim3(K1R_THREADS), 0, h->aux.stream, t, e, n, c.rsum, s0 > 0 ? 1 : 0);
+      hipLaunchKernelGGL(scan, dim3(grid_for(h->B, K1R_THREADS)), dim3(K1R_THREADS), 0, h->aux.stream, t, e, n, c.rsum, s0 > 0 ? 1 : 0);
       if (last) HIP_TRY(hipEventRecord(h->ev_time[4], h->aux.stream));
       HIP_TRY(hipEventRecord(h->aux.scan[i], h->aux.stream));
       h->aux.used[i] = true;
       h->aux.pending = true;
       h->aux.seq++;
     } else {
-      hipLaunchKernelGGL(k_reward_scan, dim3(grid_for(h->B, K1R_THREADS)), dim3(K1R_THREADS), 0, st, t, e, n, c.rsum, s0 > 0 ? 1 : 0);
+      hipLaunchKernelGGL(scan, dim3(grid_for(h->B, K1R_THREADS)), dim3(K1R_THREADS), 0, st, t, e, n, c.rsum, s0 > 0 ? 1 : 0);
       if (last) HIP_TRY(hipEventRecord(h->ev_time[2], st));
     }
   }

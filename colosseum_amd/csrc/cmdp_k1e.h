@@ -69,10 +69,14 @@
 //         chooses per launch; everything else takes the form below, k_rollout_epi<0>.
 // k_reward_scan -- lane = instance: the float64 reward sum in TRANSITION ORDER from the code words (bit-equal to the
 //         oracle's and every other kernel's sequential sum).  It loads the code words in tiles of eight, three tiles in
-//         registers, and forms the packed step counts n1 | n2 << 11 | n3 << 22 of a word itself (k1e_code_counts_few for
-//         at most three reward codes, k1e_code_counts for four: one wave-uniform branch per tile); the words a lane has to add
-//         step by step are already in its registers.  No LDS at all and <= 128 VGPRs: k_rollout_epi holds every byte
-//         of the CU's LDS and 4 x 96 VGPRs per SIMD, and a wavefront of the scan still fits beside it.
+//         registers.  A PLAIN tile (eight whole single-chunk episodes for every lane of the wavefront: 106 of a wavefront's
+//         125 at C2) costs the step counts per code of its eight words, accumulated straight into registers, and one integer
+//         advance.  Any other tile, and a lane whose plain advance fails, forms the packed step counts n1 | n2 << 11 |
+//         n3 << 22 of each word (k1e_code_counts_few for at most three reward codes, k1e_code_counts for four: one
+//         wave-uniform branch per tile) and their prefix sums; the words a lane has to add step by step are already in its
+//         registers.  The lane's arithmetic is __host__ __device__ (K1rLane, k1r_scan) and exported as cmdp_k1e_scan_words.
+//         No LDS at all and <= 128 VGPRs: k_rollout_epi holds every byte of the CU's LDS and 4 x 96 VGPRs per SIMD, and a
+//         wavefront of the scan still fits beside it.
 // Results: visit counts, final states, in-episode times, Philox counters and reward sums bit-equal to K1 / K1T / K1U and the
 // CPU oracle (tests/test_gpu_parity.py, tests/test_gpu_fullsize.py, tools/stress_k1t.py k1e, tools/fuzz_parity.py).
 #pragma once
@@ -654,236 +658,446 @@ __global__ void __launch_bounds__(K1E_THREADS) k_epi_fold(EnvTables t, K1ePlan p
 // negative or a tie case -- the chunk is added step by step in float64, exactly as the oracle does, and (k, m, q) are
 // re-derived from the result.  An episode's code word holds the 2-bit reward codes of its steps, step j of a 32-step
 // chunk at bits 2 j of the 64-bit word (unused fields zero).
+//
+// The lane's arithmetic -- its state (K1rLane), rebase, both forms of advance, the counts of a plain tile, the slow path
+// and the episode / chunk bookkeeping -- is __host__ __device__ code: the kernel instantiates k1r_scan with a loader of
+// global memory, cmdp_k1e_scan_words (cmdp.hip) with one of a host array, so the tests check on the CPU the very
+// functions the kernel runs.  A wave-uniform vote of the kernel is the lane's own predicate on the host.
 // element `i` (run-time, per lane) of a register array of 8: a select tree instead of an LDS round trip -- the reward scan
 // keeps NO tile in LDS, so that its wavefronts fit beside k_rollout_epi's workgroups (whose tables take the CU's LDS)
 typedef uint32_t k1r_u32x8 __attribute__((ext_vector_type(8)));   // (a vector value, not an array: it cannot end up in scratch)
-__device__ __forceinline__ uint32_t k1r_sel8(const k1r_u32x8 a, int i) {
+__host__ __device__ __forceinline__ uint32_t k1r_sel8(const k1r_u32x8 a, int i) {
   const bool i0 = (i & 1) != 0, i1 = (i & 2) != 0, i2 = (i & 4) != 0;
   const uint32_t b0 = i0 ? a[1] : a[0], b1 = i0 ? a[3] : a[2], b2 = i0 ? a[5] : a[4], b3 = i0 ? a[7] : a[6];
   const uint32_t c0 = i1 ? b1 : b0, c1 = i1 ? b3 : b2;
   return i2 ? c1 : c0;
 }
 
+// ... and halfword `i` of a register array of 4 (the prefix sums of a tile's steps, <= 256, two to a register)
+typedef uint32_t k1r_u32x4 __attribute__((ext_vector_type(4)));
+__host__ __device__ __forceinline__ uint32_t k1r_sel8h(const k1r_u32x4 a, int i) {
+  const bool i1 = (i & 2) != 0, i2 = (i & 4) != 0;
+  const uint32_t b0 = i1 ? a[1] : a[0], b1 = i1 ? a[3] : a[2];
+  return ((i2 ? b1 : b0) >> ((i & 1) << 4)) & 0xffffu;
+}
+
 #define K1R_THREADS 64
-// The scan loads the CODE words (8 B) and counts the steps per code itself (k1e_code_counts_few / k1e_code_counts): the walk
-// is bound by VALU issue and the scan -- one wavefront per SIMD, hidden under the next walk -- takes the slots the walk leaves.
-// THREE tiles of EIGHT words: while one is summed, two are in flight (128 B per lane, what two tiles of sixteen 4-byte count
-// words were), and the tile being summed stays in registers for the step-by-step path: 3 x 16 registers of code words + 2 x 8
-// of prefix sums, where the count words took 2 x 16 + 2 x 16.
+// The scan loads the CODE words (8 B) and counts the steps per code itself: the walk is bound by VALU issue and the scan --
+// one wavefront per SIMD, hidden under the next walk -- takes the slots the walk leaves, so it is priced by its instruction
+// count.  THREE tiles of EIGHT words: while one is summed, two are in flight (128 B per lane), and the tile being summed
+// stays in registers for the step-by-step path.
+//   plain a tile of single-chunk episodes that is neither the lane's first nor its last, for every lane of the wavefront
+//         (one vote), holds 8 H steps: the steps per code of its eight words are accumulated straight into two or three
+//         registers (v_bcnt_u32_b32 adds to its second operand) and ONE integer advance follows -- no packed word, no
+//         prefix sums.  A lane whose advance fails forms the packed prefix sums then, from the words still in its
+//         registers, and takes the slow path under exec.
+//   loads when the eight words of a tile exist for every lane of the wavefront (one vote) they are loaded unpredicated;
+//         otherwise word by word under a test against W, unloaded words zero.  Either way the address is the word's scalar
+//         base (advanced in SALU) plus the lane's 8 b: in the loop one v_lshl_add_u64 per load (K1rDeviceLoader).
 #define K1R_T 8    // code words per tile
 #define K1R_D 3    // tiles in registers: one being summed, the others' loads in flight
+#if defined(__HIP_DEVICE_COMPILE__)
+#define K1R_ALL(x) (__all(x) != 0)   // every lane of the wavefront ...
+#else
+#define K1R_ALL(x) (x)               // ... the lane itself on the host
+#endif
+
+// which paths a scan took (cmdp_k1e_scan_words reports them: the tests prove with them that their inputs reach every path);
+// the kernel counts nothing
+struct K1rNoStats {
+  __host__ __device__ __forceinline__ void plain() {}
+  __host__ __device__ __forceinline__ void slow() {}
+  __host__ __device__ __forceinline__ void word() {}
+  __host__ __device__ __forceinline__ void rebase() {}
+};
+struct K1rStats {
+  int32_t n[4] = {0, 0, 0, 0};   // plain tiles advanced whole, tiles on the slow path, words added step by step, rebases after them
+  void plain() { ++n[0]; }
+  void slow() { ++n[1]; }
+  void word() { ++n[2]; }
+  void rebase() { ++n[3]; }
+};
+
+struct K1rLane {
+  // the rewards by code (codes >= n_codes: 0.0): value, mantissa with the hidden bit, biased exponent (zero / subnormal: 0)
+  double rv[4];
+  unsigned long long mv[4];
+  int eb[4];
+  bool bulk_allowed;   // no reward is negative (or huge): the integer form may be used at all
+  int n_codes, H, nch;
+  int W;               // code words of the lane's instance in this segment, in order (< 2^31)
+  // the sum: while !kvalid `m` holds the bits of the float64 sum S, else the integer form S = m * 2^(kb - 1075) with
+  // 2^52 <= m < 2^53 (kb = biased exponent) -- one register pair for both; q[c] = round(rv[c] / spacing) as (low, high)
+  // halves; `tie`: codes whose presence forces the float64 path (a tie case in this binade, a subnormal reward, a reward
+  // at or above 2^(k+1))
+  bool kvalid;
+  int kb;
+  unsigned long long m;
+  uint32_t qlo[4], qhi[4];
+  uint32_t tie;
+  // episode / chunk bookkeeping of the next word to be laid out
+  int ch;
+  int e_len;          // steps of the current episode inside this segment
+  int ep_left;        // ... not yet covered by earlier chunks
+  int tot_left;       // steps from the current episode's first one on (a segment: < 2^31)
+};
+
+// (k, m, q, tie) from the float64 sum in L.m (!kvalid).  q is derived for the codes c < n_codes only (wave-uniform): the
+// others stay 0 as k1r_init left them
+__host__ __device__ __forceinline__ void k1r_rebase(K1rLane& L) {
+  const unsigned long long M52 = (1ull << 52) - 1ull, B52 = 1ull << 52;
+  L.kvalid = false;
+  const unsigned long long sb = L.m;
+  const double S = __builtin_bit_cast(double, sb);
+  if (!L.bulk_allowed || !(S >= 2.2250738585072014e-308) || !(S < 1.0e300)) return;
+  L.kb = (int)(sb >> 52);
+  L.m = (sb & M52) | B52;
+  L.tie = 0u;
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    if (c < L.n_codes) {
+      unsigned long long qq = 0ull;
+      if (L.rv[c] != 0.0) {
+        const int d = L.kb - L.eb[c];
+        if (L.eb[c] == 0 || d < 0) L.tie |= 1u << c;   // subnormal reward, or v >= 2^(k+1): the sum would leave the binade
+        else if (d == 0) qq = L.mv[c];
+        else if (d < 55) {
+          const unsigned long long half = 1ull << (d - 1), rem = L.mv[c] & ((1ull << d) - 1ull);
+          qq = (L.mv[c] >> d) + (rem > half ? 1ull : 0ull);
+          if (rem == half) L.tie |= 1u << c;
+        }
+      }
+      L.qlo[c] = (uint32_t)qq;
+      L.qhi[c] = (uint32_t)(qq >> 32);
+    }
+  }
+  L.kvalid = true;
+}
+
+// the lane at the start of a segment of n_steps transitions that begins h0 steps into an episode, its sum at S0
+__host__ __device__ __forceinline__ void k1r_init(K1rLane& L, const double (&rv)[4], int n_codes, int H, int nch, int h0,
+                                                  int64_t n_steps, double S0) {
+  const unsigned long long M52 = (1ull << 52) - 1ull, B52 = 1ull << 52;
+  L.n_codes = n_codes; L.H = H; L.nch = nch;
+  L.bulk_allowed = true;
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    L.rv[c] = rv[c];
+    L.bulk_allowed = L.bulk_allowed && rv[c] >= 0.0 && rv[c] < 1.0e300;
+    const unsigned long long vb = __builtin_bit_cast(unsigned long long, rv[c]);
+    L.eb[c] = (int)(vb >> 52) & 0x7ff;
+    L.mv[c] = (vb & M52) | B52;
+    L.qlo[c] = 0u; L.qhi[c] = 0u;
+  }
+  const int64_t E = ((int64_t)h0 + n_steps + H - 1) / H;
+  L.W = (int)(E * nch);
+  L.m = __builtin_bit_cast(unsigned long long, S0);
+  L.kvalid = false; L.kb = 0; L.tie = 0u;
+  L.ch = 0;
+  L.e_len = (int)((int64_t)(H - h0) < n_steps ? (int64_t)(H - h0) : n_steps);
+  L.ep_left = L.e_len;
+  L.tot_left = (int)n_steps;
+  k1r_rebase(L);
+}
+
+// m + the advance of `steps` (<= 512) transitions of which n1, n2, n3 have reward code 1, 2, 3; true = the whole of it stays
+// in the integer form
+__host__ __device__ __forceinline__ bool k1r_advance(const K1rLane& L, uint32_t n1, uint32_t n2, uint32_t n3, uint32_t steps,
+                                                     unsigned long long& m2) {
+  const uint32_t n0 = steps - n1 - n2 - n3;
+  const uint32_t present = (n0 ? 1u : 0u) | (n1 ? 2u : 0u) | (n2 ? 4u : 0u) | (n3 ? 8u : 0u);
+  unsigned long long lo64 = (unsigned long long)n0 * L.qlo[0];
+  lo64 += (unsigned long long)n1 * L.qlo[1];
+  lo64 += (unsigned long long)n2 * L.qlo[2];
+  lo64 += (unsigned long long)n3 * L.qlo[3];
+  const uint32_t hi32 = n0 * L.qhi[0] + n1 * L.qhi[1] + n2 * L.qhi[2] + n3 * L.qhi[3];   // <= 512 * 2^22
+  m2 = L.m + lo64 + ((unsigned long long)hi32 << 32);
+  return L.kvalid && (present & L.tie) == 0u && m2 < (1ull << 53);
+}
+// ... with the packed counts nw = n1 | n2 << 11 | n3 << 22 (k1e_code_counts) of the slow path's prefix sums
+__host__ __device__ __forceinline__ bool k1r_advance(const K1rLane& L, uint32_t nw, uint32_t steps, unsigned long long& m2) {
+  return k1r_advance(L, nw & 0x7ffu, (nw >> 11) & 0x7ffu, nw >> 22, steps, m2);
+}
+// the float64 sum (its bits) of the integer form
+__host__ __device__ __forceinline__ unsigned long long k1r_compose(const K1rLane& L) {
+  return ((unsigned long long)L.kb << 52) | (L.m & ((1ull << 52) - 1ull));
+}
+__host__ __device__ __forceinline__ double k1r_sum(const K1rLane& L) {
+  return __builtin_bit_cast(double, L.kvalid ? k1r_compose(L) : L.m);
+}
+
+// The steps per code of a whole tile, accumulated over its eight words (popcount + accumulator is one v_bcnt_u32_b32).
+// At most three codes: no field is 3, so all set bits are n1 + n2 and the odd planes hold n2; the odd plane of the low half
+// and -- shifted down -- that of the high half are merged into one word before they are counted (one v_lshrrev, one v_bfi).
+__host__ __device__ __forceinline__ void k1r_tile_counts_few(const k1r_u32x8& clo, const k1r_u32x8& chi, uint32_t& n1, uint32_t& n2) {
+  uint32_t n12 = 0u, c2 = 0u;
+#pragma unroll
+  for (int k = 0; k < K1R_T; ++k) {
+    n12 += (uint32_t)__builtin_popcount(clo[k]);
+    n12 += (uint32_t)__builtin_popcount(chi[k]);
+    c2 += (uint32_t)__builtin_popcount((clo[k] & 0xaaaaaaaau) | ((chi[k] >> 1) & 0x55555555u));
+  }
+  n1 = n12 - c2; n2 = c2;
+}
+// Four codes: all set bits are n1 + n2 + 2 n3, the odd planes n2 + n3, and a third plane (both bits of a field) n3.
+__host__ __device__ __forceinline__ void k1r_tile_counts(const k1r_u32x8& clo, const k1r_u32x8& chi, uint32_t& n1, uint32_t& n2,
+                                                         uint32_t& n3) {
+  uint32_t all = 0u, odd = 0u, c3 = 0u;
+#pragma unroll
+  for (int k = 0; k < K1R_T; ++k) {
+    all += (uint32_t)__builtin_popcount(clo[k]);
+    all += (uint32_t)__builtin_popcount(chi[k]);
+    odd += (uint32_t)__builtin_popcount((clo[k] & 0xaaaaaaaau) | ((chi[k] >> 1) & 0x55555555u));
+    const uint32_t l3 = clo[k] & (clo[k] >> 1), h3 = chi[k] & (chi[k] >> 1);   // (bit 2 j: field j is 3; odd bits: anything)
+    c3 += (uint32_t)__builtin_popcount((l3 & 0x55555555u) | ((h3 << 1) & 0xaaaaaaaau));
+  }
+  n3 = c3; n2 = odd - c3; n1 = all - odd - c3;
+}
+
+// The slow path of a tile whose whole advance has failed for this lane: the first word that does not advance (binary
+// search over the prefix sums P of packed counts and SP of steps; SP holds two sums to a register), everything before it
+// in one piece, that word in float64 step by step exactly as the oracle adds, then the rest of the tile again.  The search
+// is valid because advancing is monotone: q >= 0, and a code that forces the float64 path stays present in every longer prefix.
+template <class ST>
+__host__ __device__ __forceinline__ void k1r_slow(K1rLane& L, const k1r_u32x8& clo, const k1r_u32x8& chi, const k1r_u32x8& P,
+                                                  const k1r_u32x4& SP, ST& st) {
+  const uint32_t Pt = P[K1R_T - 1], St = SP[K1R_T / 2 - 1] >> 16;
+  const double rv0 = L.rv[0], rv1 = L.rv[1], rv2 = L.rv[2], rv3 = L.rv[3];
+  unsigned long long m2;
+  uint32_t base_n = 0u, base_s = 0u;
+  int from = 0;
+  for (;;) {   // (here the advance of the words from `from` on is known to fail: the caller's, or the test at the bottom)
+    int lo = from, hi = K1R_T - 1;
+#pragma unroll
+    for (int it = 0; it < 3; ++it) {   // 2^3 = K1R_T
+      const int mid = (lo + hi) >> 1;
+      const bool ok = k1r_advance(L, k1r_sel8(P, mid) - base_n, k1r_sel8h(SP, mid) - base_s, m2);
+      if (lo < hi) { if (ok) lo = mid + 1; else hi = mid; }
+    }
+    const int k = lo;
+    const uint32_t Sk1 = k > 0 ? k1r_sel8h(SP, k - 1) : 0u;
+    if (k > from && k1r_advance(L, k1r_sel8(P, k - 1) - base_n, Sk1 - base_s, m2)) L.m = m2;
+    const uint32_t Sk = k1r_sel8h(SP, k);
+    const uint32_t Lw = Sk - Sk1;
+    if (Lw) {
+      st.word();
+      // (the word is in registers: the tile is reloaded only when it is done)
+      const uint32_t cx = k1r_sel8(clo, k), cy = k1r_sel8(chi, k);
+      double S = __builtin_bit_cast(double, L.kvalid ? k1r_compose(L) : L.m);
+      // (step by step exactly as the oracle adds, but for the steps whose reward is +0.0 -- x + 0.0 == x, the sum is never
+      // -0.0 -- which are skipped: the scaled minimum reward is 0, half of DeepSea's steps.  The reward of a code by a
+      // select on four registers: the scan owns no LDS at all, k_rollout_epi may hold every byte of the CU's.  One wavefront
+      // per SIMD issues an instruction every ~8 cycles, so this path is priced by its instruction count)
+#pragma unroll
+      for (int half = 0; half < 2; ++half) {
+        const uint32_t cw = half ? cy : cx;
+        const int Lh = (int)Lw - 16 * half;
+        if (Lh > 0) {
+          const uint32_t vm = Lh >= 16 ? 0x55555555u : ((1u << (2 * Lh)) - 1u) & 0x55555555u;
+          const uint32_t b0 = cw & vm, b1 = (cw >> 1) & vm;
+          uint32_t nz = 0u;
+          if (rv0 != 0.0) nz |= vm & ~(b0 | b1);
+          if (rv1 != 0.0) nz |= b0 & ~b1;
+          if (rv2 != 0.0) nz |= b1 & ~b0;
+          if (rv3 != 0.0) nz |= b0 & b1;
+          while (nz) {
+            const uint32_t pos = (uint32_t)__builtin_ctz(nz);
+            nz &= nz - 1u;
+            const uint32_t cd = cw >> pos;
+            const bool c0 = (cd & 1u) != 0u, c1 = (cd & 2u) != 0u;
+            const double lo2 = c0 ? rv1 : rv0, hi2 = c0 ? rv3 : rv2;
+            S += c1 ? hi2 : lo2;
+          }
+        }
+      }
+      L.m = __builtin_bit_cast(unsigned long long, S);
+      k1r_rebase(L);
+      st.rebase();
+    }
+    base_n = k1r_sel8(P, k);
+    base_s = Sk;
+    from = k + 1;
+    if (from >= K1R_T) break;
+    if (k1r_advance(L, Pt - base_n, St - base_s, m2)) { L.m = m2; break; }
+  }
+}
+
+// The tile of code words w0 .. w0 + K1R_T - 1 (low and high halves; past the lane's end: zero).
+template <class ST>
+__host__ __device__ __forceinline__ void k1r_tile(K1rLane& L, const k1r_u32x8& clo, const k1r_u32x8& chi, const int w0, ST& st) {
+  const int H = L.H;
+  const bool few = L.n_codes <= 3;   // (wave-uniform: no field of a code word is 3)
+  unsigned long long m2;
+  k1r_u32x8 P;
+  k1r_u32x4 SP;   // (prefix sums of steps, SP[k] in halfword k & 1 of register k >> 1)
+  // plain tiles -- interior ones of single-chunk episodes, for all lanes: every word holds H steps
+  const bool plain = L.nch == 1 && K1R_ALL(w0 >= 1 && w0 + K1R_T <= L.W - 1);
+  if (plain) {
+    uint32_t n1, n2, n3;
+    bool whole;
+    if (few) {
+      k1r_tile_counts_few(clo, chi, n1, n2);
+      whole = k1r_advance(L, n1, n2, 0u, (uint32_t)(K1R_T * H), m2);
+    } else {
+      k1r_tile_counts(clo, chi, n1, n2, n3);
+      whole = k1r_advance(L, n1, n2, n3, (uint32_t)(K1R_T * H), m2);
+    }
+    L.tot_left -= K1R_T * H;   // eight full episodes on: the next one may be the segment's last, partial one
+    L.e_len = H < L.tot_left ? H : L.tot_left;
+    L.ep_left = L.e_len;
+    if (whole) { L.m = m2; st.plain(); return; }
+  }
+  // Every other tile, and the lanes of a plain tile that did not advance: the packed counts of the tile's words (still in
+  // registers) and their prefix sums
+  uint32_t rn[K1R_T];
+  if (few) {
+#pragma unroll
+    for (int k = 0; k < K1R_T; ++k) rn[k] = k1e_code_counts_few(clo[k], chi[k]);
+  } else {
+#pragma unroll
+    for (int k = 0; k < K1R_T; ++k) rn[k] = k1e_code_counts(clo[k], chi[k]);
+  }
+  if (plain) {
+    uint32_t acc = 0u;
+#pragma unroll
+    for (int k = 0; k < K1R_T; ++k) { acc += rn[k]; P[k] = acc; }
+#pragma unroll
+    for (int k = 0; k < K1R_T; k += 2) SP[k >> 1] = (uint32_t)((k + 1) * H) | ((uint32_t)((k + 2) * H) << 16);
+  } else {
+    // the first and the last tile, chunked episodes, ragged ends: 0 steps for a chunk a partial episode does not reach or
+    // a word past the end
+    uint32_t acc = 0u, sacc = 0u;
+#pragma unroll
+    for (int k = 0; k < K1R_T; ++k) {
+      const int Lk = (w0 + k < L.W) ? (L.ep_left < 0 ? 0 : (L.ep_left < 32 ? L.ep_left : 32)) : 0;
+      acc += Lk > 0 ? rn[k] : 0u;
+      sacc += (uint32_t)Lk;
+      P[k] = acc;
+      if (k & 1) SP[k >> 1] |= sacc << 16; else SP[k >> 1] = sacc;
+      L.ep_left -= 32;
+      if (++L.ch == L.nch) {
+        L.ch = 0;
+        L.tot_left -= L.e_len;
+        L.e_len = H < L.tot_left ? H : L.tot_left;
+        L.ep_left = L.e_len;
+      }
+    }
+    if (k1r_advance(L, P[K1R_T - 1], sacc, m2)) { L.m = m2; return; }
+  }
+  st.slow();
+  k1r_slow(L, clo, chi, P, SP, st);
+}
+
+// The scan of a lane: three tiles of code words (A, B, C in turn); a tile's registers take the words K1R_D tiles on as soon
+// as it is summed.  LD::fetch(clo, chi, w0) loads the words w0 .. w0 + K1R_T - 1 (past the end: zero, not loaded).
+template <class LD, class ST>
+__host__ __device__ __forceinline__ void k1r_scan(K1rLane& L, LD& ld, ST& st) {
+  k1r_u32x8 loA, hiA, loB, hiB, loC, hiC;
+  ld.fetch(loA, hiA, 0);
+  ld.fetch(loB, hiB, K1R_T);
+  ld.fetch(loC, hiC, 2 * K1R_T);
+  const int W = L.W;
+  for (int w0 = 0; w0 < W; w0 += K1R_D * K1R_T) {
+    k1r_tile(L, loA, hiA, w0, st);
+    ld.fetch(loA, hiA, w0 + K1R_D * K1R_T);
+    if (w0 + K1R_T < W) {
+      k1r_tile(L, loB, hiB, w0 + K1R_T, st);
+      ld.fetch(loB, hiB, w0 + (K1R_D + 1) * K1R_T);
+    }
+    if (w0 + 2 * K1R_T < W) {
+      k1r_tile(L, loC, hiC, w0 + 2 * K1R_T, st);
+      ld.fetch(loC, hiC, w0 + (K1R_D + 2) * K1R_T);
+    }
+  }
+}
+
+// the words of ONE instance in a host array (cmdp_k1e_scan_words)
+struct K1rHostLoader {
+  const uint64_t* words;
+  int W;
+  void fetch(k1r_u32x8& clo, k1r_u32x8& chi, const int w0) const {
+    for (int k = 0; k < K1R_T; ++k) {
+      const uint64_t v = w0 + k < W ? words[w0 + k] : 0ull;
+      clo[k] = (uint32_t)v; chi[k] = (uint32_t)(v >> 32);
+    }
+  }
+};
+
+// codes[word][instance] in global memory: word w of the lane's instance b lies B words after word w - 1
+typedef uint32_t k1r_u32x2 __attribute__((ext_vector_type(2)));
+typedef __attribute__((address_space(1))) unsigned char* k1r_glb_u8;
+template <bool OFF32>   // 8 B < 2^31: the lane keeps its byte offset 8 b, else b
+struct K1rDeviceLoader {
+  k1r_glb_u8 codes;    // (wave-uniform)
+  uint32_t lane_off;   // OFF32: 8 b, the lane's byte offset from a word's base; else b
+  int B, W;
+  // The address of word w0 + k: the word's base, pinned to a scalar register pair (s_mov / s_add_u32 / s_addc_u32 per load),
+  // plus the lane's offset.  What the compiler makes of it for gfx950: only the loads before the loop take the form "scalar
+  // base + 32-bit vector offset"; every load inside the loop is one v_lshl_add_u64 of the base and the pair (8 b, 0), which
+  // stays in two registers across the scan, and a load through the 64-bit vector address -- with OFF32 and without.  So the
+  // pins and OFF32 do NOT buy the scalar-base form where the time goes.  They stay for what was measured: the same loader
+  // written plainly (base + k stride + 8 b, one kernel, no pin; 126 VGPRs, 7 % less SALU in the code) ran the scan alone in
+  // 0.187 ms against 0.160 ms for this form and 0.173 ms for the parent, and the step slower than the parent
+  // (profiles/k1e_scan_lean.json, "plain_loader").  Why the plain form is slower was not found.
+  __device__ __forceinline__ const __attribute__((address_space(1))) k1r_u32x2* word(k1r_glb_u8 base, size_t stride, int k) const {
+    k1r_glb_u8 wb = base + (size_t)k * stride;
+    asm volatile("" : "+s"(wb));
+    if constexpr (OFF32) return (const __attribute__((address_space(1))) k1r_u32x2*)(wb + (size_t)lane_off);
+    else {
+      uint32_t bo = lane_off;
+      asm volatile("" : "+v"(bo));   // (the 64-bit lane offset formed at the load, not kept in a register pair across the scan)
+      return (const __attribute__((address_space(1))) k1r_u32x2*)(wb + (size_t)bo * 8);
+    }
+  }
+  __device__ __forceinline__ int instance() const { return (int)(OFF32 ? lane_off >> 3 : lane_off); }
+  __device__ __forceinline__ void fetch(k1r_u32x8& clo, k1r_u32x8& chi, const int w0) const {
+    const size_t stride = (size_t)(uint32_t)__builtin_amdgcn_readfirstlane(B) * 8;
+    const uint64_t a0 = (uint64_t)(uintptr_t)codes + (size_t)w0 * stride;
+    const k1r_glb_u8 base = (k1r_glb_u8)(uintptr_t)((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)a0) |
+                                                    ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(a0 >> 32)) << 32));
+    if (__all(w0 + K1R_T <= W)) {
+      // every lane of the wavefront owns all eight words: no test, no zeroing -- for seven of them: the compiler merges the
+      // eighth load into the tested path below (two zeroed registers, an exec branch whose test holds).  A scheduling barrier
+      // at the end of this branch keeps it apart; that was built with the plain loader only (above) and not measured alone
+#pragma unroll
+      for (int k = 0; k < K1R_T; ++k) {
+        const k1r_u32x2 v = __builtin_nontemporal_load(word(base, stride, k));
+        clo[k] = v.x; chi[k] = v.y;
+      }
+      return;
+    }
+#pragma unroll
+    for (int k = 0; k < K1R_T; ++k) {
+      k1r_u32x2 v = {0u, 0u};
+      if (w0 + k < W) v = __builtin_nontemporal_load(word(base, stride, k));
+      clo[k] = v.x; chi[k] = v.y;
+    }
+  }
+};
+
 // (<= 128 VGPRs and NO LDS: a wavefront of the scan fits on every SIMD beside k_rollout_epi's workgroup -- 4 x 96 VGPRs
 // per SIMD, 163 840 B of LDS per CU -- so that the scan of one segment runs under the walk of the next)
+// OFF32: 8 B < 2^31 (launch_k1e)
+template <bool OFF32>
 __global__ void __launch_bounds__(K1R_THREADS) __attribute__((amdgpu_waves_per_eu(4, 8))) k_reward_scan(EnvTables t, K1ePlan p, int64_t n_steps,
                                                             double* __restrict__ reward_sum, int accumulate) {
   const int lane = threadIdx.x;
   const int b = min(blockIdx.x * K1R_THREADS + lane, t.B - 1);   // (lanes past the batch repeat its last instance, unstored)
   const bool mine = blockIdx.x * K1R_THREADS + lane < t.B;
   double rv[4];
-  bool bulk_allowed = true;
 #pragma unroll
-  for (int c = 0; c < 4; ++c) {
-    rv[c] = c < p.n_codes ? p.rvals[c] * t.rscale - t.rmin : 0.0;
-    bulk_allowed = bulk_allowed && rv[c] >= 0.0 && rv[c] < 1.0e300;
-  }
-  const double rv0 = rv[0], rv1 = rv[1], rv2 = rv[2], rv3 = rv[3];
-  // per code: mantissa with the hidden bit and biased exponent of the reward (zero / subnormal rewards: eb = 0)
-  unsigned long long mv[4];
-  int eb[4];
-  const unsigned long long M52 = (1ull << 52) - 1ull, B52 = 1ull << 52;
-#pragma unroll
-  for (int c = 0; c < 4; ++c) {
-    const unsigned long long vb = (unsigned long long)__double_as_longlong(rv[c]);
-    eb[c] = (int)(vb >> 52) & 0x7ff;
-    mv[c] = (vb & M52) | B52;
-  }
-  const int H = p.H, h0 = p.seg_h0[b], nch = p.nch;
-  double S = accumulate ? reward_sum[b] : 0.0;
-  const int64_t E = ((int64_t)h0 + n_steps + H - 1) / H;
-  const int W = (int)(E * nch);   // code words of this instance, in order (a segment: < 2^31)
-  typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-  const u32x2* csrc = reinterpret_cast<const u32x2*>(p.codes) + b;
-  const bool few = p.n_codes <= 3;   // (wave-uniform: no field of a code word is 3)
-  // integer form of the sum, valid while `kvalid`: S = m * 2^(kb - 1075) with 2^52 <= m < 2^53 (kb = biased exponent);
-  // q[c] = round(rv[c] / spacing) as (low, high) halves; `tie`: codes whose presence forces the float64 path (a tie case in
-  // this binade, a subnormal reward, a reward at or above 2^(k+1))
-  bool kvalid = false;
-  int kb = 0;
-  unsigned long long m = 0ull;
-  uint32_t qlo[4] = {0u, 0u, 0u, 0u}, qhi[4] = {0u, 0u, 0u, 0u};
-  uint32_t tie = 0u;
-  auto rebase = [&]() {
-    kvalid = false;
-    if (!bulk_allowed || !(S >= 2.2250738585072014e-308) || !(S < 1.0e300)) return;
-    const unsigned long long sb = (unsigned long long)__double_as_longlong(S);
-    kb = (int)(sb >> 52);
-    m = (sb & M52) | B52;
-    tie = 0u;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      unsigned long long qq = 0ull;
-      if (rv[c] != 0.0) {
-        const int d = kb - eb[c];
-        if (eb[c] == 0 || d < 0) tie |= 1u << c;   // subnormal reward, or v >= 2^(k+1): the sum would leave the binade
-        else if (d == 0) qq = mv[c];
-        else if (d < 55) {
-          const unsigned long long half = 1ull << (d - 1), rem = mv[c] & ((1ull << d) - 1ull);
-          qq = (mv[c] >> d) + (rem > half ? 1ull : 0ull);
-          if (rem == half) tie |= 1u << c;
-        }
-      }
-      qlo[c] = (uint32_t)qq;
-      qhi[c] = (uint32_t)(qq >> 32);
-    }
-    kvalid = true;
-  };
-  rebase();
-  // m + the advance of `steps` (<= 512) transitions with packed counts nw; true = the whole of it stays in the integer form
-  auto advance = [&](uint32_t nw, uint32_t steps, unsigned long long& m2) -> bool {
-    const uint32_t n1 = nw & 0x7ffu, n2 = (nw >> 11) & 0x7ffu, n3 = nw >> 22, n0 = steps - n1 - n2 - n3;
-    const uint32_t present = (n0 ? 1u : 0u) | (n1 ? 2u : 0u) | (n2 ? 4u : 0u) | (n3 ? 8u : 0u);
-    unsigned long long lo64 = (unsigned long long)n0 * qlo[0];
-    lo64 += (unsigned long long)n1 * qlo[1];
-    lo64 += (unsigned long long)n2 * qlo[2];
-    lo64 += (unsigned long long)n3 * qlo[3];
-    const uint32_t hi32 = n0 * qhi[0] + n1 * qhi[1] + n2 * qhi[2] + n3 * qhi[3];   // <= 512 * 2^22
-    m2 = m + lo64 + ((unsigned long long)hi32 << 32);
-    return kvalid && (present & tie) == 0u && m2 < (1ull << 53);
-  };
-  auto compose = [&]() { return __longlong_as_double((long long)(((unsigned long long)kb << 52) | (m & M52))); };
-
-  // episode / chunk bookkeeping of the next word to be laid out
-  int ch = 0;
-  int e_len = (int)min((int64_t)(H - h0), n_steps);   // steps of the current episode inside this segment
-  int ep_left = e_len;                                 // ... not yet covered by earlier chunks
-  int64_t tot_left = n_steps;                          // steps from the current episode's first one on
-
-  // the code words w0 .. w0 + K1R_T - 1 of the lane's instance (low and high halves; past the end: zero, not loaded)
-  auto fetch = [&](k1r_u32x8& clo, k1r_u32x8& chi, const int w0) {
-    const u32x2* src = csrc + (size_t)w0 * t.B;
-#pragma unroll
-    for (int k = 0; k < K1R_T; ++k) {
-      u32x2 v = {0u, 0u};
-      if (w0 + k < W) v = __builtin_nontemporal_load(&src[(size_t)k * t.B]);
-      clo[k] = v.x; chi[k] = v.y;
-    }
-  };
-  // three tiles of code words (A, B, C in turn)
-  k1r_u32x8 loA, hiA, loB, hiB, loC, hiC;
-  fetch(loA, hiA, 0);
-  fetch(loB, hiB, K1R_T);
-  fetch(loC, hiC, 2 * K1R_T);
-  auto tile = [&](const k1r_u32x8& clo, const k1r_u32x8& chi, const int w0) {
-    // the packed counts of the tile's words
-    uint32_t rn[K1R_T];
-    if (few) {
-#pragma unroll
-      for (int k = 0; k < K1R_T; ++k) rn[k] = k1e_code_counts_few(clo[k], chi[k]);
-    } else {
-#pragma unroll
-      for (int k = 0; k < K1R_T; ++k) rn[k] = k1e_code_counts(clo[k], chi[k]);
-    }
-    // prefix sums of the tile's packed counts and steps (0 steps: a chunk a partial episode does not reach, or past the end)
-    k1r_u32x8 P, SP;
-    // interior tiles of single-chunk episodes (all lanes): every word holds H steps
-    const bool interior = nch == 1 && __all(w0 >= 1 && w0 + K1R_T <= W - 1);
-    if (interior) {
-      uint32_t acc = 0u;
-#pragma unroll
-      for (int k = 0; k < K1R_T; ++k) { acc += rn[k]; P[k] = acc; SP[k] = (uint32_t)((k + 1) * H); }
-      tot_left -= (int64_t)K1R_T * H;   // eight full episodes on: the next one may be the segment's last, partial one
-      e_len = (int)min((int64_t)H, tot_left);
-      ep_left = e_len;
-    } else {
-      uint32_t acc = 0u, sacc = 0u;
-#pragma unroll
-      for (int k = 0; k < K1R_T; ++k) {
-        const int L = (w0 + k < W) ? max(0, min(32, ep_left)) : 0;
-        acc += L > 0 ? rn[k] : 0u;
-        sacc += (uint32_t)L;
-        P[k] = acc; SP[k] = sacc;
-        ep_left -= 32;
-        if (++ch == nch) {
-          ch = 0;
-          tot_left -= e_len;
-          e_len = (int)min((int64_t)H, tot_left);
-          ep_left = e_len;
-        }
-      }
-    }
-    const uint32_t Pt = P[K1R_T - 1], St = SP[K1R_T - 1];
-    unsigned long long m2;
-    const bool whole = advance(Pt, St, m2);
-    if (whole) { m = m2; return; }
-    // ---- this lane: the first word that does not advance (binary search over the prefix sums: advancing is monotone --
-    // q >= 0, and a forcing code stays present), everything before it in one piece, that word in float64 step by step
-    // exactly as the oracle adds, then the rest of the tile again ----
-    uint32_t base_n = 0u, base_s = 0u;
-    int from = 0;
-    while (from < K1R_T) {
-      if (advance(Pt - base_n, St - base_s, m2)) { m = m2; break; }
-      int lo = from, hi = K1R_T - 1;
-#pragma unroll
-      for (int it = 0; it < 3; ++it) {   // 2^3 = K1R_T
-        const int mid = (lo + hi) >> 1;
-        const bool ok = advance(k1r_sel8(P, mid) - base_n, k1r_sel8(SP, mid) - base_s, m2);
-        if (lo < hi) { if (ok) lo = mid + 1; else hi = mid; }
-      }
-      const int k = lo;
-      const uint32_t Sk1 = k > 0 ? k1r_sel8(SP, k - 1) : 0u;
-      if (k > from && advance(k1r_sel8(P, k - 1) - base_n, Sk1 - base_s, m2)) m = m2;
-      const uint32_t Sk = k1r_sel8(SP, k);
-      const uint32_t L = Sk - Sk1;
-      if (L) {
-        u32x2 c;   // (the word is in registers: the tile is reloaded only when it is done)
-        c.x = k1r_sel8(clo, k); c.y = k1r_sel8(chi, k);
-        if (kvalid) S = compose();
-        // (step by step exactly as the oracle adds, but for the steps whose reward is +0.0 -- x + 0.0 == x, the sum is never
-        // -0.0 -- which are skipped: the scaled minimum reward is 0, half of DeepSea's steps.  The reward of a code by a
-        // select on four registers: the scan owns no LDS at all, k_rollout_epi may hold every byte of the CU's.  One wavefront
-        // per SIMD issues an instruction every ~8 cycles, so this path is priced by its instruction count)
-#pragma unroll
-        for (int half = 0; half < 2; ++half) {
-          const uint32_t cw = half ? c.y : c.x;
-          const int Lh = (int)L - 16 * half;
-          if (Lh > 0) {
-            const uint32_t vm = Lh >= 16 ? 0x55555555u : ((1u << (2 * Lh)) - 1u) & 0x55555555u;
-            const uint32_t b0 = cw & vm, b1 = (cw >> 1) & vm;
-            uint32_t nz = 0u;
-            if (rv0 != 0.0) nz |= vm & ~(b0 | b1);
-            if (rv1 != 0.0) nz |= b0 & ~b1;
-            if (rv2 != 0.0) nz |= b1 & ~b0;
-            if (rv3 != 0.0) nz |= b0 & b1;
-            while (nz) {
-              const uint32_t pos = (uint32_t)__builtin_ctz(nz);
-              nz &= nz - 1u;
-              const uint32_t cd = cw >> pos;
-              const bool c0 = (cd & 1u) != 0u, c1 = (cd & 2u) != 0u;
-              const double lo2 = c0 ? rv1 : rv0, hi2 = c0 ? rv3 : rv2;
-              S += c1 ? hi2 : lo2;
-            }
-          }
-        }
-        rebase();
-      }
-      base_n = k1r_sel8(P, k);
-      base_s = Sk;
-      from = k + 1;
-    }
-  };
-  // (a tile's registers take the words K1R_D tiles on as soon as it is summed)
-  for (int w0 = 0; w0 < W; w0 += K1R_D * K1R_T) {
-    tile(loA, hiA, w0);
-    fetch(loA, hiA, w0 + K1R_D * K1R_T);
-    if (w0 + K1R_T < W) {
-      tile(loB, hiB, w0 + K1R_T);
-      fetch(loB, hiB, w0 + (K1R_D + 1) * K1R_T);
-    }
-    if (w0 + 2 * K1R_T < W) {
-      tile(loC, hiC, w0 + 2 * K1R_T);
-      fetch(loC, hiC, w0 + (K1R_D + 2) * K1R_T);
-    }
-  }
-  if (kvalid) S = compose();
-  if (mine) reward_sum[b] = S;
+  for (int c = 0; c < 4; ++c) rv[c] = c < p.n_codes ? p.rvals[c] * t.rscale - t.rmin : 0.0;
+  K1rLane L;
+  k1r_init(L, rv, p.n_codes, p.H, p.nch, p.seg_h0[b], n_steps, accumulate ? reward_sum[b] : 0.0);
+  K1rDeviceLoader<OFF32> ld;
+  ld.codes = (k1r_glb_u8)(uintptr_t)p.codes;
+  ld.lane_off = OFF32 ? (uint32_t)b * 8u : (uint32_t)b;
+  ld.B = t.B; ld.W = L.W;
+  K1rNoStats st;
+  k1r_scan(L, ld, st);
+  // (b again, from the one register the loader keeps of it, and pinned: the address of reward_sum[b] formed here, not kept in a
+  // register pair from the load above across the whole scan)
+  int bs = ld.instance();
+  asm volatile("" : "+v"(bs));
+  if (mine) reward_sum[bs] = k1r_sum(L);
 }

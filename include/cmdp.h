@@ -181,6 +181,15 @@ int cmdp_k1e_round_interior(int e_lo, int horizon, int64_t n_steps, int n_instan
    only when no field is 3), else its four-code form.  The very functions the kernel calls; needs no handle and no device.
    No reference counterpart. */
 uint32_t cmdp_k1e_code_counts(uint32_t lo, uint32_t hi, int few);
+/* K1E: the float64 reward sum of ONE instance over a segment, by the very per-lane code k_reward_scan runs (a wave-uniform
+   vote of the kernel is the lane's own predicate here).  words[n_words]: the instance's code words in order -- the segment
+   has n_steps transitions and starts h0 steps into an episode of horizon H with nch = ceil(H / 32) words per episode, so
+   n_words = ceil((h0 + n_steps) / H) * nch; step j of a chunk at bits 2 j, unused fields zero.  rv[c]: the scaled reward of
+   code c < n_codes (<= 4); s0: the sum before the segment.  *sum: s0 + the rewards one by one in float64, in transition
+   order.  stats: plain tiles advanced whole, tiles that took the slow path, words added step by step, rebases after them.
+   Needs no handle and no device.  No reference counterpart. */
+int cmdp_k1e_scan_words(const uint64_t* words, int64_t n_words, int H, int h0, int64_t n_steps, int nch, int n_codes,
+                        const double rv[4], double s0, double* sum, int32_t stats[4]);
 int cmdp_device_count(void);
 int cmdp_set_device(int device);
 
