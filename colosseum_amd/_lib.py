@@ -88,7 +88,7 @@ EXPORTS = [
     "cmdp_ucrl2_set_option", "cmdp_ucrl2_policy", "cmdp_ucrl2_average_reward", "cmdp_model_vi_scheme", "cmdp_vi_discounted_model",
     "cmdp_psrl_create", "cmdp_psrl_destroy", "cmdp_psrl_run", "cmdp_psrl_layout", "cmdp_psrl_model", "cmdp_psrl_last_sample",
     "cmdp_psrl_reference_sample", "cmdp_vi_episodic_dense", "cmdp_psrl_episode_end_update", "cmdp_k1e_round_interior",
-    "cmdp_k1e_code_counts", "cmdp_k1e_scan_words", "cmdp_k1s_plan", "cmdp_k1s_plan_desc", "cmdp_det_plan", "cmdp_det_plan_desc", "cmdp_chain_plan_desc", "cmdp_chain_choice",
+    "cmdp_k1e_code_counts", "cmdp_k1e_scan_words", "cmdp_k1e_scan_words_ex", "cmdp_k1s_plan", "cmdp_k1s_plan_desc", "cmdp_det_plan", "cmdp_det_plan_desc", "cmdp_chain_plan_desc", "cmdp_chain_choice",
     "cmdp_k1e_pair_plan", "cmdp_k1e_pair_plan_desc",
     "cmdp_psrl_map_rows", "cmdp_vi_episodic_map", "cmdp_psrl_policy", "cmdp_psrl_evaluate",
     "cmdp_ucrl2_run_logged", "cmdp_psrl_run_logged",
@@ -288,6 +288,7 @@ def load():
         L.cmdp_k1e_round_interior.argtypes = [i32, i32, i64, i32]
         L.cmdp_k1e_code_counts.argtypes = [C.c_uint32, C.c_uint32, i32]
         L.cmdp_k1e_scan_words.argtypes = [vp, i64, i32, i32, i64, i32, i32, vp, f64, vp, vp]
+        L.cmdp_k1e_scan_words_ex.argtypes = [vp, i64, i32, i32, i64, i32, i32, vp, f64, vp, vp]
         L.cmdp_k1s_plan.argtypes = [vp, vp]
         L.cmdp_k1s_plan_desc.argtypes = [C.POINTER(CmdpDesc), i32, i32, vp]
         L.cmdp_det_plan.argtypes = [vp, vp]

@@ -839,6 +839,16 @@ uint32_t cmdp_k1e_code_counts(uint32_t lo, uint32_t hi, int few) {
 
 int cmdp_k1e_scan_words(const uint64_t* words, int64_t n_words, int H, int h0, int64_t n_steps, int nch, int n_codes,
                         const double rv[4], double s0, double* sum, int32_t stats[4]) {
+  if (!stats) return fail(CMDP_ERR_INVALID, "cmdp_k1e_scan_words: null argument");
+  int32_t all[8];
+  const int rc = cmdp_k1e_scan_words_ex(words, n_words, H, h0, n_steps, nch, n_codes, rv, s0, sum, all);
+  if (rc != CMDP_OK) return rc;
+  for (int i = 0; i < 4; ++i) stats[i] = all[i];
+  return CMDP_OK;
+}
+
+int cmdp_k1e_scan_words_ex(const uint64_t* words, int64_t n_words, int H, int h0, int64_t n_steps, int nch, int n_codes,
+                           const double rv[4], double s0, double* sum, int32_t stats[8]) {
   if (!words || !rv || !sum || !stats) return fail(CMDP_ERR_INVALID, "cmdp_k1e_scan_words: null argument");
   // (a segment: the lane counts its steps in an int)
   if (H < 1 || h0 < 0 || h0 >= H || n_steps < 1 || n_steps >= ((int64_t)1 << 31) || nch != (H + 31) / 32 || n_codes < 1 || n_codes > 4)
@@ -854,7 +864,7 @@ int cmdp_k1e_scan_words(const uint64_t* words, int64_t n_words, int H, int h0, i
   K1rStats st;
   k1r_scan(L, ld, st);
   *sum = k1r_sum(L);
-  for (int i = 0; i < 4; ++i) stats[i] = st.n[i];
+  for (int i = 0; i < 8; ++i) stats[i] = st.n[i];
   return CMDP_OK;
 }
 

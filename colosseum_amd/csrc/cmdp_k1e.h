@@ -71,10 +71,14 @@
 //         oracle's and every other kernel's sequential sum).  It loads the code words in tiles of eight, three tiles in
 //         registers.  A PLAIN tile (eight whole single-chunk episodes for every lane of the wavefront: 106 of a wavefront's
 //         125 at C2) costs the step counts per code of its eight words, accumulated straight into registers, and one integer
-//         advance.  Any other tile, and a lane whose plain advance fails, forms the packed step counts n1 | n2 << 11 |
+//         advance.  A lane whose advance fails (its sum leaves a binade inside the tile: ~8 tiles per lane at C2) in a tile
+//         where only ONE nonzero reward value occurs -- sparse rewards: every such tile of C2 -- takes the single-value path
+//         (k1r_single): the order of the steps does not matter then, so the tile's counts are enough, no word is searched.
+//         Any other tile, and a lane that fails with two nonzero values present, forms the packed step counts n1 | n2 << 11 |
 //         n3 << 22 of each word (k1e_code_counts_few for at most three reward codes, k1e_code_counts for four: one
-//         wave-uniform branch per tile) and their prefix sums; the words a lane has to add step by step are already in its
-//         registers.  The lane's arithmetic is __host__ __device__ (K1rLane, k1r_scan) and exported as cmdp_k1e_scan_words.
+//         wave-uniform branch per tile) and their prefix sums -- in a plain tile only when some lane of the wavefront needs
+//         them; the words a lane has to add step by step are already in its registers.  The lane's arithmetic is
+//         __host__ __device__ (K1rLane, k1r_scan) and exported as cmdp_k1e_scan_words / cmdp_k1e_scan_words_ex.
 //         No LDS at all and <= 128 VGPRs: k_rollout_epi holds every byte of the CU's LDS and 4 x 96 VGPRs per SIMD, and a
 //         wavefront of the scan still fits beside it.
 // Results: visit counts, final states, in-episode times, Philox counters and reward sums bit-equal to K1 / K1T / K1U and the
@@ -689,8 +693,9 @@ __host__ __device__ __forceinline__ uint32_t k1r_sel8h(const k1r_u32x4 a, int i)
 //   plain a tile of single-chunk episodes that is neither the lane's first nor its last, for every lane of the wavefront
 //         (one vote), holds 8 H steps: the steps per code of its eight words are accumulated straight into two or three
 //         registers (v_bcnt_u32_b32 adds to its second operand) and ONE integer advance follows -- no packed word, no
-//         prefix sums.  A lane whose advance fails forms the packed prefix sums then, from the words still in its
-//         registers, and takes the slow path under exec.
+//         prefix sums.  A lane whose advance fails takes the single-value path (k1r_single) when at most one nonzero reward
+//         value occurs in the tile; otherwise it forms the packed prefix sums then, from the words still in its registers,
+//         and takes the slow path under exec.
 //   loads when the eight words of a tile exist for every lane of the wavefront (one vote) they are loaded unpredicated;
 //         otherwise word by word under a test against W, unloaded words zero.  Either way the address is the word's scalar
 //         base (advanced in SALU) plus the lane's 8 b: in the loop one v_lshl_add_u64 per load (K1rDeviceLoader).
@@ -698,8 +703,10 @@ __host__ __device__ __forceinline__ uint32_t k1r_sel8h(const k1r_u32x4 a, int i)
 #define K1R_D 3    // tiles in registers: one being summed, the others' loads in flight
 #if defined(__HIP_DEVICE_COMPILE__)
 #define K1R_ALL(x) (__all(x) != 0)   // every lane of the wavefront ...
+#define K1R_ANY(x) (__any(x) != 0)   // some lane of the wavefront ...
 #else
 #define K1R_ALL(x) (x)               // ... the lane itself on the host
+#define K1R_ANY(x) (x)
 #endif
 
 // which paths a scan took (cmdp_k1e_scan_words reports them: the tests prove with them that their inputs reach every path);
@@ -709,13 +716,22 @@ struct K1rNoStats {
   __host__ __device__ __forceinline__ void slow() {}
   __host__ __device__ __forceinline__ void word() {}
   __host__ __device__ __forceinline__ void rebase() {}
+  __host__ __device__ __forceinline__ void single() {}
+  __host__ __device__ __forceinline__ void cross() {}
+  __host__ __device__ __forceinline__ void fadd() {}
 };
 struct K1rStats {
-  int32_t n[4] = {0, 0, 0, 0};   // plain tiles advanced whole, tiles on the slow path, words added step by step, rebases after them
+  // plain tiles advanced whole, tiles on the slow path (the single-value ones among them), words added step by step, rebases
+  // (after a word, or on the single-value path); then the single-value path alone (k1r_single): tiles it resolved, crossing
+  // additions it made, additions of its float64 loop; one reserved
+  int32_t n[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   void plain() { ++n[0]; }
   void slow() { ++n[1]; }
   void word() { ++n[2]; }
   void rebase() { ++n[3]; }
+  void single() { ++n[4]; }
+  void cross() { ++n[5]; }
+  void fadd() { ++n[6]; }
 };
 
 struct K1rLane {
@@ -854,6 +870,71 @@ __host__ __device__ __forceinline__ void k1r_tile_counts(const k1r_u32x8& clo, c
   n3 = c3; n2 = odd - c3; n1 = all - odd - c3;
 }
 
+// The SINGLE-VALUE path of a tile whose whole advance has failed for this lane: among the codes present in the tile (n_c > 0
+// of the tile's totals) at most ONE has a nonzero reward v.  The order of the tile's steps then does not matter -- adding
+// +0.0 leaves the sum as it is (it is never -0.0) and every other addition is the same number -- so the sum after the tile is
+// "v added na times", wherever the na steps sit: no code word, no prefix sum and no search enters.  (Sparse rewards: DeepSea
+// under the random policy -- the goal reward needs H right moves -- FrozenLake, MiniGrid; every crossing tile of C2.)
+//   integer form  the largest j <= na with m + j q < 2^53: a float32 quotient of room = 2^53 - 1 - m and q, cut at na, gives
+//                 an estimate, integer comparisons DECIDE.  Two conversions and a division are each within 2^-24 of their
+//                 result, na <= 256: a quotient below 2^20 is estimated to within 1/4, a larger one is cut at na like the
+//                 true one.  So the estimate is off by one at the most, and one step down (m + j q does not fit) or up (one
+//                 more fits) makes it exact.  j == na: done.  Else the ONE float64 addition that leaves the binade, as the
+//                 oracle makes it, a rebase, and the rest of the steps again.  (A float64 quotient and fix-up LOOPS cost the
+//                 kernel its last registers: 8 to 20 B of scratch.)
+//   float64 loop  no integer form (the sum is zero or subnormal: the first tile of a launch from 0.0) or v is a tie case in
+//                 this binade (k1r_rebase: subnormal v and v >= 2^(k+1) too): v is added na times, one addition per trip,
+//                 and ONE rebase follows.
+// false: the lane is not eligible (a negative reward, two nonzero values present) and goes on to k1r_slow, nothing changed.
+template <class ST>
+__host__ __device__ __forceinline__ bool k1r_single(K1rLane& L, uint32_t n1, uint32_t n2, uint32_t n3, uint32_t steps, ST& st) {
+  const uint32_t n0 = steps - n1 - n2 - n3;
+  // (every member of the lane's arrays is read into a value of its own before it is selected: a select between two loads
+  // becomes a load through a selected address, and the lane would live in scratch)
+  const double rv0 = L.rv[0], rv1 = L.rv[1], rv2 = L.rv[2], rv3 = L.rv[3];
+  const bool a0 = (n0 != 0u) & (rv0 != 0.0), a1 = (n1 != 0u) & (rv1 != 0.0), a2 = (n2 != 0u) & (rv2 != 0.0),
+             a3 = (n3 != 0u) & (rv3 != 0.0);
+  if (!L.bulk_allowed || (int)a0 + (int)a1 + (int)a2 + (int)a3 > 1) return false;
+  st.slow();
+  st.single();
+  // the active code (none: every step adds +0.0), its count and value by selects -- the lane's arrays stay in registers
+  uint32_t na = a3 ? n3 : (a2 ? n2 : (a1 ? n1 : (a0 ? n0 : 0u)));
+  const double v = a3 ? rv3 : (a2 ? rv2 : (a1 ? rv1 : rv0));
+  const uint32_t abit = a3 ? 8u : (a2 ? 4u : (a1 ? 2u : 1u));
+  const unsigned long long LIM = 1ull << 53;
+  while (na) {
+    double S;
+    if (!L.kvalid || (L.tie & abit) != 0u) {
+      S = __builtin_bit_cast(double, L.kvalid ? k1r_compose(L) : L.m);
+      for (uint32_t i = 0; i < na; ++i) { S += v; st.fadd(); }
+      na = 0u;
+    } else {
+      const uint32_t ql0 = L.qlo[0], ql1 = L.qlo[1], ql2 = L.qlo[2], ql3 = L.qlo[3];
+      const uint32_t qh0 = L.qhi[0], qh1 = L.qhi[1], qh2 = L.qhi[2], qh3 = L.qhi[3];
+      const uint32_t ql = a3 ? ql3 : (a2 ? ql2 : (a1 ? ql1 : ql0));
+      const uint32_t qh = a3 ? qh3 : (a2 ? qh2 : (a1 ? qh1 : qh0));   // (< 2^21: j qh fits 32 bits)
+      const unsigned long long q = (unsigned long long)ql | ((unsigned long long)qh << 32);
+      uint32_t j = na;
+      if (q) {
+        const float e = (float)(LIM - 1ull - L.m) / (float)q, en = (float)na;
+        j = (uint32_t)(e < en ? e : en);
+      }
+      unsigned long long t = L.m + (unsigned long long)j * ql + ((unsigned long long)(j * qh) << 32);   // (j q < 2^61)
+      if (j > 0u && t >= LIM) { --j; t -= q; }          // (the estimate is off by one at the most, see above)
+      else if (j < na && t + q < LIM) { ++j; t += q; }
+      L.m = t;
+      if (j == na) break;
+      S = __builtin_bit_cast(double, k1r_compose(L)) + v;   // addition j + 1 leaves the binade
+      st.cross();
+      na -= j + 1u;
+    }
+    L.m = __builtin_bit_cast(unsigned long long, S);
+    k1r_rebase(L);
+    st.rebase();
+  }
+  return true;
+}
+
 // The slow path of a tile whose whole advance has failed for this lane: the first word that does not advance (binary
 // search over the prefix sums P of packed counts and SP of steps; SP holds two sums to a register), everything before it
 // in one piece, that word in float64 step by step exactly as the oracle adds, then the rest of the tile again.  The search
@@ -932,45 +1013,31 @@ __host__ __device__ __forceinline__ void k1r_tile(K1rLane& L, const k1r_u32x8& c
   k1r_u32x4 SP;   // (prefix sums of steps, SP[k] in halfword k & 1 of register k >> 1)
   // plain tiles -- interior ones of single-chunk episodes, for all lanes: every word holds H steps
   const bool plain = L.nch == 1 && K1R_ALL(w0 >= 1 && w0 + K1R_T <= L.W - 1);
+  uint32_t n1, n2, n3, steps;   // the tile's totals
+  bool whole;
   if (plain) {
-    uint32_t n1, n2, n3;
-    bool whole;
+    steps = (uint32_t)(K1R_T * H);
     if (few) {
       k1r_tile_counts_few(clo, chi, n1, n2);
-      whole = k1r_advance(L, n1, n2, 0u, (uint32_t)(K1R_T * H), m2);
+      n3 = 0u;
+      whole = k1r_advance(L, n1, n2, 0u, steps, m2);
     } else {
       k1r_tile_counts(clo, chi, n1, n2, n3);
-      whole = k1r_advance(L, n1, n2, n3, (uint32_t)(K1R_T * H), m2);
+      whole = k1r_advance(L, n1, n2, n3, steps, m2);
     }
     L.tot_left -= K1R_T * H;   // eight full episodes on: the next one may be the segment's last, partial one
     L.e_len = H < L.tot_left ? H : L.tot_left;
     L.ep_left = L.e_len;
-    if (whole) { L.m = m2; st.plain(); return; }
-  }
-  // Every other tile, and the lanes of a plain tile that did not advance: the packed counts of the tile's words (still in
-  // registers) and their prefix sums
-  uint32_t rn[K1R_T];
-  if (few) {
-#pragma unroll
-    for (int k = 0; k < K1R_T; ++k) rn[k] = k1e_code_counts_few(clo[k], chi[k]);
+    if (whole) st.plain();
   } else {
-#pragma unroll
-    for (int k = 0; k < K1R_T; ++k) rn[k] = k1e_code_counts(clo[k], chi[k]);
-  }
-  if (plain) {
-    uint32_t acc = 0u;
-#pragma unroll
-    for (int k = 0; k < K1R_T; ++k) { acc += rn[k]; P[k] = acc; }
-#pragma unroll
-    for (int k = 0; k < K1R_T; k += 2) SP[k >> 1] = (uint32_t)((k + 1) * H) | ((uint32_t)((k + 2) * H) << 16);
-  } else {
-    // the first and the last tile, chunked episodes, ragged ends: 0 steps for a chunk a partial episode does not reach or
-    // a word past the end
+    // the first and the last tile, chunked episodes, ragged ends: the packed counts of the tile's words and their prefix
+    // sums; 0 steps for a chunk a partial episode does not reach or a word past the end
     uint32_t acc = 0u, sacc = 0u;
 #pragma unroll
     for (int k = 0; k < K1R_T; ++k) {
       const int Lk = (w0 + k < L.W) ? (L.ep_left < 0 ? 0 : (L.ep_left < 32 ? L.ep_left : 32)) : 0;
-      acc += Lk > 0 ? rn[k] : 0u;
+      const uint32_t rn = few ? k1e_code_counts_few(clo[k], chi[k]) : k1e_code_counts(clo[k], chi[k]);
+      acc += Lk > 0 ? rn : 0u;
       sacc += (uint32_t)Lk;
       P[k] = acc;
       if (k & 1) SP[k >> 1] |= sacc << 16; else SP[k >> 1] = sacc;
@@ -982,7 +1049,26 @@ __host__ __device__ __forceinline__ void k1r_tile(K1rLane& L, const k1r_u32x8& c
         L.ep_left = L.e_len;
       }
     }
-    if (k1r_advance(L, P[K1R_T - 1], sacc, m2)) { L.m = m2; return; }
+    n1 = acc & 0x7ffu; n2 = (acc >> 11) & 0x7ffu; n3 = acc >> 22;
+    steps = sacc;
+    whole = k1r_advance(L, n1, n2, n3, steps, m2);
+  }
+  if (whole) { L.m = m2; return; }
+  // A lane whose advance fails takes the single-value path when it may (every crossing tile of C2).  Only when some lane of
+  // the wavefront goes on to k1r_slow are the packed counts and the prefix vectors of a plain tile formed, from the words
+  // still in registers
+  const bool done = k1r_single(L, n1, n2, n3, steps, st);
+  if (!K1R_ANY(!done)) return;
+  if (done) return;
+  if (plain) {
+    uint32_t acc = 0u;
+#pragma unroll
+    for (int k = 0; k < K1R_T; ++k) {
+      acc += few ? k1e_code_counts_few(clo[k], chi[k]) : k1e_code_counts(clo[k], chi[k]);
+      P[k] = acc;
+    }
+#pragma unroll
+    for (int k = 0; k < K1R_T; k += 2) SP[k >> 1] = (uint32_t)((k + 1) * H) | ((uint32_t)((k + 2) * H) << 16);
   }
   st.slow();
   k1r_slow(L, clo, chi, P, SP, st);

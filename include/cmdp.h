@@ -190,6 +190,13 @@ uint32_t cmdp_k1e_code_counts(uint32_t lo, uint32_t hi, int few);
    Needs no handle and no device.  No reference counterpart. */
 int cmdp_k1e_scan_words(const uint64_t* words, int64_t n_words, int H, int h0, int64_t n_steps, int nch, int n_codes,
                         const double rv[4], double s0, double* sum, int32_t stats[4]);
+/* ... with the counters of the scan's SINGLE-VALUE path as well (a tile whose whole advance fails and in which at most one
+   code present has a nonzero reward: no code word is searched, see csrc/cmdp_k1e.h, k1r_single).  stats[0..3] as above -- a
+   single-value tile counts as a slow tile, its rebases as rebases, and it never counts a word -- stats[4]: tiles resolved on
+   the single-value path, stats[5]: the float64 additions it made that left a binade, stats[6]: the additions of its float64
+   loop (no integer form, or the value is a tie case), stats[7]: reserved, zero. */
+int cmdp_k1e_scan_words_ex(const uint64_t* words, int64_t n_words, int H, int h0, int64_t n_steps, int nch, int n_codes,
+                           const double rv[4], double s0, double* sum, int32_t stats[8]);
 int cmdp_device_count(void);
 int cmdp_set_device(int device);
 
