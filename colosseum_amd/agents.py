@@ -13,14 +13,56 @@ from .batched import BatchedMDP
 
 
 class _DeviceAgent:
-    """A handle of the library's: `_DESTROY` names the C function that frees it."""
+    """A handle of the library's: `_PREFIX` names the agent's C functions (`<_PREFIX>_destroy` frees it)."""
 
-    _DESTROY = None
+    _PREFIX = None
+
+    def _create(self, env, seeds, *args, create="_create"):
+        """Loads the library, takes one seed per instance, creates the handle with `<_PREFIX><create>(&h, env, seeds, *args)`
+        and ties it to the environment's."""
+        self._lib = L.load()
+        self.env = env
+        seeds = np.ascontiguousarray(seeds, np.int32)
+        assert len(seeds) == env.B
+        self._h = C.c_void_p()
+        L.check(getattr(self._lib, self._PREFIX + create)(C.byref(self._h), env._h, L.ptr(seeds), *args))
+        env._register_agent(self)
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
-            getattr(self._lib, self._DESTROY)(self._h)
+            getattr(self._lib, self._PREFIX + "_destroy")(self._h)
             self._h = C.c_void_p()
+
+    def run_logged(self, desc, n_logs: int):
+        """`MDPLoop.run` for the whole batch in one library call (cmdp_qlearning_run_logged, cmdp_ucrl2_run_logged,
+        cmdp_psrl_run_logged): interaction, policy evaluation at every logging step and the reference's indicators, all
+        without returning to Python; the agents that park their instances take the rows strictly in order and must not have
+        taken a step yet.  `desc` from `vector_tracker.loop_desc`.  Returns (steps [n_logs], values, kinds [n_logs, 17, B],
+        last_training_step, is_training)."""
+        B = self.env.B
+        steps = np.zeros(n_logs, np.int64)
+        values = np.zeros((n_logs, len(L.LOG_COLUMNS), B), np.float64)
+        kinds = np.zeros((n_logs, len(L.LOG_COLUMNS), B), np.uint8)
+        last = np.zeros(B, np.int64)
+        training = np.zeros(B, np.uint8)
+        L.check(getattr(self._lib, self._PREFIX + "_run_logged")(self._h, C.byref(desc), int(n_logs), L.ptr(steps), L.ptr(values),
+                                                                 L.ptr(kinds), L.ptr(last), L.ptr(training)))
+        return steps, values, kinds, last, training.astype(bool)
+
+    def _sa(self, x):
+        """A per-row array of the library's -> list of [S, A] per instance."""
+        return [y.reshape(-1, self.env.A) for y in self.env.split_rows(x)]
+
+    def _mask(self, mask):
+        m = None if mask is None else np.ascontiguousarray(mask, np.uint8)
+        assert m is None or m.shape == (self.env.B,)
+        return m, (range(self.env.B) if m is None else np.flatnonzero(m))
+
+    def _average_reward(self, mask):
+        m, sel = self._mask(mask)
+        avg, kind = np.zeros(self.env.B, np.float64), np.zeros(self.env.B, np.int32)
+        L.check(getattr(self._lib, self._PREFIX + "_average_reward")(self._h, L.ptr(m), L.ptr(avg), L.ptr(kind)))
+        return [np.float32(avg[b]) if kind[b] else np.float64(avg[b]) for b in sel]
 
     def __del__(self):
         try:
@@ -30,19 +72,12 @@ class _DeviceAgent:
 
 
 class BatchedQLearningEpisodic(_DeviceAgent):
-    _DESTROY = "cmdp_qlearning_destroy"
+    _PREFIX = "cmdp_qlearning"
 
     def __init__(self, env: BatchedMDP, seeds: Sequence[int], optimization_horizon: int, p: float, c_1: float,
                  c_2: Optional[float] = None, min_at: float = 0.0, UCB_type: str = "hoeffding"):
         ucb = {"hoeffding": 0, "bernstein": 1}[UCB_type.lower()]
-        self._lib = L.load()
-        self.env = env
-        seeds = np.ascontiguousarray(seeds, np.int32)
-        assert len(seeds) == env.B
-        self._h = C.c_void_p()
-        L.check(self._lib.cmdp_qlearning_create(C.byref(self._h), env._h, L.ptr(seeds), int(optimization_horizon), float(p),
-                                                float(c_1), float(c_2 or 0.0), float(min_at), ucb))
-        env._register_agent(self)
+        self._create(env, seeds, int(optimization_horizon), float(p), float(c_1), float(c_2 or 0.0), float(min_at), ucb)
 
     def run(self, n_steps: int, train=True, trace_actions: bool = False):
         """n_steps of select_action -> step -> step_update per instance.  `train`: bool or per-instance mask.
@@ -55,20 +90,6 @@ class BatchedQLearningEpisodic(_DeviceAgent):
             mask = np.ascontiguousarray(np.broadcast_to(np.asarray(train, bool), (self.env.B,)), np.uint8)
         L.check(self._lib.cmdp_qlearning_run(self._h, n_steps, L.ptr(mask), L.ptr(acts), L.ptr(rsum)))
         return dict(cumulative_reward=rsum, actions=acts)
-
-    def run_logged(self, desc, n_logs: int):
-        """`MDPLoop.run` for the whole batch in one library call (cmdp_qlearning_run_logged): interaction, policy
-        evaluation at every logging step and the reference's indicators, all without returning to Python.  `desc` from
-        `vector_tracker.loop_desc`.  Returns (steps [n_logs], values, kinds [n_logs, 17, B], last_training_step, is_training)."""
-        B = self.env.B
-        steps = np.zeros(n_logs, np.int64)
-        values = np.zeros((n_logs, len(L.LOG_COLUMNS), B), np.float64)
-        kinds = np.zeros((n_logs, len(L.LOG_COLUMNS), B), np.uint8)
-        last = np.zeros(B, np.int64)
-        training = np.zeros(B, np.uint8)
-        L.check(self._lib.cmdp_qlearning_run_logged(self._h, C.byref(desc), int(n_logs), L.ptr(steps), L.ptr(values), L.ptr(kinds),
-                                                    L.ptr(last), L.ptr(training)))
-        return steps, values, kinds, last, training.astype(bool)
 
     def evaluate(self) -> np.ndarray:
         """V[0, :] (concatenated over instances) of the current greedy policies, policy and evaluation on device."""
@@ -93,22 +114,15 @@ class BatchedQLearningContinuous(BatchedQLearningEpisodic):
 
     def __init__(self, env: BatchedMDP, seeds: Sequence[int], optimization_horizon: int, min_at: float = 0.0,
                  confidence: float = 0.95, span_approx_weight: float = 1.0, h_weight: float = 1.0):
-        self._lib = L.load()
-        self.env = env
-        seeds = np.ascontiguousarray(seeds, np.int32)
-        assert len(seeds) == env.B
-        self._h = C.c_void_p()
-        L.check(self._lib.cmdp_qlearning_continuous_create(C.byref(self._h), env._h, L.ptr(seeds), int(optimization_horizon),
-                                                           float(min_at), float(confidence), float(span_approx_weight),
-                                                           float(h_weight)))
-        env._register_agent(self)
+        self._create(env, seeds, int(optimization_horizon), float(min_at), float(confidence), float(span_approx_weight),
+                     float(h_weight), create="_continuous_create")
 
     def tables(self):
         env = self.env
         Q = np.zeros(int(env.row_off[-1]), np.float64)  # float64 tables (NEP 50: float32 zeros + numpy float64 H)
         N = np.zeros(int(env.row_off[-1]), np.int32)
         L.check(self._lib.cmdp_qlearning_tables(self._h, L.ptr(Q), L.ptr(N)))
-        return ([x.reshape(-1, env.A) for x in env.split_rows(Q)], [x.reshape(-1, env.A) for x in env.split_rows(N)])
+        return self._sa(Q), self._sa(N)
 
     def evaluate(self):
         raise NotImplementedError("use policy(): continuous regrets come from the stationary distribution")
@@ -116,27 +130,19 @@ class BatchedQLearningContinuous(BatchedQLearningEpisodic):
     def average_reward(self, mask=None) -> list:
         """`get_average_reward` of the current greedy policies from the current states, on the device (kernel K9): a
         list of numpy scalars (np.float32 where the reference's value is one) for the instances selected by `mask`."""
-        B = self.env.B
-        m = None if mask is None else np.ascontiguousarray(mask, np.uint8)
-        avg = np.zeros(B, np.float64)
-        kind = np.zeros(B, np.int32)
-        L.check(self._lib.cmdp_qlearning_average_reward(self._h, L.ptr(m), L.ptr(avg), L.ptr(kind)))
-        sel = range(B) if m is None else np.flatnonzero(m)
-        return [np.float32(avg[b]) if kind[b] else np.float64(avg[b]) for b in sel]
+        return self._average_reward(mask)
 
     def policy(self):
         """argmax_2d greedy policies (RandomState(42) tie-break), per instance [S, A]."""
-        env = self.env
-        pi = np.zeros(int(env.row_off[-1]), np.float32)
+        pi = np.zeros(int(self.env.row_off[-1]), np.float32)
         L.check(self._lib.cmdp_qlearning_policy(self._h, L.ptr(pi)))
-        return [x.reshape(-1, env.A) for x in env.split_rows(pi)]
+        return self._sa(pi)
 
 
 class _ParkAndSolveAgent(_DeviceAgent):
     """What the agents that park their instances for a solve share (csrc: ParkAgent): the layout of the model's tables (per
-    row the distinct successors), run(), stats().  `_PREFIX` names the agent's C functions, `_STATS` its counters."""
+    row the distinct successors), run(), stats().  `_STATS` names the agent's counters."""
 
-    _PREFIX = None
     _STATS = ()
 
     def _fetch_layout(self):
@@ -164,21 +170,6 @@ class _ParkAndSolveAgent(_DeviceAgent):
                                                           L.ptr(acts), L.ptr(obs), L.ptr(rew), L.ptr(rsum), L.ptr(taken)))
         return dict(cumulative_reward=rsum, steps_taken=taken, actions=acts, observations=obs, rewards=rew)
 
-    def run_logged(self, desc, n_logs: int):
-        """`MDPLoop.run` for the whole batch in one library call (cmdp_ucrl2_run_logged / cmdp_psrl_run_logged): the rows
-        strictly in order, interaction, evaluation and indicators without returning to Python.  `desc` from
-        `vector_tracker.loop_desc`; the agent must not have taken a step yet.  Returns what
-        `BatchedQLearningEpisodic.run_logged` returns."""
-        B = self.env.B
-        steps = np.zeros(n_logs, np.int64)
-        values = np.zeros((n_logs, len(L.LOG_COLUMNS), B), np.float64)
-        kinds = np.zeros((n_logs, len(L.LOG_COLUMNS), B), np.uint8)
-        last = np.zeros(B, np.int64)
-        training = np.zeros(B, np.uint8)
-        L.check(getattr(self._lib, self._PREFIX + "_run_logged")(self._h, C.byref(desc), int(n_logs), L.ptr(steps), L.ptr(values),
-                                                                 L.ptr(kinds), L.ptr(last), L.ptr(training)))
-        return steps, values, kinds, last, training.astype(bool)
-
     def _dense(self, values, dtype, fill=None, uniform=None):
         """Layout values as dense [S, A, S] arrays per instance; elsewhere `fill[b]` (default 0), and rows with
         `uniform` > 0 hold that value at every state."""
@@ -195,11 +186,6 @@ class _ParkAndSolveAgent(_DeviceAgent):
             out.append(M.reshape(S, env.A, S))
         return out
 
-    def _mask(self, mask):
-        m = None if mask is None else np.ascontiguousarray(mask, np.uint8)
-        assert m is None or m.shape == (self.env.B,)
-        return m, (range(self.env.B) if m is None else np.flatnonzero(m))
-
     def _stats(self) -> dict:
         v, out = C.c_double(), {}
         for k, w in self._STATS:
@@ -208,14 +194,44 @@ class _ParkAndSolveAgent(_DeviceAgent):
         return out
 
 
-class BatchedUCRL2Continuous(_ParkAndSolveAgent):
+class _ContinuousModelPolicy:
+    """`policy()`, `policy_solve()` and `average_reward()` of the continuous agents that solve a model for their greedy policy:
+    UCRL2 its estimated model (ucrl2.py:80-83, kernel K14), PSRL the MAP estimate of its posterior
+    (infinite_horizon/posterior_sampling.py:174-178, by the route of `policy_solver`).  Touch nothing the agent acts or
+    learns with."""
+
+    def policy(self, mask=None):
+        """argmax_2d (RandomState(42) tie-break) of discounted value iteration on the agent's model, on the device, per
+        instance [S, A]; with `mask`, for the selected instances only, in their order."""
+        m, sel = self._mask(mask)
+        pi = np.zeros(int(self.env.row_off[-1]), np.float32)
+        L.check(getattr(self._lib, self._PREFIX + "_policy")(self._h, L.ptr(m), L.ptr(pi), None, None, None))
+        rows = self._sa(pi)
+        return [rows[b] for b in sel]
+
+    def policy_solve(self, mask=None):
+        """The solve behind `policy()`: `Q` per instance [S, A] float32, `sweeps` and `scheme` (L.SCHEME_JACOBI /
+        L.SCHEME_GAUSS_SEIDEL, the reference's rule on the model) [B]; with `mask`, zeros elsewhere."""
+        m, _ = self._mask(mask)
+        Q = np.zeros(int(self.env.row_off[-1]), np.float32)
+        sweeps, scheme = np.zeros(self.env.B, np.int64), np.zeros(self.env.B, np.int32)
+        L.check(getattr(self._lib, self._PREFIX + "_policy")(self._h, L.ptr(m), None, L.ptr(Q), L.ptr(sweeps), L.ptr(scheme)))
+        return dict(Q=self._sa(Q), sweeps=sweeps, scheme=scheme)
+
+    def average_reward(self, mask=None) -> list:
+        """`get_average_reward` of `policy()` from the environments' current states, on the device (the solve, then kernel
+        K9): a list of numpy scalars (np.float32 where the reference's value is one) for the instances selected by `mask`."""
+        return self._average_reward(mask)
+
+
+class BatchedUCRL2Continuous(_ContinuousModelPolicy, _ParkAndSolveAgent):
     """One reference `UCRL2Continuous` (colosseum/agent/agents/infinite_horizon/ucrl2.py) per instance of a continuous
     `BatchedMDP`, driven as `MDPLoop.run` drives it: interaction, counts, confidence bounds, the estimated model and the
     optimistic solves (extended value iteration, kernel K10) stay on the device (kernel K11, csrc/cmdp_ucrl2.h).  The
     keyword names and defaults are the reference's.  `bound_type_rew="bernstein"` is refused: the reference raises
     AttributeError there at its first solve."""
 
-    _DESTROY, _PREFIX = "cmdp_ucrl2_destroy", "cmdp_ucrl2"
+    _PREFIX = "cmdp_ucrl2"
     _STATS = (("rounds", L.STAT_UCRL2_ROUNDS), ("solves", L.STAT_UCRL2_SOLVES), ("unconverged", L.STAT_UCRL2_UNCONVERGED),
               ("round_ms", L.STAT_UCRL2_ROUND_MS), ("wait_ms", L.STAT_UCRL2_WAIT_MS),
               ("policy_kernel_ms", L.STAT_UCRL2_POLICY_KERNEL_MS), ("policy_solved", L.STAT_UCRL2_POLICY_SOLVED),
@@ -225,19 +241,13 @@ class BatchedUCRL2Continuous(_ParkAndSolveAgent):
     def __init__(self, env: BatchedMDP, seeds: Sequence[int], optimization_horizon: int, alpha_r=1.0, alpha_p=1.0,
                  bound_type_p="_chernoff", bound_type_rew="_chernoff", epsilon_greedy=None, boltzmann_temperature=None):
         assert bound_type_p in self._BOUNDS and bound_type_rew in self._BOUNDS  # ucrl2.py:130-131
-        self._lib = L.load()
-        self.env = env
-        seeds = np.ascontiguousarray(seeds, np.int32)
-        assert len(seeds) == env.B
         actor = L.ACTOR_GREEDY
         if epsilon_greedy is not None:
             actor = L.ACTOR_EPSILON_GREEDY
         elif boltzmann_temperature is not None:
             actor = L.ACTOR_BOLTZMANN
-        self._h = C.c_void_p()
-        L.check(self._lib.cmdp_ucrl2_create(C.byref(self._h), env._h, L.ptr(seeds), int(optimization_horizon), float(alpha_r),
-                                            float(alpha_p), self._BOUNDS[bound_type_p], self._BOUNDS[bound_type_rew], actor))
-        env._register_agent(self)
+        self._create(env, seeds, int(optimization_horizon), float(alpha_r), float(alpha_p), self._BOUNDS[bound_type_p],
+                     self._BOUNDS[bound_type_rew], actor)
         self._fetch_layout()
 
     def run(self, n_steps: int, train=True, trace: bool = False, stop_at_episode_end: bool = False):
@@ -257,7 +267,7 @@ class BatchedUCRL2Continuous(_ParkAndSolveAgent):
         it, ep, delta = np.zeros(env.B, np.int64), np.zeros(env.B, np.int64), np.zeros(env.B, np.float64)
         L.check(self._lib.cmdp_ucrl2_model(self._h, L.ptr(N), L.ptr(P), L.ptr(uni), L.ptr(er), L.ptr(vr), L.ptr(ht), L.ptr(it),
                                            L.ptr(ep), L.ptr(delta)))
-        sa = lambda x: [y.reshape(-1, env.A) for y in env.split_rows(x)]  # noqa: E731
+        sa = self._sa
         return dict(N=self._dense(N, np.int32), P=self._dense(P, np.float32, uniform=uni), estimated_rewards=sa(er),
                     variance_proxy_reward=sa(vr), estimated_holding_times=sa(ht), iteration=it, episode=ep, delta=delta)
 
@@ -272,39 +282,9 @@ class BatchedUCRL2Continuous(_ParkAndSolveAgent):
         span, sweeps, status = np.zeros(env.B, np.float64), np.zeros(env.B, np.int64), np.zeros(env.B, np.int32)
         L.check(self._lib.cmdp_ucrl2_last_solve(self._h, L.ptr(P), L.ptr(uni), L.ptr(er), L.ptr(br), L.ptr(bp), L.ptr(Q),
                                                 L.ptr(span), L.ptr(sweeps), L.ptr(status)))
-        sa = lambda x: [y.reshape(-1, env.A) for y in env.split_rows(x)]  # noqa: E731
+        sa = self._sa
         return dict(P=self._dense(P, np.float32, uniform=uni), estimated_rewards=sa(er), beta_r=sa(br), beta_p0=sa(bp), Q=sa(Q),
                     span=span, sweeps=sweeps, status=status)
-
-    def policy(self, mask=None):
-        """ucrl2.py:80-83 on the device: argmax_2d (RandomState(42) tie-break) of discounted value iteration on the estimated
-        model (kernel K14), per instance [S, A]; with `mask`, for the selected instances only, in their order."""
-        env = self.env
-        m, sel = self._mask(mask)
-        pi = np.zeros(int(env.row_off[-1]), np.float32)
-        L.check(self._lib.cmdp_ucrl2_policy(self._h, L.ptr(m), L.ptr(pi), None, None, None))
-        rows = env.split_rows(pi)
-        return [rows[b].reshape(-1, env.A) for b in sel]
-
-    def policy_solve(self, mask=None):
-        """The solve behind `policy()`: `Q` per instance [S, A] float32, `sweeps` and `scheme` (L.SCHEME_JACOBI /
-        L.SCHEME_GAUSS_SEIDEL, the reference's rule on the estimated model) [B]; with `mask`, zeros elsewhere."""
-        env = self.env
-        m, _ = self._mask(mask)
-        Q = np.zeros(int(env.row_off[-1]), np.float32)
-        sweeps, scheme = np.zeros(env.B, np.int64), np.zeros(env.B, np.int32)
-        L.check(self._lib.cmdp_ucrl2_policy(self._h, L.ptr(m), None, L.ptr(Q), L.ptr(sweeps), L.ptr(scheme)))
-        return dict(Q=[x.reshape(-1, env.A) for x in env.split_rows(Q)], sweeps=sweeps, scheme=scheme)
-
-    def average_reward(self, mask=None) -> list:
-        """`get_average_reward` of `policy()` from the environments' current states, on the device (K14, then kernel K9): a
-        list of numpy scalars (np.float32 where the reference's value is one) for the instances selected by `mask`."""
-        B = self.env.B
-        m, sel = self._mask(mask)
-        avg = np.zeros(B, np.float64)
-        kind = np.zeros(B, np.int32)
-        L.check(self._lib.cmdp_ucrl2_average_reward(self._h, L.ptr(m), L.ptr(avg), L.ptr(kind)))
-        return [np.float32(avg[b]) if kind[b] else np.float64(avg[b]) for b in sel]
 
     def current_optimal_stochastic_policy(self):
         """ucrl2.py:80-83 per instance: `policy()`."""
@@ -360,10 +340,6 @@ class _PosteriorSamplingAgent(_ParkAndSolveAgent):
         for prms in (rewards_prior_prms, transitions_prior_prms):
             if prms is not None and (isinstance(prms, dict) or type(prms[0]) in (list, tuple, np.ndarray)):
                 raise NotImplementedError("per-pair prior lists are not built: give one parameter list for all pairs")
-        self._lib = L.load()
-        self.env = env
-        seeds = np.ascontiguousarray(seeds, np.int32)
-        assert len(seeds) == env.B
         if rewards_prior_prms is None:
             rewards_prior_prms = [float(env.rewards_range[1]), 1, 1, 1]
         assert len(rewards_prior_prms) == 4 and (transitions_prior_prms is None or len(transitions_prior_prms) == 1)
@@ -377,11 +353,16 @@ class _PosteriorSamplingAgent(_ParkAndSolveAgent):
             tprior = np.array([np.tile([1.0 / int(S)], (1, 1, 1)).astype(np.float32)[0, 0, 0] for S in env.n_states], np.float32)
         else:
             tprior = np.full(env.B, np.tile(transitions_prior_prms, (1, 1, 1)).astype(np.float32)[0, 0, 0], np.float32)
-        self._h = C.c_void_p()
-        L.check(getattr(self._lib, self._PREFIX + "_create")(C.byref(self._h), env._h, L.ptr(seeds), int(optimization_horizon),
-                                                             L.ptr(rprior), L.ptr(tprior), self._SAMPLERS[sampler], L.ACTOR_GREEDY))
-        env._register_agent(self)
+        self._create(env, seeds, int(optimization_horizon), L.ptr(rprior), L.ptr(tprior), self._SAMPLERS[sampler], L.ACTOR_GREEDY)
         self._fetch_layout()
+
+    def _sample_T(self, fetch):
+        """The last posterior sample's `T` per instance [S, A, S]: `fetch(T)` fills the library's dense, unpadded array."""
+        env = self.env
+        sizes = [int(S) * env.A * int(S) for S in env.n_states]
+        T = np.zeros(sum(sizes), np.float32)
+        fetch(T)
+        return [x.reshape(int(S), env.A, int(S)) for x, S in zip(np.split(T, np.cumsum(sizes)[:-1]), env.n_states)]
 
     def episode_end_update(self):
         """The reference agent's `episode_end_update()` for every instance: a new posterior sample on the tables as they are,
@@ -408,7 +389,7 @@ class BatchedPSRLEpisodic(_PosteriorSamplingAgent):
     distributions from a counter-based stream, a pure function of (seed, episode, tables).  Per-pair prior lists, the
     N_N reward model and the exploration actors are refused."""
 
-    _DESTROY, _PREFIX = "cmdp_psrl_destroy", "cmdp_psrl"
+    _PREFIX = "cmdp_psrl"
 
     def run(self, n_steps: int, train=True, trace: bool = False, stop_at_episode_end: bool = False):
         """n_steps of select_action -> step -> step_update -> (episode_end_update, reset) per instance; with
@@ -432,20 +413,10 @@ class BatchedPSRLEpisodic(_PosteriorSamplingAgent):
     def last_sample(self):
         """The last posterior sample of every instance, `T` [S, A, S] and `R` [S, A] float32, and the `Q` [H + 1, S, A]
         the actor holds (solved on them)."""
-        env, H = self.env, int(self.env.H)
-        R = int(env.row_off[-1])
-        nT = int(sum(int(S) * env.A * int(S) for S in env.n_states))
-        T, Rs, Q = np.zeros(nT, np.float32), np.zeros(R, np.float32), np.zeros((H + 1) * R, np.float32)
-        L.check(self._lib.cmdp_psrl_last_sample(self._h, L.ptr(T), L.ptr(Rs), L.ptr(Q)))
-        Ts, Qs, o = [], [], 0
-        for b in range(env.B):
-            S = int(env.n_states[b])
-            n = S * env.A * S
-            Ts.append(T[o:o + n].reshape(S, env.A, S))
-            o += n
-            q0 = (H + 1) * int(env.row_off[b])
-            Qs.append(Q[q0:q0 + (H + 1) * S * env.A].reshape(H + 1, S, env.A))
-        return dict(T=Ts, R=[x.reshape(-1, env.A) for x in env.split_rows(Rs)], Q=Qs)
+        R = int(self.env.row_off[-1])
+        Rs, Q = np.zeros(R, np.float32), np.zeros((int(self.env.H) + 1) * R, np.float32)
+        Ts = self._sample_T(lambda T: L.check(self._lib.cmdp_psrl_last_sample(self._h, L.ptr(T), L.ptr(Rs), L.ptr(Q))))
+        return dict(T=Ts, R=self._sa(Rs), Q=self._layers(Q))
 
     def _layers(self, x):
         """A per-instance [H + 1][S][A] array of the library's -> list of [H + 1, S, A]."""
@@ -488,7 +459,7 @@ class BatchedPSRLEpisodic(_PosteriorSamplingAgent):
         return self._stats()
 
 
-class BatchedPSRLContinuous(_PosteriorSamplingAgent):
+class BatchedPSRLContinuous(_ContinuousModelPolicy, _PosteriorSamplingAgent):
     """One reference `PSRLContinuous` (colosseum/agent/agents/infinite_horizon/posterior_sampling.py) with PLAIN posterior
     sampling -- the reference's own `no_optimistic_sampling=True` path -- per instance of a continuous `BatchedMDP`, driven as
     `MDPLoop.run` drives it: interaction, the N_NIG / M_DIR posterior tables (K12's), the artificial-episode rule, the
@@ -500,7 +471,7 @@ class BatchedPSRLContinuous(_PosteriorSamplingAgent):
     reference switches by itself), `truncate_reward_with_max=True`, `min_steps_before_new_episode != 0`, the exploration
     actors, and what `BatchedPSRLEpisodic` refuses of the priors.  `run_logged` is not built."""
 
-    _DESTROY, _PREFIX = "cmdp_psrlc_destroy", "cmdp_psrlc"
+    _PREFIX = "cmdp_psrlc"
     _STATS = _PosteriorSamplingAgent._STATS + (("unconverged", L.STAT_PSRL_UNCONVERGED), ("sweeps", L.STAT_PSRL_SWEEPS))
 
     def __init__(self, env: BatchedMDP, seeds: Sequence[int], optimization_horizon: int, reward_prior_model=None,
@@ -541,10 +512,9 @@ class BatchedPSRLContinuous(_PosteriorSamplingAgent):
         prior, ep = np.zeros(env.B, np.float32), np.zeros(env.B, np.int64)
         nsa, nu = np.zeros(R, np.int32), np.zeros(R, np.int32)
         L.check(self._lib.cmdp_psrlc_model(self._h, L.ptr(rp), L.ptr(tp), L.ptr(prior), L.ptr(nsa), L.ptr(nu), L.ptr(ep)))
-        sa = lambda x: [y.reshape(-1, env.A) for y in env.split_rows(x)]  # noqa: E731
         return dict(transitions=self._dense(tp, np.float32, fill=prior),
-                    rewards=[x.reshape(-1, env.A, 4) for x in env.split_rows(rp.reshape(R, 4))], N_sa=sa(nsa), nu_k=sa(nu),
-                    episode=ep)
+                    rewards=[x.reshape(-1, env.A, 4) for x in env.split_rows(rp.reshape(R, 4))], N_sa=self._sa(nsa),
+                    nu_k=self._sa(nu), episode=ep)
 
     def last_sample(self):
         """The last posterior sample of every instance, `T` [S, A, S] and `R` [S, A] float32, the `Q` [S, A] the actor holds
@@ -552,18 +522,11 @@ class BatchedPSRLContinuous(_PosteriorSamplingAgent):
         (0, or L.ERR_MAX_ITER: Q is then the last sweep's) [B]."""
         env = self.env
         R = int(env.row_off[-1])
-        nT = int(sum(int(S) * env.A * int(S) for S in env.n_states))
-        T, Rs, Q = np.zeros(nT, np.float32), np.zeros(R, np.float32), np.zeros(R, np.float32)
+        Rs, Q = np.zeros(R, np.float32), np.zeros(R, np.float32)
         sweeps, scheme, status = np.zeros(env.B, np.int64), np.zeros(env.B, np.int32), np.zeros(env.B, np.int32)
-        L.check(self._lib.cmdp_psrlc_last_sample(self._h, L.ptr(T), L.ptr(Rs), L.ptr(Q), L.ptr(sweeps), L.ptr(scheme),
-                                                 L.ptr(status)))
-        Ts, o = [], 0
-        for b in range(env.B):
-            S = int(env.n_states[b])
-            Ts.append(T[o:o + S * env.A * S].reshape(S, env.A, S))
-            o += S * env.A * S
-        sa = lambda x: [y.reshape(-1, env.A) for y in env.split_rows(x)]  # noqa: E731
-        return dict(T=Ts, R=sa(Rs), Q=sa(Q), sweeps=sweeps, scheme=scheme, status=status)
+        Ts = self._sample_T(lambda T: L.check(self._lib.cmdp_psrlc_last_sample(self._h, L.ptr(T), L.ptr(Rs), L.ptr(Q), L.ptr(sweeps),
+                                                                                L.ptr(scheme), L.ptr(status))))
+        return dict(T=Ts, R=self._sa(Rs), Q=self._sa(Q), sweeps=sweeps, scheme=scheme, status=status)
 
     _POLICY_SOLVERS = ("dense", "tables")
 
@@ -582,36 +545,6 @@ class BatchedPSRLContinuous(_PosteriorSamplingAgent):
     @property
     def policy_solver(self) -> str:
         return getattr(self, "_policy_solver", "dense")
-
-    def policy(self, mask=None):
-        """posterior_sampling.py:174-178 on the device: argmax_2d (RandomState(42) tie-break) of discounted value iteration
-        on the MAP estimate of the model, per instance [S, A]; with `mask`, for the selected instances only, in their order.
-        The solve takes the route of `policy_solver`.  Touches nothing the agent acts or learns with."""
-        env = self.env
-        m, sel = self._mask(mask)
-        pi = np.zeros(int(env.row_off[-1]), np.float32)
-        L.check(self._lib.cmdp_psrlc_policy(self._h, L.ptr(m), L.ptr(pi), None, None, None))
-        rows = env.split_rows(pi)
-        return [rows[b].reshape(-1, env.A) for b in sel]
-
-    def policy_solve(self, mask=None):
-        """The solve behind `policy()`, by the route of `policy_solver` (k_vi_discounted_dense on the dense MAP model, or K17
-        on the tables): `Q` per instance [S, A] float32, `sweeps` and `scheme` [B]; with `mask`, zeros elsewhere."""
-        env = self.env
-        m, _ = self._mask(mask)
-        Q = np.zeros(int(env.row_off[-1]), np.float32)
-        sweeps, scheme = np.zeros(env.B, np.int64), np.zeros(env.B, np.int32)
-        L.check(self._lib.cmdp_psrlc_policy(self._h, L.ptr(m), None, L.ptr(Q), L.ptr(sweeps), L.ptr(scheme)))
-        return dict(Q=[x.reshape(-1, env.A) for x in env.split_rows(Q)], sweeps=sweeps, scheme=scheme)
-
-    def average_reward(self, mask=None) -> list:
-        """`get_average_reward` of `policy()` (solved by the route of `policy_solver`) from the environments' current states,
-        on the device: a list of numpy scalars (np.float32 where the reference's value is one) for the instances selected by
-        `mask`."""
-        m, sel = self._mask(mask)
-        avg, kind = np.zeros(self.env.B, np.float64), np.zeros(self.env.B, np.int32)
-        L.check(self._lib.cmdp_psrlc_average_reward(self._h, L.ptr(m), L.ptr(avg), L.ptr(kind)))
-        return [np.float32(avg[b]) if kind[b] else np.float64(avg[b]) for b in sel]
 
     def stats(self) -> dict:
         """As `BatchedPSRLEpisodic.stats`, with `unconverged` (solves that reached the sweep limit; the actor then holds the

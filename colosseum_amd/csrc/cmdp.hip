@@ -3093,6 +3093,22 @@ int agent_stage_run(AgentBase* a, size_t NB, bool trace, const uint8_t* train_ma
   return CMDP_OK;
 }
 
+// The policy stage of an agent that solves a model for its greedy policy (UCRL2: K14; PSRL: K15; continuous PSRL: K13 on the
+// dense MAP model or K17): everything policy(), policy_solve(), evaluate(), average_reward() and a logged row share.
+// Allocated by the first request.  `layers` is 1 for the continuous agents and H + 1 for the episodic one.
+struct PolicyStage {
+  int layers = 0;
+  DevBuf<float> d_Q, d_V, d_pi;         // [layers][rows], [layers][states], [layers][rows] one-hot
+  DevBuf<int64_t> d_sweeps;             // [B], iterative solvers only -- as d_scheme and d_status
+  DevBuf<int32_t> d_scheme, d_status, d_list;
+  std::vector<int32_t> asked, todo, status;   // the request: instances the caller wants back, instances to solve; their status
+  hipEvent_t ev[2] = {nullptr, nullptr};      // around the solve
+  ~PolicyStage() {
+    for (hipEvent_t e : ev)
+      if (e) (void)hipEventDestroy(e);
+  }
+};
+
 // ---- agents that park their instances for a solve (UCRL2: K11, PSRL: K12) -------------------------------------------------
 // A walk kernel steps every instance until it has taken the call's steps or its (artificial) episode ends; the instances
 // that parked are solved in one round of kernels, released, and walked again.
@@ -3108,6 +3124,7 @@ struct ParkAgent : AgentBase {
   void* walk_dst = nullptr;
   const void* walk_src = nullptr;
   size_t walk_bytes = 0;
+  PolicyStage pol;
 
   ParkCall call() const { return ParkCall{d_left.p, d_taken.p, d_park.p, d_park.p + 2}; }
 };
@@ -3259,6 +3276,96 @@ int park_run(ParkAgent* a, int64_t n_steps, int stop_at_episode_end, const uint8
     if (steps_taken) steps_taken[b] = taken[b];
   }
   return visits_commit(h, n_steps, rc);
+}
+
+// A request to the policy stage begins here: the stage's buffers (first request), then `asked` = the instances of the host
+// mask (null: all) and `todo` = `asked`, which the agent may narrow before policy_stage (UCRL2 drops unchanged models).
+int policy_select(ParkAgent* a, int layers, bool iterative, const uint8_t* mask) {
+  cmdp_t* h = a->env;
+  hipStream_t st = h->stream;
+  const int B = h->B;
+  PolicyStage& p = a->pol;
+  if (!p.layers) {
+    const size_t nq = (size_t)layers * h->n_rows;
+    AGENT_ZERO(pol.d_Q, nq); AGENT_ZERO(pol.d_V, (size_t)layers * h->n_states); AGENT_ZERO(pol.d_pi, nq);
+    if (iterative) { AGENT_ZERO(pol.d_sweeps, B); AGENT_ZERO(pol.d_scheme, B); AGENT_ZERO(pol.d_status, B); }
+    HIP_TRY(p.d_list.alloc((size_t)B));
+    for (hipEvent_t& e : p.ev) HIP_TRY(hipEventCreate(&e));
+    p.layers = layers;
+  }
+  p.asked.clear();
+  for (int b = 0; b < B; ++b)
+    if (!mask || mask[b]) p.asked.push_back(b);
+  p.todo = p.asked;
+  return CMDP_OK;
+}
+
+// Enqueues the request: `solve(list, count)` launches the agent's solver for the `count` instances of `todo` (list: on the
+// device, null when that is the whole batch) into d_Q / d_V / d_sweeps / d_scheme / d_status; then the greedy policy of the
+// first `pi_layers` layers of Q into d_pi (0: no policy wanted), for every instance -- an instance outside `todo` gets the
+// policy of the Q it was last solved to -- and the status's read-back.  With nothing to solve the stage holds what it held.
+// `todo` is read by the upload: it stays as it is until policy_finish.
+template <typename Solve>
+int policy_stage(ParkAgent* a, int pi_layers, Solve&& solve) {
+  cmdp_t* h = a->env;
+  hipStream_t st = h->stream;
+  const int B = h->B;
+  PolicyStage& p = a->pol;
+  const int count = (int)p.todo.size();
+  if (count == 0) return CMDP_OK;
+  const int32_t* list = nullptr;
+  if (count < B) {
+    HIP_TRY(p.d_list.upload(p.todo.data(), (size_t)count, st));
+    list = p.d_list.p;
+  }
+  HIP_TRY(hipEventRecord(p.ev[0], st));
+  if (int rc = solve(list, count)) return rc;
+  HIP_TRY(hipEventRecord(p.ev[1], st));
+  if (pi_layers > 0) {
+    hipLaunchKernelGGL(k_greedy_policy_episodic<float>, dim3(B), dim3(64), 0, st, B, h->A, pi_layers, p.layers, h->d_state_off.p,
+                       p.d_Q.p, p.d_pi.p);
+    HIP_TRY(hipGetLastError());
+  }
+  p.status.assign((size_t)B, 0);
+  if (p.d_status.p) HIP_TRY(hipMemcpyAsync(p.status.data(), p.d_status.p, sizeof(int32_t) * B, hipMemcpyDeviceToHost, st));
+  return CMDP_OK;
+}
+
+// Waits for the stream -- the request and whatever the caller enqueued behind it -- leaves the solve's time in *ms and fails
+// on the first instance of `todo` that hit its sweep limit (iterative solvers; `model` and `max_sweeps` are for that text)
+int policy_finish(ParkAgent* a, double* ms, const char* model, long long max_sweeps) {
+  PolicyStage& p = a->pol;
+  HIP_TRY(hipStreamSynchronize(a->env->stream));
+  if (p.todo.empty()) return CMDP_OK;
+  float t = 0.0f;
+  HIP_TRY(hipEventElapsedTime(&t, p.ev[0], p.ev[1]));
+  *ms = (double)t;
+  for (int32_t b : p.todo)
+    if (p.status[(size_t)b] != 0)
+      return fail(CMDP_ERR_MAX_ITER, "discounted value iteration on the %s model of instance %d did not converge in %lld sweeps",
+                  model, (int)b, max_sweeps);
+  return CMDP_OK;
+}
+
+// The segments of the instances in `asked` of a per-instance device array into the caller's (null: nothing).  `per_state`
+// elements per state of the instance, 0: one element per instance.  Outside `asked` the caller's memory is zeroed
+// (`zero_outside`) or left as it is.  Enqueued: the caller waits for the stream.
+template <typename T>
+int policy_fetch(ParkAgent* a, T* dst, const T* src, int64_t per_state, bool zero_outside) {
+  if (!dst) return CMDP_OK;
+  cmdp_t* h = a->env;
+  const std::vector<int32_t>& asked = a->pol.asked;
+  auto first = [&](int b) { return per_state ? per_state * h->state_off[b] : (int64_t)b; };
+  const bool all = (int)asked.size() == h->B;
+  if (!all && zero_outside) std::memset(dst, 0, sizeof(T) * (size_t)first(h->B));
+  for (size_t i = 0; i < asked.size();) {   // one copy per run of neighbours
+    size_t j = i;
+    while (j + 1 < asked.size() && asked[j + 1] == asked[j] + 1) ++j;
+    const int64_t lo = first(asked[i]), hi = first(asked[j] + 1);
+    HIP_TRY(hipMemcpyAsync(dst + lo, src + lo, sizeof(T) * (size_t)(hi - lo), hipMemcpyDeviceToHost, h->stream));
+    i = j + 1;
+  }
+  return CMDP_OK;
 }
 
 }  // namespace
@@ -3934,30 +4041,45 @@ int cmdp_qlearning_run(cmdp_agent_t* a, int64_t n_steps, const uint8_t* train_ma
   return CMDP_OK;
 }
 
-// greedy policy of the agents' Q tables -> episodic policy evaluation -> V[0, :] packed into a->d_v0 (no synchronisation)
-static int ql_enqueue_evaluate(cmdp_agent_t* a, float* v0_out = nullptr, int32_t* snap = nullptr) {
-  cmdp_t* h = a->env;
-  if (a->continuous) return fail(CMDP_ERR_INVALID, "cmdp_qlearning_evaluate is for the episodic agent; use cmdp_qlearning_policy");
-  if (!h->has_dp) return fail(CMDP_ERR_INVALID, "the environment handle was created without the DP half");
+// What the value of a policy on the true episodic MDP asks of the handle; `dp_code` / `dp_text`: the entry point's refusal of
+// a handle without the DP half
+static int episodic_value_check(cmdp_t* h, int dp_code, const char* dp_text) {
+  if (!h->has_dp) return fail(dp_code, "%s", dp_text);
+  if (2 * sizeof(float) * (size_t)h->max_S > (size_t)kLdsBudget)
+    return fail(CMDP_ERR_UNSUPPORTED, "instance with %d states does not fit LDS", h->max_S);
+  return CMDP_OK;
+}
+
+// One-hot policy `pi` [H][S][A] per instance (device) -> episodic policy evaluation on the true MDP -> V[0, :] packed into
+// `v0` (device-accessible); `snap` (nullable, device-accessible [3][B]) receives last_start | prev_start | hstep from the
+// same gather.  After episodic_value_check; no synchronisation.
+static int enqueue_episodic_value(cmdp_t* h, const float* pi, float* v0, int32_t* snap) {
   hipStream_t st = h->stream;
   const int H = h->H;
   const size_t lds = 2 * sizeof(float) * (size_t)h->max_S;
-  if (lds > (size_t)kLdsBudget) return fail(CMDP_ERR_UNSUPPORTED, "instance with %d states does not fit LDS", h->max_S);
-  if (int rc = ql_enqueue_greedy(a)) return rc;
   const size_t nq = (size_t)(H + 1) * h->n_rows, nv = (size_t)(H + 1) * h->n_states;
   if (h->d_Q.n < nq) HIP_TRY(h->d_Q.alloc(nq));
   if (h->d_V.n < nv) HIP_TRY(h->d_V.alloc(nv));
   DpTables t = dp_tables(h);
-  t.pi = a->d_pi.p;
+  t.pi = pi;
   if (int rc = set_lds(k_episodic<DP_PE>, lds)) return rc;
   hipLaunchKernelGGL((k_episodic<DP_PE>), dim3(h->B), dim3(kDpBlock), lds, st, t, H, h->d_Q.p, h->d_V.p);
   HIP_TRY(hipGetLastError());
   // V[0, :] of instance b sits at (H+1)*state_off[b]: pack
-  if (a->d_v0.n < (size_t)h->n_states) HIP_TRY(a->d_v0.alloc(h->n_states));
-  hipLaunchKernelGGL(k_gather_v0, dim3(h->B), dim3(256), 0, st, h->B, H, h->d_state_off.p, h->d_V.p, v0_out ? v0_out : a->d_v0.p,
-                     h->d_last_start.p, h->d_prev_start.p, h->d_h.p, snap);
+  hipLaunchKernelGGL(k_gather_v0, dim3(h->B), dim3(256), 0, st, h->B, H, h->d_state_off.p, h->d_V.p, v0, h->d_last_start.p,
+                     h->d_prev_start.p, h->d_h.p, snap);
   HIP_TRY(hipGetLastError());
   return CMDP_OK;
+}
+
+// greedy policy of the agents' Q tables -> its value -> V[0, :] packed into `v0_out` (null: a->d_v0); no synchronisation
+static int ql_enqueue_evaluate(cmdp_agent_t* a, float* v0_out = nullptr, int32_t* snap = nullptr) {
+  cmdp_t* h = a->env;
+  if (a->continuous) return fail(CMDP_ERR_INVALID, "cmdp_qlearning_evaluate is for the episodic agent; use cmdp_qlearning_policy");
+  if (int rc = episodic_value_check(h, CMDP_ERR_INVALID, "the environment handle was created without the DP half")) return rc;
+  if (int rc = ql_enqueue_greedy(a)) return rc;
+  if (a->d_v0.n < (size_t)h->n_states) HIP_TRY(a->d_v0.alloc(h->n_states));
+  return enqueue_episodic_value(h, a->d_pi.p, v0_out ? v0_out : a->d_v0.p, snap);
 }
 
 int cmdp_qlearning_evaluate(cmdp_agent_t* a, float* V0) {
@@ -3998,98 +4120,6 @@ static const cmdp_tracker::LoggedSwitches& logged_switches() {
   return sw;
 }
 
-// The device side of one cmdp_qlearning_run_logged call.  Two things overlap with the evaluation of row i and with the
-// host's work on it: the agents' NEXT interval (same stream, enqueued before the host waits) and, for the continuous agent,
-// the stationary-distribution solve itself (second stream, on a snapshot of the policy and of the current states).  Rows
-// that could change the training mask are processed in order: the results are the same either way
-// (tests/test_gpu_mdploop.py holds both against the step-by-step loop).
-struct LoggedLoop {
-  cmdp_agent_t* a;
-  const std::vector<cmdp_tracker::LoggedRow>& plan;
-  const cmdp_tracker::Tracker& tr;
-  cmdp_t* h = a->env;
-  hipStream_t st = h->stream, sx = st;   // sx: the continuous solve's -- the second stream when rows run ahead
-  // `cum` twice: the next interval's kernel may already be writing its sums while the host reads this row's
-  PinnedBuf<double> cum[2], avg;
-  PinnedBuf<float> v0;
-  PinnedBuf<int32_t> snap, akind;
-  PinnedBuf<uint8_t> mask, need;
-
-  int setup(const cmdp_tracker::LoggedSwitches& sw) {
-    const int B = h->B;
-    if (int rc = cum[0].alloc(B)) return rc;
-    if (int rc = cum[1].alloc(B)) return rc;
-    if (int rc = avg.alloc(B)) return rc;
-    if (int rc = v0.alloc((size_t)h->n_states)) return rc;
-    if (int rc = snap.alloc((size_t)3 * B)) return rc;
-    if (int rc = akind.alloc(B)) return rc;
-    if (int rc = mask.alloc(B)) return rc;
-    if (int rc = need.alloc(B)) return rc;
-    for (int b = 0; b < B; ++b) cum[0].p[b] = cum[1].p[b] = 0.0;
-    if (a->d_mask.n < (size_t)B) HIP_TRY(a->d_mask.alloc(B));
-    if (h->d_ch_mask.n < (size_t)B) HIP_TRY(h->d_ch_mask.alloc(B));
-    for (int i = 0; i < 2; ++i)
-      if (!h->ev_row[i])
-        HIP_TRY(hipEventCreateWithFlags(&h->ev_row[i], hipEventDisableTiming | (sw.blocking_sync ? hipEventBlockingSync : 0)));
-    if (a->continuous && sw.pipeline) {
-      if (!h->aux.stream) HIP_TRY(hipStreamCreateWithFlags(&h->aux.stream, hipStreamNonBlocking));
-      sx = h->aux.stream;
-      if (h->d_cur_snap.n < (size_t)B) HIP_TRY(h->d_cur_snap.alloc(B));
-    }
-    return CMDP_OK;
-  }
-
-  int upload_mask() {
-    HIP_TRY(hipMemcpyAsync(a->d_mask.p, mask.p, h->B, hipMemcpyHostToDevice, st));
-    return CMDP_OK;
-  }
-
-  // the steps of row i: those whose reward sums it logs, then -- inside the loop -- step t itself
-  int enqueue_interval(size_t i) {
-    const cmdp_tracker::LoggedRow& r = plan[i];
-    double* c = cum[i & 1].p;
-    if (r.n_run > 0) {   // the kernel leaves the sums in `c` (page-locked) itself
-      if (int rc = ql_enqueue_run(a, r.n_run, a->d_mask.p, nullptr, c)) return rc;
-    } else {
-      HIP_TRY(hipMemcpyAsync(c, a->d_rsum.p, sizeof(double) * h->B, hipMemcpyDeviceToHost, st));
-    }
-    if (r.in_loop)
-      if (int rc = ql_enqueue_run(a, 1, a->d_mask.p, nullptr)) return rc;
-    return CMDP_OK;
-  }
-
-  // evaluation of the agents' current greedy policies; everything a row reads comes back WITHOUT copy kernels: the kernels
-  // write into page-locked host memory directly (V[0, :], the start states and in-episode times, the average rewards and
-  // their kinds, the reward sums) and read the evaluation mask from it.  ev_row[1] marks its end.
-  int enqueue_eval() {
-    const int B = h->B;
-    if (!a->continuous) {
-      if (int rc = ql_enqueue_evaluate(a, v0.p, snap.p)) return rc;
-    } else {
-      cmdp_tracker::continuous_need(tr, need.p);
-      bool any = false;
-      for (int b = 0; b < B; ++b) any = any || need.p[b];
-      if (any) {
-        if (int rc = ql_enqueue_greedy(a)) return rc;
-        const int32_t* start = h->d_cur.p;
-        if (sx != st) {
-          HIP_TRY(hipMemcpyAsync(h->d_cur_snap.p, h->d_cur.p, sizeof(int32_t) * B, hipMemcpyDeviceToDevice, st));
-          start = h->d_cur_snap.p;
-          HIP_TRY(hipEventRecord(h->ev_row[0], st));
-          HIP_TRY(hipStreamWaitEvent(sx, h->ev_row[0], 0));
-        }
-        if (int rc = chain_launch(h, a->d_pi.p, nullptr, start, need.p, avg.p, akind.p, nullptr, true, false, sx)) return rc;
-        HIP_TRY(hipEventRecord(h->ev_row[1], sx));
-        return CMDP_OK;
-      }
-    }
-    HIP_TRY(hipEventRecord(h->ev_row[1], st));
-    return CMDP_OK;
-  }
-
-  cmdp_tracker::RowReadback readback(size_t i) const { return {cum[i & 1].p, v0.p, snap.p, need.p, avg.p, akind.p}; }
-};
-
 // the rows of (n_steps, log_every), for a caller whose arrays hold n_logs rows
 static int logged_plan(const cmdp_loop_desc* d, int64_t n_logs, std::vector<cmdp_tracker::LoggedRow>* rows) {
   if (d->n_steps < 1) return fail(CMDP_ERR_INVALID, "n_steps < 1");
@@ -4097,96 +4127,6 @@ static int logged_plan(const cmdp_loop_desc* d, int64_t n_logs, std::vector<cmdp
   if (n_logs != (int64_t)rows->size())
     return fail(CMDP_ERR_INVALID, "n_logs must be %lld for %lld steps logged every %lld", (long long)rows->size(), (long long)d->n_steps,
                 (long long)d->log_every);
-  return CMDP_OK;
-}
-
-int cmdp_qlearning_run_logged(cmdp_agent_t* a, const cmdp_loop_desc* d, int64_t n_logs, int64_t* steps, double* values,
-                              uint8_t* kinds, int64_t* last_training_step, uint8_t* is_training) {
-  using namespace cmdp_tracker;
-  using clk = std::chrono::steady_clock;
-  if (!a || !d || !steps || !values || !kinds) return fail(CMDP_ERR_INVALID, "null argument");
-  cmdp_t* h = a->env;
-  if (int rc = bind(h)) return rc;
-  const int B = h->B;
-  const int64_t T = d->n_steps;
-  std::vector<LoggedRow> plan;
-  if (int rc = logged_plan(d, n_logs, &plan)) return rc;
-  if (!d->base_val || !d->base_kind) return fail(CMDP_ERR_INVALID, "baseline average rewards missing");
-  const bool episodic = !a->continuous;
-  if (episodic && (!d->opt0 || !d->worst0 || !d->start_pos || !d->start_prob || d->kmax < 1))
-    return fail(CMDP_ERR_INVALID, "episodic baselines missing");
-  if (!episodic)
-    for (int b = 0; b < B; ++b)
-      if (!(d->base_val[3 * b] - d->base_val[3 * b + 1] > 0.0002))   // agent_mdp_interaction.py:379-382
-        return fail(CMDP_ERR_INVALID, "instance %d: optimal and worst average reward are closer than 0.0002", b);
-  // refused before anything is stepped or reset: a caller that falls back to another loop must find the agent untouched
-  if (!episodic && d->log_every > 0 && chain_lds_bytes(h->max_S, h->max_row_nnz) > (size_t)kLdsBudget)
-    return fail(CMDP_ERR_UNSUPPORTED, "instance with %d states (max %d successors per row) exceeds the LDS budget of K9",
-                h->max_S, h->max_row_nnz);
-  if (!episodic && !h->has_dp) return fail(CMDP_ERR_INVALID, "the handle was created without the DP half (CSR transition matrices)");
-  const LoggedSwitches& sw = logged_switches();
-  LoggedRun run;
-  LoggedLoop loop{a, plan, run.tr};
-  if (int rc = loop.setup(sw)) return rc;
-  run.init(B, episodic, T, d, h->H, h->state_off.data(), loop.mask.p, last_training_step);
-  if (int rc = loop.upload_mask()) return rc;
-  // MDPLoop.run: visitation counts cleared, environment reset (agent_mdp_interaction.py:219-224)
-  if (int rc = cmdp_reset_visits(h)) return rc;
-  if (int rc = cmdp_reset(h, nullptr, nullptr)) return rc;
-  const auto t_start = clk::now();
-  auto secs = [](clk::time_point a0, clk::time_point a1) { return std::chrono::duration<double>(a1 - a0).count(); };
-  auto elapsed = [&]() { return secs(t_start, clk::now()); };
-
-  const size_t n_rows = plan.size();
-  double longest_row = 0.0, last_row_done = elapsed();
-  double t_enq = 0.0, t_wait = 0.0, t_host = 0.0;   // the debug line's
-  int64_t n_ahead = 0;
-  if (int rc = loop.enqueue_interval(0)) return rc;
-  for (size_t i = 0; i < n_rows; ++i) {
-    const LoggedRow& r = plan[i];
-    const auto c0 = clk::now();
-    if (int rc = loop.enqueue_eval()) return rc;
-    const bool drain = sw.drain_every > 0 && (i + 1) % (size_t)sw.drain_every == 0;
-    const bool ahead = sw.pipeline && i + 1 < n_rows && !drain &&
-                       !limit_within_reach(d->max_time - elapsed(), longest_row, run.limit_passed_while_ahead) &&
-                       !row_may_freeze(run.tr, episodic, r.t, T);
-    if (ahead)
-      if (int rc = loop.enqueue_interval(i + 1)) return rc;
-    n_ahead += ahead;
-    const auto c1 = clk::now();
-    HIP_TRY(hipEventSynchronize(h->ev_row[1]));
-    const auto c2 = clk::now();
-    {
-      const double e = elapsed();
-      longest_row = std::max(longest_row, e - last_row_done);
-      last_row_done = e;
-    }
-    t_enq += secs(c0, c1);
-    t_wait += secs(c1, c2);
-    steps[i] = r.t;
-    const double sps = (double)r.t / std::max(elapsed(), 1e-9);
-    bool changed = false;
-    if (int rc = log_row(run, r, loop.readback(i), sps, d->max_time - elapsed(), ahead, values + i * N_COLUMNS * B,
-                         kinds + i * N_COLUMNS * B, &changed))
-      return rc;
-    if (!r.in_loop) { t_host += secs(c2, clk::now()); break; }
-    if (changed)
-      if (int rc = loop.upload_mask()) return rc;
-    const auto c3 = clk::now();
-    t_host += secs(c2, c3);
-    if (!ahead) {
-      if (drain) HIP_TRY(hipStreamSynchronize(loop.st));
-      if (int rc = loop.enqueue_interval(i + 1)) return rc;
-      t_enq += secs(c3, clk::now());
-    }
-  }
-  HIP_TRY(hipStreamSynchronize(loop.st));
-  if (sw.debug)
-    std::fprintf(stderr, "[logged loop] %d instances, %zu rows (%lld with the next interval started early): enqueue %.2f s, waiting for the device %.2f s, "
-                 "host row work %.2f s\n", B, n_rows, (long long)n_ahead, t_enq, t_wait, t_host);
-  if (is_training)
-    for (int b = 0; b < B; ++b) is_training[b] = run.tr.inst[(size_t)b].training ? 1 : 0;
-  h->known_reset = true;
   return CMDP_OK;
 }
 
@@ -4366,7 +4306,7 @@ int cmdp_extended_vi(int count, const int32_t* n_states, const int32_t* n_action
 }
 
 // K14's launch on device-resident arguments: what cmdp_vi_discounted_model does after its uploads and what the UCRL2 agent
-// does for its policy (cmdp_ucrl2_policy), block b solving instance b
+// does for its policy (cmdp_ucrl2_policy), block k solving instance list[k] (null: k)
 static int mvi_launch(const ModelViArgs& a, int count, int max_S, hipStream_t st) {
   const size_t lds = model_vi_lds_bytes(max_S);
   if (int rc = set_lds(k_vi_model, lds)) return rc;
@@ -4469,23 +4409,16 @@ struct cmdp_ucrl2 : ParkAgent {
   DevBuf<double> d_delta, d_tr_rew, d_beta_r, d_beta_p0, d_span, d_e_rmax, d_e_span, d_host;
   PinnedBuf<int64_t> pin_iter;   // [B]
   PinnedBuf<double> pin_host;    // [3][B]: the round's scalars per parked instance
-  // the policy solve (K14, cmdp_ucrl2_policy): buffers of its own, allocated by the first call
+  // the policy solve (K14 through the policy stage): its per-instance arguments, uploaded by the first request
   int64_t policy_size_threshold = 300 * 3 * 300;   // CMDP_UCRL2_OPT_POLICY_SIZE_THRESHOLD
-  DevBuf<int32_t> d_pS, d_pA, d_p_scheme, d_p_status;
-  DevBuf<int64_t> d_p_roff, d_p_sweeps;
-  DevBuf<float> d_pQ, d_pV, d_ppi;
-  DevBuf<uint8_t> d_p_mask;
-  hipEvent_t p_ev[2] = {nullptr, nullptr};
+  DevBuf<int32_t> d_pS, d_pA;
+  DevBuf<int64_t> d_p_roff;
   // The estimated model changes in model_update only, which ends an artificial episode: while `episode` stands, the solve
-  // and its greedy policy are what they were.  p_stamp[b]: `episode` of instance b when d_pQ / d_ppi were last computed
-  // for it by a solve that converged (-1: never, or invalidated by an option).  CMDP_UCRL2_OPT_POLICY_REUSE switches it.
+  // and its greedy policy are what they were.  p_stamp[b]: `episode` of instance b when the stage's Q and policy were last
+  // computed for it by a solve that converged (-1: never, or invalidated by an option).  CMDP_UCRL2_OPT_POLICY_REUSE
+  // switches it.
   bool policy_reuse = true;
   std::vector<int64_t> p_stamp, p_episode;   // [B]
-  std::vector<uint8_t> p_todo;               // [B] the instances of a request that K14 has to solve
-  ~cmdp_ucrl2() {
-    for (hipEvent_t e : p_ev)
-      if (e) (void)hipEventDestroy(e);
-  }
 };
 
 namespace {
@@ -4684,14 +4617,13 @@ int cmdp_ucrl2_run(cmdp_ucrl2_t* a, int64_t n_steps, int stop_at_episode_end, co
       [&](int count) { return ucrl2_round(a, count, stop, n_steps); }, &h->uc_wait_ms, &h->uc_round_ms);
 }
 
-// discounted_value_iteration(self.P, self.estimated_rewards) (K14) and argmax_2d of its Q for the instances of `mask`, on the
-// handle's stream over the agent's own tables; waits for it and fails when an instance hit max_sweeps, as the reference
-// raises.  Leaves the one-hot policy in d_ppi and Q in d_pQ; reads nothing but the model and writes nothing of the agent's.
-static int ucrl2_policy_solve(cmdp_ucrl2_t* a, const uint8_t* mask, std::vector<int64_t>* sweeps_out, std::vector<int32_t>* scheme_out) {
+// discounted_value_iteration(self.P, self.estimated_rewards) (K14) and argmax_2d of its Q for the instances of `mask` whose
+// model has changed since their stored solve, through the policy stage: fails when one hit max_sweeps, as the reference
+// raises.  Reads nothing but the model and writes nothing of the agent's but the stage.
+static int ucrl2_policy_solve(cmdp_ucrl2_t* a, const uint8_t* mask) {
   cmdp_t* h = a->env;
   hipStream_t st = h->stream;
   const int B = h->B;
-  const int64_t R = h->n_rows;
   if (h->A > MVI_MAX_ACTIONS)
     return fail(CMDP_ERR_UNSUPPORTED, "%d actions: value iteration on a model (K14) takes at most %d", h->A, MVI_MAX_ACTIONS);
   if (!a->d_pS.p) {
@@ -4703,112 +4635,51 @@ static int ucrl2_policy_solve(cmdp_ucrl2_t* a, const uint8_t* mask, std::vector<
     }
     HIP_TRY(a->d_pA.upload(A.data(), B, st));
     HIP_TRY(a->d_p_roff.upload(roff.data(), B, st));
-    AGENT_ZERO(d_pQ, R); AGENT_ZERO(d_pV, h->n_states); AGENT_ZERO(d_ppi, R); AGENT_ZERO(d_p_sweeps, B);
-    AGENT_ZERO(d_p_scheme, B); AGENT_ZERO(d_p_status, B);
-    HIP_TRY(a->d_p_mask.alloc(B));
-    for (hipEvent_t& e : a->p_ev) HIP_TRY(hipEventCreate(&e));
     a->p_stamp.assign((size_t)B, -1);
     a->p_episode.assign((size_t)B, 0);
-    a->p_todo.assign((size_t)B, 0);
     HIP_TRY(a->d_pS.upload(S.data(), B, st));
     HIP_TRY(hipStreamSynchronize(st));  // the vectors are locals
   }
-  // the instances of the request whose model has changed since their stored solve: the others keep d_pQ / d_ppi
+  if (int rc = policy_select(a, 1, true, mask)) return rc;
+  PolicyStage& p = a->pol;
   HIP_TRY(hipMemcpyAsync(a->p_episode.data(), a->d_episode.p, sizeof(int64_t) * B, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
-  int n_asked = 0, n_todo = 0;
-  for (int b = 0; b < B; ++b) {
-    const bool asked = !mask || mask[b];
-    const bool todo = asked && !(a->policy_reuse && a->p_stamp[(size_t)b] == a->p_episode[(size_t)b]);
-    a->p_todo[(size_t)b] = todo ? 1 : 0;
-    n_asked += asked;
-    n_todo += todo;
-  }
-  h->uc_policy_solved += n_todo;
-  h->uc_policy_reused += n_asked - n_todo;
-  if (n_todo == 0) {   // nothing to launch; sweeps and scheme are those of the stored solves
-    if (sweeps_out) {
-      sweeps_out->resize((size_t)B);
-      HIP_TRY(hipMemcpyAsync(sweeps_out->data(), a->d_p_sweeps.p, sizeof(int64_t) * B, hipMemcpyDeviceToHost, st));
-    }
-    if (scheme_out) {
-      scheme_out->resize((size_t)B);
-      HIP_TRY(hipMemcpyAsync(scheme_out->data(), a->d_p_scheme.p, sizeof(int32_t) * B, hipMemcpyDeviceToHost, st));
-    }
-    HIP_TRY(hipStreamSynchronize(st));
-    return CMDP_OK;
-  }
-  const uint8_t* dmask = nullptr;
-  if (n_todo < B) {
-    HIP_TRY(a->d_p_mask.upload(a->p_todo.data(), B, st));
-    dmask = a->d_p_mask.p;
-  }
-  ModelViArgs g{a->d_pS.p, a->d_pA.p, h->d_state_off.p, a->d_p_roff.p, a->d_row_ptr.p, a->d_col.p, a->d_val.p, a->d_uni.p,
-                a->d_ER.p, dmask, 0.99f, 1e-3, CMDP_SCHEME_AUTO, a->policy_size_threshold, 0.2, 1000000, a->d_pQ.p, a->d_pV.p,
-                a->d_p_sweeps.p, a->d_p_scheme.p, a->d_p_status.p};
-  HIP_TRY(hipEventRecord(a->p_ev[0], st));
-  if (int rc = mvi_launch(g, B, h->max_S, st)) return rc;
-  HIP_TRY(hipEventRecord(a->p_ev[1], st));
-  hipLaunchKernelGGL(k_greedy_policy_episodic<float>, dim3(B), dim3(64), 0, st, B, h->A, 1, 1, h->d_state_off.p, a->d_pQ.p,
-                     a->d_ppi.p);
-  HIP_TRY(hipGetLastError());
-  std::vector<int32_t> status((size_t)B);
-  HIP_TRY(hipMemcpyAsync(status.data(), a->d_p_status.p, sizeof(int32_t) * B, hipMemcpyDeviceToHost, st));
-  if (sweeps_out) {
-    sweeps_out->resize((size_t)B);
-    HIP_TRY(hipMemcpyAsync(sweeps_out->data(), a->d_p_sweeps.p, sizeof(int64_t) * B, hipMemcpyDeviceToHost, st));
-  }
-  if (scheme_out) {
-    scheme_out->resize((size_t)B);
-    HIP_TRY(hipMemcpyAsync(scheme_out->data(), a->d_p_scheme.p, sizeof(int32_t) * B, hipMemcpyDeviceToHost, st));
-  }
-  HIP_TRY(hipStreamSynchronize(st));
-  float ms = 0.0f;
-  HIP_TRY(hipEventElapsedTime(&ms, a->p_ev[0], a->p_ev[1]));
-  h->uc_policy_ms = (double)ms;
-  int unconverged = -1;
-  for (int b = 0; b < B; ++b) {
-    if (!a->p_todo[(size_t)b]) continue;
-    // a solve that hit max_sweeps is never reused: the next request solves (and fails) again
-    a->p_stamp[(size_t)b] = status[b] == 0 ? a->p_episode[(size_t)b] : -1;
-    if (status[b] != 0 && unconverged < 0) unconverged = b;
-  }
-  if (unconverged >= 0)
-    return fail(CMDP_ERR_MAX_ITER, "discounted value iteration on the estimated model of instance %d did not converge in "
-                "%d sweeps", unconverged, 1000000);
-  return CMDP_OK;
+  if (a->policy_reuse)
+    p.todo.erase(std::remove_if(p.todo.begin(), p.todo.end(), [&](int32_t b) { return a->p_stamp[(size_t)b] == a->p_episode[(size_t)b]; }),
+                 p.todo.end());
+  h->uc_policy_solved += (int64_t)p.todo.size();
+  h->uc_policy_reused += (int64_t)(p.asked.size() - p.todo.size());
+  int rc = policy_stage(a, 1, [&](const int32_t* list, int count) {
+    ModelViArgs g{a->d_pS.p, a->d_pA.p, h->d_state_off.p, a->d_p_roff.p, a->d_row_ptr.p, a->d_col.p, a->d_val.p, a->d_uni.p,
+                  a->d_ER.p, list, 0.99f, 1e-3, CMDP_SCHEME_AUTO, a->policy_size_threshold, 0.2, 1000000, p.d_Q.p, p.d_V.p,
+                  p.d_sweeps.p, p.d_scheme.p, p.d_status.p};
+    return mvi_launch(g, count, h->max_S, st);
+  });
+  if (rc == CMDP_OK) rc = policy_finish(a, &h->uc_policy_ms, "estimated", 1000000);
+  if (rc == CMDP_OK || rc == CMDP_ERR_MAX_ITER)   // a solve that hit max_sweeps is never reused: the next request solves (and fails) again
+    for (int32_t b : p.todo) a->p_stamp[(size_t)b] = p.status[(size_t)b] == 0 ? a->p_episode[(size_t)b] : -1;
+  return rc;
 }
 
 int cmdp_ucrl2_policy(cmdp_ucrl2_t* a, const uint8_t* mask, float* pi, float* Q, int64_t* sweeps, int32_t* scheme_used) {
   if (!a || !a->env) return fail(CMDP_ERR_INVALID, "null agent, or its environment handle has been destroyed");
   cmdp_t* h = a->env;
   if (int rc = bind(h)) return rc;
-  std::vector<int64_t> sw;
-  std::vector<int32_t> sc;
-  if (int rc = ucrl2_policy_solve(a, mask, sweeps ? &sw : nullptr, scheme_used ? &sc : nullptr)) return rc;
-  if (!mask) {
-    if (pi) HIP_TRY(hipMemcpyAsync(pi, a->d_ppi.p, sizeof(float) * (size_t)h->n_rows, hipMemcpyDeviceToHost, h->stream));
-    if (Q) HIP_TRY(hipMemcpyAsync(Q, a->d_pQ.p, sizeof(float) * (size_t)h->n_rows, hipMemcpyDeviceToHost, h->stream));
-  }
+  if (int rc = ucrl2_policy_solve(a, mask)) return rc;
   // the instances of the mask only: what the call leaves of the others is what it found
-  for (int b = 0; b < h->B; ++b) {
-    if (mask && !mask[b]) continue;
-    const int64_t r0 = h->state_off[b] * h->A, n = (h->state_off[b + 1] - h->state_off[b]) * h->A;
-    if (mask && pi) HIP_TRY(hipMemcpyAsync(pi + r0, a->d_ppi.p + r0, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
-    if (mask && Q) HIP_TRY(hipMemcpyAsync(Q + r0, a->d_pQ.p + r0, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
-    if (sweeps) sweeps[b] = sw[(size_t)b];
-    if (scheme_used) scheme_used[b] = sc[(size_t)b];
-  }
+  if (int rc = policy_fetch(a, pi, a->pol.d_pi.p, h->A, false)) return rc;
+  if (int rc = policy_fetch(a, Q, a->pol.d_Q.p, h->A, false)) return rc;
+  if (int rc = policy_fetch(a, sweeps, a->pol.d_sweeps.p, 0, false)) return rc;
+  if (int rc = policy_fetch(a, scheme_used, a->pol.d_scheme.p, 0, false)) return rc;
   HIP_TRY(hipStreamSynchronize(h->stream));
   return CMDP_OK;
 }
 
 int cmdp_ucrl2_average_reward(cmdp_ucrl2_t* a, const uint8_t* mask, double* avg, int32_t* kind) {
   if (!a || !a->env || !avg || !kind) return fail(CMDP_ERR_INVALID, "null argument, or the agent's environment handle has been destroyed");
-  cmdp_t* h = a->env;
-  if (int rc = bind(h)) return rc;
-  if (int rc = ucrl2_policy_solve(a, mask, nullptr, nullptr)) return rc;
-  return chain_launch(h, a->d_ppi.p, nullptr, h->d_cur.p, mask, avg, kind, nullptr);
+  if (int rc = bind(a->env)) return rc;
+  if (int rc = ucrl2_policy_solve(a, mask)) return rc;
+  return chain_launch(a->env, a->pol.d_pi.p, nullptr, a->env->d_cur.p, mask, avg, kind, nullptr);
 }
 
 int cmdp_ucrl2_layout(cmdp_ucrl2_t* a, int64_t* n_positions, int64_t* row_ptr, int32_t* col) {
@@ -4859,15 +4730,11 @@ struct cmdp_psrl : ParkAgent {
   DevBuf<uint2> d_key;
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};   // around k_psrl_sample and k_vi_episodic_dense of the last round
   bool ev_sample = false, ev_vi = false;
-  // the MAP-policy solve (K15, cmdp_psrl_policy / cmdp_psrl_evaluate): buffers of its own, allocated by the first call
-  DevBuf<float> d_mapt, d_mapc, d_mQ, d_mV, d_mpi, d_mpiH, d_mv0;
-  DevBuf<int32_t> d_mlist;
-  hipEvent_t m_ev[2] = {nullptr, nullptr};
+  // the MAP model of the policy solve (K15, K17; the rest is the policy stage's), allocated by the first request
+  DevBuf<float> d_mapt, d_mapc, d_mv0;
   size_t map_lds = 0;   // dynamic LDS of a K15 launch on this batch
   ~cmdp_psrl() {
     for (hipEvent_t e : ev)
-      if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : m_ev)
       if (e) (void)hipEventDestroy(e);
   }
 };
@@ -4897,71 +4764,34 @@ int mapvi_launch(MapViArgs g, int count, int max_S, size_t lds, hipStream_t st) 
   return CMDP_OK;
 }
 
-// episodic_value_iteration(H, *get_map_estimate()) (K15) for the instances of `mask` on the handle's stream, over the agent's
-// posterior tables; Q in d_mQ.  Reads nothing but the model and writes nothing of the agent's but these buffers.  The
-// instances it solved are left in `sel`; the caller waits for the stream and then calls psrl_map_time.
-int psrl_map_solve(cmdp_psrl_t* a, const uint8_t* mask, std::vector<int32_t>& sel) {
+// episodic_value_iteration(H, *get_map_estimate()) (K15) for the instances of `mask` over the agent's posterior tables, and
+// argmax_3d of the first `pi_layers` layers of its Q (0: none), enqueued on the policy stage: the caller enqueues what it
+// wants behind it and ends with psrl_policy_finish.  Reads nothing but the model and writes nothing of the agent's but the
+// stage and the MAP model's buffers.
+int psrl_policy_solve(cmdp_psrl_t* a, const uint8_t* mask, int pi_layers) {
   cmdp_t* h = a->env;
   hipStream_t st = h->stream;
   const int B = h->B, H = h->H;
-  const int64_t R = h->n_rows;
-  if (!a->d_mQ.p) {
+  if (!a->d_mapc.p) {
     HIP_TRY(a->d_mapt.alloc((size_t)a->nz));
-    HIP_TRY(a->d_mapc.alloc((size_t)R));
-    HIP_TRY(a->d_mV.alloc((size_t)(H + 1) * h->n_states));
-    HIP_TRY(a->d_mpi.alloc((size_t)(H + 1) * R));
-    HIP_TRY(a->d_mpiH.alloc((size_t)H * R));
     HIP_TRY(a->d_mv0.alloc((size_t)h->n_states));
-    HIP_TRY(a->d_mlist.alloc((size_t)B));
-    for (hipEvent_t& e : a->m_ev) HIP_TRY(hipEventCreate(&e));
     a->map_lds = 0;
     for (int b = 0; b < B; ++b) {
       const int64_t s0 = h->state_off[b], s1 = h->state_off[b + 1];
       a->map_lds = std::max(a->map_lds, map_vi_lds_bytes((int)(s1 - s0), h->A, a->h_ptr[(size_t)(s1 * h->A)] - a->h_ptr[(size_t)(s0 * h->A)]));
     }
-    HIP_TRY(a->d_mQ.alloc((size_t)(H + 1) * R));
+    HIP_TRY(a->d_mapc.alloc((size_t)h->n_rows));
   }
-  sel.clear();
-  for (int b = 0; b < B; ++b)
-    if (!mask || mask[b]) sel.push_back(b);
-  const int32_t* list = nullptr;
-  if (mask) {
-    HIP_TRY(a->d_mQ.zero(st));   // the greedy kernel walks every instance: those outside the mask keep no Q of an earlier call
-    HIP_TRY(a->d_mlist.upload(sel.data(), sel.size(), st));
-    HIP_TRY(hipStreamSynchronize(st));   // `sel` may be reallocated by the caller
-    list = a->d_mlist.p;
-  }
-  MapViArgs g{list, a->d_S.p, a->d_A.p, a->d_roff.p, h->d_state_off.p, a->d_row_ptr.p, a->d_col.p, a->d_tp.p, a->d_tprior.p,
-              a->d_rp.p, 4, a->d_mapt.p, a->d_mapc.p, a->d_mQ.p, a->d_mV.p, H, 0};
-  HIP_TRY(hipEventRecord(a->m_ev[0], st));
-  if (int rc = mapvi_launch(g, (int)sel.size(), h->max_S, a->map_lds, st)) return rc;
-  HIP_TRY(hipEventRecord(a->m_ev[1], st));
-  return CMDP_OK;
+  if (int rc = policy_select(a, H + 1, false, mask)) return rc;
+  PolicyStage& p = a->pol;
+  return policy_stage(a, pi_layers, [&](const int32_t* list, int count) {
+    MapViArgs g{list, a->d_S.p, a->d_A.p, a->d_roff.p, h->d_state_off.p, a->d_row_ptr.p, a->d_col.p, a->d_tp.p, a->d_tprior.p,
+                a->d_rp.p, 4, a->d_mapt.p, a->d_mapc.p, p.d_Q.p, p.d_V.p, H, 0};
+    return mapvi_launch(g, count, h->max_S, a->map_lds, st);
+  });
 }
 
-int psrl_map_time(cmdp_psrl_t* a) {   // after a stream synchronisation
-  float ms = 0.0f;
-  HIP_TRY(hipEventElapsedTime(&ms, a->m_ev[0], a->m_ev[1]));
-  a->env->ps_policy_ms = (double)ms;
-  return CMDP_OK;
-}
-
-// the selected instances' segments of a per-instance device array ([lead * rows or states]) into a zeroed host array
-template <typename OffsetOf>
-int psrl_map_fetch(cmdp_psrl_t* a, const std::vector<int32_t>& sel, float* dst, const float* src, size_t total, OffsetOf&& span) {
-  if (!dst) return CMDP_OK;
-  hipStream_t st = a->env->stream;
-  if ((int)sel.size() == a->env->B) {
-    HIP_TRY(hipMemcpyAsync(dst, src, sizeof(float) * total, hipMemcpyDeviceToHost, st));
-    return CMDP_OK;
-  }
-  std::memset(dst, 0, sizeof(float) * total);
-  for (int32_t b : sel) {
-    const std::pair<int64_t, int64_t> s = span(b);   // (first element, count)
-    HIP_TRY(hipMemcpyAsync(dst + s.first, src + s.first, sizeof(float) * (size_t)s.second, hipMemcpyDeviceToHost, st));
-  }
-  return CMDP_OK;
-}
+int psrl_policy_finish(cmdp_psrl_t* a) { return policy_finish(a, &a->env->ps_policy_ms, "MAP", 0); }
 
 void psrl_times(cmdp_psrl_t* a) {   // after a stream synchronisation: the last round's kernel times
   float ms = 0.0f;
@@ -5379,82 +5209,39 @@ int cmdp_psrl_policy(cmdp_psrl_t* a, const uint8_t* mask, float* pi, float* Q) {
   if (!a || !a->env) return fail(CMDP_ERR_INVALID, "null agent, or its environment handle has been destroyed");
   cmdp_t* h = a->env;
   if (int rc = bind(h)) return rc;
-  hipStream_t st = h->stream;
-  const int H = h->H;
-  std::vector<int32_t> sel;
-  if (int rc = psrl_map_solve(a, mask, sel)) return rc;
   // get_policy_from_q_values(Q, True) = argmax_3d over all H + 1 layers (posterior_sampling.py:82)
-  if (pi) {
-    hipLaunchKernelGGL(k_greedy_policy_episodic<float>, dim3(h->B), dim3(64), 0, st, h->B, h->A, H + 1, H + 1, h->d_state_off.p,
-                       a->d_mQ.p, a->d_mpi.p);
-    HIP_TRY(hipGetLastError());
-  }
-  const size_t total = (size_t)(H + 1) * h->n_rows;
-  auto span = [&](int b) {
-    return std::make_pair((int64_t)(H + 1) * h->state_off[b] * h->A, (int64_t)(H + 1) * (h->state_off[b + 1] - h->state_off[b]) * h->A);
-  };
-  if (int rc = psrl_map_fetch(a, sel, pi, a->d_mpi.p, total, span)) return rc;
-  if (int rc = psrl_map_fetch(a, sel, Q, a->d_mQ.p, total, span)) return rc;
-  HIP_TRY(hipStreamSynchronize(st));
-  return psrl_map_time(a);
+  if (int rc = psrl_policy_solve(a, mask, pi ? h->H + 1 : 0)) return rc;
+  const int64_t per_state = (int64_t)(h->H + 1) * h->A;
+  if (int rc = policy_fetch(a, pi, a->pol.d_pi.p, per_state, true)) return rc;
+  if (int rc = policy_fetch(a, Q, a->pol.d_Q.p, per_state, true)) return rc;
+  return psrl_policy_finish(a);
 }
 
 }  // extern "C"
 
 // What the evaluation of the MAP policy on the true MDP refuses (after bind)
 static int psrl_evaluate_check(cmdp_t* h) {
-  if (!h->has_dp)
-    return fail(CMDP_ERR_UNSUPPORTED, "cmdp_psrl_evaluate evaluates the policy on the true MDP: the environment handle was created "
-                "without the DP half (CSR transition matrices)");
-  if (2 * sizeof(float) * (size_t)h->max_S > (size_t)kLdsBudget)
-    return fail(CMDP_ERR_UNSUPPORTED, "instance with %d states does not fit LDS", h->max_S);
-  return CMDP_OK;
+  return episodic_value_check(h, CMDP_ERR_UNSUPPORTED, "cmdp_psrl_evaluate evaluates the policy on the true MDP: the environment "
+                              "handle was created without the DP half (CSR transition matrices)");
 }
 
-// K15 -> greedy policy of the first H layers -> episodic policy evaluation on the true MDP -> V[0, :] packed into `v0`
-// (device-accessible; null: a->d_mv0), all enqueued on the handle's stream after psrl_evaluate_check.  `snap` (nullable,
-// device-accessible [3][B]) receives last_start | prev_start | hstep from the same gather.  The instances solved are left
-// in `sel`; the caller waits for the stream and then calls psrl_map_time.
-static int psrl_enqueue_evaluate(cmdp_psrl_t* a, const uint8_t* mask, std::vector<int32_t>& sel, float* v0, int32_t* snap) {
-  cmdp_t* h = a->env;
-  hipStream_t st = h->stream;
-  const int H = h->H;
-  const size_t lds = 2 * sizeof(float) * (size_t)h->max_S;
-  if (int rc = psrl_map_solve(a, mask, sel)) return rc;
-  // the first H layers of argmax_3d's walk: the same draws of its tie-break stream, laid out as the evaluation reads them
-  hipLaunchKernelGGL(k_greedy_policy_episodic<float>, dim3(h->B), dim3(64), 0, st, h->B, h->A, H, H + 1, h->d_state_off.p,
-                     a->d_mQ.p, a->d_mpiH.p);
-  HIP_TRY(hipGetLastError());
-  const size_t nq = (size_t)(H + 1) * h->n_rows, nv = (size_t)(H + 1) * h->n_states;
-  if (h->d_Q.n < nq) HIP_TRY(h->d_Q.alloc(nq));
-  if (h->d_V.n < nv) HIP_TRY(h->d_V.alloc(nv));
-  DpTables t = dp_tables(h);
-  t.pi = a->d_mpiH.p;
-  if (int rc = set_lds(k_episodic<DP_PE>, lds)) return rc;
-  hipLaunchKernelGGL((k_episodic<DP_PE>), dim3(h->B), dim3(kDpBlock), lds, st, t, H, h->d_Q.p, h->d_V.p);
-  HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(k_gather_v0, dim3(h->B), dim3(256), 0, st, h->B, H, h->d_state_off.p, h->d_V.p, v0 ? v0 : a->d_mv0.p,
-                     h->d_last_start.p, h->d_prev_start.p, h->d_h.p, snap);
-  HIP_TRY(hipGetLastError());
-  return CMDP_OK;
+// K15 -> greedy policy of the first H layers (the same draws of argmax_3d's tie-break stream, laid out as the evaluation reads
+// them) -> its value on the true MDP: V[0, :] packed into `v0` (device-accessible; null: a->d_mv0), `snap` as
+// enqueue_episodic_value's.  All enqueued: the caller ends with psrl_policy_finish.
+static int psrl_enqueue_evaluate(cmdp_psrl_t* a, const uint8_t* mask, float* v0, int32_t* snap) {
+  if (int rc = psrl_evaluate_check(a->env)) return rc;
+  if (int rc = psrl_policy_solve(a, mask, a->env->H)) return rc;
+  return enqueue_episodic_value(a->env, a->pol.d_pi.p, v0 ? v0 : a->d_mv0.p, snap);
 }
 
 extern "C" {
 
 int cmdp_psrl_evaluate(cmdp_psrl_t* a, const uint8_t* mask, float* V0) {
   if (!a || !a->env || !V0) return fail(CMDP_ERR_INVALID, "null argument, or the agent's environment handle has been destroyed");
-  cmdp_t* h = a->env;
-  if (int rc = bind(h)) return rc;
-  if (int rc = psrl_evaluate_check(h)) return rc;
-  hipStream_t st = h->stream;
-  std::vector<int32_t> sel;
-  if (int rc = psrl_enqueue_evaluate(a, mask, sel, nullptr, nullptr)) return rc;
-  if (int rc = psrl_map_fetch(a, sel, V0, a->d_mv0.p, (size_t)h->n_states, [&](int b) {
-        return std::make_pair((int64_t)h->state_off[b], (int64_t)(h->state_off[b + 1] - h->state_off[b]));
-      }))
-    return rc;
-  HIP_TRY(hipStreamSynchronize(st));
-  return psrl_map_time(a);
+  if (int rc = bind(a->env)) return rc;
+  if (int rc = psrl_enqueue_evaluate(a, mask, nullptr, nullptr)) return rc;
+  if (int rc = policy_fetch(a, V0, a->d_mv0.p, 1, true)) return rc;
+  return psrl_policy_finish(a);
 }
 
 }  // extern "C"
@@ -5470,12 +5257,9 @@ struct cmdp_psrlc : cmdp_psrl {
   PcCounters cnt{};
   DevBuf<int32_t> d_nsa, d_nu, d_stamp, d_scheme, d_status;
   DevBuf<int64_t> d_sweeps;
-  // the MAP-policy solve (cmdp_psrlc_policy / cmdp_psrlc_average_reward): buffers of its own, allocated by the first call;
-  // the list and the events are d_mlist and m_ev of the base.  d_Tmap, d_Rmap and d_mrs are the dense route's alone and
-  // allocated by its first call; the tables route keeps T_map in d_mapt [NZ] and d_mapc [R] of the base instead.
-  DevBuf<float> d_Tmap, d_Rmap, d_mrs, d_pQ, d_pV, d_ppi;
-  DevBuf<int32_t> d_pscheme, d_pstatus;
-  DevBuf<int64_t> d_psweeps;
+  // the dense route of the MAP-policy solve alone, allocated by its first request: the dense MAP model.  The tables route
+  // keeps T_map in d_mapt [NZ] and d_mapc [R] of the base instead.
+  DevBuf<float> d_Tmap, d_Rmap, d_mrs;
 };
 
 namespace {
@@ -5690,13 +5474,12 @@ int cmdp_psrlc_last_sample(cmdp_psrlc_t* a, float* T, float* R, float* Q, int64_
   return CMDP_OK;
 }
 
-// discounted_value_iteration(*get_map_estimate()) and argmax_2d for the instances of `mask` on the handle's stream.  The dense
-// route: the dense MAP model into d_Tmap / d_Rmap (k_psrlc_map_fill), K13's solver on it.  The tables route
-// (CMDP_PSRLC_OPT_POLICY_SOLVER = 1): K17 straight on the posterior tables, no dense workspace.  Then, for both, the greedy
-// policy of Q in d_ppi.  Reads nothing
-// but the model and writes nothing of the agent's but these buffers: the last sample and the actor's Q stay what they were.
-// Returns after the stream has drained, with the instances it solved in `sel`; CMDP_ERR_MAX_ITER when one did not converge.
-static int psrlc_policy_solve(cmdp_psrlc_t* a, const uint8_t* mask, std::vector<int32_t>& sel) {
+// discounted_value_iteration(*get_map_estimate()) and argmax_2d for the instances of `mask`, through the policy stage.  The
+// dense route: the dense MAP model into d_Tmap / d_Rmap (k_psrlc_map_fill), K13's solver on it.  The tables route
+// (CMDP_PSRLC_OPT_POLICY_SOLVER = 1): K17 straight on the posterior tables, no dense workspace.  Reads nothing but the model
+// and writes nothing of the agent's but the stage and the MAP model's buffers: the last sample and the actor's Q stay what
+// they were.  CMDP_ERR_MAX_ITER when an instance did not converge.
+static int psrlc_policy_solve(cmdp_psrlc_t* a, const uint8_t* mask) {
   cmdp_t* h = a->env;
   hipStream_t st = h->stream;
   const int B = h->B;
@@ -5713,89 +5496,52 @@ static int psrlc_policy_solve(cmdp_psrlc_t* a, const uint8_t* mask, std::vector<
   if (tables && !a->d_mapc.p) {
     HIP_TRY(a->d_mapt.alloc((size_t)a->nz)); HIP_TRY(a->d_mapc.alloc((size_t)R));
   }
-  if (!a->d_pQ.p) {
-    HIP_TRY(a->d_pV.alloc((size_t)h->n_states));
-    HIP_TRY(a->d_ppi.alloc((size_t)R)); HIP_TRY(a->d_psweeps.alloc((size_t)B)); HIP_TRY(a->d_pscheme.alloc((size_t)B));
-    HIP_TRY(a->d_pstatus.alloc((size_t)B)); HIP_TRY(a->d_mlist.alloc((size_t)B));
-    for (hipEvent_t& e : a->m_ev) HIP_TRY(hipEventCreate(&e));
-    HIP_TRY(a->d_pQ.alloc((size_t)R));
-  }
-  sel.clear();
-  for (int b = 0; b < B; ++b)
-    if (!mask || mask[b]) sel.push_back(b);
-  const int32_t* list = nullptr;
-  if (mask) {
-    HIP_TRY(a->d_pQ.zero(st));   // the greedy kernel walks every instance: those outside the mask keep no Q of an earlier call
-    HIP_TRY(a->d_psweeps.zero(st)); HIP_TRY(a->d_pscheme.zero(st)); HIP_TRY(a->d_pstatus.zero(st));
-    HIP_TRY(a->d_mlist.upload(sel.data(), sel.size(), st));
-    list = a->d_mlist.p;
-  }
-  const int count = (int)sel.size();
-  size_t map_lds = 0;   // of a K17 launch on this batch, by the picker's form
-  if (tables) {
-    size_t staged = 0, plain = 0;
-    for (int b = 0; b < B; ++b) {
-      const int64_t s0 = h->state_off[b], s1 = h->state_off[b + 1];
-      staged = std::max(staged, map_dvi_lds_bytes((int)(s1 - s0), h->A, a->h_ptr[(size_t)(s1 * h->A)] - a->h_ptr[(size_t)(s0 * h->A)],
-                                                  MAPDVI_STAGE_MAX_BYTES));
-      plain = std::max(plain, map_dvi_value_bytes((int)(s1 - s0)));
+  if (int rc = policy_select(a, 1, true, mask)) return rc;
+  PolicyStage& p = a->pol;
+  const int rc = policy_stage(a, 1, [&](const int32_t* list, int count) -> int {
+    if (tables) {
+      size_t staged = 0, plain = 0;   // dynamic LDS of a K17 launch on this batch, by the picker's form
+      for (int b = 0; b < B; ++b) {
+        const int64_t s0 = h->state_off[b], s1 = h->state_off[b + 1];
+        staged = std::max(staged, map_dvi_lds_bytes((int)(s1 - s0), h->A, a->h_ptr[(size_t)(s1 * h->A)] - a->h_ptr[(size_t)(s0 * h->A)],
+                                                    MAPDVI_STAGE_MAX_BYTES));
+        plain = std::max(plain, map_dvi_value_bytes((int)(s1 - s0)));
+      }
+      MapDviArgs g{list, a->d_S.p, a->d_A.p, a->d_roff.p, h->d_state_off.p, a->d_row_ptr.p, a->d_col.p, a->d_tp.p, a->d_tprior.p,
+                   a->d_rp.p, 4, a->d_mapt.p, a->d_mapc.p, 0.99f, 1e-3, CMDP_SCHEME_AUTO, a->size_threshold, a->density_threshold,
+                   a->max_sweeps, p.d_Q.p, p.d_V.p, p.d_sweeps.p, p.d_scheme.p, p.d_status.p, 0};
+      return mapdvi_launch(g, count, h->max_S, mapdvi_pick_lds(count, h->cus, staged, plain), st);
     }
-    map_lds = mapdvi_pick_lds((int)sel.size(), h->cus, staged, plain);
-  }
-  HIP_TRY(hipEventRecord(a->m_ev[0], st));
-  if (count > 0 && tables) {
-    MapDviArgs g{list, nullptr, a->d_S.p, a->d_A.p, a->d_roff.p, h->d_state_off.p, a->d_row_ptr.p, a->d_col.p, a->d_tp.p,
-                 a->d_tprior.p, a->d_rp.p, 4, a->d_mapt.p, a->d_mapc.p, 0.99f, 1e-3, CMDP_SCHEME_AUTO, a->size_threshold,
-                 a->density_threshold, a->max_sweeps, a->d_pQ.p, a->d_pV.p, a->d_psweeps.p, a->d_pscheme.p, a->d_pstatus.p, 0};
-    if (int rc = mapdvi_launch(g, count, h->max_S, map_lds, st)) return rc;
-  } else if (count > 0) {
     PcMapArgs m{list, a->d_S.p, a->d_A.p, a->d_roff.p, a->d_toff.p, a->d_row_ptr.p, a->d_col.p, a->d_tp.p, a->d_tprior.p, a->d_rp.p,
                 a->d_mrs.p, a->d_Tmap.p, a->d_Rmap.p};
     hipLaunchKernelGGL(k_psrlc_map_fill, dim3(count), dim3(MAPVI_THREADS), 0, st, m);
     HIP_TRY(hipGetLastError());
     DdvArgs g{list, a->d_S.p, a->d_A.p, a->d_toff.p, a->d_roff.p, h->d_state_off.p, a->d_Tmap.p, a->d_Rmap.p, 0.99f, 1e-3,
-              CMDP_SCHEME_AUTO, a->size_threshold, a->density_threshold, a->max_sweeps, a->d_pQ.p, a->d_pV.p, a->d_psweeps.p,
-              a->d_pscheme.p, a->d_pstatus.p};
-    if (int rc = ddv_launch(g, count, h->max_S, st)) return rc;
-  }
-  HIP_TRY(hipEventRecord(a->m_ev[1], st));
-  hipLaunchKernelGGL(k_greedy_policy_episodic<float>, dim3(B), dim3(64), 0, st, B, h->A, 1, 1, h->d_state_off.p, a->d_pQ.p,
-                     a->d_ppi.p);
-  HIP_TRY(hipGetLastError());
-  std::vector<int32_t> status((size_t)B);
-  HIP_TRY(hipMemcpyAsync(status.data(), a->d_pstatus.p, sizeof(int32_t) * B, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  if (int rc = psrl_map_time(a)) return rc;
-  for (int32_t b : sel)
-    if (status[(size_t)b] != 0)
-      return fail(CMDP_ERR_MAX_ITER, "discounted value iteration on the MAP model of instance %d did not converge in %lld sweeps",
-                  (int)b, (long long)a->max_sweeps);
-  return CMDP_OK;
+              CMDP_SCHEME_AUTO, a->size_threshold, a->density_threshold, a->max_sweeps, p.d_Q.p, p.d_V.p, p.d_sweeps.p,
+              p.d_scheme.p, p.d_status.p};
+    return ddv_launch(g, count, h->max_S, st);
+  });
+  return rc ? rc : policy_finish(a, &h->ps_policy_ms, "MAP", (long long)a->max_sweeps);
 }
 
 int cmdp_psrlc_policy(cmdp_psrlc_t* a, const uint8_t* mask, float* pi, float* Q, int64_t* sweeps, int32_t* scheme) {
   if (!a || !a->env) return fail(CMDP_ERR_INVALID, "null agent, or its environment handle has been destroyed");
   cmdp_t* h = a->env;
   if (int rc = bind(h)) return rc;
-  std::vector<int32_t> sel;
-  if (int rc = psrlc_policy_solve(a, mask, sel)) return rc;
-  auto span = [&](int b) {
-    return std::make_pair((int64_t)h->state_off[b] * h->A, (int64_t)(h->state_off[b + 1] - h->state_off[b]) * h->A);
-  };
-  if (int rc = psrl_map_fetch(a, sel, pi, a->d_ppi.p, (size_t)h->n_rows, span)) return rc;
-  if (int rc = psrl_map_fetch(a, sel, Q, a->d_pQ.p, (size_t)h->n_rows, span)) return rc;
-  AGENT_FETCH(sweeps, d_psweeps, h->B); AGENT_FETCH(scheme, d_pscheme, h->B);   // zeros outside the mask
+  if (int rc = psrlc_policy_solve(a, mask)) return rc;
+  if (int rc = policy_fetch(a, pi, a->pol.d_pi.p, h->A, true)) return rc;
+  if (int rc = policy_fetch(a, Q, a->pol.d_Q.p, h->A, true)) return rc;
+  if (int rc = policy_fetch(a, sweeps, a->pol.d_sweeps.p, 0, true)) return rc;
+  if (int rc = policy_fetch(a, scheme, a->pol.d_scheme.p, 0, true)) return rc;
   HIP_TRY(hipStreamSynchronize(h->stream));
   return CMDP_OK;
 }
 
 int cmdp_psrlc_average_reward(cmdp_psrlc_t* a, const uint8_t* mask, double* avg, int32_t* kind) {
   if (!a || !a->env || !avg || !kind) return fail(CMDP_ERR_INVALID, "null argument, or the agent's environment handle has been destroyed");
-  cmdp_t* h = a->env;
-  if (int rc = bind(h)) return rc;
-  std::vector<int32_t> sel;
-  if (int rc = psrlc_policy_solve(a, mask, sel)) return rc;
-  return chain_launch(h, a->d_ppi.p, nullptr, h->d_cur.p, mask, avg, kind, nullptr);
+  if (int rc = bind(a->env)) return rc;
+  if (int rc = psrlc_policy_solve(a, mask)) return rc;
+  return chain_launch(a->env, a->pol.d_pi.p, nullptr, a->env->d_cur.p, mask, avg, kind, nullptr);
 }
 
 int cmdp_vi_discounted_dense(int count, const int32_t* n_states, const int32_t* n_actions, const float* T, const float* R,
@@ -5928,7 +5674,7 @@ int cmdp_vi_discounted_map(int count, const int32_t* n_states, const int32_t* n_
   HIP_TRY(ws->sweeps.alloc(count));
   HIP_TRY(ws->scheme.alloc(count));
   HIP_TRY(ws->status.alloc(count));
-  MapDviArgs g{nullptr, nullptr, ws->S.p, ws->A.p, ws->roff.p, ws->soff.p, ws->ptr.p, ws->col.p, ws->hp.p, ws->prior.p, ws->mu.p, 1,
+  MapDviArgs g{nullptr, ws->S.p, ws->A.p, ws->roff.p, ws->soff.p, ws->ptr.p, ws->col.p, ws->hp.p, ws->prior.p, ws->mu.p, 1,
                ws->t.p, ws->c.p, gamma, epsilon, scheme, size_threshold, density_threshold, max_sweeps, ws->Q.p, ws->V.p,
                ws->sweeps.p, ws->scheme.p, ws->status.p, 0};
   int dev = 0, cus = 0;
@@ -5948,18 +5694,20 @@ int cmdp_vi_discounted_map(int count, const int32_t* n_states, const int32_t* n_
 
 }  // extern "C"
 
-// ---- the logged loop of the agents that park (UCRL2, PSRL): one in-order driver ------------------------------------------
-// MDPLoop.run for the batch, as cmdp_qlearning_run_logged, on the rows, the tracker and log_row of cmdp_logged_loop.h.
-// park_run synchronises in every round, so no interval can start before its row is known: the rows are processed strictly in
-// order (`ahead` is false throughout), on the handle's stream alone.  The agent supplies three hooks:
-//   pre()                     the agent's own refusals and allocations for the whole of desc->n_steps; steps nothing
-//   run_steps(n, mask, cum)   n steps under the training mask; the reward sums afterwards into `cum` (page-locked); waits
-//   evaluate(row buffers)     the row's evaluation into page-locked memory; waits
+// ---- the logged loop's driver -------------------------------------------------------------------------------------------------
+// MDPLoop.run for the batch on the rows, the tracker and log_row of cmdp_logged_loop.h: interval, step t, evaluation, log_row,
+// the next interval -- which is enqueued BEFORE the host waits for the row when the agent allows it and the row cannot change
+// the training mask (row_may_freeze, limit_within_reach); the results are the same either way (tests/test_gpu_mdploop.py
+// holds both against the step-by-step loop).  The agent's adapter supplies:
+//   ahead                      may rows run ahead at all?  Not for the agents that park: park_run synchronises in every round
+//   pre(switches)              the agent's own refusals and allocations for the whole of desc->n_steps; steps nothing
+//   run(n, mask, cum)          n steps under the training mask (page-locked); `cum` (page-locked, nullable) receives the reward
+//                              sums after them, by the time the stream has run them
+//   evaluate(buffers, &done)   the row's evaluation into page-locked memory; `done`: the stream it ends on, if not the handle's
 namespace {
 
-struct ParkRowBuffers {
-  // `cum` twice: row i reads slot i & 1; the single step a row takes inside the loop leaves its sums in the other slot, which
-  // is what the next row logs when no step lies between the two
+struct RowBuffers {
+  // `cum` twice: the next interval's kernel may already be writing its sums while the host reads this row's
   PinnedBuf<double> cum[2], avg;
   PinnedBuf<float> v0;
   PinnedBuf<int32_t> snap, akind;
@@ -5978,10 +5726,9 @@ struct ParkRowBuffers {
   }
 };
 
-template <typename Pre, typename RunSteps, typename Evaluate>
-int park_run_logged(ParkAgent* a, bool episodic, int64_t step_limit, const char* limit_text, const cmdp_loop_desc* d, int64_t n_logs,
-                    int64_t* steps, double* values, uint8_t* kinds, int64_t* last_training_step, uint8_t* is_training, Pre&& pre,
-                    RunSteps&& run_steps, Evaluate&& evaluate) {
+template <typename Adapter>
+int run_logged(AgentBase* a, bool episodic, Adapter&& ad, const cmdp_loop_desc* d, int64_t n_logs, int64_t* steps, double* values,
+               uint8_t* kinds, int64_t* last_training_step, uint8_t* is_training) {
   using namespace cmdp_tracker;
   using clk = std::chrono::steady_clock;
   if (!a || !d || !steps || !values || !kinds) return fail(CMDP_ERR_INVALID, "null argument");
@@ -5989,6 +5736,7 @@ int park_run_logged(ParkAgent* a, bool episodic, int64_t step_limit, const char*
   if (int rc = bind(h)) return rc;
   const int B = h->B;
   const int64_t T = d->n_steps;
+  hipStream_t st = h->stream;
   // everything below is refused before anything is reset or stepped: a caller that falls back to another loop must find the
   // agent untouched
   std::vector<LoggedRow> plan;
@@ -5998,85 +5746,212 @@ int park_run_logged(ParkAgent* a, bool episodic, int64_t step_limit, const char*
   if (!episodic && d->log_every > 0 && chain_lds_bytes(h->max_S, h->max_row_nnz) > (size_t)kLdsBudget)
     return fail(CMDP_ERR_UNSUPPORTED, "instance with %d states (max %d successors per row) exceeds the LDS budget of K9",
                 h->max_S, h->max_row_nnz);
-  // MDPLoop._cumulative_reward starts at zero with the run; the agent's sums count from its creation
-  for (int b = 0; b < B; ++b)
-    if (a->steps_total[(size_t)b] != 0)
-      return fail(CMDP_ERR_INVALID, "instance %d has already taken %lld steps: a logged run starts from a new agent", b,
-                  (long long)a->steps_total[(size_t)b]);
-  // what every run() call of the loop would check, once for all of the run's steps (the counters start from the reset below)
-  if (T > step_limit) return fail(CMDP_ERR_OVERFLOW, limit_text, 0, 0LL, (long long)T);
-  if (2 + 2 * T > 0x7fffffffLL)
-    return fail(CMDP_ERR_OVERFLOW, "a visit counter (int32 on the device) could wrap in a run of %lld steps", (long long)T);
-  if (int rc = pre()) return rc;
-  ParkRowBuffers buf;
+  const LoggedSwitches& sw = logged_switches();
+  if (int rc = ad.pre(sw)) return rc;
+  RowBuffers buf;
   if (int rc = buf.alloc(B, (size_t)h->n_states)) return rc;
+  for (int i = 0; i < 2; ++i)
+    if (!h->ev_row[i])
+      HIP_TRY(hipEventCreateWithFlags(&h->ev_row[i], hipEventDisableTiming | (sw.blocking_sync ? hipEventBlockingSync : 0)));
   LoggedRun run;
   run.init(B, episodic, T, d, h->H, h->state_off.data(), buf.mask.p, last_training_step);
-  const auto t_start = clk::now();
-  auto elapsed = [&]() { return std::chrono::duration<double>(clk::now() - t_start).count(); };
   // MDPLoop.run: visitation counts cleared, environment reset (agent_mdp_interaction.py:219-224)
   if (int rc = cmdp_reset_visits(h)) return rc;
   if (int rc = cmdp_reset(h, nullptr, nullptr)) return rc;
-  for (size_t i = 0; i < plan.size(); ++i) {
+  const auto t_start = clk::now();
+  auto secs = [](clk::time_point a0, clk::time_point a1) { return std::chrono::duration<double>(a1 - a0).count(); };
+  auto elapsed = [&]() { return secs(t_start, clk::now()); };
+  // the steps of row i: those whose reward sums it logs, then -- inside the loop -- step t itself
+  auto enqueue_interval = [&](size_t i) -> int {
     const LoggedRow& r = plan[i];
-    // the reward sums through step t - 1, then -- inside the loop -- step t itself
-    if (r.n_run > 0 || i == 0)
-      if (int rc = run_steps(r.n_run, buf.mask.p, buf.cum[i & 1].p)) return rc;
-    if (r.in_loop)
-      if (int rc = run_steps(1, buf.mask.p, buf.cum[(i + 1) & 1].p)) return rc;
-    RowReadback in{buf.cum[i & 1].p, buf.v0.p, buf.snap.p, buf.need.p, buf.avg.p, buf.akind.p};
+    double* c = buf.cum[i & 1].p;
+    if (r.n_run > 0) {
+      if (int rc = ad.run(r.n_run, buf.mask.p, c)) return rc;
+    } else {   // no step since the previous row's own: its sums
+      HIP_TRY(hipMemcpyAsync(c, a->d_rsum.p, sizeof(double) * B, hipMemcpyDeviceToHost, st));
+    }
+    return r.in_loop ? ad.run(1, buf.mask.p, nullptr) : CMDP_OK;
+  };
+
+  const size_t n_rows = plan.size();
+  double longest_row = 0.0, last_row_done = elapsed();
+  double t_enq = 0.0, t_wait = 0.0, t_host = 0.0;   // the debug line's
+  int64_t n_ahead = 0;
+  if (int rc = enqueue_interval(0)) return rc;
+  for (size_t i = 0; i < n_rows; ++i) {
+    const LoggedRow& r = plan[i];
+    const auto c0 = clk::now();
     if (!episodic) continuous_need(run.tr, buf.need.p);
-    if (int rc = evaluate(buf)) return rc;
+    hipStream_t done = st;
+    if (int rc = ad.evaluate(buf, &done)) return rc;
+    HIP_TRY(hipEventRecord(h->ev_row[1], done));   // the row's end
+    const bool drain = sw.drain_every > 0 && (i + 1) % (size_t)sw.drain_every == 0;
+    const bool ahead = ad.ahead && sw.pipeline && i + 1 < n_rows && !drain &&
+                       !limit_within_reach(d->max_time - elapsed(), longest_row, run.limit_passed_while_ahead) &&
+                       !row_may_freeze(run.tr, episodic, r.t, T);
+    if (ahead)
+      if (int rc = enqueue_interval(i + 1)) return rc;
+    n_ahead += ahead;
+    const auto c1 = clk::now();
+    HIP_TRY(hipEventSynchronize(h->ev_row[1]));
+    const auto c2 = clk::now();
+    {
+      const double e = elapsed();
+      longest_row = std::max(longest_row, e - last_row_done);
+      last_row_done = e;
+    }
+    t_enq += secs(c0, c1);
+    t_wait += secs(c1, c2);
     steps[i] = r.t;
     const double sps = (double)r.t / std::max(elapsed(), 1e-9);
-    bool changed = false;   // the hooks read the mask from buf.mask at every call: nothing to upload here
-    if (int rc = log_row(run, r, in, sps, d->max_time - elapsed(), false, values + i * N_COLUMNS * B, kinds + i * N_COLUMNS * B, &changed))
+    const RowReadback in{buf.cum[i & 1].p, buf.v0.p, buf.snap.p, buf.need.p, buf.avg.p, buf.akind.p};
+    bool changed = false;   // run() reads the mask from buf.mask at every call
+    if (int rc = log_row(run, r, in, sps, d->max_time - elapsed(), ahead, values + i * N_COLUMNS * B, kinds + i * N_COLUMNS * B, &changed))
       return rc;
+    const auto c3 = clk::now();
+    t_host += secs(c2, c3);
     if (!r.in_loop) break;
+    if (!ahead) {
+      if (drain) HIP_TRY(hipStreamSynchronize(st));
+      if (int rc = enqueue_interval(i + 1)) return rc;
+      t_enq += secs(c3, clk::now());
+    }
   }
+  HIP_TRY(hipStreamSynchronize(st));
+  if (sw.debug)
+    std::fprintf(stderr, "[logged loop] %d instances, %zu rows (%lld with the next interval started early): enqueue %.2f s, waiting for the device %.2f s, "
+                 "host row work %.2f s\n", B, n_rows, (long long)n_ahead, t_enq, t_wait, t_host);
   if (is_training)
     for (int b = 0; b < B; ++b) is_training[b] = run.tr.inst[(size_t)b].training ? 1 : 0;
   return CMDP_OK;
 }
 
+// Q-learning: everything is enqueued.  Two things overlap with the evaluation of row i and with the host's work on it: the
+// agents' NEXT interval (same stream) and, for the continuous agent, the stationary-distribution solve itself (second stream,
+// on a snapshot of the policy and of the current states).  Everything a row reads comes back WITHOUT copy kernels: the
+// kernels write into page-locked host memory directly (V[0, :], the start states and in-episode times, the average rewards
+// and their kinds, the reward sums) and read the evaluation mask from it.
+struct QlLogged {
+  static constexpr bool ahead = true;
+  cmdp_agent_t* a;
+  cmdp_t* h = a->env;
+  hipStream_t sx = nullptr;        // the continuous solve's: the second stream when rows run ahead
+  std::vector<uint8_t> on_device;  // the training mask a->d_mask holds: uploaded only when it has changed
+
+  int pre(const cmdp_tracker::LoggedSwitches& sw) {
+    const int B = h->B;
+    sx = h->stream;
+    if (a->d_mask.n < (size_t)B) HIP_TRY(a->d_mask.alloc(B));
+    if (h->d_ch_mask.n < (size_t)B) HIP_TRY(h->d_ch_mask.alloc(B));
+    if (a->continuous && sw.pipeline) {
+      if (!h->aux.stream) HIP_TRY(hipStreamCreateWithFlags(&h->aux.stream, hipStreamNonBlocking));
+      sx = h->aux.stream;
+      if (h->d_cur_snap.n < (size_t)B) HIP_TRY(h->d_cur_snap.alloc(B));
+    }
+    return CMDP_OK;
+  }
+
+  int run(int64_t n, const uint8_t* mask, double* cum) {   // the kernel leaves the sums in `cum` itself
+    if (on_device.empty() || std::memcmp(on_device.data(), mask, on_device.size()) != 0) {
+      on_device.assign(mask, mask + h->B);
+      HIP_TRY(hipMemcpyAsync(a->d_mask.p, mask, h->B, hipMemcpyHostToDevice, h->stream));
+    }
+    return ql_enqueue_run(a, n, a->d_mask.p, nullptr, cum);
+  }
+
+  int evaluate(RowBuffers& buf, hipStream_t* done) {
+    const int B = h->B;
+    hipStream_t st = h->stream;
+    if (!a->continuous) return ql_enqueue_evaluate(a, buf.v0.p, buf.snap.p);
+    bool any = false;
+    for (int b = 0; b < B; ++b) any = any || buf.need.p[b];
+    if (!any) return CMDP_OK;
+    if (int rc = ql_enqueue_greedy(a)) return rc;
+    const int32_t* start = h->d_cur.p;
+    if (sx != st) {
+      HIP_TRY(hipMemcpyAsync(h->d_cur_snap.p, h->d_cur.p, sizeof(int32_t) * B, hipMemcpyDeviceToDevice, st));
+      start = h->d_cur_snap.p;
+      HIP_TRY(hipEventRecord(h->ev_row[0], st));
+      HIP_TRY(hipStreamWaitEvent(sx, h->ev_row[0], 0));
+    }
+    *done = sx;
+    return chain_launch(h, a->d_pi.p, nullptr, start, buf.need.p, buf.avg.p, buf.akind.p, nullptr, true, false, sx);
+  }
+};
+
+// What the agents that park refuse of a logged run of T steps besides their own: an agent that has taken steps, and what
+// every run() call of the loop would check, once for all of the run's steps (the counters start from the driver's reset)
+int park_logged_check(ParkAgent* a, int64_t T, int64_t step_limit, const char* limit_text) {
+  // MDPLoop._cumulative_reward starts at zero with the run; the agent's sums count from its creation
+  for (int b = 0; b < a->env->B; ++b)
+    if (a->steps_total[(size_t)b] != 0)
+      return fail(CMDP_ERR_INVALID, "instance %d has already taken %lld steps: a logged run starts from a new agent", b,
+                  (long long)a->steps_total[(size_t)b]);
+  if (T > step_limit) return fail(CMDP_ERR_OVERFLOW, limit_text, 0, 0LL, (long long)T);
+  if (2 + 2 * T > 0x7fffffffLL)
+    return fail(CMDP_ERR_OVERFLOW, "a visit counter (int32 on the device) could wrap in a run of %lld steps", (long long)T);
+  return CMDP_OK;
+}
+
+struct Ucrl2Logged {
+  static constexpr bool ahead = false;
+  cmdp_ucrl2_t* a;
+  const cmdp_loop_desc* d;
+  int pre(const cmdp_tracker::LoggedSwitches&) {
+    if (int rc = park_logged_check(a, d->n_steps, 0x7fffffffLL, "a transition count of the model (int32, as the reference's N) "
+                                   "could wrap: instance %d has taken %lld steps, %lld asked for")) return rc;
+    return ucrl2_ensure_trace(a, d->n_steps);
+  }
+  int run(int64_t n, const uint8_t* mask, double* cum) { return cmdp_ucrl2_run(a, n, 0, mask, nullptr, nullptr, nullptr, cum, nullptr); }
+  int evaluate(RowBuffers& buf, hipStream_t*) {
+    cmdp_t* h = a->env;
+    bool any = false;
+    for (int b = 0; b < h->B; ++b) any = any || buf.need.p[b];
+    if (!any) return CMDP_OK;
+    // cmdp_ucrl2_average_reward(a, need, .): K14 where the model has changed, then the chain kernels on the stored policies
+    if (int rc = ucrl2_policy_solve(a, buf.need.p)) return rc;
+    return chain_launch(h, a->pol.d_pi.p, nullptr, h->d_cur.p, buf.need.p, buf.avg.p, buf.akind.p, nullptr, true, false);
+  }
+};
+
+struct PsrlLogged {
+  static constexpr bool ahead = false;
+  cmdp_psrl_t* a;
+  const cmdp_loop_desc* d;
+  int pre(const cmdp_tracker::LoggedSwitches&) {
+    if (int rc = park_logged_check(a, d->n_steps, 1LL << 24, "a transition count of the model (float32, as the reference's "
+                                   "hyper-parameters) would stop counting at 2^24: instance %d has taken %lld steps, %lld asked for"))
+      return rc;
+    return psrl_evaluate_check(a->env);
+  }
+  int run(int64_t n, const uint8_t* mask, double* cum) { return cmdp_psrl_run(a, n, 0, mask, nullptr, nullptr, nullptr, cum, nullptr); }
+  // what cmdp_psrl_evaluate(a, NULL, .) enqueues; the gather writes V[0, :] and the start states straight into the row's memory
+  int evaluate(RowBuffers& buf, hipStream_t*) {
+    if (int rc = psrl_enqueue_evaluate(a, nullptr, buf.v0.p, buf.snap.p)) return rc;
+    return psrl_policy_finish(a);
+  }
+};
+
 }  // namespace
 
 extern "C" {
 
+int cmdp_qlearning_run_logged(cmdp_agent_t* a, const cmdp_loop_desc* d, int64_t n_logs, int64_t* steps, double* values,
+                              uint8_t* kinds, int64_t* last_training_step, uint8_t* is_training) {
+  if (!a) return fail(CMDP_ERR_INVALID, "null argument");
+  const int rc = run_logged(a, !a->continuous, QlLogged{a}, d, n_logs, steps, values, kinds, last_training_step, is_training);
+  if (rc == CMDP_OK) a->env->known_reset = true;   // the interaction kernels reset at once after every terminating step
+  return rc;
+}
+
 int cmdp_ucrl2_run_logged(cmdp_ucrl2_t* a, const cmdp_loop_desc* d, int64_t n_logs, int64_t* steps, double* values, uint8_t* kinds,
                           int64_t* last_training_step, uint8_t* is_training) {
-  return park_run_logged(
-      a, false, 0x7fffffffLL, "a transition count of the model (int32, as the reference's N) could wrap: instance %d has taken "
-      "%lld steps, %lld asked for", d, n_logs, steps, values, kinds, last_training_step, is_training,
-      [&]() { return ucrl2_ensure_trace(a, d->n_steps); },
-      [&](int64_t n, const uint8_t* mask, double* cum) { return cmdp_ucrl2_run(a, n, 0, mask, nullptr, nullptr, nullptr, cum, nullptr); },
-      [&](ParkRowBuffers& buf) -> int {
-        cmdp_t* h = a->env;
-        bool any = false;
-        for (int b = 0; b < h->B; ++b) any = any || buf.need.p[b];
-        if (!any) return CMDP_OK;
-        // cmdp_ucrl2_average_reward(a, need, .): K14 where the model has changed, then the chain kernels on the stored policies
-        if (int rc = ucrl2_policy_solve(a, buf.need.p, nullptr, nullptr)) return rc;
-        if (int rc = chain_launch(h, a->d_ppi.p, nullptr, h->d_cur.p, buf.need.p, buf.avg.p, buf.akind.p, nullptr, true, false)) return rc;
-        HIP_TRY(hipStreamSynchronize(h->stream));
-        return CMDP_OK;
-      });
+  return run_logged(a, false, Ucrl2Logged{a, d}, d, n_logs, steps, values, kinds, last_training_step, is_training);
 }
 
 int cmdp_psrl_run_logged(cmdp_psrl_t* a, const cmdp_loop_desc* d, int64_t n_logs, int64_t* steps, double* values, uint8_t* kinds,
                          int64_t* last_training_step, uint8_t* is_training) {
-  std::vector<int32_t> sel;
-  return park_run_logged(
-      a, true, 1LL << 24, "a transition count of the model (float32, as the reference's hyper-parameters) would stop counting at "
-      "2^24: instance %d has taken %lld steps, %lld asked for", d, n_logs, steps, values, kinds, last_training_step, is_training,
-      [&]() { return psrl_evaluate_check(a->env); },
-      [&](int64_t n, const uint8_t* mask, double* cum) { return cmdp_psrl_run(a, n, 0, mask, nullptr, nullptr, nullptr, cum, nullptr); },
-      [&](ParkRowBuffers& buf) -> int {
-        // what cmdp_psrl_evaluate(a, NULL, .) enqueues; the gather writes V[0, :] and the start states straight into the row's memory
-        if (int rc = psrl_enqueue_evaluate(a, nullptr, sel, buf.v0.p, buf.snap.p)) return rc;
-        HIP_TRY(hipStreamSynchronize(a->env->stream));
-        return psrl_map_time(a);
-      });
+  return run_logged(a, true, PsrlLogged{a, d}, d, n_logs, steps, values, kinds, last_training_step, is_training);
 }
 
 }  // extern "C"

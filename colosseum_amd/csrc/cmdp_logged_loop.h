@@ -1,6 +1,7 @@
 // cmdp_logged_loop.h -- host side of the logged interaction loop that is not indicator arithmetic: the rows of a run
 // (MDPLoop.run's schedule), the rule that lets the next interval start before a row's result is known, and what a row does
-// on the host once its evaluation has come back (log_row).  cmdp_qlearning_run_logged drives the device around these;
+// on the host once its evaluation has come back (log_row).  run_logged of cmdp.hip -- the one driver behind
+// cmdp_qlearning_run_logged, cmdp_ucrl2_run_logged and cmdp_psrl_run_logged -- drives the device around these;
 // cmdp_tracker_replay runs the same rows on inputs given by the caller, which is how the CPU test suite reaches this code.
 // Nothing here makes a HIP call, reads the environment or looks at a clock: times are handed in.  Included by cmdp.hip
 // after cmdp_tracker.h.
@@ -147,13 +148,13 @@ inline int log_row(LoggedRun& run, const LoggedRow& r, const RowReadback& in, do
   return CMDP_OK;
 }
 
-// ---- the in-order driver (cmdp_ucrl2_run_logged, cmdp_psrl_run_logged) -------------------------------------------------------
+// ---- what the driver refuses of a description ------------------------------------------------------------------------------
 // The agents that park their instances for a solve synchronise in every round of a run, so there is nothing to start early:
-// their driver (park_run_logged of cmdp.hip) walks the same rows strictly in order -- interval, step t, evaluation,
-// log_row with `ahead` false, the next interval's mask -- and uses neither the second stream nor LoggedSwitches.
+// for them the driver never runs ahead and walks the rows strictly in order -- interval, step t, evaluation, log_row with
+// `ahead` false, the next interval's mask -- with neither the second stream nor LoggedSwitches.pipeline playing a part.
 
-// What that driver refuses of a description before anything is reset or stepped: the baselines a row needs, and the
-// continuous setting's `optimal - worst > 0.0002` (agent_mdp_interaction.py:379-382)
+// Before anything is reset or stepped: the baselines a row needs, and the continuous setting's `optimal - worst > 0.0002`
+// (agent_mdp_interaction.py:379-382)
 inline int check_logged_baselines(const cmdp_loop_desc* d, int B, bool episodic) {
   if (!d->base_val || !d->base_kind) return fail(CMDP_ERR_INVALID, "baseline average rewards missing");
   if (episodic && (!d->opt0 || !d->worst0 || !d->start_pos || !d->start_prob || d->kmax < 1))

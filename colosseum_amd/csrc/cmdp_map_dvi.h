@@ -54,7 +54,6 @@
 
 struct MapDviArgs {
   const int32_t* list;     // block k solves instance list[k]; null: instance k
-  const uint8_t* mask;     // [count] or null: an instance with mask[b] == 0 is skipped, its outputs left as they are
   const int32_t* S;        // [count]
   const int32_t* A;        // [count]
   const int64_t* r_off;    // [count] first row: row_ptr, c, mu, Q
@@ -285,7 +284,6 @@ __global__ void __launch_bounds__(MAPDVI_THREADS) k_vi_discounted_map(MapDviArgs
   __shared__ int plan_n;
   const int lane = threadIdx.x;
   const int b = g.list ? g.list[blockIdx.x] : blockIdx.x;
-  if (g.mask && !g.mask[b]) return;
   const int S = g.S[b], A = g.A[b];
   const int vpad = map_dvi_vpad(S);
   const int rows = S * A;

@@ -1,6 +1,7 @@
 // cmdp_model_vi.h -- K14 k_vi_model: discounted value iteration (colosseum/dynamic_programming/infinite_horizon.py:14-44,
 // 121-164) on models in K10's row form, every instance of a launch to convergence or to max_sweeps without a host round trip.
 // What UCRL2Continuous.current_optimal_stochastic_policy solves (ucrl2.py:80-83), straight from the agent's device tables.
+// A launch solves the instances of `list`, one workgroup each, as the other batch solvers select theirs (null: all of them).
 //
 // A row (s, a) is either UNIFORM -- uni[r] = c > 0: T[s, a, j] = c at every state j, its CSR entries (if any) are not read --
 // or the CSR row ptr[r] .. ptr[r + 1] with ascending columns.  By this kernel's definition, with every product and every sum
@@ -42,7 +43,7 @@ struct ModelViArgs {
   const float* val;          // T[s, a, col] >= 0
   const float* uni;          // [n_rows] c when the row is c > 0 at every state (its CSR entries are then not read), else 0
   const float* R;            // [n_rows]
-  const uint8_t* mask;       // [count] or null: instances with mask[b] == 0 are skipped, their outputs left as they are
+  const int32_t* list;       // block k solves instance list[k]; null: instance k.  The other instances' outputs stay as they are
   float gamma;
   double eps;
   int scheme;                // CMDP_SCHEME_AUTO: model_vi_scheme per instance
@@ -78,8 +79,7 @@ __device__ __forceinline__ float mvi_chain(float acc, const float* __restrict__ 
 
 __global__ void __launch_bounds__(MVI_THREADS) k_vi_model(ModelViArgs g) {
   extern __shared__ __align__(16) unsigned char mvi_lds[];
-  const int b = blockIdx.x, lane = threadIdx.x;
-  if (g.mask && !g.mask[b]) return;
+  const int b = g.list ? g.list[blockIdx.x] : blockIdx.x, lane = threadIdx.x;
   const int S = g.S[b], A = g.A[b];
   const int SP = (S + 3) & ~3;
   float* V = reinterpret_cast<float*>(mvi_lds);

@@ -188,8 +188,11 @@ def test_ucrl2_plain_calls_reuse_the_policy_of_an_unchanged_model(need_gpu):
     B = env.B
     for e in (env, env2):
         e.reset()
+    # Step counts picked on the MI355X: the 40th step of this batch ends an artificial episode of one of its two instances
+    # and not of the other, so the request after it solves a strict, non-empty subset of what it is asked for -- the only
+    # case in which K14 is launched on a list of instances
     for ag in (agent, agent2):
-        ag.run(37)
+        ag.run(39)
     first, first2 = agent.average_reward(), agent2.average_reward()
     s0 = agent.stats()
     assert (s0["policy_solved"], s0["policy_reused"]) == (B, 0)
@@ -202,6 +205,7 @@ def test_ucrl2_plain_calls_reuse_the_policy_of_an_unchanged_model(need_gpu):
     second, second2 = agent.average_reward(), agent2.average_reward()
     s2 = agent.stats()
     moved = int((ep1 != ep0).sum())
+    assert 0 < moved < B
     assert s2["policy_solved"] - s1["policy_solved"] == moved and s2["policy_reused"] - s1["policy_reused"] == B - moved
     pi1, pi2 = agent.policy(), agent2.policy()
     for b in range(B):   # the switch changes no bit, whether a stored policy was used or not
