@@ -96,6 +96,7 @@ EXPORTS = [
     "cmdp_psrlc_create", "cmdp_psrlc_destroy", "cmdp_psrlc_run", "cmdp_psrlc_episode_end_update", "cmdp_psrlc_layout",
     "cmdp_psrlc_model", "cmdp_psrlc_last_sample", "cmdp_psrlc_set_option", "cmdp_psrlc_policy", "cmdp_psrlc_average_reward",
     "cmdp_vi_discounted_dense", "cmdp_vi_discounted_map",
+    "cmdp_psrlc_create_optimistic", "cmdp_psrlc_last_sample_optimistic", "cmdp_psrlc_counts", "cmdp_psrlo_reference_draw",
 ]
 
 
@@ -283,6 +284,10 @@ def load():
         L.cmdp_psrlc_set_option.argtypes = [vp, i32, i64]
         L.cmdp_psrlc_policy.argtypes = [vp, vp, vp, vp, vp, vp]
         L.cmdp_psrlc_average_reward.argtypes = [vp, vp, vp, vp]
+        L.cmdp_psrlc_create_optimistic.argtypes = [C.POINTER(vp), vp, vp, i64, vp, vp, vp, vp, vp, i32, i32]
+        L.cmdp_psrlc_last_sample_optimistic.argtypes = [vp] * 10
+        L.cmdp_psrlc_counts.argtypes = [vp, vp]
+        L.cmdp_psrlo_reference_draw.argtypes = [vp] * 12 + [i32, i32, i32, f64, i64, vp, vp, vp, vp, f32] + [vp] * 6
         L.cmdp_vi_discounted_dense.argtypes = [i32, vp, vp, vp, vp, f32, f64, i32, i64, f64, i64, vp, vp, vp, vp, vp]
         L.cmdp_vi_discounted_map.argtypes = [i32, vp, vp, vp, vp, vp, vp, vp, f32, f64, i32, i64, f64, i64, vp, vp, vp, vp, vp, vp, vp]
         L.cmdp_k1e_round_interior.argtypes = [i32, i32, i64, i32]

@@ -482,8 +482,8 @@ class BatchedPSRLContinuous(_ContinuousModelPolicy, _PosteriorSamplingAgent):
         # posterior_sampling.py:272-275: the reference takes the plain path by itself for large instances
         plain = no_optimistic_sampling or all(int(S) ** 2 * env.A > 6_000_000 for S in env.n_states)
         if not plain:
-            raise NotImplementedError("optimistic sampling (psi extended actions) is not built: pass no_optimistic_sampling=True "
-                                      "for the reference's plain posterior sampling")
+            raise NotImplementedError("optimistic sampling (psi extended actions) is BatchedPSRLContinuousOptimistic: pass "
+                                      "no_optimistic_sampling=True for the reference's plain posterior sampling")
         if truncate_reward_with_max:
             raise NotImplementedError("truncate_reward_with_max=True is not built")
         if min_steps_before_new_episode != 0:
@@ -558,3 +558,94 @@ class BatchedPSRLContinuous(_ContinuousModelPolicy, _PosteriorSamplingAgent):
     def _set_max_sweeps(self, n: int):
         """Test hook: the sweeps a solve may take (the reference's DP_MAX_ITERATION = 10^6)."""
         L.check(self._lib.cmdp_psrlc_set_option(self._h, L.PSRLC_OPT_MAX_SWEEPS, int(n)))
+
+
+def optimistic_sampling_scalars(n_states, n_actions, optimization_horizon, p=0.05, psi_weight=1.0, omega_weight=1.0,
+                                eta_weight=1.0, max_psi=60):
+    """(psi, omega, eta, log(4 S)) of one reference PSRLContinuous (posterior_sampling.py:22-113, :278-307, :426) with the
+    reference's own expressions in NumPy."""
+    S, A, T = int(n_states), int(n_actions), int(optimization_horizon)
+    psi = min(max_psi, max(2, int(psi_weight * (S * np.log(S * A / p)))))
+    omega = omega_weight * np.log(T / p)
+    eta = max(5, min(10 * S, eta_weight * (np.sqrt(T * S / A) + 12 * omega * S ** 4)))
+    return int(psi), float(omega), float(eta), float(np.log(4 * S))
+
+
+class BatchedPSRLContinuousOptimistic(BatchedPSRLContinuous):
+    """One reference `PSRLContinuous` with its DEFAULT, optimistic sampling (Agrawal & Jia: psi extended actions per real
+    action) per instance of a continuous `BatchedMDP` (kernel K18, csrc/cmdp_psrlo.h), next to `BatchedPSRLContinuous`, whose
+    tables, artificial-episode rule, round driver, solver and MAP policy it shares.  Per instance psi, omega, eta and log(4 S)
+    are the reference's expressions (`optimistic_sampling_scalars`).  The walk is greedy on the extended Q [S, A * psi] and
+    plays j // psi; the sample is T_ext [S, A * psi, S] with R_ext[s, j] = R[s, j % A], as the reference pairs them.  The
+    keyword names and defaults are the reference's.  Refused, each by name: `no_optimistic_sampling=True` and an instance with
+    S^2 * A > 6 000 000 (the reference samples plainly there: `BatchedPSRLContinuous`), custom `get_psi` / `get_omega` /
+    `get_kappa` / `get_eta`, and what `BatchedPSRLContinuous` refuses.  `sampler="reference"` draws the reference's own
+    numbers on the host (a fourth stream, the agent's own RandomState(seed), gives z); `sampler="philox"` draws posterior
+    rows, z and rewards on the device, a pure function of (seed, episode, tables).  `run_logged` is not built."""
+
+    def __init__(self, env: BatchedMDP, seeds: Sequence[int], optimization_horizon: int, reward_prior_model=None,
+                 transitions_prior_model=None, rewards_prior_prms=None, transitions_prior_prms=None, epsilon_greedy=None,
+                 boltzmann_temperature=None, psi_weight=1.0, omega_weight=1.0, kappa_weight=1.0, eta_weight=1.0, get_psi=None,
+                 get_omega=None, get_kappa=None, get_eta=None, p=0.05, no_optimistic_sampling=False,
+                 truncate_reward_with_max=False, min_steps_before_new_episode=0, max_psi=60, sampler="reference"):
+        if no_optimistic_sampling:
+            raise NotImplementedError("no_optimistic_sampling=True is BatchedPSRLContinuous: this class builds the reference's "
+                                      "optimistic sampling only")
+        for b, S in enumerate(env.n_states):
+            if int(S) ** 2 * env.A > 6_000_000:
+                raise NotImplementedError(f"instance {b}: S^2 * A = {int(S) ** 2 * env.A} > 6 000 000, where the reference samples "
+                                          f"plainly by itself: use BatchedPSRLContinuous")
+        for name, f in (("get_psi", get_psi), ("get_omega", get_omega), ("get_kappa", get_kappa), ("get_eta", get_eta)):
+            if f is not None:
+                raise NotImplementedError(f"a custom {name} is not built: the reference's theoretical value is used")
+        if truncate_reward_with_max:
+            raise NotImplementedError("truncate_reward_with_max=True is not built")
+        if min_steps_before_new_episode != 0:
+            raise NotImplementedError("min_steps_before_new_episode != 0 is not built")
+        sc = [optimistic_sampling_scalars(S, env.A, optimization_horizon, p, psi_weight, omega_weight, eta_weight, max_psi)
+              for S in env.n_states]
+        self.psi = np.array([s[0] for s in sc], np.int32)
+        self.omega = np.array([s[1] for s in sc], np.float64)
+        self.eta = np.array([s[2] for s in sc], np.float64)
+        self._log4s = np.array([s[3] for s in sc], np.float64)
+        self._xoff = np.concatenate([[0], np.cumsum(np.asarray(env.n_states, np.int64) * env.A * self.psi)])
+        _PosteriorSamplingAgent.__init__(self, env, seeds, optimization_horizon, reward_prior_model=reward_prior_model,
+                                         transitions_prior_model=transitions_prior_model, rewards_prior_prms=rewards_prior_prms,
+                                         transitions_prior_prms=transitions_prior_prms, epsilon_greedy=epsilon_greedy,
+                                         boltzmann_temperature=boltzmann_temperature, sampler=sampler)
+
+    def _create(self, env, seeds, horizon, rprior, tprior, sampler, actor):
+        super()._create(env, seeds, horizon, rprior, tprior, L.ptr(self.psi), L.ptr(self.eta), L.ptr(self._log4s), sampler, actor,
+                        create="_create_optimistic")
+
+    def run_logged(self, desc, n_logs: int):
+        raise NotImplementedError("the logged loop of BatchedPSRLContinuousOptimistic is not built")
+
+    def model(self):
+        """As `BatchedPSRLContinuous.model`, with the agent's `N` dense [S, A, S] int32 per instance and `psi`, `eta` [B]."""
+        out = super().model()
+        N = np.zeros(self._nz, np.int32)
+        L.check(self._lib.cmdp_psrlc_counts(self._h, L.ptr(N)))
+        out.update(N=self._dense(N, np.int32), psi=self.psi.copy(), eta=self.eta.copy())
+        return out
+
+    def _ext(self, x):
+        """A per-extended-row array of the library's -> list of [S, A * psi] per instance."""
+        return [x[self._xoff[b]:self._xoff[b + 1]].reshape(int(self.env.n_states[b]), -1) for b in range(self.env.B)]
+
+    def last_sample(self):
+        """The last optimistic sample of every instance: `T` [S, A * psi, S], `R` [S, A] as N_NIG gave it, `R_ext` and the
+        actor's `Q` [S, A * psi], `z` [psi] (reference sampler: -1 where the call drew none), `simple` [S, A] bool, and of the solve `sweeps`,
+        `scheme`, `status` [B]."""
+        env = self.env
+        R, X = int(env.row_off[-1]), int(self._xoff[-1])
+        Rs, Rx, Q = np.zeros(R, np.float32), np.zeros(X, np.float32), np.zeros(X, np.float32)
+        z, simple = np.zeros(int(self.psi.sum()), np.int32), np.zeros(R, np.uint8)
+        sweeps, scheme, status = np.zeros(env.B, np.int64), np.zeros(env.B, np.int32), np.zeros(env.B, np.int32)
+        sizes = [int(S) * env.A * int(k) * int(S) for S, k in zip(env.n_states, self.psi)]
+        T = np.zeros(sum(sizes), np.float32)
+        L.check(self._lib.cmdp_psrlc_last_sample_optimistic(self._h, L.ptr(T), L.ptr(Rs), L.ptr(Rx), L.ptr(Q), L.ptr(z), L.ptr(simple),
+                                                            L.ptr(sweeps), L.ptr(scheme), L.ptr(status)))
+        Ts = [x.reshape(int(S), -1, int(S)) for x, S in zip(np.split(T, np.cumsum(sizes)[:-1]), env.n_states)]
+        return dict(T=Ts, R=self._sa(Rs), R_ext=self._ext(Rx), Q=self._ext(Q), z=np.split(z, np.cumsum(self.psi)[:-1]),
+                    simple=[m.astype(bool) for m in self._sa(simple)], sweeps=sweeps, scheme=scheme, status=status)

@@ -42,6 +42,7 @@ extern char** environ;
 #include "cmdp_ucrl2.h"
 #include "cmdp_psrl.h"
 #include "cmdp_psrlc.h"
+#include "cmdp_psrlo.h"
 #include "cmdp_map_vi.h"
 #include "cmdp_map_dvi.h"
 
@@ -5260,6 +5261,26 @@ struct cmdp_psrlc : cmdp_psrl {
   // the dense route of the MAP-policy solve alone, allocated by its first request: the dense MAP model.  The tables route
   // keeps T_map in d_mapt [NZ] and d_mapc [R] of the base instead.
   DevBuf<float> d_Tmap, d_Rmap, d_mrs;
+  bool optimistic = false;                  // the handle is a cmdp_psrlo (K18): its round, walk and destroy are dispatched on it
+};
+
+// ---- ... with optimistic sampling (K18, cmdp_psrlo.h): the extended sample, the extended Q of the actor, the agent's N ------
+struct cmdp_psrlo : cmdp_psrlc {
+  std::vector<int32_t> h_psi;
+  std::vector<double> h_eta;
+  std::vector<int64_t> h_qoff, h_txoff, h_koff, h_pmoff;   // [B] offsets of the extended arrays (cmdp_psrlo.h: PoArgs)
+  int64_t q_total = 0, tx_total = 0, k_total = 0;
+  PoArgs po{};
+  DevBuf<int32_t> d_psi, d_N, d_z, d_pidx, d_n1, d_Ax;
+  DevBuf<double> d_eta, d_log4s, d_pm;
+  DevBuf<int64_t> d_qoff, d_txoff, d_koff, d_pmoff;
+  DevBuf<float> d_pmk, d_bump, d_Tx, d_Rx, d_Qx, d_post;
+  DevBuf<uint8_t> d_simple;
+  // reference sampler: the agent's own RandomState(seed) and the host staging of a round's draws
+  std::vector<cmdp_rc::NumpyStream> as;
+  std::vector<int32_t> h_nsa, h_z, h_pidx, h_n1;
+  std::vector<uint8_t> h_simple;
+  std::vector<float> h_post;
 };
 
 namespace {
@@ -5316,16 +5337,75 @@ int mapdvi_launch(MapDviArgs g, int count, int max_S, size_t lds, hipStream_t st
   return CMDP_OK;
 }
 
+// The reference sampler's half of an optimistic sample: the host draws each listed instance's posterior rows, z and rewards
+// (psrlo_host::draw) and uploads them compactly
+int psrlo_reference_draws(cmdp_psrlo* a, int count) {
+  cmdp_t* h = a->env;
+  hipStream_t st = h->stream;
+  const int A = h->A;
+  HIP_TRY(hipMemcpyAsync(a->h_tp.data(), a->d_tp.p, sizeof(float) * a->nz, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(a->h_rp.data(), a->d_rp.p, sizeof(float) * 4 * h->n_rows, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(a->h_nsa.data(), a->d_nsa.p, sizeof(int32_t) * h->n_rows, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  const auto t0 = std::chrono::steady_clock::now();
+  const int32_t* hl = a->pin_park.p + 2;
+  cmdp_rc::Pool::get().parallel_for(count, [&](int k) {
+    const int b = hl[k];
+    const int64_t r0 = h->state_off[b] * A;
+    const int S = (int)(h->state_off[b + 1] - h->state_off[b]);
+    a->h_n1[b] = psrlo_host::draw(a->ts[b], a->rs[b], a->as[b], S, A, a->h_psi[b], a->h_eta[b], a->h_nsa.data() + r0,
+                                  a->h_ptr.data() + r0, a->h_col.data(), a->h_tp.data(), a->h_prior[b], a->h_rp.data() + r0 * 4,
+                                  a->h_simple.data() + r0, a->h_pidx.data() + r0, a->h_post.data() + a->h_txoff[b],
+                                  a->h_z.data() + a->h_koff[b], a->h_R.data() + r0);
+  });
+  h->ps_ref_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  for (int k = 0; k < count; ++k) {
+    const int b = hl[k];
+    const int64_t r0 = h->state_off[b] * A, S = h->state_off[b + 1] - h->state_off[b], rows = S * A;
+    const int64_t np = (int64_t)a->h_psi[b] * a->h_n1[b] * S;
+    if (np) HIP_TRY(hipMemcpyAsync(a->d_post.p + a->h_txoff[b], a->h_post.data() + a->h_txoff[b], sizeof(float) * np, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(a->d_z.p + a->h_koff[b], a->h_z.data() + a->h_koff[b], sizeof(int32_t) * a->h_psi[b], hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(a->d_pidx.p + r0, a->h_pidx.data() + r0, sizeof(int32_t) * rows, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(a->d_Rs.p + r0, a->h_R.data() + r0, sizeof(float) * rows, hipMemcpyHostToDevice, st));
+  }
+  HIP_TRY(hipMemcpyAsync(a->d_n1.p, a->h_n1.data(), sizeof(int32_t) * h->B, hipMemcpyHostToDevice, st));
+  return CMDP_OK;
+}
+
+// The optimistic sample (K18) of the `count` instances of pin_park's list into d_Tx / d_Rx: k_psrlo_sample, after the host's
+// draws with the reference sampler; with the Philox sampler the kernel draws everything itself.
+int psrlo_sample(cmdp_psrlo* a, int count) {
+  cmdp_t* h = a->env;
+  hipStream_t st = h->stream;
+  const int A = h->A;
+  const int32_t* list = a->d_park.p + 2;
+  if (a->sampler == CMDP_PSRL_SAMPLER_REFERENCE)
+    if (int rc = psrlo_reference_draws(a, count)) return rc;
+  HIP_TRY(hipEventRecord(a->ev[0], st));
+  if (int rc = set_lds(k_psrlo_sample, a->sample_lds)) return rc;
+  hipLaunchKernelGGL(k_psrlo_sample, dim3(count), dim3(PSRLO_THREADS), a->sample_lds, st, a->args, a->cnt, a->po, list,
+                     h->d_state_off.p, A, h->max_S);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(a->ev[1], st));
+  a->ev_sample = true;
+  return CMDP_OK;
+}
+
 // sample -> solve (straight into the actor's Q) -> tally -> release for the `count` instances of pin_park's list (already on
 // the device at d_park + 2).  The environment is not reset.  An instance that does not converge keeps the last sweep's Q.
 int psrlc_round(cmdp_psrlc_t* a, int count, int stop, int64_t n_steps) {
   cmdp_t* h = a->env;
   hipStream_t st = h->stream;
   const int32_t* list = a->d_park.p + 2;
-  if (int rc = psrl_sample(a, count)) return rc;
+  cmdp_psrlo* o = a->optimistic ? static_cast<cmdp_psrlo*>(a) : nullptr;
+  if (int rc = o ? psrlo_sample(o, count) : psrl_sample(a, count)) return rc;
   DdvArgs g{list, a->d_S.p, a->d_A.p, a->d_toff.p, a->d_roff.p, h->d_state_off.p, a->d_T.p, a->d_Rs.p, 0.99f, 1e-3,
             CMDP_SCHEME_AUTO, a->size_threshold, a->density_threshold, a->max_sweeps, a->d_Q.p, a->d_V.p, a->d_sweeps.p,
             a->d_scheme.p, a->d_status.p};
+  if (o) {   // the same solver on the extended arrays: A * psi actions per instance, Q straight into the actor's extended table
+    g.A = o->d_Ax.p; g.t_off = o->d_txoff.p; g.r_off = o->d_qoff.p;
+    g.T = o->d_Tx.p; g.R = o->d_Rx.p; g.Q = o->d_Qx.p;
+  }
   HIP_TRY(hipEventRecord(a->ev[2], st));
   if (int rc = ddv_launch(g, count, h->max_S, st)) return rc;
   HIP_TRY(hipEventRecord(a->ev[3], st));
@@ -5346,6 +5426,24 @@ int psrlc_bind(cmdp_psrlc_t* a) {
   return bind(a->env);
 }
 
+// What both creates of the continuous agent build: K12's tables and samplers, the counters of the artificial-episode rule,
+// the solve's outputs and the handle's tally
+int psrlc_build(cmdp_psrlc_t* a, const int32_t* seeds, const float* reward_prior, const float* transition_prior) {
+  if (int rc = psrl_build(a, seeds, reward_prior, transition_prior)) return rc;
+  cmdp_t* env = a->env;
+  hipStream_t st = env->stream;
+  const int B = env->B;
+  const int64_t R = env->n_rows;
+  AGENT_ZERO(d_nsa, R); AGENT_ZERO(d_nu, R); AGENT_ZERO(d_stamp, R);
+  AGENT_ZERO(d_scheme, B); AGENT_ZERO(d_status, B); AGENT_ZERO(d_sweeps, B);
+  a->cnt = PcCounters{a->d_nsa.p, a->d_nu.p, a->d_stamp.p};
+  if (!env->d_ps_tally.p) {
+    HIP_TRY(env->d_ps_tally.alloc(2));
+    HIP_TRY(env->d_ps_tally.zero(st));
+  }
+  return CMDP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -5362,26 +5460,119 @@ int cmdp_psrlc_create(cmdp_psrlc_t** out, cmdp_t* env, const int32_t* seeds, int
   std::unique_ptr<cmdp_psrlc> guard(a);
   a->env = env;
   a->sampler = sampler;
-  if (int rc = psrl_build(a, seeds, reward_prior, transition_prior)) return rc;
-  hipStream_t st = env->stream;
-  const int B = env->B;
-  const int64_t R = env->n_rows;
-  AGENT_ZERO(d_nsa, R); AGENT_ZERO(d_nu, R); AGENT_ZERO(d_stamp, R);
-  AGENT_ZERO(d_scheme, B); AGENT_ZERO(d_status, B); AGENT_ZERO(d_sweeps, B);
-  a->cnt = PcCounters{a->d_nsa.p, a->d_nu.p, a->d_stamp.p};
-  if (!env->d_ps_tally.p) {
-    HIP_TRY(env->d_ps_tally.alloc(2));
-    HIP_TRY(env->d_ps_tally.zero(st));
-  }
+  if (int rc = psrlc_build(a, seeds, reward_prior, transition_prior)) return rc;
   // before_start_interacting (infinite_horizon/posterior_sampling.py:379-383): one episode_end_update on the prior
   if (int rc = park_all(a)) return rc;
-  if (int rc = psrlc_round(a, B, 0, 0)) return rc;
-  HIP_TRY(hipStreamSynchronize(st));
+  if (int rc = psrlc_round(a, env->B, 0, 0)) return rc;
+  HIP_TRY(hipStreamSynchronize(env->stream));
   psrl_times(a);
   return agent_attach(guard, out);
 }
 
-int cmdp_psrlc_destroy(cmdp_psrlc_t* a) { return agent_destroy(a); }
+int cmdp_psrlc_create_optimistic(cmdp_psrlc_t** out, cmdp_t* env, const int32_t* seeds, int64_t optimization_horizon,
+                                 const float* reward_prior, const float* transition_prior, const int32_t* psi, const double* eta,
+                                 const double* log4s, int sampler, int actor) {
+  if (!out) return fail(CMDP_ERR_INVALID, "null output");
+  *out = nullptr;
+  if (int rc = psrl_create_check(env, seeds, optimization_horizon, reward_prior, transition_prior, sampler, actor)) return rc;
+  if (!psi || !eta || !log4s) return fail(CMDP_ERR_INVALID, "null argument (psi, eta or log4s)");
+  if (int rc = park_check_env(env, false, "PSRLContinuous is the continuous setting's agent: the environment handle is episodic "
+                              "(horizon %d; cmdp_psrl_create builds PSRLEpisodic)", "PSRLContinuous", "the dense solver (K13)",
+                              PSRL_MAX_STATES)) return rc;
+  const int B = env->B, A = env->A;
+  std::unique_ptr<cmdp_psrlo> guard(new cmdp_psrlo);
+  cmdp_psrlo* a = guard.get();
+  a->env = env;
+  a->sampler = sampler;
+  a->optimistic = true;
+  a->h_psi.assign(psi, psi + B);
+  a->h_eta.assign(eta, eta + B);
+  a->h_qoff.assign((size_t)B, 0); a->h_txoff.assign((size_t)B, 0); a->h_koff.assign((size_t)B, 0); a->h_pmoff.assign((size_t)B, 0);
+  std::vector<int32_t> hAx((size_t)B);
+  for (int b = 0; b < B; ++b) {
+    const int64_t S = env->state_off[b + 1] - env->state_off[b];
+    if (psi[b] < 1 || (int64_t)psi[b] * A > 1 << 20)
+      return fail(CMDP_ERR_INVALID, "psi[%d] = %d: at least 1, and at most 2^20 extended actions", b, psi[b]);
+    if (!(eta[b] > 0.0) || !std::isfinite(eta[b])) return fail(CMDP_ERR_INVALID, "eta[%d] = %g is not a finite value > 0", b, eta[b]);
+    if (!std::isfinite(log4s[b])) return fail(CMDP_ERR_INVALID, "log4s[%d] is not finite", b);
+    const int64_t n = S * A * psi[b] * S;
+    if (n >= (int64_t)1 << 32)
+      return fail(CMDP_ERR_UNSUPPORTED, "instance %d: S * A * psi * S = %lld reaches 2^32 (%lld bytes for its extended sample): the "
+                  "dense optimistic sample is not built for it", b, (long long)n, (long long)(n * 4));
+    hAx[b] = A * psi[b];
+    a->h_qoff[b] = a->q_total; a->h_txoff[b] = a->tx_total; a->h_koff[b] = a->k_total;
+    a->q_total += S * A * psi[b];
+    a->tx_total += (n + 3) & ~(int64_t)3;   // every instance's T_ext starts on a 16-byte boundary
+    a->k_total += psi[b];
+  }
+  // the extended sample is psi times K13's, and the reference sampler's compact upload may be as large again; with them the
+  // bump, R_ext and Q arrays and K13's plain-sized sample workspace, which psrl_build allocates: refuse before anything is
+  // allocated (what is left out is per layout position, psi * 4 + 12 bytes each: small next to these)
+  const bool reference = sampler == CMDP_PSRL_SAMPLER_REFERENCE;
+  long long plain = 0;
+  for (int b = 0; b < B; ++b) {
+    const long long S = env->state_off[b + 1] - env->state_off[b];
+    plain += (S * A * S + 3) & ~3LL;
+  }
+  const long long need = ((long long)a->tx_total * (reference ? 2 : 1) + 3 * (long long)a->q_total + plain) * 4;
+  size_t free_b = 0, total_b = 0;
+  HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+  if ((unsigned long long)need > free_b)
+    return fail(CMDP_ERR_OVERFLOW, "the extended samples T_ext [S, A * psi, S] of the batch and their upload take %lld bytes, %zu "
+                "bytes of device memory are free -- create smaller batches or lower max_psi", need, free_b);
+  if (int rc = psrlc_build(a, seeds, reward_prior, transition_prior)) return rc;
+  hipStream_t st = env->stream;
+  const int64_t R = env->n_rows, NZ = a->nz;
+  int64_t pm_total = 0;
+  for (int b = 0; b < B; ++b) {
+    a->h_pmoff[b] = pm_total;
+    pm_total += (int64_t)psi[b] * (a->h_ptr[(size_t)(env->state_off[b + 1] * A)] - a->h_ptr[(size_t)(env->state_off[b] * A)]);
+  }
+  if (a->d_Tx.alloc((size_t)a->tx_total) != hipSuccess || (reference && a->d_post.alloc((size_t)a->tx_total) != hipSuccess)) {
+    (void)hipGetLastError();
+    return fail(CMDP_ERR_OVERFLOW, "the extended samples of the batch cannot be allocated: %lld bytes", need);
+  }
+  HIP_TRY(a->d_Tx.zero(st));
+  HIP_TRY(a->d_psi.upload(psi, B, st)); HIP_TRY(a->d_eta.upload(eta, B, st)); HIP_TRY(a->d_log4s.upload(log4s, B, st));
+  HIP_TRY(a->d_Ax.upload(hAx.data(), B, st));
+  HIP_TRY(a->d_qoff.upload(a->h_qoff.data(), B, st)); HIP_TRY(a->d_txoff.upload(a->h_txoff.data(), B, st));
+  HIP_TRY(a->d_koff.upload(a->h_koff.data(), B, st)); HIP_TRY(a->d_pmoff.upload(a->h_pmoff.data(), B, st));
+  AGENT_ZERO(d_N, NZ); AGENT_ZERO(d_pm, NZ); AGENT_ZERO(d_pmk, std::max<int64_t>(pm_total, 1)); AGENT_ZERO(d_bump, a->q_total);
+  AGENT_ZERO(d_z, a->k_total); AGENT_ZERO(d_simple, R); AGENT_ZERO(d_pidx, R); AGENT_ZERO(d_n1, B);
+  AGENT_ZERO(d_Rx, a->q_total); AGENT_ZERO(d_Qx, a->q_total);
+  a->po = PoArgs{a->d_psi.p, a->d_eta.p, a->d_log4s.p, a->d_qoff.p, a->d_txoff.p, a->d_koff.p, a->d_pmoff.p, a->d_N.p, a->d_pm.p,
+                 a->d_pmk.p, a->d_bump.p, a->d_z.p, a->d_simple.p, a->d_pidx.p, a->d_n1.p, a->d_post.p, a->d_Tx.p, a->d_Rx.p,
+                 a->d_Qx.p};
+  if (reference) {
+    try {
+      a->h_nsa.resize((size_t)R); a->h_z.resize((size_t)a->k_total); a->h_pidx.resize((size_t)R); a->h_n1.assign((size_t)B, 0);
+      a->h_simple.resize((size_t)R); a->h_post.resize((size_t)a->tx_total);
+    } catch (const std::bad_alloc&) {
+      return fail(CMDP_ERR_OVERFLOW, "the host staging of the reference sampler's posterior rows cannot be allocated: %lld bytes",
+                  (long long)a->tx_total * 4);
+    }
+    // before_start_interacting: randn(S, A * psi) on the agent's own RandomState(seed)
+    a->as.resize((size_t)B);
+    for (int b = 0; b < B; ++b) {
+      psrl_host::seed_numpy(a->as[b], (uint32_t)seeds[b]);
+      psrlo_host::skip_randn(a->as[b], (b + 1 < B ? a->h_qoff[b + 1] : a->q_total) - a->h_qoff[b]);
+    }
+  }
+  // ... then one episode_end_update on the prior
+  if (int rc = park_all(a)) return rc;
+  if (int rc = psrlc_round(a, B, 0, 0)) return rc;
+  HIP_TRY(hipStreamSynchronize(st));
+  psrl_times(a);
+  cmdp_psrlo* attached = nullptr;
+  const int rc = agent_attach(guard, &attached);
+  *out = attached;
+  return rc;
+}
+
+int cmdp_psrlc_destroy(cmdp_psrlc_t* a) {
+  if (a && a->optimistic) return agent_destroy(static_cast<cmdp_psrlo*>(a));
+  return agent_destroy(a);
+}
 
 int cmdp_psrlc_run(cmdp_psrlc_t* a, int64_t n_steps, int stop_at_episode_end, const uint8_t* train_mask, int8_t* actions_trace,
                    int32_t* obs_trace, double* reward_trace, double* cumulative_reward, int64_t* steps_taken) {
@@ -5393,8 +5584,12 @@ int cmdp_psrlc_run(cmdp_psrlc_t* a, int64_t n_steps, int stop_at_episode_end, co
   const int rc = park_run(
       a, n_steps, stop, train_mask, actions_trace, obs_trace, reward_trace, cumulative_reward, steps_taken,
       [&](const uint8_t* dmask, int8_t* act, int32_t* obs, double* rew) {
-        hipLaunchKernelGGL(k_psrlc_walk, dim3(grid_for(h->B, 256)), dim3(256), 0, h->stream, h->env(), a->args, a->cnt, n_steps,
-                           dmask, act, obs, rew, a->d_rsum.p);
+        if (a->optimistic)
+          hipLaunchKernelGGL(k_psrlo_walk, dim3(grid_for(h->B, 256)), dim3(256), 0, h->stream, h->env(), a->args, a->cnt,
+                             static_cast<cmdp_psrlo*>(a)->po, n_steps, dmask, act, obs, rew, a->d_rsum.p);
+        else
+          hipLaunchKernelGGL(k_psrlc_walk, dim3(grid_for(h->B, 256)), dim3(256), 0, h->stream, h->env(), a->args, a->cnt, n_steps,
+                             dmask, act, obs, rew, a->d_rsum.p);
       },
       [&]() -> int { psrl_times(a); return CMDP_OK; }, [&](int count) { return psrlc_round(a, count, stop, n_steps); });
   psrl_times(a);   // after the call's last synchronisation
@@ -5456,8 +5651,87 @@ int cmdp_psrlc_model(cmdp_psrlc_t* a, float* reward_hp, float* transition_hp, fl
   return CMDP_OK;
 }
 
+int cmdp_psrlc_last_sample_optimistic(cmdp_psrlc_t* a, float* T, float* R, float* R_ext, float* Q, int32_t* z, uint8_t* simple,
+                                      int64_t* sweeps, int32_t* scheme, int32_t* status) {
+  if (int rc = psrlc_bind(a)) return rc;
+  if (!a->optimistic) return fail(CMDP_ERR_UNSUPPORTED, "the handle samples plainly: cmdp_psrlc_last_sample returns its sample");
+  cmdp_psrlo* o = static_cast<cmdp_psrlo*>(a);
+  cmdp_t* h = a->env;
+  hipStream_t st = h->stream;
+  if (T) {
+    int64_t at = 0;
+    for (int b = 0; b < h->B; ++b) {   // the workspace pads every instance to 16 bytes; the caller's array is dense
+      const int64_t S = h->state_off[b + 1] - h->state_off[b], n = S * h->A * o->h_psi[b] * S;
+      HIP_TRY(hipMemcpyAsync(T + at, o->d_Tx.p + o->h_txoff[b], sizeof(float) * n, hipMemcpyDeviceToHost, st));
+      at += n;
+    }
+  }
+  if (R_ext) HIP_TRY(hipMemcpyAsync(R_ext, o->d_Rx.p, sizeof(float) * o->q_total, hipMemcpyDeviceToHost, st));
+  if (Q) HIP_TRY(hipMemcpyAsync(Q, o->d_Qx.p, sizeof(float) * o->q_total, hipMemcpyDeviceToHost, st));
+  if (z) HIP_TRY(hipMemcpyAsync(z, o->d_z.p, sizeof(int32_t) * o->k_total, hipMemcpyDeviceToHost, st));
+  if (simple) HIP_TRY(hipMemcpyAsync(simple, o->d_simple.p, (size_t)h->n_rows, hipMemcpyDeviceToHost, st));
+  AGENT_FETCH(R, d_Rs, h->n_rows); AGENT_FETCH(sweeps, d_sweeps, h->B);
+  AGENT_FETCH(scheme, d_scheme, h->B); AGENT_FETCH(status, d_status, h->B);
+  HIP_TRY(hipStreamSynchronize(st));
+  return CMDP_OK;
+}
+
+int cmdp_psrlc_counts(cmdp_psrlc_t* a, int32_t* N) {
+  if (int rc = psrlc_bind(a)) return rc;
+  if (!a->optimistic) return fail(CMDP_ERR_UNSUPPORTED, "the handle samples plainly: it keeps N.sum(-1) only (cmdp_psrlc_model)");
+  if (!N) return fail(CMDP_ERR_INVALID, "null argument");
+  cmdp_t* h = a->env;
+  HIP_TRY(hipMemcpyAsync(N, static_cast<cmdp_psrlo*>(a)->d_N.p, sizeof(int32_t) * a->nz, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  return CMDP_OK;
+}
+
+int cmdp_psrlo_reference_draw(uint32_t* t_key, int32_t* t_pos, int32_t* t_has_gauss, double* t_gauss, uint32_t* r_key,
+                              int32_t* r_pos, int32_t* r_has_gauss, double* r_gauss, uint32_t* a_key, int32_t* a_pos,
+                              int32_t* a_has_gauss, double* a_gauss, int n_states, int n_actions, int psi, double eta,
+                              int64_t skip_randn, const int32_t* n_sa, const int64_t* row_ptr, const int32_t* col, const float* val,
+                              float prior, const float* reward_hp, uint8_t* simple, int32_t* n_posterior, float* posterior,
+                              int32_t* z, float* R) {
+  if (!t_key || !t_pos || !t_has_gauss || !t_gauss || !r_key || !r_pos || !r_has_gauss || !r_gauss || !a_key || !a_pos ||
+      !a_has_gauss || !a_gauss || !n_sa || !row_ptr || !col || !val || !reward_hp || !simple || !n_posterior || !posterior || !z || !R)
+    return fail(CMDP_ERR_INVALID, "null argument");
+  if (n_states < 1 || n_actions < 1 || psi < 1) return fail(CMDP_ERR_INVALID, "n_states, n_actions and psi must be >= 1");
+  if (!(prior > 0.0f) || !(eta > 0.0) || skip_randn < 0) return fail(CMDP_ERR_INVALID, "prior and eta must be > 0, skip_randn >= 0");
+  if (*t_pos < 0 || *t_pos > 624 || *r_pos < 0 || *r_pos > 624 || *a_pos < 0 || *a_pos > 624)
+    return fail(CMDP_ERR_INVALID, "MT19937 position outside [0, 624]");
+  const int64_t SA = (int64_t)n_states * n_actions;
+  for (int64_t r = 0; r < SA; ++r) {
+    if (row_ptr[r + 1] < row_ptr[r]) return fail(CMDP_ERR_INVALID, "row_ptr decreases at row %lld", (long long)r);
+    for (int64_t q = row_ptr[r]; q < row_ptr[r + 1]; ++q)
+      if (col[q] < 0 || col[q] >= n_states || (q > row_ptr[r] && col[q] <= col[q - 1]) || !(val[q] >= 0.0f))
+        return fail(CMDP_ERR_INVALID, "row %lld of the layout: columns ascending within [0, %d), values >= 0", (long long)r, n_states);
+    if (!(reward_hp[4 * r + 1] > 0.0f) || !(reward_hp[4 * r + 2] > 0.0f) || !(reward_hp[4 * r + 3] > 0.0f))
+      return fail(CMDP_ERR_INVALID, "reward hyper-parameters of row %lld: lambda, alpha and beta must be > 0", (long long)r);
+  }
+  cmdp_rc::NumpyStream s[3];
+  uint32_t* keys[3] = {t_key, r_key, a_key};
+  int32_t* pos[3] = {t_pos, r_pos, a_pos};
+  int32_t* has[3] = {t_has_gauss, r_has_gauss, a_has_gauss};
+  double* gs[3] = {t_gauss, r_gauss, a_gauss};
+  for (int i = 0; i < 3; ++i) {
+    std::memcpy(s[i].key, keys[i], sizeof s[i].key);
+    s[i].pos = *pos[i]; s[i].has_gauss = *has[i]; s[i].gauss = *gs[i];
+  }
+  psrlo_host::skip_randn(s[2], skip_randn);
+  std::vector<int32_t> pidx((size_t)SA);
+  *n_posterior = psrlo_host::draw(s[0], s[1], s[2], n_states, n_actions, psi, eta, n_sa, row_ptr, col, val, prior, reward_hp, simple,
+                                  pidx.data(), posterior, z, R);
+  for (int i = 0; i < 3; ++i) {
+    std::memcpy(keys[i], s[i].key, sizeof s[i].key);
+    *pos[i] = s[i].pos; *has[i] = s[i].has_gauss; *gs[i] = s[i].gauss;
+  }
+  return CMDP_OK;
+}
+
 int cmdp_psrlc_last_sample(cmdp_psrlc_t* a, float* T, float* R, float* Q, int64_t* sweeps, int32_t* scheme, int32_t* status) {
   if (int rc = psrlc_bind(a)) return rc;
+  if (a->optimistic)   // never extended data into a plain-sized buffer
+    return fail(CMDP_ERR_UNSUPPORTED, "the handle samples optimistically: cmdp_psrlc_last_sample_optimistic returns its extended sample");
   cmdp_t* h = a->env;
   hipStream_t st = h->stream;
   if (T) {

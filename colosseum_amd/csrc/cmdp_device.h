@@ -20,6 +20,9 @@
 //           philox_gamma: the gamma variate of element (row, column) of the Dirichlet sample of episode `episode`
 // domain 7, PSRL reward sample, same key: n = episode << 32 | row, c3 = draw counter: philox_gamma for tau, then ONE more
 //           block whose four words give the two uniforms of a Box-Muller normal (sqrt(-2 log(1 - u1)) cos(2 pi u2))
+// domain 8, optimistic PSRL posterior rows (cmdp_psrlo.h), same key: n = episode << 32 | ((row * psi + k) * S + column), c3 =
+//           draw counter of philox_gamma (S * A * psi * S < 2^32 is checked at creation)
+// domain 9, optimistic PSRL z, same key: n = episode << 32 | k: z_k = (w0 * S) >> 32
 // ---------------------------------------------------------------------------------------------------
 __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,
                                               uint32_t k1, uint32_t (&w)[4]) {

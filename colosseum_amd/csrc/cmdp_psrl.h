@@ -306,29 +306,20 @@ inline float pairwise_sum_f32(const float* a, int64_t n) {
   return pairwise_sum_f32(a, n2) + pairwise_sum_f32(a + n2, n - n2);
 }
 
-// M_DIR.sample and N_NIG.sample of one instance (conjugate_transitions.py:48-60, conjugate_rewards.py:84-99) on its two
-// RandomState streams.  Transition hyper-parameters: `dense` [S * A * S], or (ptr, col, val) over `prior` when null
-// (ptr relative to the instance's first row is NOT assumed: ptr[r] indexes col / val directly).
-inline void reference_draw(cmdp_rc::NumpyStream& ts, cmdp_rc::NumpyStream& rs, int S, int A, const float* dense,
-                           const int64_t* ptr, const int32_t* col, const float* val, float prior, const float* rhp,
-                           float* T, float* R) {
-  const int SA = S * A;
-  for (int r = 0; r < SA; ++r) {
-    float* row = T + (int64_t)r * S;
-    if (dense) {
-      for (int c = 0; c < S; ++c) row[c] = (float)ts.standard_gamma((double)dense[(int64_t)r * S + c]);
-    } else {
-      int64_t z = ptr[r];
-      const int64_t ze = ptr[r + 1];
-      for (int c = 0; c < S; ++c) {
-        float shape = prior;
-        if (z < ze && col[z] == c) shape = val[z++];
-        row[c] = (float)ts.standard_gamma((double)shape);
-      }
-    }
-    const float den = 1e-5f + (0.0f + pairwise_sum_f32(row, S));   // 1e-5 + r.sum(-1, keepdims=True), float32
-    for (int c = 0; c < S; ++c) row[c] = row[c] / den;
+// One row of M_DIR's sample from the layout positions [z, ze) over `prior`; K18's posterior rows are drawn with it too
+inline void reference_draw_row(cmdp_rc::NumpyStream& ts, int S, int64_t z, int64_t ze, const int32_t* col, const float* val,
+                               float prior, float* row) {
+  for (int c = 0; c < S; ++c) {
+    float shape = prior;
+    if (z < ze && col[z] == c) shape = val[z++];
+    row[c] = (float)ts.standard_gamma((double)shape);
   }
+  const float den = 1e-5f + (0.0f + pairwise_sum_f32(row, S));   // 1e-5 + r.sum(-1, keepdims=True), float32
+  for (int c = 0; c < S; ++c) row[c] = row[c] / den;
+}
+
+// N_NIG.sample of SA rows (conjugate_rewards.py:84-99)
+inline void reference_draw_rewards(cmdp_rc::NumpyStream& rs, int SA, const float* rhp, float* R) {
   // tau = rng.gamma(shape=alpha, scale=1.0 / beta).astype(float32): every gamma first, then every normal
   std::vector<float> tau((size_t)SA);
   for (int r = 0; r < SA; ++r) {
@@ -340,6 +331,26 @@ inline void reference_draw(cmdp_rc::NumpyStream& ts, cmdp_rc::NumpyStream& rs, i
     const float sd = std::sqrt(var);
     R[r] = (float)((double)rhp[4 * r] + (double)sd * rs.legacy_gauss());
   }
+}
+
+// M_DIR.sample and N_NIG.sample of one instance (conjugate_transitions.py:48-60, conjugate_rewards.py:84-99) on its two
+// RandomState streams.  Transition hyper-parameters: `dense` [S * A * S], or (ptr, col, val) over `prior` when null
+// (ptr relative to the instance's first row is NOT assumed: ptr[r] indexes col / val directly).
+inline void reference_draw(cmdp_rc::NumpyStream& ts, cmdp_rc::NumpyStream& rs, int S, int A, const float* dense,
+                           const int64_t* ptr, const int32_t* col, const float* val, float prior, const float* rhp,
+                           float* T, float* R) {
+  const int SA = S * A;
+  for (int r = 0; r < SA; ++r) {
+    float* row = T + (int64_t)r * S;
+    if (dense) {
+      for (int c = 0; c < S; ++c) row[c] = (float)ts.standard_gamma((double)dense[(int64_t)r * S + c]);
+      const float den = 1e-5f + (0.0f + pairwise_sum_f32(row, S));
+      for (int c = 0; c < S; ++c) row[c] = row[c] / den;
+    } else {
+      reference_draw_row(ts, S, ptr[r], ptr[r + 1], col, val, prior, row);
+    }
+  }
+  reference_draw_rewards(rs, SA, rhp, R);
 }
 
 inline void seed_numpy(cmdp_rc::NumpyStream& s, uint32_t seed) {  // RandomState(seed): init_genrand, position 624

@@ -1,0 +1,388 @@
+// cmdp_psrlo.h -- K18: OPTIMISTIC posterior sampling for the continuous setting (Agrawal & Jia), the reference's default path
+// (no_optimistic_sampling=False), one reference agent per instance,
+//   colosseum/agent/agents/infinite_horizon/posterior_sampling.py   (PSRLContinuous.optimistic_sampling, episode_end_update)
+// next to K13's plain path (cmdp_psrlc.h), whose posterior tables, artificial-episode rule, round driver and solver
+// (k_vi_discounted_dense with a per-instance A) it shares unchanged.
+//
+// What the reference does on this path:
+//   Scalars (__init__ :268-307), computed by the caller in NumPy and handed over per instance:
+//     psi = min(max_psi, max(2, int(psi_weight * S * log(S * A / p)))),  omega = omega_weight * log(T / p),
+//     eta = max(5, min(10 * S, eta_weight * (sqrt(T * S / A) + 12 * omega * S^4)));  kappa and self.M are never read.
+//   before_start_interacting.  self._rng.randn(S, A * psi) on the AGENT's RandomState(seed) -- a fourth stream next to the
+//     actor's and the two conjugate models'; the Q it gives is replaced at once, what stays is the stream's position (legacy
+//     polar Gaussians).  Then one episode_end_update.
+//   optimistic_sampling (:411-443), per call.  Nsum = N.sum(-1); a row (s, a) is SIMPLE iff Nsum < eta, else POSTERIOR.
+//     Posterior rows, row-major, for every k in range(psi): M_DIR.sample_sa(rows) = standard_gamma(hyper_params[rows],
+//       (1, n1, S)) on the transitions model's stream, cast to float32, then r / (1e-5 + r.sum(-1, keepdims=True)).
+//     Simple rows, in float64:  P_hat = N / maximum(Nsum, 1),  Nm = maximum(N, 1),  l = log(4 S),
+//       P_minus = P_hat - minimum(sqrt(((3 * P_hat) * l) / Nm) + (3 * l) / Nm, P_hat)
+//       and for every k:  z = agent_rng.randint(S);  summing = 1 - P_minus.sum(-1) (NumPy's pairwise float64 sum of the dense
+//       row);  P_minus[:, :, z] += summing;  Q[k, simple rows] = float32(P_minus[simple rows]);  P_minus[:, :, z] -= summing.
+//       The += / -= pair is not exact: a layout value may drift, and summing is taken from the restored row at every k.
+//     A call with no simple row draws no z; a call with no posterior row draws no gamma.
+//   episode_end_update (:360-377).  T_ext = moveaxis(Q, 0, 2).reshape(S, A * psi, S): extended action j = a * psi + k carries
+//     sample k of real action a.  R = N_NIG.sample(), R_ext = tile(R, (1, psi)): R_ext[s, j] = R[s, j % A] -- not j / psi; the
+//     reference pairs them this way and so does this file.  discounted_value_iteration(T_ext, R_ext): the scheme rule sees the
+//     EXTENDED array.
+//   select_action.  Greedy on Q[s, :] of length A * psi with the tie-break over all of it; the real action is j / psi.
+//   step_update, is_episode_end, current_optimal_stochastic_policy: as on the plain path; the agent's N[s, a, s'] is kept as
+//     int32 at the layout's positions (the float32 hyper-parameters cannot give it back).
+//
+// Kernels:
+//   k_psrlo_walk    K13's walk on A * psi_b Q values per state (per-instance offsets), plays and traces j / psi_b, counts N.
+//   k_psrlo_sample  one workgroup per listed instance, fills T_ext [S, A * psi, S] and R_ext [S, A * psi].
+//     Phase 1, a lane per row: the flag (double)n_sa < eta, P_minus at the row's layout positions, then the serial chain over k.
+//       A non-zero of the dense row sits at a layout position or at z_k, so the pairwise sum is mapvi_rowsum's tree (cmdp_map_vi.h)
+//       in float64 with zero fill.  A z_k outside the layout holds 0 + summing and returns to 0 - exactly.  Per k the lane
+//       leaves float32(P_minus) of its layout positions (`pmk`) and the float32 value at z_k (`bump`).
+//     Phase 2, a wavefront per (row, k): the row of T_ext written once, coalesced (16-byte stores where S % 4 == 0): zeros,
+//       the layout positions and z_k for a simple row; the host's compact upload for a posterior row.
+// CMDP_PSRL_SAMPLER_REFERENCE: psrlo_host::draw below draws the gammas, the z and the N_NIG sample on the instance's streams.
+// CMDP_PSRL_SAMPLER_PHILOX (`post` null): everything is drawn in the kernel, a pure function of (seed, episode, tables):
+//   z_k = (w0 * S) >> 32 of the block (n = episode << 32 | k, domain 9);  the gamma variate of element c of extended row
+//   j = row * psi + k on domain 8 with n = episode << 32 | (j * S + c) (S * A * psi * S < 2^32 is checked at creation), the
+//   row then as k_psrl_sample's: float64 sum rounded once, T = r / (1e-5f + sum);  the reward of a row as k_psrl_sample draws
+//   it (domain 7).  A wavefront keeps its row's variates in its LDS slice (dynamic LDS: 4 * s_max floats).
+#pragma once
+#include "cmdp_psrlc.h"
+
+#define PSRLO_THREADS 256
+
+struct PoArgs {
+  const int32_t* psi;       // [B]
+  const double* eta;        // [B]
+  const double* log4s;      // [B] numpy's log(4 * S)
+  const int64_t* q_off;     // [B] first extended row: R_ext, Q [S][A * psi], bump [psi][S * A]
+  const int64_t* tx_off;    // [B] first element of T_ext (a multiple of 4); also of the compact posterior rows
+  const int64_t* k_off;     // [B] first of the instance's psi values of z
+  const int64_t* pm_off;    // [B] first of the instance's psi * nz_b values of pmk
+  int32_t* N;               // [NZ] the agent's N at the layout's positions
+  double* pm;               // [NZ] P_minus of the chain
+  float* pmk;               // per k the float32 layout values of the simple rows
+  float* bump;              // per (k, row) the float32 value at z_k
+  int32_t* z;               // [sum psi]
+  uint8_t* simple;          // [R]
+  const int32_t* pidx;      // [R] index of a posterior row among the instance's posterior rows (reference sampler)
+  const int32_t* n1;        // [B] posterior rows of the last draw
+  const float* post;        // at tx_off[b]: [psi][n1][S] posterior rows as the host drew them; null: the Philox sampler
+  float* Tx;
+  float* Rx;                // [sum S * A * psi]
+  float* Qx;                // the actor's table
+};
+
+__global__ void __launch_bounds__(256) k_psrlo_walk(EnvTables t, PsArgs p, PcCounters c, PoArgs o, int64_t n_steps,
+                                                    const uint8_t* __restrict__ train_mask, int8_t* __restrict__ act_trace,
+                                                    int32_t* __restrict__ obs_trace, double* __restrict__ rew_trace,
+                                                    double* __restrict__ cum_reward) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= t.B) return;
+  long long left = p.call.left[b];
+  if (left == 0) return;
+  const int64_t soff = t.state_off[b], ebase = t.entry_base[b];
+  const int A = t.A, psi = o.psi[b], AX = A * psi;
+  const uint2 key = t.philox_key ? t.philox_key[b] : make_uint2(0, 0);
+  int32_t cur = t.cur[b], h = t.hstep[b];
+  unsigned long long nt = t.n_trans[b];
+  const float* Q = o.Qx + o.q_off[b];
+  float* RP = p.rp + soff * A * 4;
+  uint32_t* mt = p.mt + (int64_t)b * 624;
+  int32_t* mtp = p.mt_pos + b;
+  const int32_t ep = (int32_t)p.episode[b];
+  const bool train = train_mask ? train_mask[b] != 0 : true;
+  double sum = cum_reward[b];
+  bool parked = false;
+  while (left > 0) {
+    const int64_t step = n_steps - left;
+    int action = greedy_action_row(Q + (int64_t)cur * AX, AX, mt, mtp) / psi;   // extended_action_to_real
+    const int32_t idx = cur * A + action;
+    const unsigned long long n0 = nt;
+    int32_t obs;
+    double rraw;
+    int64_t e;
+    env_transition(t, soff, ebase, key, cur, h, nt, action, obs, rraw, e);
+    if (t.sp_rkind && t.sp_rkind[e] == 1) rraw = philox_beta(t.sp_rp0[e], t.sp_rp1[e], n0, key, t.beta_gammas);
+    const double reward = rraw * t.rscale - t.rmin;
+    sum += reward;
+    if (act_trace) act_trace[step * t.B + b] = (int8_t)action;
+    if (obs_trace) obs_trace[step * t.B + b] = obs;
+    if (rew_trace) rew_trace[step * t.B + b] = reward;
+    --left;
+    if (train) {
+      psrl_nnig_update(RP + (int64_t)idx * 4, reward);
+      const int32_t pos = p.slot[e];
+      float* tc = p.tp + pos;
+      *tc = __fadd_rn(*tc, 1.0f);
+      o.N[pos] += 1;
+      const int64_t r = soff * A + idx;
+      const int32_t n_tau = c.n_sa[r] + 1;
+      const int32_t nu_k = (c.stamp[r] == ep ? c.nu[r] : 0) + 1;
+      c.n_sa[r] = n_tau;
+      c.nu[r] = nu_k;
+      c.stamp[r] = ep;
+      if (n_tau >= 2 * (n_tau - nu_k)) {
+        parked = true;
+        break;
+      }
+    }
+  }
+  t.cur[b] = cur;
+  t.hstep[b] = h;
+  t.n_trans[b] = nt;
+  cum_reward[b] = sum;
+  p.call.left[b] = left;
+  if (parked) p.call.park_list[atomicAdd(p.call.park_count, 1)] = b;
+}
+
+// the dense float64 row of the chain, read once in ascending column order: the layout's values, 0 elsewhere (a z outside
+// the layout is 0 whenever the row is summed)
+struct PoRow {
+  const int32_t* col;
+  const double* pm;
+  int64_t z, ze;
+  __device__ __forceinline__ double at(int j) {
+    if (z < ze && col[z] == j) return pm[z++];
+    return 0.0;
+  }
+};
+
+// DOUBLE_pairwise_sum on a run of n <= 128 elements starting at column j0 (mapvi_run in float64)
+__device__ __forceinline__ double psrlo_run(PoRow& r, int j0, int n) {
+  if (n < 8) {
+    double res = 0.0;
+    for (int i = 0; i < n; ++i) res = __dadd_rn(res, r.at(j0 + i));
+    return res;
+  }
+  double acc[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) acc[j] = r.at(j0 + j);
+  int i = 8;
+  for (; i < n - (n % 8); i += 8) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc[j] = __dadd_rn(acc[j], r.at(j0 + i + j));
+  }
+  double res = __dadd_rn(__dadd_rn(__dadd_rn(acc[0], acc[1]), __dadd_rn(acc[2], acc[3])),
+                         __dadd_rn(__dadd_rn(acc[4], acc[5]), __dadd_rn(acc[6], acc[7])));
+  for (; i < n; ++i) res = __dadd_rn(res, r.at(j0 + i));
+  return res;
+}
+
+// numpy's pairwise float64 sum of the dense row: mapvi_rowsum's replay of mapvi_plan's list
+__device__ __forceinline__ double psrlo_rowsum(PoRow& r, int n_runs, const short* plan_run, const signed char* plan_merges) {
+  double st[MAPVI_DEPTH + 1];
+#pragma unroll
+  for (int k = 0; k <= MAPVI_DEPTH; ++k) st[k] = 0.0;
+  int j0 = 0;
+  for (int k = 0; k < n_runs; ++k) {
+    const int n = plan_run[k];
+    const double x = psrlo_run(r, j0, n);
+    j0 += n;
+#pragma unroll
+    for (int d = MAPVI_DEPTH; d > 0; --d) st[d] = st[d - 1];
+    st[0] = x;
+    for (int m = plan_merges[k]; m > 0; --m) {
+      st[0] = __dadd_rn(st[1], st[0]);
+#pragma unroll
+      for (int d = 1; d < MAPVI_DEPTH; ++d) st[d] = st[d + 1];
+    }
+  }
+  return st[0];
+}
+
+// element j of the simple row (ptr range [rb, re)) at sample k: the layout's value, the value at z, or 0
+__device__ __forceinline__ float psrlo_simple_at(const int32_t* __restrict__ col, const float* __restrict__ pmk, int64_t rb,
+                                                 int64_t re, int j, int zk, float bump) {
+  if (j == zk) return bump;
+  int64_t lo = rb, hi = re;
+  while (lo < hi) {
+    const int64_t m = lo + ((hi - lo) >> 1);
+    const int cc = col[m];
+    if (cc == j) return pmk[m];
+    if (cc < j) lo = m + 1; else hi = m;
+  }
+  return 0.0f;
+}
+
+__global__ void __launch_bounds__(PSRLO_THREADS) k_psrlo_sample(PsArgs p, PcCounters c, PoArgs o, const int32_t* __restrict__ list,
+                                                                const int64_t* __restrict__ state_off, int A, int s_max) {
+  extern __shared__ __align__(16) float po_lds[];
+  __shared__ int plan_work[2 * MAPVI_DEPTH + 2];
+  __shared__ short plan_run[MAPVI_MAX_RUNS];
+  __shared__ signed char plan_merges[MAPVI_MAX_RUNS];
+  __shared__ int plan_n;
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int b = list[blockIdx.x];
+  const int64_t soff = state_off[b];
+  const int S = (int)(state_off[b + 1] - soff);
+  const int rows = S * A, psi = o.psi[b];
+  const int64_t r0 = soff * A;
+  const int64_t* __restrict__ ptr = p.row_ptr + r0;
+  const int64_t nz0 = ptr[0], nzb = ptr[rows] - nz0;
+  int32_t* __restrict__ z = o.z + o.k_off[b];
+  float* __restrict__ pmk = o.pmk + o.pm_off[b];   // [psi][nzb], indexed by layout position - nz0
+  float* __restrict__ bump = o.bump + o.q_off[b];  // [psi][rows]
+  if (tid == 0) plan_n = mapvi_plan(S, plan_work, plan_run, plan_merges);
+  const bool philox = o.post == nullptr;
+  const uint2 key = p.key[b];
+  const unsigned long long ep = (unsigned long long)p.episode[b] << 32;
+  if (philox) {
+    for (int k = tid; k < psi; k += PSRLO_THREADS) {
+      uint32_t w[4];
+      philox4x32_10((uint32_t)k, (uint32_t)(ep >> 32), 9u, 0u, key.x, key.y, w);
+      z[k] = (int32_t)(((unsigned long long)w[0] * (unsigned long long)S) >> 32);
+    }
+    for (int row = tid; row < rows; row += PSRLO_THREADS) {   // N_NIG.sample as k_psrl_sample's lane 0 draws it
+      const float* hp = p.rp + (r0 + row) * 4;
+      uint32_t draw = 0;
+      const unsigned long long n = ep | (uint32_t)row;
+      const double ga = philox_gamma((double)hp[2], n, key, draw, 7u);
+      const float tau = (float)__dmul_rn((double)__fdiv_rn(1.0f, hp[3]), ga);
+      const float sd = __fsqrt_rn(__fdiv_rn(1.0f, __fmul_rn(hp[1], tau)));
+      uint32_t w[4];
+      philox4x32_10((uint32_t)n, (uint32_t)(n >> 32), 7u, draw, key.x, key.y, w);
+      const double g = sqrt(-2.0 * log(1.0 - u53(w[0], w[1]))) * cos(6.283185307179586476925286766559 * u53(w[2], w[3]));
+      p.Rs[r0 + row] = (float)__dadd_rn((double)hp[0], __dmul_rn((double)sd, g));
+    }
+  }
+  __syncthreads();   // the plan, and with the Philox sampler the workgroup's z and rewards
+  const int n_runs = plan_n;
+  const double eta = o.eta[b], l4 = o.log4s[b];
+  const double l3 = __dmul_rn(3.0, l4);
+  for (int row = tid; row < rows; row += PSRLO_THREADS) {
+    const int32_t nsa = c.n_sa[r0 + row];
+    const bool simple = (double)nsa < eta;
+    o.simple[r0 + row] = simple ? 1 : 0;
+    if (!simple) continue;
+    const int64_t rb = ptr[row], re = ptr[row + 1];
+    const double den = (double)(nsa > 1 ? nsa : 1);
+    for (int64_t e = rb; e < re; ++e) {
+      const int32_t n = o.N[e];
+      const double ph = __ddiv_rn((double)n, den), nm = (double)(n > 1 ? n : 1);
+      const double w = __dadd_rn(__dsqrt_rn(__ddiv_rn(__dmul_rn(__dmul_rn(3.0, ph), l4), nm)), __ddiv_rn(l3, nm));
+      o.pm[e] = __dsub_rn(ph, w < ph ? w : ph);
+    }
+    for (int k = 0; k < psi; ++k) {
+      const int zk = z[k];
+      PoRow r{p.col, o.pm, rb, re};
+      const double summing = __dsub_rn(1.0, __dadd_rn(0.0, psrlo_rowsum(r, n_runs, plan_run, plan_merges)));
+      int64_t ez = -1;
+      for (int64_t e = rb; e < re; ++e)
+        if (p.col[e] == zk) ez = e;
+      double at_z = __dadd_rn(0.0, summing);
+      if (ez >= 0) {
+        at_z = __dadd_rn(o.pm[ez], summing);
+        o.pm[ez] = at_z;
+      }
+      float* __restrict__ out = pmk + (int64_t)k * nzb - nz0;
+      for (int64_t e = rb; e < re; ++e) out[e] = (float)o.pm[e];
+      bump[(int64_t)k * rows + row] = (float)at_z;
+      if (ez >= 0) o.pm[ez] = __dsub_rn(at_z, summing);
+    }
+  }
+  // R_ext[s, j] = R[s, j % A]
+  const int AX = A * psi;
+  float* __restrict__ Rx = o.Rx + o.q_off[b];
+  for (int i = tid; i < rows * psi; i += PSRLO_THREADS) Rx[i] = p.Rs[r0 + (int64_t)(i / AX) * A + (i % AX) % A];
+  __syncthreads();   // the workgroup's flags, pmk and bump are written
+  float* __restrict__ T = o.Tx + o.tx_off[b];
+  const float* __restrict__ post = philox ? nullptr : o.post + o.tx_off[b];
+  const int n1 = o.n1[b];
+  const float prior = p.tprior[b];
+  float* g = po_lds + (size_t)wid * s_max;   // Philox: the wavefront's variates between the draw and the division
+  const bool vec = (S & 3) == 0;   // tx_off is a multiple of 4 elements and so is every row's start
+  for (int item = wid; item < rows * psi; item += PSRLO_THREADS / 64) {
+    const int row = item / psi, k = item % psi;
+    float* __restrict__ dst = T + (int64_t)item * S;
+    if (o.simple[r0 + row]) {
+      const int64_t rb = ptr[row], re = ptr[row + 1];
+      const float* __restrict__ vk = pmk + (int64_t)k * nzb - nz0;
+      const int zk = z[k];
+      const float bv = bump[(int64_t)k * rows + row];
+      if (vec) {
+        for (int j = lane * 4; j < S; j += 256) {
+          float4 v;
+          v.x = psrlo_simple_at(p.col, vk, rb, re, j, zk, bv);
+          v.y = psrlo_simple_at(p.col, vk, rb, re, j + 1, zk, bv);
+          v.z = psrlo_simple_at(p.col, vk, rb, re, j + 2, zk, bv);
+          v.w = psrlo_simple_at(p.col, vk, rb, re, j + 3, zk, bv);
+          *reinterpret_cast<float4*>(dst + j) = v;
+        }
+      } else {
+        for (int j = lane; j < S; j += 64) dst[j] = psrlo_simple_at(p.col, vk, rb, re, j, zk, bv);
+      }
+    } else if (philox) {
+      const int64_t rb = ptr[row], re = ptr[row + 1];
+      double part = 0.0;
+      for (int c = lane; c < S; c += 64) {
+        float shape = prior;
+        int64_t lo = rb, hi = re;
+        while (lo < hi) {   // the row's layout positions scattered over the prior
+          const int64_t m = lo + ((hi - lo) >> 1);
+          const int cc = p.col[m];
+          if (cc == c) { shape = p.tp[m]; break; }
+          if (cc < c) lo = m + 1; else hi = m;
+        }
+        uint32_t draw = 0;
+        const float v = (float)philox_gamma((double)shape, ep | ((uint32_t)item * (uint32_t)S + (uint32_t)c), key, draw, 8u);
+        g[c] = v;
+        part += (double)v;
+      }
+      part = psrl_wave_sum(part);
+      const float den = __fadd_rn(1e-5f, (float)part);
+      for (int c = lane; c < S; c += 64) dst[c] = __fdiv_rn(g[c], den);
+    } else {
+      const float* __restrict__ src = post + ((int64_t)k * n1 + o.pidx[r0 + row]) * S;
+      if (vec) {
+        for (int j = lane * 4; j < S; j += 256) *reinterpret_cast<float4*>(dst + j) = *reinterpret_cast<const float4*>(src + j);
+      } else {
+        for (int j = lane; j < S; j += 64) dst[j] = src[j];
+      }
+    }
+  }
+}
+
+// ---- host side: the reference's own draws of one optimistic_sampling call ---------------------------------------------------
+namespace psrlo_host {
+
+// RandomState.randint(n) for 1 <= n <= 2^32: masked rejection on 32-bit words; n = 1 draws nothing
+inline int32_t randint(cmdp_rc::NumpyStream& s, int n) {
+  const uint32_t mx = (uint32_t)(n - 1);
+  if (mx == 0) return 0;
+  uint32_t mask = mx;
+  mask |= mask >> 1; mask |= mask >> 2; mask |= mask >> 4; mask |= mask >> 8; mask |= mask >> 16;
+  uint32_t v;
+  do { v = s.next_u32() & mask; } while (v > mx);
+  return (int32_t)v;
+}
+
+// before_start_interacting's randn(S, A * psi) on the agent's stream: only its position matters
+inline void skip_randn(cmdp_rc::NumpyStream& s, int64_t n) {
+  for (int64_t i = 0; i < n; ++i) (void)s.legacy_gauss();
+}
+
+// One optimistic_sampling call and the N_NIG sample that follows it, on the instance's three streams (`ts` M_DIR's, `rs`
+// N_NIG's, `as` the agent's).  n_sa [S * A]; (ptr, col, val) the M_DIR hyper-parameters over `prior`, ptr[r] indexing col /
+// val directly.  Out: simple [S * A]; pidx [S * A] the index of a posterior row among the posterior rows, -1 for a simple
+// one; post [psi][n1][S] the normalised posterior rows; z [psi], -1 where the reference draws none; R [S * A].  Returns n1.
+inline int draw(cmdp_rc::NumpyStream& ts, cmdp_rc::NumpyStream& rs, cmdp_rc::NumpyStream& as, int S, int A, int psi, double eta,
+                const int32_t* n_sa, const int64_t* ptr, const int32_t* col, const float* val, float prior, const float* rhp,
+                uint8_t* simple, int32_t* pidx, float* post, int32_t* z, float* R) {
+  const int SA = S * A;
+  int n1 = 0;
+  for (int r = 0; r < SA; ++r) {
+    simple[r] = (double)n_sa[r] < eta ? 1 : 0;
+    pidx[r] = simple[r] ? -1 : n1++;
+  }
+  const int n2 = SA - n1;
+  for (int k = 0; k < psi; ++k) {
+    for (int r = 0; r < SA; ++r) {
+      if (simple[r]) continue;
+      float* row = post + ((int64_t)k * n1 + pidx[r]) * S;
+      psrl_host::reference_draw_row(ts, S, ptr[r], ptr[r + 1], col, val, prior, row);
+    }
+    z[k] = n2 > 0 ? randint(as, S) : -1;
+  }
+  psrl_host::reference_draw_rewards(rs, SA, rhp, R);
+  return n1;
+}
+
+}  // namespace psrlo_host

@@ -896,7 +896,8 @@ int cmdp_psrl_run_logged(cmdp_psrl_t* a, const cmdp_loop_desc* desc, int64_t n_l
    with N[s, a].sum() >= 2 * (N[s, a].sum() - nu_k[s, a]); the solve is discounted_value_iteration(T, R) with gamma = 0.99,
    epsilon = 1e-3 and the reference's scheme rule per sample (cmdp_vi_discounted_dense).  Creation performs
    before_start_interacting: the first sample and solve, on the prior.  The statistics are CMDP_STAT_PSRL_*.  Optimistic
-   sampling, truncate_reward_with_max and min_steps_before_new_episode != 0 are not built. */
+   sampling is cmdp_psrlc_create_optimistic's (below); truncate_reward_with_max and min_steps_before_new_episode != 0 are not
+   built. */
 typedef struct cmdp_psrlc cmdp_psrlc_t;
 int cmdp_psrlc_create(cmdp_psrlc_t** out, cmdp_t* env, const int32_t* seeds, int64_t optimization_horizon,
                       const float* reward_prior, const float* transition_prior, int sampler, int actor);
@@ -934,6 +935,38 @@ int cmdp_psrlc_average_reward(cmdp_psrlc_t* a, const uint8_t* mask, double* avg,
    value is CMDP_ERR_INVALID.  Both routes fill the same outputs and CMDP_STAT_PSRL_POLICY_KERNEL_MS. */
 enum { CMDP_PSRLC_OPT_SIZE_THRESHOLD = 1, CMDP_PSRLC_OPT_MAX_SWEEPS = 2, CMDP_PSRLC_OPT_POLICY_SOLVER = 3 };
 int cmdp_psrlc_set_option(cmdp_psrlc_t* a, int option, int64_t value);
+/* The same agent with the reference's OPTIMISTIC sampling (no_optimistic_sampling=False, its default; K18,
+   csrc/cmdp_psrlo.h): psi [B] extended actions per real action, eta [B] the visit count below which a row is sampled simply,
+   log4s [B] = log(4 S) as the caller's NumPy gives it.  The handle serves every cmdp_psrlc_* entry: the walk acts greedily on
+   the extended Q [S][A * psi] and plays j / psi, the sample is T_ext [S, A * psi, S] with R_ext[s, j] = R[s, j % A], the
+   solver is cmdp_vi_discounted_dense's on the extended arrays, and the agent's N[s, a, s'] is kept as int32.
+   CMDP_PSRL_SAMPLER_REFERENCE draws on the host (the two models' streams and the agent's own RandomState(seed));
+   CMDP_PSRL_SAMPLER_PHILOX draws the posterior rows, z and the rewards in k_psrlo_sample, a pure function of (seed, episode,
+   tables).  Refused before anything is allocated: S * A * psi * S of an instance reaching 2^32 (CMDP_ERR_UNSUPPORTED) and a
+   batch whose extended arrays (with the reference sampler also their upload) exceed the free device memory
+   (CMDP_ERR_OVERFLOW; the message names the bytes). */
+int cmdp_psrlc_create_optimistic(cmdp_psrlc_t** out, cmdp_t* env, const int32_t* seeds, int64_t optimization_horizon,
+                                 const float* reward_prior, const float* transition_prior, const int32_t* psi, const double* eta,
+                                 const double* log4s, int sampler, int actor);
+/* The last optimistic sample of every instance: T dense [sum S * A * psi * S], R [R] as N_NIG gave it, R_ext and the actor's
+   Q [sum S * A * psi], z [sum psi] (reference sampler: -1 where no row was simple and none was drawn), the simple mask [R], and the solve's
+   sweeps, scheme and status [B].  Each may be NULL.  CMDP_ERR_UNSUPPORTED on a plain handle, as cmdp_psrlc_last_sample is on
+   an optimistic one. */
+int cmdp_psrlc_last_sample_optimistic(cmdp_psrlc_t* a, float* T, float* R, float* R_ext, float* Q, int32_t* z, uint8_t* simple,
+                                      int64_t* sweeps, int32_t* scheme, int32_t* status);
+/* The agent's N[s, a, s'] at the positions of cmdp_psrlc_layout (0 elsewhere, for ever); optimistic handles only. */
+int cmdp_psrlc_counts(cmdp_psrlc_t* a, int32_t* N);
+/* The host half of an optimistic sample with the reference sampler, callable without a device: one optimistic_sampling call's
+   draws and the N_NIG sample that follows on three RandomState streams handed over and returned as cmdp_psrl_reference_sample
+   does (t: M_DIR's, r: N_NIG's, a: the agent's, which first skips `skip_randn` legacy Gaussians).  n_sa [S * A]; the M_DIR
+   hyper-parameters as a layout over `prior`.  Out: simple [S * A]; *n_posterior = n1; posterior [psi][n1][S] the normalised
+   posterior rows in row-major order (capacity psi * S * A * S); z [psi], -1 where none is drawn; R [S * A]. */
+int cmdp_psrlo_reference_draw(uint32_t* t_key, int32_t* t_pos, int32_t* t_has_gauss, double* t_gauss, uint32_t* r_key,
+                              int32_t* r_pos, int32_t* r_has_gauss, double* r_gauss, uint32_t* a_key, int32_t* a_pos,
+                              int32_t* a_has_gauss, double* a_gauss, int n_states, int n_actions, int psi, double eta,
+                              int64_t skip_randn, const int32_t* n_sa, const int64_t* row_ptr, const int32_t* col, const float* val,
+                              float prior, const float* reward_hp, uint8_t* simple, int32_t* n_posterior, float* posterior,
+                              int32_t* z, float* R);
 /* discounted_value_iteration(T, R) (colosseum/dynamic_programming/infinite_horizon.py:14-44) on `count` dense float32 problems
    in one launch (k_vi_discounted_dense, csrc/cmdp_psrlc.h): T concatenated [S, A, S] per instance, R [S, A]; Q receives [S][A]
    and V [S] per instance.  scheme: CMDP_SCHEME_AUTO applies the reference's rule per instance on its count of non-zero
