@@ -581,13 +581,26 @@ class BatchedPSRLContinuousOptimistic(BatchedPSRLContinuous):
     S^2 * A > 6 000 000 (the reference samples plainly there: `BatchedPSRLContinuous`), custom `get_psi` / `get_omega` /
     `get_kappa` / `get_eta`, and what `BatchedPSRLContinuous` refuses.  `sampler="reference"` draws the reference's own
     numbers on the host (a fourth stream, the agent's own RandomState(seed), gives z); `sampler="philox"` draws posterior
-    rows, z and rewards on the device, a pure function of (seed, episode, tables).  `run_logged` is not built."""
+    rows, z and rewards on the device, a pure function of (seed, episode, tables).  The sample and its solve take one of two
+    routes, `sample_solver="dense" | "compact"` at creation or `set_sample_solver` later.  "dense" (the default) writes T_ext
+    and solves it with k_vi_discounted_dense: O(S * A * psi * S) memory and work per sweep.  "compact" (kernel K19,
+    csrc/cmdp_psrlo_vi.h) keeps the sample as the sampler leaves it -- per sample the layout values and the value at z_k of the
+    simple rows, dense rows only for the posterior rows of the draw -- and solves it there: T_ext is never built, a simple row
+    costs its layout length per sweep, and the Q agrees with the dense route's within the two kernels' rounding bounds, not
+    bit for bit.  `last_sample()["T"]` is the same T_ext on both routes, bit for bit.  `run_logged` is not built."""
+
+    _SAMPLE_SOLVERS = ("dense", "compact")
+    _STATS = BatchedPSRLContinuous._STATS + (("sample_bytes", L.STAT_PSRL_SAMPLE_BYTES), ("sample_solver", L.STAT_PSRL_SAMPLE_SOLVER))
 
     def __init__(self, env: BatchedMDP, seeds: Sequence[int], optimization_horizon: int, reward_prior_model=None,
                  transitions_prior_model=None, rewards_prior_prms=None, transitions_prior_prms=None, epsilon_greedy=None,
                  boltzmann_temperature=None, psi_weight=1.0, omega_weight=1.0, kappa_weight=1.0, eta_weight=1.0, get_psi=None,
                  get_omega=None, get_kappa=None, get_eta=None, p=0.05, no_optimistic_sampling=False,
-                 truncate_reward_with_max=False, min_steps_before_new_episode=0, max_psi=60, sampler="reference"):
+                 truncate_reward_with_max=False, min_steps_before_new_episode=0, max_psi=60, sampler="reference",
+                 sample_solver="dense"):
+        if sample_solver not in self._SAMPLE_SOLVERS:
+            raise ValueError(f"sample solver {sample_solver!r}: one of {self._SAMPLE_SOLVERS}")
+        self._sample_solver = sample_solver
         if no_optimistic_sampling:
             raise NotImplementedError("no_optimistic_sampling=True is BatchedPSRLContinuous: this class builds the reference's "
                                       "optimistic sampling only")
@@ -616,7 +629,29 @@ class BatchedPSRLContinuousOptimistic(BatchedPSRLContinuous):
 
     def _create(self, env, seeds, horizon, rprior, tprior, sampler, actor):
         super()._create(env, seeds, horizon, rprior, tprior, L.ptr(self.psi), L.ptr(self.eta), L.ptr(self._log4s), sampler, actor,
-                        create="_create_optimistic")
+                        self._SAMPLE_SOLVERS.index(self._sample_solver), create="_create_optimistic_route")
+
+    def set_sample_solver(self, route: str):
+        """The route of the optimistic sample and its solve from the next `episode_end_update` on, internal or external:
+        "dense" or "compact" (the class docstring).  Anything else is a ValueError.  Switching an agent created compact to
+        dense allocates T_ext then; when it does not fit the call raises and the agent stays compact."""
+        routes = self._SAMPLE_SOLVERS
+        if route not in routes:   # before the handle is touched
+            raise ValueError(f"sample solver {route!r}: one of {routes}")
+        L.check(self._lib.cmdp_psrlc_set_option(self._h, L.PSRLC_OPT_SAMPLE_SOLVER, routes.index(route)))
+        self._sample_solver = route
+
+    @property
+    def sample_solver(self) -> str:
+        return self._sample_solver
+
+    def stats(self) -> dict:
+        """As `BatchedPSRLContinuous.stats`, with `sample_bytes` (device bytes the sample routes hold: pmk and bump, T_ext and
+        its upload once the dense route has run, the posterior blocks of the compact one) and `sample_solver` (the route of
+        the last round, whose kernels `sample_kernel_ms` and `vi_kernel_ms` time)."""
+        out = self._stats()
+        out["sample_solver"] = self._SAMPLE_SOLVERS[out["sample_solver"]]
+        return out
 
     def run_logged(self, desc, n_logs: int):
         raise NotImplementedError("the logged loop of BatchedPSRLContinuousOptimistic is not built")

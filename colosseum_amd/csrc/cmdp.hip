@@ -43,6 +43,7 @@ extern char** environ;
 #include "cmdp_psrl.h"
 #include "cmdp_psrlc.h"
 #include "cmdp_psrlo.h"
+#include "cmdp_psrlo_vi.h"
 #include "cmdp_map_vi.h"
 #include "cmdp_map_dvi.h"
 
@@ -350,6 +351,8 @@ struct cmdp {
   int64_t ps_rounds = 0, ps_solves = 0;
   double ps_sample_ms = 0.0, ps_vi_ms = 0.0, ps_ref_ms = 0.0;
   double ps_policy_ms = 0.0;   // CMDP_STAT_PSRL_POLICY_KERNEL_MS: the last K15 launch of an agent of this handle
+  double ps_sample_bytes = 0.0;   // CMDP_STAT_PSRL_SAMPLE_BYTES: what the optimistic agent's sample routes hold (K18 / K19)
+  int ps_sample_solver = 0;       // CMDP_STAT_PSRL_SAMPLE_SOLVER: the route of the optimistic agent's last round
   DevBuf<unsigned long long> d_ps_tally;   // continuous PSRL (K13): solves that did not converge, sweeps of the last round
   DevBuf<float> d_dense;  // CMDP_LAYOUT_DENSE: [R][dense_spad]
   int dense_spad = 0;
@@ -2004,6 +2007,10 @@ int cmdp_stat(cmdp_t* h, int which, double* out) {
   }
   if (which == CMDP_STAT_UCRL2_POLICY_SOLVED || which == CMDP_STAT_UCRL2_POLICY_REUSED) {
     *out = (double)(which == CMDP_STAT_UCRL2_POLICY_SOLVED ? h->uc_policy_solved : h->uc_policy_reused);
+    return CMDP_OK;
+  }
+  if (which == CMDP_STAT_PSRL_SAMPLE_BYTES || which == CMDP_STAT_PSRL_SAMPLE_SOLVER) {
+    *out = which == CMDP_STAT_PSRL_SAMPLE_BYTES ? h->ps_sample_bytes : (double)h->ps_sample_solver;
     return CMDP_OK;
   }
   if (which == CMDP_STAT_PSRL_UNCONVERGED || which == CMDP_STAT_PSRL_SWEEPS) {
@@ -5281,6 +5288,16 @@ struct cmdp_psrlo : cmdp_psrlc {
   std::vector<int32_t> h_nsa, h_z, h_pidx, h_n1;
   std::vector<uint8_t> h_simple;
   std::vector<float> h_post;
+  // the sample routes (CMDP_PSRLC_OPT_SAMPLE_SOLVER): 0 dense (d_Tx, d_post, h_post), 1 compact (K19, cmdp_psrlo_vi.h).  A
+  // route's arrays exist from the first round that takes it; an instance's last sample stays in the form of its round.
+  int sample_solver = 0;
+  bool has_dense = false, has_compact = false;
+  std::vector<uint8_t> h_route;            // [B] the route of the instance's last sample; 2: none (psrlo_grow failed)
+  std::vector<DevBuf<float>> pk;           // [B] compact: the posterior rows [psi][n1][S] of the last draw, grown on demand
+  std::vector<float*> h_pkptr;             // [B] their addresses, and on the device
+  DevBuf<float*> d_pkptr;
+  std::vector<std::vector<float>> h_pk;    // [B] reference sampler: the host staging of the same rows
+  DevBuf<float> d_stage;                   // one instance's expansion, for cmdp_psrlc_last_sample_optimistic
 };
 
 namespace {
@@ -5337,9 +5354,84 @@ int mapdvi_launch(MapDviArgs g, int count, int max_S, size_t lds, hipStream_t st
   return CMDP_OK;
 }
 
+// What the sample routes of an optimistic agent hold on the device (CMDP_STAT_PSRL_SAMPLE_BYTES): pmk and bump, which both
+// routes fill; T_ext and the reference sampler's upload of the dense route; the posterior blocks and their address table of
+// the compact one
+void psrlo_account(cmdp_psrlo* a) {
+  size_t n = 4 * (a->d_pmk.cap + a->d_bump.cap + a->d_Tx.cap + a->d_post.cap) + sizeof(float*) * a->d_pkptr.cap;
+  for (const DevBuf<float>& d : a->pk) n += 4 * d.cap;
+  a->env->ps_sample_bytes = (double)n;
+}
+
+// The arrays of sample route `route`, at the first round that takes it.  CMDP_ERR_OVERFLOW when the dense route's do not fit.
+int psrlo_ensure_route(cmdp_psrlo* a, int route) {
+  cmdp_t* h = a->env;
+  const bool reference = a->sampler == CMDP_PSRL_SAMPLER_REFERENCE;
+  if (route == 0 && !a->has_dense) {
+    const long long need = (long long)a->tx_total * (reference ? 2 : 1) * 4;
+    if (a->d_Tx.alloc((size_t)a->tx_total) != hipSuccess || (reference && a->d_post.alloc((size_t)a->tx_total) != hipSuccess)) {
+      (void)hipGetLastError();
+      a->d_Tx.release(); a->d_post.release();
+      return fail(CMDP_ERR_OVERFLOW, "the extended samples of the batch cannot be allocated: %lld bytes", need);
+    }
+    HIP_TRY(a->d_Tx.zero(h->stream));
+    if (reference) {
+      try {
+        a->h_post.resize((size_t)a->tx_total);
+      } catch (const std::bad_alloc&) {
+        a->d_Tx.release(); a->d_post.release();
+        return fail(CMDP_ERR_OVERFLOW, "the host staging of the reference sampler's posterior rows cannot be allocated: %lld bytes",
+                    (long long)a->tx_total * 4);
+      }
+    }
+    a->po.post = a->d_post.p;
+    a->po.Tx = a->d_Tx.p;
+    a->has_dense = true;
+  }
+  if (route == 1 && !a->has_compact) {
+    a->pk = std::vector<DevBuf<float>>((size_t)h->B);
+    a->h_pkptr.assign((size_t)h->B, nullptr);
+    a->h_pk.resize((size_t)h->B);
+    HIP_TRY(a->d_pkptr.upload(a->h_pkptr.data(), (size_t)h->B, h->stream));
+    a->has_compact = true;
+  }
+  psrlo_account(a);
+  return CMDP_OK;
+}
+
+// The compact route's block of instance b for n1 posterior rows: psi * n1 * S floats.  It only grows, to
+// max(need, min(2 * capacity, psi * S * A * S)) floats (to `need` alone when that much cannot be had) -- never to the worst
+// case ahead of need, which is T_ext itself.
+int psrlo_grow(cmdp_psrlo* a, int b, int n1, bool* moved) {
+  cmdp_t* h = a->env;
+  const size_t S = (size_t)(h->state_off[b + 1] - h->state_off[b]), psi = (size_t)a->h_psi[b];
+  const size_t need = psi * (size_t)n1 * S, worst = psi * S * (size_t)h->A * S;
+  DevBuf<float>& d = a->pk[(size_t)b];
+  if (need <= d.cap) return CMDP_OK;
+  // the new block is allocated before the old one is given up, first at the growth step and then at the need alone.  When
+  // neither fits the round fails; the row numbering of the new draw may already be on the device, so the instance counts as
+  // holding no sample (route 2) until a later round draws one
+  const size_t want = std::max(need, std::min(2 * d.cap, worst));
+  DevBuf<float> fresh;
+  if (fresh.alloc(want) != hipSuccess) {
+    (void)hipGetLastError();
+    if (want == need || fresh.alloc(need) != hipSuccess) {
+      (void)hipGetLastError();
+      a->h_route[(size_t)b] = 2;
+      return fail(CMDP_ERR_OVERFLOW, "the %d posterior rows of instance %d's optimistic sample cannot be held on the device: %zu "
+                  "bytes", n1, b, need * 4);
+    }
+  }
+  d.swap(fresh);   // `fresh` now holds the old block and frees it
+  a->h_pkptr[(size_t)b] = d.p;
+  *moved = true;
+  return CMDP_OK;
+}
+
 // The reference sampler's half of an optimistic sample: the host draws each listed instance's posterior rows, z and rewards
-// (psrlo_host::draw) and uploads them compactly
-int psrlo_reference_draws(cmdp_psrlo* a, int count) {
+// (psrlo_host::draw) and uploads them compactly -- on the dense route into d_post at the instance's T_ext offset, on the
+// compact route into the instance's own block, sized to this draw's posterior rows
+int psrlo_reference_draws(cmdp_psrlo* a, int count, bool compact) {
   cmdp_t* h = a->env;
   hipStream_t st = h->stream;
   const int A = h->A;
@@ -5347,15 +5439,37 @@ int psrlo_reference_draws(cmdp_psrlo* a, int count) {
   HIP_TRY(hipMemcpyAsync(a->h_rp.data(), a->d_rp.p, sizeof(float) * 4 * h->n_rows, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipMemcpyAsync(a->h_nsa.data(), a->d_nsa.p, sizeof(int32_t) * h->n_rows, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
-  const auto t0 = std::chrono::steady_clock::now();
   const int32_t* hl = a->pin_park.p + 2;
+  if (compact) {
+    bool moved = false;
+    int rc = CMDP_OK;
+    for (int k = 0; k < count && !rc; ++k) {
+      const int b = hl[k];
+      const int64_t r0 = h->state_off[b] * A, S = h->state_off[b + 1] - h->state_off[b];
+      int n1 = 0;
+      for (int64_t r = r0; r < r0 + S * A; ++r) n1 += !((double)a->h_nsa[(size_t)r] < a->h_eta[b]);
+      rc = psrlo_grow(a, b, n1, &moved);
+      if (!rc) {
+        try {
+          a->h_pk[(size_t)b].resize((size_t)a->h_psi[b] * n1 * S);
+        } catch (const std::bad_alloc&) {
+          rc = fail(CMDP_ERR_OVERFLOW, "the host staging of instance %d's posterior rows cannot be allocated: %lld bytes", b,
+                    (long long)a->h_psi[b] * n1 * S * 4);
+        }
+      }
+    }
+    if (moved) HIP_TRY(a->d_pkptr.upload(a->h_pkptr.data(), (size_t)h->B, st));
+    if (rc) return rc;
+  }
+  const auto t0 = std::chrono::steady_clock::now();
   cmdp_rc::Pool::get().parallel_for(count, [&](int k) {
     const int b = hl[k];
     const int64_t r0 = h->state_off[b] * A;
     const int S = (int)(h->state_off[b + 1] - h->state_off[b]);
     a->h_n1[b] = psrlo_host::draw(a->ts[b], a->rs[b], a->as[b], S, A, a->h_psi[b], a->h_eta[b], a->h_nsa.data() + r0,
                                   a->h_ptr.data() + r0, a->h_col.data(), a->h_tp.data(), a->h_prior[b], a->h_rp.data() + r0 * 4,
-                                  a->h_simple.data() + r0, a->h_pidx.data() + r0, a->h_post.data() + a->h_txoff[b],
+                                  a->h_simple.data() + r0, a->h_pidx.data() + r0,
+                                  compact ? a->h_pk[(size_t)b].data() : a->h_post.data() + a->h_txoff[b],
                                   a->h_z.data() + a->h_koff[b], a->h_R.data() + r0);
   });
   h->ps_ref_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -5363,7 +5477,9 @@ int psrlo_reference_draws(cmdp_psrlo* a, int count) {
     const int b = hl[k];
     const int64_t r0 = h->state_off[b] * A, S = h->state_off[b + 1] - h->state_off[b], rows = S * A;
     const int64_t np = (int64_t)a->h_psi[b] * a->h_n1[b] * S;
-    if (np) HIP_TRY(hipMemcpyAsync(a->d_post.p + a->h_txoff[b], a->h_post.data() + a->h_txoff[b], sizeof(float) * np, hipMemcpyHostToDevice, st));
+    float* dst = compact ? a->pk[(size_t)b].p : a->d_post.p + a->h_txoff[b];
+    const float* src = compact ? a->h_pk[(size_t)b].data() : a->h_post.data() + a->h_txoff[b];
+    if (np) HIP_TRY(hipMemcpyAsync(dst, src, sizeof(float) * np, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(a->d_z.p + a->h_koff[b], a->h_z.data() + a->h_koff[b], sizeof(int32_t) * a->h_psi[b], hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(a->d_pidx.p + r0, a->h_pidx.data() + r0, sizeof(int32_t) * rows, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(a->d_Rs.p + r0, a->h_R.data() + r0, sizeof(float) * rows, hipMemcpyHostToDevice, st));
@@ -5372,22 +5488,69 @@ int psrlo_reference_draws(cmdp_psrlo* a, int count) {
   return CMDP_OK;
 }
 
-// The optimistic sample (K18) of the `count` instances of pin_park's list into d_Tx / d_Rx: k_psrlo_sample, after the host's
-// draws with the reference sampler; with the Philox sampler the kernel draws everything itself.
+// The compact route with the Philox sampler: k_psrlo_count numbers the listed instances' posterior rows, the host reads the
+// counts and sizes the blocks the sample kernel will fill
+int psrlo_size_blocks(cmdp_psrlo* a, int count) {
+  cmdp_t* h = a->env;
+  hipStream_t st = h->stream;
+  hipLaunchKernelGGL(k_psrlo_count, dim3(count), dim3(64), 0, st, a->cnt, a->d_eta.p, a->d_park.p + 2, h->d_state_off.p, h->A,
+                     a->d_pidx.p, a->d_n1.p);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(a->h_n1.data(), a->d_n1.p, sizeof(int32_t) * h->B, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  const int32_t* hl = a->pin_park.p + 2;
+  bool moved = false;
+  int rc = CMDP_OK;
+  for (int k = 0; k < count && !rc; ++k) rc = psrlo_grow(a, hl[k], a->h_n1[hl[k]], &moved);
+  if (moved) HIP_TRY(a->d_pkptr.upload(a->h_pkptr.data(), (size_t)h->B, st));
+  return rc;
+}
+
+// The optimistic sample (K18) of the `count` instances of pin_park's list, by the handle's sample route: k_psrlo_sample after
+// the host's draws with the reference sampler; with the Philox sampler the kernel draws everything itself.  The dense route
+// fills d_Tx / d_Rx, the compact one (K19) leaves the compact sample of cmdp_psrlo_vi.h.
 int psrlo_sample(cmdp_psrlo* a, int count) {
   cmdp_t* h = a->env;
   hipStream_t st = h->stream;
   const int A = h->A;
   const int32_t* list = a->d_park.p + 2;
-  if (a->sampler == CMDP_PSRL_SAMPLER_REFERENCE)
-    if (int rc = psrlo_reference_draws(a, count)) return rc;
+  const bool compact = a->sample_solver == 1;
+  if (int rc = psrlo_ensure_route(a, a->sample_solver)) return rc;
+  if (a->sampler == CMDP_PSRL_SAMPLER_REFERENCE) {
+    if (int rc = psrlo_reference_draws(a, count, compact)) return rc;
+  } else if (compact) {
+    if (int rc = psrlo_size_blocks(a, count)) return rc;
+  }
+  PoArgs po = a->po;
+  if (compact) {
+    po.pk = a->d_pkptr.p;
+    po.pk_from_host = a->sampler == CMDP_PSRL_SAMPLER_REFERENCE ? 1 : 0;
+  }
   HIP_TRY(hipEventRecord(a->ev[0], st));
   if (int rc = set_lds(k_psrlo_sample, a->sample_lds)) return rc;
-  hipLaunchKernelGGL(k_psrlo_sample, dim3(count), dim3(PSRLO_THREADS), a->sample_lds, st, a->args, a->cnt, a->po, list,
+  hipLaunchKernelGGL(k_psrlo_sample, dim3(count), dim3(PSRLO_THREADS), a->sample_lds, st, a->args, a->cnt, po, list,
                      h->d_state_off.p, A, h->max_S);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipEventRecord(a->ev[1], st));
   a->ev_sample = true;
+  for (int k = 0; k < count; ++k) a->h_route[(size_t)a->pin_park.p[2 + k]] = (uint8_t)a->sample_solver;
+  h->ps_sample_solver = a->sample_solver;
+  psrlo_account(a);
+  return CMDP_OK;
+}
+
+// K19's launch on device-resident arguments: what cmdp_vi_discounted_optimistic does after its uploads and what the optimistic
+// agent does for the instances of a round on the compact route
+int pov_launch(PovArgs g, int count, int max_S, int max_rows, hipStream_t st) {
+  if (count == 0) return CMDP_OK;
+  // Host-only picker of where the sweeps read the row flags and ranges: LDS when they fit, else global memory.  The results
+  // do not depend on it (cmdp_psrlo_vi.h); CMDP_POV_DESC=0 forces global memory, for measurements and the tests.
+  const char* e = std::getenv("CMDP_POV_DESC");
+  g.desc_rows = e && e[0] == '0' && e[1] == '\0' ? 0 : pov_desc_rows(max_rows);
+  const size_t lds = pov_lds_bytes(max_S, g.desc_rows);
+  if (int rc = set_lds(k_vi_discounted_optimistic, lds)) return rc;
+  hipLaunchKernelGGL(k_vi_discounted_optimistic, dim3(count), dim3(POV_WAVES * 64), lds, st, g);
+  HIP_TRY(hipGetLastError());
   return CMDP_OK;
 }
 
@@ -5407,7 +5570,15 @@ int psrlc_round(cmdp_psrlc_t* a, int count, int stop, int64_t n_steps) {
     g.T = o->d_Tx.p; g.R = o->d_Rx.p; g.Q = o->d_Qx.p;
   }
   HIP_TRY(hipEventRecord(a->ev[2], st));
-  if (int rc = ddv_launch(g, count, h->max_S, st)) return rc;
+  if (o && o->sample_solver == 1) {   // K19 on the compact sample: the same outputs, T_ext never built
+    PovArgs v{list, a->d_S.p, a->d_A.p, o->d_psi.p, a->d_roff.p, h->d_state_off.p, o->d_qoff.p, o->d_koff.p, o->d_pmoff.p,
+              a->d_row_ptr.p, a->d_col.p, o->d_simple.p, o->d_pidx.p, o->d_n1.p, o->d_z.p, o->d_pmk.p, o->d_bump.p, o->d_pkptr.p,
+              a->d_Rs.p, 0.99f, 1e-3, CMDP_SCHEME_AUTO, a->size_threshold, a->density_threshold, a->max_sweeps, o->d_Qx.p,
+              a->d_V.p, a->d_sweeps.p, a->d_scheme.p, a->d_status.p, 0};
+    if (int rc = pov_launch(v, count, h->max_S, h->max_S * h->A, st)) return rc;
+  } else if (int rc = ddv_launch(g, count, h->max_S, st)) {
+    return rc;
+  }
   HIP_TRY(hipEventRecord(a->ev[3], st));
   a->ev_vi = true;
   HIP_TRY(hipMemsetAsync(h->d_ps_tally.p + 1, 0, sizeof(unsigned long long), st));
@@ -5469,11 +5640,13 @@ int cmdp_psrlc_create(cmdp_psrlc_t** out, cmdp_t* env, const int32_t* seeds, int
   return agent_attach(guard, out);
 }
 
-int cmdp_psrlc_create_optimistic(cmdp_psrlc_t** out, cmdp_t* env, const int32_t* seeds, int64_t optimization_horizon,
-                                 const float* reward_prior, const float* transition_prior, const int32_t* psi, const double* eta,
-                                 const double* log4s, int sampler, int actor) {
+int cmdp_psrlc_create_optimistic_route(cmdp_psrlc_t** out, cmdp_t* env, const int32_t* seeds, int64_t optimization_horizon,
+                                       const float* reward_prior, const float* transition_prior, const int32_t* psi,
+                                       const double* eta, const double* log4s, int sampler, int actor, int sample_solver) {
   if (!out) return fail(CMDP_ERR_INVALID, "null output");
   *out = nullptr;
+  if (sample_solver != 0 && sample_solver != 1)
+    return fail(CMDP_ERR_INVALID, "sample solver %d: 0 (the dense route) or 1 (the compact route, K19)", sample_solver);
   if (int rc = psrl_create_check(env, seeds, optimization_horizon, reward_prior, transition_prior, sampler, actor)) return rc;
   if (!psi || !eta || !log4s) return fail(CMDP_ERR_INVALID, "null argument (psi, eta or log4s)");
   if (int rc = park_check_env(env, false, "PSRLContinuous is the continuous setting's agent: the environment handle is episodic "
@@ -5514,12 +5687,19 @@ int cmdp_psrlc_create_optimistic(cmdp_psrlc_t** out, cmdp_t* env, const int32_t*
     const long long S = env->state_off[b + 1] - env->state_off[b];
     plain += (S * A * S + 3) & ~3LL;
   }
-  const long long need = ((long long)a->tx_total * (reference ? 2 : 1) + 3 * (long long)a->q_total + plain) * 4;
+  // the compact route (K19) allocates neither T_ext nor its upload: its posterior blocks grow with the draws
+  const bool dense = sample_solver == 0;
+  const long long need = ((dense ? (long long)a->tx_total * (reference ? 2 : 1) : 0) + 3 * (long long)a->q_total + plain) * 4;
   size_t free_b = 0, total_b = 0;
   HIP_TRY(hipMemGetInfo(&free_b, &total_b));
   if ((unsigned long long)need > free_b)
-    return fail(CMDP_ERR_OVERFLOW, "the extended samples T_ext [S, A * psi, S] of the batch and their upload take %lld bytes, %zu "
-                "bytes of device memory are free -- create smaller batches or lower max_psi", need, free_b);
+    return fail(CMDP_ERR_OVERFLOW, dense ? "the extended samples T_ext [S, A * psi, S] of the batch and their upload take %lld bytes, "
+                "%zu bytes of device memory are free -- create smaller batches or lower max_psi"
+                : "the extended Q, R_ext and bump arrays of the batch take %lld bytes, %zu bytes of device memory are free -- "
+                "create smaller batches or lower max_psi", need, free_b);
+  a->sample_solver = sample_solver;
+  a->h_route.assign((size_t)B, (uint8_t)sample_solver);
+  a->h_n1.assign((size_t)B, 0);
   if (int rc = psrlc_build(a, seeds, reward_prior, transition_prior)) return rc;
   hipStream_t st = env->stream;
   const int64_t R = env->n_rows, NZ = a->nz;
@@ -5528,11 +5708,8 @@ int cmdp_psrlc_create_optimistic(cmdp_psrlc_t** out, cmdp_t* env, const int32_t*
     a->h_pmoff[b] = pm_total;
     pm_total += (int64_t)psi[b] * (a->h_ptr[(size_t)(env->state_off[b + 1] * A)] - a->h_ptr[(size_t)(env->state_off[b] * A)]);
   }
-  if (a->d_Tx.alloc((size_t)a->tx_total) != hipSuccess || (reference && a->d_post.alloc((size_t)a->tx_total) != hipSuccess)) {
-    (void)hipGetLastError();
-    return fail(CMDP_ERR_OVERFLOW, "the extended samples of the batch cannot be allocated: %lld bytes", need);
-  }
-  HIP_TRY(a->d_Tx.zero(st));
+  if (dense)
+    if (int rc = psrlo_ensure_route(a, 0)) return rc;
   HIP_TRY(a->d_psi.upload(psi, B, st)); HIP_TRY(a->d_eta.upload(eta, B, st)); HIP_TRY(a->d_log4s.upload(log4s, B, st));
   HIP_TRY(a->d_Ax.upload(hAx.data(), B, st));
   HIP_TRY(a->d_qoff.upload(a->h_qoff.data(), B, st)); HIP_TRY(a->d_txoff.upload(a->h_txoff.data(), B, st));
@@ -5545,11 +5722,11 @@ int cmdp_psrlc_create_optimistic(cmdp_psrlc_t** out, cmdp_t* env, const int32_t*
                  a->d_Qx.p};
   if (reference) {
     try {
-      a->h_nsa.resize((size_t)R); a->h_z.resize((size_t)a->k_total); a->h_pidx.resize((size_t)R); a->h_n1.assign((size_t)B, 0);
-      a->h_simple.resize((size_t)R); a->h_post.resize((size_t)a->tx_total);
+      a->h_nsa.resize((size_t)R); a->h_z.resize((size_t)a->k_total); a->h_pidx.resize((size_t)R);
+      a->h_simple.resize((size_t)R);
     } catch (const std::bad_alloc&) {
-      return fail(CMDP_ERR_OVERFLOW, "the host staging of the reference sampler's posterior rows cannot be allocated: %lld bytes",
-                  (long long)a->tx_total * 4);
+      return fail(CMDP_ERR_OVERFLOW, "the host staging of the reference sampler's draws cannot be allocated: %lld bytes",
+                  (long long)R * 9 + (long long)a->k_total * 4);
     }
     // before_start_interacting: randn(S, A * psi) on the agent's own RandomState(seed)
     a->as.resize((size_t)B);
@@ -5567,6 +5744,13 @@ int cmdp_psrlc_create_optimistic(cmdp_psrlc_t** out, cmdp_t* env, const int32_t*
   const int rc = agent_attach(guard, &attached);
   *out = attached;
   return rc;
+}
+
+int cmdp_psrlc_create_optimistic(cmdp_psrlc_t** out, cmdp_t* env, const int32_t* seeds, int64_t optimization_horizon,
+                                 const float* reward_prior, const float* transition_prior, const int32_t* psi, const double* eta,
+                                 const double* log4s, int sampler, int actor) {
+  return cmdp_psrlc_create_optimistic_route(out, env, seeds, optimization_horizon, reward_prior, transition_prior, psi, eta, log4s,
+                                            sampler, actor, 0);
 }
 
 int cmdp_psrlc_destroy(cmdp_psrlc_t* a) {
@@ -5628,6 +5812,16 @@ int cmdp_psrlc_set_option(cmdp_psrlc_t* a, int option, int64_t value) {
     a->policy_solver = (int)value;
     return CMDP_OK;
   }
+  if (option == CMDP_PSRLC_OPT_SAMPLE_SOLVER) {
+    if (!a->optimistic)
+      return fail(CMDP_ERR_UNSUPPORTED, "the handle samples plainly: the sample solver is the optimistic agent's option");
+    if (value != 0 && value != 1)
+      return fail(CMDP_ERR_INVALID, "sample solver %lld: 0 (the dense route) or 1 (the compact route, K19)", (long long)value);
+    cmdp_psrlo* o = static_cast<cmdp_psrlo*>(a);
+    if (int rc = psrlo_ensure_route(o, (int)value)) return rc;   // the dense arrays may not fit: the handle stays as it is
+    o->sample_solver = (int)value;
+    return CMDP_OK;
+  }
   return fail(CMDP_ERR_INVALID, "unknown option %d", option);
 }
 
@@ -5658,11 +5852,33 @@ int cmdp_psrlc_last_sample_optimistic(cmdp_psrlc_t* a, float* T, float* R, float
   cmdp_psrlo* o = static_cast<cmdp_psrlo*>(a);
   cmdp_t* h = a->env;
   hipStream_t st = h->stream;
+  bool staged = false;
   if (T) {
     int64_t at = 0;
     for (int b = 0; b < h->B; ++b) {   // the workspace pads every instance to 16 bytes; the caller's array is dense
       const int64_t S = h->state_off[b + 1] - h->state_off[b], n = S * h->A * o->h_psi[b] * S;
-      HIP_TRY(hipMemcpyAsync(T + at, o->d_Tx.p + o->h_txoff[b], sizeof(float) * n, hipMemcpyDeviceToHost, st));
+      if (o->h_route[(size_t)b] == 2)
+        return fail(CMDP_ERR_INVALID, "instance %d holds no sample: its last round could not allocate its posterior rows", b);
+      if (o->h_route[(size_t)b] == 1) {
+        // a compact sample (K19): its expansion, instance by instance through a staging buffer of one instance's size
+        const int64_t r0 = h->state_off[b] * h->A;
+        const int n1 = o->h_n1[(size_t)b];
+        if (o->d_stage.alloc((size_t)n) != hipSuccess) {
+          (void)hipGetLastError();
+          return fail(CMDP_ERR_OVERFLOW, "the staging buffer of one instance's expansion cannot be allocated: %lld bytes",
+                      (long long)n * 4);
+        }
+        PoxArgs x{(int)S, h->A, o->h_psi[b], n1, a->d_row_ptr.p + r0, a->d_col.p, o->d_simple.p + r0, o->d_pidx.p + r0,
+                  o->d_z.p + o->h_koff[b], o->d_pmk.p + o->h_pmoff[b], o->d_bump.p + o->h_qoff[b], o->pk[(size_t)b].p, o->d_stage.p};
+        const int64_t items = S * h->A * o->h_psi[b];
+        hipLaunchKernelGGL(k_psrlo_expand, dim3((unsigned)std::min<int64_t>((items + 3) / 4, 4096)), dim3(256), 0, st, x);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(T + at, o->d_stage.p, sizeof(float) * n, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));   // the next instance reuses (and may reallocate) the staging buffer
+        staged = true;
+      } else {
+        HIP_TRY(hipMemcpyAsync(T + at, o->d_Tx.p + o->h_txoff[b], sizeof(float) * n, hipMemcpyDeviceToHost, st));
+      }
       at += n;
     }
   }
@@ -5673,6 +5889,7 @@ int cmdp_psrlc_last_sample_optimistic(cmdp_psrlc_t* a, float* T, float* R, float
   AGENT_FETCH(R, d_Rs, h->n_rows); AGENT_FETCH(sweeps, d_sweeps, h->B);
   AGENT_FETCH(scheme, d_scheme, h->B); AGENT_FETCH(status, d_status, h->B);
   HIP_TRY(hipStreamSynchronize(st));
+  if (staged) o->d_stage.release();   // an instance's T_ext: not kept between calls
   return CMDP_OK;
 }
 
@@ -5883,6 +6100,123 @@ int cmdp_vi_discounted_dense(int count, const int32_t* n_states, const int32_t* 
   HIP_TRY(ws->scheme.download(scheme_used, count, st));
   HIP_TRY(ws->status.download(status, count, st));
   HIP_TRY(hipStreamSynchronize(st));
+  return CMDP_OK;
+}
+
+int cmdp_vi_discounted_optimistic(int count, const int32_t* n_states, const int32_t* n_actions, const int32_t* psi,
+                                  const int64_t* row_ptr, const int32_t* col, const uint8_t* simple, const int32_t* z,
+                                  const float* pmk, const float* bump, const int32_t* pidx, const float* post, const float* R,
+                                  float gamma, double epsilon, int scheme, int64_t size_threshold, double density_threshold,
+                                  int64_t max_sweeps, float* Q, float* V, int64_t* sweeps, int32_t* scheme_used, int32_t* status) {
+  if (count < 0) return fail(CMDP_ERR_INVALID, "count %d is negative", count);
+  if (count == 0) return CMDP_OK;
+  const std::pair<const void*, const char*> needed[] = {{n_states, "n_states"}, {n_actions, "n_actions"}, {psi, "psi"},
+      {row_ptr, "row_ptr"}, {simple, "simple"}, {z, "z"}, {bump, "bump"}, {pidx, "pidx"}, {R, "R"}, {Q, "Q"}, {V, "V"},
+      {sweeps, "sweeps"}, {scheme_used, "scheme_used"}, {status, "status"}};
+  for (const auto& n : needed)
+    if (!n.first) return fail(CMDP_ERR_INVALID, "%s is null", n.second);
+  if (!std::isfinite(gamma)) return fail(CMDP_ERR_INVALID, "gamma %g is not finite", (double)gamma);
+  if (!(epsilon >= 0.0) || !std::isfinite(epsilon)) return fail(CMDP_ERR_INVALID, "epsilon %g is not a finite value >= 0", epsilon);
+  if (max_sweeps < 1) return fail(CMDP_ERR_INVALID, "max_sweeps %lld < 1", (long long)max_sweeps);
+  if (scheme != CMDP_SCHEME_AUTO && scheme != CMDP_SCHEME_JACOBI && scheme != CMDP_SCHEME_GAUSS_SEIDEL)
+    return fail(CMDP_ERR_INVALID, "scheme %d: CMDP_SCHEME_AUTO, CMDP_SCHEME_JACOBI or CMDP_SCHEME_GAUSS_SEIDEL", scheme);
+  if (size_threshold < 0) return fail(CMDP_ERR_INVALID, "size_threshold %lld is negative", (long long)size_threshold);
+  if (std::isnan(density_threshold)) return fail(CMDP_ERR_INVALID, "density_threshold is not a number");
+  BatchLayout L;
+  if (int rc = L.build(count, n_states, n_actions,
+                       {PSRL_MAX_STATES, "instance %d has %d states: the optimistic discounted solver (K19) keeps V and V_old in LDS "
+                                         "for at most %d states"}))
+    return rc;
+  const int64_t ns = L.ns, nr = L.nr;
+  if (row_ptr[0] != 0) return fail(CMDP_ERR_INVALID, "row_ptr[0] = %lld, not 0", (long long)row_ptr[0]);
+  for (int64_t r = 0; r < nr; ++r)
+    if (row_ptr[r + 1] < row_ptr[r]) return fail(CMDP_ERR_INVALID, "row_ptr decreases at row %lld", (long long)r);
+  const int64_t nz = row_ptr[nr];
+  if (nz > 0 && (!col || !pmk)) return fail(CMDP_ERR_INVALID, "null col / pmk");
+  // where the instances start in z, pmk, bump / Q and post; the blocks of post are padded to 16 bytes on the device
+  std::vector<int64_t> koff((size_t)count), pmoff((size_t)count), qoff((size_t)count), psrc((size_t)count), pdst((size_t)count);
+  std::vector<int32_t> n1((size_t)count, 0);
+  int64_t nk = 0, npm = 0, nq = 0, nps = 0, npd = 0;
+  for (int b = 0; b < count; ++b) {
+    const int S = n_states[b], A = n_actions[b];
+    if (psi[b] < 1 || (int64_t)psi[b] * A > 1 << 20)
+      return fail(CMDP_ERR_INVALID, "psi[%d] = %d: at least 1, and at most 2^20 extended actions", b, psi[b]);
+    if ((int64_t)S * A * psi[b] * S >= (int64_t)1 << 32)
+      return fail(CMDP_ERR_UNSUPPORTED, "instance %d: S * A * psi * S reaches 2^32", b);
+    koff[b] = nk; pmoff[b] = npm; qoff[b] = nq; psrc[b] = nps; pdst[b] = npd;
+    const int64_t r0 = L.roff[b], rows = L.rows(b), nzb = row_ptr[r0 + rows] - row_ptr[r0];
+    bool any_simple = false;
+    for (int64_t r = r0; r < r0 + rows; ++r) {
+      for (int64_t e = row_ptr[r]; e < row_ptr[r + 1]; ++e)
+        if (col[e] < 0 || col[e] >= S || (e > row_ptr[r] && col[e] <= col[e - 1]))
+          return fail(CMDP_ERR_INVALID, "col of row %lld is not ascending within [0, %d)", (long long)r, S);
+      if (!std::isfinite(R[r])) return fail(CMDP_ERR_INVALID, "R[%lld] is not finite", (long long)r);
+      if (simple[r]) {
+        any_simple = true;
+      } else {
+        if (pidx[r] != n1[b])
+          return fail(CMDP_ERR_INVALID, "pidx[%lld] = %d: posterior row %d of instance %d in row order", (long long)r, pidx[r], n1[b], b);
+        ++n1[b];
+      }
+    }
+    for (int k = 0; k < psi[b]; ++k) {
+      if (any_simple && (z[nk + k] < 0 || z[nk + k] >= S))
+        return fail(CMDP_ERR_INVALID, "z[%lld] = %d is not a state of instance %d", (long long)(nk + k), z[nk + k], b);
+      for (int64_t e = 0; e < nzb; ++e)
+        if (!std::isfinite(pmk[npm + k * nzb + e])) return fail(CMDP_ERR_INVALID, "pmk[%lld] is not finite", (long long)(npm + k * nzb + e));
+      for (int64_t r = 0; r < rows; ++r)
+        if (!std::isfinite(bump[nq + k * rows + r])) return fail(CMDP_ERR_INVALID, "bump[%lld] is not finite", (long long)(nq + k * rows + r));
+    }
+    const int64_t np = (int64_t)psi[b] * n1[b] * S;
+    if (np > 0 && !post) return fail(CMDP_ERR_INVALID, "post is null and instance %d has posterior rows", b);
+    for (int64_t i = 0; i < np; ++i)
+      if (!std::isfinite(post[nps + i])) return fail(CMDP_ERR_INVALID, "post[%lld] is not finite", (long long)(nps + i));
+    nk += psi[b]; npm += psi[b] * nzb; nq += psi[b] * rows; nps += np; npd += (np + 3) & ~(int64_t)3;
+  }
+  struct Ws {
+    DevBuf<int32_t> S, A, psi, col, pidx, n1, z, scheme, status;
+    DevBuf<int64_t> soff, roff, qoff, koff, pmoff, ptr, sweeps;
+    DevBuf<uint8_t> simple;
+    DevBuf<float> pmk, bump, post, R, Q, V;
+    DevBuf<float*> pp;
+  };
+  DeviceWorkspace<Ws> ws;
+  if (int rc = ws.acquire()) return rc;
+  hipStream_t st = ws.st;
+  HIP_TRY(ws->S.upload(n_states, count, st)); HIP_TRY(ws->A.upload(n_actions, count, st)); HIP_TRY(ws->psi.upload(psi, count, st));
+  HIP_TRY(ws->soff.upload(L.soff.data(), L.soff.size(), st)); HIP_TRY(ws->roff.upload(L.roff.data(), count, st));
+  HIP_TRY(ws->qoff.upload(qoff.data(), count, st)); HIP_TRY(ws->koff.upload(koff.data(), count, st));
+  HIP_TRY(ws->pmoff.upload(pmoff.data(), count, st)); HIP_TRY(ws->ptr.upload(row_ptr, (size_t)nr + 1, st));
+  HIP_TRY(ws->col.upload(col, (size_t)nz, st)); HIP_TRY(ws->simple.upload(simple, (size_t)nr, st));
+  HIP_TRY(ws->pidx.upload(pidx, (size_t)nr, st)); HIP_TRY(ws->n1.upload(n1.data(), count, st));
+  HIP_TRY(ws->z.upload(z, (size_t)nk, st)); HIP_TRY(ws->pmk.upload(pmk, (size_t)npm, st));
+  HIP_TRY(ws->bump.upload(bump, (size_t)nq, st)); HIP_TRY(ws->R.upload(R, (size_t)nr, st));
+  if (ws->post.alloc((size_t)npd) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(CMDP_ERR_OVERFLOW, "the posterior rows cannot be held on the device: %lld bytes", (long long)(npd * 4));
+  }
+  std::vector<float*> pp((size_t)count, nullptr);
+  for (int b = 0; b < count; ++b) {
+    const int64_t np = (int64_t)psi[b] * n1[b] * n_states[b];
+    if (!np) continue;
+    pp[b] = ws->post.p + pdst[b];
+    HIP_TRY(hipMemcpyAsync(pp[b], post + psrc[b], sizeof(float) * (size_t)np, hipMemcpyHostToDevice, st));
+  }
+  HIP_TRY(ws->pp.upload(pp.data(), count, st));
+  HIP_TRY(ws->Q.alloc((size_t)nq)); HIP_TRY(ws->V.alloc((size_t)ns));
+  HIP_TRY(ws->sweeps.alloc(count)); HIP_TRY(ws->scheme.alloc(count)); HIP_TRY(ws->status.alloc(count));
+  PovArgs g{nullptr, ws->S.p, ws->A.p, ws->psi.p, ws->roff.p, ws->soff.p, ws->qoff.p, ws->koff.p, ws->pmoff.p, ws->ptr.p, ws->col.p,
+            ws->simple.p, ws->pidx.p, ws->n1.p, ws->z.p, ws->pmk.p, ws->bump.p, ws->pp.p, ws->R.p, gamma, epsilon, scheme,
+            size_threshold, density_threshold, max_sweeps, ws->Q.p, ws->V.p, ws->sweeps.p, ws->scheme.p, ws->status.p, 0};
+  int max_rows = 0;
+  for (int b = 0; b < count; ++b) max_rows = std::max(max_rows, (int)L.rows(b));
+  if (int rc = pov_launch(g, count, L.max_S, max_rows, st)) return rc;
+  HIP_TRY(ws->Q.download(Q, (size_t)nq, st));
+  HIP_TRY(ws->V.download(V, (size_t)ns, st));
+  HIP_TRY(ws->sweeps.download(sweeps, count, st));
+  HIP_TRY(ws->scheme.download(scheme_used, count, st));
+  HIP_TRY(ws->status.download(status, count, st));
+  HIP_TRY(hipStreamSynchronize(st));   // `pp` is read by the upload until here
   return CMDP_OK;
 }
 

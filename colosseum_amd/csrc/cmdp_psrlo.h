@@ -37,6 +37,14 @@
 //       leaves float32(P_minus) of its layout positions (`pmk`) and the float32 value at z_k (`bump`).
 //     Phase 2, a wavefront per (row, k): the row of T_ext written once, coalesced (16-byte stores where S % 4 == 0): zeros,
 //       the layout positions and z_k for a simple row; the host's compact upload for a posterior row.
+// The COMPACT route (K19, cmdp_psrlo_vi.h; PoArgs::pk set) stops after Phase 1 for the simple rows: the compact sample of an
+//   instance is simple [R], z [psi], pmk [psi][nz_b] and bump [psi][S * A] exactly as Phase 1 leaves them (sample-major, the
+//   arrangement Phase 2 reads) and, for the n1_b posterior rows of THIS draw, the packed block pk[b] = [psi][n1_b][S]
+//   indexed through pidx -- sample-major, the arrangement psrlo_host::draw produces, so the reference sampler's rows are
+//   uploaded as drawn.  k_psrlo_count numbers the posterior rows (pidx, n1) before the block is sized.  With the Philox sampler
+//   Phase 2 writes each posterior row's variates into the block: the same counters (domain 8, n = episode << 32 | (j * S + c)
+//   with j the row of T_ext) and the same normalisation, so the sample stays the same pure function and its expansion is
+//   bit for bit the T_ext of the dense route.  T_ext, and R_ext's pairing, are never written to a T_ext-sized array.
 // CMDP_PSRL_SAMPLER_REFERENCE: psrlo_host::draw below draws the gammas, the z and the N_NIG sample on the instance's streams.
 // CMDP_PSRL_SAMPLER_PHILOX (`post` null): everything is drawn in the kernel, a pure function of (seed, episode, tables):
 //   z_k = (w0 * S) >> 32 of the block (n = episode << 32 | k, domain 9);  the gamma variate of element c of extended row
@@ -68,7 +76,31 @@ struct PoArgs {
   float* Tx;
   float* Rx;                // [sum S * A * psi]
   float* Qx;                // the actor's table
+  float* const* pk;         // [B] null: the dense route.  The compact route: the instance's posterior rows [psi][n1][S]; Tx unread
+  int pk_from_host;         // compact route: 1 the host has drawn and uploaded the posterior rows (reference sampler; `post`
+                            // unread), 0 the kernel draws them (Philox sampler)
 };
+
+// The compact route's numbering of the posterior rows of the listed instances, a wavefront per instance: pidx[row] = index of
+// a posterior row among the instance's posterior rows (-1 for a simple one), n1[b] their number.  The flag is Phase 1's.
+__global__ void __launch_bounds__(64) k_psrlo_count(PcCounters c, const double* __restrict__ eta, const int32_t* __restrict__ list,
+                                                    const int64_t* __restrict__ state_off, int A, int32_t* __restrict__ pidx,
+                                                    int32_t* __restrict__ n1) {
+  const int lane = threadIdx.x;
+  const int b = list[blockIdx.x];
+  const int64_t r0 = state_off[b] * A;
+  const int rows = (int)(state_off[b + 1] - state_off[b]) * A;
+  const double e = eta[b];
+  int run = 0;
+  for (int base = 0; base < rows; base += 64) {
+    const int row = base + lane;
+    const bool post = row < rows && !((double)c.n_sa[r0 + row] < e);
+    const unsigned long long m = __ballot(post);
+    if (row < rows) pidx[r0 + row] = post ? run + __popcll(m & ((1ull << lane) - 1ull)) : -1;
+    run += __popcll(m);
+  }
+  if (lane == 0) n1[b] = run;
+}
 
 __global__ void __launch_bounds__(256) k_psrlo_walk(EnvTables t, PsArgs p, PcCounters c, PoArgs o, int64_t n_steps,
                                                     const uint8_t* __restrict__ train_mask, int8_t* __restrict__ act_trace,
@@ -221,7 +253,7 @@ __global__ void __launch_bounds__(PSRLO_THREADS) k_psrlo_sample(PsArgs p, PcCoun
   float* __restrict__ pmk = o.pmk + o.pm_off[b];   // [psi][nzb], indexed by layout position - nz0
   float* __restrict__ bump = o.bump + o.q_off[b];  // [psi][rows]
   if (tid == 0) plan_n = mapvi_plan(S, plan_work, plan_run, plan_merges);
-  const bool philox = o.post == nullptr;
+  const bool philox = o.pk ? o.pk_from_host == 0 : o.post == nullptr;
   const uint2 key = p.key[b];
   const unsigned long long ep = (unsigned long long)p.episode[b] << 32;
   if (philox) {
@@ -283,7 +315,9 @@ __global__ void __launch_bounds__(PSRLO_THREADS) k_psrlo_sample(PsArgs p, PcCoun
   float* __restrict__ Rx = o.Rx + o.q_off[b];
   for (int i = tid; i < rows * psi; i += PSRLO_THREADS) Rx[i] = p.Rs[r0 + (int64_t)(i / AX) * A + (i % AX) % A];
   __syncthreads();   // the workgroup's flags, pmk and bump are written
-  float* __restrict__ T = o.Tx + o.tx_off[b];
+  const bool compact = o.pk != nullptr;
+  if (compact && !philox) return;   // the host has uploaded the posterior rows into the instance's block
+  float* __restrict__ T = compact ? o.pk[b] : o.Tx + o.tx_off[b];
   const float* __restrict__ post = philox ? nullptr : o.post + o.tx_off[b];
   const int n1 = o.n1[b];
   const float prior = p.tprior[b];
@@ -291,8 +325,10 @@ __global__ void __launch_bounds__(PSRLO_THREADS) k_psrlo_sample(PsArgs p, PcCoun
   const bool vec = (S & 3) == 0;   // tx_off is a multiple of 4 elements and so is every row's start
   for (int item = wid; item < rows * psi; item += PSRLO_THREADS / 64) {
     const int row = item / psi, k = item % psi;
-    float* __restrict__ dst = T + (int64_t)item * S;
-    if (o.simple[r0 + row]) {
+    const bool is_simple = o.simple[r0 + row] != 0;
+    if (compact && is_simple) continue;
+    float* __restrict__ dst = compact ? T + ((int64_t)k * n1 + o.pidx[r0 + row]) * S : T + (int64_t)item * S;
+    if (is_simple) {
       const int64_t rb = ptr[row], re = ptr[row + 1];
       const float* __restrict__ vk = pmk + (int64_t)k * nzb - nz0;
       const int zk = z[k];

@@ -143,6 +143,109 @@ def discounted_value_iteration_dense_batch(problems, gamma=0.99, epsilon=1e-3, s
     return out
 
 
+def optimistic_compact_from_dense(T_ext, psi, row_ptr, col, R, simple=None, z=None):
+    """The compact form (csrc/cmdp_psrlo_vi.h) of an extended sample `T_ext` [S, A * psi, S] float32 over the layout
+    (`row_ptr` [S * A + 1], `col`) of its real rows, with the real rewards `R` [S, A]: a dict of S, A, psi, row_ptr, col,
+    `simple` [S * A] bool, `z` [psi], `pmk` [psi, nz], `bump` [psi, S * A], `pidx` [S * A] (-1 on simple rows), `post`
+    [psi, n1, S] and R.  A real row can be simple when each of its psi copies is zero outside its layout columns and z_k.
+    Without `z`, z_k is the column outside the layout most such rows are non-zero at in copy k (0 when there is none);
+    without `simple`, every row that can be simple under that z is; the others are posterior rows, kept dense.
+    `optimistic_expand` is the inverse and is asserted to give `T_ext` back bit for bit."""
+    T = np.ascontiguousarray(T_ext, np.float32)
+    S, AX, S2 = T.shape
+    psi = int(psi)
+    A = AX // psi
+    assert S == S2 and A * psi == AX, T.shape
+    rows = S * A
+    row_ptr, col = np.asarray(row_ptr, np.int64), np.asarray(col, np.int32)
+    assert row_ptr.shape == (rows + 1,) and row_ptr[0] == 0 and len(col) == row_ptr[-1]
+    Tk = T.reshape(rows, psi, S)                     # extended row j = a * psi + k of state s: real row s * A + a, copy k
+    inlay = np.zeros((rows, S), bool)
+    inlay[np.repeat(np.arange(rows), np.diff(row_ptr)), col] = True
+    off = (Tk != 0) & ~inlay[:, None, :]             # non-zeros outside the layout
+    if z is None:
+        cand = (off.sum(-1) <= 1).all(-1)
+        z = np.zeros(psi, np.int32)
+        for k in range(psi):
+            votes = off[cand, k].sum(0)
+            z[k] = int(votes.argmax()) if votes.any() else 0
+    z = np.asarray(z, np.int32)
+    outside = off.copy()
+    outside[:, np.arange(psi), np.clip(z, 0, S - 1)] = False
+    can = ~outside.any((1, 2))
+    simple = can if simple is None else np.asarray(simple, bool).reshape(rows)
+    assert not (simple & ~can).any(), "a row marked simple is non-zero outside its layout and z"
+    assert not simple.any() or ((z >= 0) & (z < S)).all()
+    nz = len(col)
+    erow = np.repeat(np.arange(rows), np.diff(row_ptr))
+    pmk = np.ascontiguousarray(Tk[erow, :, col].T) if nz else np.zeros((psi, 0), np.float32)
+    pmk = pmk * simple[erow][None, :].astype(np.float32)
+    bump = np.where(simple[None, :], Tk[:, np.arange(psi), np.clip(z, 0, S - 1)].T, np.float32(0)).astype(np.float32)
+    pidx = np.where(simple, -1, np.cumsum(~simple) - 1).astype(np.int32)
+    post = np.ascontiguousarray(np.moveaxis(Tk[~simple], 0, 1))
+    out = dict(S=S, A=A, psi=psi, row_ptr=row_ptr, col=col, simple=simple, z=z, pmk=np.ascontiguousarray(pmk, np.float32),
+               bump=np.ascontiguousarray(bump), pidx=pidx, post=post, R=np.ascontiguousarray(R, np.float32).reshape(S, A))
+    assert np.array_equal(optimistic_expand(out), T)
+    return out
+
+
+def optimistic_expand(p):
+    """T_ext [S, A * psi, S] float32 of a compact sample (the dict of `optimistic_compact_from_dense`): zeros, the layout's
+    values, then z_k for a simple row; the dense rows for a posterior one."""
+    S, A, psi = p["S"], p["A"], p["psi"]
+    rows = S * A
+    row_ptr, col, simple = p["row_ptr"], p["col"], np.asarray(p["simple"], bool).reshape(rows)
+    Tk = np.zeros((rows, psi, S), np.float32)
+    erow = np.repeat(np.arange(rows), np.diff(row_ptr))
+    keep = simple[erow]
+    Tk[erow[keep], :, col[keep]] = p["pmk"][:, keep].T
+    if simple.any():
+        Tk[np.flatnonzero(simple)[:, None], np.arange(psi)[None, :], np.asarray(p["z"])[None, :]] = p["bump"][:, simple].T
+    if (~simple).any():
+        Tk[~simple] = np.moveaxis(np.asarray(p["post"], np.float32).reshape(psi, -1, S), 0, 1)
+    return Tk.reshape(S, A * psi, S)
+
+
+def discounted_value_iteration_optimistic_batch(problems, gamma=0.99, epsilon=1e-3, sparse_n_states_threshold=300 * 3 * 300,
+                                                sparse_nnz_per_threshold=0.2, scheme=None, max_sweeps=DP_MAX_ITERATION):
+    """`discounted_value_iteration(T_ext, R_ext)` on many COMPACT optimistic samples (dicts of
+    `optimistic_compact_from_dense`; they may differ in S, A and psi) in one launch of k_vi_discounted_optimistic (K19), the
+    optimistic PSRL agent's solver on its compact route: T_ext is never built, R_ext[s, j] = R[s, j % A] is computed.  The
+    arguments and the returns are `discounted_value_iteration_dense_batch`'s, with Q [S, A * psi]; the rule counts the
+    non-zero elements the expansion would hold.  `status` of the last call is left in
+    `discounted_value_iteration_optimistic_batch.status`."""
+    if not problems:
+        return []
+    n = len(problems)
+    S = np.array([p["S"] for p in problems], np.int32)
+    A = np.array([p["A"] for p in problems], np.int32)
+    psi = np.array([p["psi"] for p in problems], np.int32)
+    ptr, at = [np.zeros(1, np.int64)], 0
+    for p in problems:
+        rp = np.asarray(p["row_ptr"], np.int64)
+        assert rp.shape == (p["S"] * p["A"] + 1,) and np.shape(p["pmk"]) == (p["psi"], int(rp[-1]))
+        assert np.shape(p["bump"]) == (p["psi"], p["S"] * p["A"]) and np.shape(p["z"]) == (p["psi"],)
+        ptr.append(rp[1:] + at)
+        at += int(rp[-1])
+    cat = lambda key, dt: np.ascontiguousarray(np.concatenate([np.asarray(p[key], dt).ravel() for p in problems]), dt)  # noqa: E731
+    ptr = np.concatenate(ptr)
+    col, simple, z = cat("col", np.int32), cat("simple", np.uint8), cat("z", np.int32)
+    pmk, bump, pidx, post, R = cat("pmk", np.float32), cat("bump", np.float32), cat("pidx", np.int32), cat("post", np.float32), cat("R", np.float32)
+    Q, V = np.zeros(int((S * A * psi).sum()), np.float32), np.zeros(int(S.sum()), np.float32)
+    sweeps, used, status = np.zeros(n, np.int64), np.zeros(n, np.int32), np.zeros(n, np.int32)
+    L.check(L.load().cmdp_vi_discounted_optimistic(n, L.ptr(S), L.ptr(A), L.ptr(psi), L.ptr(ptr), L.ptr(col), L.ptr(simple), L.ptr(z),
+                                                   L.ptr(pmk), L.ptr(bump), L.ptr(pidx), L.ptr(post) if len(post) else None, L.ptr(R),
+                                                   float(gamma), float(epsilon), L.SCHEME_AUTO if scheme is None else int(scheme),
+                                                   int(sparse_n_states_threshold), float(sparse_nnz_per_threshold), int(max_sweeps),
+                                                   L.ptr(Q), L.ptr(V), L.ptr(sweeps), L.ptr(used), L.ptr(status)))
+    discounted_value_iteration_optimistic_batch.status = status
+    out, q0, v0 = [], 0, 0
+    for b, (s, ax) in enumerate(zip(S.tolist(), (A * psi).tolist())):
+        out.append((Q[q0:q0 + s * ax].reshape(s, ax), V[v0:v0 + s], int(sweeps[b]), int(used[b])))
+        q0, v0 = q0 + s * ax, v0 + s
+    return out
+
+
 def map_layout_from_dense(transition_hp, prior, keep=None):
     """Table form of dense M_DIR hyper-parameters [S, A, S] over `prior`: the positions that differ from the prior, plus
     those `keep` (bool [S, A, S]) names, per row in ascending column order -> (row_ptr [S * A + 1], col, hp)."""

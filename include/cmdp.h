@@ -323,7 +323,11 @@ enum { CMDP_STAT_DP_KERNEL_MS = 1, CMDP_STAT_DP_KERNEL = 2,
                                                 (k_mt_actions, the action bits) before the walk CMDP_STAT_ROLLOUT_KERNEL_MS times  */,
        CMDP_STAT_PSRL_UNCONVERGED = 28,      /* continuous PSRL agents of this handle (K13): solves that reached max_sweeps; the
                                                 actor then holds the last sweep's Q                                                */
-       CMDP_STAT_PSRL_SWEEPS = 29            /* ... sweeps of the last round's solves, summed over its instances                  */ };
+       CMDP_STAT_PSRL_SWEEPS = 29            /* ... sweeps of the last round's solves, summed over its instances                  */,
+       CMDP_STAT_PSRL_SAMPLE_BYTES = 30,     /* optimistic PSRL agent of this handle (K18 / K19): device bytes its sample routes hold
+                                                -- pmk and bump, T_ext and its upload (dense), the posterior blocks (compact)    */
+       CMDP_STAT_PSRL_SAMPLE_SOLVER = 31     /* ... the route of its last round (CMDP_PSRLC_OPT_SAMPLE_SOLVER), whose kernels
+                                                CMDP_STAT_PSRL_SAMPLE_KERNEL_MS and CMDP_STAT_PSRL_VI_KERNEL_MS time               */ };
 /* The UCRL2 and PSRL statistics belong to the environment handle: agents created on the same handle share them. */
 int cmdp_stat(cmdp_t* h, int which, double* out);
 /* Latency floor of the LDS-resident rollout kernels, measured on the current device: one wavefront per CU follows
@@ -933,7 +937,14 @@ int cmdp_psrlc_average_reward(cmdp_psrlc_t* a, const uint8_t* mask, double* avg,
    cmdp_psrlc_average_reward: 0 (the default) the dense route described above, 1 the tables route -- K17
    (cmdp_vi_discounted_map's kernel) straight on the posterior tables, which never allocates the dense workspace; any other
    value is CMDP_ERR_INVALID.  Both routes fill the same outputs and CMDP_STAT_PSRL_POLICY_KERNEL_MS. */
-enum { CMDP_PSRLC_OPT_SIZE_THRESHOLD = 1, CMDP_PSRLC_OPT_MAX_SWEEPS = 2, CMDP_PSRLC_OPT_POLICY_SOLVER = 3 };
+/* CMDP_PSRLC_OPT_SAMPLE_SOLVER (optimistic handles; CMDP_ERR_UNSUPPORTED on a plain one, any value but 0 and 1
+   CMDP_ERR_INVALID) picks the route of the optimistic sample and its solve from the next episode_end_update on, internal or
+   external: 0 (the default) the dense route, T_ext written and cmdp_vi_discounted_dense's kernel on it; 1 the compact route,
+   K19 (cmdp_vi_discounted_optimistic's kernel) on the compact sample, T_ext never built.  Switching a handle created compact to
+   dense allocates the dense arrays at that moment; when they do not fit it returns CMDP_ERR_OVERFLOW and the handle stays
+   compact.  An instance's last sample stays in the form of the round that drew it. */
+enum { CMDP_PSRLC_OPT_SIZE_THRESHOLD = 1, CMDP_PSRLC_OPT_MAX_SWEEPS = 2, CMDP_PSRLC_OPT_POLICY_SOLVER = 3,
+       CMDP_PSRLC_OPT_SAMPLE_SOLVER = 4 };
 int cmdp_psrlc_set_option(cmdp_psrlc_t* a, int option, int64_t value);
 /* The same agent with the reference's OPTIMISTIC sampling (no_optimistic_sampling=False, its default; K18,
    csrc/cmdp_psrlo.h): psi [B] extended actions per real action, eta [B] the visit count below which a row is sampled simply,
@@ -948,10 +959,24 @@ int cmdp_psrlc_set_option(cmdp_psrlc_t* a, int option, int64_t value);
 int cmdp_psrlc_create_optimistic(cmdp_psrlc_t** out, cmdp_t* env, const int32_t* seeds, int64_t optimization_horizon,
                                  const float* reward_prior, const float* transition_prior, const int32_t* psi, const double* eta,
                                  const double* log4s, int sampler, int actor);
+/* cmdp_psrlc_create_optimistic with the sample route chosen at creation: sample_solver 0 is that entry, 1 the compact route
+   (K19, csrc/cmdp_psrlo_vi.h; CMDP_PSRLC_OPT_SAMPLE_SOLVER), anything else CMDP_ERR_INVALID.  Created compact, the handle
+   allocates neither T_ext nor the reference sampler's T_ext-sized upload, and the memory refusal counts only the extended Q,
+   R_ext and bump arrays and the plain-sized workspace.  Per instance the compact sample keeps pmk [psi][nz_b] and bump
+   [psi][S * A] and one block of posterior rows [psi][n1_b][S] for the n1_b posterior rows of its last draw; a block only grows,
+   to max(need, min(2 * capacity, psi * S * A * S)) floats (to need alone when that much cannot be had), and a round that
+   cannot grow one fails with CMDP_ERR_OVERFLOW (the message names the bytes); that instance then holds no sample until a
+   later round.  CMDP_STAT_PSRL_SAMPLE_BYTES of a handle that was never dense is therefore
+     4 * (max(1, sum_b psi_b * nz_b) + sum_b S_b * A * psi_b) + 8 * B + 4 * sum_b capacity_b.
+   The S * A * psi * S < 2^32 refusal stays: the Philox sampler's counters are the dense route's. */
+int cmdp_psrlc_create_optimistic_route(cmdp_psrlc_t** out, cmdp_t* env, const int32_t* seeds, int64_t optimization_horizon,
+                                       const float* reward_prior, const float* transition_prior, const int32_t* psi,
+                                       const double* eta, const double* log4s, int sampler, int actor, int sample_solver);
 /* The last optimistic sample of every instance: T dense [sum S * A * psi * S], R [R] as N_NIG gave it, R_ext and the actor's
    Q [sum S * A * psi], z [sum psi] (reference sampler: -1 where no row was simple and none was drawn), the simple mask [R], and the solve's
    sweeps, scheme and status [B].  Each may be NULL.  CMDP_ERR_UNSUPPORTED on a plain handle, as cmdp_psrlc_last_sample is on
-   an optimistic one. */
+   an optimistic one.  For an instance whose last sample is compact, T is its expansion, produced instance by instance
+   through a staging buffer of one instance's size. */
 int cmdp_psrlc_last_sample_optimistic(cmdp_psrlc_t* a, float* T, float* R, float* R_ext, float* Q, int32_t* z, uint8_t* simple,
                                       int64_t* sweeps, int32_t* scheme, int32_t* status);
 /* The agent's N[s, a, s'] at the positions of cmdp_psrlc_layout (0 elsewhere, for ever); optimistic handles only. */
@@ -980,6 +1005,33 @@ int cmdp_psrlo_reference_draw(uint32_t* t_key, int32_t* t_pos, int32_t* t_has_ga
 int cmdp_vi_discounted_dense(int count, const int32_t* n_states, const int32_t* n_actions, const float* T, const float* R,
                              float gamma, double epsilon, int scheme, int64_t size_threshold, double density_threshold,
                              int64_t max_sweeps, float* Q, float* V, int64_t* sweeps, int32_t* scheme_used, int32_t* status);
+
+/* discounted_value_iteration(T_ext, R_ext) on `count` COMPACT optimistic samples in one launch (K19,
+   k_vi_discounted_optimistic, csrc/cmdp_psrlo_vi.h), T_ext [S, A * psi, S] never built.  Per problem b with S states, A real
+   actions and psi[b] samples, the arrays of all problems concatenated in problem order:
+     row_ptr [sum S * A + 1], col   the layout of the real rows (row_ptr[0] = 0; col problem-relative, ascending within a row);
+                                    nz_b positions in problem b
+     simple  [sum S * A]            1: a simple row, 0: a posterior row
+     z       [sum psi]              the bumped column of sample k; in [0, S) when the problem has a simple row, else unread
+     pmk     [sum psi * nz_b]       per problem [psi][nz_b]: the value of sample k at layout position e (simple rows' are read)
+     bump    [sum S * A * psi]      per problem [psi][S * A]: the value of sample k of a simple row at column z_k
+     pidx    [sum S * A]            posterior rows: their index among the problem's n1_b posterior rows in row order; simple
+                                    rows: unread
+     post    [sum psi * n1_b * S]   per problem [psi][n1_b][S] the dense posterior rows; NULL when no problem has one
+     R       [sum S * A]            the real rewards; R_ext[s, j] = R[s, j % A] is computed
+   Extended row j = a * psi + k of state s is, for a simple row (s, a), zero except pmk[k][e] at col[e] and bump[k][row] at z_k
+   (at z_k the bump stands, once), and post[k][pidx][:] for a posterior row.  A posterior row's sum is
+   cmdp_vi_discounted_dense's (same lanes, same order); a simple row's terms are taken in ascending column order and added one
+   at a time in float64 to +0, double(fl32(gamma * t)) * double(V[c]) under Gauss-Seidel and double(t) * double(V_old[c])
+   under Jacobi, and wrapped up as the dense definition does.  CMDP_SCHEME_AUTO counts the non-zero elements of the expansion
+   from the compact form.  The solver's arguments, refusals and outputs (Q [S][A * psi], V [S], sweeps, scheme_used, status)
+   are cmdp_vi_discounted_dense's; psi < 1 or A * psi > 2^20, a malformed layout, a pidx out of order, a z outside [0, S) and
+   values that are not finite are CMDP_ERR_INVALID, S * A * psi * S >= 2^32 CMDP_ERR_UNSUPPORTED. */
+int cmdp_vi_discounted_optimistic(int count, const int32_t* n_states, const int32_t* n_actions, const int32_t* psi,
+                                  const int64_t* row_ptr, const int32_t* col, const uint8_t* simple, const int32_t* z,
+                                  const float* pmk, const float* bump, const int32_t* pidx, const float* post, const float* R,
+                                  float gamma, double epsilon, int scheme, int64_t size_threshold, double density_threshold,
+                                  int64_t max_sweeps, float* Q, float* V, int64_t* sweeps, int32_t* scheme_used, int32_t* status);
 
 /* discounted_value_iteration(T_map, mu) on `count` MAP models in table form (K17, csrc/cmdp_map_dvi.h), one launch, no dense
    array.  The problem is cmdp_vi_episodic_map's: row_ptr [sum S * A + 1] over the rows of all problems (row_ptr[0] = 0), col
