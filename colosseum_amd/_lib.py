@@ -40,6 +40,7 @@ STAT_ACTIONS_KERNEL_MS = 27  # K16 before the last K1E walk under POLICY_RANDOM_
 STAT_PSRL_UNCONVERGED, STAT_PSRL_SWEEPS = 28, 29  # continuous PSRL (K13): solves at max_sweeps / sweeps of the last round
 STAT_PSRL_SAMPLE_BYTES, STAT_PSRL_SAMPLE_SOLVER = 30, 31  # optimistic PSRL (K18 / K19): bytes of the sample routes / last round's route
 PSRLC_OPT_SIZE_THRESHOLD, PSRLC_OPT_MAX_SWEEPS, PSRLC_OPT_POLICY_SOLVER, PSRLC_OPT_SAMPLE_SOLVER = 1, 2, 3, 4
+PSRLC_OPT_MIN_STEPS = 5
 PSRL_SAMPLER_REFERENCE, PSRL_SAMPLER_PHILOX = 0, 1
 PSRL_KEY_HI = 0x5053524C
 BOUND_CHERNOFF, BOUND_BERNSTEIN = 0, 1
@@ -98,6 +99,7 @@ EXPORTS = [
     "cmdp_psrlc_model", "cmdp_psrlc_last_sample", "cmdp_psrlc_set_option", "cmdp_psrlc_policy", "cmdp_psrlc_average_reward",
     "cmdp_vi_discounted_dense", "cmdp_vi_discounted_map", "cmdp_vi_discounted_optimistic", "cmdp_psrlc_create_optimistic_route",
     "cmdp_psrlc_create_optimistic", "cmdp_psrlc_last_sample_optimistic", "cmdp_psrlc_counts", "cmdp_psrlo_reference_draw",
+    "cmdp_psrlc_run_logged", "cmdp_psrlc_episode_gate",
 ]
 
 
@@ -290,6 +292,8 @@ def load():
         L.cmdp_psrlc_create_optimistic_route.argtypes = [C.POINTER(vp), vp, vp, i64, vp, vp, vp, vp, vp, i32, i32, i32]
         L.cmdp_vi_discounted_optimistic.argtypes = [i32] + [vp] * 12 + [f32, f64, i32, i64, f64, i64, vp, vp, vp, vp, vp]
         L.cmdp_psrlc_counts.argtypes = [vp, vp]
+        L.cmdp_psrlc_run_logged.argtypes = [vp, C.POINTER(CmdpLoopDesc), i64, vp, vp, vp, vp, vp]
+        L.cmdp_psrlc_episode_gate.argtypes = [vp, vp, vp]
         L.cmdp_psrlo_reference_draw.argtypes = [vp] * 12 + [i32, i32, i32, f64, i64, vp, vp, vp, vp, f32] + [vp] * 6
         L.cmdp_vi_discounted_dense.argtypes = [i32, vp, vp, vp, vp, f32, f64, i32, i64, f64, i64, vp, vp, vp, vp, vp]
         L.cmdp_vi_discounted_map.argtypes = [i32, vp, vp, vp, vp, vp, vp, vp, f32, f64, i32, i64, f64, i64, vp, vp, vp, vp, vp, vp, vp]

@@ -39,6 +39,10 @@ class _DeviceAgent:
         without returning to Python; the agents that park their instances take the rows strictly in order and must not have
         taken a step yet.  `desc` from `vector_tracker.loop_desc`.  Returns (steps [n_logs], values, kinds [n_logs, 17, B],
         last_training_step, is_training)."""
+        return self._run_logged_native(desc, n_logs)
+
+    def _run_logged_native(self, desc, n_logs: int):
+        """`<_PREFIX>_run_logged`: what `run_logged` returns, and what the batched loops call."""
         B = self.env.B
         steps = np.zeros(n_logs, np.int64)
         values = np.zeros((n_logs, len(L.LOG_COLUMNS), B), np.float64)
@@ -468,8 +472,10 @@ class BatchedPSRLContinuous(_ContinuousModelPolicy, _PosteriorSamplingAgent):
     model by one of two routes, `set_policy_solver("dense" | "tables")`.  The keyword names and defaults are the reference's; the four weights
     and `max_psi` only shape optimistic sampling and are accepted and unused, as on the reference's plain path.  Refused, each
     by name: optimistic sampling (`no_optimistic_sampling=False` unless every instance has S^2 * A > 6 000 000, where the
-    reference switches by itself), `truncate_reward_with_max=True`, `min_steps_before_new_episode != 0`, the exploration
-    actors, and what `BatchedPSRLEpisodic` refuses of the priors.  `run_logged` is not built."""
+    reference switches by itself), `truncate_reward_with_max=True`, `min_steps_before_new_episode != 0` as a constructor
+    keyword (`set_min_steps_before_new_episode(n)` on the new agent sets it), the exploration actors, and what
+    `BatchedPSRLEpisodic` refuses of the priors.  The logged run is `BatchedContinuousLoop`'s; the public `run_logged`
+    stays refused."""
 
     _PREFIX = "cmdp_psrlc"
     _STATS = _PosteriorSamplingAgent._STATS + (("unconverged", L.STAT_PSRL_UNCONVERGED), ("sweeps", L.STAT_PSRL_SWEEPS))
@@ -487,7 +493,8 @@ class BatchedPSRLContinuous(_ContinuousModelPolicy, _PosteriorSamplingAgent):
         if truncate_reward_with_max:
             raise NotImplementedError("truncate_reward_with_max=True is not built")
         if min_steps_before_new_episode != 0:
-            raise NotImplementedError("min_steps_before_new_episode != 0 is not built")
+            raise NotImplementedError("min_steps_before_new_episode != 0 at construction is not built: call "
+                                      "set_min_steps_before_new_episode(n) on the new agent")
         super().__init__(env, seeds, optimization_horizon, reward_prior_model=reward_prior_model,
                          transitions_prior_model=transitions_prior_model, rewards_prior_prms=rewards_prior_prms,
                          transitions_prior_prms=transitions_prior_prms, epsilon_greedy=epsilon_greedy,
@@ -500,7 +507,28 @@ class BatchedPSRLContinuous(_ContinuousModelPolicy, _PosteriorSamplingAgent):
         return self._run(n_steps, train, trace, stop_at_episode_end)
 
     def run_logged(self, desc, n_logs: int):
-        raise NotImplementedError("the logged loop of BatchedPSRLContinuous is not built")
+        raise NotImplementedError("BatchedPSRLContinuous.run_logged is not built as a public call: the logged run "
+                                  "(cmdp_psrlc_run_logged) is reached through BatchedContinuousLoop(env, agent).run")
+
+    def set_min_steps_before_new_episode(self, n: int):
+        """The reference's `min_steps_before_new_episode` (posterior_sampling.py:353-355), on a new agent only: with n > 0
+        `is_episode_end` evaluates its rule only at a step whose in-run time h (steps since the environment's last reset,
+        read before the step) is at least n past `last_change`, and every check that passes moves `last_change` to h.  A run
+        of T steps then takes at most T / n artificial episodes per instance.  0 (the default) is the ungated walk.  A
+        negative or non-integer n is a ValueError; once an instance has taken a step the library refuses (ERR_INVALID)."""
+        if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 0:   # before the handle is touched
+            raise ValueError(f"min_steps_before_new_episode {n!r}: an integer >= 0")
+        L.check(self._lib.cmdp_psrlc_set_option(self._h, L.PSRLC_OPT_MIN_STEPS, int(n)))
+
+    @property
+    def min_steps_before_new_episode(self) -> int:
+        return int(self.episode_gate()["min_steps"])
+
+    def episode_gate(self) -> dict:
+        """The gate's state: `min_steps` and `last_change` [B] int32 (the reference agent's `last_change`, 0 at creation)."""
+        m, lc = C.c_int64(), np.zeros(self.env.B, np.int32)
+        L.check(self._lib.cmdp_psrlc_episode_gate(self._h, C.byref(m), L.ptr(lc)))
+        return dict(min_steps=int(m.value), last_change=lc)
 
     def model(self):
         """Per instance the reference's tables: `transitions` dense [S, A, S] float32 (M_DIR.hyper_params), `rewards`
@@ -587,7 +615,8 @@ class BatchedPSRLContinuousOptimistic(BatchedPSRLContinuous):
     csrc/cmdp_psrlo_vi.h) keeps the sample as the sampler leaves it -- per sample the layout values and the value at z_k of the
     simple rows, dense rows only for the posterior rows of the draw -- and solves it there: T_ext is never built, a simple row
     costs its layout length per sweep, and the Q agrees with the dense route's within the two kernels' rounding bounds, not
-    bit for bit.  `last_sample()["T"]` is the same T_ext on both routes, bit for bit.  `run_logged` is not built."""
+    bit for bit.  `last_sample()["T"]` is the same T_ext on both routes, bit for bit.  The logged run is
+    `BatchedContinuousLoop`'s; the public `run_logged` stays refused."""
 
     _SAMPLE_SOLVERS = ("dense", "compact")
     _STATS = BatchedPSRLContinuous._STATS + (("sample_bytes", L.STAT_PSRL_SAMPLE_BYTES), ("sample_solver", L.STAT_PSRL_SAMPLE_SOLVER))
@@ -614,7 +643,8 @@ class BatchedPSRLContinuousOptimistic(BatchedPSRLContinuous):
         if truncate_reward_with_max:
             raise NotImplementedError("truncate_reward_with_max=True is not built")
         if min_steps_before_new_episode != 0:
-            raise NotImplementedError("min_steps_before_new_episode != 0 is not built")
+            raise NotImplementedError("min_steps_before_new_episode != 0 at construction is not built: call "
+                                      "set_min_steps_before_new_episode(n) on the new agent")
         sc = [optimistic_sampling_scalars(S, env.A, optimization_horizon, p, psi_weight, omega_weight, eta_weight, max_psi)
               for S in env.n_states]
         self.psi = np.array([s[0] for s in sc], np.int32)
@@ -654,7 +684,8 @@ class BatchedPSRLContinuousOptimistic(BatchedPSRLContinuous):
         return out
 
     def run_logged(self, desc, n_logs: int):
-        raise NotImplementedError("the logged loop of BatchedPSRLContinuousOptimistic is not built")
+        raise NotImplementedError("BatchedPSRLContinuousOptimistic.run_logged is not built as a public call: the logged run "
+                                  "(cmdp_psrlc_run_logged) is reached through BatchedContinuousLoop(env, agent).run")
 
     def model(self):
         """As `BatchedPSRLContinuous.model`, with the agent's `N` dense [S, A, S] int32 per instance and `psi`, `eta` [B]."""

@@ -24,7 +24,8 @@ from typing import Any, Dict, List, Optional, Sequence
 import numpy as np
 
 from . import _lib as L
-from .agents import BatchedPSRLEpisodic, BatchedQLearningContinuous, BatchedQLearningEpisodic, BatchedUCRL2Continuous
+from .agents import (BatchedPSRLContinuous, BatchedPSRLContinuousOptimistic, BatchedPSRLEpisodic, BatchedQLearningContinuous,
+                     BatchedQLearningEpisodic, BatchedUCRL2Continuous)
 from .batched import BatchedMDP
 from .experiment.batched_loop import BatchedContinuousLoop, BatchedEpisodicLoop
 from .mdp import make_model
@@ -40,7 +41,45 @@ DEFAULT_AGENT_CONFIGS = {
     "PSRLEpisodic": dict(reward_prior_model="N_NIG", transitions_prior_model="M_DIR",
                          rewards_prior_prms=[0.41854463543357456, 1, 1, 1], transitions_prior_prms=[0.32345772625210756]),
     "UCRL2Continuous": dict(bound_type_p="bernstein", alpha_p=0.9883750006754203, alpha_r=0.10294276593728004),
+    "PSRLContinuous": dict(reward_prior_model="N_NIG", rewards_prior_prms=[0.23589883401606418, 1, 1, 1],
+                           psi_weight=0.016737988780906453, omega_weight=0.1104641036501887, kappa_weight=2.694052439968039,
+                           eta_weight=1.3826913305347895e-07),
 }
+
+
+def samples_plainly(n_states: int, n_actions: int) -> bool:
+    """Where the reference's PSRLContinuous drops optimistic sampling by itself (posterior_sampling.py:272-275)."""
+    return int(n_states) ** 2 * int(n_actions) > 6_000_000
+
+
+def make_psrl_continuous(env, seeds, optimization_horizon, **kw):
+    """The reference's `PSRLContinuous` for a device batch, deciding as its constructor does: `BatchedPSRLContinuous` (plain
+    sampling) when `no_optimistic_sampling` is set or every instance has S^2 * A > 6 000 000,
+    `BatchedPSRLContinuousOptimistic` when no instance does, ValueError on a batch that mixes the two.  Three keys are not
+    constructor keywords and are applied to the new agent: `min_steps_before_new_episode` (default 0), `sample_solver`
+    (default "compact") and `policy_solver` (default "tables").  The defaults are the two table-form routes because neither
+    T_ext [S, A * psi, S] nor the dense MAP workspace [S, A, S] of a whole batch fits at benchmark sizes; their Q carry the
+    same rounding bounds against the reference as the dense routes'.  `DEFAULT_AGENT_CONFIGS["PSRLContinuous"]` holds the
+    reference's tuned values for it.  It is not an entry of `DEVICE_AGENTS` yet: the enumeration's tests pin "PSRLContinuous"
+    as a name `enumerate_instances` does not know, so `tools/run_benchmark.py --agents` does not offer it."""
+    kw = dict(kw)
+    min_steps = kw.pop("min_steps_before_new_episode", 0)
+    sample_solver = kw.pop("sample_solver", "compact")
+    policy_solver = kw.pop("policy_solver", "tables")
+    large = [samples_plainly(S, env.A) for S in env.n_states]
+    if kw.get("no_optimistic_sampling", False) or all(large):
+        kw["no_optimistic_sampling"] = True
+        agent = BatchedPSRLContinuous(env, seeds, optimization_horizon, **kw)
+    elif any(large):
+        raise ValueError("a device batch mixes instances with S^2 * A above and below 6 000 000: the reference samples the "
+                         "former plainly and the latter optimistically, which are two agent classes here")
+    else:
+        agent = BatchedPSRLContinuousOptimistic(env, seeds, optimization_horizon, sample_solver=sample_solver, **kw)
+    agent.set_policy_solver(policy_solver)
+    if min_steps:
+        agent.set_min_steps_before_new_episode(min_steps)
+    return agent
+
 
 # the agents built on the device: class name -> (episodic, agent class, loop class)
 DEVICE_AGENTS = {

@@ -5269,6 +5269,10 @@ struct cmdp_psrlc : cmdp_psrl {
   // keeps T_map in d_mapt [NZ] and d_mapc [R] of the base instead.
   DevBuf<float> d_Tmap, d_Rmap, d_mrs;
   bool optimistic = false;                  // the handle is a cmdp_psrlo (K18): its round, walk and destroy are dispatched on it
+  // CMDP_PSRLC_OPT_MIN_STEPS: the reference's min_steps_before_new_episode.  0 runs the walks compiled without the gate;
+  // d_lastchg [B] exists from the first value > 0
+  int32_t min_steps = 0;
+  DevBuf<int32_t> d_lastchg;
 };
 
 // ---- ... with optimistic sampling (K18, cmdp_psrlo.h): the extended sample, the extended Q of the actor, the agent's N ------
@@ -5768,12 +5772,25 @@ int cmdp_psrlc_run(cmdp_psrlc_t* a, int64_t n_steps, int stop_at_episode_end, co
   const int rc = park_run(
       a, n_steps, stop, train_mask, actions_trace, obs_trace, reward_trace, cumulative_reward, steps_taken,
       [&](const uint8_t* dmask, int8_t* act, int32_t* obs, double* rew) {
-        if (a->optimistic)
-          hipLaunchKernelGGL(k_psrlo_walk, dim3(grid_for(h->B, 256)), dim3(256), 0, h->stream, h->env(), a->args, a->cnt,
-                             static_cast<cmdp_psrlo*>(a)->po, n_steps, dmask, act, obs, rew, a->d_rsum.p);
-        else
-          hipLaunchKernelGGL(k_psrlc_walk, dim3(grid_for(h->B, 256)), dim3(256), 0, h->stream, h->env(), a->args, a->cnt, n_steps,
-                             dmask, act, obs, rew, a->d_rsum.p);
+        // host-only picker of the walk's form: min_steps = 0 runs the kernels without the gate, which touch no last_change
+        const bool gate = a->min_steps > 0;
+        const PcGate gt{a->min_steps, a->d_lastchg.p};
+        const dim3 grid(grid_for(h->B, 256)), block(256);
+        if (a->optimistic) {
+          const PoArgs& po = static_cast<cmdp_psrlo*>(a)->po;
+          if (gate)
+            hipLaunchKernelGGL(k_psrlo_walk<true>, grid, block, 0, h->stream, h->env(), a->args, a->cnt, po, gt, n_steps, dmask, act,
+                               obs, rew, a->d_rsum.p);
+          else
+            hipLaunchKernelGGL(k_psrlo_walk<false>, grid, block, 0, h->stream, h->env(), a->args, a->cnt, po, gt, n_steps, dmask, act,
+                               obs, rew, a->d_rsum.p);
+        } else if (gate) {
+          hipLaunchKernelGGL(k_psrlc_walk<true>, grid, block, 0, h->stream, h->env(), a->args, a->cnt, gt, n_steps, dmask, act, obs,
+                             rew, a->d_rsum.p);
+        } else {
+          hipLaunchKernelGGL(k_psrlc_walk<false>, grid, block, 0, h->stream, h->env(), a->args, a->cnt, gt, n_steps, dmask, act, obs,
+                             rew, a->d_rsum.p);
+        }
       },
       [&]() -> int { psrl_times(a); return CMDP_OK; }, [&](int count) { return psrlc_round(a, count, stop, n_steps); });
   psrl_times(a);   // after the call's last synchronisation
@@ -5822,7 +5839,36 @@ int cmdp_psrlc_set_option(cmdp_psrlc_t* a, int option, int64_t value) {
     o->sample_solver = (int)value;
     return CMDP_OK;
   }
+  if (option == CMDP_PSRLC_OPT_MIN_STEPS) {
+    if (value < 0 || value > 0x7fffffffLL)
+      return fail(CMDP_ERR_INVALID, "min_steps_before_new_episode %lld: at least 0 and at most 2^31 - 1", (long long)value);
+    cmdp_t* h = a->env;
+    for (int b = 0; b < h->B; ++b)   // the reference fixes it at construction
+      if (a->steps_total[(size_t)b] != 0)
+        return fail(CMDP_ERR_INVALID, "instance %d has already taken %lld steps: min_steps_before_new_episode is set on a new "
+                    "agent", b, (long long)a->steps_total[(size_t)b]);
+    if (value > 0 && !a->d_lastchg.p) {
+      hipStream_t st = h->stream;
+      AGENT_ZERO(d_lastchg, h->B);
+    }
+    a->min_steps = (int32_t)value;
+    return CMDP_OK;
+  }
   return fail(CMDP_ERR_INVALID, "unknown option %d", option);
+}
+
+int cmdp_psrlc_episode_gate(cmdp_psrlc_t* a, int64_t* min_steps, int32_t* last_change) {
+  if (int rc = psrlc_bind(a)) return rc;
+  cmdp_t* h = a->env;
+  if (min_steps) *min_steps = a->min_steps;
+  if (last_change) {
+    std::memset(last_change, 0, sizeof(int32_t) * (size_t)h->B);   // no value > 0 yet: nothing has moved it
+    if (a->d_lastchg.p) {
+      AGENT_FETCH(last_change, d_lastchg, h->B);
+      HIP_TRY(hipStreamSynchronize(h->stream));
+    }
+  }
+  return CMDP_OK;
 }
 
 int cmdp_psrlc_model(cmdp_psrlc_t* a, float* reward_hp, float* transition_hp, float* transition_prior, int32_t* n_sa,
@@ -5970,11 +6016,10 @@ int cmdp_psrlc_last_sample(cmdp_psrlc_t* a, float* T, float* R, float* Q, int64_
 // (CMDP_PSRLC_OPT_POLICY_SOLVER = 1): K17 straight on the posterior tables, no dense workspace.  Reads nothing but the model
 // and writes nothing of the agent's but the stage and the MAP model's buffers: the last sample and the actor's Q stay what
 // they were.  CMDP_ERR_MAX_ITER when an instance did not converge.
-static int psrlc_policy_solve(cmdp_psrlc_t* a, const uint8_t* mask) {
-  cmdp_t* h = a->env;
-  hipStream_t st = h->stream;
-  const int B = h->B;
-  const int64_t R = h->n_rows;
+// The workspace of the handle's current policy route, at the route's first request.  CMDP_ERR_OVERFLOW when the dense MAP
+// models do not fit.
+static int psrlc_policy_workspace(cmdp_psrlc_t* a) {
+  const int64_t R = a->env->n_rows;
   const bool tables = a->policy_solver == 1;
   if (!tables && !a->d_mrs.p) {
     if (a->d_Tmap.alloc((size_t)a->t_total) != hipSuccess) {
@@ -5987,6 +6032,15 @@ static int psrlc_policy_solve(cmdp_psrlc_t* a, const uint8_t* mask) {
   if (tables && !a->d_mapc.p) {
     HIP_TRY(a->d_mapt.alloc((size_t)a->nz)); HIP_TRY(a->d_mapc.alloc((size_t)R));
   }
+  return CMDP_OK;
+}
+
+static int psrlc_policy_solve(cmdp_psrlc_t* a, const uint8_t* mask) {
+  cmdp_t* h = a->env;
+  hipStream_t st = h->stream;
+  const int B = h->B;
+  const bool tables = a->policy_solver == 1;
+  if (int rc = psrlc_policy_workspace(a)) return rc;
   if (int rc = policy_select(a, 1, true, mask)) return rc;
   PolicyStage& p = a->pol;
   const int rc = policy_stage(a, 1, [&](const int32_t* list, int count) -> int {
@@ -6540,6 +6594,34 @@ struct PsrlLogged {
   }
 };
 
+// The continuous PSRL agents, plain and optimistic (K13, K18): the rows' evaluation is what cmdp_psrlc_average_reward(a, need, .)
+// enqueues, by the handle's current policy route
+struct PsrlcLogged {
+  static constexpr bool ahead = false;
+  cmdp_psrlc_t* a;
+  const cmdp_loop_desc* d;
+  int pre(const cmdp_tracker::LoggedSwitches&) {
+    if (int rc = park_logged_check(a, d->n_steps, 1LL << 24, "a transition count of the model (float32, as the reference's "
+                                   "hyper-parameters) would stop counting at 2^24: instance %d has taken %lld steps, %lld asked for"))
+      return rc;
+    // everything the rows allocate, now: the route's workspace (the dense MAP models may not fit) and the policy stage
+    if (a->policy_solver == 1 && a->env->max_S > MAPVI_MAX_STATES)
+      return fail(CMDP_ERR_UNSUPPORTED, "%d states: value iteration on a MAP model (K17) keeps V and V_old in LDS for at most %d",
+                  a->env->max_S, MAPVI_MAX_STATES);
+    if (int rc = psrlc_policy_workspace(a)) return rc;
+    return policy_select(a, 1, true, nullptr);
+  }
+  int run(int64_t n, const uint8_t* mask, double* cum) { return cmdp_psrlc_run(a, n, 0, mask, nullptr, nullptr, nullptr, cum, nullptr); }
+  int evaluate(RowBuffers& buf, hipStream_t*) {
+    cmdp_t* h = a->env;
+    bool any = false;
+    for (int b = 0; b < h->B; ++b) any = any || buf.need.p[b];
+    if (!any) return CMDP_OK;
+    if (int rc = psrlc_policy_solve(a, buf.need.p)) return rc;
+    return chain_launch(h, a->pol.d_pi.p, nullptr, h->d_cur.p, buf.need.p, buf.avg.p, buf.akind.p, nullptr, true, false);
+  }
+};
+
 }  // namespace
 
 extern "C" {
@@ -6560,6 +6642,11 @@ int cmdp_ucrl2_run_logged(cmdp_ucrl2_t* a, const cmdp_loop_desc* d, int64_t n_lo
 int cmdp_psrl_run_logged(cmdp_psrl_t* a, const cmdp_loop_desc* d, int64_t n_logs, int64_t* steps, double* values, uint8_t* kinds,
                          int64_t* last_training_step, uint8_t* is_training) {
   return run_logged(a, true, PsrlLogged{a, d}, d, n_logs, steps, values, kinds, last_training_step, is_training);
+}
+
+int cmdp_psrlc_run_logged(cmdp_psrlc_t* a, const cmdp_loop_desc* d, int64_t n_logs, int64_t* steps, double* values, uint8_t* kinds,
+                          int64_t* last_training_step, uint8_t* is_training) {
+  return run_logged(a, false, PsrlcLogged{a, d}, d, n_logs, steps, values, kinds, last_training_step, is_training);
 }
 
 }  // extern "C"

@@ -67,7 +67,18 @@ struct PcCounters {
   int32_t* stamp;   // [R] starts at 0; `episode` is >= 1 once the agent exists (the solve on the prior)
 };
 
-__global__ void __launch_bounds__(256) k_psrlc_walk(EnvTables t, PsArgs p, PcCounters c, int64_t n_steps,
+// min_steps_before_new_episode (posterior_sampling.py:353-355), for the walks compiled with GATE: is_episode_end evaluates its
+// rule only when the in-run time h of the step (mdp.h read BEFORE the step: t.hstep at the top of the loop) is at least
+// `min_steps` past last_change, and every check that passes moves last_change to h, whether or not the episode ends.  A
+// frozen instance never calls is_episode_end; episode_end_update touches neither.  GATE = false is the walk of
+// min_steps = 0: it reads and writes no last_change.
+struct PcGate {
+  int32_t min_steps;
+  int32_t* last_change;   // [B] starts at 0
+};
+
+template <bool GATE>
+__global__ void __launch_bounds__(256) k_psrlc_walk(EnvTables t, PsArgs p, PcCounters c, PcGate gt, int64_t n_steps,
                                                     const uint8_t* __restrict__ train_mask, int8_t* __restrict__ act_trace,
                                                     int32_t* __restrict__ obs_trace, double* __restrict__ rew_trace,
                                                     double* __restrict__ cum_reward) {
@@ -86,10 +97,13 @@ __global__ void __launch_bounds__(256) k_psrlc_walk(EnvTables t, PsArgs p, PcCou
   int32_t* mtp = p.mt_pos + b;
   const int32_t ep = (int32_t)p.episode[b];
   const bool train = train_mask ? train_mask[b] != 0 : true;   // a frozen instance acts on the Q it holds and never parks
+  int32_t lc = 0;
+  if (GATE && train) lc = gt.last_change[b];
   double sum = cum_reward[b];
   bool parked = false;
   while (left > 0) {
     const int64_t step = n_steps - left;
+    const int32_t h0 = h;
     int action = greedy_action_row(Q + (int64_t)cur * A, A, mt, mtp);
     const int32_t idx = cur * A + action;
     const unsigned long long n0 = nt;
@@ -114,7 +128,12 @@ __global__ void __launch_bounds__(256) k_psrlc_walk(EnvTables t, PsArgs p, PcCou
       c.n_sa[r] = n_tau;
       c.nu[r] = nu_k;
       c.stamp[r] = ep;
-      if (n_tau >= 2 * (n_tau - nu_k)) {   // is_episode_end: the round samples, solves and installs Q
+      bool checked = true;
+      if (GATE) {
+        checked = h0 - lc >= gt.min_steps;   // both >= 0: the difference cannot wrap
+        if (checked) lc = h0;
+      }
+      if (checked && n_tau >= 2 * (n_tau - nu_k)) {   // is_episode_end: the round samples, solves and installs Q
         parked = true;
         break;
       }
@@ -125,6 +144,7 @@ __global__ void __launch_bounds__(256) k_psrlc_walk(EnvTables t, PsArgs p, PcCou
   t.n_trans[b] = nt;
   cum_reward[b] = sum;
   p.call.left[b] = left;
+  if (GATE && train) gt.last_change[b] = lc;
   if (parked) p.call.park_list[atomicAdd(p.call.park_count, 1)] = b;
 }
 

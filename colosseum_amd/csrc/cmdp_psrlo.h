@@ -102,7 +102,8 @@ __global__ void __launch_bounds__(64) k_psrlo_count(PcCounters c, const double* 
   if (lane == 0) n1[b] = run;
 }
 
-__global__ void __launch_bounds__(256) k_psrlo_walk(EnvTables t, PsArgs p, PcCounters c, PoArgs o, int64_t n_steps,
+template <bool GATE>   // cmdp_psrlc.h: PcGate
+__global__ void __launch_bounds__(256) k_psrlo_walk(EnvTables t, PsArgs p, PcCounters c, PoArgs o, PcGate gt, int64_t n_steps,
                                                     const uint8_t* __restrict__ train_mask, int8_t* __restrict__ act_trace,
                                                     int32_t* __restrict__ obs_trace, double* __restrict__ rew_trace,
                                                     double* __restrict__ cum_reward) {
@@ -121,10 +122,13 @@ __global__ void __launch_bounds__(256) k_psrlo_walk(EnvTables t, PsArgs p, PcCou
   int32_t* mtp = p.mt_pos + b;
   const int32_t ep = (int32_t)p.episode[b];
   const bool train = train_mask ? train_mask[b] != 0 : true;
+  int32_t lc = 0;
+  if (GATE && train) lc = gt.last_change[b];
   double sum = cum_reward[b];
   bool parked = false;
   while (left > 0) {
     const int64_t step = n_steps - left;
+    const int32_t h0 = h;
     int action = greedy_action_row(Q + (int64_t)cur * AX, AX, mt, mtp) / psi;   // extended_action_to_real
     const int32_t idx = cur * A + action;
     const unsigned long long n0 = nt;
@@ -151,7 +155,12 @@ __global__ void __launch_bounds__(256) k_psrlo_walk(EnvTables t, PsArgs p, PcCou
       c.n_sa[r] = n_tau;
       c.nu[r] = nu_k;
       c.stamp[r] = ep;
-      if (n_tau >= 2 * (n_tau - nu_k)) {
+      bool checked = true;
+      if (GATE) {
+        checked = h0 - lc >= gt.min_steps;
+        if (checked) lc = h0;
+      }
+      if (checked && n_tau >= 2 * (n_tau - nu_k)) {
         parked = true;
         break;
       }
@@ -162,6 +171,7 @@ __global__ void __launch_bounds__(256) k_psrlo_walk(EnvTables t, PsArgs p, PcCou
   t.n_trans[b] = nt;
   cum_reward[b] = sum;
   p.call.left[b] = left;
+  if (GATE && train) gt.last_change[b] = lc;
   if (parked) p.call.park_list[atomicAdd(p.call.park_count, 1)] = b;
 }
 

@@ -18,7 +18,8 @@ from typing import Dict, List, Union
 
 import numpy as np
 
-from ..agents import BatchedPSRLEpisodic, BatchedQLearningContinuous, BatchedQLearningEpisodic, BatchedUCRL2Continuous
+from ..agents import (BatchedPSRLContinuous, BatchedPSRLEpisodic, BatchedQLearningContinuous, BatchedQLearningEpisodic,
+                      BatchedUCRL2Continuous)
 from .. import _lib as L
 from ..batched import BatchedMDP
 from .vector_tracker import MP, ContinuousVectorTracker, EpisodicVectorTracker
@@ -33,8 +34,8 @@ class _BatchedLoop:
     def _log(self, t: int, cum: np.ndarray, n_since: int, T: int, in_loop: bool):
         raise NotImplementedError
 
-    # the whole run in one library call (`agent.run_logged`: cmdp_qlearning_run_logged, cmdp_psrl_run_logged,
-    # cmdp_ucrl2_run_logged); False: the Python-driven loop below
+    # the whole run in one library call (`agent._run_logged_native`: cmdp_qlearning_run_logged, cmdp_psrl_run_logged,
+    # cmdp_ucrl2_run_logged, cmdp_psrlc_run_logged); False: the Python-driven loop below
     native = True
 
     def _desc(self, T: int, log_every: int, max_time: float):
@@ -56,7 +57,7 @@ class _BatchedLoop:
 
         self.vt.reset()
         desc, keep = self._desc(T, log_every, max_time)
-        steps, values, kinds, last, training = self.agent.run_logged(desc, n_log_rows(T, log_every))
+        steps, values, kinds, last, training = self.agent._run_logged_native(desc, n_log_rows(T, log_every))
         self.vt.log = native_log(self.env.B, steps, values, kinds)
         self.vt.is_training = training
         self.last_training_step = last
@@ -133,12 +134,14 @@ class BatchedEpisodicLoop(_BatchedLoop):
 
 
 class BatchedContinuousLoop(_BatchedLoop):
-    """`MDPLoop.run` for a batch of continuous (environment, agent) pairs, the agent a `BatchedQLearningContinuous` or a
-    `BatchedUCRL2Continuous`: interaction on the device, regrets from the average rewards of the agents' greedy policies
-    (`average_reward(need)`: kernel K9; above its LDS budget `policy()` for all B instances, host class bookkeeping and the
-    GTH kernel)."""
+    """`MDPLoop.run` for a batch of continuous (environment, agent) pairs, the agent a `BatchedQLearningContinuous`, a
+    `BatchedUCRL2Continuous`, a `BatchedPSRLContinuous` or a `BatchedPSRLContinuousOptimistic`: interaction on the device,
+    regrets from the average rewards of the agents' greedy policies (`average_reward(need)`: kernel K9; above its LDS budget
+    `policy()` for all B instances, host class bookkeeping and the GTH kernel).  The loop needs `run(n, train=mask)`,
+    `average_reward(need)` and, for the one-call route, `_run_logged_native`."""
 
-    def __init__(self, env: BatchedMDP, agent: Union[BatchedQLearningContinuous, BatchedUCRL2Continuous],
+    def __init__(self, env: BatchedMDP,
+                 agent: Union[BatchedQLearningContinuous, BatchedUCRL2Continuous, BatchedPSRLContinuous],
                  n_log_intervals_to_check_for_agent_optimality: int = 10):
         from ..dynamic_programming import get_policy_from_q_values
         from ..markov_chain import AverageRewardCache, get_average_reward_batch

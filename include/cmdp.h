@@ -943,9 +943,24 @@ int cmdp_psrlc_average_reward(cmdp_psrlc_t* a, const uint8_t* mask, double* avg,
    K19 (cmdp_vi_discounted_optimistic's kernel) on the compact sample, T_ext never built.  Switching a handle created compact to
    dense allocates the dense arrays at that moment; when they do not fit it returns CMDP_ERR_OVERFLOW and the handle stays
    compact.  An instance's last sample stays in the form of the round that drew it. */
+/* CMDP_PSRLC_OPT_MIN_STEPS (plain and optimistic handles) is the reference's min_steps_before_new_episode
+   (posterior_sampling.py:353-355): is_episode_end evaluates its rule only at a step whose in-run time h (steps since the
+   environment's last reset, read before the step) is at least that many past last_change, and every check that passes moves
+   last_change [B] (0 at creation) to h, whether or not the episode ends; a frozen instance never checks, and no
+   episode_end_update touches last_change.  0 (the default) runs the walk kernels compiled without the gate.  A value outside
+   [0, 2^31 - 1] is CMDP_ERR_INVALID, and so is any call once an instance has taken a step: the reference fixes the value at
+   construction. */
 enum { CMDP_PSRLC_OPT_SIZE_THRESHOLD = 1, CMDP_PSRLC_OPT_MAX_SWEEPS = 2, CMDP_PSRLC_OPT_POLICY_SOLVER = 3,
-       CMDP_PSRLC_OPT_SAMPLE_SOLVER = 4 };
+       CMDP_PSRLC_OPT_SAMPLE_SOLVER = 4, CMDP_PSRLC_OPT_MIN_STEPS = 5 };
 int cmdp_psrlc_set_option(cmdp_psrlc_t* a, int option, int64_t value);
+/* The gate's state: the option's value and last_change [B]; either may be null. */
+int cmdp_psrlc_episode_gate(cmdp_psrlc_t* a, int64_t* min_steps, int32_t* last_change);
+/* MDPLoop.run as one call for the continuous PSRL agents, plain and optimistic: as cmdp_ucrl2_run_logged.  The interaction is
+   cmdp_psrlc_run's, a row's evaluation what cmdp_psrlc_average_reward(a, need, .) enqueues, by the handle's current policy
+   route.  The same refusals, with the float32 limit of 2^24 steps of cmdp_psrlc_run; the route's workspace is allocated
+   before anything is reset or stepped (the dense route's may be CMDP_ERR_OVERFLOW). */
+int cmdp_psrlc_run_logged(cmdp_psrlc_t* a, const cmdp_loop_desc* desc, int64_t n_logs, int64_t* steps, double* values,
+                          uint8_t* kinds, int64_t* last_training_step, uint8_t* is_training);
 /* The same agent with the reference's OPTIMISTIC sampling (no_optimistic_sampling=False, its default; K18,
    csrc/cmdp_psrlo.h): psi [B] extended actions per real action, eta [B] the visit count below which a row is sampled simply,
    log4s [B] = log(4 S) as the caller's NumPy gives it.  The handle serves every cmdp_psrlc_* entry: the walk acts greedily on

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Runs a Colosseum-style benchmark folder (mdp_configs/*.gin, experiment_config.yml) for the four supported MDP
-families with tabular Q-learning agents on the GPU(s) and writes the reference's CSV log files.
+families with the tabular agents of colosseum_amd.benchmark.DEVICE_AGENTS on the GPU(s) (--agents; default: Q-learning) and
+writes the reference's CSV log files.
 
     python tools/run_benchmark.py --folder <benchmark folder> --out results [--steps N --seeds K --log-every L]
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 tools/run_benchmark.py ...
