@@ -5329,6 +5329,19 @@ int ddv_launch(const DdvArgs& g, int count, int max_S, hipStream_t st) {
   return CMDP_OK;
 }
 
+// PSRLContinuous calls discounted_value_iteration(T, R) with nothing else (posterior_sampling.py:177, :374): the defaults of
+// colosseum/dynamic_programming/infinite_horizon.py:17-18
+constexpr float PSRLC_GAMMA = 0.99f;
+constexpr double PSRLC_EPSILON = 1e-3;
+
+// K13's solver as the agent calls it, for a round's sample and for the dense MAP model alike: the handle's plain layout, the
+// reference's gamma and epsilon, the scheme by the rule at the handle's thresholds
+DdvArgs psrlc_ddv_args(const cmdp_psrlc* a, const int32_t* list, const float* T, const float* R, float* Q, float* V, int64_t* sweeps,
+                       int32_t* scheme, int32_t* status) {
+  return DdvArgs{list, a->d_S.p, a->d_A.p, a->d_toff.p, a->d_roff.p, a->env->d_state_off.p, T, R, PSRLC_GAMMA, PSRLC_EPSILON,
+                 CMDP_SCHEME_AUTO, a->size_threshold, a->density_threshold, a->max_sweeps, Q, V, sweeps, scheme, status};
+}
+
 // Host-only picker of k_vi_discounted_map's form and launch geometry (one wavefront per instance, `count` workgroups).  An
 // instance may keep its tables in LDS next to its value arrays when they take at most MAPDVI_STAGE_MAX_BYTES (two such
 // workgroups share a CU's 160 KB); `staged` is the launch's dynamic LDS in that form, `plain` with every instance's tables
@@ -5566,9 +5579,7 @@ int psrlc_round(cmdp_psrlc_t* a, int count, int stop, int64_t n_steps) {
   const int32_t* list = a->d_park.p + 2;
   cmdp_psrlo* o = a->optimistic ? static_cast<cmdp_psrlo*>(a) : nullptr;
   if (int rc = o ? psrlo_sample(o, count) : psrl_sample(a, count)) return rc;
-  DdvArgs g{list, a->d_S.p, a->d_A.p, a->d_toff.p, a->d_roff.p, h->d_state_off.p, a->d_T.p, a->d_Rs.p, 0.99f, 1e-3,
-            CMDP_SCHEME_AUTO, a->size_threshold, a->density_threshold, a->max_sweeps, a->d_Q.p, a->d_V.p, a->d_sweeps.p,
-            a->d_scheme.p, a->d_status.p};
+  DdvArgs g = psrlc_ddv_args(a, list, a->d_T.p, a->d_Rs.p, a->d_Q.p, a->d_V.p, a->d_sweeps.p, a->d_scheme.p, a->d_status.p);
   if (o) {   // the same solver on the extended arrays: A * psi actions per instance, Q straight into the actor's extended table
     g.A = o->d_Ax.p; g.t_off = o->d_txoff.p; g.r_off = o->d_qoff.p;
     g.T = o->d_Tx.p; g.R = o->d_Rx.p; g.Q = o->d_Qx.p;
@@ -5577,8 +5588,8 @@ int psrlc_round(cmdp_psrlc_t* a, int count, int stop, int64_t n_steps) {
   if (o && o->sample_solver == 1) {   // K19 on the compact sample: the same outputs, T_ext never built
     PovArgs v{list, a->d_S.p, a->d_A.p, o->d_psi.p, a->d_roff.p, h->d_state_off.p, o->d_qoff.p, o->d_koff.p, o->d_pmoff.p,
               a->d_row_ptr.p, a->d_col.p, o->d_simple.p, o->d_pidx.p, o->d_n1.p, o->d_z.p, o->d_pmk.p, o->d_bump.p, o->d_pkptr.p,
-              a->d_Rs.p, 0.99f, 1e-3, CMDP_SCHEME_AUTO, a->size_threshold, a->density_threshold, a->max_sweeps, o->d_Qx.p,
-              a->d_V.p, a->d_sweeps.p, a->d_scheme.p, a->d_status.p, 0};
+              a->d_Rs.p, PSRLC_GAMMA, PSRLC_EPSILON, CMDP_SCHEME_AUTO, a->size_threshold, a->density_threshold, a->max_sweeps,
+              o->d_Qx.p, a->d_V.p, a->d_sweeps.p, a->d_scheme.p, a->d_status.p, 0};
     if (int rc = pov_launch(v, count, h->max_S, h->max_S * h->A, st)) return rc;
   } else if (int rc = ddv_launch(g, count, h->max_S, st)) {
     return rc;
@@ -5619,6 +5630,28 @@ int psrlc_build(cmdp_psrlc_t* a, const int32_t* seeds, const float* reward_prior
   return CMDP_OK;
 }
 
+// What both creates refuse before they build anything, in this order: K12's arguments, the optimistic create's own arrays
+// (`optimistic_args` false: one of psi, eta, log4s is null; the plain create passes true), then the environment handle
+int psrlc_create_check(cmdp_t* env, const int32_t* seeds, int64_t optimization_horizon, const float* reward_prior,
+                       const float* transition_prior, int sampler, int actor, bool optimistic_args) {
+  if (int rc = psrl_create_check(env, seeds, optimization_horizon, reward_prior, transition_prior, sampler, actor)) return rc;
+  if (!optimistic_args) return fail(CMDP_ERR_INVALID, "null argument (psi, eta or log4s)");
+  return park_check_env(env, false, "PSRLContinuous is the continuous setting's agent: the environment handle is episodic "
+                        "(horizon %d; cmdp_psrl_create builds PSRLEpisodic)", "PSRLContinuous", "the dense solver (K13)",
+                        PSRL_MAX_STATES);
+}
+
+// An episode_end_update of every instance, outside a run: before_start_interacting's on the prior
+// (infinite_horizon/posterior_sampling.py:379-383) and cmdp_psrlc_episode_end_update's.  Park all, one round, and the round's
+// kernel times once the stream has drained.
+int psrlc_update_all(cmdp_psrlc_t* a) {
+  if (int rc = park_all(a)) return rc;
+  if (int rc = psrlc_round(a, a->env->B, 0, 0)) return rc;
+  HIP_TRY(hipStreamSynchronize(a->env->stream));
+  psrl_times(a);
+  return CMDP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -5627,20 +5660,13 @@ int cmdp_psrlc_create(cmdp_psrlc_t** out, cmdp_t* env, const int32_t* seeds, int
                       const float* reward_prior, const float* transition_prior, int sampler, int actor) {
   if (!out) return fail(CMDP_ERR_INVALID, "null output");
   *out = nullptr;
-  if (int rc = psrl_create_check(env, seeds, optimization_horizon, reward_prior, transition_prior, sampler, actor)) return rc;
-  if (int rc = park_check_env(env, false, "PSRLContinuous is the continuous setting's agent: the environment handle is episodic "
-                              "(horizon %d; cmdp_psrl_create builds PSRLEpisodic)", "PSRLContinuous", "the dense solver (K13)",
-                              PSRL_MAX_STATES)) return rc;
+  if (int rc = psrlc_create_check(env, seeds, optimization_horizon, reward_prior, transition_prior, sampler, actor, true)) return rc;
   cmdp_psrlc_t* a = new cmdp_psrlc;
   std::unique_ptr<cmdp_psrlc> guard(a);
   a->env = env;
   a->sampler = sampler;
   if (int rc = psrlc_build(a, seeds, reward_prior, transition_prior)) return rc;
-  // before_start_interacting (infinite_horizon/posterior_sampling.py:379-383): one episode_end_update on the prior
-  if (int rc = park_all(a)) return rc;
-  if (int rc = psrlc_round(a, env->B, 0, 0)) return rc;
-  HIP_TRY(hipStreamSynchronize(env->stream));
-  psrl_times(a);
+  if (int rc = psrlc_update_all(a)) return rc;   // before_start_interacting: one episode_end_update on the prior
   return agent_attach(guard, out);
 }
 
@@ -5651,11 +5677,8 @@ int cmdp_psrlc_create_optimistic_route(cmdp_psrlc_t** out, cmdp_t* env, const in
   *out = nullptr;
   if (sample_solver != 0 && sample_solver != 1)
     return fail(CMDP_ERR_INVALID, "sample solver %d: 0 (the dense route) or 1 (the compact route, K19)", sample_solver);
-  if (int rc = psrl_create_check(env, seeds, optimization_horizon, reward_prior, transition_prior, sampler, actor)) return rc;
-  if (!psi || !eta || !log4s) return fail(CMDP_ERR_INVALID, "null argument (psi, eta or log4s)");
-  if (int rc = park_check_env(env, false, "PSRLContinuous is the continuous setting's agent: the environment handle is episodic "
-                              "(horizon %d; cmdp_psrl_create builds PSRLEpisodic)", "PSRLContinuous", "the dense solver (K13)",
-                              PSRL_MAX_STATES)) return rc;
+  if (int rc = psrlc_create_check(env, seeds, optimization_horizon, reward_prior, transition_prior, sampler, actor,
+                                  psi && eta && log4s)) return rc;
   const int B = env->B, A = env->A;
   std::unique_ptr<cmdp_psrlo> guard(new cmdp_psrlo);
   cmdp_psrlo* a = guard.get();
@@ -5739,11 +5762,7 @@ int cmdp_psrlc_create_optimistic_route(cmdp_psrlc_t** out, cmdp_t* env, const in
       psrlo_host::skip_randn(a->as[b], (b + 1 < B ? a->h_qoff[b + 1] : a->q_total) - a->h_qoff[b]);
     }
   }
-  // ... then one episode_end_update on the prior
-  if (int rc = park_all(a)) return rc;
-  if (int rc = psrlc_round(a, B, 0, 0)) return rc;
-  HIP_TRY(hipStreamSynchronize(st));
-  psrl_times(a);
+  if (int rc = psrlc_update_all(a)) return rc;   // ... then one episode_end_update on the prior
   cmdp_psrlo* attached = nullptr;
   const int rc = agent_attach(guard, &attached);
   *out = attached;
@@ -5775,22 +5794,13 @@ int cmdp_psrlc_run(cmdp_psrlc_t* a, int64_t n_steps, int stop_at_episode_end, co
         // host-only picker of the walk's form: min_steps = 0 runs the kernels without the gate, which touch no last_change
         const bool gate = a->min_steps > 0;
         const PcGate gt{a->min_steps, a->d_lastchg.p};
-        const dim3 grid(grid_for(h->B, 256)), block(256);
-        if (a->optimistic) {
-          const PoArgs& po = static_cast<cmdp_psrlo*>(a)->po;
-          if (gate)
-            hipLaunchKernelGGL(k_psrlo_walk<true>, grid, block, 0, h->stream, h->env(), a->args, a->cnt, po, gt, n_steps, dmask, act,
-                               obs, rew, a->d_rsum.p);
-          else
-            hipLaunchKernelGGL(k_psrlo_walk<false>, grid, block, 0, h->stream, h->env(), a->args, a->cnt, po, gt, n_steps, dmask, act,
-                               obs, rew, a->d_rsum.p);
-        } else if (gate) {
-          hipLaunchKernelGGL(k_psrlc_walk<true>, grid, block, 0, h->stream, h->env(), a->args, a->cnt, gt, n_steps, dmask, act, obs,
-                             rew, a->d_rsum.p);
-        } else {
-          hipLaunchKernelGGL(k_psrlc_walk<false>, grid, block, 0, h->stream, h->env(), a->args, a->cnt, gt, n_steps, dmask, act, obs,
-                             rew, a->d_rsum.p);
-        }
+        const PoArgs ow = a->optimistic ? static_cast<cmdp_psrlo*>(a)->po : PoArgs{};   // the plain walk reads none of it
+        auto launch = [&](auto walk) {
+          hipLaunchKernelGGL(walk, dim3(grid_for(h->B, 256)), dim3(256), 0, h->stream, h->env(), a->args, a->cnt, ow, gt, n_steps,
+                             dmask, act, obs, rew, a->d_rsum.p);
+        };
+        if (a->optimistic) gate ? launch(k_psrlc_walk<true, true>) : launch(k_psrlc_walk<false, true>);
+        else gate ? launch(k_psrlc_walk<true, false>) : launch(k_psrlc_walk<false, false>);
       },
       [&]() -> int { psrl_times(a); return CMDP_OK; }, [&](int count) { return psrlc_round(a, count, stop, n_steps); });
   psrl_times(a);   // after the call's last synchronisation
@@ -5799,12 +5809,7 @@ int cmdp_psrlc_run(cmdp_psrlc_t* a, int64_t n_steps, int stop_at_episode_end, co
 
 int cmdp_psrlc_episode_end_update(cmdp_psrlc_t* a) {
   if (int rc = psrlc_bind(a)) return rc;
-  cmdp_t* h = a->env;
-  if (int rc = park_all(a)) return rc;
-  if (int rc = psrlc_round(a, h->B, 0, 0)) return rc;
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  psrl_times(a);
-  return CMDP_OK;
+  return psrlc_update_all(a);
 }
 
 int cmdp_psrlc_layout(cmdp_psrlc_t* a, int64_t* n_positions, int64_t* row_ptr, int32_t* col) {
@@ -6053,18 +6058,16 @@ static int psrlc_policy_solve(cmdp_psrlc_t* a, const uint8_t* mask) {
         plain = std::max(plain, map_dvi_value_bytes((int)(s1 - s0)));
       }
       MapDviArgs g{list, a->d_S.p, a->d_A.p, a->d_roff.p, h->d_state_off.p, a->d_row_ptr.p, a->d_col.p, a->d_tp.p, a->d_tprior.p,
-                   a->d_rp.p, 4, a->d_mapt.p, a->d_mapc.p, 0.99f, 1e-3, CMDP_SCHEME_AUTO, a->size_threshold, a->density_threshold,
-                   a->max_sweeps, p.d_Q.p, p.d_V.p, p.d_sweeps.p, p.d_scheme.p, p.d_status.p, 0};
+                   a->d_rp.p, 4, a->d_mapt.p, a->d_mapc.p, PSRLC_GAMMA, PSRLC_EPSILON, CMDP_SCHEME_AUTO, a->size_threshold,
+                   a->density_threshold, a->max_sweeps, p.d_Q.p, p.d_V.p, p.d_sweeps.p, p.d_scheme.p, p.d_status.p, 0};
       return mapdvi_launch(g, count, h->max_S, mapdvi_pick_lds(count, h->cus, staged, plain), st);
     }
     PcMapArgs m{list, a->d_S.p, a->d_A.p, a->d_roff.p, a->d_toff.p, a->d_row_ptr.p, a->d_col.p, a->d_tp.p, a->d_tprior.p, a->d_rp.p,
                 a->d_mrs.p, a->d_Tmap.p, a->d_Rmap.p};
     hipLaunchKernelGGL(k_psrlc_map_fill, dim3(count), dim3(MAPVI_THREADS), 0, st, m);
     HIP_TRY(hipGetLastError());
-    DdvArgs g{list, a->d_S.p, a->d_A.p, a->d_toff.p, a->d_roff.p, h->d_state_off.p, a->d_Tmap.p, a->d_Rmap.p, 0.99f, 1e-3,
-              CMDP_SCHEME_AUTO, a->size_threshold, a->density_threshold, a->max_sweeps, p.d_Q.p, p.d_V.p, p.d_sweeps.p,
-              p.d_scheme.p, p.d_status.p};
-    return ddv_launch(g, count, h->max_S, st);
+    return ddv_launch(psrlc_ddv_args(a, list, a->d_Tmap.p, a->d_Rmap.p, p.d_Q.p, p.d_V.p, p.d_sweeps.p, p.d_scheme.p, p.d_status.p),
+                      count, h->max_S, st);
   });
   return rc ? rc : policy_finish(a, &h->ps_policy_ms, "MAP", (long long)a->max_sweeps);
 }

@@ -154,6 +154,12 @@ __device__ __forceinline__ float wave_max(float v) {
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
   return v;
 }
+// the sum in every lane, by the xor butterfly 32, 16, 8, 4, 2, 1: the fixed order the float64 row sums of the solvers (EVI,
+// the dense and MAP value iterations, the posterior samplers) are defined with
+__device__ __forceinline__ double wave_sum(double x) {
+  for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
+  return x;
+}
 // max over the wave with DPP moves (VALU only: no LDS traffic, no lgkmcnt waits); the result is valid in LANE 63.
 // quad_perm [1,0,3,2], [2,3,0,1], row_ror:4, row_ror:8, row_bcast:15, row_bcast:31; lanes a move does not reach
 // keep their own value (old = src), which is harmless for an idempotent operation.

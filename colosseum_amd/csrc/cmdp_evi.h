@@ -94,11 +94,6 @@ struct EviWalk {
   }
 };
 
-__device__ __forceinline__ double evi_wave_sum(double x) {
-  for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
-  return x;
-}
-
 __global__ void __launch_bounds__(EVI_THREADS) k_evi(EviArgs g) {
   extern __shared__ __align__(16) unsigned char evi_lds[];
   __shared__ double red_d[EVI_THREADS / 64];
@@ -140,7 +135,7 @@ __global__ void __launch_bounds__(EVI_THREADS) k_evi(EviArgs g) {
       rank[(uint32_t)keys[i]] = (uint16_t)i;
       part += (double)u1[i];
     }
-    part = evi_wave_sum(part);
+    part = wave_sum(part);
     if (lane == 0) red_d[wid] = part;
     __syncthreads();
     double sumU = 0.0;

@@ -13,7 +13,7 @@
 // The solver's arithmetic is k_vi_discounted_dense's with the prior's share factored out.  V starts at 0; every float64
 // operation is rounded on its own (no contraction); the two sums over e run in layout order from +0; len = the row's number
 // of layout positions.  SV(X) is the float64 sum of X[0 .. S): 64 partial sums, partial l adding double(X[l]), double(X[l + 64]),
-// ... in ascending order to +0, combined by the xor butterfly 32, 16, 8, 4, 2, 1 (mapvi_wave_sum; K15's order).
+// ... in ascending order to +0, combined by the xor butterfly 32, 16, 8, 4, 2, 1 (wave_sum; K15's order).
 //   Gauss-Seidel  per row, once: gt[e] = fl32(gamma * t[e]), gc = fl32(gamma * c)
 //                 per sweep: SV = SV(V), taken afresh, so nothing drifts from sweep to sweep; then per state s in order
 //                   per action:  sub = sum_e double(V[col e]);  dot = sum_e double(gt[e]) * double(V[col e])
@@ -98,7 +98,7 @@ inline size_t map_dvi_lds_bytes(int S, int A, int64_t nz, size_t stage_max) {
 __device__ __forceinline__ double mapdvi_sv(const float* v, int S, int lane) {
   double sv = 0.0;
   for (int j = lane; j < S; j += 64) sv = __dadd_rn(sv, (double)v[j]);
-  return mapvi_wave_sum(sv);
+  return wave_sum(sv);
 }
 
 // max over the lanes 0 .. min(A, 64) - 1 (the others hold -inf), wave-uniform.  DPP moves: quad_perm [1,0,3,2], [2,3,0,1],
@@ -310,7 +310,7 @@ __global__ void __launch_bounds__(MAPDVI_THREADS) k_vi_discounted_map(MapDviArgs
   long long nnz = 0;
   for (int row = lane; row < rows; row += MAPDVI_THREADS) {
     const int64_t zb = ptr[row], ze = ptr[row + 1];
-    MapViRow r{g.col, g.hp, zb, ze, prior};
+    MapViRow<float> r{g.col, g.hp, zb, ze, prior};
     const float rowsum = mapvi_rowsum(r, n_runs, plan_run, plan_merges);
     const float c = __fdiv_rn(prior, rowsum);
     cmap[row] = c;

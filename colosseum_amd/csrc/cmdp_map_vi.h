@@ -67,36 +67,44 @@ inline size_t map_vi_lds_bytes(int S, int A, int64_t nz) {
   return full <= MAPVI_STAGE_MAX_BYTES ? full : map_vi_value_bytes(S);
 }
 
-// the dense row, read once in ascending column order
+// the rounded add of numpy's pairwise sums, chosen by the element type
+__device__ __forceinline__ float rn_add(float a, float b) { return __fadd_rn(a, b); }
+__device__ __forceinline__ double rn_add(double a, double b) { return __dadd_rn(a, b); }
+
+// the dense row, read once in ascending column order: val[e] at the layout's columns col[e], e in [z, ze), `fill` elsewhere.
+// K15 / K17 and the MAP fill read float32 hyper-parameters over the prior, K18's chain float64 P_minus over 0.
+template <typename T>
 struct MapViRow {
+  typedef T elem;
   const int32_t* col;
-  const float* hp;
+  const T* val;
   int64_t z, ze;
-  float prior;
-  __device__ __forceinline__ float at(int j) {
-    if (z < ze && col[z] == j) return hp[z++];
-    return prior;
+  T fill;
+  __device__ __forceinline__ T at(int j) {
+    if (z < ze && col[z] == j) return val[z++];
+    return fill;
   }
 };
 
-// FLOAT_pairwise_sum on a run of n <= 128 elements starting at column j0
-__device__ __forceinline__ float mapvi_run(MapViRow& r, int j0, int n) {
+// FLOAT_pairwise_sum / DOUBLE_pairwise_sum on a run of n <= 128 elements starting at column j0
+template <typename Row>
+__device__ __forceinline__ typename Row::elem mapvi_run(Row& r, int j0, int n) {
+  typedef typename Row::elem T;
   if (n < 8) {
-    float res = 0.0f;
-    for (int i = 0; i < n; ++i) res = __fadd_rn(res, r.at(j0 + i));
+    T res = 0;
+    for (int i = 0; i < n; ++i) res = rn_add(res, r.at(j0 + i));
     return res;
   }
-  float acc[8];
+  T acc[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) acc[j] = r.at(j0 + j);
   int i = 8;
   for (; i < n - (n % 8); i += 8) {
 #pragma unroll
-    for (int j = 0; j < 8; ++j) acc[j] = __fadd_rn(acc[j], r.at(j0 + i + j));
+    for (int j = 0; j < 8; ++j) acc[j] = rn_add(acc[j], r.at(j0 + i + j));
   }
-  float res = __fadd_rn(__fadd_rn(__fadd_rn(acc[0], acc[1]), __fadd_rn(acc[2], acc[3])),
-                        __fadd_rn(__fadd_rn(acc[4], acc[5]), __fadd_rn(acc[6], acc[7])));
-  for (; i < n; ++i) res = __fadd_rn(res, r.at(j0 + i));
+  T res = rn_add(rn_add(rn_add(acc[0], acc[1]), rn_add(acc[2], acc[3])), rn_add(rn_add(acc[4], acc[5]), rn_add(acc[6], acc[7])));
+  for (; i < n; ++i) res = rn_add(res, r.at(j0 + i));
   return res;
 }
 
@@ -126,32 +134,30 @@ __device__ inline int mapvi_plan(int n, int* work, short* run, signed char* merg
   }
 }
 
-// numpy's pairwise float32 sum of the dense row `r`: one lane replays the plan of mapvi_plan with its partial sums in registers.
-// K15's prologue and the MAP fill of the continuous PSRL agent (cmdp_psrlc.h) share it.
-__device__ __forceinline__ float mapvi_rowsum(MapViRow& r, int n_runs, const short* plan_run, const signed char* plan_merges) {
-  float st[MAPVI_DEPTH + 1];   // the partial sums waiting for their right-hand halves, st[0] the newest
+// numpy's pairwise sum of the dense row `r` in the row's element type: one lane replays the plan of mapvi_plan with its
+// partial sums in registers.  K15's and K17's prologues, the MAP fill of the continuous PSRL agent (cmdp_psrlc.h) and, in
+// float64 over zero fill, the P_minus chain of its optimistic sample (cmdp_psrlo.h) share it.
+template <typename Row>
+__device__ __forceinline__ typename Row::elem mapvi_rowsum(Row& r, int n_runs, const short* plan_run, const signed char* plan_merges) {
+  typedef typename Row::elem T;
+  T st[MAPVI_DEPTH + 1];   // the partial sums waiting for their right-hand halves, st[0] the newest
 #pragma unroll
-  for (int k = 0; k <= MAPVI_DEPTH; ++k) st[k] = 0.0f;
+  for (int k = 0; k <= MAPVI_DEPTH; ++k) st[k] = 0;
   int j0 = 0;
   for (int k = 0; k < n_runs; ++k) {
     const int n = plan_run[k];
-    const float x = mapvi_run(r, j0, n);
+    const T x = mapvi_run(r, j0, n);
     j0 += n;
 #pragma unroll
     for (int d = MAPVI_DEPTH; d > 0; --d) st[d] = st[d - 1];
     st[0] = x;
     for (int m = plan_merges[k]; m > 0; --m) {
-      st[0] = __fadd_rn(st[1], st[0]);
+      st[0] = rn_add(st[1], st[0]);
 #pragma unroll
       for (int d = 1; d < MAPVI_DEPTH; ++d) st[d] = st[d + 1];
     }
   }
   return st[0];
-}
-
-__device__ __forceinline__ double mapvi_wave_sum(double x) {
-  for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
-  return x;
 }
 
 __global__ void __launch_bounds__(MAPVI_THREADS) k_vi_episodic_map(MapViArgs g) {
@@ -193,7 +199,7 @@ __global__ void __launch_bounds__(MAPVI_THREADS) k_vi_episodic_map(MapViArgs g) 
   if (staged && tid == 0) lptr[nrows] = z0 + nz;
   for (int row = tid; row < nrows; row += MAPVI_THREADS) {
     const int64_t zb = ptr[row], ze = ptr[row + 1];
-    MapViRow r{col, hp, zb, ze, prior};
+    MapViRow<float> r{col, hp, zb, ze, prior};
     const float rowsum = mapvi_rowsum(r, n_runs, plan_run, plan_merges);
     const float c = __fdiv_rn(prior, rowsum);
     cmap[row] = c;
@@ -223,7 +229,7 @@ __global__ void __launch_bounds__(MAPVI_THREADS) k_vi_episodic_map(MapViArgs g) 
   for (int h = H - 1; h >= 0; --h) {
     double sv = 0.0;
     for (int j = lane; j < S; j += 64) sv += (double)vn[j];
-    sv = mapvi_wave_sum(sv);
+    sv = wave_sum(sv);
     for (int s = tid; s < S; s += MAPVI_THREADS) {
       float vmax = -INFINITY;
       for (int a = 0; a < A; ++a) {

@@ -15,7 +15,8 @@
 //                         environment's step, the two model updates, and PARKS at the episode's last step;
 //   k_psrl_sample         CMDP_PSRL_SAMPLER_PHILOX: a wavefront per row (s, a) of a parked instance, lanes over columns:
 //                         gamma variates on Philox domain 6, the row sum in float64 rounded once, T = r / (1e-5f + sum)
-//                         written once, coalesced, into the dense workspace; lane 0 draws the row's reward on domain 7;
+//                         written once, coalesced, into the dense workspace (psrl_dirichlet_row, which K18's sample shares
+//                         on domain 8); lane 0 draws the row's reward on domain 7 (psrl_nnig_draw, shared likewise);
 //   k_vi_episodic_dense   workgroup per instance: colosseum/dynamic_programming/finite_horizon.py:11-26 on dense float32 T,
 //                         V[h + 1] in LDS, a wavefront per state walking its actions, each row T[s, a, :] streamed with
 //                         16-byte loads, the dot product accumulated in float64 (exact float32 x float32 products), reduced across the wavefront in a
@@ -134,9 +135,52 @@ __global__ void __launch_bounds__(256) k_psrl_walk(EnvTables t, PsArgs p, int64_
   if (parked) p.call.park_list[atomicAdd(p.call.park_count, 1)] = b;
 }
 
-__device__ __forceinline__ double psrl_wave_sum(double x) {
-  for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
-  return x;
+// The layout position of column j in a row's ascending columns col[rb .. re), or -1: every other element of the dense row holds
+// the prior (or, in the optimistic sample's simple rows, zero).  The one lookup of K12, K13 and K18.
+__device__ __forceinline__ int64_t psrl_layout_find(const int32_t* __restrict__ col, int64_t rb, int64_t re, int j) {
+  int64_t lo = rb, hi = re;
+  while (lo < hi) {
+    const int64_t m = lo + ((hi - lo) >> 1);
+    const int cc = col[m];
+    if (cc == j) return m;
+    if (cc < j) lo = m + 1; else hi = m;
+  }
+  return -1;
+}
+
+// One row of M_DIR's sample by the Philox sampler, a wavefront per row with its lanes over the columns: the gamma variate of
+// column c on Philox domain DOMAIN with n = ep | (base + c), shapes tp at the layout positions [rb, re) over `prior`, cast to
+// float32 and kept in the wave's LDS slice `g`; the row sum in float64 rounded once; dst = r / (1e-5f + sum).
+template <uint32_t DOMAIN>
+__device__ __forceinline__ void psrl_dirichlet_row(const int32_t* __restrict__ col, const float* __restrict__ tp, int64_t rb,
+                                                   int64_t re, float prior, int S, int lane, unsigned long long ep, uint32_t base,
+                                                   uint2 key, float* g, float* __restrict__ dst) {
+  double part = 0.0;
+  for (int c = lane; c < S; c += 64) {
+    const int64_t m = psrl_layout_find(col, rb, re, c);
+    const float shape = m >= 0 ? tp[m] : prior;
+    uint32_t draw = 0;
+    const float v = (float)philox_gamma((double)shape, ep | (base + (uint32_t)c), key, draw, DOMAIN);
+    g[c] = v;
+    part += (double)v;
+  }
+  part = wave_sum(part);
+  const float den = __fadd_rn(1e-5f, (float)part);
+  for (int c = lane; c < S; c += 64) dst[c] = __fdiv_rn(g[c], den);
+}
+
+// N_NIG.sample of one row (conjugate_rewards.py:84-99) by the Philox sampler, domain 7, n = ep | row: tau = gamma(alpha,
+// 1 / beta) as float32 (the scale a float32 quotient), var = 1 / (lambda * tau) and its root in float32, mean = normal(mu,
+// sqrt(var)) rounded to float32
+__device__ __forceinline__ float psrl_nnig_draw(const float* hp, unsigned long long n, uint2 key) {
+  uint32_t draw = 0;
+  const double ga = philox_gamma((double)hp[2], n, key, draw, 7u);
+  const float tau = (float)__dmul_rn((double)__fdiv_rn(1.0f, hp[3]), ga);
+  const float sd = __fsqrt_rn(__fdiv_rn(1.0f, __fmul_rn(hp[1], tau)));
+  uint32_t w[4];
+  philox4x32_10((uint32_t)n, (uint32_t)(n >> 32), 7u, draw, key.x, key.y, w);
+  const double z = sqrt(-2.0 * log(1.0 - u53(w[0], w[1]))) * cos(6.283185307179586476925286766559 * u53(w[2], w[3]));
+  return (float)__dadd_rn((double)hp[0], __dmul_rn((double)sd, z));
 }
 
 // The posterior sample of episode k of the parked instances (Philox sampler; the counter packing is documented in
@@ -158,39 +202,9 @@ __global__ void __launch_bounds__(PSRL_SAMPLE_THREADS) k_psrl_sample(PsArgs p, c
   const float prior = p.tprior[b];
   const uint2 key = p.key[b];
   const unsigned long long ep = (unsigned long long)p.episode[b] << 32;
-  double part = 0.0;
-  for (int c = lane; c < S; c += 64) {
-    float shape = prior;
-    int64_t lo = rb, hi = re;
-    while (lo < hi) {   // the row's layout positions scattered over the prior
-      const int64_t m = lo + ((hi - lo) >> 1);
-      const int cc = p.col[m];
-      if (cc == c) { shape = p.tp[m]; break; }
-      if (cc < c) lo = m + 1; else hi = m;
-    }
-    uint32_t draw = 0;
-    const float v = (float)philox_gamma((double)shape, ep | ((uint32_t)row * (uint32_t)S + (uint32_t)c), key, draw, 6u);
-    g[c] = v;
-    part += (double)v;
-  }
-  part = psrl_wave_sum(part);
-  const float den = __fadd_rn(1e-5f, (float)part);
-  float* T = p.T + p.t_off[b] + (int64_t)row * S;
-  for (int c = lane; c < S; c += 64) T[c] = __fdiv_rn(g[c], den);
-  if (lane == 0) {
-    // N_NIG.sample (conjugate_rewards.py:84-99): tau = gamma(alpha, 1 / beta) as float32 (the scale a float32 quotient),
-    // var = 1 / (lambda * tau) and its root in float32, mean = normal(mu, sqrt(var)) rounded to float32
-    const float* hp = p.rp + r * 4;
-    uint32_t draw = 0;
-    const unsigned long long n = ep | (uint32_t)row;
-    const double ga = philox_gamma((double)hp[2], n, key, draw, 7u);
-    const float tau = (float)__dmul_rn((double)__fdiv_rn(1.0f, hp[3]), ga);
-    const float sd = __fsqrt_rn(__fdiv_rn(1.0f, __fmul_rn(hp[1], tau)));
-    uint32_t w[4];
-    philox4x32_10((uint32_t)n, (uint32_t)(n >> 32), 7u, draw, key.x, key.y, w);
-    const double z = sqrt(-2.0 * log(1.0 - u53(w[0], w[1]))) * cos(6.283185307179586476925286766559 * u53(w[2], w[3]));
-    p.Rs[r] = (float)__dadd_rn((double)hp[0], __dmul_rn((double)sd, z));
-  }
+  psrl_dirichlet_row<6u>(p.col, p.tp, rb, re, prior, S, lane, ep, (uint32_t)row * (uint32_t)S, key, g,
+                         p.T + p.t_off[b] + (int64_t)row * S);
+  if (lane == 0) p.Rs[r] = psrl_nnig_draw(p.rp + r * 4, ep | (uint32_t)row, key);
 }
 
 struct DviArgs {
@@ -247,7 +261,7 @@ __global__ void __launch_bounds__(PSRL_VI_THREADS) k_vi_episodic_dense(DviArgs g
         } else {
           for (int c = lane; c < S; c += 64) acc += (double)tr[c] * (double)vn[c];
         }
-        acc = psrl_wave_sum(acc);
+        acc = wave_sum(acc);
         const float q = (float)__dadd_rn((double)R[row], acc);
         if (lane == 0) Q[(int64_t)h * nrows + row] = q;
         vmax = fmaxf(vmax, q);

@@ -35,6 +35,9 @@
 //                           n_sa [R] is N[s, a].sum() and is never cleared.  nu [R] carries the episode it was last written in
 //                           (stamp [R]) and counts as 0 when that is not the instance's current `episode`: an
 //                           episode_end_update, internal or external, resets every nu_k at the cost of one increment.
+//                           One template for the whole family, <GATE, OPT>: GATE compiles min_steps_before_new_episode in
+//                           (PcGate), OPT is the optimistic agent's walk (K18: PoArgs).  <false, false> is the walk described
+//                           here; the host picks the instantiation (cmdp_psrlc_run).
 //   k_vi_discounted_dense   workgroup per listed instance, V (and V_old) in LDS; the arithmetic is defined below.
 //
 // The solver's arithmetic, one definition for the agent and for cmdp_vi_discounted_dense.  A ROW SUM over the columns j of
@@ -77,8 +80,38 @@ struct PcGate {
   int32_t* last_change;   // [B] starts at 0
 };
 
-template <bool GATE>
-__global__ void __launch_bounds__(256) k_psrlc_walk(EnvTables t, PsArgs p, PcCounters c, PcGate gt, int64_t n_steps,
+// The device arguments of the optimistic agent (K18, cmdp_psrlo.h), defined here because the walk takes them.  Of these the
+// walk (OPT = true) reads psi, q_off, N and Qx: its Q has A * psi_b values per state at per-instance offsets, the action played
+// is j / psi_b, and the agent's N is counted at the layout's positions.  The plain walk (OPT = false) reads no member; the
+// host passes it empty.  The struct is passed whole, not as a view of the four: the kernel-argument layout is part of what the
+// register allocator sees, and this one gives every instantiation the counts recorded in DESIGN.md.
+struct PoArgs {
+  const int32_t* psi;       // [B]
+  const double* eta;        // [B]
+  const double* log4s;      // [B] numpy's log(4 * S)
+  const int64_t* q_off;     // [B] first extended row: R_ext, Q [S][A * psi], bump [psi][S * A]
+  const int64_t* tx_off;    // [B] first element of T_ext (a multiple of 4); also of the compact posterior rows
+  const int64_t* k_off;     // [B] first of the instance's psi values of z
+  const int64_t* pm_off;    // [B] first of the instance's psi * nz_b values of pmk
+  int32_t* N;               // [NZ] the agent's N at the layout's positions
+  double* pm;               // [NZ] P_minus of the chain
+  float* pmk;               // per k the float32 layout values of the simple rows
+  float* bump;              // per (k, row) the float32 value at z_k
+  int32_t* z;               // [sum psi]
+  uint8_t* simple;          // [R]
+  const int32_t* pidx;      // [R] index of a posterior row among the instance's posterior rows (reference sampler)
+  const int32_t* n1;        // [B] posterior rows of the last draw
+  const float* post;        // at tx_off[b]: [psi][n1][S] posterior rows as the host drew them; null: the Philox sampler
+  float* Tx;
+  float* Rx;                // [sum S * A * psi]
+  float* Qx;                // the actor's table
+  float* const* pk;         // [B] null: the dense route.  The compact route: the instance's posterior rows [psi][n1][S]; Tx unread
+  int pk_from_host;         // compact route: 1 the host has drawn and uploaded the posterior rows (reference sampler; `post`
+                            // unread), 0 the kernel draws them (Philox sampler)
+};
+
+template <bool GATE, bool OPT>
+__global__ void __launch_bounds__(256) k_psrlc_walk(EnvTables t, PsArgs p, PcCounters c, PoArgs o, PcGate gt, int64_t n_steps,
                                                     const uint8_t* __restrict__ train_mask, int8_t* __restrict__ act_trace,
                                                     int32_t* __restrict__ obs_trace, double* __restrict__ rew_trace,
                                                     double* __restrict__ cum_reward) {
@@ -88,10 +121,14 @@ __global__ void __launch_bounds__(256) k_psrlc_walk(EnvTables t, PsArgs p, PcCou
   if (left == 0) return;
   const int64_t soff = t.state_off[b], ebase = t.entry_base[b];
   const int A = t.A;
+  int psi = 1;
+  if constexpr (OPT) psi = o.psi[b];
+  const int AX = A * psi;   // Q values per state
   const uint2 key = t.philox_key ? t.philox_key[b] : make_uint2(0, 0);
   int32_t cur = t.cur[b], h = t.hstep[b];
   unsigned long long nt = t.n_trans[b];
   const float* Q = p.Q + soff * A;
+  if constexpr (OPT) Q = o.Qx + o.q_off[b];
   float* RP = p.rp + soff * A * 4;
   uint32_t* mt = p.mt + (int64_t)b * 624;
   int32_t* mtp = p.mt_pos + b;
@@ -104,7 +141,8 @@ __global__ void __launch_bounds__(256) k_psrlc_walk(EnvTables t, PsArgs p, PcCou
   while (left > 0) {
     const int64_t step = n_steps - left;
     const int32_t h0 = h;
-    int action = greedy_action_row(Q + (int64_t)cur * A, A, mt, mtp);
+    int action = greedy_action_row(Q + (int64_t)cur * AX, AX, mt, mtp);
+    if constexpr (OPT) action /= psi;   // extended_action_to_real
     const int32_t idx = cur * A + action;
     const unsigned long long n0 = nt;
     int32_t obs;
@@ -120,8 +158,10 @@ __global__ void __launch_bounds__(256) k_psrlc_walk(EnvTables t, PsArgs p, PcCou
     --left;
     if (train) {
       psrl_nnig_update(RP + (int64_t)idx * 4, reward);
-      float* tc = p.tp + p.slot[e];   // M_DIR.update_sa: every step
+      const int32_t pos = p.slot[e];
+      float* tc = p.tp + pos;   // M_DIR.update_sa: every step
       *tc = __fadd_rn(*tc, 1.0f);
+      if constexpr (OPT) o.N[pos] += 1;
       const int64_t r = soff * A + idx;
       const int32_t n_tau = c.n_sa[r] + 1;
       const int32_t nu_k = (c.stamp[r] == ep ? c.nu[r] : 0) + 1;
@@ -246,7 +286,7 @@ __device__ __forceinline__ double ddv_dot(const DdvRow& d, const float* __restri
     }
     for (int c = lane + DDV_PF * 64; c < S; c += 64) acc += ddv_term<GS>(tr[c], v[c], gamma);
   }
-  return psrl_wave_sum(acc);
+  return wave_sum(acc);
 }
 
 template <int WAVES>
@@ -414,7 +454,7 @@ __global__ void __launch_bounds__(MAPVI_THREADS) k_psrlc_map_fill(PcMapArgs g) {
   __syncthreads();
   const int n_runs = plan_n;
   for (int row = tid; row < nrows; row += MAPVI_THREADS) {
-    MapViRow r{g.col, g.hp, ptr[row], ptr[row + 1], prior};
+    MapViRow<float> r{g.col, g.hp, ptr[row], ptr[row + 1], prior};
     g.rowsum[r0 + row] = mapvi_rowsum(r, n_runs, plan_run, plan_merges);
     g.Rm[r0 + row] = g.rp[(r0 + row) * 4];
   }
@@ -424,15 +464,8 @@ __global__ void __launch_bounds__(MAPVI_THREADS) k_psrlc_map_fill(PcMapArgs g) {
     const float c = __fdiv_rn(prior, rs);
     const int64_t rb = ptr[row], re = ptr[row + 1];
     for (int j = lane; j < S; j += 64) {
-      float v = c;
-      int64_t lo = rb, hi = re;
-      while (lo < hi) {   // the row's layout positions scattered over the prior
-        const int64_t m = lo + ((hi - lo) >> 1);
-        const int cc = g.col[m];
-        if (cc == j) { v = __fdiv_rn(g.hp[m], rs); break; }
-        if (cc < j) lo = m + 1; else hi = m;
-      }
-      T[(int64_t)row * S + j] = v;
+      const int64_t m = psrl_layout_find(g.col, rb, re, j);   // the row's layout positions scattered over the prior
+      T[(int64_t)row * S + j] = m >= 0 ? __fdiv_rn(g.hp[m], rs) : c;
     }
   }
 }

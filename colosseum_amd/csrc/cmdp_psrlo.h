@@ -29,14 +29,16 @@
 //     int32 at the layout's positions (the float32 hyper-parameters cannot give it back).
 //
 // Kernels:
-//   k_psrlo_walk    K13's walk on A * psi_b Q values per state (per-instance offsets), plays and traces j / psi_b, counts N.
+//   k_psrlc_walk<GATE, true>  (cmdp_psrlc.h) K13's walk on A * psi_b Q values per state (per-instance offsets): it plays and
+//     traces j / psi_b and counts N.  It reads psi, Qx, q_off and N of PoArgs and nothing else of it.
 //   k_psrlo_sample  one workgroup per listed instance, fills T_ext [S, A * psi, S] and R_ext [S, A * psi].
 //     Phase 1, a lane per row: the flag (double)n_sa < eta, P_minus at the row's layout positions, then the serial chain over k.
-//       A non-zero of the dense row sits at a layout position or at z_k, so the pairwise sum is mapvi_rowsum's tree (cmdp_map_vi.h)
-//       in float64 with zero fill.  A z_k outside the layout holds 0 + summing and returns to 0 - exactly.  Per k the lane
-//       leaves float32(P_minus) of its layout positions (`pmk`) and the float32 value at z_k (`bump`).
+//       A non-zero of the dense row sits at a layout position or at z_k, so the pairwise sum is mapvi_rowsum itself
+//       (cmdp_map_vi.h) on a float64 row with zero fill.  A z_k outside the layout holds 0 + summing and returns to 0 - exactly.
+//       Per k the lane leaves float32(P_minus) of its layout positions (`pmk`) and the float32 value at z_k (`bump`).
 //     Phase 2, a wavefront per (row, k): the row of T_ext written once, coalesced (16-byte stores where S % 4 == 0): zeros,
-//       the layout positions and z_k for a simple row; the host's compact upload for a posterior row.
+//       the layout positions and z_k for a simple row (psrlo_write_simple); the host's compact upload for a posterior row
+//       (psrlo_write_posterior).  k_psrlo_expand (cmdp_psrlo_vi.h) writes its rows with the same two functions.
 // The COMPACT route (K19, cmdp_psrlo_vi.h; PoArgs::pk set) stops after Phase 1 for the simple rows: the compact sample of an
 //   instance is simple [R], z [psi], pmk [psi][nz_b] and bump [psi][S * A] exactly as Phase 1 leaves them (sample-major, the
 //   arrangement Phase 2 reads) and, for the n1_b posterior rows of THIS draw, the packed block pk[b] = [psi][n1_b][S]
@@ -49,37 +51,14 @@
 // CMDP_PSRL_SAMPLER_PHILOX (`post` null): everything is drawn in the kernel, a pure function of (seed, episode, tables):
 //   z_k = (w0 * S) >> 32 of the block (n = episode << 32 | k, domain 9);  the gamma variate of element c of extended row
 //   j = row * psi + k on domain 8 with n = episode << 32 | (j * S + c) (S * A * psi * S < 2^32 is checked at creation), the
-//   row then as k_psrl_sample's: float64 sum rounded once, T = r / (1e-5f + sum);  the reward of a row as k_psrl_sample draws
-//   it (domain 7).  A wavefront keeps its row's variates in its LDS slice (dynamic LDS: 4 * s_max floats).
+//   row by k_psrl_sample's own psrl_dirichlet_row: float64 sum rounded once, T = r / (1e-5f + sum);  the reward of a row by
+//   psrl_nnig_draw (domain 7).  A wavefront keeps its row's variates in its LDS slice (dynamic LDS: 4 * s_max floats).
 #pragma once
 #include "cmdp_psrlc.h"
 
 #define PSRLO_THREADS 256
 
-struct PoArgs {
-  const int32_t* psi;       // [B]
-  const double* eta;        // [B]
-  const double* log4s;      // [B] numpy's log(4 * S)
-  const int64_t* q_off;     // [B] first extended row: R_ext, Q [S][A * psi], bump [psi][S * A]
-  const int64_t* tx_off;    // [B] first element of T_ext (a multiple of 4); also of the compact posterior rows
-  const int64_t* k_off;     // [B] first of the instance's psi values of z
-  const int64_t* pm_off;    // [B] first of the instance's psi * nz_b values of pmk
-  int32_t* N;               // [NZ] the agent's N at the layout's positions
-  double* pm;               // [NZ] P_minus of the chain
-  float* pmk;               // per k the float32 layout values of the simple rows
-  float* bump;              // per (k, row) the float32 value at z_k
-  int32_t* z;               // [sum psi]
-  uint8_t* simple;          // [R]
-  const int32_t* pidx;      // [R] index of a posterior row among the instance's posterior rows (reference sampler)
-  const int32_t* n1;        // [B] posterior rows of the last draw
-  const float* post;        // at tx_off[b]: [psi][n1][S] posterior rows as the host drew them; null: the Philox sampler
-  float* Tx;
-  float* Rx;                // [sum S * A * psi]
-  float* Qx;                // the actor's table
-  float* const* pk;         // [B] null: the dense route.  The compact route: the instance's posterior rows [psi][n1][S]; Tx unread
-  int pk_from_host;         // compact route: 1 the host has drawn and uploaded the posterior rows (reference sampler; `post`
-                            // unread), 0 the kernel draws them (Philox sampler)
-};
+// PoArgs, the optimistic agent's device arguments, is defined in cmdp_psrlc.h: the shared walk takes it.
 
 // The compact route's numbering of the posterior rows of the listed instances, a wavefront per instance: pidx[row] = index of
 // a posterior row among the instance's posterior rows (-1 for a simple one), n1[b] their number.  The flag is Phase 1's.
@@ -102,146 +81,31 @@ __global__ void __launch_bounds__(64) k_psrlo_count(PcCounters c, const double* 
   if (lane == 0) n1[b] = run;
 }
 
-template <bool GATE>   // cmdp_psrlc.h: PcGate
-__global__ void __launch_bounds__(256) k_psrlo_walk(EnvTables t, PsArgs p, PcCounters c, PoArgs o, PcGate gt, int64_t n_steps,
-                                                    const uint8_t* __restrict__ train_mask, int8_t* __restrict__ act_trace,
-                                                    int32_t* __restrict__ obs_trace, double* __restrict__ rew_trace,
-                                                    double* __restrict__ cum_reward) {
-  const int b = blockIdx.x * blockDim.x + threadIdx.x;
-  if (b >= t.B) return;
-  long long left = p.call.left[b];
-  if (left == 0) return;
-  const int64_t soff = t.state_off[b], ebase = t.entry_base[b];
-  const int A = t.A, psi = o.psi[b], AX = A * psi;
-  const uint2 key = t.philox_key ? t.philox_key[b] : make_uint2(0, 0);
-  int32_t cur = t.cur[b], h = t.hstep[b];
-  unsigned long long nt = t.n_trans[b];
-  const float* Q = o.Qx + o.q_off[b];
-  float* RP = p.rp + soff * A * 4;
-  uint32_t* mt = p.mt + (int64_t)b * 624;
-  int32_t* mtp = p.mt_pos + b;
-  const int32_t ep = (int32_t)p.episode[b];
-  const bool train = train_mask ? train_mask[b] != 0 : true;
-  int32_t lc = 0;
-  if (GATE && train) lc = gt.last_change[b];
-  double sum = cum_reward[b];
-  bool parked = false;
-  while (left > 0) {
-    const int64_t step = n_steps - left;
-    const int32_t h0 = h;
-    int action = greedy_action_row(Q + (int64_t)cur * AX, AX, mt, mtp) / psi;   // extended_action_to_real
-    const int32_t idx = cur * A + action;
-    const unsigned long long n0 = nt;
-    int32_t obs;
-    double rraw;
-    int64_t e;
-    env_transition(t, soff, ebase, key, cur, h, nt, action, obs, rraw, e);
-    if (t.sp_rkind && t.sp_rkind[e] == 1) rraw = philox_beta(t.sp_rp0[e], t.sp_rp1[e], n0, key, t.beta_gammas);
-    const double reward = rraw * t.rscale - t.rmin;
-    sum += reward;
-    if (act_trace) act_trace[step * t.B + b] = (int8_t)action;
-    if (obs_trace) obs_trace[step * t.B + b] = obs;
-    if (rew_trace) rew_trace[step * t.B + b] = reward;
-    --left;
-    if (train) {
-      psrl_nnig_update(RP + (int64_t)idx * 4, reward);
-      const int32_t pos = p.slot[e];
-      float* tc = p.tp + pos;
-      *tc = __fadd_rn(*tc, 1.0f);
-      o.N[pos] += 1;
-      const int64_t r = soff * A + idx;
-      const int32_t n_tau = c.n_sa[r] + 1;
-      const int32_t nu_k = (c.stamp[r] == ep ? c.nu[r] : 0) + 1;
-      c.n_sa[r] = n_tau;
-      c.nu[r] = nu_k;
-      c.stamp[r] = ep;
-      bool checked = true;
-      if (GATE) {
-        checked = h0 - lc >= gt.min_steps;
-        if (checked) lc = h0;
-      }
-      if (checked && n_tau >= 2 * (n_tau - nu_k)) {
-        parked = true;
-        break;
-      }
-    }
+// Extended row (row, k) of a SIMPLE row, written by one wavefront: zeros, the float32 layout values `vk` of sample k at the
+// columns of [rb, re), and `bump` at z_k, where it wins over a layout value.  `vec`: 16-byte stores (S % 4 == 0, dst aligned).
+__device__ __forceinline__ void psrlo_write_simple(float* __restrict__ dst, const int32_t* __restrict__ col,
+                                                   const float* __restrict__ vk, int64_t rb, int64_t re, int zk, float bump, int S,
+                                                   int lane, bool vec) {
+  auto at = [&](int j) {
+    if (j == zk) return bump;
+    const int64_t m = psrl_layout_find(col, rb, re, j);
+    return m >= 0 ? vk[m] : 0.0f;
+  };
+  if (vec) {
+    for (int j = lane * 4; j < S; j += 256) *reinterpret_cast<float4*>(dst + j) = make_float4(at(j), at(j + 1), at(j + 2), at(j + 3));
+  } else {
+    for (int j = lane; j < S; j += 64) dst[j] = at(j);
   }
-  t.cur[b] = cur;
-  t.hstep[b] = h;
-  t.n_trans[b] = nt;
-  cum_reward[b] = sum;
-  p.call.left[b] = left;
-  if (GATE && train) gt.last_change[b] = lc;
-  if (parked) p.call.park_list[atomicAdd(p.call.park_count, 1)] = b;
 }
 
-// the dense float64 row of the chain, read once in ascending column order: the layout's values, 0 elsewhere (a z outside
-// the layout is 0 whenever the row is summed)
-struct PoRow {
-  const int32_t* col;
-  const double* pm;
-  int64_t z, ze;
-  __device__ __forceinline__ double at(int j) {
-    if (z < ze && col[z] == j) return pm[z++];
-    return 0.0;
+// ... and of a POSTERIOR row: the dense row `src` as it was drawn, copied
+__device__ __forceinline__ void psrlo_write_posterior(float* __restrict__ dst, const float* __restrict__ src, int S, int lane,
+                                                      bool vec) {
+  if (vec) {
+    for (int j = lane * 4; j < S; j += 256) *reinterpret_cast<float4*>(dst + j) = *reinterpret_cast<const float4*>(src + j);
+  } else {
+    for (int j = lane; j < S; j += 64) dst[j] = src[j];
   }
-};
-
-// DOUBLE_pairwise_sum on a run of n <= 128 elements starting at column j0 (mapvi_run in float64)
-__device__ __forceinline__ double psrlo_run(PoRow& r, int j0, int n) {
-  if (n < 8) {
-    double res = 0.0;
-    for (int i = 0; i < n; ++i) res = __dadd_rn(res, r.at(j0 + i));
-    return res;
-  }
-  double acc[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) acc[j] = r.at(j0 + j);
-  int i = 8;
-  for (; i < n - (n % 8); i += 8) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) acc[j] = __dadd_rn(acc[j], r.at(j0 + i + j));
-  }
-  double res = __dadd_rn(__dadd_rn(__dadd_rn(acc[0], acc[1]), __dadd_rn(acc[2], acc[3])),
-                         __dadd_rn(__dadd_rn(acc[4], acc[5]), __dadd_rn(acc[6], acc[7])));
-  for (; i < n; ++i) res = __dadd_rn(res, r.at(j0 + i));
-  return res;
-}
-
-// numpy's pairwise float64 sum of the dense row: mapvi_rowsum's replay of mapvi_plan's list
-__device__ __forceinline__ double psrlo_rowsum(PoRow& r, int n_runs, const short* plan_run, const signed char* plan_merges) {
-  double st[MAPVI_DEPTH + 1];
-#pragma unroll
-  for (int k = 0; k <= MAPVI_DEPTH; ++k) st[k] = 0.0;
-  int j0 = 0;
-  for (int k = 0; k < n_runs; ++k) {
-    const int n = plan_run[k];
-    const double x = psrlo_run(r, j0, n);
-    j0 += n;
-#pragma unroll
-    for (int d = MAPVI_DEPTH; d > 0; --d) st[d] = st[d - 1];
-    st[0] = x;
-    for (int m = plan_merges[k]; m > 0; --m) {
-      st[0] = __dadd_rn(st[1], st[0]);
-#pragma unroll
-      for (int d = 1; d < MAPVI_DEPTH; ++d) st[d] = st[d + 1];
-    }
-  }
-  return st[0];
-}
-
-// element j of the simple row (ptr range [rb, re)) at sample k: the layout's value, the value at z, or 0
-__device__ __forceinline__ float psrlo_simple_at(const int32_t* __restrict__ col, const float* __restrict__ pmk, int64_t rb,
-                                                 int64_t re, int j, int zk, float bump) {
-  if (j == zk) return bump;
-  int64_t lo = rb, hi = re;
-  while (lo < hi) {
-    const int64_t m = lo + ((hi - lo) >> 1);
-    const int cc = col[m];
-    if (cc == j) return pmk[m];
-    if (cc < j) lo = m + 1; else hi = m;
-  }
-  return 0.0f;
 }
 
 __global__ void __launch_bounds__(PSRLO_THREADS) k_psrlo_sample(PsArgs p, PcCounters c, PoArgs o, const int32_t* __restrict__ list,
@@ -272,18 +136,8 @@ __global__ void __launch_bounds__(PSRLO_THREADS) k_psrlo_sample(PsArgs p, PcCoun
       philox4x32_10((uint32_t)k, (uint32_t)(ep >> 32), 9u, 0u, key.x, key.y, w);
       z[k] = (int32_t)(((unsigned long long)w[0] * (unsigned long long)S) >> 32);
     }
-    for (int row = tid; row < rows; row += PSRLO_THREADS) {   // N_NIG.sample as k_psrl_sample's lane 0 draws it
-      const float* hp = p.rp + (r0 + row) * 4;
-      uint32_t draw = 0;
-      const unsigned long long n = ep | (uint32_t)row;
-      const double ga = philox_gamma((double)hp[2], n, key, draw, 7u);
-      const float tau = (float)__dmul_rn((double)__fdiv_rn(1.0f, hp[3]), ga);
-      const float sd = __fsqrt_rn(__fdiv_rn(1.0f, __fmul_rn(hp[1], tau)));
-      uint32_t w[4];
-      philox4x32_10((uint32_t)n, (uint32_t)(n >> 32), 7u, draw, key.x, key.y, w);
-      const double g = sqrt(-2.0 * log(1.0 - u53(w[0], w[1]))) * cos(6.283185307179586476925286766559 * u53(w[2], w[3]));
-      p.Rs[r0 + row] = (float)__dadd_rn((double)hp[0], __dmul_rn((double)sd, g));
-    }
+    for (int row = tid; row < rows; row += PSRLO_THREADS)
+      p.Rs[r0 + row] = psrl_nnig_draw(p.rp + (r0 + row) * 4, ep | (uint32_t)row, key);
   }
   __syncthreads();   // the plan, and with the Philox sampler the workgroup's z and rewards
   const int n_runs = plan_n;
@@ -304,8 +158,8 @@ __global__ void __launch_bounds__(PSRLO_THREADS) k_psrlo_sample(PsArgs p, PcCoun
     }
     for (int k = 0; k < psi; ++k) {
       const int zk = z[k];
-      PoRow r{p.col, o.pm, rb, re};
-      const double summing = __dsub_rn(1.0, __dadd_rn(0.0, psrlo_rowsum(r, n_runs, plan_run, plan_merges)));
+      MapViRow<double> r{p.col, o.pm, rb, re, 0.0};   // a z outside the layout is 0 whenever the row is summed
+      const double summing = __dsub_rn(1.0, __dadd_rn(0.0, mapvi_rowsum(r, n_runs, plan_run, plan_merges)));
       int64_t ez = -1;
       for (int64_t e = rb; e < re; ++e)
         if (p.col[e] == zk) ez = e;
@@ -339,49 +193,12 @@ __global__ void __launch_bounds__(PSRLO_THREADS) k_psrlo_sample(PsArgs p, PcCoun
     if (compact && is_simple) continue;
     float* __restrict__ dst = compact ? T + ((int64_t)k * n1 + o.pidx[r0 + row]) * S : T + (int64_t)item * S;
     if (is_simple) {
-      const int64_t rb = ptr[row], re = ptr[row + 1];
-      const float* __restrict__ vk = pmk + (int64_t)k * nzb - nz0;
-      const int zk = z[k];
-      const float bv = bump[(int64_t)k * rows + row];
-      if (vec) {
-        for (int j = lane * 4; j < S; j += 256) {
-          float4 v;
-          v.x = psrlo_simple_at(p.col, vk, rb, re, j, zk, bv);
-          v.y = psrlo_simple_at(p.col, vk, rb, re, j + 1, zk, bv);
-          v.z = psrlo_simple_at(p.col, vk, rb, re, j + 2, zk, bv);
-          v.w = psrlo_simple_at(p.col, vk, rb, re, j + 3, zk, bv);
-          *reinterpret_cast<float4*>(dst + j) = v;
-        }
-      } else {
-        for (int j = lane; j < S; j += 64) dst[j] = psrlo_simple_at(p.col, vk, rb, re, j, zk, bv);
-      }
+      psrlo_write_simple(dst, p.col, pmk + (int64_t)k * nzb - nz0, ptr[row], ptr[row + 1], z[k], bump[(int64_t)k * rows + row], S,
+                         lane, vec);
     } else if (philox) {
-      const int64_t rb = ptr[row], re = ptr[row + 1];
-      double part = 0.0;
-      for (int c = lane; c < S; c += 64) {
-        float shape = prior;
-        int64_t lo = rb, hi = re;
-        while (lo < hi) {   // the row's layout positions scattered over the prior
-          const int64_t m = lo + ((hi - lo) >> 1);
-          const int cc = p.col[m];
-          if (cc == c) { shape = p.tp[m]; break; }
-          if (cc < c) lo = m + 1; else hi = m;
-        }
-        uint32_t draw = 0;
-        const float v = (float)philox_gamma((double)shape, ep | ((uint32_t)item * (uint32_t)S + (uint32_t)c), key, draw, 8u);
-        g[c] = v;
-        part += (double)v;
-      }
-      part = psrl_wave_sum(part);
-      const float den = __fadd_rn(1e-5f, (float)part);
-      for (int c = lane; c < S; c += 64) dst[c] = __fdiv_rn(g[c], den);
+      psrl_dirichlet_row<8u>(p.col, p.tp, ptr[row], ptr[row + 1], prior, S, lane, ep, (uint32_t)item * (uint32_t)S, key, g, dst);
     } else {
-      const float* __restrict__ src = post + ((int64_t)k * n1 + o.pidx[r0 + row]) * S;
-      if (vec) {
-        for (int j = lane * 4; j < S; j += 256) *reinterpret_cast<float4*>(dst + j) = *reinterpret_cast<const float4*>(src + j);
-      } else {
-        for (int j = lane; j < S; j += 64) dst[j] = src[j];
-      }
+      psrlo_write_posterior(dst, post + ((int64_t)k * n1 + o.pidx[r0 + row]) * S, S, lane, vec);
     }
   }
 }

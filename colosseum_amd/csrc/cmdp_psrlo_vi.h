@@ -405,14 +405,10 @@ __global__ void __launch_bounds__(256) k_psrlo_expand(PoxArgs g) {
     const int row = (int)(item / g.psi), k = (int)(item % g.psi);
     float* __restrict__ dst = g.T + item * g.S;
     if (g.simple[row]) {
-      const int64_t rb = g.ptr[row], re = g.ptr[row + 1];
-      const float* __restrict__ vk = g.pmk + (int64_t)k * nz - nz0;
-      const int zk = g.z[k];
-      const float bv = g.bump[(int64_t)k * rows + row];
-      for (int j = lane; j < g.S; j += 64) dst[j] = psrlo_simple_at(g.col, vk, rb, re, j, zk, bv);
+      psrlo_write_simple(dst, g.col, g.pmk + (int64_t)k * nz - nz0, g.ptr[row], g.ptr[row + 1], g.z[k],
+                         g.bump[(int64_t)k * rows + row], g.S, lane, false);
     } else {
-      const float* __restrict__ src = g.post + ((int64_t)k * g.n1 + g.pidx[row]) * g.S;
-      for (int j = lane; j < g.S; j += 64) dst[j] = src[j];
+      psrlo_write_posterior(dst, g.post + ((int64_t)k * g.n1 + g.pidx[row]) * g.S, g.S, lane, false);
     }
   }
 }

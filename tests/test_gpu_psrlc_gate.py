@@ -1,4 +1,4 @@
-"""min_steps_before_new_episode on the device (the gate of k_psrlc_walk / k_psrlo_walk, CMDP_PSRLC_OPT_MIN_STEPS): the steps at
+"""min_steps_before_new_episode on the device (the gate of k_psrlc_walk<GATE, OPT>, CMDP_PSRLC_OPT_MIN_STEPS): the steps at
 which an instance's `episode` advances are those of the gated rule of tests/helpers_psrlc_gate.py -- which
 tests/test_psrlc_gate.py holds against the reference's own runs (golden G24) -- fed the device's transitions, and
 `last_change` is the rule's; the reference's `ended` flags themselves where the device can follow the reference's trajectory;

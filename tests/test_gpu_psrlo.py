@@ -1,5 +1,5 @@
 """The device PSRL agent for the continuous setting with OPTIMISTIC sampling (K18,
-colosseum_amd.agents.BatchedPSRLContinuousOptimistic: k_psrlo_walk, k_psrlo_sample, K13's solver on the extended arrays) against
+colosseum_amd.agents.BatchedPSRLContinuousOptimistic: k_psrlc_walk<GATE, true>, k_psrlo_sample, K13's solver on the extended arrays) against
 the NumPy twin of tests/helpers_psrlo.py, which tests/test_psrlo.py holds against the reference (golden G23) on the CPU.
 
 As in test_gpu_psrlc.py the twin is fed the DEVICE's transitions, artificial episode by artificial episode, and after every
@@ -339,5 +339,35 @@ def test_chain_on_nonzero_p_minus_with_sixteen_byte_rows(need_gpu):
     assert agent.psi.tolist() == [6] and agent.eta.tolist() == [80.0]
     f.follow(400, chunk=64)
     print(f"{f.nonzero_p_minus} simple rows with non-zero P_minus in {int(f.n_solves[0])} samples, calls {sorted(f.kinds)}")
+    assert f.nonzero_p_minus > 0
+    env.close()
+
+
+# (size, seed, steps): seed and step count chosen with PSRLOTwin on the CPU over seeds 0..19 at max_psi = 3 -- `steps` is the step
+# of the first episode_end_update whose sample has a non-zero P_minus (its tenth sample in both runs: pair (0, a) visited 64
+# times by then), so the followed run ends with that sample.  The device's run reaches it at the same step.
+SPLIT_PLAN_RUNS = [(144, 17, 66), (264, 13, 66)]
+
+
+@pytest.mark.parametrize("size,seed,steps", SPLIT_PLAN_RUNS, ids=[f"S{c[0]}" for c in SPLIT_PLAN_RUNS])
+def test_chain_on_nonzero_p_minus_where_the_pairwise_sum_splits(need_gpu, size, seed, steps):
+    """The float64 pairwise sum of the chain beyond one run of its plan (mapvi_plan first splits at S = 129): S = 144 is two runs
+    (72 + 72) and one merge; S = 264 splits into 128 + 136 and the right half into 64 + 72, three runs with two partial sums
+    waiting on the stack.  eta stays at its default 10 S, so every row is simple for the whole run; max_psi = 3 keeps a sample
+    at six extended actions.  A row of zeros sums right by accident, so what makes the test mean something is P_minus > 0 in a
+    summed row: P_hat > sqrt(3 L P_hat / N) + 3 L / N with L = log 4S, which for a successor that is certain (P_hat = 1) is
+    1 > sqrt(3 L / N) + 3 L / N: N >= 50 visits of the pair at S = 144 (L = 6.356) and N >= 55 at S = 264 (L = 6.962), a few more
+    for a successor that merely dominates (52 and 57 at P_hat = 0.97).  The seeds are those for which the twin's
+    RiverSwim agent gets a pair there soonest, and `steps` ends the run at the episode_end_update that first samples it.  The
+    float64 restatement of the solve is a Python loop over the states per sweep and not what this test is about: it is held
+    for the first three solves only."""
+    models = [make_model("RiverSwimContinuous", seed=seed, size=size)]
+    env = make_env(models, "mt", False)
+    agent = BatchedPSRLContinuousOptimistic(env, [seed], HORIZON, max_psi=3)
+    assert env.n_states.tolist() == [size] and agent.psi.tolist() == [3] and agent.eta.tolist() == [10.0 * size]
+    f = OFollower(env, agent, [seed], q64_every=10 ** 6)
+    f.follow(steps, chunk=64)
+    print(f"S = {size}: {f.nonzero_p_minus} simple rows with non-zero P_minus in {int(f.n_solves[0])} samples, calls {sorted(f.kinds)}")
+    assert f.kinds == {"all_simple"}
     assert f.nonzero_p_minus > 0
     env.close()
